@@ -3,12 +3,17 @@
 step = speech noise -> forward_loss -> cleargrads -> backward -> [RCCL all-reduce of the flat gradient] -> WeightDecay +
 GradientClipping + AMSGrad, data already resident in HBM.  Workload (N=1 and per GPU for N>1, weak scaling): BASELINE.json
 configs[1]: synthetic fbank (T=800, 80-d) batch 32, 2x[Conv+BN+ReLU] -> 3-layer 2x256 LSTM encoder -> attention ->
-1-layer LSTM-512 decoder, V=1098, L=40, shipped training knobs (dropout .3, speech noise .25, teacher forcing .8).
+1-layer LSTM-512 decoder, V=1098, L=40, shipped training knobs (dropout .3, speech noise .25, teacher forcing .8).  Every step
+starts from the same initial parameters, so what it computes is the same in every run up to rounding.
 
     python bench.py --gpus 1 --steps 50 --warmup 10            # BASELINE configs[1] (1-layer decoder): the metric's workload
     python bench.py --model es_en_20h                          # the shipped model (3 decoder layers, experiments/es_en_20h)
     python bench.py --gpus N                                   # N > 1 without a launcher: starts the N ranks itself (child process)
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P bench.py --gpus N ...
+    python bench.py --full                                     # + per-kernel roofline, other schemes, es_en_20h, epoch, CPU baseline
+    python bench.py --dump-outputs DIR                         # + the last timed step's results as DIR/<name>.npy
+
+A plain run sets up, warms up, times --steps steps and prints the line; everything else it can measure runs under --full only.
 """
 import argparse
 import copy
@@ -47,6 +52,8 @@ PRECISIONS = {"fp16x2": "f32 storage / f32 accumulate, products as fp16x2 splits
                         "v_mfma_f32_16x16x32_bf16); decoder loop, attention, softmax-CE, optimizer in IEEE f32 (f32-input MFMAs / f32 FMAs)",
               "f32": "IEEE f32 products everywhere (f32-input MFMA v_mfma_f32_32x32x2_f32 / 16x16x4_f32), f32 accumulate"}
 SCHEME_OF_MODE = {0: "fp16x2", 1: "bf16x3", 2: "f32"}       # astk_get_gemm_precision()
+DUMP_SAMPLE = 1 << 16       # --dump-outputs: elements kept per tensor (larger ones as a fixed sample: ~18 MB in all for configs[1])
+DUMP_LIMIT_BYTES = 64 << 20
 
 
 def synth_batch(B, T, D, L, V, seed):
@@ -95,6 +102,29 @@ def cpu_baseline(model_cfg, B, T, D, L, V, budget_s=30.0):
             "sample": f"one full train step of the same model at batch {Bs} (GPU batch {B}; T={T}, D={D}, L={L}) in {best:.2f} s, after a "
                       f"batch-{b2} step of {t2:.2f} s = {round(b2 * T / t2, 1)} frames/s; float32 NumPy restatement of the Chainer "
                       "path, per-step Python loop and one BLAS sgemm per Linear like Chainer-on-NumPy (Chainer is not installable offline)"}
+
+
+def dump_outputs(outdir, model, opt, loss_val):
+    """What a caller of the timed step has after its last call, as float32 / float64 .npy files: the loss, the norm the clipping
+    compared, every updated parameter, its gradient and the BatchNorm statistics.  A tensor above DUMP_SAMPLE elements is cut to the
+    same DUMP_SAMPLE flat positions every run (drawn from a generator seeded by the tensor's name), so two builds compare file by file."""
+    import zlib
+    import numpy as np
+    os.makedirs(outdir, exist_ok=True)
+    arrays = {"loss": np.array([loss_val], dtype=np.float64), "grad_norm": np.array([opt.last_grad_norm], dtype=np.float64)}
+    tensors = [("param", model.arena.views), ("grad", model.arena.gviews), ("persist", model.persist)]
+    for kind, views in tensors:
+        for name in views:
+            flat = views[name].detach().reshape(-1).float().cpu().numpy()
+            if flat.size > DUMP_SAMPLE:
+                rng = np.random.default_rng(zlib.crc32(name.encode()))
+                flat = flat[np.sort(rng.choice(flat.size, DUMP_SAMPLE, replace=False))]
+            arrays[kind + "." + name.replace("/", ".")] = flat
+    total = sum(a.nbytes for a in arrays.values())
+    assert total <= DUMP_LIMIT_BYTES, f"--dump-outputs would write {total} bytes"
+    for name, a in arrays.items():
+        np.save(os.path.join(outdir, name + ".npy"), a)
+    return len(arrays), total
 
 
 def bucket_plan(path, B, tokens_per_word, bucket_batch=None, num_b=20, width_b=80, max_sp=1680, max_pred=175, seed="seed-ast-20h"):
@@ -204,16 +234,16 @@ def main():
     ap.add_argument("--frames", type=int, default=800)
     ap.add_argument("--feat", type=int, default=80)
     ap.add_argument("--tgt-len", type=int, default=40)
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full: skip the CPU oracle timings")
     ap.add_argument("--sync-bn", action="store_true", help="N>1: BatchNorm statistics over the global batch (4 extra 5-10 KB all-reduces)")
-    ap.add_argument("--profile-steps", type=int, default=3, help="extra steps with per-kernel HIP-event timing")
-    ap.add_argument("--no-alt-precisions", action="store_true", help="skip the re-timings of the same step under the other two arithmetic schemes")
+    ap.add_argument("--profile-steps", type=int, default=3, help="--full: extra steps with per-kernel HIP-event timing")
+    ap.add_argument("--no-alt-precisions", action="store_true", help="--full: skip the re-timings of the same step under the other two arithmetic schemes")
     ap.add_argument("--precision", default=None, choices=["bf16x3", "f32", "fp16x2"],
                     help="arithmetic of the batched products for the headline (default: the library's default, bf16x3 = exact f32 operands "
                          "as three bf16 terms; f32 = f32-input MFMAs; fp16x2 = two scaled fp16 terms, narrower than float32)")
-    ap.add_argument("--no-also", action="store_true", help="skip the second workload (the shipped es_en_20h model) of the default cfg1 run")
+    ap.add_argument("--no-also", action="store_true", help="--full: skip the second workload (the shipped es_en_20h model) of a cfg1 run")
     ap.add_argument("--histogram", default=os.path.join(ROOT, "tests", "golden", "fisher_20h_frames.json"),
-                    help="corpus description (per-utterance frame and word counts of the reference's data/fisher/fisher_20h.info, extracted by "
+                    help="--full: corpus description (per-utterance frame and word counts of the reference's data/fisher/fisher_20h.info, extracted by "
                          "tests/golden/make_fisher_frames.py): one timed step per bucket of the reference's bucketing rule (prep_buckets.py:52, "
                          "20 buckets of 80 frames), weighted by the batches per bucket => epoch frames/s on the REAL shape distribution "
                          "(`epoch` in the JSON line); 'none' skips the leg")
@@ -222,6 +252,13 @@ def main():
                     "LDC-licensed text the reference does not ship; the .info file holds word counts)")
     ap.add_argument("--bucket-batch", default=None, help="--histogram: per-bucket batch sizes 'max,med,min' of the reference's OLD path "
                     "(nmt_run.py:421-426: first third of the buckets / second third / rest), e.g. 64,48,32; default: --batch everywhere")
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline, also run the legs a plain run skips: per-kernel profile steps (`roofline`, `roofline_scan`, "
+                         "`kernels`), the other arithmetic schemes, the es_en_20h workload, the --histogram epoch and the CPU baseline "
+                         "(each still switchable off by its own option)")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="write what the last timed step computed (loss, gradient norm, updated parameters, their gradients, BatchNorm "
+                         "statistics; tensors above %d elements as a fixed seeded sample) to DIR/<name>.npy" % DUMP_SAMPLE)
     args = ap.parse_args()
     maybe_self_launch(args, sys.argv[1:])
 
@@ -279,12 +316,16 @@ def main():
         torch.cuda.synchronize()
 
     class Workload:
-        """One model + optimizer + resident synthetic batch; step() = the whole train step of SURVEY.md 8(d)."""
+        """One model + optimizer + resident synthetic batch; step() = the whole train step of SURVEY.md 8(d), from the initial parameters."""
 
         def __init__(self, name):
             self.name, self.cfg = name, model_cfg(name)
             self.V = self.cfg["rnn_config"]["dec_vocab_size"]
             m = self.model = SpeechEncoderDecoder(local, self.cfg).materialize(D, seed=0)       # identical replicas
+            # every step starts from these parameters: the backward's float-atomic sums differ run to run by rounding, and steps that
+            # built on each other would let Adam grow those differences into lr-sized ones; so each step computes the same function
+            # of the seeded inputs (batch, noise, dropout masks, teacher forcing) in every run and two builds compare output for output
+            self.start = m.arena.data.clone()
             m.gemm_precision = base_scheme
             m.gemm_operands = args.gemm_operands
             o = self.opt = O.Adam(alpha=TRAIN["lr"], beta1=0.9, beta2=0.999, eps=1e-8, amsgrad=True).setup(m)
@@ -310,6 +351,7 @@ def main():
 
         def step(self):
             with torch.cuda.stream(compute), using_config("train", True):
+                self.model.arena.data.copy_(self.start)
                 loss = self.model.forward_loss(X=self.X, y=self.y, teach_ratio=TRAIN["teach_ratio"], random_out=0, add_noise=TRAIN["speech_noise"])
                 self.model.cleargrads()
                 loss.backward()
@@ -361,6 +403,10 @@ def main():
     dt, loss_val = w.timed(args.warmup, args.steps)
     ms = dt / args.steps * 1e3
     value = world * B * T / (dt / args.steps)
+    if args.dump_outputs and rank == 0:
+        # before any --full leg: those run more steps on the same model
+        n, nbytes = dump_outputs(args.dump_outputs, model, w.opt, loss_val)
+        print(f"bench: {n} arrays ({nbytes / 2**20:.1f} MB) of the last timed step in {args.dump_outputs}", file=sys.stderr, flush=True)
 
     # ---- which kernels ran (a silent fall-back to the per-launch paths must show in the driver's line)
     def paths_of(model):
@@ -400,7 +446,7 @@ def main():
 
     # ---- per-kernel timing with HIP events on the launch stream (in situ), plus in-kernel phase stamps of the persistent decoder
     roof, scan, extra = None, None, {}
-    if args.profile_steps > 0:
+    if args.full and args.profile_steps > 0:
         res = w.profile(args.profile_steps)
         T2 = model._cur["T2"]
         H = cfg["rnn_config"]["hidden_units"]
@@ -478,7 +524,7 @@ def main():
     # ---- the SAME step, same process, under the other two arithmetic schemes (the model's gemm_precision -> the descriptors' precision
     # field): driver-timed figures for the literal f32 MFMA chain and for the narrower opt-in fp16x2 split next to the headline's
     alt = []
-    if not args.no_alt_precisions:
+    if args.full and not args.no_alt_precisions:
         for scheme in ("bf16x3", "f32", "fp16x2"):
             if scheme == base_scheme:
                 continue
@@ -492,7 +538,7 @@ def main():
     # quoted on), same batch, same scheme, same step definition, `--steps` timed steps after `--warmup` warm-ups
     also = []
     w2 = None
-    if args.model == "cfg1" and not args.no_also:
+    if args.full and args.model == "cfg1" and not args.no_also:
         w2 = Workload("es_en_20h")
         d2, l2v = w2.timed(max(1, args.warmup), args.steps)
         e2 = {"workload": w2.describe(), "precision": base_scheme, "steps": args.steps, "ms_per_step": round(d2 / args.steps * 1e3, 3),
@@ -503,7 +549,7 @@ def main():
 
     # ---- the reference's REAL shape distribution (round 6): one timed step per bucket of the Fisher-20h training set
     epoch = None
-    if args.histogram and args.histogram != "none" and os.path.exists(args.histogram) and world == 1:
+    if args.full and args.histogram and args.histogram != "none" and os.path.exists(args.histogram) and world == 1:
         epoch = histogram_leg(w2 if w2 is not None else w, args, B, T, L, barrier)
         (w2 if w2 is not None else w).set_batch(B, T, L)
 
@@ -524,7 +570,7 @@ def main():
     if epoch is not None:
         out["epoch"] = epoch
     if rank == 0:
-        if world == 1 and not args.no_cpu_baseline:
+        if world == 1 and args.full and not args.no_cpu_baseline:
             # bounded CPU samples (the NumPy oracle on this box's host cores): ~20 s each for the headline's model and the shipped one,
             # both at the GPU's batch
             out["cpu_baseline"] = cpu_baseline(cfg, B, T, D, L, V)

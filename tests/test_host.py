@@ -489,6 +489,41 @@ def test_bench_starts_its_own_ranks_when_no_launcher_did(monkeypatch, capsys):
     assert len(calls) == 1
 
 
+def test_bench_dump_outputs_are_bounded_and_sample_the_same_positions(tmp_path):
+    """`bench.py --dump-outputs DIR` on the benchmark model's parameter layout (a CPU arena: the function only reads tensors): float32 /
+    float64 arrays, every parameter, gradient and BatchNorm statistic present, large tensors cut to the same seeded positions in every
+    run, the whole dump within 64 MB."""
+    import copy
+    import types
+    import torch
+    import bench
+    from ast_amd.params import ParamArena, param_shapes
+    cfg = copy.deepcopy(bench.MODEL_CFG)
+    train, persist = param_shapes(cfg, 80, cfg["rnn_config"]["dec_vocab_size"])
+    dirs = []
+    for run in range(2):
+        arena = ParamArena(train, "cpu")
+        arena.data.copy_(torch.arange(arena.size, dtype=torch.float32))
+        arena._grad.copy_(-torch.arange(arena.size, dtype=torch.float32))
+        model = types.SimpleNamespace(arena=arena, persist={k: torch.full(s, 0.5) for k, s in persist.items()})
+        d = tmp_path / str(run)
+        n, total = bench.dump_outputs(str(d), model, types.SimpleNamespace(last_grad_norm=1.25), 3.5)
+        assert n == 2 + 2 * len(train) + len(persist) and total <= 64 << 20
+        dirs.append(d)
+    files = sorted(p.name for p in dirs[0].iterdir())
+    assert files == sorted(p.name for p in dirs[1].iterdir()) and len(files) == n
+    assert np.load(dirs[0] / "loss.npy").tolist() == [3.5] and np.load(dirs[0] / "grad_norm.npy").tolist() == [1.25]
+    for f in files:
+        a, b = np.load(dirs[0] / f), np.load(dirs[1] / f)
+        assert a.dtype in (np.float32, np.float64) and np.array_equal(a, b), f
+    big = max(train, key=lambda k: int(np.prod(train[k])))
+    w = np.load(dirs[0] / ("param." + big.replace("/", ".") + ".npy"))
+    o = arena.offsets[big]
+    assert w.size == bench.DUMP_SAMPLE and np.all(np.diff(w) > 0) and o <= w[0] and w[-1] < o + int(np.prod(train[big]))
+    g = np.load(dirs[0] / ("grad." + big.replace("/", ".") + ".npy"))
+    assert np.array_equal(g, -w)
+
+
 # ---------------------------------------------------------------------------------------------------------------------------------
 # oracle/loader_ref.py: the reference's batch construction restated with injectable draws (SURVEY 8f rank 3)
 def test_loader_oracle_known_answers():
