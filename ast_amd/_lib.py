@@ -104,6 +104,20 @@ class DecoderGrads(C.Structure):
                 ("d_ln_gamma", C.c_void_p * MAX_RNN), ("d_ln_beta", C.c_void_p * MAX_RNN)]
 
 
+BEAM_MAX_N, BEAM_MAX_K = 16, 16        # astk.h ASTK_BEAM_MAX_N / _K
+
+
+class BeamDesc(_Sized, C.Structure):
+    _fields_ = [("struct_size", C.c_size_t), ("U", C.c_int), ("N", C.c_int), ("K", C.c_int), ("S", C.c_int), ("T", C.c_int),
+                ("V", C.c_int), ("eos", C.c_int), ("lengths_host", C.POINTER(C.c_int32))]
+
+
+class BeamState(_Sized, C.Structure):
+    _fields_ = [("struct_size", C.c_size_t), ("row_utt", C.c_void_p), ("row_len", C.c_void_p), ("c", C.c_void_p), ("h", C.c_void_p),
+                ("ht", C.c_void_p), ("tokens", C.c_void_p), ("score", C.c_void_p), ("status", C.c_void_p), ("frozen", C.c_void_p),
+                ("n_frozen", C.c_void_p), ("hist", C.c_void_p), ("hist_alpha", C.c_void_p)]
+
+
 # every symbol include/astk.h declares: name -> (restype, argtypes)
 _VP, _I, _L, _SZ, _F, _U64 = C.c_void_p, C.c_int, C.c_long, C.c_size_t, C.c_float, C.c_uint64
 SIGNATURES = {
@@ -154,6 +168,11 @@ SIGNATURES = {
                                          _VP, _VP, _VP, _VP, _VP, _VP, _SZ, _I, _VP]),
     "astk_decoder_step_infer": (C.c_int, [C.POINTER(DecoderDesc), C.POINTER(DecoderParams), _VP, _VP, _VP, _VP, _VP, _VP, _VP, _VP,
                                           _VP, _SZ, _VP]),
+    "astk_beam_workspace_bytes": (_SZ, [C.POINTER(BeamDesc), C.POINTER(DecoderDesc)]),
+    "astk_beam_step": (C.c_int, [C.POINTER(BeamDesc), C.POINTER(DecoderDesc), C.POINTER(DecoderParams), _VP, C.POINTER(BeamState), _I, _VP,
+                                 _SZ, _VP]),
+    "astk_beam_select": (C.c_int, [C.POINTER(BeamDesc), _I, _I, _I, _VP, _VP, _L, _VP, _VP, _VP, C.POINTER(BeamState), _I, _VP]),
+    "astk_attn_step_fwd_rows": (C.c_int, [_I, _I, _I, _VP, _VP, _VP, _VP, _VP, _VP, _VP, _SZ, _VP]),
     "astk_spin": (C.c_int, [C.c_uint, _VP, _VP]),
     "astk_softmax_ce_fwd": (C.c_int, [_I, _I, _L, _VP, _VP, _L, _VP, _F, _VP, _VP, _VP]),
     "astk_grad_sqnorm": (C.c_int, [_VP, _VP, _F, _SZ, _VP, _VP]),

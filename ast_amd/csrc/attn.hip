@@ -60,24 +60,29 @@ __device__ __forceinline__ float dot_row(const float4 (&a)[NCH], const float4 (&
   return s;
 }
 
-template <int NCH>
+// ROWS (the batched beam search, beam.hip): row b attends over enc[row_utt[b], 0:row_len[b]] of a (U, T, H) encoder buffer -- the
+// softmax covers those positions only and alpha is 0 behind them.  Split workgroups whose chunk lies wholly behind row_len[b] store an
+// empty partial (m = -inf, l = 0), which the merge weighs with 0.  Without ROWS the two pointers are not read.
+template <int NCH, bool ROWS>
 __global__ __launch_bounds__(256) void attn_fwd_partial(int B, int T, int H, const float* __restrict__ enc,
                                                         const float* __restrict__ q, long ldq, float* __restrict__ scores,
                                                         int Tp, float* __restrict__ part, int nsplit, int chunk,
                                                         unsigned* __restrict__ cnt, float* __restrict__ cv, long ldcv,
-                                                        float* __restrict__ cv2, long ldcv2) {
+                                                        float* __restrict__ cv2, long ldcv2, const int32_t* __restrict__ row_utt,
+                                                        const int32_t* __restrict__ row_len) {
   extern __shared__ __attribute__((aligned(16))) float sm[];   // [4][H] + 8 + 2*MAX_SPLIT
   __shared__ int s_last;
   const int b = blockIdx.x % B, sp = blockIdx.x / B;
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  const int t0 = sp * chunk, t1 = min(T, t0 + chunk);
+  const int Tb = ROWS ? min(max(row_len[b], 1), T) : T;
+  const int t0 = sp * chunk, t1 = min(Tb, t0 + chunk);
   float4 qv[NCH];
   load_row<NCH>(q + (long)b * ldq, H, lane, qv);
   float m = -INFINITY, l = 0.f;
   float4 acc[NCH];
 #pragma unroll
   for (int c = 0; c < NCH; ++c) acc[c] = make_float4(0.f, 0.f, 0.f, 0.f);
-  const float* base = enc + (long)b * T * H;
+  const float* base = enc + (long)(ROWS ? row_utt[b] : b) * T * H;
   for (int t = t0 + wave; t < t1; t += 8) {
     float4 e0[NCH], e1[NCH];
     const bool two = t + 4 < t1;
@@ -158,8 +163,8 @@ __global__ __launch_bounds__(256) void attn_fwd_partial(int B, int T, int H, con
   }
   for (int t = threadIdx.x; t < Tp; t += 256) {
     float* ap = scores + (long)b * Tp + t;
-    const float sc = t < T ? ld_sc1(ap) : 0.f;
-    *ap = t < T ? expf(sc - Mx) * inv : 0.f;
+    const float sc = t < Tb ? ld_sc1(ap) : 0.f;
+    *ap = t < Tb ? expf(sc - Mx) * inv : 0.f;
   }
 }
 
@@ -250,10 +255,12 @@ int attn_ws_init(void* ws, int B, int T, int H, hipStream_t s) {
   return 0;
 }
 
-int attn_fwd_launch(int B, int T, int H, const float* enc, const float* q, long ldq, float* alpha, float* cv, long ldcv,
-                    float* cv2, long ldcv2, void* ws, hipStream_t s) {
+template <bool ROWS>
+int attn_fwd_impl(int B, int T, int H, const float* enc, const int32_t* row_utt, const int32_t* row_len, const float* q, long ldq,
+                  float* alpha, float* cv, long ldcv, float* cv2, long ldcv2, void* ws, hipStream_t s) {
   ASTK_CHECK(B > 0 && T > 0 && H > 0 && (H % 4) == 0 && H <= 2048, "attn: need H %% 4 == 0 and H <= 2048 (H=%d)", H);
   ASTK_CHECK(enc && q && alpha && cv && ws && aligned16(enc) && aligned16(q) && (ldq % 4) == 0, "attn_fwd: bad pointers");
+  ASTK_CHECK(!ROWS || (row_utt && row_len), "attn_fwd_rows: null row map");
   int nsplit, chunk;
   split_for(B, T, nsplit, chunk);
   const int Tp = (T + 3) / 4 * 4;
@@ -264,13 +271,23 @@ int attn_fwd_launch(int B, int T, int H, const float* enc, const float* q, long 
   const int nch = cdiv(H, 256);
   {
   ProfScope prof(PROF_ATTN_FWD, s);
-  if (nch <= 1) hipLaunchKernelGGL((attn_fwd_partial<1>), grid, blk, shm, s, B, T, H, enc, q, ldq, alpha, Tp, part, nsplit, chunk, cnt, cv, ldcv, cv2, ldcv2);
-  else if (nch <= 2) hipLaunchKernelGGL((attn_fwd_partial<2>), grid, blk, shm, s, B, T, H, enc, q, ldq, alpha, Tp, part, nsplit, chunk, cnt, cv, ldcv, cv2, ldcv2);
-  else if (nch <= 4) hipLaunchKernelGGL((attn_fwd_partial<4>), grid, blk, shm, s, B, T, H, enc, q, ldq, alpha, Tp, part, nsplit, chunk, cnt, cv, ldcv, cv2, ldcv2);
-  else hipLaunchKernelGGL((attn_fwd_partial<8>), grid, blk, shm, s, B, T, H, enc, q, ldq, alpha, Tp, part, nsplit, chunk, cnt, cv, ldcv, cv2, ldcv2);
+  if (nch <= 1) hipLaunchKernelGGL((attn_fwd_partial<1, ROWS>), grid, blk, shm, s, B, T, H, enc, q, ldq, alpha, Tp, part, nsplit, chunk, cnt, cv, ldcv, cv2, ldcv2, row_utt, row_len);
+  else if (nch <= 2) hipLaunchKernelGGL((attn_fwd_partial<2, ROWS>), grid, blk, shm, s, B, T, H, enc, q, ldq, alpha, Tp, part, nsplit, chunk, cnt, cv, ldcv, cv2, ldcv2, row_utt, row_len);
+  else if (nch <= 4) hipLaunchKernelGGL((attn_fwd_partial<4, ROWS>), grid, blk, shm, s, B, T, H, enc, q, ldq, alpha, Tp, part, nsplit, chunk, cnt, cv, ldcv, cv2, ldcv2, row_utt, row_len);
+  else hipLaunchKernelGGL((attn_fwd_partial<8, ROWS>), grid, blk, shm, s, B, T, H, enc, q, ldq, alpha, Tp, part, nsplit, chunk, cnt, cv, ldcv, cv2, ldcv2, row_utt, row_len);
   }
   ASTK_LAUNCH_CHECK();
   return 0;
+}
+
+int attn_fwd_launch(int B, int T, int H, const float* enc, const float* q, long ldq, float* alpha, float* cv, long ldcv,
+                    float* cv2, long ldcv2, void* ws, hipStream_t s) {
+  return attn_fwd_impl<false>(B, T, H, enc, nullptr, nullptr, q, ldq, alpha, cv, ldcv, cv2, ldcv2, ws, s);
+}
+
+int attn_fwd_rows_launch(int B, int T, int H, const float* enc, const int32_t* row_utt, const int32_t* row_len, const float* q, long ldq,
+                         float* alpha, float* cv, long ldcv, void* ws, hipStream_t s) {
+  return attn_fwd_impl<true>(B, T, H, enc, row_utt, row_len, q, ldq, alpha, cv, ldcv, nullptr, 0, ws, s);
 }
 
 int attn_bwd_launch(int B, int T, int H, const float* enc, const float* alpha, const float* cv, long ldcv, const float* d_cv,
@@ -311,6 +328,13 @@ int astk_attn_step_fwd(int B, int T, int H, const float* enc, const float* q, fl
   ASTK_CHECK(ws_bytes >= attn_ws_bytes(B, T, H), "attn_step_fwd: workspace too small");
   ASTK_TRY(attn_ws_init(ws, B, T, H, (hipStream_t)stream));
   return attn_fwd_launch(B, T, H, enc, q, H, alpha, cv, H, nullptr, 0, ws, (hipStream_t)stream);
+}
+
+int astk_attn_step_fwd_rows(int R, int T, int H, const float* enc, const int32_t* row_utt, const int32_t* row_len, const float* q,
+                            float* alpha, float* cv, void* ws, size_t ws_bytes, void* stream) {
+  ASTK_CHECK(ws_bytes >= attn_ws_bytes(R, T, H), "attn_step_fwd_rows: workspace too small");
+  ASTK_TRY(attn_ws_init(ws, R, T, H, (hipStream_t)stream));
+  return attn_fwd_rows_launch(R, T, H, enc, row_utt, row_len, q, H, alpha, cv, H, ws, (hipStream_t)stream);
 }
 
 int astk_attn_step_bwd(int B, int T, int H, const float* enc, const float* alpha, const float* cv, const float* d_cv,

@@ -526,6 +526,31 @@ int lstm_cell_bwd_launch(const LstmCellBwdArgs* cells, int ncells, hipStream_t s
 // ---- attention (attn.hip)
 int attn_fwd_launch(int B, int T, int H, const float* enc, const float* q, long ldq, float* alpha, float* cv, long ldcv,
                     float* cv2, long ldcv2, void* ws, hipStream_t s);
+// ---- the eval-mode decoder step (decoder.hip): the body of astk_decoder_step_infer, shared with the batched beam search (beam.hip),
+// which brings its own attention launch (per-row encoder slices) and keeps the old states of the rows it carries
+typedef int (*AttnFwdFn)(const void* ctx, int B, int T, int H, const float* enc, const float* q, long ldq, float* alpha, float* cv,
+                         long ldcv, void* ws, hipStream_t s);
+struct DecStepIO {
+  const float* enc;
+  float* c; float* h;                      // (n_layers, B, H) states going in; overwritten with the new ones when states_in_place
+  const float* ht_in; float* ht_out;       // (B, A): the step's attentional vector in / out (may be the same buffer)
+  const int32_t* tokens;                   // (B) fed tokens
+  float* logits;                           // (B, V)
+  float* alpha;                            // (B, T) copy of the first head's alpha, or null
+  int32_t* argmax;                         // (B) or null
+  AttnFwdFn attn; const void* attn_ctx;    // null: attn_fwd_launch over enc (B, T, H)
+  bool states_in_place;
+  // written by the call: where the new states and the first head's alpha (row stride ld_alpha_ws) are left in the workspace
+  const float* c_new[ASTK_MAX_RNN_LAYERS];
+  const float* h_new[ASTK_MAX_RNN_LAYERS];
+  const float* alpha_ws;
+  int ld_alpha_ws;
+};
+size_t decoder_step_ws_bytes(const astk_decoder_desc* d);
+int decoder_step_run(const astk_decoder_desc* d, const astk_decoder_params* prm, DecStepIO& io, void* ws, size_t ws_bytes, hipStream_t s);
+// rows b attend over enc[row_utt[b], 0:row_len[b]] of a (U, T, H) buffer (beam.hip); alpha (B, Tp) is 0 behind row_len[b]
+int attn_fwd_rows_launch(int B, int T, int H, const float* enc, const int32_t* row_utt, const int32_t* row_len, const float* q, long ldq,
+                         float* alpha, float* cv, long ldcv, void* ws, hipStream_t s);
 int attn_bwd_launch(int B, int T, int H, const float* enc, const float* alpha, const float* cv, long ldcv,
                     const float* d_cv, long ld_dcv, float* ds, float* dq, void* ws, hipStream_t s);
 size_t attn_ws_bytes(int B, int T, int H);

@@ -958,13 +958,32 @@ int astk_decoder_bwd_phase_ex(const astk_decoder_desc* d, const astk_decoder_par
 int astk_decoder_step_infer(const astk_decoder_desc* d, const astk_decoder_params* prm, const float* enc, float* c, float* h, float* ht,
                             const int32_t* tokens, float* logits, float* alpha, int32_t* argmax, void* ws, size_t ws_bytes,
                             void* stream) {
-  hipStream_t s = (hipStream_t)stream;
+  DecStepIO io;
+  memset(&io, 0, sizeof(io));
+  io.enc = enc; io.c = c; io.h = h; io.ht_in = ht; io.ht_out = ht; io.tokens = tokens; io.logits = logits; io.alpha = alpha;
+  io.argmax = argmax; io.states_in_place = true;
+  return decoder_step_run(d, prm, io, ws, ws_bytes, (hipStream_t)stream);
+}
+
+}  // extern "C"
+
+namespace astk {
+
+size_t decoder_step_ws_bytes(const astk_decoder_desc* d) {
+  DecPlan P;
+  return make_plan(d, nullptr, P) == 0 ? P.bytes : 0;
+}
+
+int decoder_step_run(const astk_decoder_desc* d, const astk_decoder_params* prm, DecStepIO& io, void* ws, size_t ws_bytes, hipStream_t s) {
   ASTK_CHECK_DESC(d, astk_decoder_desc);
   PrecScope prec_scope(d->precision, d->gemm_operands);
   DecPlan P;
   ASTK_TRY(make_plan(d, ws, P));
   ASTK_CHECK(ws && ws_bytes >= P.bytes, "decoder_step_infer: workspace too small");
-  ASTK_CHECK(prm && enc && c && h && ht && tokens && logits, "decoder_step_infer: null pointer");
+  float *c = io.c, *h = io.h, *ht_out = io.ht_out;
+  const float *enc = io.enc, *ht = io.ht_in;
+  const int32_t* tokens = io.tokens;
+  ASTK_CHECK(prm && enc && c && h && ht && ht_out && tokens && io.logits, "decoder_step_infer: null pointer");
   const int B = P.B, H = P.H, E = P.E, A = P.A, V = P.V, XI = P.XI, nl = P.nl, NA = P.NA, CW = P.CW;
   const size_t bh = (size_t)B * H;
   float* x0 = P.X0;
@@ -985,8 +1004,12 @@ int astk_decoder_step_infer(const astk_decoder_desc* d, const astk_decoder_param
     // new states go to scratch first (the cell reads h_prev while other workgroups write h_out)
     ASTK_TRY(cell_fwd(P, prm, l, x_in, ld_x, in, h + l * bh, c + l * bh, P.G[l], P.C[l], P.HR[l], nullptr, raw, P.ln ? H : ld_hd, s));
     if (P.ln) ASTK_TRY(layernorm_fwd_launch(B, H, raw, H, prm->ln_gamma[l], prm->ln_beta[l], LN_EPS, hd, ld_hd, s));
-    ASTK_TRY(copy_f32(c + l * bh, P.C[l], bh, s));
-    ASTK_TRY(copy_f32(h + l * bh, P.HR[l], bh, s));
+    if (io.states_in_place) {
+      ASTK_TRY(copy_f32(c + l * bh, P.C[l], bh, s));
+      ASTK_TRY(copy_f32(h + l * bh, P.HR[l], bh, s));
+    }
+    io.c_new[l] = P.C[l];
+    io.h_new[l] = P.HR[l];
     x_in = hd; ld_x = ld_hd; in = H;
   }
   for (int k = 0; k < NA; ++k) {
@@ -995,26 +1018,30 @@ int astk_decoder_step_infer(const astk_decoder_desc* d, const astk_decoder_param
     a.bias = k == 0 ? prm->ba : prm->ba_x[k - 1];
     ASTK_TRY(rowgemm_launch(a, s));
     // (the alphas handed back are the FIRST head's, seq2seq.py:379-383)
-    ASTK_TRY(attn_fwd_launch(B, P.T, H, enc, q, H, k == 0 ? P.ALPHA : P.DS, cvh + (size_t)k * H, CW, nullptr, 0, P.attn_ws, s));
+    float* al = k == 0 ? P.ALPHA : P.DS;
+    if (io.attn) ASTK_TRY(io.attn(io.attn_ctx, B, P.T, H, enc, q, H, al, cvh + (size_t)k * H, CW, P.attn_ws, s));
+    else ASTK_TRY(attn_fwd_launch(B, P.T, H, enc, q, H, al, cvh + (size_t)k * H, CW, nullptr, 0, P.attn_ws, s));
   }
-  if (alpha) ASTK_TRY(copy2d_f32(alpha, P.T, P.ALPHA, P.Tp, B, P.T, P.T, s));
+  io.alpha_ws = P.ALPHA;
+  io.ld_alpha_ws = P.Tp;
+  if (io.alpha) ASTK_TRY(copy2d_f32(io.alpha, P.T, P.ALPHA, P.Tp, B, P.T, P.T, s));
   {
-    RowGemmArgs a = rg(B, A, cvh, CW, prm->Wc, CW, CW, ht, A);
+    RowGemmArgs a = rg(B, A, cvh, CW, prm->Wc, CW, CW, ht_out, A);
     a.bias = prm->bc;
     a.act = ACT_TANH;
     ASTK_TRY(rowgemm_launch(a, s));
   }
   {
-    RowGemmArgs a = rg(B, V, ht, A, prm->Wo, A, A, logits, V);
+    RowGemmArgs a = rg(B, V, ht_out, A, prm->Wo, A, A, io.logits, V);
     a.bias = prm->bo;
     ASTK_TRY(rowgemm_launch(a, s));
   }
-  if (argmax) {
+  if (io.argmax) {
     // argmax only: run the CE kernel on a scratch copy so that `logits` stays intact
-    ASTK_TRY(copy2d_f32(P.LOGITS, P.Vp, logits, V, B, V, P.Vp, s));
-    ASTK_TRY(softmax_ce_launch(B, V, P.Vp, P.LOGITS, tokens, 1, nullptr, 1.f, nullptr, argmax, s));
+    ASTK_TRY(copy2d_f32(P.LOGITS, P.Vp, io.logits, V, B, V, P.Vp, s));
+    ASTK_TRY(softmax_ce_launch(B, V, P.Vp, P.LOGITS, tokens, 1, nullptr, 1.f, nullptr, io.argmax, s));
   }
   return 0;
 }
 
-}  // extern "C"
+}  // namespace astk

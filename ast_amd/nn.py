@@ -56,6 +56,115 @@ def decode_beam(model, X, stop_limit, N, K):
     return n_best
 
 
+def decode_beam_batch(model, Xs, stop_limit, N, K):
+    """decode_beam for many utterances at once: Xs is a list of (1, T_u, D) inputs; returns one N-best list per utterance, each the
+    list decode_beam(model, Xs[u], stop_limit, N, K) returns (same hypotheses, order and types).  Every slot of every utterance is one
+    row of a single decoder step (include/astk.h astk_beam_step: decoder step, float64 top-K / top-N selection and state gather on the
+    device); the host reads one counter per step, a step late, and backtracks the device's history once at the end."""
+    import ctypes as C
+    import numpy as np
+    from . import _lib
+    if not (1 <= N <= _lib.BEAM_MAX_N and 1 <= K <= _lib.BEAM_MAX_K):
+        raise ValueError(f"decode_beam_batch: N = {N} and K = {K} must lie in 1..{_lib.BEAM_MAX_N} / 1..{_lib.BEAM_MAX_K} (use decode_beam)")
+    lib = model._require_gpu()
+    dev = model.device
+    GO, EOS = SYMBOLS.GO_ID, SYMBOLS.EOS_ID
+    with using_config("train", False):
+        # ---- every utterance encoded at its own length (no length masks in the encoder, quirk Q2), copied out of the pooled buffers
+        encs, seeds = [], []
+        for X in Xs:
+            model.encode(X)
+            encs.append(model.enc_states[0].clone())
+            seeds.append(model.get_encoder_states())
+        if stop_limit <= 0:
+            return [[_init_hyp_from(model, s)] for s in seeds]
+        U, nl, H, A, V = len(Xs), len(model.rnn_dec), model.H, model.A, model.V
+        R, lens = U * N, [int(e.shape[0]) for e in encs]
+        Tmax = max(lens)
+        f32, i32 = dict(dtype=torch.float32, device=dev), dict(dtype=torch.int32, device=dev)
+        enc = torch.zeros(U, Tmax, H, **f32)
+        c, h = torch.zeros(nl, R, H, **f32), torch.zeros(nl, R, H, **f32)
+        # slot 0 of utterance u: the encoder's final states layer by layer (set_decoder_states(get_encoder_states()) of init_hyp)
+        for u, (e, sd) in enumerate(zip(encs, seeds)):
+            enc[u, :lens[u]] = e
+            for l in range(min(nl, len(sd["c"]))):
+                c[l, u * N] = sd["c"][l][0]
+                h[l, u * N] = sd["h"][l][0]
+        ht = torch.zeros(R, A, **f32)
+        tokens = torch.full((R,), GO, **i32)
+        score = torch.zeros(R, dtype=torch.float64, device=dev)
+        status = torch.zeros(R, **i32)
+        status[::N] = 1
+        frozen, n_frozen = torch.zeros(U, **i32), torch.zeros(1, **i32)
+        hist = torch.zeros(stop_limit, R, 4, **i32)
+        hist_alpha = torch.empty(stop_limit, R, Tmax, **f32)
+        row_utt = torch.arange(R, **i32) // N
+        row_len = torch.tensor(lens, **i32)[row_utt.long()].contiguous()
+        lens_host = np.asarray(lens, dtype=np.int32)
+        bd = _lib.BeamDesc(U, N, K, stop_limit, Tmax, V, EOS, lens_host.ctypes.data_as(C.POINTER(C.c_int32)))
+        bs = _lib.BeamState(*[t.data_ptr() for t in (row_utt, row_len, c, h, ht, tokens, score, status, frozen, n_frozen, hist, hist_alpha)])
+        dd = _lib.DecoderDesc.from_buffer_copy(model._cur["dd"])
+        dd.B, dd.T, dd.L, dd.status_dst, dd.use_truth_host = R, Tmax, 2, None, None
+        nbytes = int(lib.astk_beam_workspace_bytes(C.byref(bd), C.byref(dd)))
+        if nbytes == 0:
+            _lib.check(-1)
+        ws = model._workspace("beam", nbytes)
+        dp, stream = model._cur["dp"], torch.cuda.current_stream(dev)
+        sp = C.c_void_p(stream.cuda_stream)
+        # ---- the loop: one astk_beam_step per step; the frozen-utterance count of step s is read after step s+1 is enqueued (steps on
+        # frozen utterances only carry them again, so a step too many changes nothing)
+        seen = torch.zeros(2, dtype=torch.int32, pin_memory=True)
+        events, steps = [None, None], 0
+        for step in range(stop_limit):
+            _lib.check(lib.astk_beam_step(C.byref(bd), C.byref(dd), C.byref(dp), C.c_void_p(enc.data_ptr()), C.byref(bs), step,
+                                          C.c_void_p(ws.data_ptr()), ws.numel(), sp))
+            steps = step + 1
+            slot = step % 2
+            seen[slot:slot + 1].copy_(n_frozen, non_blocking=True)
+            events[slot] = torch.cuda.Event()
+            events[slot].record(stream)
+            if step > 0:
+                events[1 - slot].synchronize()
+                if int(seen[1 - slot]) >= U:
+                    break
+        stream.synchronize()
+        # ---- backtrack the history once
+        H_ = hist[:steps].cpu().numpy()
+        sc, stt = score.cpu().numpy(), status.cpu().numpy()
+        found, rows_s, rows_r = [], [], []
+        for u in range(U):
+            lst = []
+            for i in range(N):
+                r = u * N + i
+                if stt[r] == 0:
+                    break
+                toks, arow, j = [], [], i
+                for s in range(steps - 1, -1, -1):
+                    p, t, carried = (int(v) for v in H_[s, u * N + j, :3])
+                    if not carried:
+                        toks.append(t)
+                        arow.append(len(rows_s))
+                        rows_s.append(s)
+                        rows_r.append(u * N + j)
+                    j = p
+                lst.append((r, toks[::-1], arow[::-1]))
+            found.append(lst)
+        alphas = hist_alpha[torch.tensor(rows_s, dtype=torch.long, device=dev), torch.tensor(rows_r, dtype=torch.long, device=dev)].cpu().numpy() \
+            if rows_s else np.zeros((0, Tmax), np.float32)
+        out = []
+        for u, lst in enumerate(found):
+            out.append([{"hyp": [GO] + toks, "score": float(sc[r]),
+                         "dec_state": {"c": [c[l, r:r + 1].clone() for l in range(nl)], "h": [h[l, r:r + 1].clone() for l in range(nl)]},
+                         "attn_v": ht[r:r + 1].clone(), "attn_history": [alphas[k, :lens[u]].copy() for k in arow]}
+                        for r, toks, arow in lst])
+        return out
+
+
+def _init_hyp_from(model, enc_states):
+    return {"hyp": [SYMBOLS.GO_ID], "score": 0, "dec_state": enc_states,
+            "attn_v": torch.zeros(1, model.cfg["rnn_config"]["attn_units"], dtype=torch.float32, device=model.device), "attn_history": []}
+
+
 class NN:
     def __init__(self, cfg_path, vocab_size=None):
         self.cfg = Config(cfg_path, vocab_size=vocab_size)
@@ -200,6 +309,9 @@ class NN:
 
     def decode_beam(self, X, stop_limit, N, K):
         return decode_beam(self.model, X, stop_limit, N, K)
+
+    def decode_beam_batch(self, Xs, stop_limit, N, K):
+        return decode_beam_batch(self.model, Xs, stop_limit, N, K)
 
     def predict(self, set_key):
         preds = []

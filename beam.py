@@ -1,9 +1,11 @@
 """beam.py drop-in (beam.py:46-146 of the reference):
-    python beam.py -m <cfg_dir> -n <N hyps kept> -k <K candidates per step> -s <set key> -w <length weight> [--resume]
+    python beam.py -m <cfg_dir> -n <N hyps kept> -k <K candidates per step> -s <set key> -w <length weight> [--resume] [-b U]
 Beam search over one set with the newest checkpoint of the experiment, n-best lists pickled to
 <cfg_dir>/<set>_beam_N-<N>_K-<K>.p, the length-normalised best hypothesis of each utterance scored with corpus BLEU
-(ast_amd.eval) and written to <cfg_dir>/<set>_beam_N-<N>_K-<K>_W-<W>.en."""
+(ast_amd.eval) and written to <cfg_dir>/<set>_beam_N-<N>_K-<K>_W-<W>.en.  -b U decodes U utterances per batched search on the
+GPU (ast_amd.nn.decode_beam_batch): the same utterances and hypotheses, the same files."""
 import argparse
+import itertools
 import math
 import os
 import pickle
@@ -11,6 +13,7 @@ import random
 
 from tqdm import tqdm
 
+from ast_amd._lib import BEAM_MAX_K, BEAM_MAX_N
 from ast_amd.eval import Eval
 from ast_amd.nn import NN
 
@@ -33,8 +36,13 @@ if __name__ == "__main__":
     parser.add_argument("-s", "--S", help="dev/dev2/test", required=True)
     parser.add_argument("-w", "--W", help="len normalization weight", required=True)
     parser.add_argument("--resume", action="store_true", help="re-score the saved beam results instead of decoding again")
+    parser.add_argument("-b", "--batch", type=int, default=0, help="decode U utterances at once on the GPU (same hypotheses)")
     args = vars(parser.parse_args())
     cfg_path, N, K, W, set_key = args["cfg_path"], int(args["N"]), int(args["K"]), float(args["W"]), args["S"]
+    U = args["batch"]
+    if U >= 1 and not (N <= BEAM_MAX_N and K <= BEAM_MAX_K):
+        print("-b {0:d}: N and K above {1:d} / {2:d} are decoded one utterance at a time".format(U, BEAM_MAX_N, BEAM_MAX_K))
+        U = 0
     nn = NN(cfg_path)
     metrics = Eval(os.path.join(nn.cfg.train["data"]["refs_path"], set_key), nn.cfg.train["data"]["n_evals"])
     random.seed("meh")
@@ -51,10 +59,23 @@ if __name__ == "__main__":
         stop_limit = nn.cfg.train["data"]["max_pred"]
         beam = {}
         with tqdm(total=nn.data_loader.n_utts[set_key], ncols=80) as pbar:
-            for utt in nn.data_loader.get_batch(1, set_key, train=False, labels=False):
-                n_best = nn.decode_beam(utt["X"], stop_limit=stop_limit, N=N, K=K)
-                beam[utt["utts"][0]] = [(e["hyp"], e["score"], e["attn_history"]) for e in n_best]
-                pbar.update(len(utt["X"]))
+            if U >= 1:
+                # the same utterances, order and truncation as below, U of them per batched search
+                group = []
+                for utt in itertools.chain(nn.data_loader.get_batch(1, set_key, train=False, labels=False), [None]):
+                    if utt is not None:
+                        group.append(utt)
+                    if group and (utt is None or len(group) == U):
+                        lists = nn.decode_beam_batch([g["X"] for g in group], stop_limit=stop_limit, N=N, K=K)
+                        for g, n_best in zip(group, lists):
+                            beam[g["utts"][0]] = [(e["hyp"], e["score"], e["attn_history"]) for e in n_best]
+                        pbar.update(len(group))
+                        group = []
+            else:
+                for utt in nn.data_loader.get_batch(1, set_key, train=False, labels=False):
+                    n_best = nn.decode_beam(utt["X"], stop_limit=stop_limit, N=N, K=K)
+                    beam[utt["utts"][0]] = [(e["hyp"], e["score"], e["attn_history"]) for e in n_best]
+                    pbar.update(len(utt["X"]))
         print("saving hyps")
         with open(beam_fname, "wb") as f:
             pickle.dump(beam, f)

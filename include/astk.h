@@ -30,7 +30,7 @@
 extern "C" {
 #endif
 
-#define ASTK_VERSION 106
+#define ASTK_VERSION 107
 #define ASTK_MAX_CNN_LAYERS 4
 #define ASTK_MAX_RNN_LAYERS 8
 #define ASTK_MAX_ATTN 4
@@ -377,6 +377,57 @@ int astk_decoder_bwd_phase_ex(const astk_decoder_desc* d, const astk_decoder_par
 int astk_decoder_step_infer(const astk_decoder_desc* d, const astk_decoder_params* p, const float* enc,
                             float* c, float* h, float* ht, const int32_t* tokens, float* logits, float* alpha,
                             int32_t* argmax, void* ws, size_t ws_bytes, void* stream);
+
+/* ---------------------------------------------------------------- batched beam search  (nn.py:235-322 over many utterances)
+ * U utterances, N hypotheses kept per utterance, K candidates per live hypothesis: every slot is one row of ONE decoder step over
+ * R = U*N rows, row u*N + j = slot j of utterance u.  enc is (U, T, H): utterance u's encoder states in enc[u, 0:T''_u] (the rest
+ * is never read); row r attends over its utterance's T''_u positions only.  A step, per utterance and in the reference's order:
+ * slot by slot, an empty slot contributes nothing, a finished one (status 2) itself, a live one (status 1) its K best tokens by
+ * float64 log_softmax (equal log-probabilities: lower token id first) with score = score_j + logp; the N best candidates are kept
+ * (equal scores: the earlier candidate).  A new expansion takes the states its parent row computed in this step, a carried slot
+ * keeps its own.  An utterance whose non-empty slots have all finished is frozen (frozen[u] = 1, *n_frozen counts them); further
+ * steps only carry it again.  Limits: N and K at most 16. */
+#define ASTK_BEAM_MAX_N 16
+#define ASTK_BEAM_MAX_K 16
+typedef struct {
+  size_t struct_size;  /* sizeof(astk_beam_desc), see astk_cnn_desc.struct_size */
+  int U, N, K;
+  int S;               /* steps the history buffers hold (the stop limit); `step` runs 0..S-1 */
+  int T;               /* T''max: positions per utterance of enc and of the alpha history */
+  int V;               /* vocabulary (the decoder's) */
+  int eos;             /* id of the token that finishes a hypothesis */
+  const int32_t* lengths_host;  /* HOST, U entries: T''_u in 1..T (checked at every call; the kernels read row_len) */
+} astk_beam_desc;
+
+typedef struct {       /* caller-owned DEVICE buffers of a search; the caller seeds them (slot 0 live with the encoder's final states) */
+  size_t struct_size;  /* sizeof(astk_beam_state) */
+  const int32_t* row_utt;  /* (R) utterance of every row (r / N) */
+  const int32_t* row_len;  /* (R) T''_u of every row's utterance */
+  float* c; float* h;      /* (n_layers, R, H) decoder states of every slot */
+  float* ht;               /* (R, A) attentional vector of every slot */
+  int32_t* tokens;         /* (R) last token of every slot */
+  double* score;           /* (R) */
+  int32_t* status;         /* (R) 0 empty, 1 live, 2 finished */
+  int32_t* frozen;         /* (U) */
+  uint32_t* n_frozen;      /* (1) */
+  int32_t* hist;           /* (S, R, 4) per step and new slot: parent slot (-1: empty), token, carried (1) or new expansion (0), 0 */
+  float* hist_alpha;       /* (S, R, T) the parent row's (first head's) alpha of the step, for new expansions only */
+} astk_beam_state;
+
+/* d: the decoder's descriptor with B = U*N, T = T''max (its L is ignored: one step). 0 = bad arguments. */
+size_t astk_beam_workspace_bytes(const astk_beam_desc* b, const astk_decoder_desc* d);
+/* One step for all R rows: decoder step (astk_decoder_step_infer's kernels, per-row attention), selection, history row `step`,
+ * state gather. */
+int astk_beam_step(const astk_beam_desc* b, const astk_decoder_desc* d, const astk_decoder_params* p, const float* enc,
+                   const astk_beam_state* st, int step, void* ws, size_t ws_bytes, void* stream);
+/* The selection and gather alone, on a step's results supplied by the caller: logits (R, V), alpha (R, ld_alpha >= T), the new
+ * states c_new / h_new (n_layers, R, H) and ht_new (R, A) every row computed. */
+int astk_beam_select(const astk_beam_desc* b, int n_layers, int H, int A, const float* logits, const float* alpha, long ld_alpha,
+                     const float* c_new, const float* h_new, const float* ht_new, const astk_beam_state* st, int step, void* stream);
+/* The attention scan of astk_attn_step_fwd with per-row encoder slices: row r attends over enc[row_utt[r], 0:row_len[r]] of enc
+ * (U, T, H); alpha (R, Tp) is 0 from row_len[r] on.  Workspace: astk_attn_workspace_bytes(R, T, H). */
+int astk_attn_step_fwd_rows(int R, int T, int H, const float* enc, const int32_t* row_utt, const int32_t* row_len, const float* q,
+                            float* alpha, float* cv, void* ws, size_t ws_bytes, void* stream);
 
 /* ---------------------------------------------------------------- normalisation layers of the optional encoder variants
  * L.LayerNormalization(units) behind an LSTM (rnn_config.ln; seq2seq.py:85-87, 200-202): rows x n, row strides ld*, per-row mean and
