@@ -43,6 +43,10 @@ struct DecPersistBwdBuffers {
   unsigned* ctr;
 };
 bool decoder_persist_b6_split(const astk_decoder_desc* d);
+// greedy decoding on the persistent loop (decoder_persist.hip)
+size_t greedy_workspace_bytes(const astk_decoder_desc* d, int stop_limit);
+int greedy_decode_launch(const astk_decoder_desc* d, const astk_decoder_params* prm, const float* enc, const float* c0, const float* h0, int go,
+                         int eos, int stop_limit, int32_t* tokens, int32_t* n_steps, float* status_dst, void* ws, size_t ws_bytes, hipStream_t s);
 int decoder_persist_bwd_launch(const astk_decoder_desc* d, const float* enc, const float* rnn_masks, const DecPersistBwdBuffers& bf,
                                hipStream_t s);
 
@@ -963,6 +967,14 @@ int astk_decoder_step_infer(const astk_decoder_desc* d, const astk_decoder_param
   io.enc = enc; io.c = c; io.h = h; io.ht_in = ht; io.ht_out = ht; io.tokens = tokens; io.logits = logits; io.alpha = alpha;
   io.argmax = argmax; io.states_in_place = true;
   return decoder_step_run(d, prm, io, ws, ws_bytes, (hipStream_t)stream);
+}
+
+size_t astk_greedy_workspace_bytes(const astk_decoder_desc* d, int stop_limit) { return greedy_workspace_bytes(d, stop_limit); }
+
+int astk_greedy_decode(const astk_decoder_desc* d, const astk_decoder_params* p, const float* enc, const float* c0, const float* h0,
+                       int go, int eos, int stop_limit, int32_t* tokens, int32_t* n_steps, float* status_dst,
+                       void* ws, size_t ws_bytes, void* stream) {
+  return greedy_decode_launch(d, p, enc, c0, h0, go, eos, stop_limit, tokens, n_steps, status_dst, ws, ws_bytes, (hipStream_t)stream);
 }
 
 }  // extern "C"

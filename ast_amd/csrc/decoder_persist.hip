@@ -88,6 +88,12 @@ struct PDecArgs {
   AbortCtl ab;
   int dbg;
   float* tick_out;         // profiler: [G] accumulated attention-phase microseconds per workgroup, [G+0] launches
+  // greedy mode (GR): feed `go` at step 0, stop once every row has emitted `eos` (S = the stop limit; PRED = the caller's tokens)
+  int go, eos;
+  unsigned* gctl;          // 4 counter lines: [0] max over batch tiles of the step their last row finished, [1] tiles reported,
+                           // [2] workgroups that left, [3] the stop word (n_steps; preset to S)
+  int32_t* n_steps_out;    // written by the last workgroup to leave: the stop word
+  float* status_dst;       // ... and a copy of the persistent status word (or null)
 };
 
 __device__ __forceinline__ unsigned ld_flag(const unsigned* p) { return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
@@ -122,27 +128,36 @@ __device__ __forceinline__ float4 ldb128_sc1(__amdgpu_buffer_rsrc_t r, long floa
   const u32x4 v = __builtin_amdgcn_raw_buffer_load_b128(r, (int)(float_off * 4), 0, 16);
   return make_float4(__uint_as_float(v.x), __uint_as_float(v.y), __uint_as_float(v.z), __uint_as_float(v.w));
 }
-__device__ __forceinline__ bool wait_ge(const unsigned* ctr, unsigned target, const AbortCtl& ab) {
+// Greedy decoding's stop (decoder_persist_fwd<.., GR = true>): `word` holds n_steps once every row has emitted EOS (stop_limit until
+// then).  A wait made for decoder step `step` gives up, without raising the abort word, once step >= n_steps: its producer may have left.
+// A wait for a step below n_steps never leaves on it -- every producer finishes all steps below n_steps before it leaves.  The training
+// kernels pass no word (the check folds away).  `recheck`: look once more after the counter is satisfied (the layer-0 cells' wait on
+// their own tile's P6, which writes the word in front of that arrival).
+struct StopCtl { const unsigned* word; int step; bool recheck; };
+__device__ __forceinline__ bool stop_seen(const StopCtl& st) { return st.word && (unsigned)st.step >= ld_flag(st.word); }
+__device__ __forceinline__ bool wait_ge(const unsigned* ctr, unsigned target, const AbortCtl& ab, const StopCtl& st = StopCtl{nullptr, 0, false}) {
   unsigned spins = 0;
   while (ld_flag(ctr) < target) {
     if (++spins > ab.limit) {
       abort_raise(ab);
       return false;
     }
-    if ((spins & 63u) == 0 && abort_seen(ab)) return false;
+    if ((spins & 63u) == 0 && (abort_seen(ab) || stop_seen(st))) return false;
   }
   return true;
 }
 // workgroup-wide wait: lane 0 polls, everyone learns the outcome
-__device__ __forceinline__ bool wg_wait(const unsigned* ctr, unsigned target, const AbortCtl& ab, int* s_flag) {
-  if (threadIdx.x == 0) *s_flag = wait_ge(ctr, target, ab) ? 1 : 0;
+__device__ __forceinline__ bool wg_wait(const unsigned* ctr, unsigned target, const AbortCtl& ab, int* s_flag,
+                                        const StopCtl& st = StopCtl{nullptr, 0, false}) {
+  if (threadIdx.x == 0) *s_flag = wait_ge(ctr, target, ab, st) ? 1 : 0;
   __syncthreads();
   const bool ok = *s_flag != 0;
   __syncthreads();            // s_flag may be rewritten by the next wait
   return ok;
 }
 // workgroup-wide wait on `count` (<= 64) counters `stride` words apart: lane i of wave 0 polls counter i
-__device__ __forceinline__ bool wg_wait_multi(const unsigned* base, int stride, int count, unsigned target, const AbortCtl& ab, int* s_flag) {
+__device__ __forceinline__ bool wg_wait_multi(const unsigned* base, int stride, int count, unsigned target, const AbortCtl& ab, int* s_flag,
+                                              const StopCtl& st = StopCtl{nullptr, 0, false}) {
   if (threadIdx.x < 64) {
     const int lane = threadIdx.x;
     bool ok = true;
@@ -151,7 +166,7 @@ __device__ __forceinline__ bool wg_wait_multi(const unsigned* base, int stride, 
       const bool mine = lane < count ? ld_flag(base + (long)lane * stride) >= target : true;
       if (__all(mine)) break;
       if (++spins > ab.limit) { abort_raise(ab); ok = false; break; }
-      if ((spins & 63u) == 0 && abort_seen(ab)) { ok = false; break; }
+      if ((spins & 63u) == 0 && (abort_seen(ab) || stop_seen(st))) { ok = false; break; }
     }
     if (lane == 0) *s_flag = ok ? 1 : 0;
   }
@@ -165,7 +180,8 @@ __device__ __forceinline__ bool wg_wait_multi(const unsigned* base, int stride, 
 // far more under load): with 32-128 arrivals per hand-off on ONE word the decoder kernels ran 1.00 / 1.00 ms; 4 / 8 / 16 / 32 / 64 words:
 // 0.84/0.82, 0.80/0.78, 0.79/0.75, 0.78/0.73, 0.78/0.75 ms (forward / backward).
 constexpr int NSH = 32;
-__device__ __forceinline__ bool wg_wait_sh(const unsigned* base, int n_items, int steps, const AbortCtl& ab, int* s_flag) {
+__device__ __forceinline__ bool wg_wait_sh(const unsigned* base, int n_items, int steps, const AbortCtl& ab, int* s_flag,
+                                           const StopCtl& st = StopCtl{nullptr, 0, false}) {
   if (threadIdx.x < 64) {
     const int lane = threadIdx.x;
     const unsigned target = lane < NSH ? (unsigned)(((n_items - lane + NSH - 1) / NSH) * steps) : 0u;   // items with idx % NSH == lane
@@ -175,8 +191,9 @@ __device__ __forceinline__ bool wg_wait_sh(const unsigned* base, int n_items, in
       const bool mine = (lane < NSH && target > 0) ? ld_flag(base + lane * CTRS) >= target : true;
       if (__all(mine)) break;
       if (++spins > ab.limit) { abort_raise(ab); ok = false; break; }
-      if ((spins & 63u) == 0 && abort_seen(ab)) { ok = false; break; }
+      if ((spins & 63u) == 0 && (abort_seen(ab) || stop_seen(st))) { ok = false; break; }
     }
+    if (ok && st.recheck && lane == 0 && stop_seen(st)) ok = false;
     if (lane == 0) *s_flag = ok ? 1 : 0;
   }
   __syncthreads();
@@ -294,15 +311,24 @@ __device__ __forceinline__ void mfma_blocks(f32x4& acc, const float4* a, const f
 // NC = 0: generic loops.
 // XS: the slice has more rows than stay resident (chunk > PDEC_RES_ROWS): the streamed-row code is compiled into its own instantiation
 // so that the common short-chunk case keeps its register budget.
-template <int NC, int NL, bool XS>
-__global__ __launch_bounds__(256, 1) void decoder_persist_fwd(PDecArgs a) {
+// GR: greedy decoding (inference): step 0 feeds `go` to every row, every later step its own argmax; no targets, masks, loss or saved
+// state for a backward pass (Gt, Cst, X0, ALPHA, ML, LOGITS, LSE and loss rows are neither read nor written: the input-feeding part of
+// a cell reads ht_{s-1} from HT).  The CE owner of each batch tile keeps a sticky per-row done flag (padding rows are done); once its
+// tile is all done it reports that step (atomic max, then one arrival), and the tile that completes the count writes the stop word
+// n_steps = max + 1 before its PH_CE arrival of that step.  The layer-0 cells read the stop word behind that arrival and leave at
+// step n_steps; every other wait learns of it in its slow path (StopCtl).  DESIGN.md section 11.
+template <int NC, int NL, bool XS, bool GR>
+__device__ __forceinline__ void decoder_persist_fwd_body(const PDecArgs& a) {
   extern __shared__ __attribute__((aligned(16))) float lds[];   // enc slice [chunk][H], encA slice [chunk][H], scratch
   __shared__ __attribute__((aligned(16))) float red[4 * 256];
   __shared__ __attribute__((aligned(16))) float zt[2 * 256];
   __shared__ int s_flag;
-  __shared__ int yS[16 * 192];         // targets of this workgroup's batch tile (L <= 192)
-  __shared__ int flagS[192];           // teacher-forcing flags
+  __shared__ int yS[GR ? 1 : 16 * 192];    // targets of this workgroup's batch tile (L <= 192)
+  __shared__ int flagS[GR ? 1 : 192];      // teacher-forcing flags
+  __shared__ int s_stop;                   // GR: a sentinel poll saw the stop
+  __shared__ int s_wdone[4];               // GR: per wave of the CE role, all of its rows are done
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  if (GR && tid == 0) s_stop = 0;          // (the first barrier below orders it before every use)
   const int wg = blockIdx.x;
   const int B = a.B, S = a.S, H = a.H, E = a.E, A = a.A, V = a.V, XI = a.XI, T = a.T, Tp = a.Tp;
   const int nbt = a.nbt;
@@ -380,11 +406,13 @@ __global__ __launch_bounds__(256, 1) void decoder_persist_fwd(PDecArgs a) {
         wload<NB_L>(wreg + OFF_WL + t * NB_L, a.Wo, A, min(n0 + r16, V - 1), A, lane, wave);
       }
   }
-  if (has_cell) {
-    for (int i = tid; i < 16 * a.L; i += 256) yS[i] = a.y[(long)min(cell_bt * 16 + i / a.L, B - 1) * a.L + (i % a.L)];
-    for (int i = tid; i < S; i += 256) flagS[i] = a.use_truth[i];
-  } else if (has_ce) {
-    for (int i = tid; i < S; i += 256) flagS[i] = a.use_truth[i];     // (which steps feed their argmax back: decides when P6 may be deferred)
+  if constexpr (!GR) {
+    if (has_cell) {
+      for (int i = tid; i < 16 * a.L; i += 256) yS[i] = a.y[(long)min(cell_bt * 16 + i / a.L, B - 1) * a.L + (i % a.L)];
+      for (int i = tid; i < S; i += 256) flagS[i] = a.use_truth[i];
+    } else if (has_ce) {
+      for (int i = tid; i < S; i += 256) flagS[i] = a.use_truth[i];     // (which steps feed their argmax back: decides when P6 may be deferred)
+    }
   }
   // ---------------- resident slices of enc_states and encA = enc Wa in LDS: rows [t0, t1) of batch row att_b
   const int t0 = att_sp * a.chunk, t1 = min(T, t0 + a.chunk);
@@ -447,9 +475,11 @@ __global__ __launch_bounds__(256, 1) void decoder_persist_fwd(PDecArgs a) {
 #define TQ(i) if (timing) { const long long now_ = wall_clock64(); tq[i] += now_ - tlast; tlast = now_; }
 #define TICK(i) if (timing) { const long long now_ = wall_clock64(); tk[i] += now_ - tlast; tlast = now_; }
   int p6_pending = -1;
+  bool row_done = ce_rank * 16 + (tid >> 4) >= B;     // GR, CE role: sticky "this thread's row has emitted EOS" (padding rows: done)
+  bool tile_done = false;                             // GR, CE role (thread 0): this batch tile has reported
   auto run_p6 = [&](const int s) -> bool {
       const int bt = ce_rank, m0 = bt * 16;
-      if (!wg_wait_sh(CTR(PH_LOG, bt), a.ntile_v, s + 1, a.ab, &s_flag)) return false;
+      if (!wg_wait_sh(CTR(PH_LOG, bt), a.ntile_v, s + 1, a.ab, &s_flag, StopCtl{GR ? a.gctl + 3 * CTRS : nullptr, s, false})) return false;
       const int row = m0 + (tid >> 4), sub = tid & 15;       // 16 threads per row sweep the tiles
       float mx = -INFINITY, se = 0.f, xt = 0.f;
       int mi = 0x7fffffff;
@@ -459,7 +489,7 @@ __global__ __launch_bounds__(256, 1) void decoder_persist_fwd(PDecArgs a) {
           const float tm = cs.x, ts = cs.y, tx = cs.w;
           const int ti = __float_as_int(cs.z);
           const float nm = fmaxf(mx, tm);
-          se = se * expf(mx - nm) + ts * expf(tm - nm);
+          if constexpr (!GR) se = se * expf(mx - nm) + ts * expf(tm - nm);
           if (tm > mx || (tm == mx && ti < mi)) mi = ti;
           mx = nm;
           xt += tx;
@@ -469,33 +499,61 @@ __global__ __launch_bounds__(256, 1) void decoder_persist_fwd(PDecArgs a) {
         const float om = __shfl_xor(mx, o), os = __shfl_xor(se, o), ox = __shfl_xor(xt, o);
         const int oi = __shfl_xor(mi, o);
         const float nm = fmaxf(mx, om);
-        se = (mx == -INFINITY ? 0.f : se * expf(mx - nm)) + (om == -INFINITY ? 0.f : os * expf(om - nm));
+        if constexpr (!GR) se = (mx == -INFINITY ? 0.f : se * expf(mx - nm)) + (om == -INFINITY ? 0.f : os * expf(om - nm));
         if (om > mx || (om == mx && oi < mi)) mi = oi;
         mx = nm;
         xt += ox;
       }
-      if (sub == 0 && row < B) {
-        const float lse = mx + logf(se);
-        const int tgt = *ua(a.ytgt + s + 1, (unsigned)(row * a.L));
-        const float w = a.cw ? a.cw[tgt < 0 ? 0 : (tgt >= V ? V - 1 : tgt)] : 1.f;
-        *ua(a.LSE + (long)s * B, (unsigned)row) = lse;
-        *ua(a.LOSSROWS + (long)s * B, (unsigned)row) = -(xt - lse) * w * a.inv_count;
-        sti_sc1(ua(a.PRED + (long)s * B, (unsigned)row), mi);
+      if constexpr (GR) {
+        if (sub == 0 && row < B) {
+          sti_sc1(ua(a.PRED + (long)s * B, (unsigned)row), mi);
+          row_done = row_done || mi == a.eos;
+        }
+        const bool wdone = __all(sub != 0 || row_done);
+        if (lane == 0) s_wdone[wave] = wdone ? 1 : 0;
+        // publish_sh() with the tile's report between its barrier and its arrival: the stop word is written in front of PH_CE(s)
+        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+        __syncthreads();
+        if (tid == 0) {
+          if (!tile_done && s_wdone[0] && s_wdone[1] && s_wdone[2] && s_wdone[3]) {
+            tile_done = true;
+            unsigned* gc = a.gctl;
+            __hip_atomic_fetch_max(gc, (unsigned)s, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+            if (__hip_atomic_fetch_add(gc + CTRS, 1u, __ATOMIC_ACQ_REL, __HIP_MEMORY_SCOPE_AGENT) + 1 == (unsigned)a.nbt) {
+              const unsigned n = __hip_atomic_load(gc, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) + 1;
+              __hip_atomic_store(gc + 3 * CTRS, n, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+              asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+            }
+          }
+          __hip_atomic_fetch_add(CTR(PH_CE, bt), 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        }
+      } else {
+        if (sub == 0 && row < B) {
+          const float lse = mx + logf(se);
+          const int tgt = *ua(a.ytgt + s + 1, (unsigned)(row * a.L));
+          const float w = a.cw ? a.cw[tgt < 0 ? 0 : (tgt >= V ? V - 1 : tgt)] : 1.f;
+          *ua(a.LSE + (long)s * B, (unsigned)row) = lse;
+          *ua(a.LOSSROWS + (long)s * B, (unsigned)row) = -(xt - lse) * w * a.inv_count;
+          sti_sc1(ua(a.PRED + (long)s * B, (unsigned)row), mi);
+        }
+        publish_sh(CTR(PH_CE, bt), 0);
       }
-      publish_sh(CTR(PH_CE, bt), 0);
       TICK(12)
     return true;
   };
+  const unsigned* const stopw = GR ? a.gctl + 3 * CTRS : nullptr;
   for (int s = 0; s < S; ++s) {
+    const StopCtl sc{stopw, s, false};
     // ================= P1: embed + LSTM cell =================
     if (has_cell) {
       const int bt = cell_bt, m0 = bt * 16;
       const int brow = min(m0 + r16, B - 1);             // this lane's A-operand batch row
-      const bool truth = s == 0 || flagS[s] != 0;
-      if (!truth) { if (!wg_wait_sh(CTR(PH_CE, bt), 1, s, a.ab, &s_flag)) return; }
-      int tok = truth ? yS[r16 * a.L + s] : ldi_sc1(ua(a.PRED + (long)(s - 1) * B, (unsigned)brow));
+      const bool truth = s == 0 || (!GR && flagS[s] != 0);
+      // (GR: the stop word is read behind this tile's P6 of step s-1, which wrote it in front of that arrival: the cells leave at n_steps)
+      if (!truth) { if (!wg_wait_sh(CTR(PH_CE, bt), 1, s, a.ab, &s_flag, StopCtl{stopw, s, true})) return; }
+      int tok = truth ? (GR ? a.go : yS[r16 * a.L + s]) : ldi_sc1(ua(a.PRED + (long)(s - 1) * B, (unsigned)brow));
       tok = tok < 0 ? 0 : (tok >= V ? V - 1 : tok);
-      if (s > 0) { if (!wg_wait_sh(CTR(PH_CELL, bt), H / 8, s, a.ab, &s_flag)) return; }
+      if (s > 0) { if (!wg_wait_sh(CTR(PH_CELL, bt), H / 8, s, a.ab, &s_flag, sc)) return; }
       f32x4 acc[2] = {{0.f, 0.f, 0.f, 0.f}, {0.f, 0.f, 0.f, 0.f}};
       {
         // (a) embedding part and (b) recurrent part: neither depends on this step's ht, so they run before the wait on P4
@@ -527,10 +585,11 @@ __global__ __launch_bounds__(256, 1) void decoder_persist_fwd(PDecArgs a) {
       TICK(0)
       // (c) input-feeding part: ht_{s-1}, written into X0[s][:, E:] by P4 of step s-1
       if (s > 0) {
-        if (!wg_wait_sh(CTR(PH_CTX, bt), A / 16, s, a.ab, &s_flag)) return;
+        if (!wg_wait_sh(CTR(PH_CTX, bt), A / 16, s, a.ab, &s_flag, sc)) return;
         TICK(1)
         float4 at[NB_A];
-        aload_sc1<NB_A>(at, r_x0, ((long)s * B + brow) * XI + E, A, lane, wave);
+        if constexpr (GR) aload_sc1<NB_A>(at, r_ht, ((long)s * B + brow) * A, A, lane, wave);     // (HT[s] = ht_{s-1}: no X0)
+        else aload_sc1<NB_A>(at, r_x0, ((long)s * B + brow) * XI + E, A, lane, wave);
         __builtin_amdgcn_sched_barrier(0);
         mfma_blocks<NB_A>(acc[0], at, wreg + W0_A);
         mfma_blocks<NB_A>(acc[1], at, wreg + CW0 + W0_A);
@@ -556,7 +615,7 @@ __global__ __launch_bounds__(256, 1) void decoder_persist_fwd(PDecArgs a) {
       TICK(2)
       publish_sh(CTR(PH_CELL, bt), cell_u0 / 8);
       TICK(3)
-      if (ev) {                                    // saved for the backward (plain stores, off the critical path)
+      if (!GR && ev) {                             // saved for the backward (plain stores, off the critical path)
         *ua(reinterpret_cast<float4*>(a.Gt[0] + (long)s * B * 4 * H), cell_off) = gsave;
         *ua(a.Cst[0] + (long)(s + 1) * B * H, cell_off) = c_state;
       }
@@ -572,7 +631,7 @@ __global__ __launch_bounds__(256, 1) void decoder_persist_fwd(PDecArgs a) {
         const int l = pass == 0 ? 1 : TOP;
         const int bt = c2_bt, m0 = bt * 16;
         const int brow = min(m0 + r16, B - 1);
-        if (s > 0) { if (!wg_wait_sh(CTR(PH_CELL + l, bt), H / 8, s, a.ab, &s_flag)) return; }
+        if (s > 0) { if (!wg_wait_sh(CTR(PH_CELL + l, bt), H / 8, s, a.ab, &s_flag, sc)) return; }
         f32x4 acc[2] = {{0.f, 0.f, 0.f, 0.f}, {0.f, 0.f, 0.f, 0.f}};
         {
           float4 ah[NB_H];
@@ -582,7 +641,7 @@ __global__ __launch_bounds__(256, 1) void decoder_persist_fwd(PDecArgs a) {
           mfma_blocks<NB_H>(acc[1], ah, wreg + OFF_C2 + CELLW2 + NB_H);
         }
 #if !(ASTK_PDEC_SENT_HD && ASTK_PDEC_SENT_H)
-        if (!wg_wait_sh(CTR(PH_CELL + l - 1, bt), H / 8, s + 1, a.ab, &s_flag)) return;
+        if (!wg_wait_sh(CTR(PH_CELL + l - 1, bt), H / 8, s + 1, a.ab, &s_flag, sc)) return;
 #endif
         {
           float4 ax[NB_H];
@@ -602,7 +661,12 @@ __global__ __launch_bounds__(256, 1) void decoder_persist_fwd(PDecArgs a) {
               if (__all(ok) || att_dead) break;
               if (++spins > (a.ab.limit >> 1)) { abort_raise(a.ab); att_dead = true; }
               else if ((spins & 63u) == 0 && abort_seen(a.ab)) att_dead = true;
+              else if ((spins & 63u) == 0 && __any(stop_seen(sc))) { if (lane == 0) s_stop = 1; break; }
             }
+          }
+          if constexpr (GR) {     // (a stop: the whole workgroup leaves, after the barrier that shows every wave's verdict)
+            __syncthreads();
+            if (s_stop) return;
           }
 #else
           aload_sc1<NB_H>(ax, make_rsrc(a.HD[l - 1]), ((long)s * B + brow) * H, H, lane, wave);  // dropped output of the layer below
@@ -630,7 +694,7 @@ __global__ __launch_bounds__(256, 1) void decoder_persist_fwd(PDecArgs a) {
           else st_sc1_u(a.HD[l] + (long)s * B * H, c2_off, hd);
         }
         publish_sh(CTR(PH_CELL + l, bt), c2_u0 / 8);
-        if (ev) {
+        if (!GR && ev) {
           *ua(reinterpret_cast<float4*>(a.Gt[l] + (long)s * B * 4 * H), c2_off) = gsave;
           *ua(a.Cst[l] + (long)(s + 1) * B * H, c2_off) = c_state2;
         }
@@ -656,13 +720,14 @@ __global__ __launch_bounds__(256, 1) void decoder_persist_fwd(PDecArgs a) {
           if (__all((v.x != PDEC_SENTINEL) & (v.y != PDEC_SENTINEL) & (v.z != PDEC_SENTINEL) & (v.w != PDEC_SENTINEL)) || att_dead) break;
           if (++spins > (a.ab.limit >> 1)) { abort_raise(a.ab); att_dead = true; }
           else if ((spins & 63u) == 0 && abort_seen(a.ab)) att_dead = true;
+          else if ((spins & 63u) == 0 && __any(stop_seen(sc))) { if (lane == 0) s_stop = 1; break; }   // (GR: read behind the barrier below)
         }
         *reinterpret_cast<float4*>(hS + 4 * tid) = make_float4(__uint_as_float(v.x), __uint_as_float(v.y), __uint_as_float(v.z), __uint_as_float(v.w));
       }
       TICK(4)
       const long long ta0 = a.tick_out ? wall_clock64() : 0;
 #else
-      if (!wg_wait_sh(CTR(PH_CELL + TOP, bt), H / 8, s + 1, a.ab, &s_flag)) return;
+      if (!wg_wait_sh(CTR(PH_CELL + TOP, bt), H / 8, s + 1, a.ab, &s_flag, sc)) return;
       TICK(4)
       const long long ta0 = a.tick_out ? wall_clock64() : 0;
       if (tid < H / 4) *reinterpret_cast<float4*>(hS + 4 * tid) = ldb128_sc1(r_cvh, ((long)s * B + b) * 2 * H + H + 4 * tid);
@@ -677,6 +742,7 @@ __global__ __launch_bounds__(256, 1) void decoder_persist_fwd(PDecArgs a) {
         float* const pS_ = scr + HH + 64;                // scratch: hS[H] | scores[64] | p[64] | fold
         if (tid >= nrow && tid < 64) scS[tid] = -INFINITY;
         __syncthreads();
+        if (GR && s_stop) return;
         TICK(13)
         {
           // pass 1: 16 lanes per row; group g owns rows g and g + 16; lane l covers floats 4l + 64c of the row
@@ -802,6 +868,7 @@ __global__ __launch_bounds__(256, 1) void decoder_persist_fwd(PDecArgs a) {
         float mg = -INFINITY;
         if (tid >= nrow && tid < c4) scS[tid] = -INFINITY;        // pad the score vector for the float4 sweeps below
         __syncthreads();
+        if (GR && s_stop) return;
         TICK(13)
         {
           // pass 1: 16 lanes per row, two rows per trip; lane l covers floats 4l + 64c (conflict-free LDS reads)
@@ -871,7 +938,7 @@ __global__ __launch_bounds__(256, 1) void decoder_persist_fwd(PDecArgs a) {
       publish(ROWCTR(b));      // per-row counter: 8 arrivals instead of 128 on one word, and the combine waits for ITS row only
       TQ(5)
       if (a.tick_out) tk_att += wall_clock64() - ta0;
-      if (tid < nrow) a.ALPHA[((long)s * B + b) * Tp + t0 + tid] = my_score;   // raw score, normalised by the backward (M, 1/L in ML)
+      if (!GR && tid < nrow) a.ALPHA[((long)s * B + b) * Tp + t0 + tid] = my_score;   // raw score, normalised by the backward (M, 1/L in ML)
       TICK(5)
     }
     if (has_ce && p6_pending >= 0) {       // P6 of the previous step, deferred behind this step's attention partial (see P6 below)
@@ -883,7 +950,7 @@ __global__ __launch_bounds__(256, 1) void decoder_persist_fwd(PDecArgs a) {
       const int b = cmb_b, bt = b / 16;
       const int rows_bt = min(16, B - bt * 16);
       TICK(15)
-      if (!wg_wait(ROWCTR(b), (unsigned)(a.nsplit * (s + 1)), a.ab, &s_flag)) return;
+      if (!wg_wait(ROWCTR(b), (unsigned)(a.nsplit * (s + 1)), a.ab, &s_flag, sc)) return;
       TICK(6)
       // No staging, no barrier: lane k of EVERY wave reads the header {max_k, sum_k} of partial k, the softmax weights of the
       // nsplit partials are formed with wave shuffles (identically in every wave), and thread tid < H/4 folds its four columns of the
@@ -920,7 +987,7 @@ __global__ __launch_bounds__(256, 1) void decoder_persist_fwd(PDecArgs a) {
       }
       publish_sh(CTR(PH_CMB, bt), b - bt * 16);
       TICK(7)
-      if (tid == 0) { a.ML[((long)s * B + b) * 2] = Mx; a.ML[((long)s * B + b) * 2 + 1] = inv; }
+      if (!GR && tid == 0) { a.ML[((long)s * B + b) * 2] = Mx; a.ML[((long)s * B + b) * 2 + 1] = inv; }
     }
     // ================= P4: ht = tanh(Wc [cv;h] + bc) =================
     if (has_c) {
@@ -932,7 +999,7 @@ __global__ __launch_bounds__(256, 1) void decoder_persist_fwd(PDecArgs a) {
       if constexpr (NC > 0) {
         // the h half of [cv ; h] was published by the cells long ago: its fragments (k-blocks NC..2NC-1 of each wave) and their MFMAs
         // run BEFORE the wait on the combine; only the cv half is fetched and multiplied behind it
-        if (!wg_wait_sh(CTR(PH_CELL + TOP, bt), H / 8, s + 1, a.ab, &s_flag)) return;
+        if (!wg_wait_sh(CTR(PH_CELL + TOP, bt), H / 8, s + 1, a.ab, &s_flag, sc)) return;
         {
           float4 ahd[NC];
           const int q = lane >> 4;
@@ -941,7 +1008,7 @@ __global__ __launch_bounds__(256, 1) void decoder_persist_fwd(PDecArgs a) {
           __builtin_amdgcn_sched_barrier(0);
           mfma_blocks<NC>(acc, ahd, wreg + OFF_WC + NC);
         }
-        if (!wg_wait_sh(CTR(PH_CMB, bt), rows_bt, s + 1, a.ab, &s_flag)) return;
+        if (!wg_wait_sh(CTR(PH_CMB, bt), rows_bt, s + 1, a.ab, &s_flag, sc)) return;
         TICK(8)
         {
           float4 acv[NC];
@@ -952,7 +1019,7 @@ __global__ __launch_bounds__(256, 1) void decoder_persist_fwd(PDecArgs a) {
           mfma_blocks<NC>(acc, acv, wreg + OFF_WC);
         }
       } else {
-        if (!wg_wait_sh(CTR(PH_CMB, bt), rows_bt, s + 1, a.ab, &s_flag)) return;
+        if (!wg_wait_sh(CTR(PH_CMB, bt), rows_bt, s + 1, a.ab, &s_flag, sc)) return;
         TICK(8)
         wmac<NB_C>(acc, wreg + OFF_WC, r_cvh, crow, 2 * H, lane, wave);
       }
@@ -961,7 +1028,7 @@ __global__ __launch_bounds__(256, 1) void decoder_persist_fwd(PDecArgs a) {
       if (row < B) {
         const float ht = tanh_fast(v + a.bc[n]);
         st_sc1_u(a.HT + (long)(s + 1) * B * A, (unsigned)(row * A + n), ht);
-        if (s + 1 < S) st_sc1_u(a.X0 + (long)(s + 1) * B * XI + E, (unsigned)(row * XI + n), ht);
+        if (!GR && s + 1 < S) st_sc1_u(a.X0 + (long)(s + 1) * B * XI + E, (unsigned)(row * XI + n), ht);
       }
       publish_sh(CTR(PH_CTX, bt), c_n0 / 16);
       TICK(9)
@@ -972,7 +1039,7 @@ __global__ __launch_bounds__(256, 1) void decoder_persist_fwd(PDecArgs a) {
       if (l_item[t] < 0) continue;
       const int bt = l_item[t] / a.ntile_v, tile = l_item[t] % a.ntile_v, m0 = bt * 16, n0 = tile * 16;
       TICK(15)
-      if (!wg_wait_sh(CTR(PH_CTX, bt), A / 16, s + 1, a.ab, &s_flag)) return;
+      if (!wg_wait_sh(CTR(PH_CTX, bt), A / 16, s + 1, a.ab, &s_flag, sc)) return;
       TICK(10)
       f32x4 acc = {0.f, 0.f, 0.f, 0.f};
       wmac<NB_L>(acc, wreg + OFF_WL + t * NB_L, r_ht, ((long)(s + 1) * B + min(m0 + r16, B - 1)) * A, A, lane, wave);
@@ -980,8 +1047,10 @@ __global__ __launch_bounds__(256, 1) void decoder_persist_fwd(PDecArgs a) {
       const int row = m0 + (tid >> 4), n = n0 + (tid & 15);
       const bool ok = row < B && n < V;
       const float x = ok ? v + a.bo[n] : -INFINITY;
-      if (ok) *ua(a.LOGITS + (long)s * B * a.Vp, (unsigned)(row * a.Vp + n)) = x;
-      else if (row < B && n < a.Vp) *ua(a.LOGITS + (long)s * B * a.Vp, (unsigned)(row * a.Vp + n)) = 0.f;
+      if (!GR) {       // (GR: P6 needs the tile's maximum and its index only)
+        if (ok) *ua(a.LOGITS + (long)s * B * a.Vp, (unsigned)(row * a.Vp + n)) = x;
+        else if (row < B && n < a.Vp) *ua(a.LOGITS + (long)s * B * a.Vp, (unsigned)(row * a.Vp + n)) = 0.f;
+      }
       float mx = x;
       int mi = n;
 #pragma unroll
@@ -990,13 +1059,16 @@ __global__ __launch_bounds__(256, 1) void decoder_persist_fwd(PDecArgs a) {
         const int oi = __shfl_xor(mi, o);
         if (om > mx || (om == mx && oi < mi)) { mx = om; mi = oi; }
       }
-      float se = ok ? expf(x - mx) : 0.f;
+      float se = 0.f, xt = 0.f;
+      if constexpr (!GR) {
+        se = ok ? expf(x - mx) : 0.f;
 #pragma unroll
-      for (int o = 8; o > 0; o >>= 1) se += __shfl_xor(se, o);
-      const int tgt = row < B ? *ua(a.ytgt + s + 1, (unsigned)(row * a.L)) : 0;
-      float xt = (ok && n == tgt) ? x : 0.f;
+        for (int o = 8; o > 0; o >>= 1) se += __shfl_xor(se, o);
+        const int tgt = row < B ? *ua(a.ytgt + s + 1, (unsigned)(row * a.L)) : 0;
+        xt = (ok && n == tgt) ? x : 0.f;
 #pragma unroll
-      for (int o = 8; o > 0; o >>= 1) xt += __shfl_xor(xt, o);
+        for (int o = 8; o > 0; o >>= 1) xt += __shfl_xor(xt, o);
+      }
       if ((tid & 15) == 0 && row < B) {
         float* cs = ua(a.CESTAT + ((long)s * B * a.ntile_v + tile) * 4, (unsigned)(row * a.ntile_v * 4));
         st_sc1(cs, mx); st_sc1(cs + 1, se); st_sc1(cs + 2, __int_as_float(mi)); st_sc1(cs + 3, xt);
@@ -1012,7 +1084,7 @@ __global__ __launch_bounds__(256, 1) void decoder_persist_fwd(PDecArgs a) {
     // it is then DEFERRED behind the workgroup's P3 of step s+1.  When step s+1 feeds the argmax back its cells wait for PH_CE(s)
     // anyway and P6(s) runs in place (deferring it there would dead-lock: P3(s+1) waits for cells that wait for P6(s)).
     if (has_ce) {
-      const bool defer = s + 1 < S && flagS[s + 1] != 0;
+      const bool defer = !GR && s + 1 < S && flagS[s + 1] != 0;      // (GR: every step feeds its argmax back)
       if (defer) p6_pending = s;
       else if (!run_p6(s)) return;
     }
@@ -1033,6 +1105,20 @@ __global__ __launch_bounds__(256, 1) void decoder_persist_fwd(PDecArgs a) {
 #undef TQ
 #undef CTR
 #undef ROWCTR
+}
+
+template <int NC, int NL, bool XS, bool GR>
+__global__ __launch_bounds__(256, 1) void decoder_persist_fwd(PDecArgs a) {
+  decoder_persist_fwd_body<NC, NL, XS, GR>(a);     // (every return in it is workgroup-uniform)
+  if constexpr (GR) {
+    // the last workgroup to leave -- after every stop, abort or time-out of the launch -- writes n_steps and the status copy
+    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    __syncthreads();
+    if (threadIdx.x == 0 && __hip_atomic_fetch_add(a.gctl + 2 * CTRS, 1u, __ATOMIC_ACQ_REL, __HIP_MEMORY_SCOPE_AGENT) + 1 == (unsigned)G) {
+      *a.n_steps_out = (int32_t)__hip_atomic_load(a.gctl + 3 * CTRS, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+      if (a.status_dst) *a.status_dst = (float)__hip_atomic_load(a.ab.status, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    }
+  }
 }
 
 // =====================================================================================================================
@@ -1706,7 +1792,9 @@ static size_t pdec_bwd_lds_floats(int chunk, int H) {
   return 2 * (size_t)pdec_res_rows(H, chunk) * H + 2 * (size_t)H + (size_t)((chunk + 3) & ~3) + 16 + 160 + 512;
 }
 
-bool decoder_persist_applicable(const astk_decoder_desc* d, int* nsplit_out, int* chunk_out) {
+// max_L: the training kernel keeps a batch tile's targets and the teacher-forcing flags in LDS (yS / flagS: L <= 192); greedy mode
+// reads neither and passes its own cap (d->L = stop_limit + 1)
+static bool pdec_applicable(const astk_decoder_desc* d, int max_L, int* nsplit_out, int* chunk_out) {
   if (!tune_on(TUNE_DEC_PERSIST)) return false;
   if (d->n_attn > 1 || d->no_feed_attn || d->ln) return false;      // optional model features: per-launch loop (decoder.hip)
   if (d->n_layers < 1 || d->n_layers > PDEC_MAX_LAYERS) return false;
@@ -1725,7 +1813,7 @@ bool decoder_persist_applicable(const astk_decoder_desc* d, int* nsplit_out, int
   if (nsplit < 1) return false;
   int chunk = (d->T + nsplit - 1) / nsplit;
   nsplit = (d->T + chunk - 1) / chunk;
-  if (chunk > 256 || d->L > 192) return false;
+  if (chunk > 256 || d->L > max_L) return false;
   {   // backward roles and register budgets
     const int XI = d->E + d->A, Vp = (d->V + 3) / 4 * 4;
     if (Vp > 64 * NB_B1 || d->A > 64 * NB_B2 || 4 * d->H > 64 * NB_B5 || (XI % 16) || ((2 * d->H) % 32)) return false;
@@ -1745,6 +1833,7 @@ bool decoder_persist_applicable(const astk_decoder_desc* d, int* nsplit_out, int
   *chunk_out = chunk;
   return true;
 }
+bool decoder_persist_applicable(const astk_decoder_desc* d, int* nsplit_out, int* chunk_out) { return pdec_applicable(d, 192, nsplit_out, chunk_out); }
 
 // d_x0 phase of the backward kernel as 2 K-halves per item over the ht columns only: fits when the roles still fit 256 workgroups
 bool decoder_persist_b6_split(const astk_decoder_desc* d) {
@@ -1780,18 +1869,18 @@ static void pdec_launch_bwd(bool special, bool xs, size_t shm, hipStream_t s, co
   else if (special) hipLaunchKernelGGL((decoder_persist_bwd<8, NL, false>), dim3(G), dim3(256), shm, s, a);
   else hipLaunchKernelGGL((decoder_persist_bwd<0, NL, false>), dim3(G), dim3(256), shm, s, a);
 }
-template <int NL>
+template <int NL, bool GR = false>
 static void pdec_launch_fwd(bool special, bool xs, size_t shm, hipStream_t s, const PDecArgs& a) {
   static bool attr_done = false;
   if (!attr_done) {
-    (void)hipFuncSetAttribute((const void*)decoder_persist_fwd<0, NL, false>, hipFuncAttributeMaxDynamicSharedMemorySize, 138 * 1024);
-    (void)hipFuncSetAttribute((const void*)decoder_persist_fwd<8, NL, false>, hipFuncAttributeMaxDynamicSharedMemorySize, 138 * 1024);
-    (void)hipFuncSetAttribute((const void*)decoder_persist_fwd<8, NL, true>, hipFuncAttributeMaxDynamicSharedMemorySize, 138 * 1024);
+    (void)hipFuncSetAttribute((const void*)decoder_persist_fwd<0, NL, false, GR>, hipFuncAttributeMaxDynamicSharedMemorySize, 138 * 1024);
+    (void)hipFuncSetAttribute((const void*)decoder_persist_fwd<8, NL, false, GR>, hipFuncAttributeMaxDynamicSharedMemorySize, 138 * 1024);
+    (void)hipFuncSetAttribute((const void*)decoder_persist_fwd<8, NL, true, GR>, hipFuncAttributeMaxDynamicSharedMemorySize, 138 * 1024);
     attr_done = true;
   }
-  if (special && xs) hipLaunchKernelGGL((decoder_persist_fwd<8, NL, true>), dim3(G), dim3(256), shm, s, a);
-  else if (special) hipLaunchKernelGGL((decoder_persist_fwd<8, NL, false>), dim3(G), dim3(256), shm, s, a);
-  else hipLaunchKernelGGL((decoder_persist_fwd<0, NL, false>), dim3(G), dim3(256), shm, s, a);
+  if (special && xs) hipLaunchKernelGGL((decoder_persist_fwd<8, NL, true, GR>), dim3(G), dim3(256), shm, s, a);
+  else if (special) hipLaunchKernelGGL((decoder_persist_fwd<8, NL, false, GR>), dim3(G), dim3(256), shm, s, a);
+  else hipLaunchKernelGGL((decoder_persist_fwd<0, NL, false, GR>), dim3(G), dim3(256), shm, s, a);
 }
 
 int decoder_persist_bwd_launch(const astk_decoder_desc* d, const float* enc, const float* rnn_masks, const DecPersistBwdBuffers& bf,
@@ -1921,6 +2010,106 @@ int decoder_persist_fwd_launch(const astk_decoder_desc* d, const astk_decoder_pa
   ASTK_TRY(gemm_launch(GEMM_NT, gemm_args(a.S * a.B, a.H, a.H, mat(bf.CVH + a.H, 2 * a.H), mat(prm->Wa, a.H), bf.Q, a.H, prm->ba), s));
   hipLaunchKernelGGL(k_decoder_post, dim3(a.S * a.B), dim3(256), 0, s, prm->embed, y, ytgt ? ytgt : y, use_truth, bf.PRED, emb_mask, bf.TOK, bf.X0, bf.LOGITS, bf.LSE,
                      prm->class_weight, bf.LOSSROWS, loss, pred_out, a.S, a.B, a.L, a.E, a.XI, a.V, a.Vp, a.inv_count, persist_status_word(), d->status_dst);
+  ASTK_LAUNCH_CHECK();
+  return 0;
+}
+
+// ---------------------------------------------------------------------------------------------------- greedy decoding
+// decoder_persist_fwd<.., GR = true> on a workspace of its own: the step-indexed hand-off buffers of the training loop, sized by the stop
+// limit, without the ones greedy mode never touches (X0, Q, G, C, ALPHA, ML, LOGITS, LSE, loss rows).
+struct GreedyPlan {
+  float *ENCA, *CVH, *HT, *PART, *CESTAT;
+  float *HR[PDEC_MAX_LAYERS], *HD[PDEC_MAX_LAYERS];
+  unsigned* ctr;           // phase counters, abort word, per-row counters, then the 4 lines of PDecArgs::gctl
+  int nsplit, chunk;
+  size_t bytes;
+};
+static size_t greedy_ctr_lines(int B) { return (size_t)NPHASE_SLOTS * NSH * ((B + 15) / 16) + 2 + B + 4; }
+
+static bool greedy_plan(const astk_decoder_desc* d0, int stop_limit, void* ws, GreedyPlan& g) {
+  if (!d0 || d0->struct_size != sizeof(astk_decoder_desc)) return false;
+  if (stop_limit < 1 || stop_limit > ASTK_GREEDY_MAX_STEPS || d0->B < 1 || d0->B > 32 || d0->T < 1 || d0->V < 2) return false;
+  astk_decoder_desc d = *d0;
+  d.L = stop_limit + 1;
+  if (!pdec_applicable(&d, ASTK_GREEDY_MAX_STEPS + 1, &g.nsplit, &g.chunk)) return false;
+  const size_t S = stop_limit, B = d.B, H = d.H;
+  Carver c(ws);
+  g.ENCA = c.take<float>(B * d.T * H);
+  g.CVH = c.take<float>(S * B * 2 * H);
+  g.HT = c.take<float>((S + 1) * B * d.A);
+  for (int l = 0; l < PDEC_MAX_LAYERS; ++l) {
+    g.HR[l] = l < d.n_layers ? c.take<float>((S + 1) * B * H) : nullptr;
+    g.HD[l] = l + 1 < d.n_layers ? c.take<float>(S * B * H) : nullptr;
+  }
+  g.PART = c.take<float>(S * B * g.nsplit * (H + 4));
+  g.CESTAT = c.take<float>(S * B * (size_t)((d.V + 15) / 16) * 4);
+  g.ctr = c.take<unsigned>(greedy_ctr_lines(d.B) * CTRS);
+  g.bytes = c.total();
+  return true;
+}
+
+size_t greedy_workspace_bytes(const astk_decoder_desc* d, int stop_limit) {
+  GreedyPlan g;
+  return greedy_plan(d, stop_limit, nullptr, g) ? g.bytes : 0;
+}
+
+int greedy_decode_launch(const astk_decoder_desc* d, const astk_decoder_params* prm, const float* enc, const float* c0, const float* h0, int go,
+                         int eos, int stop_limit, int32_t* tokens, int32_t* n_steps, float* status_dst, void* ws, size_t ws_bytes, hipStream_t s) {
+  ASTK_CHECK_DESC(d, astk_decoder_desc);
+  ASTK_CHECK(d->V > 1 && go >= 0 && go < d->V && eos >= 0 && eos < d->V, "greedy_decode: go %d / eos %d outside [0, V = %d)", go, eos, d->V);
+  ASTK_CHECK(stop_limit >= 1 && stop_limit <= ASTK_GREEDY_MAX_STEPS, "greedy_decode: stop_limit %d outside [1, %d]", stop_limit, ASTK_GREEDY_MAX_STEPS);
+  GreedyPlan g;
+  ASTK_CHECK(greedy_plan(d, stop_limit, nullptr, g), "greedy_decode: B = %d, H = %d, %d layers (or the knob dec.persist = 0) does not run on the "
+             "device loop: astk_greedy_workspace_bytes returns 0, decode with astk_decoder_step_infer", d->B, d->H, d->n_layers);
+  ASTK_CHECK(ws && ws_bytes >= g.bytes, "greedy_decode: workspace too small (%zu < %zu)", ws_bytes, g.bytes);
+  ASTK_CHECK(prm && enc && c0 && h0 && tokens && n_steps, "greedy_decode: null pointer");
+  greedy_plan(d, stop_limit, ws, g);
+  PrecScope prec_scope(d->precision, d->gemm_operands);
+  GemmForwardScope forward_scope;
+  ASTK_TRY(gemm_launch(GEMM_NN, gemm_args(d->B * d->T, d->H, d->H, mat(enc, d->H), mat(prm->Wa, d->H), g.ENCA, d->H), s));   // encA = enc . Wa
+  PDecArgs a;
+  memset(&a, 0, sizeof(a));
+  a.B = d->B; a.S = stop_limit; a.L = stop_limit + 1; a.T = d->T; a.Tp = (d->T + 3) / 4 * 4; a.H = d->H; a.E = d->E; a.A = d->A; a.V = d->V;
+  a.Vp = (d->V + 3) / 4 * 4; a.XI = d->E + d->A; a.nbt = (d->B + 15) / 16; a.nsplit = g.nsplit; a.chunk = g.chunk;
+  a.ntile_v = (d->V + 15) / 16;
+  a.inv_count = 1.f / (float)d->B;
+  a.embed = prm->embed;
+  const size_t bh = (size_t)d->B * d->H;
+  for (int l = 0; l < d->n_layers; ++l) {
+    a.Wu[l] = prm->lstm[l].Wu; a.bias[l] = prm->lstm[l].b; a.Wl[l] = prm->lstm[l].Wl;
+    a.Cst[l] = const_cast<float*>(c0 + l * bh);       // (read once: the cells keep c in a register and save no states)
+    a.HR[l] = g.HR[l]; a.HD[l] = g.HD[l];
+  }
+  a.Wa = prm->Wa; a.ba = prm->ba; a.Wc = prm->Wc; a.bc = prm->bc; a.Wo = prm->Wo; a.bo = prm->bo;
+  a.enc = enc; a.encA = g.ENCA;
+  a.PRED = tokens; a.CVH = g.CVH; a.HT = g.HT; a.PART = g.PART; a.CESTAT = g.CESTAT;
+  a.ctr = g.ctr;
+  a.ab = abort_ctl(g.ctr + (size_t)NPHASE_SLOTS * NSH * a.nbt * CTRS, PERSIST_DEC_FWD);
+  a.dbg = persist_dbg_env();
+  a.go = go; a.eos = eos;
+  a.gctl = g.ctr + (greedy_ctr_lines(d->B) - 4) * CTRS;
+  a.n_steps_out = n_steps; a.status_dst = status_dst;
+  {
+    // one fill launch: counters, abort word, tile reports and exit count to 0, the stop word to stop_limit, the sentinel hand-offs, h0
+    FillSegs f;
+    f.n = 0;
+    fill_seg_add(f, g.ctr, (greedy_ctr_lines(d->B) - 1) * CTRS * sizeof(unsigned), 0u);
+    fill_seg_add(f, a.gctl + 3 * CTRS, CTRS * sizeof(unsigned), (unsigned)stop_limit);
+#if ASTK_PDEC_SENT_H
+    fill_seg_add(f, g.CVH, (size_t)a.S * a.B * 2 * a.H * sizeof(float));
+#endif
+#if ASTK_PDEC_SENT_HD && ASTK_PDEC_SENT_H
+    for (int l = 0; l + 1 < d->n_layers; ++l) fill_seg_add(f, g.HD[l], (size_t)a.S * bh * sizeof(float));
+#endif
+    for (int l = 0; l < d->n_layers; ++l) fill_seg_add_copy(f, g.HR[l], h0 + l * bh, bh * sizeof(float));
+    ASTK_TRY(fill_u32_segments(f, PDEC_SENTINEL, s));
+  }
+  const size_t shm = pdec_lds_floats(g.chunk, a.H, g.nsplit) * sizeof(float);
+  const bool special = pdec_special(a.H, g.chunk);
+  const bool xs = special && g.chunk > PDEC_RES_ROWS;
+  if (d->n_layers == 1) pdec_launch_fwd<1, true>(special, xs, shm, s, a);
+  else if (d->n_layers == 2) pdec_launch_fwd<2, true>(special, xs, shm, s, a);
+  else pdec_launch_fwd<3, true>(special, xs, shm, s, a);
   ASTK_LAUNCH_CHECK();
   return 0;
 }

@@ -316,10 +316,22 @@ class NN:
     def predict(self, set_key):
         preds = []
         stop_limit = self.cfg.train["data"]["max_pred"]
+        # Like train_epoch's loss: the tokens of batch i are read after batch i+1 has been enqueued (two alternating read-back buffers,
+        # SpeechEncoderDecoder.predict_async), so the device never waits for the host; the predictions are the same.
+        pending = None
+
+        def settle(p):
+            utts, n, handle = p
+            preds.extend(zip(utts, handle.result().tolist()))
+            pbar.update(n)
         with tqdm(total=self.data_loader.n_utts[set_key], ncols=80, disable=adist.rank() != 0) as pbar:
-            for batch in self.data_loader.get_batch(self.cfg.train["batch_size"], set_key, train=False, labels=False):
+            for i, batch in enumerate(self.data_loader.get_batch(self.cfg.train["batch_size"], set_key, train=False, labels=False)):
                 with using_config("train", False):
-                    p = self.model.predict(batch["X"], SYMBOLS.GO_ID, SYMBOLS.EOS_ID, stop_limit)
-                    preds.extend(zip(batch["utts"], p.tolist()))
-                pbar.update(len(batch["X"]))
+                    cur = (batch["utts"], len(batch["X"]),
+                           self.model.predict_async(batch["X"], SYMBOLS.GO_ID, SYMBOLS.EOS_ID, stop_limit, slot=i % 2))
+                if pending is not None:
+                    settle(pending)
+                pending = cur
+            if pending is not None:
+                settle(pending)
         return preds

@@ -159,6 +159,29 @@ class Loss:
         return float(self.data)
 
 
+class _PendingPredict:
+    """SpeechEncoderDecoder.predict_async on the device path: [n_steps, status word, 2 pad words, tokens (stop_limit, B)] on their way
+    into pinned memory.  result() waits for that copy and returns the (B, n_steps) int32 predictions."""
+
+    def __init__(self, host, event, B):
+        self.host, self.event, self.B = host, event, B
+
+    def result(self):
+        self.event.synchronize()
+        v = self.host.numpy()
+        raise_if_aborted(v[1:2].view(np.float32)[0], "predict")
+        n = int(v[0])
+        return v[4:4 + n * self.B].reshape(n, self.B).T.copy()
+
+
+class _Ready:
+    def __init__(self, value):
+        self.value = value
+
+    def result(self):
+        return self.value
+
+
 def _vp(t):
     return None if t is None else C.c_void_p(t.data_ptr())
 
@@ -225,6 +248,8 @@ class SpeechEncoderDecoder:
         self._side = None
         self._side_by_main = {}
         self.mask_pad_id = None
+        self._greedy_pinned = {}        # predict_async: pinned read-back buffers per slot
+        self.last_predict_path = None   # "device" (astk_greedy_decode) | "steps" (the per-step loop): which path the last predict() took
         # Arithmetic of the batched products, per model (-> the descriptors' `precision` / `gemm_operands` fields): None = the library's
         # process-wide default (bf16x3: exact f32 operands on the 16-bit matrix pipe); "bf16x3" | "f32" | "fp16x2" (narrower, opt-in);
         # gemm_operands "fp16" = single-term fp16 operands for the eligible products (BASELINE configs[4]; reduced precision).
@@ -841,12 +866,54 @@ class SpeechEncoderDecoder:
         return logits, ht, alpha.unsqueeze(2)
 
     def predict(self, X, start_token, end_token, stop_limit):
+        return self.predict_async(X, start_token, end_token, stop_limit).result()
+
+    def predict_async(self, X, start_token, end_token, stop_limit, slot=0):
+        """predict() with the read-back left to the caller: returns a handle whose result() is predict()'s array.  On the device path
+        (include/astk.h astk_greedy_decode: the whole decode in one persistent launch) the tokens, n_steps and the status word come back
+        in ONE copy into pinned buffer `slot` (0 or 1), which result() waits for: a caller that enqueues the next batch before it reads this
+        one keeps the device busy (NN.predict alternates the slots).  Shapes the library does not run on the device loop (it reports a
+        workspace of 0) take the per-step loop, which finishes before this returns.  `last_predict_path` says which path ran."""
         with using_config("train", False):
             X = self._as_input(X)
-            B = X.shape[0]
             self._cur = None
             self.encode(X)
             self.init_decoder_state()
+            handle = self._greedy_device(start_token, end_token, stop_limit, slot)
+            if handle is not None:
+                self.last_predict_path = "device"
+                return handle
+            self.last_predict_path = "steps"
+            return _Ready(self._predict_steps(start_token, end_token, stop_limit))
+
+    def _greedy_device(self, start_token, end_token, stop_limit, slot):
+        lib = _lib.load()
+        st = self._cur
+        B = st["B"]
+        nbytes = int(lib.astk_greedy_workspace_bytes(C.byref(st["dd"]), int(stop_limit)))
+        if nbytes == 0:
+            return None
+        ws = self._workspace("greedy", nbytes)
+        # [n_steps, status word (float), 2 pad words, tokens (stop_limit, B)]: one device buffer, read back in one copy
+        n = 4 + int(stop_limit) * B
+        out = self._pool(f"greedy_out{slot}", (n,), torch.int32)
+        host = self._greedy_pinned.get(slot)
+        if host is None or host.numel() < n:
+            host = self._greedy_pinned[slot] = torch.empty(n, dtype=torch.int32, pin_memory=True)
+        host = host[:n]
+        base = out.data_ptr()
+        check(lib.astk_greedy_decode(C.byref(st["dd"]), C.byref(st["dp"]), _vp(st["enc_states"]), _vp(self._dec_c), _vp(self._dec_h),
+                                     int(start_token), int(end_token), int(stop_limit), C.c_void_p(base + 16), C.c_void_p(base),
+                                     C.c_void_p(base + 4), _vp(ws), ws.numel(), self._stream()))
+        host.copy_(out, non_blocking=True)
+        ev = torch.cuda.Event()
+        ev.record(torch.cuda.current_stream(self.device))
+        return _PendingPredict(host, ev, B)
+
+    def _predict_steps(self, start_token, end_token, stop_limit):
+        """The per-step greedy loop (seq2seq.py:475-527): one astk_decoder_step_infer, an argmax and a host read per token."""
+        with using_config("train", False):
+            B = self._cur["B"]
             ht = torch.zeros(B, self.A, dtype=torch.float32, device=self.device)
             word = torch.full((B,), start_token, dtype=torch.int32, device=self.device)
             done = torch.zeros(B, dtype=torch.bool, device=self.device)

@@ -378,6 +378,27 @@ int astk_decoder_step_infer(const astk_decoder_desc* d, const astk_decoder_param
                             float* c, float* h, float* ht, const int32_t* tokens, float* logits, float* alpha,
                             int32_t* argmax, void* ws, size_t ws_bytes, void* stream);
 
+/* ---------------------------------------------------------------- greedy decoding on the device  (seq2seq.py:475-527, predict)
+ * The whole eval-mode greedy decode of a batch in ONE persistent launch (the persistent decoder loop in its greedy mode, after a
+ * fill launch and the encA product): step 0 feeds `go` to every row, every later step the row's own argmax (first maximum).  Stop
+ * rule, the reference's: a row is done from the first step whose argmax is `eos` and stays done, but keeps decoding (its later
+ * tokens are defined output); the decode ends after n_steps = the first step count s+1 at which every row is done, or stop_limit.
+ * Runs where the persistent training loop runs (astk_decoder_path != 0 for the same shape, with the step count set to stop_limit)
+ * and the tuning knob dec.persist is on, for B <= 32 and stop_limit <= ASTK_GREEDY_MAX_STEPS; otherwise
+ * astk_greedy_workspace_bytes returns 0 and the caller decodes with astk_decoder_step_infer step by step.  d->L and d->status_dst
+ * are ignored. */
+#define ASTK_GREEDY_MAX_STEPS 512
+size_t astk_greedy_workspace_bytes(const astk_decoder_desc* d, int stop_limit);
+/* enc (B,T,H), c0/h0 (n_layers,B,H) as for astk_decoder_fwd; tokens (stop_limit,B) int32 device, rows [0, *n_steps) defined (rows at
+ * and past n_steps: unspecified); n_steps: one device int32; status_dst (optional, NULL = none): a copy of the persistent kernels'
+ * status word as a float (see astk_persist_status_snapshot), written by the launch -- non-zero: a bounded spin timed out and the
+ * tokens are invalid.  n_steps and status_dst are written by the last workgroup to finish.  Returns < 0 with a message (and launches
+ * nothing) for a wrong struct_size, go / eos outside [0, V), stop_limit outside [1, ASTK_GREEDY_MAX_STEPS], a shape that does not
+ * run on the device loop, a null pointer or a workspace below astk_greedy_workspace_bytes. */
+int astk_greedy_decode(const astk_decoder_desc* d, const astk_decoder_params* p, const float* enc, const float* c0, const float* h0,
+                       int go, int eos, int stop_limit, int32_t* tokens, int32_t* n_steps, float* status_dst,
+                       void* ws, size_t ws_bytes, void* stream);
+
 /* ---------------------------------------------------------------- batched beam search  (nn.py:235-322 over many utterances)
  * U utterances, N hypotheses kept per utterance, K candidates per live hypothesis: every slot is one row of ONE decoder step over
  * R = U*N rows, row u*N + j = slot j of utterance u.  enc is (U, T, H): utterance u's encoder states in enc[u, 0:T''_u] (the rest
