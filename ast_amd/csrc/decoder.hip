@@ -47,6 +47,10 @@ bool decoder_persist_b6_split(const astk_decoder_desc* d);
 size_t greedy_workspace_bytes(const astk_decoder_desc* d, int stop_limit);
 int greedy_decode_launch(const astk_decoder_desc* d, const astk_decoder_params* prm, const float* enc, const float* c0, const float* h0, int go,
                          int eos, int stop_limit, int32_t* tokens, int32_t* n_steps, float* status_dst, void* ws, size_t ws_bytes, hipStream_t s);
+size_t greedy_scored_workspace_bytes(const astk_decoder_desc* d, int stop_limit);
+int greedy_decode_scored_launch(const astk_decoder_desc* d, const astk_decoder_params* prm, const float* enc, const float* c0, const float* h0,
+                                int go, int eos, int stop_limit, const int32_t* y, int ldy, const float* class_weight, int32_t* tokens,
+                                float* logp, float* nll, int32_t* n_steps, float* status_dst, void* ws, size_t ws_bytes, hipStream_t s);
 int decoder_persist_bwd_launch(const astk_decoder_desc* d, const float* enc, const float* rnn_masks, const DecPersistBwdBuffers& bf,
                                hipStream_t s);
 
@@ -975,6 +979,15 @@ int astk_greedy_decode(const astk_decoder_desc* d, const astk_decoder_params* p,
                        int go, int eos, int stop_limit, int32_t* tokens, int32_t* n_steps, float* status_dst,
                        void* ws, size_t ws_bytes, void* stream) {
   return greedy_decode_launch(d, p, enc, c0, h0, go, eos, stop_limit, tokens, n_steps, status_dst, ws, ws_bytes, (hipStream_t)stream);
+}
+
+size_t astk_greedy_scored_workspace_bytes(const astk_decoder_desc* d, int stop_limit) { return greedy_scored_workspace_bytes(d, stop_limit); }
+
+int astk_greedy_decode_scored(const astk_decoder_desc* d, const astk_decoder_params* p, const float* enc, const float* c0, const float* h0,
+                              int go, int eos, int stop_limit, const int32_t* y, int ldy, const float* class_weight, int32_t* tokens,
+                              float* logp, float* nll, int32_t* n_steps, float* status_dst, void* ws, size_t ws_bytes, void* stream) {
+  return greedy_decode_scored_launch(d, p, enc, c0, h0, go, eos, stop_limit, y, ldy, class_weight, tokens, logp, nll, n_steps, status_dst, ws,
+                                     ws_bytes, (hipStream_t)stream);
 }
 
 }  // extern "C"

@@ -89,6 +89,8 @@ struct PDecArgs {
   int dbg;
   float* tick_out;         // profiler: [G] accumulated attention-phase microseconds per workgroup, [G+0] launches
   // greedy mode (GR): feed `go` at step 0, stop once every row has emitted `eos` (S = the stop limit; PRED = the caller's tokens)
+  // scored greedy mode (SC) reuses training fields: LSE = LOGP [S][B], LOSSROWS = NLL [S][B] or null, ytgt = targets [B][L] or null
+  // (L = their row length, column s+1 scored at step s; steps with s+1 >= L have none), cw = class weights or null
   int go, eos;
   unsigned* gctl;          // 4 counter lines: [0] max over batch tiles of the step their last row finished, [1] tiles reported,
                            // [2] workgroups that left, [3] the stop word (n_steps; preset to S)
@@ -317,8 +319,14 @@ __device__ __forceinline__ void mfma_blocks(f32x4& acc, const float4* a, const f
 // tile is all done it reports that step (atomic max, then one arrival), and the tile that completes the count writes the stop word
 // n_steps = max + 1 before its PH_CE arrival of that step.  The layer-0 cells read the stop word behind that arrival and leave at
 // step n_steps; every other wait learns of it in its slow path (StopCtl).  DESIGN.md section 11.
-template <int NC, int NL, bool XS, bool GR>
+// SC (with GR): scored greedy decoding.  P5 also keeps the tile's sum of exponentials and, with targets, the target logit; P6 merges the
+// sums as the training mode does and stores, beside the token, the log-probability of that token and the weighted negative
+// log-likelihood of the target (PDecArgs: LSE = LOGP, LOSSROWS = NLL, ytgt / L / cw).  Two more plain stores in front of the vmcnt(0)
+// and the barrier that the token store already had: no wait, arrival, counter or exit condition is added.  DESIGN.md section 12.
+template <int NC, int NL, bool XS, bool GR, bool SC = false>
 __device__ __forceinline__ void decoder_persist_fwd_body(const PDecArgs& a) {
+  static_assert(GR || !SC, "the scored mode is a greedy mode");
+  constexpr bool SUMS = !GR || SC;         // P5 / P6 keep the sum of exponentials and the target logit
   extern __shared__ __attribute__((aligned(16))) float lds[];   // enc slice [chunk][H], encA slice [chunk][H], scratch
   __shared__ __attribute__((aligned(16))) float red[4 * 256];
   __shared__ __attribute__((aligned(16))) float zt[2 * 256];
@@ -479,8 +487,19 @@ __device__ __forceinline__ void decoder_persist_fwd_body(const PDecArgs& a) {
   bool tile_done = false;                             // GR, CE role (thread 0): this batch tile has reported
   auto run_p6 = [&](const int s) -> bool {
       const int bt = ce_rank, m0 = bt * 16;
-      if (!wg_wait_sh(CTR(PH_LOG, bt), a.ntile_v, s + 1, a.ab, &s_flag, StopCtl{GR ? a.gctl + 3 * CTRS : nullptr, s, false})) return false;
       const int row = m0 + (tid >> 4), sub = tid & 15;       // 16 threads per row sweep the tiles
+      [[maybe_unused]] bool sc_tgt = false;                  // SC: step s has a target (column s+1 of y); its class weight
+      [[maybe_unused]] float sc_w = 0.f;
+      if constexpr (SC) {       // (read in front of the wait: neither load is on the chain)
+        sc_tgt = a.ytgt && s + 1 < a.L;
+        if (sc_tgt && sub == 0 && row < B) {
+          int r = row;
+          asm volatile("" : "+v"(r));       // (keeps the address out of the loop-invariant registers: they are full, it would spill)
+          const int tgt = *ua(a.ytgt + s + 1, (unsigned)(r * a.L));
+          sc_w = a.cw ? a.cw[tgt < 0 ? 0 : (tgt >= V ? V - 1 : tgt)] : 1.f;
+        }
+      }
+      if (!wg_wait_sh(CTR(PH_LOG, bt), a.ntile_v, s + 1, a.ab, &s_flag, StopCtl{GR ? a.gctl + 3 * CTRS : nullptr, s, false})) return false;
       float mx = -INFINITY, se = 0.f, xt = 0.f;
       int mi = 0x7fffffff;
       if (row < B)
@@ -489,7 +508,7 @@ __device__ __forceinline__ void decoder_persist_fwd_body(const PDecArgs& a) {
           const float tm = cs.x, ts = cs.y, tx = cs.w;
           const int ti = __float_as_int(cs.z);
           const float nm = fmaxf(mx, tm);
-          if constexpr (!GR) se = se * expf(mx - nm) + ts * expf(tm - nm);
+          if constexpr (SUMS) se = se * expf(mx - nm) + ts * expf(tm - nm);
           if (tm > mx || (tm == mx && ti < mi)) mi = ti;
           mx = nm;
           xt += tx;
@@ -499,13 +518,24 @@ __device__ __forceinline__ void decoder_persist_fwd_body(const PDecArgs& a) {
         const float om = __shfl_xor(mx, o), os = __shfl_xor(se, o), ox = __shfl_xor(xt, o);
         const int oi = __shfl_xor(mi, o);
         const float nm = fmaxf(mx, om);
-        if constexpr (!GR) se = (mx == -INFINITY ? 0.f : se * expf(mx - nm)) + (om == -INFINITY ? 0.f : os * expf(om - nm));
+        if constexpr (SUMS) se = (mx == -INFINITY ? 0.f : se * expf(mx - nm)) + (om == -INFINITY ? 0.f : os * expf(om - nm));
         if (om > mx || (om == mx && oi < mi)) mi = oi;
         mx = nm;
         xt += ox;
       }
       if constexpr (GR) {
-        if (sub == 0 && row < B) {
+        if constexpr (SC) {
+          if (sub == 0 && row < B) {
+            // lse = mx + logf(se): log p(token) = mx - lse and the target's -log p = lse - xt, formed without rounding lse first
+            const float lg = logf(se);
+            int r = row;
+            asm volatile("" : "+v"(r));     // (as above)
+            *ua(a.LSE + (long)s * B, (unsigned)r) = -lg;
+            if (a.LOSSROWS) *ua(a.LOSSROWS + (long)s * B, (unsigned)r) = sc_tgt ? sc_w * ((mx - xt) + lg) : 0.f;
+            sti_sc1(ua(a.PRED + (long)s * B, (unsigned)r), mi);
+            row_done = row_done || mi == a.eos;
+          }
+        } else if (sub == 0 && row < B) {
           sti_sc1(ua(a.PRED + (long)s * B, (unsigned)row), mi);
           row_done = row_done || mi == a.eos;
         }
@@ -1039,6 +1069,12 @@ __device__ __forceinline__ void decoder_persist_fwd_body(const PDecArgs& a) {
       if (l_item[t] < 0) continue;
       const int bt = l_item[t] / a.ntile_v, tile = l_item[t] % a.ntile_v, m0 = bt * 16, n0 = tile * 16;
       TICK(15)
+      [[maybe_unused]] int sc_tgt = -1;          // SC: this row's target of step s, read in front of the wait (-1: none)
+      if constexpr (SC) {
+        int r = m0 + (tid >> 4);
+        asm volatile("" : "+v"(r));         // (keeps the address out of the loop-invariant registers: they are full, it would spill)
+        if (a.ytgt && s + 1 < a.L && r < B) sc_tgt = *ua(a.ytgt + s + 1, (unsigned)(r * a.L));
+      }
       if (!wg_wait_sh(CTR(PH_CTX, bt), A / 16, s + 1, a.ab, &s_flag, sc)) return;
       TICK(10)
       f32x4 acc = {0.f, 0.f, 0.f, 0.f};
@@ -1060,11 +1096,13 @@ __device__ __forceinline__ void decoder_persist_fwd_body(const PDecArgs& a) {
         if (om > mx || (om == mx && oi < mi)) { mx = om; mi = oi; }
       }
       float se = 0.f, xt = 0.f;
-      if constexpr (!GR) {
+      if constexpr (SUMS) {
         se = ok ? expf(x - mx) : 0.f;
 #pragma unroll
         for (int o = 8; o > 0; o >>= 1) se += __shfl_xor(se, o);
-        const int tgt = row < B ? *ua(a.ytgt + s + 1, (unsigned)(row * a.L)) : 0;
+        int tgt;
+        if constexpr (SC) tgt = sc_tgt;
+        else tgt = row < B ? *ua(a.ytgt + s + 1, (unsigned)(row * a.L)) : 0;
         xt = (ok && n == tgt) ? x : 0.f;
 #pragma unroll
         for (int o = 8; o > 0; o >>= 1) xt += __shfl_xor(xt, o);
@@ -1107,18 +1145,27 @@ __device__ __forceinline__ void decoder_persist_fwd_body(const PDecArgs& a) {
 #undef ROWCTR
 }
 
+// greedy modes: the last workgroup to leave -- after every stop, abort or time-out of the launch -- writes n_steps and the status copy
+__device__ __forceinline__ void greedy_last_out(const PDecArgs& a) {
+  asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+  __syncthreads();
+  if (threadIdx.x == 0 && __hip_atomic_fetch_add(a.gctl + 2 * CTRS, 1u, __ATOMIC_ACQ_REL, __HIP_MEMORY_SCOPE_AGENT) + 1 == (unsigned)G) {
+    *a.n_steps_out = (int32_t)__hip_atomic_load(a.gctl + 3 * CTRS, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    if (a.status_dst) *a.status_dst = (float)__hip_atomic_load(a.ab.status, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+  }
+}
+
 template <int NC, int NL, bool XS, bool GR>
 __global__ __launch_bounds__(256, 1) void decoder_persist_fwd(PDecArgs a) {
   decoder_persist_fwd_body<NC, NL, XS, GR>(a);     // (every return in it is workgroup-uniform)
-  if constexpr (GR) {
-    // the last workgroup to leave -- after every stop, abort or time-out of the launch -- writes n_steps and the status copy
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    __syncthreads();
-    if (threadIdx.x == 0 && __hip_atomic_fetch_add(a.gctl + 2 * CTRS, 1u, __ATOMIC_ACQ_REL, __HIP_MEMORY_SCOPE_AGENT) + 1 == (unsigned)G) {
-      *a.n_steps_out = (int32_t)__hip_atomic_load(a.gctl + 3 * CTRS, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-      if (a.status_dst) *a.status_dst = (float)__hip_atomic_load(a.ab.status, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    }
-  }
+  if constexpr (GR) greedy_last_out(a);
+}
+
+// The scored greedy mode as a kernel of its own: the instantiations above keep their names and their code.
+template <int NC, int NL, bool XS>
+__global__ __launch_bounds__(256, 1) void decoder_persist_greedy_scored(PDecArgs a) {
+  decoder_persist_fwd_body<NC, NL, XS, true, true>(a);
+  greedy_last_out(a);
 }
 
 // =====================================================================================================================
@@ -1869,6 +1916,19 @@ static void pdec_launch_bwd(bool special, bool xs, size_t shm, hipStream_t s, co
   else if (special) hipLaunchKernelGGL((decoder_persist_bwd<8, NL, false>), dim3(G), dim3(256), shm, s, a);
   else hipLaunchKernelGGL((decoder_persist_bwd<0, NL, false>), dim3(G), dim3(256), shm, s, a);
 }
+template <int NL>
+static void pdec_launch_scored(bool special, bool xs, size_t shm, hipStream_t s, const PDecArgs& a) {
+  static bool attr_done = false;
+  if (!attr_done) {
+    (void)hipFuncSetAttribute((const void*)decoder_persist_greedy_scored<0, NL, false>, hipFuncAttributeMaxDynamicSharedMemorySize, 138 * 1024);
+    (void)hipFuncSetAttribute((const void*)decoder_persist_greedy_scored<8, NL, false>, hipFuncAttributeMaxDynamicSharedMemorySize, 138 * 1024);
+    (void)hipFuncSetAttribute((const void*)decoder_persist_greedy_scored<8, NL, true>, hipFuncAttributeMaxDynamicSharedMemorySize, 138 * 1024);
+    attr_done = true;
+  }
+  if (special && xs) hipLaunchKernelGGL((decoder_persist_greedy_scored<8, NL, true>), dim3(G), dim3(256), shm, s, a);
+  else if (special) hipLaunchKernelGGL((decoder_persist_greedy_scored<8, NL, false>), dim3(G), dim3(256), shm, s, a);
+  else hipLaunchKernelGGL((decoder_persist_greedy_scored<0, NL, false>), dim3(G), dim3(256), shm, s, a);
+}
 template <int NL, bool GR = false>
 static void pdec_launch_fwd(bool special, bool xs, size_t shm, hipStream_t s, const PDecArgs& a) {
   static bool attr_done = false;
@@ -2053,8 +2113,19 @@ size_t greedy_workspace_bytes(const astk_decoder_desc* d, int stop_limit) {
   return greedy_plan(d, stop_limit, nullptr, g) ? g.bytes : 0;
 }
 
-int greedy_decode_launch(const astk_decoder_desc* d, const astk_decoder_params* prm, const float* enc, const float* c0, const float* h0, int go,
-                         int eos, int stop_limit, int32_t* tokens, int32_t* n_steps, float* status_dst, void* ws, size_t ws_bytes, hipStream_t s) {
+// (the scored mode needs no workspace of its own: LOGP and NLL are the caller's)
+size_t greedy_scored_workspace_bytes(const astk_decoder_desc* d, int stop_limit) { return greedy_workspace_bytes(d, stop_limit); }
+
+// the scored mode's arguments
+struct GreedyScoredIO {
+  const int32_t* y; int ldy;       // targets [B][ldy] or null
+  const float* class_weight;       // [V] or null = all 1
+  float *logp, *nll;               // [stop_limit][B]; nll null iff y is null
+};
+// sc: null for the unscored kernel
+static int greedy_launch(const astk_decoder_desc* d, const astk_decoder_params* prm, const float* enc, const float* c0, const float* h0, int go,
+                         int eos, int stop_limit, const GreedyScoredIO* sc, int32_t* tokens, int32_t* n_steps, float* status_dst, void* ws,
+                         size_t ws_bytes, hipStream_t s) {
   ASTK_CHECK_DESC(d, astk_decoder_desc);
   ASTK_CHECK(d->V > 1 && go >= 0 && go < d->V && eos >= 0 && eos < d->V, "greedy_decode: go %d / eos %d outside [0, V = %d)", go, eos, d->V);
   ASTK_CHECK(stop_limit >= 1 && stop_limit <= ASTK_GREEDY_MAX_STEPS, "greedy_decode: stop_limit %d outside [1, %d]", stop_limit, ASTK_GREEDY_MAX_STEPS);
@@ -2063,6 +2134,12 @@ int greedy_decode_launch(const astk_decoder_desc* d, const astk_decoder_params* 
              "device loop: astk_greedy_workspace_bytes returns 0, decode with astk_decoder_step_infer", d->B, d->H, d->n_layers);
   ASTK_CHECK(ws && ws_bytes >= g.bytes, "greedy_decode: workspace too small (%zu < %zu)", ws_bytes, g.bytes);
   ASTK_CHECK(prm && enc && c0 && h0 && tokens && n_steps, "greedy_decode: null pointer");
+  if (sc) {
+    ASTK_CHECK(sc->logp, "greedy_decode_scored: null pointer (logp)");
+    ASTK_CHECK((sc->y != nullptr) == (sc->nll != nullptr), "greedy_decode_scored: nll goes with y (%s given without %s)",
+               sc->y ? "y" : "nll", sc->y ? "nll" : "y");
+    ASTK_CHECK(!sc->y || sc->ldy >= 1, "greedy_decode_scored: ldy %d < 1", sc->ldy);
+  }
   greedy_plan(d, stop_limit, ws, g);
   PrecScope prec_scope(d->precision, d->gemm_operands);
   GemmForwardScope forward_scope;
@@ -2089,6 +2166,9 @@ int greedy_decode_launch(const astk_decoder_desc* d, const astk_decoder_params* 
   a.go = go; a.eos = eos;
   a.gctl = g.ctr + (greedy_ctr_lines(d->B) - 4) * CTRS;
   a.n_steps_out = n_steps; a.status_dst = status_dst;
+  if (sc) {
+    a.LSE = sc->logp; a.LOSSROWS = sc->nll; a.ytgt = sc->y; a.L = sc->y ? sc->ldy : 1; a.cw = sc->class_weight;
+  }
   {
     // one fill launch: counters, abort word, tile reports and exit count to 0, the stop word to stop_limit, the sentinel hand-offs, h0
     FillSegs f;
@@ -2107,11 +2187,29 @@ int greedy_decode_launch(const astk_decoder_desc* d, const astk_decoder_params* 
   const size_t shm = pdec_lds_floats(g.chunk, a.H, g.nsplit) * sizeof(float);
   const bool special = pdec_special(a.H, g.chunk);
   const bool xs = special && g.chunk > PDEC_RES_ROWS;
-  if (d->n_layers == 1) pdec_launch_fwd<1, true>(special, xs, shm, s, a);
-  else if (d->n_layers == 2) pdec_launch_fwd<2, true>(special, xs, shm, s, a);
-  else pdec_launch_fwd<3, true>(special, xs, shm, s, a);
+  if (sc) {
+    if (d->n_layers == 1) pdec_launch_scored<1>(special, xs, shm, s, a);
+    else if (d->n_layers == 2) pdec_launch_scored<2>(special, xs, shm, s, a);
+    else pdec_launch_scored<3>(special, xs, shm, s, a);
+  } else {
+    if (d->n_layers == 1) pdec_launch_fwd<1, true>(special, xs, shm, s, a);
+    else if (d->n_layers == 2) pdec_launch_fwd<2, true>(special, xs, shm, s, a);
+    else pdec_launch_fwd<3, true>(special, xs, shm, s, a);
+  }
   ASTK_LAUNCH_CHECK();
   return 0;
+}
+
+int greedy_decode_launch(const astk_decoder_desc* d, const astk_decoder_params* prm, const float* enc, const float* c0, const float* h0, int go,
+                         int eos, int stop_limit, int32_t* tokens, int32_t* n_steps, float* status_dst, void* ws, size_t ws_bytes, hipStream_t s) {
+  return greedy_launch(d, prm, enc, c0, h0, go, eos, stop_limit, nullptr, tokens, n_steps, status_dst, ws, ws_bytes, s);
+}
+
+int greedy_decode_scored_launch(const astk_decoder_desc* d, const astk_decoder_params* prm, const float* enc, const float* c0, const float* h0,
+                                int go, int eos, int stop_limit, const int32_t* y, int ldy, const float* class_weight, int32_t* tokens,
+                                float* logp, float* nll, int32_t* n_steps, float* status_dst, void* ws, size_t ws_bytes, hipStream_t s) {
+  const GreedyScoredIO sc{y, ldy, class_weight, logp, nll};
+  return greedy_launch(d, prm, enc, c0, h0, go, eos, stop_limit, &sc, tokens, n_steps, status_dst, ws, ws_bytes, s);
 }
 
 }  // namespace astk

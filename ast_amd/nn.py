@@ -335,3 +335,31 @@ class NN:
             if pending is not None:
                 settle(pending)
         return preds
+
+    def predict_scored(self, set_key):
+        """predict() with the dev loss of the reference's older trainer and a score per hypothesis: returns (preds, dev_loss, scores).
+        `preds` is what predict() returns; dev_loss = the mean over the batches of (the free-running cross-entropy summed over the decoded
+        steps / the padded target length) (nmt_run.py:543, 558-560; SpeechEncoderDecoder.predict_scored); scores = (utt, log-probability of
+        the hypothesis up to and including its first EOS) pairs.  Read one batch late like predict()."""
+        preds, scores, losses = [], [], []
+        stop_limit = self.cfg.train["data"]["max_pred"]
+        pending = None
+
+        def settle(p):
+            utts, n, L, handle = p
+            r = handle.result()
+            preds.extend(zip(utts, r.tokens.tolist()))
+            scores.extend(zip(utts, r.score.tolist()))
+            losses.append(r.loss / L)
+            pbar.update(n)
+        with tqdm(total=self.data_loader.n_utts[set_key], ncols=80, disable=adist.rank() != 0) as pbar:
+            for i, batch in enumerate(self.data_loader.get_batch(self.cfg.train["batch_size"], set_key, train=False, labels=True)):
+                with using_config("train", False):
+                    cur = (batch["utts"], len(batch["X"]), int(batch["y"].shape[1]),
+                           self.model.predict_scored_async(batch["X"], SYMBOLS.GO_ID, SYMBOLS.EOS_ID, stop_limit, batch["y"], slot=i % 2))
+                if pending is not None:
+                    settle(pending)
+                pending = cur
+            if pending is not None:
+                settle(pending)
+        return preds, (sum(losses) / len(losses) if losses else 0.0), scores

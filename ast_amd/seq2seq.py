@@ -174,6 +174,46 @@ class _PendingPredict:
         return v[4:4 + n * self.B].reshape(n, self.B).T.copy()
 
 
+class ScoredPrediction:
+    """What predict_scored returns: `tokens` (B, n_steps) int32 exactly as predict() returns them, `logp` (B, n_steps) float32 the
+    log-probability of each emitted token, `nll` (B, n_steps) float32 the class-weighted negative log-likelihood of the target of each
+    step (0 where a step has no target; None without targets), `n_steps`, and the two reductions (float64, on the host):
+      loss     = sum over the steps of the mean over the B rows of nll -- the free-running dev loss of the reference's older trainer
+                 (enc_dec.py:372-429: rows that have emitted EOS keep contributing, PAD targets weigh 0); None without targets;
+      score[b] = sum of logp[b, :k], k = the position of row b's first `end_token` plus one, or n_steps."""
+
+    def __init__(self, tokens, logp, nll, end_token):
+        self.tokens, self.logp, self.nll = tokens, logp, nll
+        self.n_steps = int(tokens.shape[1])
+        self.loss = None if nll is None else float(nll.astype(np.float64).sum(axis=0).sum() / max(tokens.shape[0], 1))
+        is_end = tokens == end_token
+        k = np.where(is_end.any(axis=1), is_end.argmax(axis=1) + 1, self.n_steps)
+        keep = np.arange(self.n_steps)[None, :] < k[:, None]
+        self.score = np.where(keep, logp.astype(np.float64), 0.0).sum(axis=1)
+
+
+def scored_from_rows(words, n_steps, B, stop_limit, has_nll, end_token):
+    """The read-back words of a scored greedy decode -- step-major [tokens | logp | nll], each (stop_limit, B), the last two float32
+    bit patterns -- cut to the first n_steps steps and reduced (ScoredPrediction)."""
+    n, sb = int(n_steps), int(stop_limit) * B
+    rows = lambda k: words[k * sb:k * sb + n * B].reshape(n, B).T.copy()
+    return ScoredPrediction(rows(0), rows(1).view(np.float32), rows(2).view(np.float32) if has_nll else None, end_token)
+
+
+class _PendingScored:
+    """predict_scored_async on the device path: [n_steps, status word, 2 pad words, tokens, logp, nll] on their way into pinned memory."""
+
+    def __init__(self, host, event, B, stop_limit, has_nll, end_token, keep):
+        self.host, self.event, self.args, self.keep = host, event, (B, stop_limit, has_nll, end_token), keep
+
+    def result(self):
+        self.event.synchronize()
+        self.keep = None
+        v = self.host.numpy()
+        raise_if_aborted(v[1:2].view(np.float32)[0], "predict_scored")
+        return scored_from_rows(v[4:], int(v[0]), *self.args)
+
+
 class _Ready:
     def __init__(self, value):
         self.value = value
@@ -909,6 +949,87 @@ class SpeechEncoderDecoder:
         ev = torch.cuda.Event()
         ev.record(torch.cuda.current_stream(self.device))
         return _PendingPredict(host, ev, B)
+
+    def predict_scored(self, X, start_token, end_token, stop_limit, y=None):
+        """predict() that also scores what it decodes: a ScoredPrediction (tokens as predict() returns them, the log-probability of each
+        emitted token, and -- with targets y (B, L) -- the free-running cross-entropy of every step against y[:, s+1] and its sum, the
+        dev loss).  The decode is predict()'s in every case (up to stop_limit steps, all-EOS early stop): steps past L - 1 have no
+        target and add 0, so `loss` is the value of the reference's loop, which stops at L - 1 (enc_dec.py:384-385)."""
+        return self.predict_scored_async(X, start_token, end_token, stop_limit, y).result()
+
+    def predict_scored_async(self, X, start_token, end_token, stop_limit, y=None, slot=0):
+        """predict_scored with the read-back left to the caller, like predict_async: on the device path (astk_greedy_decode_scored) ONE
+        copy of [n_steps, status, tokens, logp, nll] into pinned buffer `slot`; otherwise the per-step loop, finished on return."""
+        with using_config("train", False):
+            X = self._as_input(X)
+            self._cur = None
+            self.encode(X)
+            self.init_decoder_state()
+            if y is not None:
+                y = torch.as_tensor(y).to(self.device, torch.int32).contiguous()
+                if y.dim() != 2 or y.shape[0] != self._cur["B"] or y.shape[1] < 1:
+                    raise ValueError(f"predict_scored: y must be (B = {self._cur['B']}, L >= 1), got {tuple(y.shape)}")
+            handle = self._greedy_scored_device(start_token, end_token, stop_limit, y, slot)
+            if handle is not None:
+                self.last_predict_path = "device"
+                return handle
+            self.last_predict_path = "steps"
+            return _Ready(self._predict_scored_steps(start_token, end_token, stop_limit, y))
+
+    def _greedy_scored_device(self, start_token, end_token, stop_limit, y, slot):
+        lib = _lib.load()
+        st = self._cur
+        B = st["B"]
+        nbytes = int(lib.astk_greedy_scored_workspace_bytes(C.byref(st["dd"]), int(stop_limit)))
+        if nbytes == 0:
+            return None
+        ws = self._workspace("greedy", nbytes)
+        # [n_steps, status word (float), 2 pad words, tokens | logp | nll, each (stop_limit, B)]: one device buffer, read back in one copy
+        sb = int(stop_limit) * B
+        n = 4 + (3 if y is not None else 2) * sb
+        out = self._pool(f"greedy_scored_out{slot}", (n,), torch.int32)
+        host = self._greedy_pinned.get(("scored", slot))
+        if host is None or host.numel() < n:
+            host = self._greedy_pinned[("scored", slot)] = torch.empty(n, dtype=torch.int32, pin_memory=True)
+        host = host[:n]
+        base = out.data_ptr()
+        check(lib.astk_greedy_decode_scored(C.byref(st["dd"]), C.byref(st["dp"]), _vp(st["enc_states"]), _vp(self._dec_c), _vp(self._dec_h),
+                                            int(start_token), int(end_token), int(stop_limit), _vp(y), int(y.shape[1]) if y is not None else 0,
+                                            _vp(self.mask_pad_id), C.c_void_p(base + 16), C.c_void_p(base + 16 + 4 * sb),
+                                            C.c_void_p(base + 16 + 8 * sb) if y is not None else None, C.c_void_p(base),
+                                            C.c_void_p(base + 4), _vp(ws), ws.numel(), self._stream()))
+        host.copy_(out, non_blocking=True)
+        ev = torch.cuda.Event()
+        ev.record(torch.cuda.current_stream(self.device))
+        return _PendingScored(host, ev, B, int(stop_limit), y is not None, int(end_token), y)
+
+    def _predict_scored_steps(self, start_token, end_token, stop_limit, y):
+        """_predict_steps with each step's logits scored: a float64 log_softmax on the device, the maximum's and the target's entries."""
+        with using_config("train", False):
+            B = self._cur["B"]
+            ht = torch.zeros(B, self.A, dtype=torch.float32, device=self.device)
+            word = torch.full((B,), start_token, dtype=torch.int32, device=self.device)
+            done = torch.zeros(B, dtype=torch.bool, device=self.device)
+            w64 = self.mask_pad_id.double()
+            rows, lps, nlls, npred = [], [], [], 0
+            while npred < stop_limit:
+                logits, ht, _ = self.decode_step(word, ht)
+                word = logits.argmax(dim=1).to(torch.int32)
+                ls = torch.log_softmax(logits.double(), dim=1)
+                rows.append(word)
+                lps.append(ls.gather(1, word.long()[:, None])[:, 0])
+                if y is not None:
+                    if len(rows) < y.shape[1]:
+                        t = y[:, len(rows)].long().clamp(0, self.V - 1)
+                        nlls.append(-w64[t] * ls.gather(1, t[:, None])[:, 0])
+                    else:
+                        nlls.append(torch.zeros(B, dtype=torch.float64, device=self.device))
+                done |= word == end_token
+                if bool(done.all()):
+                    break
+                npred += 1
+            f32 = lambda r: torch.stack(r, 0).T.float().cpu().numpy()
+            return ScoredPrediction(torch.stack(rows, 0).T.cpu().numpy(), f32(lps), f32(nlls) if y is not None else None, int(end_token))
 
     def _predict_steps(self, start_token, end_token, stop_limit):
         """The per-step greedy loop (seq2seq.py:475-527): one astk_decoder_step_infer, an argmax and a host read per token."""

@@ -399,6 +399,20 @@ int astk_greedy_decode(const astk_decoder_desc* d, const astk_decoder_params* p,
                        int go, int eos, int stop_limit, int32_t* tokens, int32_t* n_steps, float* status_dst,
                        void* ws, size_t ws_bytes, void* stream);
 
+/* The same decode, scored (the greedy loop of the reference's older trainer with targets: enc_dec.py:372-429): the kernel keeps each
+ * step's log-sum-exp and returns, beside the tokens,
+ *   logp[s][b] = log p(tokens[s][b])                                  (maximum logit - LSE), and, with targets,
+ *   nll[s][b]  = w[y[b][s+1]] * (LSE - logit[y[b][s+1]])              the free-running cross-entropy term of step s, row b
+ * (w = class_weight, NULL = all 1; its index is clamped to [0, V)).  y is (B, ldy) int32 on the device or NULL; a step with
+ * s + 1 >= ldy has no target and writes nll = 0.  tokens, logp and nll are (stop_limit, B) on the device, rows [0, *n_steps) defined;
+ * nll is NULL exactly when y is.  The decode is astk_greedy_decode's in every case: same stop rule, same tokens, same shapes (the
+ * workspace query returns 0 where astk_greedy_workspace_bytes does).  Fails like astk_greedy_decode, and also for a null logp, nll
+ * without y or y without nll, or ldy < 1. */
+size_t astk_greedy_scored_workspace_bytes(const astk_decoder_desc* d, int stop_limit);
+int astk_greedy_decode_scored(const astk_decoder_desc* d, const astk_decoder_params* p, const float* enc, const float* c0, const float* h0,
+                              int go, int eos, int stop_limit, const int32_t* y, int ldy, const float* class_weight, int32_t* tokens,
+                              float* logp, float* nll, int32_t* n_steps, float* status_dst, void* ws, size_t ws_bytes, void* stream);
+
 /* ---------------------------------------------------------------- batched beam search  (nn.py:235-322 over many utterances)
  * U utterances, N hypotheses kept per utterance, K candidates per live hypothesis: every slot is one row of ONE decoder step over
  * R = U*N rows, row u*N + j = slot j of utterance u.  enc is (U, T, H): utterance u's encoder states in enc[u, 0:T''_u] (the rest

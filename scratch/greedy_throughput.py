@@ -2,6 +2,8 @@
 the per-step loop (dec.persist = 0), in the same process, alternating, after a warm-up, each timed to a device synchronise.
 
     python scratch/greedy_throughput.py                                   # both shapes, both cases
+    python scratch/greedy_throughput.py --scored                          # the device loop unscored / scored without targets / scored
+                                                                          # with targets (predict_scored)
     python scratch/greedy_throughput.py --only device --shape es_en_20h --case no_eos --batches 1   # for a rocprofv3 --kernel-trace
                                                                           # --stats pass of its own (launches per batch: two such runs,
                                                                           # --batches 1 and 3, differenced)
@@ -78,6 +80,48 @@ def timed_predict(m, X, stop, persist):
     return dt, out
 
 
+def timed_scored(m, X, stop, y):
+    torch.cuda.synchronize()
+    t = time.perf_counter()
+    out = m.predict_scored(X, GO, EOS, stop, y=y)
+    torch.cuda.synchronize()
+    dt = time.perf_counter() - t
+    assert m.last_predict_path == "device", m.last_predict_path
+    return dt, out
+
+
+def run_scored(m, name, case, Xs, ys, stop, reps, n_plan):
+    """The device loop three ways on the same batches, alternating within every repetition; per batch the median over the repetitions."""
+    for X, y in zip(Xs, ys):                                         # warm-up of every shape of all three
+        timed_predict(m, X, stop, 1)
+        timed_scored(m, X, stop, None)
+        timed_scored(m, X, stop, y)
+    t = {k: [[] for _ in Xs] for k in ("unscored", "scored", "scored_y")}
+    te, steps = [[] for _ in Xs], [0] * len(Xs)
+    for _ in range(reps):
+        for i, (X, y) in enumerate(zip(Xs, ys)):
+            dt, out = timed_predict(m, X, stop, 1)
+            t["unscored"][i].append(dt)
+            dt, r0 = timed_scored(m, X, stop, None)
+            t["scored"][i].append(dt)
+            dt, r1 = timed_scored(m, X, stop, y)
+            t["scored_y"][i].append(dt)
+            te[i].append(timed_encode(m, X))
+            assert (r0.tokens == out).all() and (r1.tokens == out).all()
+            steps[i] = out.shape[1]
+    enc = np.array([np.median(v) for v in te])
+    res = dict(shape=name, case=case, reps=reps, frames=[int(X.shape[1]) for X in Xs], steps=steps, ms_encode=round(1e3 * float(enc.mean()), 3))
+    for k, v in t.items():
+        med = np.array([np.median(b) for b in v])
+        res["ms_" + k] = round(1e3 * float(med.mean()), 3)
+        res["us_per_step_" + k] = round(1e6 * float(((med - enc) / np.array(steps)).mean()), 2)
+        res["spread_" + k] = round(float(np.mean([(max(b) - min(b)) / np.median(b) for b in v])), 3)
+        res["dev_pass_s_" + k] = round(n_plan * float(med.mean()), 3)
+    res["ratio_per_step_scored"] = round(res["us_per_step_scored"] / res["us_per_step_unscored"], 3)
+    res["ratio_per_step_scored_y"] = round(res["us_per_step_scored_y"] / res["us_per_step_unscored"], 3)
+    print(json.dumps(res), flush=True)
+
+
 def timed_encode(m, X):
     with using_config("train", False):
         torch.cuda.synchronize()
@@ -96,6 +140,8 @@ def main():
     ap.add_argument("--only", default="", choices=["", "device"])
     ap.add_argument("--shape", default="", choices=[""] + list(SHAPES))
     ap.add_argument("--case", default="", choices=["", "no_eos", "early"])
+    ap.add_argument("--scored", action="store_true", help="time the device loop unscored, scored without targets and scored with targets")
+    ap.add_argument("--reps", type=int, default=7, help="--scored: repetitions of every batch (the median is reported)")
     a = ap.parse_args()
     plan = dev_plan()
     idx = np.linspace(0, len(plan) - 1, a.batches).round().astype(int) if a.batches > 1 else [len(plan) // 2]
@@ -122,6 +168,15 @@ def main():
                         hi = mid
                     else:
                         break
+            if a.scored:
+                # targets of the longest padded length the loader makes (max_pred 175), a quarter of them PAD
+                ys = []
+                for X in Xs:
+                    y = rng.integers(1, shape["V"], size=(X.shape[0], a.stop)).astype(np.int32)
+                    y[rng.random(y.shape) < 0.25] = 0
+                    ys.append(torch.from_numpy(y).cuda())
+                run_scored(m, name, case, Xs, ys, a.stop, a.reps, len(plan))
+                continue
             timed_predict(m, Xs[0], a.stop, 1)                       # warm-up of both paths
             if a.only != "device":
                 timed_predict(m, Xs[0], a.stop, 0)

@@ -10,6 +10,8 @@ if __name__ == "__main__":
     parser = argparse.ArgumentParser(description="Train and evaluate NN model")
     parser.add_argument("-m", "--cfg_path", help="path for model config", required=True)
     parser.add_argument("-e", "--epochs", help="num epochs", required=True)
+    parser.add_argument("--dev-loss", action="store_true",
+                        help="also log the free-running dev loss of the greedy decode (nmt_run.py:518-560) as a third column of the dev log")
     args = vars(parser.parse_args())
     cfg_path, epochs = args["cfg_path"], int(args["epochs"])
     print("number of epochs={0:d}".format(epochs))
@@ -45,11 +47,20 @@ if __name__ == "__main__":
             with open(nn.train_log, mode="a") as f:
                 f.write("{0:d}, {1:.4f}\n".format(epoch, epoch_loss))
         if metrics is not None and adist.rank() == 0:
-            hyps = nn.data_loader.get_hyps(nn.predict(dev_key))
+            if args["dev_loss"]:
+                preds, dev_loss, _ = nn.predict_scored(dev_key)
+            else:
+                preds, dev_loss = nn.predict(dev_key), None
+            hyps = nn.data_loader.get_hyps(preds)
             bleu = metrics.calc_bleu(hyps) * 100
             with open(nn.dev_log, mode="a") as f:
-                f.write("{0:d}, {1:.2f}\n".format(epoch, bleu))
+                if dev_loss is None:
+                    f.write("{0:d}, {1:.2f}\n".format(epoch, bleu))
+                else:
+                    f.write("{0:d}, {1:.2f}, {2:.4f}\n".format(epoch, bleu, dev_loss))
             print("BLEU = {0:.2f}".format(bleu))
+            if dev_loss is not None:
+                print("dev loss = {0:.4f}".format(dev_loss))
         if (epoch % iters_save == 0 or epoch == max_epoch - 1) and adist.rank() == 0:
             print("Saving model")
             serializers.save_npz(nn.model_fname.replace(".model", "_{0:d}.model".format(epoch)), nn.model,
