@@ -174,6 +174,9 @@ SIGNATURES = {
     "astk_greedy_scored_workspace_bytes": (_SZ, [C.POINTER(DecoderDesc), _I]),
     "astk_greedy_decode_scored": (C.c_int, [C.POINTER(DecoderDesc), C.POINTER(DecoderParams), _VP, _VP, _VP, _I, _I, _I, _VP, _I, _VP, _VP, _VP,
                                             _VP, _VP, _VP, _VP, _SZ, _VP]),
+    "astk_forced_workspace_bytes": (_SZ, [C.POINTER(DecoderDesc), _I, _I]),
+    "astk_forced_score": (C.c_int, [C.POINTER(DecoderDesc), C.POINTER(DecoderParams), _VP, _VP, _VP, _VP, _I, _VP, _VP, _VP, _VP, _VP, _VP, _SZ,
+                                    _VP]),
     "astk_beam_workspace_bytes": (_SZ, [C.POINTER(BeamDesc), C.POINTER(DecoderDesc)]),
     "astk_beam_step": (C.c_int, [C.POINTER(BeamDesc), C.POINTER(DecoderDesc), C.POINTER(DecoderParams), _VP, C.POINTER(BeamState), _I, _VP,
                                  _SZ, _VP]),

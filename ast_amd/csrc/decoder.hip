@@ -51,6 +51,10 @@ size_t greedy_scored_workspace_bytes(const astk_decoder_desc* d, int stop_limit)
 int greedy_decode_scored_launch(const astk_decoder_desc* d, const astk_decoder_params* prm, const float* enc, const float* c0, const float* h0,
                                 int go, int eos, int stop_limit, const int32_t* y, int ldy, const float* class_weight, int32_t* tokens,
                                 float* logp, float* nll, int32_t* n_steps, float* status_dst, void* ws, size_t ws_bytes, hipStream_t s);
+size_t forced_workspace_bytes(const astk_decoder_desc* d, int n_steps, int with_alpha);
+int forced_score_launch(const astk_decoder_desc* d, const astk_decoder_params* prm, const float* enc, const float* c0, const float* h0,
+                        const int32_t* y, int ldy, float* logp, float* logp_max, int32_t* pred, float* alpha, float* status_dst, void* ws,
+                        size_t ws_bytes, hipStream_t s);
 int decoder_persist_bwd_launch(const astk_decoder_desc* d, const float* enc, const float* rnn_masks, const DecPersistBwdBuffers& bf,
                                hipStream_t s);
 
@@ -988,6 +992,16 @@ int astk_greedy_decode_scored(const astk_decoder_desc* d, const astk_decoder_par
                               float* logp, float* nll, int32_t* n_steps, float* status_dst, void* ws, size_t ws_bytes, void* stream) {
   return greedy_decode_scored_launch(d, p, enc, c0, h0, go, eos, stop_limit, y, ldy, class_weight, tokens, logp, nll, n_steps, status_dst, ws,
                                      ws_bytes, (hipStream_t)stream);
+}
+
+size_t astk_forced_workspace_bytes(const astk_decoder_desc* d, int n_steps, int with_alpha) {
+  return forced_workspace_bytes(d, n_steps, with_alpha);
+}
+
+int astk_forced_score(const astk_decoder_desc* d, const astk_decoder_params* p, const float* enc, const float* c0, const float* h0,
+                      const int32_t* y, int ldy, float* logp, float* logp_max, int32_t* pred, float* alpha, float* status_dst, void* ws,
+                      size_t ws_bytes, void* stream) {
+  return forced_score_launch(d, p, enc, c0, h0, y, ldy, logp, logp_max, pred, alpha, status_dst, ws, ws_bytes, (hipStream_t)stream);
 }
 
 }  // extern "C"

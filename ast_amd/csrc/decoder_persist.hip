@@ -323,9 +323,17 @@ __device__ __forceinline__ void mfma_blocks(f32x4& acc, const float4* a, const f
 // sums as the training mode does and stores, beside the token, the log-probability of that token and the weighted negative
 // log-likelihood of the target (PDecArgs: LSE = LOGP, LOSSROWS = NLL, ytgt / L / cw).  Two more plain stores in front of the vmcnt(0)
 // and the barrier that the token store already had: no wait, arrival, counter or exit condition is added.  DESIGN.md section 12.
-template <int NC, int NL, bool XS, bool GR, bool SC = false>
+// FD (with GR and SC): forced decoding -- the model run along a given translation.  Step s feeds y[b][s] (read from global memory, clamped),
+// so no step waits for an argmax: the hand-offs are the training loop's with every step teacher-forced (P6 deferred behind the next
+// step's attention partial), and there is no stop: the stop word is never passed to a wait (STOP = false), no tile reports, every
+// workgroup runs all S steps.  P5 keeps what the scored mode keeps; P6 stores LOGP = log p(y[b][s+1]) (PDecArgs: LSE), the confidence
+// max logit - LSE (LOSSROWS, or null) and the argmax (PRED, or null).  With ALPHA / ML given, the attention and combine roles store the
+// raw scores and (max, 1 / sum) as the training mode does; k_alpha_normalise turns them into alpha behind the loop.  DESIGN.md section 13.
+template <int NC, int NL, bool XS, bool GR, bool SC = false, bool FD = false>
 __device__ __forceinline__ void decoder_persist_fwd_body(const PDecArgs& a) {
   static_assert(GR || !SC, "the scored mode is a greedy mode");
+  static_assert(!FD || (GR && SC), "the forced mode builds on the scored inference mode");
+  constexpr bool STOP = GR && !FD;         // the greedy modes' stop word exists
   constexpr bool SUMS = !GR || SC;         // P5 / P6 keep the sum of exponentials and the target logit
   extern __shared__ __attribute__((aligned(16))) float lds[];   // enc slice [chunk][H], encA slice [chunk][H], scratch
   __shared__ __attribute__((aligned(16))) float red[4 * 256];
@@ -490,7 +498,7 @@ __device__ __forceinline__ void decoder_persist_fwd_body(const PDecArgs& a) {
       const int row = m0 + (tid >> 4), sub = tid & 15;       // 16 threads per row sweep the tiles
       [[maybe_unused]] bool sc_tgt = false;                  // SC: step s has a target (column s+1 of y); its class weight
       [[maybe_unused]] float sc_w = 0.f;
-      if constexpr (SC) {       // (read in front of the wait: neither load is on the chain)
+      if constexpr (SC && !FD) {       // (read in front of the wait: neither load is on the chain)
         sc_tgt = a.ytgt && s + 1 < a.L;
         if (sc_tgt && sub == 0 && row < B) {
           int r = row;
@@ -499,7 +507,7 @@ __device__ __forceinline__ void decoder_persist_fwd_body(const PDecArgs& a) {
           sc_w = a.cw ? a.cw[tgt < 0 ? 0 : (tgt >= V ? V - 1 : tgt)] : 1.f;
         }
       }
-      if (!wg_wait_sh(CTR(PH_LOG, bt), a.ntile_v, s + 1, a.ab, &s_flag, StopCtl{GR ? a.gctl + 3 * CTRS : nullptr, s, false})) return false;
+      if (!wg_wait_sh(CTR(PH_LOG, bt), a.ntile_v, s + 1, a.ab, &s_flag, StopCtl{STOP ? a.gctl + 3 * CTRS : nullptr, s, false})) return false;
       float mx = -INFINITY, se = 0.f, xt = 0.f;
       int mi = 0x7fffffff;
       if (row < B)
@@ -523,7 +531,18 @@ __device__ __forceinline__ void decoder_persist_fwd_body(const PDecArgs& a) {
         mx = nm;
         xt += ox;
       }
-      if constexpr (GR) {
+      if constexpr (FD) {
+        if (sub == 0 && row < B) {
+          // log p(target) = xt - lse, lse = mx + logf(se): formed as (xt - mx) - logf(se), without rounding lse first
+          const float lg = logf(se);
+          int r = row;
+          asm volatile("" : "+v"(r));       // (keeps the addresses out of the loop-invariant registers: they are full, they would spill)
+          *ua(a.LSE + (long)s * B, (unsigned)r) = (xt - mx) - lg;
+          if (a.LOSSROWS) *ua(a.LOSSROWS + (long)s * B, (unsigned)r) = -lg;
+          if (a.PRED) *ua(a.PRED + (long)s * B, (unsigned)r) = mi;
+        }
+        publish_sh(CTR(PH_CE, bt), 0);      // (the training loop's arrival; nothing waits for it in this mode)
+      } else if constexpr (GR) {
         if constexpr (SC) {
           if (sub == 0 && row < B) {
             // lse = mx + logf(se): log p(token) = mx - lse and the target's -log p = lse - xt, formed without rounding lse first
@@ -571,17 +590,22 @@ __device__ __forceinline__ void decoder_persist_fwd_body(const PDecArgs& a) {
       TICK(12)
     return true;
   };
-  const unsigned* const stopw = GR ? a.gctl + 3 * CTRS : nullptr;
+  const unsigned* const stopw = STOP ? a.gctl + 3 * CTRS : nullptr;
   for (int s = 0; s < S; ++s) {
     const StopCtl sc{stopw, s, false};
     // ================= P1: embed + LSTM cell =================
     if (has_cell) {
       const int bt = cell_bt, m0 = bt * 16;
       const int brow = min(m0 + r16, B - 1);             // this lane's A-operand batch row
-      const bool truth = s == 0 || (!GR && flagS[s] != 0);
+      const bool truth = FD || s == 0 || (!GR && flagS[s] != 0);
       // (GR: the stop word is read behind this tile's P6 of step s-1, which wrote it in front of that arrival: the cells leave at n_steps)
       if (!truth) { if (!wg_wait_sh(CTR(PH_CE, bt), 1, s, a.ab, &s_flag, StopCtl{stopw, s, true})) return; }
-      int tok = truth ? (GR ? a.go : yS[r16 * a.L + s]) : ldi_sc1(ua(a.PRED + (long)(s - 1) * B, (unsigned)brow));
+      int tok;
+      if constexpr (FD) {
+        int r = brow;
+        asm volatile("" : "+v"(r));         // (as in P5: the address is formed here, not kept over the loop)
+        tok = *ua(a.y + s, (unsigned)(r * a.L));
+      } else tok = truth ? (GR ? a.go : yS[r16 * a.L + s]) : ldi_sc1(ua(a.PRED + (long)(s - 1) * B, (unsigned)brow));
       tok = tok < 0 ? 0 : (tok >= V ? V - 1 : tok);
       if (s > 0) { if (!wg_wait_sh(CTR(PH_CELL, bt), H / 8, s, a.ab, &s_flag, sc)) return; }
       f32x4 acc[2] = {{0.f, 0.f, 0.f, 0.f}, {0.f, 0.f, 0.f, 0.f}};
@@ -694,7 +718,7 @@ __device__ __forceinline__ void decoder_persist_fwd_body(const PDecArgs& a) {
               else if ((spins & 63u) == 0 && __any(stop_seen(sc))) { if (lane == 0) s_stop = 1; break; }
             }
           }
-          if constexpr (GR) {     // (a stop: the whole workgroup leaves, after the barrier that shows every wave's verdict)
+          if constexpr (STOP) {     // (a stop: the whole workgroup leaves, after the barrier that shows every wave's verdict)
             __syncthreads();
             if (s_stop) return;
           }
@@ -772,7 +796,7 @@ __device__ __forceinline__ void decoder_persist_fwd_body(const PDecArgs& a) {
         float* const pS_ = scr + HH + 64;                // scratch: hS[H] | scores[64] | p[64] | fold
         if (tid >= nrow && tid < 64) scS[tid] = -INFINITY;
         __syncthreads();
-        if (GR && s_stop) return;
+        if (STOP && s_stop) return;
         TICK(13)
         {
           // pass 1: 16 lanes per row; group g owns rows g and g + 16; lane l covers floats 4l + 64c of the row
@@ -898,7 +922,7 @@ __device__ __forceinline__ void decoder_persist_fwd_body(const PDecArgs& a) {
         float mg = -INFINITY;
         if (tid >= nrow && tid < c4) scS[tid] = -INFINITY;        // pad the score vector for the float4 sweeps below
         __syncthreads();
-        if (GR && s_stop) return;
+        if (STOP && s_stop) return;
         TICK(13)
         {
           // pass 1: 16 lanes per row, two rows per trip; lane l covers floats 4l + 64c (conflict-free LDS reads)
@@ -969,6 +993,13 @@ __device__ __forceinline__ void decoder_persist_fwd_body(const PDecArgs& a) {
       TQ(5)
       if (a.tick_out) tk_att += wall_clock64() - ta0;
       if (!GR && tid < nrow) a.ALPHA[((long)s * B + b) * Tp + t0 + tid] = my_score;   // raw score, normalised by the backward (M, 1/L in ML)
+      if constexpr (FD) {
+        if (a.ALPHA && tid < nrow) {        // raw score, normalised behind the loop (k_alpha_normalise)
+          int t = tid;
+          asm volatile("" : "+v"(t));
+          *ua(a.ALPHA + ((long)s * B + b) * Tp + t0, (unsigned)t) = my_score;
+        }
+      }
       TICK(5)
     }
     if (has_ce && p6_pending >= 0) {       // P6 of the previous step, deferred behind this step's attention partial (see P6 below)
@@ -1018,6 +1049,9 @@ __device__ __forceinline__ void decoder_persist_fwd_body(const PDecArgs& a) {
       publish_sh(CTR(PH_CMB, bt), b - bt * 16);
       TICK(7)
       if (!GR && tid == 0) { a.ML[((long)s * B + b) * 2] = Mx; a.ML[((long)s * B + b) * 2 + 1] = inv; }
+      if constexpr (FD) {
+        if (a.ML && tid == 0) { float* ml = ua(a.ML + ((long)s * B + b) * 2, 0u); ml[0] = Mx; ml[1] = inv; }
+      }
     }
     // ================= P4: ht = tanh(Wc [cv;h] + bc) =================
     if (has_c) {
@@ -1074,6 +1108,7 @@ __device__ __forceinline__ void decoder_persist_fwd_body(const PDecArgs& a) {
         int r = m0 + (tid >> 4);
         asm volatile("" : "+v"(r));         // (keeps the address out of the loop-invariant registers: they are full, it would spill)
         if (a.ytgt && s + 1 < a.L && r < B) sc_tgt = *ua(a.ytgt + s + 1, (unsigned)(r * a.L));
+        if constexpr (FD) sc_tgt = sc_tgt < 0 ? 0 : (sc_tgt >= V ? V - 1 : sc_tgt);      // (a step of this mode always has a target)
       }
       if (!wg_wait_sh(CTR(PH_CTX, bt), A / 16, s + 1, a.ab, &s_flag, sc)) return;
       TICK(10)
@@ -1122,7 +1157,9 @@ __device__ __forceinline__ void decoder_persist_fwd_body(const PDecArgs& a) {
     // it is then DEFERRED behind the workgroup's P3 of step s+1.  When step s+1 feeds the argmax back its cells wait for PH_CE(s)
     // anyway and P6(s) runs in place (deferring it there would dead-lock: P3(s+1) waits for cells that wait for P6(s)).
     if (has_ce) {
-      const bool defer = !GR && s + 1 < S && flagS[s + 1] != 0;      // (GR: every step feeds its argmax back)
+      bool defer;
+      if constexpr (FD) defer = s + 1 < S;                           // (FD: no step does)
+      else defer = !GR && s + 1 < S && flagS[s + 1] != 0;            // (GR: every step feeds its argmax back)
       if (defer) p6_pending = s;
       else if (!run_p6(s)) return;
     }
@@ -1166,6 +1203,27 @@ template <int NC, int NL, bool XS>
 __global__ __launch_bounds__(256, 1) void decoder_persist_greedy_scored(PDecArgs a) {
   decoder_persist_fwd_body<NC, NL, XS, true, true>(a);
   greedy_last_out(a);
+}
+
+// The forced mode as a kernel of its own, likewise.  Of the greedy modes' control words it keeps one, the exit count (gctl[2]): the last
+// workgroup to leave writes the status copy.  It is an arrival at the end of the kernel that nothing waits for.
+template <int NC, int NL, bool XS>
+__global__ __launch_bounds__(256, 1) void decoder_persist_forced(PDecArgs a) {
+  decoder_persist_fwd_body<NC, NL, XS, true, true, true>(a);
+  if (!a.status_dst) return;
+  asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+  __syncthreads();
+  if (threadIdx.x == 0 && __hip_atomic_fetch_add(a.gctl + 2 * CTRS, 1u, __ATOMIC_ACQ_REL, __HIP_MEMORY_SCOPE_AGENT) + 1 == (unsigned)G)
+    *a.status_dst = (float)__hip_atomic_load(a.ab.status, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+}
+
+// alpha[r][t] = exp(score[r][t] - M[r]) / L[r], r = (step, row), t < T: the raw scores of the forced loop (rows of Tp floats) into the
+// caller's dense (S, B, T) buffer
+__global__ __launch_bounds__(256) void k_alpha_normalise(const float* __restrict__ raw, const float* __restrict__ ml, float* __restrict__ alpha,
+                                                         int T, int Tp) {
+  const long r = blockIdx.x;
+  const float M = ml[2 * r], inv = ml[2 * r + 1];
+  for (int t = threadIdx.x; t < T; t += 256) alpha[r * T + t] = expf(raw[r * Tp + t] - M) * inv;
 }
 
 // =====================================================================================================================
@@ -1929,6 +1987,19 @@ static void pdec_launch_scored(bool special, bool xs, size_t shm, hipStream_t s,
   else if (special) hipLaunchKernelGGL((decoder_persist_greedy_scored<8, NL, false>), dim3(G), dim3(256), shm, s, a);
   else hipLaunchKernelGGL((decoder_persist_greedy_scored<0, NL, false>), dim3(G), dim3(256), shm, s, a);
 }
+template <int NL>
+static void pdec_launch_forced(bool special, bool xs, size_t shm, hipStream_t s, const PDecArgs& a) {
+  static bool attr_done = false;
+  if (!attr_done) {
+    (void)hipFuncSetAttribute((const void*)decoder_persist_forced<0, NL, false>, hipFuncAttributeMaxDynamicSharedMemorySize, 138 * 1024);
+    (void)hipFuncSetAttribute((const void*)decoder_persist_forced<8, NL, false>, hipFuncAttributeMaxDynamicSharedMemorySize, 138 * 1024);
+    (void)hipFuncSetAttribute((const void*)decoder_persist_forced<8, NL, true>, hipFuncAttributeMaxDynamicSharedMemorySize, 138 * 1024);
+    attr_done = true;
+  }
+  if (special && xs) hipLaunchKernelGGL((decoder_persist_forced<8, NL, true>), dim3(G), dim3(256), shm, s, a);
+  else if (special) hipLaunchKernelGGL((decoder_persist_forced<8, NL, false>), dim3(G), dim3(256), shm, s, a);
+  else hipLaunchKernelGGL((decoder_persist_forced<0, NL, false>), dim3(G), dim3(256), shm, s, a);
+}
 template <int NL, bool GR = false>
 static void pdec_launch_fwd(bool special, bool xs, size_t shm, hipStream_t s, const PDecArgs& a) {
   static bool attr_done = false;
@@ -2116,6 +2187,72 @@ size_t greedy_workspace_bytes(const astk_decoder_desc* d, int stop_limit) {
 // (the scored mode needs no workspace of its own: LOGP and NLL are the caller's)
 size_t greedy_scored_workspace_bytes(const astk_decoder_desc* d, int stop_limit) { return greedy_workspace_bytes(d, stop_limit); }
 
+// What the launchers of the inference modes (greedy, scored greedy, forced) share.  inference_args: the PDecArgs of a loop of S steps on
+// a greedy plan -- shapes, parameters, hand-off buffers, counters, abort control, the control lines; a mode's own fields (tokens, targets,
+// outputs) are its launcher's.  inference_fill: the one fill launch in front of the loop -- counters, abort word, tile reports and exit
+// count to 0, the stop word to S, the sentinel hand-offs, h0.  inference_launch: the instantiation of the shape.
+static PDecArgs inference_args(const astk_decoder_desc* d, const astk_decoder_params* prm, const float* enc, const float* c0, int S,
+                               const GreedyPlan& g) {
+  PDecArgs a;
+  memset(&a, 0, sizeof(a));
+  a.B = d->B; a.S = S; a.L = S + 1; a.T = d->T; a.Tp = (d->T + 3) / 4 * 4; a.H = d->H; a.E = d->E; a.A = d->A; a.V = d->V;
+  a.Vp = (d->V + 3) / 4 * 4; a.XI = d->E + d->A; a.nbt = (d->B + 15) / 16; a.nsplit = g.nsplit; a.chunk = g.chunk;
+  a.ntile_v = (d->V + 15) / 16;
+  a.inv_count = 1.f / (float)d->B;
+  a.embed = prm->embed;
+  const size_t bh = (size_t)d->B * d->H;
+  for (int l = 0; l < d->n_layers; ++l) {
+    a.Wu[l] = prm->lstm[l].Wu; a.bias[l] = prm->lstm[l].b; a.Wl[l] = prm->lstm[l].Wl;
+    a.Cst[l] = const_cast<float*>(c0 + l * bh);       // (read once: the cells keep c in a register and save no states)
+    a.HR[l] = g.HR[l]; a.HD[l] = g.HD[l];
+  }
+  a.Wa = prm->Wa; a.ba = prm->ba; a.Wc = prm->Wc; a.bc = prm->bc; a.Wo = prm->Wo; a.bo = prm->bo;
+  a.enc = enc; a.encA = g.ENCA;
+  a.CVH = g.CVH; a.HT = g.HT; a.PART = g.PART; a.CESTAT = g.CESTAT;
+  a.ctr = g.ctr;
+  a.ab = abort_ctl(g.ctr + (size_t)NPHASE_SLOTS * NSH * a.nbt * CTRS, PERSIST_DEC_FWD);
+  a.dbg = persist_dbg_env();
+  a.gctl = g.ctr + (greedy_ctr_lines(d->B) - 4) * CTRS;
+  return a;
+}
+
+static int inference_fill(const astk_decoder_desc* d, const PDecArgs& a, const GreedyPlan& g, const float* h0, hipStream_t s) {
+  const size_t bh = (size_t)d->B * d->H;
+  FillSegs f;
+  f.n = 0;
+  fill_seg_add(f, g.ctr, (greedy_ctr_lines(d->B) - 1) * CTRS * sizeof(unsigned), 0u);
+  fill_seg_add(f, a.gctl + 3 * CTRS, CTRS * sizeof(unsigned), (unsigned)a.S);
+#if ASTK_PDEC_SENT_H
+  fill_seg_add(f, g.CVH, (size_t)a.S * a.B * 2 * a.H * sizeof(float));
+#endif
+#if ASTK_PDEC_SENT_HD && ASTK_PDEC_SENT_H
+  for (int l = 0; l + 1 < d->n_layers; ++l) fill_seg_add(f, g.HD[l], (size_t)a.S * bh * sizeof(float));
+#endif
+  for (int l = 0; l < d->n_layers; ++l) fill_seg_add_copy(f, g.HR[l], h0 + l * bh, bh * sizeof(float));
+  ASTK_TRY(fill_u32_segments(f, PDEC_SENTINEL, s));
+  return 0;
+}
+
+enum InferenceMode { INF_GREEDY, INF_SCORED, INF_FORCED };
+static void inference_launch(InferenceMode mode, const astk_decoder_desc* d, const PDecArgs& a, const GreedyPlan& g, hipStream_t s) {
+  const size_t shm = pdec_lds_floats(g.chunk, a.H, g.nsplit) * sizeof(float);
+  const bool special = pdec_special(a.H, g.chunk);
+  const bool xs = special && g.chunk > PDEC_RES_ROWS;
+  if (mode == INF_FORCED) {
+    if (d->n_layers == 1) pdec_launch_forced<1>(special, xs, shm, s, a);
+    else if (d->n_layers == 2) pdec_launch_forced<2>(special, xs, shm, s, a);
+    else pdec_launch_forced<3>(special, xs, shm, s, a);
+  } else if (mode == INF_SCORED) {
+    if (d->n_layers == 1) pdec_launch_scored<1>(special, xs, shm, s, a);
+    else if (d->n_layers == 2) pdec_launch_scored<2>(special, xs, shm, s, a);
+    else pdec_launch_scored<3>(special, xs, shm, s, a);
+  } else {
+    if (d->n_layers == 1) pdec_launch_fwd<1, true>(special, xs, shm, s, a);
+    else if (d->n_layers == 2) pdec_launch_fwd<2, true>(special, xs, shm, s, a);
+    else pdec_launch_fwd<3, true>(special, xs, shm, s, a);
+  }
+}
+
 // the scored mode's arguments
 struct GreedyScoredIO {
   const int32_t* y; int ldy;       // targets [B][ldy] or null
@@ -2144,58 +2281,15 @@ static int greedy_launch(const astk_decoder_desc* d, const astk_decoder_params* 
   PrecScope prec_scope(d->precision, d->gemm_operands);
   GemmForwardScope forward_scope;
   ASTK_TRY(gemm_launch(GEMM_NN, gemm_args(d->B * d->T, d->H, d->H, mat(enc, d->H), mat(prm->Wa, d->H), g.ENCA, d->H), s));   // encA = enc . Wa
-  PDecArgs a;
-  memset(&a, 0, sizeof(a));
-  a.B = d->B; a.S = stop_limit; a.L = stop_limit + 1; a.T = d->T; a.Tp = (d->T + 3) / 4 * 4; a.H = d->H; a.E = d->E; a.A = d->A; a.V = d->V;
-  a.Vp = (d->V + 3) / 4 * 4; a.XI = d->E + d->A; a.nbt = (d->B + 15) / 16; a.nsplit = g.nsplit; a.chunk = g.chunk;
-  a.ntile_v = (d->V + 15) / 16;
-  a.inv_count = 1.f / (float)d->B;
-  a.embed = prm->embed;
-  const size_t bh = (size_t)d->B * d->H;
-  for (int l = 0; l < d->n_layers; ++l) {
-    a.Wu[l] = prm->lstm[l].Wu; a.bias[l] = prm->lstm[l].b; a.Wl[l] = prm->lstm[l].Wl;
-    a.Cst[l] = const_cast<float*>(c0 + l * bh);       // (read once: the cells keep c in a register and save no states)
-    a.HR[l] = g.HR[l]; a.HD[l] = g.HD[l];
-  }
-  a.Wa = prm->Wa; a.ba = prm->ba; a.Wc = prm->Wc; a.bc = prm->bc; a.Wo = prm->Wo; a.bo = prm->bo;
-  a.enc = enc; a.encA = g.ENCA;
-  a.PRED = tokens; a.CVH = g.CVH; a.HT = g.HT; a.PART = g.PART; a.CESTAT = g.CESTAT;
-  a.ctr = g.ctr;
-  a.ab = abort_ctl(g.ctr + (size_t)NPHASE_SLOTS * NSH * a.nbt * CTRS, PERSIST_DEC_FWD);
-  a.dbg = persist_dbg_env();
+  PDecArgs a = inference_args(d, prm, enc, c0, stop_limit, g);
+  a.PRED = tokens;
   a.go = go; a.eos = eos;
-  a.gctl = g.ctr + (greedy_ctr_lines(d->B) - 4) * CTRS;
   a.n_steps_out = n_steps; a.status_dst = status_dst;
   if (sc) {
     a.LSE = sc->logp; a.LOSSROWS = sc->nll; a.ytgt = sc->y; a.L = sc->y ? sc->ldy : 1; a.cw = sc->class_weight;
   }
-  {
-    // one fill launch: counters, abort word, tile reports and exit count to 0, the stop word to stop_limit, the sentinel hand-offs, h0
-    FillSegs f;
-    f.n = 0;
-    fill_seg_add(f, g.ctr, (greedy_ctr_lines(d->B) - 1) * CTRS * sizeof(unsigned), 0u);
-    fill_seg_add(f, a.gctl + 3 * CTRS, CTRS * sizeof(unsigned), (unsigned)stop_limit);
-#if ASTK_PDEC_SENT_H
-    fill_seg_add(f, g.CVH, (size_t)a.S * a.B * 2 * a.H * sizeof(float));
-#endif
-#if ASTK_PDEC_SENT_HD && ASTK_PDEC_SENT_H
-    for (int l = 0; l + 1 < d->n_layers; ++l) fill_seg_add(f, g.HD[l], (size_t)a.S * bh * sizeof(float));
-#endif
-    for (int l = 0; l < d->n_layers; ++l) fill_seg_add_copy(f, g.HR[l], h0 + l * bh, bh * sizeof(float));
-    ASTK_TRY(fill_u32_segments(f, PDEC_SENTINEL, s));
-  }
-  const size_t shm = pdec_lds_floats(g.chunk, a.H, g.nsplit) * sizeof(float);
-  const bool special = pdec_special(a.H, g.chunk);
-  const bool xs = special && g.chunk > PDEC_RES_ROWS;
-  if (sc) {
-    if (d->n_layers == 1) pdec_launch_scored<1>(special, xs, shm, s, a);
-    else if (d->n_layers == 2) pdec_launch_scored<2>(special, xs, shm, s, a);
-    else pdec_launch_scored<3>(special, xs, shm, s, a);
-  } else {
-    if (d->n_layers == 1) pdec_launch_fwd<1, true>(special, xs, shm, s, a);
-    else if (d->n_layers == 2) pdec_launch_fwd<2, true>(special, xs, shm, s, a);
-    else pdec_launch_fwd<3, true>(special, xs, shm, s, a);
-  }
+  ASTK_TRY(inference_fill(d, a, g, h0, s));
+  inference_launch(sc ? INF_SCORED : INF_GREEDY, d, a, g, s);
   ASTK_LAUNCH_CHECK();
   return 0;
 }
@@ -2210,6 +2304,63 @@ int greedy_decode_scored_launch(const astk_decoder_desc* d, const astk_decoder_p
                                 float* logp, float* nll, int32_t* n_steps, float* status_dst, void* ws, size_t ws_bytes, hipStream_t s) {
   const GreedyScoredIO sc{y, ldy, class_weight, logp, nll};
   return greedy_launch(d, prm, enc, c0, h0, go, eos, stop_limit, &sc, tokens, n_steps, status_dst, ws, ws_bytes, s);
+}
+
+// ---------------------------------------------------------------------------------------------------- forced decoding
+// decoder_persist_forced on the greedy plan sized by S = ldy - 1, plus -- with an alpha output -- the raw scores [S][B][Tp] and the
+// (max, 1 / sum) pairs [S][B][2] that k_alpha_normalise reads behind the loop.
+struct ForcedPlan {
+  GreedyPlan g;
+  float *RAW, *ML;
+  size_t bytes;
+};
+static bool forced_plan(const astk_decoder_desc* d, int n_steps, int with_alpha, void* ws, ForcedPlan& f) {
+  if (!greedy_plan(d, n_steps, ws, f.g)) return false;
+  f.RAW = f.ML = nullptr;
+  f.bytes = f.g.bytes;
+  if (with_alpha) {
+    Carver c(ws ? (char*)ws + f.g.bytes : nullptr);
+    const size_t S = n_steps, B = d->B, Tp = (d->T + 3) / 4 * 4;
+    f.RAW = c.take<float>(S * B * Tp);
+    f.ML = c.take<float>(S * B * 2);
+    f.bytes += c.total();
+  }
+  return true;
+}
+
+size_t forced_workspace_bytes(const astk_decoder_desc* d, int n_steps, int with_alpha) {
+  ForcedPlan f;
+  return forced_plan(d, n_steps, with_alpha, nullptr, f) ? f.bytes : 0;
+}
+
+int forced_score_launch(const astk_decoder_desc* d, const astk_decoder_params* prm, const float* enc, const float* c0, const float* h0,
+                        const int32_t* y, int ldy, float* logp, float* logp_max, int32_t* pred, float* alpha, float* status_dst, void* ws,
+                        size_t ws_bytes, hipStream_t s) {
+  ASTK_CHECK_DESC(d, astk_decoder_desc);
+  ASTK_CHECK(ldy >= 2 && ldy - 1 <= ASTK_GREEDY_MAX_STEPS, "forced_score: ldy %d outside [2, %d]", ldy, ASTK_GREEDY_MAX_STEPS + 1);
+  const int S = ldy - 1;
+  ForcedPlan f;
+  ASTK_CHECK(forced_plan(d, S, alpha != nullptr, nullptr, f), "forced_score: B = %d, H = %d, %d layers (or the knob dec.persist = 0) does not run "
+             "on the device loop: astk_forced_workspace_bytes returns 0, score with astk_decoder_step_infer", d->B, d->H, d->n_layers);
+  ASTK_CHECK(ws && ws_bytes >= f.bytes, "forced_score: workspace too small (%zu < %zu)", ws_bytes, f.bytes);
+  ASTK_CHECK(prm && enc && c0 && h0 && y && logp, "forced_score: null pointer");
+  forced_plan(d, S, alpha != nullptr, ws, f);
+  const GreedyPlan& g = f.g;
+  PrecScope prec_scope(d->precision, d->gemm_operands);
+  GemmForwardScope forward_scope;
+  ASTK_TRY(gemm_launch(GEMM_NN, gemm_args(d->B * d->T, d->H, d->H, mat(enc, d->H), mat(prm->Wa, d->H), g.ENCA, d->H), s));   // encA = enc . Wa
+  PDecArgs a = inference_args(d, prm, enc, c0, S, g);
+  a.y = y; a.ytgt = y;                  // (a.L = S + 1 = ldy)
+  a.LSE = logp; a.LOSSROWS = logp_max; a.PRED = pred; a.ALPHA = f.RAW; a.ML = f.ML;
+  a.status_dst = status_dst;            // (of the control lines only the exit count, line 2, is used: the stop word is never read)
+  ASTK_TRY(inference_fill(d, a, g, h0, s));
+  inference_launch(INF_FORCED, d, a, g, s);
+  ASTK_LAUNCH_CHECK();
+  if (alpha) {
+    hipLaunchKernelGGL(k_alpha_normalise, dim3(a.S * a.B), dim3(256), 0, s, f.RAW, f.ML, alpha, a.T, a.Tp);
+    ASTK_LAUNCH_CHECK();
+  }
+  return 0;
 }
 
 }  // namespace astk

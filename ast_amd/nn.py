@@ -2,6 +2,7 @@
 seq2seq_<N>.model, and runs the train step of nn.py:168-194 -- forward_loss -> cleargrads -> backward -> update --
 on the HIP path.  Data-parallel runs (one process per GPU, torchrun) shard every bucketed batch over the ranks and
 all-reduce the flat gradient arena over RCCL before the hooks (ast_amd.dist)."""
+import math
 import os
 import random
 
@@ -158,6 +159,22 @@ def decode_beam_batch(model, Xs, stop_limit, N, K):
                          "attn_v": ht[r:r + 1].clone(), "attn_history": [alphas[k, :lens[u]].copy() for k in arow]}
                         for r, toks, arow in lst])
         return out
+
+
+def score_hypotheses(model, X, hyps, return_alpha=False):
+    """Forced scores of several token lists for ONE utterance: X (1, T, D) is repeated over the rows and the lists `hyps` (each
+    [GO, t1, .., tn], as beam search returns them) are PAD-padded to one length -- the encoding decode_beam saw, since batches carry no
+    length masks.  Returns (scores, r): scores[i] = the float64 sum of log p(t_k | t_<k) over hypothesis i's own n steps (a PAD id
+    inside a hypothesis counts like any other token, the padding behind it does not), r = the ForcedScore of the padded batch."""
+    import numpy as np
+    X = model._as_input(X)
+    if X.dim() == 2:
+        X = X[None]
+    y = np.zeros((len(hyps), max(2, max(len(h) for h in hyps))), dtype=np.int32)
+    for i, h in enumerate(hyps):
+        y[i, :len(h)] = h
+    r = model.score(X.expand(len(hyps), -1, -1), y, return_alpha=return_alpha)
+    return [float(r.logp[i, :len(h) - 1].astype(np.float64).sum()) for i, h in enumerate(hyps)], r
 
 
 def _init_hyp_from(model, enc_states):
@@ -363,3 +380,30 @@ class NN:
             if pending is not None:
                 settle(pending)
         return preds, (sum(losses) / len(losses) if losses else 0.0), scores
+
+    def score_set(self, set_key):
+        """Forced decoding of a set's references (SpeechEncoderDecoder.score): returns (scores, dev_loss, ppl).  scores = (utt,
+        log-probability of the reference, its number of non-PAD target tokens) triples; dev_loss = the mean over the batches of (the
+        teacher-forced cross-entropy summed over the steps / the padded target length) -- the normalisation of predict_scored's dev loss,
+        so the two are comparable; ppl = exp(-sum of the log-probabilities / sum of the token counts).  Read one batch late like predict()."""
+        scores, losses = [], []
+        pending = None
+
+        def settle(p):
+            utts, n, L, handle = p
+            r = handle.result()
+            scores.extend(zip(utts, r.score.tolist(), r.n_tokens.tolist()))
+            losses.append(r.loss / L)
+            pbar.update(n)
+        with tqdm(total=self.data_loader.n_utts[set_key], ncols=80, disable=adist.rank() != 0) as pbar:
+            for i, batch in enumerate(self.data_loader.get_batch(self.cfg.train["batch_size"], set_key, train=False, labels=True)):
+                with using_config("train", False):
+                    cur = (batch["utts"], len(batch["X"]), int(batch["y"].shape[1]), self.model.score_async(batch["X"], batch["y"], slot=i % 2))
+                if pending is not None:
+                    settle(pending)
+                pending = cur
+            if pending is not None:
+                settle(pending)
+        n_tok = sum(n for _, _, n in scores)
+        ppl = math.exp(-sum(lp for _, lp, _ in scores) / n_tok) if n_tok else float("nan")
+        return scores, (sum(losses) / len(losses) if losses else 0.0), ppl

@@ -214,6 +214,67 @@ class _PendingScored:
         return scored_from_rows(v[4:], int(v[0]), *self.args)
 
 
+class ForcedScore:
+    """What score() returns for targets y (B, L), S = L - 1 steps, step s fed y[:, s] and scored against y[:, s + 1]:
+      logp (B, S) float32      log p(y[b, s + 1]), unweighted;   logp_max (B, S) the log-probability of the argmax;
+      pred (B, S) int32        the argmax (first maximum);        weight (B, S) = mask_pad_id[y[:, 1:]] (0 at PAD targets);
+      alpha (B, S, T'') float32 the attention rows, or None;
+    and the reductions (float64, on the host):
+      score[b]    = sum of logp[b] where weight is non-zero, n_tokens[b] = how many such positions;
+      loss        = sum over the steps of the mean over the B rows of weight * (-logp): the value of eval-mode
+                    forward_loss(X, y, teach_ratio=1) (PAD targets weigh 0, every step divides by B)."""
+
+    def __init__(self, logp, logp_max, pred, weight, alpha=None):
+        self.logp, self.logp_max, self.pred, self.alpha = logp, logp_max, pred, alpha
+        self.weight = np.asarray(weight, dtype=np.float32)
+        keep = self.weight != 0
+        lp64 = logp.astype(np.float64)
+        self.score = np.where(keep, lp64, 0.0).sum(axis=1)
+        self.n_tokens = keep.sum(axis=1).astype(np.int64)
+        self.loss = float((self.weight.astype(np.float64) * -lp64).sum(axis=0).sum() / max(logp.shape[0], 1))
+
+
+def forced_from_rows(words, B, S, weight, alpha=None):
+    """The read-back words of a forced decode -- step-major [logp | logp_max | pred], each (S, B), the first two float32 bit
+    patterns -- as a ForcedScore; weight (B, S) as in ForcedScore."""
+    sb = int(S) * int(B)
+    rows = lambda k: words[k * sb:(k + 1) * sb].reshape(S, B).T.copy()
+    return ForcedScore(rows(0).view(np.float32), rows(1).view(np.float32), rows(2), weight, alpha)
+
+
+def checked_targets(y, V):
+    """y as a (B, L >= 2) int32 host array; ValueError for another shape or an id outside [0, V)."""
+    if isinstance(y, torch.Tensor):
+        y = y.detach().cpu().numpy()
+    y = np.ascontiguousarray(np.asarray(y))
+    if y.ndim != 2 or y.shape[1] < 2:
+        raise ValueError(f"score: y must be (B, L >= 2), got {tuple(y.shape)}")
+    if not np.issubdtype(y.dtype, np.integer):
+        raise ValueError(f"score: y must hold integer token ids, got {y.dtype}")
+    if y.size and (int(y.min()) < 0 or int(y.max()) >= int(V)):
+        raise ValueError(f"score: token ids must lie in [0, V = {int(V)}), got [{int(y.min())}, {int(y.max())}]")
+    return y.astype(np.int32, copy=False)
+
+
+class _PendingForced:
+    """score_async on the device path: [status word, 3 pad words, logp, logp_max, pred] (and alpha, a copy of its own) on their way into
+    pinned memory."""
+
+    def __init__(self, host, host_alpha, event, B, S, weight, keep):
+        self.host, self.host_alpha, self.event, self.args, self.keep = host, host_alpha, event, (B, S, weight), keep
+
+    def result(self):
+        self.event.synchronize()
+        self.keep = None
+        v = self.host.numpy()
+        raise_if_aborted(v[0:1].view(np.float32)[0], "score")
+        B, S, weight = self.args
+        alpha = None
+        if self.host_alpha is not None:
+            alpha = self.host_alpha.numpy().reshape(S, B, -1).transpose(1, 0, 2).copy()
+        return forced_from_rows(v[4:], B, S, weight, alpha)
+
+
 class _Ready:
     def __init__(self, value):
         self.value = value
@@ -289,6 +350,7 @@ class SpeechEncoderDecoder:
         self._side_by_main = {}
         self.mask_pad_id = None
         self._greedy_pinned = {}        # predict_async: pinned read-back buffers per slot
+        self.last_score_path = None     # "device" (astk_forced_score) | "steps": which path the last score() took
         self.last_predict_path = None   # "device" (astk_greedy_decode) | "steps" (the per-step loop): which path the last predict() took
         # Arithmetic of the batched products, per model (-> the descriptors' `precision` / `gemm_operands` fields): None = the library's
         # process-wide default (bf16x3: exact f32 operands on the 16-bit matrix pipe); "bf16x3" | "f32" | "fp16x2" (narrower, opt-in);
@@ -1030,6 +1092,89 @@ class SpeechEncoderDecoder:
                 npred += 1
             f32 = lambda r: torch.stack(r, 0).T.float().cpu().numpy()
             return ScoredPrediction(torch.stack(rows, 0).T.cpu().numpy(), f32(lps), f32(nlls) if y is not None else None, int(end_token))
+
+    def score(self, X, y, return_alpha=False):
+        """Forced decoding: the eval-mode model run along the given translations y (B, L) -- step s is fed y[:, s] and scored against
+        y[:, s + 1] -- as a ForcedScore: per-token log-probabilities, the argmax and its log-probability, PAD weights, per-row scores,
+        the teacher-forced loss and, with return_alpha, the attention rows (B, L - 1, T'').  `last_score_path` says which path ran."""
+        return self.score_async(X, y, return_alpha).result()
+
+    def score_async(self, X, y, return_alpha=False, slot=0):
+        """score() with the read-back left to the caller, like predict_scored_async: on the device path (astk_forced_score, one
+        persistent launch) ONE copy of [status, logp, logp_max, pred] into pinned buffer `slot` (alpha, when asked for, is one more
+        copy); shapes the library does not run on the device loop take the per-step loop, finished on return."""
+        y_host = checked_targets(y, self.V)
+        with using_config("train", False):
+            X = self._as_input(X)
+            self._cur = None
+            self.encode(X)
+            self.init_decoder_state()
+            B = self._cur["B"]
+            if y_host.shape[0] != B:
+                raise ValueError(f"score: y must have B = {B} rows, got {tuple(y_host.shape)}")
+            weight = (y_host[:, 1:] != 0).astype(np.float32)         # mask_pad_id[y[:, 1:]]: 0 at PAD, else 1 (materialize)
+            y_dev = torch.from_numpy(y_host).to(self.device)
+            handle = self._forced_device(y_dev, weight, bool(return_alpha), slot)
+            if handle is not None:
+                self.last_score_path = "device"
+                return handle
+            self.last_score_path = "steps"
+            return _Ready(self._score_steps(y_dev, weight, bool(return_alpha)))
+
+    def _forced_device(self, y, weight, with_alpha, slot):
+        lib = _lib.load()
+        st = self._cur
+        B, S, T2 = st["B"], int(y.shape[1]) - 1, st["T2"]
+        # (0 for shapes off the device loop and for S > ASTK_GREEDY_MAX_STEPS: the per-step loop serves those)
+        nbytes = int(lib.astk_forced_workspace_bytes(C.byref(st["dd"]), S, int(with_alpha)))
+        if nbytes == 0:
+            return None
+        ws = self._workspace("forced", nbytes)
+        # [status word (float), 3 pad words, logp | logp_max | pred, each (S, B)]: one device buffer, read back in one copy
+        sb = S * B
+        n = 4 + 3 * sb
+        out = self._pool(f"forced_out{slot}", (n,), torch.int32)
+        host = self._greedy_pinned.get(("forced", slot))
+        if host is None or host.numel() < n:
+            host = self._greedy_pinned[("forced", slot)] = torch.empty(n, dtype=torch.int32, pin_memory=True)
+        host = host[:n]
+        alpha = host_alpha = None
+        if with_alpha:
+            na = sb * T2
+            alpha = self._pool(f"forced_alpha{slot}", (na,), torch.float32)
+            host_alpha = self._greedy_pinned.get(("forced_alpha", slot))
+            if host_alpha is None or host_alpha.numel() < na:
+                host_alpha = self._greedy_pinned[("forced_alpha", slot)] = torch.empty(na, dtype=torch.float32, pin_memory=True)
+            host_alpha = host_alpha[:na]
+        base = out.data_ptr()
+        check(lib.astk_forced_score(C.byref(st["dd"]), C.byref(st["dp"]), _vp(st["enc_states"]), _vp(self._dec_c), _vp(self._dec_h),
+                                    _vp(y), S + 1, C.c_void_p(base + 16), C.c_void_p(base + 16 + 4 * sb), C.c_void_p(base + 16 + 8 * sb),
+                                    _vp(alpha), C.c_void_p(base), _vp(ws), ws.numel(), self._stream()))
+        host.copy_(out, non_blocking=True)
+        if with_alpha:
+            host_alpha.copy_(alpha, non_blocking=True)
+        ev = torch.cuda.Event()
+        ev.record(torch.cuda.current_stream(self.device))
+        return _PendingForced(host, host_alpha, ev, B, S, weight, y)
+
+    def _score_steps(self, y, weight, with_alpha):
+        """The per-step forced loop: y[:, s] through decode_step, a float64 log_softmax of each step's logits on the device."""
+        with using_config("train", False):
+            B, S = self._cur["B"], int(y.shape[1]) - 1
+            ht = torch.zeros(B, self.A, dtype=torch.float32, device=self.device)
+            lps, lpm, preds, alphas = [], [], [], []
+            for s in range(S):
+                logits, ht, al = self.decode_step(y[:, s].contiguous(), ht)
+                ls = torch.log_softmax(logits.double(), dim=1)
+                t = y[:, s + 1].long().clamp(0, self.V - 1)
+                lps.append(ls.gather(1, t[:, None])[:, 0])
+                lpm.append(ls.max(dim=1).values)
+                preds.append(logits.argmax(dim=1).to(torch.int32))
+                if with_alpha:
+                    alphas.append(al[:, :, 0])
+            f32 = lambda r: torch.stack(r, 0).T.float().cpu().numpy()
+            alpha = torch.stack(alphas, 1).cpu().numpy() if with_alpha else None
+            return ForcedScore(f32(lps), f32(lpm), torch.stack(preds, 0).T.cpu().numpy(), weight, alpha)
 
     def _predict_steps(self, start_token, end_token, stop_limit):
         """The per-step greedy loop (seq2seq.py:475-527): one astk_decoder_step_infer, an argmax and a host read per token."""

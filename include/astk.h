@@ -413,6 +413,25 @@ int astk_greedy_decode_scored(const astk_decoder_desc* d, const astk_decoder_par
                               int go, int eos, int stop_limit, const int32_t* y, int ldy, const float* class_weight, int32_t* tokens,
                               float* logp, float* nll, int32_t* n_steps, float* status_dst, void* ws, size_t ws_bytes, void* stream);
 
+/* ---------------------------------------------------------------- forced decoding on the device  (score a given translation)
+ * The eval-mode decoder run along given tokens in ONE persistent launch (the persistent decoder loop in its forced mode, after a fill
+ * launch and the encA product): step s feeds y[b][s] to row b and scores y[b][s+1], for s in [0, S), S = ldy - 1 (ids are clamped to
+ * [0, V) where they index).  There is no stop rule: every step of every row is computed.  Outputs, on the device:
+ *   logp[s][b]     = logit[y[b][s+1]] - LSE          the unweighted log-probability of the target (PAD weights are the caller's)
+ *   logp_max[s][b] = maximum logit - LSE             optional (NULL = none)
+ *   pred[s][b]     = argmax, first maximum           optional
+ *   alpha[s][b][t] = the attention row, t < d->T     optional, (S, B, d->T) dense; written by one more small launch behind the loop
+ *   status_dst     = as for astk_greedy_decode       optional
+ * y is (B, ldy) int32 on the device.  Runs where astk_greedy_workspace_bytes(d, S) is non-zero; otherwise
+ * astk_forced_workspace_bytes returns 0 and the caller scores with astk_decoder_step_infer step by step.  with_alpha != 0: the
+ * workspace also holds the raw scores (pass the same choice as alpha != NULL).  d->L and d->status_dst are ignored.  Returns < 0 with
+ * a message (and launches nothing) for a wrong struct_size, ldy outside [2, ASTK_GREEDY_MAX_STEPS + 1], a shape that does not run on
+ * the device loop, a null enc / c0 / h0 / y / logp / p or a workspace below astk_forced_workspace_bytes. */
+size_t astk_forced_workspace_bytes(const astk_decoder_desc* d, int n_steps, int with_alpha);
+int astk_forced_score(const astk_decoder_desc* d, const astk_decoder_params* p, const float* enc, const float* c0, const float* h0,
+                      const int32_t* y, int ldy, float* logp, float* logp_max, int32_t* pred, float* alpha, float* status_dst,
+                      void* ws, size_t ws_bytes, void* stream);
+
 /* ---------------------------------------------------------------- batched beam search  (nn.py:235-322 over many utterances)
  * U utterances, N hypotheses kept per utterance, K candidates per live hypothesis: every slot is one row of ONE decoder step over
  * R = U*N rows, row u*N + j = slot j of utterance u.  enc is (U, T, H): utterance u's encoder states in enc[u, 0:T''_u] (the rest

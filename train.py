@@ -12,6 +12,8 @@ if __name__ == "__main__":
     parser.add_argument("-e", "--epochs", help="num epochs", required=True)
     parser.add_argument("--dev-loss", action="store_true",
                         help="also log the free-running dev loss of the greedy decode (nmt_run.py:518-560) as a third column of the dev log")
+    parser.add_argument("--forced-dev-loss", action="store_true",
+                        help="also log the teacher-forced dev loss and perplexity of the dev references (NN.score_set) as further columns of the dev log")
     args = vars(parser.parse_args())
     cfg_path, epochs = args["cfg_path"], int(args["epochs"])
     print("number of epochs={0:d}".format(epochs))
@@ -53,14 +55,19 @@ if __name__ == "__main__":
                 preds, dev_loss = nn.predict(dev_key), None
             hyps = nn.data_loader.get_hyps(preds)
             bleu = metrics.calc_bleu(hyps) * 100
+            forced = nn.score_set(dev_key)[1:] if args["forced_dev_loss"] else None
             with open(nn.dev_log, mode="a") as f:
-                if dev_loss is None:
-                    f.write("{0:d}, {1:.2f}\n".format(epoch, bleu))
-                else:
-                    f.write("{0:d}, {1:.2f}, {2:.4f}\n".format(epoch, bleu, dev_loss))
+                line = "{0:d}, {1:.2f}".format(epoch, bleu)
+                if dev_loss is not None:
+                    line += ", {0:.4f}".format(dev_loss)
+                if forced is not None:
+                    line += ", {0:.4f}, {1:.4f}".format(*forced)
+                f.write(line + "\n")
             print("BLEU = {0:.2f}".format(bleu))
             if dev_loss is not None:
                 print("dev loss = {0:.4f}".format(dev_loss))
+            if forced is not None:
+                print("forced dev loss = {0:.4f}, perplexity = {1:.4f}".format(*forced))
         if (epoch % iters_save == 0 or epoch == max_epoch - 1) and adist.rank() == 0:
             print("Saving model")
             serializers.save_npz(nn.model_fname.replace(".model", "_{0:d}.model".format(epoch)), nn.model,
