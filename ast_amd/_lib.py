@@ -174,6 +174,11 @@ SIGNATURES = {
     "astk_greedy_scored_workspace_bytes": (_SZ, [C.POINTER(DecoderDesc), _I]),
     "astk_greedy_decode_scored": (C.c_int, [C.POINTER(DecoderDesc), C.POINTER(DecoderParams), _VP, _VP, _VP, _I, _I, _I, _VP, _I, _VP, _VP, _VP,
                                             _VP, _VP, _VP, _VP, _SZ, _VP]),
+    "astk_sample_workspace_bytes": (_SZ, [C.POINTER(DecoderDesc), _I]),
+    "astk_sample_decode": (C.c_int, [C.POINTER(DecoderDesc), C.POINTER(DecoderParams), _VP, _VP, _VP, _I, _I, _I, _VP, _F, _VP, _VP, _VP, _VP,
+                                     _VP, _SZ, _VP]),
+    "astk_gumbel_rows": (C.c_int, [_VP, _I, _I, _I, _VP, _VP]),
+    "astk_sample_row_key": (_U64, [_U64, _U64]),
     "astk_forced_workspace_bytes": (_SZ, [C.POINTER(DecoderDesc), _I, _I]),
     "astk_forced_score": (C.c_int, [C.POINTER(DecoderDesc), C.POINTER(DecoderParams), _VP, _VP, _VP, _VP, _I, _VP, _VP, _VP, _VP, _VP, _VP, _SZ,
                                     _VP]),

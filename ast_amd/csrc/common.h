@@ -655,4 +655,22 @@ static inline dim3 colreduce_grid(int rows, int cols, bool float_sums = false) {
   return dim3((unsigned)gx, (unsigned)gy);
 }
 
+// ---- counter-based RNG: the splitmix64 finaliser (util.hip's dropout / noise fills, the sampled decoder loop)
+static inline __host__ __device__ uint64_t mix64(uint64_t z) {
+  z += 0x9E3779B97F4A7C15ull;
+  z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ull;
+  z = (z ^ (z >> 27)) * 0x94D049BB133111EBull;
+  return z ^ (z >> 31);
+}
+// Sampled decoding (include/astk.h "sampled decoding on the device"): the key of a batch row, and the Gumbel noise of (row key, decoder
+// step s, class id n) -- the ONE definition that the persistent loop's P5 and k_gumbel_rows both draw from.
+//   u = (float)((word >> 40) + 1) * c, c = the float32 next to 1 / 16777217 = 2^-24 (1 - 2^-24): u lies in [c, 1 - 2^-24], never 0 or 1
+//   g = -ln(-ln(u)): logf of the device library both times (1 ulp; the inner one stays accurate at u -> 1, where a bare log2 does not)
+static inline __host__ __device__ uint64_t sample_row_key(uint64_t seed, uint64_t stream) { return mix64(seed ^ mix64(stream)); }
+__device__ __forceinline__ float sample_u01(uint64_t word) { return (float)((unsigned)(word >> 40) + 1u) * 0x1.fffffep-25f; }
+__device__ __forceinline__ float sample_gumbel(uint64_t row_key, int s, int n) {
+  const uint64_t word = mix64(row_key ^ ((uint64_t)(unsigned)s << 32 | (uint64_t)(unsigned)n));
+  return -logf(-logf(sample_u01(word)));
+}
+
 }  // namespace astk

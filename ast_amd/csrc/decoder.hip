@@ -51,6 +51,11 @@ size_t greedy_scored_workspace_bytes(const astk_decoder_desc* d, int stop_limit)
 int greedy_decode_scored_launch(const astk_decoder_desc* d, const astk_decoder_params* prm, const float* enc, const float* c0, const float* h0,
                                 int go, int eos, int stop_limit, const int32_t* y, int ldy, const float* class_weight, int32_t* tokens,
                                 float* logp, float* nll, int32_t* n_steps, float* status_dst, void* ws, size_t ws_bytes, hipStream_t s);
+size_t sample_workspace_bytes(const astk_decoder_desc* d, int stop_limit);
+int sample_decode_launch(const astk_decoder_desc* d, const astk_decoder_params* prm, const float* enc, const float* c0, const float* h0, int go,
+                         int eos, int stop_limit, const uint64_t* row_keys, float inv_temp, int32_t* tokens, float* logp, int32_t* n_steps,
+                         float* status_dst, void* ws, size_t ws_bytes, hipStream_t s);
+int gumbel_rows_launch(const uint64_t* row_keys, int B, int step, int V, float* out, hipStream_t s);
 size_t forced_workspace_bytes(const astk_decoder_desc* d, int n_steps, int with_alpha);
 int forced_score_launch(const astk_decoder_desc* d, const astk_decoder_params* prm, const float* enc, const float* c0, const float* h0,
                         const int32_t* y, int ldy, float* logp, float* logp_max, int32_t* pred, float* alpha, float* status_dst, void* ws,
@@ -993,6 +998,21 @@ int astk_greedy_decode_scored(const astk_decoder_desc* d, const astk_decoder_par
   return greedy_decode_scored_launch(d, p, enc, c0, h0, go, eos, stop_limit, y, ldy, class_weight, tokens, logp, nll, n_steps, status_dst, ws,
                                      ws_bytes, (hipStream_t)stream);
 }
+
+size_t astk_sample_workspace_bytes(const astk_decoder_desc* d, int stop_limit) { return sample_workspace_bytes(d, stop_limit); }
+
+int astk_sample_decode(const astk_decoder_desc* d, const astk_decoder_params* p, const float* enc, const float* c0, const float* h0,
+                       int go, int eos, int stop_limit, const uint64_t* row_keys, float inv_temp, int32_t* tokens, float* logp,
+                       int32_t* n_steps, float* status_dst, void* ws, size_t ws_bytes, void* stream) {
+  return sample_decode_launch(d, p, enc, c0, h0, go, eos, stop_limit, row_keys, inv_temp, tokens, logp, n_steps, status_dst, ws, ws_bytes,
+                              (hipStream_t)stream);
+}
+
+int astk_gumbel_rows(const uint64_t* row_keys, int B, int step, int V, float* out, void* stream) {
+  return gumbel_rows_launch(row_keys, B, step, V, out, (hipStream_t)stream);
+}
+
+uint64_t astk_sample_row_key(uint64_t seed, uint64_t stream) { return sample_row_key(seed, stream); }
 
 size_t astk_forced_workspace_bytes(const astk_decoder_desc* d, int n_steps, int with_alpha) {
   return forced_workspace_bytes(d, n_steps, with_alpha);

@@ -96,6 +96,9 @@ struct PDecArgs {
                            // [2] workgroups that left, [3] the stop word (n_steps; preset to S)
   int32_t* n_steps_out;    // written by the last workgroup to leave: the stop word
   float* status_dst;       // ... and a copy of the persistent status word (or null)
+  // sampled mode (SM): Gumbel-max draws from softmax(logits * inv_temp); LSE = LOGP [S][B] as in the scored mode
+  const uint64_t* row_keys;   // [B] sample_row_key(seed, stream) of every batch row
+  float inv_temp;
 };
 
 __device__ __forceinline__ unsigned ld_flag(const unsigned* p) { return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
@@ -296,6 +299,20 @@ static_assert(OFF_WL + 2 * NB_L <= NWREG, "register budget");
 constexpr int CELLW2 = 2 * NB_H, OFF_C2 = 2 * CELLW2, NWREG_ML = 4 * CELLW2;
 static_assert(OFF_WL + 2 * NB_L <= OFF_C2, "register budget");
 
+// sampled mode: the batch rows' keys, 256 bytes of LDS that only the sampled instantiations have.  One slot per batch row of the device
+// loop: greedy_plan() refuses B > PDEC_SM_ROWS, so a row index is a slot index (raise the two together).
+constexpr int PDEC_SM_ROWS = 32;
+__device__ __forceinline__ uint64_t* sm_row_keys() {
+  __shared__ uint64_t keys[PDEC_SM_ROWS];
+  return keys;
+}
+// ... and the CE role's sticky per-row done flags: one word per row of the batch tile, read and written by that row's thread sub == 0
+// alone (in the 3-layer instantiation, all 512 registers taken, the flag was spilled as a register: a scratch round trip per step in P6)
+__device__ __forceinline__ int* sm_row_done() {
+  __shared__ int done[16];
+  return done;
+}
+
 template <int NB>
 __device__ __forceinline__ void mfma_blocks(f32x4& acc, const float4* a, const float4* w) {
   f32x4 acc2 = {0.f, 0.f, 0.f, 0.f};
@@ -329,10 +346,17 @@ __device__ __forceinline__ void mfma_blocks(f32x4& acc, const float4* a, const f
 // workgroup runs all S steps.  P5 keeps what the scored mode keeps; P6 stores LOGP = log p(y[b][s+1]) (PDecArgs: LSE), the confidence
 // max logit - LSE (LOSSROWS, or null) and the argmax (PRED, or null).  With ALPHA / ML given, the attention and combine roles store the
 // raw scores and (max, 1 / sum) as the training mode does; k_alpha_normalise turns them into alpha behind the loop.  DESIGN.md section 13.
-template <int NC, int NL, bool XS, bool GR, bool SC = false, bool FD = false>
+// SM (with GR and SC, without FD): sampled decoding -- ancestral sampling by the Gumbel-max identity.  P5 perturbs the tempered logit
+// xs = x * inv_temp with the noise of (row key, step, class) (common.h sample_gumbel) and keeps the tile's winner by z = xs + g, xs at that
+// winner, and the tile's sum of exp(xs - xs at the winner) (g lies in [-2.9, 16.7]: the winner's xs is within 20 of the tile's largest, the
+// sum cannot overflow) -- the four words of the tile record, as before.  P6 merges the winner by z and the sums relative to the largest
+// reference, stores the token and LOGP = (xs_tok - ref) - logf(se), then runs the greedy branch on the SAMPLED token as it stands: no wait,
+// arrival, counter or exit condition is added.  DESIGN.md section 14.
+template <int NC, int NL, bool XS, bool GR, bool SC = false, bool FD = false, bool SM = false>
 __device__ __forceinline__ void decoder_persist_fwd_body(const PDecArgs& a) {
   static_assert(GR || !SC, "the scored mode is a greedy mode");
   static_assert(!FD || (GR && SC), "the forced mode builds on the scored inference mode");
+  static_assert(!SM || (GR && SC && !FD), "the sampled mode builds on the scored greedy mode");
   constexpr bool STOP = GR && !FD;         // the greedy modes' stop word exists
   constexpr bool SUMS = !GR || SC;         // P5 / P6 keep the sum of exponentials and the target logit
   extern __shared__ __attribute__((aligned(16))) float lds[];   // enc slice [chunk][H], encA slice [chunk][H], scratch
@@ -345,6 +369,9 @@ __device__ __forceinline__ void decoder_persist_fwd_body(const PDecArgs& a) {
   __shared__ int s_wdone[4];               // GR: per wave of the CE role, all of its rows are done
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   if (GR && tid == 0) s_stop = 0;          // (the first barrier below orders it before every use)
+  if constexpr (SM) {
+    if (tid < PDEC_SM_ROWS) sm_row_keys()[tid] = a.row_keys[min(tid, a.B - 1)];     // (ordered by that barrier too; B <= PDEC_SM_ROWS)
+  }
   const int wg = blockIdx.x;
   const int B = a.B, S = a.S, H = a.H, E = a.E, A = a.A, V = a.V, XI = a.XI, T = a.T, Tp = a.Tp;
   const int nbt = a.nbt;
@@ -492,13 +519,16 @@ __device__ __forceinline__ void decoder_persist_fwd_body(const PDecArgs& a) {
 #define TICK(i) if (timing) { const long long now_ = wall_clock64(); tk[i] += now_ - tlast; tlast = now_; }
   int p6_pending = -1;
   bool row_done = ce_rank * 16 + (tid >> 4) >= B;     // GR, CE role: sticky "this thread's row has emitted EOS" (padding rows: done)
+  if constexpr (SM) {
+    if ((tid & 15) == 0) sm_row_done()[tid >> 4] = row_done ? 1 : 0;
+  }
   bool tile_done = false;                             // GR, CE role (thread 0): this batch tile has reported
   auto run_p6 = [&](const int s) -> bool {
       const int bt = ce_rank, m0 = bt * 16;
       const int row = m0 + (tid >> 4), sub = tid & 15;       // 16 threads per row sweep the tiles
       [[maybe_unused]] bool sc_tgt = false;                  // SC: step s has a target (column s+1 of y); its class weight
       [[maybe_unused]] float sc_w = 0.f;
-      if constexpr (SC && !FD) {       // (read in front of the wait: neither load is on the chain)
+      if constexpr (SC && !FD && !SM) {       // (read in front of the wait: neither load is on the chain)
         sc_tgt = a.ytgt && s + 1 < a.L;
         if (sc_tgt && sub == 0 && row < B) {
           int r = row;
@@ -510,26 +540,42 @@ __device__ __forceinline__ void decoder_persist_fwd_body(const PDecArgs& a) {
       if (!wg_wait_sh(CTR(PH_LOG, bt), a.ntile_v, s + 1, a.ab, &s_flag, StopCtl{STOP ? a.gctl + 3 * CTRS : nullptr, s, false})) return false;
       float mx = -INFINITY, se = 0.f, xt = 0.f;
       int mi = 0x7fffffff;
+      [[maybe_unused]] float rf = -INFINITY;                 // SM: the reference of `se` (the largest winner's xs merged so far)
       if (row < B)
         for (int k = sub; k < a.ntile_v; k += 16) {
           const float4 cs = ldb128_sc1(r_ces, (((long)s * B + row) * a.ntile_v + k) * 4);
           const float tm = cs.x, ts = cs.y, tx = cs.w;
           const int ti = __float_as_int(cs.z);
-          const float nm = fmaxf(mx, tm);
-          if constexpr (SUMS) se = se * expf(mx - nm) + ts * expf(tm - nm);
-          if (tm > mx || (tm == mx && ti < mi)) mi = ti;
-          mx = nm;
-          xt += tx;
+          if constexpr (SM) {          // record: (z of the winner, sum of exp(xs - tx), index, tx = xs at the winner); xt = xs of the winner so far
+            const float nr = fmaxf(rf, tx);
+            se = (rf == -INFINITY ? 0.f : se * expf(rf - nr)) + ts * expf(tx - nr);
+            rf = nr;
+            if (tm > mx || (tm == mx && ti < mi)) { mi = ti; mx = tm; xt = tx; }
+          } else {
+            const float nm = fmaxf(mx, tm);
+            if constexpr (SUMS) se = se * expf(mx - nm) + ts * expf(tm - nm);
+            if (tm > mx || (tm == mx && ti < mi)) mi = ti;
+            mx = nm;
+            xt += tx;
+          }
         }
 #pragma unroll
       for (int o = 8; o > 0; o >>= 1) {
         const float om = __shfl_xor(mx, o), os = __shfl_xor(se, o), ox = __shfl_xor(xt, o);
         const int oi = __shfl_xor(mi, o);
-        const float nm = fmaxf(mx, om);
-        if constexpr (SUMS) se = (mx == -INFINITY ? 0.f : se * expf(mx - nm)) + (om == -INFINITY ? 0.f : os * expf(om - nm));
-        if (om > mx || (om == mx && oi < mi)) mi = oi;
-        mx = nm;
-        xt += ox;
+        if constexpr (SM) {
+          const float orf = __shfl_xor(rf, o);
+          const float nr = fmaxf(rf, orf);
+          se = (rf == -INFINITY ? 0.f : se * expf(rf - nr)) + (orf == -INFINITY ? 0.f : os * expf(orf - nr));
+          rf = nr;
+          if (om > mx || (om == mx && oi < mi)) { mi = oi; mx = om; xt = ox; }
+        } else {
+          const float nm = fmaxf(mx, om);
+          if constexpr (SUMS) se = (mx == -INFINITY ? 0.f : se * expf(mx - nm)) + (om == -INFINITY ? 0.f : os * expf(om - nm));
+          if (om > mx || (om == mx && oi < mi)) mi = oi;
+          mx = nm;
+          xt += ox;
+        }
       }
       if constexpr (FD) {
         if (sub == 0 && row < B) {
@@ -549,16 +595,34 @@ __device__ __forceinline__ void decoder_persist_fwd_body(const PDecArgs& a) {
             const float lg = logf(se);
             int r = row;
             asm volatile("" : "+v"(r));     // (as above)
-            *ua(a.LSE + (long)s * B, (unsigned)r) = -lg;
-            if (a.LOSSROWS) *ua(a.LOSSROWS + (long)s * B, (unsigned)r) = sc_tgt ? sc_w * ((mx - xt) + lg) : 0.f;
+            if constexpr (SM) {
+              // log p(token) under softmax(xs) = xs_tok - lse, lse = rf + logf(se): formed as (xs_tok - rf) - logf(se), likewise
+              *ua(a.LSE + (long)s * B, (unsigned)r) = (xt - rf) - lg;
+            } else {
+              *ua(a.LSE + (long)s * B, (unsigned)r) = -lg;
+              if (a.LOSSROWS) *ua(a.LOSSROWS + (long)s * B, (unsigned)r) = sc_tgt ? sc_w * ((mx - xt) + lg) : 0.f;
+            }
             sti_sc1(ua(a.PRED + (long)s * B, (unsigned)r), mi);
-            row_done = row_done || mi == a.eos;
+            if constexpr (SM) {
+              if (mi == a.eos) {
+                int i = tid >> 4;
+                asm volatile("" : "+v"(i));   // (as above: the LDS address formed here, not kept over the loop and spilled)
+                sm_row_done()[i] = 1;
+              }
+            }
+            else row_done = row_done || mi == a.eos;
           }
         } else if (sub == 0 && row < B) {
           sti_sc1(ua(a.PRED + (long)s * B, (unsigned)row), mi);
           row_done = row_done || mi == a.eos;
         }
-        const bool wdone = __all(sub != 0 || row_done);
+        bool wdone;
+        if constexpr (SM) {
+          int i = tid >> 4;
+          asm volatile("" : "+v"(i));         // (likewise)
+          wdone = __all(sub != 0 || sm_row_done()[i] != 0);
+        }
+        else wdone = __all(sub != 0 || row_done);
         if (lane == 0) s_wdone[wave] = wdone ? 1 : 0;
         // publish_sh() with the tile's report between its barrier and its arrival: the stop word is written in front of PH_CE(s)
         asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
@@ -1104,7 +1168,7 @@ __device__ __forceinline__ void decoder_persist_fwd_body(const PDecArgs& a) {
       const int bt = l_item[t] / a.ntile_v, tile = l_item[t] % a.ntile_v, m0 = bt * 16, n0 = tile * 16;
       TICK(15)
       [[maybe_unused]] int sc_tgt = -1;          // SC: this row's target of step s, read in front of the wait (-1: none)
-      if constexpr (SC) {
+      if constexpr (SC && !SM) {
         int r = m0 + (tid >> 4);
         asm volatile("" : "+v"(r));         // (keeps the address out of the loop-invariant registers: they are full, it would spill)
         if (a.ytgt && s + 1 < a.L && r < B) sc_tgt = *ua(a.ytgt + s + 1, (unsigned)(r * a.L));
@@ -1124,23 +1188,39 @@ __device__ __forceinline__ void decoder_persist_fwd_body(const PDecArgs& a) {
       }
       float mx = x;
       int mi = n;
-#pragma unroll
-      for (int o = 8; o > 0; o >>= 1) {
-        const float om = __shfl_xor(mx, o);
-        const int oi = __shfl_xor(mi, o);
-        if (om > mx || (om == mx && oi < mi)) { mx = om; mi = oi; }
-      }
       float se = 0.f, xt = 0.f;
-      if constexpr (SUMS) {
-        se = ok ? expf(x - mx) : 0.f;
+      if constexpr (SM) {
+        // the draw: the tile's first maximum of z = xs + g; xt = xs at that winner, the reference of the tile's sum of exponentials
+        const float xs = x * a.inv_temp;                     // (-inf stays -inf: inv_temp > 0)
+        mx = ok ? xs + sample_gumbel(sm_row_keys()[row & (PDEC_SM_ROWS - 1)], s, n) : -INFINITY;      // (the key from LDS, here: 64 bits held over the wait spill)
+        xt = xs;
+#pragma unroll
+        for (int o = 8; o > 0; o >>= 1) {
+          const float om = __shfl_xor(mx, o), ox = __shfl_xor(xt, o);
+          const int oi = __shfl_xor(mi, o);
+          if (om > mx || (om == mx && oi < mi)) { mx = om; mi = oi; xt = ox; }
+        }
+        se = ok ? expf(xs - xt) : 0.f;
 #pragma unroll
         for (int o = 8; o > 0; o >>= 1) se += __shfl_xor(se, o);
-        int tgt;
-        if constexpr (SC) tgt = sc_tgt;
-        else tgt = row < B ? *ua(a.ytgt + s + 1, (unsigned)(row * a.L)) : 0;
-        xt = (ok && n == tgt) ? x : 0.f;
+      } else {
 #pragma unroll
-        for (int o = 8; o > 0; o >>= 1) xt += __shfl_xor(xt, o);
+        for (int o = 8; o > 0; o >>= 1) {
+          const float om = __shfl_xor(mx, o);
+          const int oi = __shfl_xor(mi, o);
+          if (om > mx || (om == mx && oi < mi)) { mx = om; mi = oi; }
+        }
+        if constexpr (SUMS) {
+          se = ok ? expf(x - mx) : 0.f;
+#pragma unroll
+          for (int o = 8; o > 0; o >>= 1) se += __shfl_xor(se, o);
+          int tgt;
+          if constexpr (SC) tgt = sc_tgt;
+          else tgt = row < B ? *ua(a.ytgt + s + 1, (unsigned)(row * a.L)) : 0;
+          xt = (ok && n == tgt) ? x : 0.f;
+#pragma unroll
+          for (int o = 8; o > 0; o >>= 1) xt += __shfl_xor(xt, o);
+        }
       }
       if ((tid & 15) == 0 && row < B) {
         float* cs = ua(a.CESTAT + ((long)s * B * a.ntile_v + tile) * 4, (unsigned)(row * a.ntile_v * 4));
@@ -1203,6 +1283,20 @@ template <int NC, int NL, bool XS>
 __global__ __launch_bounds__(256, 1) void decoder_persist_greedy_scored(PDecArgs a) {
   decoder_persist_fwd_body<NC, NL, XS, true, true>(a);
   greedy_last_out(a);
+}
+
+// The sampled mode as a kernel of its own, likewise: the greedy modes' control words and exit as they are.
+template <int NC, int NL, bool XS>
+__global__ __launch_bounds__(256, 1) void decoder_persist_sampled(PDecArgs a) {
+  decoder_persist_fwd_body<NC, NL, XS, true, true, false, true>(a);
+  greedy_last_out(a);
+}
+
+// out[b][n] = the Gumbel noise of (row_keys[b], step, n), n < V: one decoder step's draws as a dense (B, V) buffer, through the function
+// the loop's P5 calls (the per-step sampled loop and the tests read it)
+__global__ __launch_bounds__(256) void k_gumbel_rows(const uint64_t* __restrict__ row_keys, int step, int V, float* __restrict__ out) {
+  const int b = blockIdx.y, n = blockIdx.x * 256 + threadIdx.x;
+  if (n < V) out[(long)b * V + n] = sample_gumbel(row_keys[b], step, n);
 }
 
 // The forced mode as a kernel of its own, likewise.  Of the greedy modes' control words it keeps one, the exit count (gctl[2]): the last
@@ -1988,6 +2082,19 @@ static void pdec_launch_scored(bool special, bool xs, size_t shm, hipStream_t s,
   else hipLaunchKernelGGL((decoder_persist_greedy_scored<0, NL, false>), dim3(G), dim3(256), shm, s, a);
 }
 template <int NL>
+static void pdec_launch_sampled(bool special, bool xs, size_t shm, hipStream_t s, const PDecArgs& a) {
+  static bool attr_done = false;
+  if (!attr_done) {
+    (void)hipFuncSetAttribute((const void*)decoder_persist_sampled<0, NL, false>, hipFuncAttributeMaxDynamicSharedMemorySize, 138 * 1024);
+    (void)hipFuncSetAttribute((const void*)decoder_persist_sampled<8, NL, false>, hipFuncAttributeMaxDynamicSharedMemorySize, 138 * 1024);
+    (void)hipFuncSetAttribute((const void*)decoder_persist_sampled<8, NL, true>, hipFuncAttributeMaxDynamicSharedMemorySize, 138 * 1024);
+    attr_done = true;
+  }
+  if (special && xs) hipLaunchKernelGGL((decoder_persist_sampled<8, NL, true>), dim3(G), dim3(256), shm, s, a);
+  else if (special) hipLaunchKernelGGL((decoder_persist_sampled<8, NL, false>), dim3(G), dim3(256), shm, s, a);
+  else hipLaunchKernelGGL((decoder_persist_sampled<0, NL, false>), dim3(G), dim3(256), shm, s, a);
+}
+template <int NL>
 static void pdec_launch_forced(bool special, bool xs, size_t shm, hipStream_t s, const PDecArgs& a) {
   static bool attr_done = false;
   if (!attr_done) {
@@ -2159,7 +2266,8 @@ static size_t greedy_ctr_lines(int B) { return (size_t)NPHASE_SLOTS * NSH * ((B 
 
 static bool greedy_plan(const astk_decoder_desc* d0, int stop_limit, void* ws, GreedyPlan& g) {
   if (!d0 || d0->struct_size != sizeof(astk_decoder_desc)) return false;
-  if (stop_limit < 1 || stop_limit > ASTK_GREEDY_MAX_STEPS || d0->B < 1 || d0->B > 32 || d0->T < 1 || d0->V < 2) return false;
+  static_assert((PDEC_SM_ROWS & (PDEC_SM_ROWS - 1)) == 0 && PDEC_SM_ROWS <= 256, "sampled mode: the row mask and the one-thread-per-key load");
+  if (stop_limit < 1 || stop_limit > ASTK_GREEDY_MAX_STEPS || d0->B < 1 || d0->B > PDEC_SM_ROWS || d0->T < 1 || d0->V < 2) return false;
   astk_decoder_desc d = *d0;
   d.L = stop_limit + 1;
   if (!pdec_applicable(&d, ASTK_GREEDY_MAX_STEPS + 1, &g.nsplit, &g.chunk)) return false;
@@ -2233,7 +2341,7 @@ static int inference_fill(const astk_decoder_desc* d, const PDecArgs& a, const G
   return 0;
 }
 
-enum InferenceMode { INF_GREEDY, INF_SCORED, INF_FORCED };
+enum InferenceMode { INF_GREEDY, INF_SCORED, INF_FORCED, INF_SAMPLED };
 static void inference_launch(InferenceMode mode, const astk_decoder_desc* d, const PDecArgs& a, const GreedyPlan& g, hipStream_t s) {
   const size_t shm = pdec_lds_floats(g.chunk, a.H, g.nsplit) * sizeof(float);
   const bool special = pdec_special(a.H, g.chunk);
@@ -2242,6 +2350,10 @@ static void inference_launch(InferenceMode mode, const astk_decoder_desc* d, con
     if (d->n_layers == 1) pdec_launch_forced<1>(special, xs, shm, s, a);
     else if (d->n_layers == 2) pdec_launch_forced<2>(special, xs, shm, s, a);
     else pdec_launch_forced<3>(special, xs, shm, s, a);
+  } else if (mode == INF_SAMPLED) {
+    if (d->n_layers == 1) pdec_launch_sampled<1>(special, xs, shm, s, a);
+    else if (d->n_layers == 2) pdec_launch_sampled<2>(special, xs, shm, s, a);
+    else pdec_launch_sampled<3>(special, xs, shm, s, a);
   } else if (mode == INF_SCORED) {
     if (d->n_layers == 1) pdec_launch_scored<1>(special, xs, shm, s, a);
     else if (d->n_layers == 2) pdec_launch_scored<2>(special, xs, shm, s, a);
@@ -2258,6 +2370,8 @@ struct GreedyScoredIO {
   const int32_t* y; int ldy;       // targets [B][ldy] or null
   const float* class_weight;       // [V] or null = all 1
   float *logp, *nll;               // [stop_limit][B]; nll null iff y is null
+  const uint64_t* row_keys;        // sampled mode: [B] row keys (null: the scored greedy mode) and 1 / temperature
+  float inv_temp;
 };
 // sc: null for the unscored kernel
 static int greedy_launch(const astk_decoder_desc* d, const astk_decoder_params* prm, const float* enc, const float* c0, const float* h0, int go,
@@ -2287,9 +2401,10 @@ static int greedy_launch(const astk_decoder_desc* d, const astk_decoder_params* 
   a.n_steps_out = n_steps; a.status_dst = status_dst;
   if (sc) {
     a.LSE = sc->logp; a.LOSSROWS = sc->nll; a.ytgt = sc->y; a.L = sc->y ? sc->ldy : 1; a.cw = sc->class_weight;
+    a.row_keys = sc->row_keys; a.inv_temp = sc->inv_temp;
   }
   ASTK_TRY(inference_fill(d, a, g, h0, s));
-  inference_launch(sc ? INF_SCORED : INF_GREEDY, d, a, g, s);
+  inference_launch(!sc ? INF_GREEDY : (sc->row_keys ? INF_SAMPLED : INF_SCORED), d, a, g, s);
   ASTK_LAUNCH_CHECK();
   return 0;
 }
@@ -2302,8 +2417,31 @@ int greedy_decode_launch(const astk_decoder_desc* d, const astk_decoder_params* 
 int greedy_decode_scored_launch(const astk_decoder_desc* d, const astk_decoder_params* prm, const float* enc, const float* c0, const float* h0,
                                 int go, int eos, int stop_limit, const int32_t* y, int ldy, const float* class_weight, int32_t* tokens,
                                 float* logp, float* nll, int32_t* n_steps, float* status_dst, void* ws, size_t ws_bytes, hipStream_t s) {
-  const GreedyScoredIO sc{y, ldy, class_weight, logp, nll};
+  const GreedyScoredIO sc{y, ldy, class_weight, logp, nll, nullptr, 1.f};
   return greedy_launch(d, prm, enc, c0, h0, go, eos, stop_limit, &sc, tokens, n_steps, status_dst, ws, ws_bytes, s);
+}
+
+// ---------------------------------------------------------------------------------------------------- sampled decoding
+// decoder_persist_sampled on the greedy plan as it is: the tile record keeps its four words (z, se relative to xs at the winner, index, xs
+// at the winner), so the workspace is the greedy modes'.
+size_t sample_workspace_bytes(const astk_decoder_desc* d, int stop_limit) { return greedy_workspace_bytes(d, stop_limit); }
+
+int sample_decode_launch(const astk_decoder_desc* d, const astk_decoder_params* prm, const float* enc, const float* c0, const float* h0, int go,
+                         int eos, int stop_limit, const uint64_t* row_keys, float inv_temp, int32_t* tokens, float* logp, int32_t* n_steps,
+                         float* status_dst, void* ws, size_t ws_bytes, hipStream_t s) {
+  ASTK_CHECK(row_keys, "sample_decode: null pointer (row_keys)");
+  ASTK_CHECK(logp, "sample_decode: null pointer (logp)");
+  ASTK_CHECK(inv_temp > 0.f && inv_temp <= 3.402823466e38f, "sample_decode: inv_temp %g is not a finite number above 0", (double)inv_temp);
+  const GreedyScoredIO sc{nullptr, 0, nullptr, logp, nullptr, row_keys, inv_temp};
+  return greedy_launch(d, prm, enc, c0, h0, go, eos, stop_limit, &sc, tokens, n_steps, status_dst, ws, ws_bytes, s);
+}
+
+int gumbel_rows_launch(const uint64_t* row_keys, int B, int step, int V, float* out, hipStream_t s) {
+  ASTK_CHECK(row_keys && out, "gumbel_rows: null pointer");
+  ASTK_CHECK(B >= 1 && B <= 65535 && V >= 1 && step >= 0, "gumbel_rows: B %d outside [1, 65535], V %d < 1 or step %d < 0", B, V, step);
+  hipLaunchKernelGGL(k_gumbel_rows, dim3((V + 255) / 256, B), dim3(256), 0, s, row_keys, step, V, out);
+  ASTK_LAUNCH_CHECK();
+  return 0;
 }
 
 // ---------------------------------------------------------------------------------------------------- forced decoding

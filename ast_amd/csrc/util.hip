@@ -278,13 +278,10 @@ __global__ void k_scale(float* x, size_t n, float s) {
 }
 
 // ---- counter-based RNG (splitmix64 finaliser over (seed, counter)); quality is ample for dropout / noise
-__device__ __forceinline__ uint64_t mix64(uint64_t z) {
-  z += 0x9E3779B97F4A7C15ull;
-  z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ull;
-  z = (z ^ (z >> 27)) * 0x94D049BB133111EBull;
-  return z ^ (z >> 31);
-}
-__device__ __forceinline__ float u01(uint64_t bits) { return (float)((bits >> 40) + 1) * (1.0f / 16777217.0f); }  // (0,1)
+// (mix64 itself lives in common.h: the sampled decoder loop draws from it too)
+// (the divisor rounds to 2^24 in float32: the factor is 2^-24 and the range (0, 1], 1.0 included.  common.h's sample_u01 uses the float32
+//  next to 1 / 16777217 instead, as the sampled decode's contract pins it.  The two are NOT to be unified: these bits are training behaviour.)
+__device__ __forceinline__ float u01(uint64_t bits) { return (float)((bits >> 40) + 1) * (1.0f / 16777217.0f); }  // (0,1]
 
 // Dropout keep-masks: element i of a fill is a function of (seed, g = offset + i) alone -- the two halves of ONE 64-bit hash of the pair
 // g >> 1 serve the counters 2 (g >> 1) and 2 (g >> 1) + 1 (round 5: the hash is 16 quarter-rate integer multiplies, and one hash per

@@ -177,6 +177,49 @@ def score_hypotheses(model, X, hyps, return_alpha=False):
     return [float(r.logp[i, :len(h) - 1].astype(np.float64).sum()) for i, h in enumerate(hyps)], r
 
 
+# ---- ancestral sampling: n scored samples of one utterance, and a minimum-Bayes-risk choice among them
+def cut_at_eos(tokens, end_token=SYMBOLS.EOS_ID):
+    """A decoded row as a token list cut behind its first `end_token`, keeping it (the whole row when it has none)."""
+    toks = [int(t) for t in tokens]
+    return toks[:toks.index(end_token) + 1] if end_token in toks else toks
+
+
+def sample_hypotheses(model, X, n, stop_limit, seed, temperature=1.0, first_stream=0):
+    """n samples of ONE utterance X (1, T, D), drawn by SpeechEncoderDecoder.sample from the streams first_stream .. first_stream + n - 1
+    of `seed`: X is repeated over the rows (the encoding decode_beam sees, as in score_hypotheses), at most 32 rows -- the device
+    loop's batch -- per call.  Returns a list in stream order of {"hyp": [GO, t1, .., tk], "score": float}, each cut behind its first
+    EOS and keeping it, like decode_beam's entries; score = the log-probability of t1..tk under the sampled distribution.  A stream's
+    sample does not depend on n or on its row, so a list can be extended later from first_stream = n."""
+    X = model._as_input(X)
+    if X.dim() == 2:
+        X = X[None]
+    out = []
+    for lo in range(0, int(n), 32):
+        m = min(32, int(n) - lo)
+        r = model.sample(X.expand(m, -1, -1), SYMBOLS.GO_ID, SYMBOLS.EOS_ID, stop_limit, seed,
+                         streams=range(first_stream + lo, first_stream + lo + m), temperature=temperature)
+        out.extend({"hyp": [SYMBOLS.GO_ID] + cut_at_eos(r.tokens[i]), "score": float(r.score[i])} for i in range(m))
+    return out
+
+
+def mbr_select(hyps):
+    """Minimum-Bayes-risk choice among samples (entries with "hyp" and "score", as sample_hypotheses returns): the index of the
+    candidate with the highest mean sentence BLEU (ast_amd.eval.corpus_bleu, smoothed) against every OTHER sample as its reference.
+    Ties go to the higher score, then to the lower index; a single hypothesis is its own choice.  Host only."""
+    from .eval import corpus_bleu
+    if not hyps:
+        raise ValueError("mbr_select: no hypotheses")
+    toks = [list(h["hyp"]) for h in hyps]
+    best = None
+    for i, cand in enumerate(toks):
+        others = [r for j, r in enumerate(toks) if j != i]
+        gain = sum(corpus_bleu([[r]], [cand]) for r in others) / len(others) if others else 0.0
+        key = (gain, float(hyps[i]["score"]), -i)
+        if best is None or key > best[0]:
+            best = (key, i)
+    return best[1]
+
+
 def _init_hyp_from(model, enc_states):
     return {"hyp": [SYMBOLS.GO_ID], "score": 0, "dec_state": enc_states,
             "attn_v": torch.zeros(1, model.cfg["rnn_config"]["attn_units"], dtype=torch.float32, device=model.device), "attn_history": []}
@@ -380,6 +423,20 @@ class NN:
             if pending is not None:
                 settle(pending)
         return preds, (sum(losses) / len(losses) if losses else 0.0), scores
+
+    def sample_set(self, set_key, n, seed, temperature=1.0):
+        """n samples of every utterance of a set (sample_hypotheses; utterance k of the set, in the loader's order, draws from the
+        streams k * n .. k * n + n - 1 of `seed`): returns {utt: [(hyp, score, [])]}, the n-best format of beam.py's pickle without
+        attention histories."""
+        out = {}
+        stop_limit = self.cfg.train["data"]["max_pred"]
+        with tqdm(total=self.data_loader.n_utts[set_key], ncols=80, disable=adist.rank() != 0) as pbar:
+            for k, utt in enumerate(self.data_loader.get_batch(1, set_key, train=False, labels=False)):
+                with using_config("train", False):
+                    hyps = sample_hypotheses(self.model, utt["X"], n, stop_limit, seed, temperature, first_stream=k * n)
+                out[utt["utts"][0]] = [(h["hyp"], h["score"], []) for h in hyps]
+                pbar.update(1)
+        return out
 
     def score_set(self, set_key):
         """Forced decoding of a set's references (SpeechEncoderDecoder.score): returns (scores, dev_loss, ppl).  scores = (utt,

@@ -203,15 +203,59 @@ def scored_from_rows(words, n_steps, B, stop_limit, has_nll, end_token):
 class _PendingScored:
     """predict_scored_async on the device path: [n_steps, status word, 2 pad words, tokens, logp, nll] on their way into pinned memory."""
 
-    def __init__(self, host, event, B, stop_limit, has_nll, end_token, keep):
-        self.host, self.event, self.args, self.keep = host, event, (B, stop_limit, has_nll, end_token), keep
+    def __init__(self, host, event, B, stop_limit, has_nll, end_token, keep, where="predict_scored"):
+        self.host, self.event, self.args, self.keep, self.where = host, event, (B, stop_limit, has_nll, end_token), keep, where
 
     def result(self):
         self.event.synchronize()
         self.keep = None
         v = self.host.numpy()
-        raise_if_aborted(v[1:2].view(np.float32)[0], "predict_scored")
+        raise_if_aborted(v[1:2].view(np.float32)[0], self.where)
         return scored_from_rows(v[4:], int(v[0]), *self.args)
+
+
+# ---- sampled decoding: the noise contract of include/astk.h ("sampled decoding on the device"), restated on the host
+_M64 = (1 << 64) - 1
+
+
+def mix64(z):
+    """The splitmix64 finaliser of csrc/common.h on Python integers."""
+    z = (z + 0x9E3779B97F4A7C15) & _M64
+    z = ((z ^ (z >> 30)) * 0xBF58476D1CE4E5B9) & _M64
+    z = ((z ^ (z >> 27)) * 0x94D049BB133111EB) & _M64
+    return z ^ (z >> 31)
+
+
+def sample_row_key(seed, stream):
+    """row_key(seed, stream) = mix64(seed ^ mix64(stream)): the key of one batch row of a sampled decode (astk_sample_row_key)."""
+    return mix64((int(seed) & _M64) ^ mix64(int(stream) & _M64))
+
+
+def gumbel_noise(row_key, step, V):
+    """The host mirror of csrc/common.h sample_gumbel: (u, g) for the classes 0..V-1 of one row and decoder step -- u the float32 uniform
+    of the contract, to the bit, g = -ln(-ln(u)) in float64 (the device's float32 g lies within 5e-6 of it)."""
+    n = np.arange(V, dtype=np.uint64)
+    with np.errstate(over="ignore"):
+        z = np.uint64(row_key) ^ ((np.uint64(step) << np.uint64(32)) | n)
+        z = z + np.uint64(0x9E3779B97F4A7C15)
+        z = (z ^ (z >> np.uint64(30))) * np.uint64(0xBF58476D1CE4E5B9)
+        z = (z ^ (z >> np.uint64(27))) * np.uint64(0x94D049BB133111EB)
+        z = z ^ (z >> np.uint64(31))
+    u = ((z >> np.uint64(40)) + np.uint64(1)).astype(np.float32) * np.float32(1.0 / 16777217.0)
+    return u, -np.log(-np.log(u.astype(np.float64)))
+
+
+def checked_temperature(temperature):
+    """1 / temperature as the float32 the library takes; ValueError unless temperature is finite and > 0 and its inverse is a finite
+    positive float32."""
+    t = float(temperature)
+    if not (np.isfinite(t) and t > 0):
+        raise ValueError(f"sample: temperature must be finite and > 0, got {temperature!r}")
+    with np.errstate(over="ignore", under="ignore"):
+        inv = float(np.float32(1.0 / t))
+    if not (np.isfinite(inv) and inv > 0):
+        raise ValueError(f"sample: 1 / temperature must be a finite positive float32, got temperature {temperature!r} (inverse {inv!r})")
+    return inv
 
 
 class ForcedScore:
@@ -1092,6 +1136,87 @@ class SpeechEncoderDecoder:
                 npred += 1
             f32 = lambda r: torch.stack(r, 0).T.float().cpu().numpy()
             return ScoredPrediction(torch.stack(rows, 0).T.cpu().numpy(), f32(lps), f32(nlls) if y is not None else None, int(end_token))
+
+    def sample(self, X, start_token, end_token, stop_limit, seed, streams=None, temperature=1.0):
+        """Ancestral sampling: predict_scored() with every step's token drawn from softmax(logits / temperature) by the Gumbel-max
+        noise of include/astk.h -- row b draws from (seed, streams[b]) alone (streams defaults to the rows' indices), whatever its
+        position and whatever the batch around it.  Returns a ScoredPrediction: tokens (B, n_steps), logp the log-probability of each
+        drawn token under the sampled distribution, score cut at the first `end_token`; nll and loss are None.  A row is finished once
+        it has drawn `end_token`; the decode stops when every row has, or at stop_limit."""
+        return self.sample_async(X, start_token, end_token, stop_limit, seed, streams, temperature).result()
+
+    def sample_async(self, X, start_token, end_token, stop_limit, seed, streams=None, temperature=1.0, slot=0):
+        """sample() with the read-back left to the caller, like predict_scored_async: on the device path (astk_sample_decode, one
+        persistent launch) ONE copy of [n_steps, status, tokens, logp] into pinned buffer `slot`; otherwise the per-step loop,
+        finished on return.  `last_predict_path` says which path ran."""
+        inv_temp = checked_temperature(temperature)
+        with using_config("train", False):
+            X = self._as_input(X)
+            self._cur = None
+            self.encode(X)
+            self.init_decoder_state()
+            B = self._cur["B"]
+            streams = list(range(B)) if streams is None else [int(v) for v in streams]
+            if len(streams) != B:
+                raise ValueError(f"sample: streams must name B = {B} rows, got {len(streams)}")
+            keys = np.array([sample_row_key(seed, v) for v in streams], dtype=np.uint64)
+            keys = torch.from_numpy(keys.view(np.int64)).to(self.device)      # (the bit patterns: torch has no uint64 arithmetic to offer)
+            handle = self._sample_device(start_token, end_token, stop_limit, keys, inv_temp, slot)
+            if handle is not None:
+                self.last_predict_path = "device"
+                return handle
+            self.last_predict_path = "steps"
+            return _Ready(self._sample_steps(start_token, end_token, stop_limit, keys, inv_temp))
+
+    def _sample_device(self, start_token, end_token, stop_limit, keys, inv_temp, slot):
+        lib = _lib.load()
+        st = self._cur
+        B = st["B"]
+        nbytes = int(lib.astk_sample_workspace_bytes(C.byref(st["dd"]), int(stop_limit)))
+        if nbytes == 0:
+            return None
+        ws = self._workspace("greedy", nbytes)
+        # [n_steps, status word (float), 2 pad words, tokens | logp, each (stop_limit, B)]: one device buffer, read back in one copy
+        sb = int(stop_limit) * B
+        n = 4 + 2 * sb
+        out = self._pool(f"sample_out{slot}", (n,), torch.int32)
+        host = self._greedy_pinned.get(("sample", slot))
+        if host is None or host.numel() < n:
+            host = self._greedy_pinned[("sample", slot)] = torch.empty(n, dtype=torch.int32, pin_memory=True)
+        host = host[:n]
+        base = out.data_ptr()
+        check(lib.astk_sample_decode(C.byref(st["dd"]), C.byref(st["dp"]), _vp(st["enc_states"]), _vp(self._dec_c), _vp(self._dec_h),
+                                     int(start_token), int(end_token), int(stop_limit), _vp(keys), inv_temp, C.c_void_p(base + 16),
+                                     C.c_void_p(base + 16 + 4 * sb), C.c_void_p(base), C.c_void_p(base + 4), _vp(ws), ws.numel(),
+                                     self._stream()))
+        host.copy_(out, non_blocking=True)
+        ev = torch.cuda.Event()
+        ev.record(torch.cuda.current_stream(self.device))
+        return _PendingScored(host, ev, B, int(stop_limit), False, int(end_token), keys, where="sample")
+
+    def _sample_steps(self, start_token, end_token, stop_limit, keys, inv_temp):
+        """The per-step sampled loop: decode_step, one astk_gumbel_rows fill, the argmax of logits * inv_temp + g in float32, and the
+        drawn token's entry of a float64 log_softmax of logits * inv_temp."""
+        lib = _lib.load()
+        with using_config("train", False):
+            B = self._cur["B"]
+            ht = torch.zeros(B, self.A, dtype=torch.float32, device=self.device)
+            word = torch.full((B,), start_token, dtype=torch.int32, device=self.device)
+            done = torch.zeros(B, dtype=torch.bool, device=self.device)
+            g = torch.empty(B, self.V, dtype=torch.float32, device=self.device)
+            rows, lps, npred = [], [], 0
+            while npred < stop_limit:
+                logits, ht, _ = self.decode_step(word, ht)
+                check(lib.astk_gumbel_rows(_vp(keys), B, len(rows), self.V, _vp(g), self._stream()))
+                word = (logits * inv_temp + g).argmax(dim=1).to(torch.int32)
+                ls = torch.log_softmax(logits.double() * inv_temp, dim=1)
+                rows.append(word)
+                lps.append(ls.gather(1, word.long()[:, None])[:, 0])
+                done |= word == end_token
+                if bool(done.all()):
+                    break
+                npred += 1
+            return ScoredPrediction(torch.stack(rows, 0).T.cpu().numpy(), torch.stack(lps, 0).T.float().cpu().numpy(), None, int(end_token))
 
     def score(self, X, y, return_alpha=False):
         """Forced decoding: the eval-mode model run along the given translations y (B, L) -- step s is fed y[:, s] and scored against

@@ -413,6 +413,37 @@ int astk_greedy_decode_scored(const astk_decoder_desc* d, const astk_decoder_par
                               int go, int eos, int stop_limit, const int32_t* y, int ldy, const float* class_weight, int32_t* tokens,
                               float* logp, float* nll, int32_t* n_steps, float* status_dst, void* ws, size_t ws_bytes, void* stream);
 
+/* ---------------------------------------------------------------- sampled decoding on the device  (ancestral sampling, Gumbel-max)
+ * The greedy decode with every step's token DRAWN from softmax(logits / temperature) instead of taken at the maximum: a draw from
+ * softmax(x * inv_temp) is the first maximum of x_n * inv_temp + g_n over independent Gumbel noise g_n, so the persistent loop runs
+ * its greedy protocol unchanged (same hand-offs, stop rule and exits) on perturbed scores.  The noise is a contract, a pure function
+ * of (seed, stream, decoder step s, class id n) that a host can restate (ast_amd.seq2seq.sample_row_key / gumbel_noise):
+ *   mix64(z)              : z += 0x9E3779B97F4A7C15; z = (z ^ z >> 30) * 0xBF58476D1CE4E5B9; z = (z ^ z >> 27) * 0x94D049BB133111EB;
+ *                           z ^ z >> 31                                           (uint64 arithmetic, the splitmix64 finaliser)
+ *   row_key(seed, stream) = mix64(seed ^ mix64(stream))                             one per batch row, formed on the host
+ *   word(b, s, n)         = mix64(row_key[b] ^ ((uint64)s << 32 | (uint64)n))
+ *   u                     = (float)((word >> 40) + 1) * c                           one float32 multiply, c = the float32 next to
+ *                           1 / 16777217 (0x1.fffffep-25 = 2^-24 (1 - 2^-24)): u lies in (0, 1), 1 - 2^-24 at the most
+ *   g(b, s, n)            = -ln(-ln(u))                                             float32, within 5e-6 of the float64 value of u
+ *   tokens[s][b]          = the first maximum over n < V of z_n = x_n * inv_temp + g(b, s, n)
+ *   logp[s][b]            = x_tok * inv_temp - LSE_n(x_n * inv_temp)                log-probability under the sampled distribution
+ * A row's draws depend on (seed, stream, s, n) alone: not on the row's position, nor on the batch around it.  (mix64(0) =
+ * 0xE220A8397B1DCDAF, row_key(2024, 0) = 0xEE8C6C05E85E6BD6.)
+ * astk_sample_decode is astk_greedy_decode_scored without targets, plus row_keys (B uint64 on the device) and inv_temp = 1 /
+ * temperature: tokens and logp are (stop_limit, B) on the device, rows [0, *n_steps) defined; a row counts as finished once it has
+ * DRAWN eos.  Same shapes and workspace as the greedy modes (astk_sample_workspace_bytes returns 0 where astk_greedy_workspace_bytes
+ * does; such shapes sample step by step: astk_decoder_step_infer, astk_gumbel_rows, argmax of logits * inv_temp + g).  Fails with a
+ * message (and launches nothing) for everything astk_greedy_decode_scored refuses, a null row_keys or logp, or an inv_temp that is
+ * not finite or is <= 0.
+ * astk_gumbel_rows writes one step's noise, out[b][n] = g(b, step, n) for b < B, n < V, as a dense (B, V) buffer.
+ * astk_sample_row_key is row_key(seed, stream): host arithmetic only. */
+size_t astk_sample_workspace_bytes(const astk_decoder_desc* d, int stop_limit);
+int astk_sample_decode(const astk_decoder_desc* d, const astk_decoder_params* p, const float* enc, const float* c0, const float* h0,
+                       int go, int eos, int stop_limit, const uint64_t* row_keys, float inv_temp, int32_t* tokens, float* logp,
+                       int32_t* n_steps, float* status_dst, void* ws, size_t ws_bytes, void* stream);
+int astk_gumbel_rows(const uint64_t* row_keys, int B, int step, int V, float* out, void* stream);
+uint64_t astk_sample_row_key(uint64_t seed, uint64_t stream);
+
 /* ---------------------------------------------------------------- forced decoding on the device  (score a given translation)
  * The eval-mode decoder run along given tokens in ONE persistent launch (the persistent decoder loop in its forced mode, after a fill
  * launch and the encA product): step s feeds y[b][s] to row b and scores y[b][s+1], for s in [0, S), S = ldy - 1 (ids are clamped to

@@ -1,0 +1,42 @@
+"""Ancestral sampling from the command line:
+    python sample.py -m <cfg_dir> -s <set key> -n <N samples> [-t <temperature>] [--seed <S>] [--mbr] [-w <out pickle>]
+Draws N scored samples of every utterance of the set with the newest checkpoint of the experiment (NN.sample_set) and pickles them
+to <cfg_dir>/<set>_sample_N-<N>_T-<T>.p (or -w) in the format of beam.py's n-best pickle, so `score.py --nbest` reads it unchanged.
+--mbr also picks one sample per utterance by minimum Bayes risk (ast_amd.nn.mbr_select: the highest mean sentence BLEU against the
+other samples), scores the choice with corpus BLEU (ast_amd.eval) and writes it beside the pickle as <pickle>.mbr.en."""
+import argparse
+import os
+import pickle
+
+from ast_amd.eval import Eval
+from ast_amd.nn import NN, mbr_select
+
+if __name__ == "__main__":
+    parser = argparse.ArgumentParser(description="Sample translations from the NN model")
+    parser.add_argument("-m", "--cfg_path", help="path for model config", required=True)
+    parser.add_argument("-s", "--S", help="dev/dev2/test", required=True)
+    parser.add_argument("-n", "--N", help="number of samples per utterance", type=int, required=True)
+    parser.add_argument("-t", "--temperature", type=float, default=1.0, help="softmax temperature (default 1)")
+    parser.add_argument("--seed", type=int, default=0, help="seed of the draws (default 0)")
+    parser.add_argument("--mbr", action="store_true", help="also choose one sample per utterance by minimum Bayes risk")
+    parser.add_argument("-w", "--out", help="pickle to write (default <cfg_dir>/<set>_sample_N-<N>_T-<T>.p)")
+    args = vars(parser.parse_args())
+    cfg_path, set_key, N, T = args["cfg_path"], args["S"], args["N"], args["temperature"]
+    if N < 1:
+        parser.error("-n must be at least 1")
+    nn = NN(cfg_path)
+    print("-" * 80)
+    print("Sampling for: {0:s} set: {1:s} gpu: {2:d}".format(cfg_path, set_key, nn.gpuid))
+    print("-" * 80)
+    samples = nn.sample_set(set_key, N, args["seed"], temperature=T)
+    out_fname = args["out"] or os.path.join(cfg_path, "{0:s}_sample_N-{1:d}_T-{2:.2f}.p".format(set_key, N, T))
+    with open(out_fname, "wb") as f:
+        pickle.dump(samples, f)
+    print("Samples written to: {0:s} (utterances: {1:d}, path: {2})".format(out_fname, len(samples), nn.model.last_predict_path))
+    if args["mbr"]:
+        metrics = Eval(os.path.join(nn.cfg.train["data"]["refs_path"], set_key), nn.cfg.train["data"]["n_evals"])
+        chosen = {u: list(lst[mbr_select([{"hyp": h, "score": sc} for h, sc, _ in lst])][0]) for u, lst in samples.items()}
+        hyps = nn.data_loader.get_hyps(chosen.items())
+        print("MBR BLEU = {0:.2f}".format(metrics.calc_bleu(hyps) * 100))
+        metrics.write_to_file(hyps, out_fname + ".mbr.en")
+        print("Predictions written to: {0:s}".format(out_fname + ".mbr.en"))
