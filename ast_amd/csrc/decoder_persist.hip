@@ -25,6 +25,8 @@
 // Applicability (else the per-launch path of decoder.hip runs): 1-3 decoder layers, H,A multiples of 16, sizes within the
 // register budgets below, grid of 256 workgroups fully resident.  All spins are bounded (abort word).
 #include "common.h"
+#include <initializer_list>
+#include <type_traits>
 
 // -DASTK_PDEC_TIMING_ALL=1: the per-phase timers of ASTK_PERSIST_DBG in the multi-layer variants too (16 more registers per lane there)
 // (the timers exist only in the test-hook build, libastk_test.so: the product library's kernels see dbg = 0 as a constant)
@@ -330,6 +332,7 @@ __device__ __forceinline__ void mfma_blocks(f32x4& acc, const float4* a, const f
 // NC = 0: generic loops.
 // XS: the slice has more rows than stay resident (chunk > PDEC_RES_ROWS): the streamed-row code is compiled into its own instantiation
 // so that the common short-chunk case keeps its register budget.
+// MODE: what the loop runs (PDecMode); the switches GR, SC, FD and SM below are derived from it at the top of the body.
 // GR: greedy decoding (inference): step 0 feeds `go` to every row, every later step its own argmax; no targets, masks, loss or saved
 // state for a backward pass (Gt, Cst, X0, ALPHA, ML, LOGITS, LSE and loss rows are neither read nor written: the input-feeding part of
 // a cell reads ht_{s-1} from HT).  The CE owner of each batch tile keeps a sticky per-row done flag (padding rows are done); once its
@@ -352,11 +355,10 @@ __device__ __forceinline__ void mfma_blocks(f32x4& acc, const float4* a, const f
 // sum cannot overflow) -- the four words of the tile record, as before.  P6 merges the winner by z and the sums relative to the largest
 // reference, stores the token and LOGP = (xs_tok - ref) - logf(se), then runs the greedy branch on the SAMPLED token as it stands: no wait,
 // arrival, counter or exit condition is added.  DESIGN.md section 14.
-template <int NC, int NL, bool XS, bool GR, bool SC = false, bool FD = false, bool SM = false>
+enum PDecMode { PDEC_TRAIN, PDEC_GREEDY, PDEC_SCORED, PDEC_FORCED, PDEC_SAMPLED };
+template <int NC, int NL, bool XS, PDecMode MODE>
 __device__ __forceinline__ void decoder_persist_fwd_body(const PDecArgs& a) {
-  static_assert(GR || !SC, "the scored mode is a greedy mode");
-  static_assert(!FD || (GR && SC), "the forced mode builds on the scored inference mode");
-  static_assert(!SM || (GR && SC && !FD), "the sampled mode builds on the scored greedy mode");
+  constexpr bool GR = MODE != PDEC_TRAIN, SC = GR && MODE != PDEC_GREEDY, FD = MODE == PDEC_FORCED, SM = MODE == PDEC_SAMPLED;
   constexpr bool STOP = GR && !FD;         // the greedy modes' stop word exists
   constexpr bool SUMS = !GR || SC;         // P5 / P6 keep the sum of exponentials and the target logit
   extern __shared__ __attribute__((aligned(16))) float lds[];   // enc slice [chunk][H], encA slice [chunk][H], scratch
@@ -1274,21 +1276,21 @@ __device__ __forceinline__ void greedy_last_out(const PDecArgs& a) {
 
 template <int NC, int NL, bool XS, bool GR>
 __global__ __launch_bounds__(256, 1) void decoder_persist_fwd(PDecArgs a) {
-  decoder_persist_fwd_body<NC, NL, XS, GR>(a);     // (every return in it is workgroup-uniform)
+  decoder_persist_fwd_body<NC, NL, XS, GR ? PDEC_GREEDY : PDEC_TRAIN>(a);     // (every return in it is workgroup-uniform)
   if constexpr (GR) greedy_last_out(a);
 }
 
 // The scored greedy mode as a kernel of its own: the instantiations above keep their names and their code.
 template <int NC, int NL, bool XS>
 __global__ __launch_bounds__(256, 1) void decoder_persist_greedy_scored(PDecArgs a) {
-  decoder_persist_fwd_body<NC, NL, XS, true, true>(a);
+  decoder_persist_fwd_body<NC, NL, XS, PDEC_SCORED>(a);
   greedy_last_out(a);
 }
 
 // The sampled mode as a kernel of its own, likewise: the greedy modes' control words and exit as they are.
 template <int NC, int NL, bool XS>
 __global__ __launch_bounds__(256, 1) void decoder_persist_sampled(PDecArgs a) {
-  decoder_persist_fwd_body<NC, NL, XS, true, true, false, true>(a);
+  decoder_persist_fwd_body<NC, NL, XS, PDEC_SAMPLED>(a);
   greedy_last_out(a);
 }
 
@@ -1303,7 +1305,7 @@ __global__ __launch_bounds__(256) void k_gumbel_rows(const uint64_t* __restrict_
 // workgroup to leave writes the status copy.  It is an arrival at the end of the kernel that nothing waits for.
 template <int NC, int NL, bool XS>
 __global__ __launch_bounds__(256, 1) void decoder_persist_forced(PDecArgs a) {
-  decoder_persist_fwd_body<NC, NL, XS, true, true, true>(a);
+  decoder_persist_fwd_body<NC, NL, XS, PDEC_FORCED>(a);
   if (!a.status_dst) return;
   asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
   __syncthreads();
@@ -2055,70 +2057,29 @@ struct DecPersistBwdBuffers {
   unsigned* ctr;
 };
 
-template <int NL>
-static void pdec_launch_bwd(bool special, bool xs, size_t shm, hipStream_t s, const PDecBwdArgs& a) {
+// The one launcher of the persistent decoder kernels.  pick(nc, nl, xs) names the instantiation <NC, NL, XS> of one kernel template (its
+// arguments are std::integral_constant values); the shape selects among the three of a layer count: generic, NC = 8, NC = 8 streamed.
+// Every `pick` is a type of its own, so each (kernel template, NL) has its own `attr_done`: a kernel's LDS cap is raised once per process.
+template <int NL, class Pick, class Args>
+static void pdec_launch_nl(Pick pick, int lds_cap, int H, int chunk, size_t shm, hipStream_t s, const Args& a) {
+  using Layers = std::integral_constant<int, NL>;
+  const auto k0 = pick(std::integral_constant<int, 0>{}, Layers{}, std::false_type{});
+  const auto k8 = pick(std::integral_constant<int, 8>{}, Layers{}, std::false_type{});
+  const auto k8x = pick(std::integral_constant<int, 8>{}, Layers{}, std::true_type{});
   static bool attr_done = false;
   if (!attr_done) {
-    (void)hipFuncSetAttribute((const void*)decoder_persist_bwd<0, NL, false>, hipFuncAttributeMaxDynamicSharedMemorySize, 150 * 1024);
-    (void)hipFuncSetAttribute((const void*)decoder_persist_bwd<8, NL, false>, hipFuncAttributeMaxDynamicSharedMemorySize, 150 * 1024);
-    (void)hipFuncSetAttribute((const void*)decoder_persist_bwd<8, NL, true>, hipFuncAttributeMaxDynamicSharedMemorySize, 150 * 1024);
+    for (auto k : {k0, k8, k8x}) (void)hipFuncSetAttribute((const void*)k, hipFuncAttributeMaxDynamicSharedMemorySize, lds_cap);
     attr_done = true;
   }
-  if (special && xs) hipLaunchKernelGGL((decoder_persist_bwd<8, NL, true>), dim3(G), dim3(256), shm, s, a);
-  else if (special) hipLaunchKernelGGL((decoder_persist_bwd<8, NL, false>), dim3(G), dim3(256), shm, s, a);
-  else hipLaunchKernelGGL((decoder_persist_bwd<0, NL, false>), dim3(G), dim3(256), shm, s, a);
+  const bool special = pdec_special(H, chunk);
+  const auto k = !special ? k0 : (chunk > PDEC_RES_ROWS ? k8x : k8);
+  hipLaunchKernelGGL(k, dim3(G), dim3(256), shm, s, a);
 }
-template <int NL>
-static void pdec_launch_scored(bool special, bool xs, size_t shm, hipStream_t s, const PDecArgs& a) {
-  static bool attr_done = false;
-  if (!attr_done) {
-    (void)hipFuncSetAttribute((const void*)decoder_persist_greedy_scored<0, NL, false>, hipFuncAttributeMaxDynamicSharedMemorySize, 138 * 1024);
-    (void)hipFuncSetAttribute((const void*)decoder_persist_greedy_scored<8, NL, false>, hipFuncAttributeMaxDynamicSharedMemorySize, 138 * 1024);
-    (void)hipFuncSetAttribute((const void*)decoder_persist_greedy_scored<8, NL, true>, hipFuncAttributeMaxDynamicSharedMemorySize, 138 * 1024);
-    attr_done = true;
-  }
-  if (special && xs) hipLaunchKernelGGL((decoder_persist_greedy_scored<8, NL, true>), dim3(G), dim3(256), shm, s, a);
-  else if (special) hipLaunchKernelGGL((decoder_persist_greedy_scored<8, NL, false>), dim3(G), dim3(256), shm, s, a);
-  else hipLaunchKernelGGL((decoder_persist_greedy_scored<0, NL, false>), dim3(G), dim3(256), shm, s, a);
-}
-template <int NL>
-static void pdec_launch_sampled(bool special, bool xs, size_t shm, hipStream_t s, const PDecArgs& a) {
-  static bool attr_done = false;
-  if (!attr_done) {
-    (void)hipFuncSetAttribute((const void*)decoder_persist_sampled<0, NL, false>, hipFuncAttributeMaxDynamicSharedMemorySize, 138 * 1024);
-    (void)hipFuncSetAttribute((const void*)decoder_persist_sampled<8, NL, false>, hipFuncAttributeMaxDynamicSharedMemorySize, 138 * 1024);
-    (void)hipFuncSetAttribute((const void*)decoder_persist_sampled<8, NL, true>, hipFuncAttributeMaxDynamicSharedMemorySize, 138 * 1024);
-    attr_done = true;
-  }
-  if (special && xs) hipLaunchKernelGGL((decoder_persist_sampled<8, NL, true>), dim3(G), dim3(256), shm, s, a);
-  else if (special) hipLaunchKernelGGL((decoder_persist_sampled<8, NL, false>), dim3(G), dim3(256), shm, s, a);
-  else hipLaunchKernelGGL((decoder_persist_sampled<0, NL, false>), dim3(G), dim3(256), shm, s, a);
-}
-template <int NL>
-static void pdec_launch_forced(bool special, bool xs, size_t shm, hipStream_t s, const PDecArgs& a) {
-  static bool attr_done = false;
-  if (!attr_done) {
-    (void)hipFuncSetAttribute((const void*)decoder_persist_forced<0, NL, false>, hipFuncAttributeMaxDynamicSharedMemorySize, 138 * 1024);
-    (void)hipFuncSetAttribute((const void*)decoder_persist_forced<8, NL, false>, hipFuncAttributeMaxDynamicSharedMemorySize, 138 * 1024);
-    (void)hipFuncSetAttribute((const void*)decoder_persist_forced<8, NL, true>, hipFuncAttributeMaxDynamicSharedMemorySize, 138 * 1024);
-    attr_done = true;
-  }
-  if (special && xs) hipLaunchKernelGGL((decoder_persist_forced<8, NL, true>), dim3(G), dim3(256), shm, s, a);
-  else if (special) hipLaunchKernelGGL((decoder_persist_forced<8, NL, false>), dim3(G), dim3(256), shm, s, a);
-  else hipLaunchKernelGGL((decoder_persist_forced<0, NL, false>), dim3(G), dim3(256), shm, s, a);
-}
-template <int NL, bool GR = false>
-static void pdec_launch_fwd(bool special, bool xs, size_t shm, hipStream_t s, const PDecArgs& a) {
-  static bool attr_done = false;
-  if (!attr_done) {
-    (void)hipFuncSetAttribute((const void*)decoder_persist_fwd<0, NL, false, GR>, hipFuncAttributeMaxDynamicSharedMemorySize, 138 * 1024);
-    (void)hipFuncSetAttribute((const void*)decoder_persist_fwd<8, NL, false, GR>, hipFuncAttributeMaxDynamicSharedMemorySize, 138 * 1024);
-    (void)hipFuncSetAttribute((const void*)decoder_persist_fwd<8, NL, true, GR>, hipFuncAttributeMaxDynamicSharedMemorySize, 138 * 1024);
-    attr_done = true;
-  }
-  if (special && xs) hipLaunchKernelGGL((decoder_persist_fwd<8, NL, true, GR>), dim3(G), dim3(256), shm, s, a);
-  else if (special) hipLaunchKernelGGL((decoder_persist_fwd<8, NL, false, GR>), dim3(G), dim3(256), shm, s, a);
-  else hipLaunchKernelGGL((decoder_persist_fwd<0, NL, false, GR>), dim3(G), dim3(256), shm, s, a);
+template <class Pick, class Args>
+static void pdec_launch(Pick pick, int n_layers, int lds_cap, int H, int chunk, size_t shm, hipStream_t s, const Args& a) {
+  if (n_layers == 1) pdec_launch_nl<1>(pick, lds_cap, H, chunk, shm, s, a);
+  else if (n_layers == 2) pdec_launch_nl<2>(pick, lds_cap, H, chunk, shm, s, a);
+  else pdec_launch_nl<3>(pick, lds_cap, H, chunk, shm, s, a);
 }
 
 int decoder_persist_bwd_launch(const astk_decoder_desc* d, const float* enc, const float* rnn_masks, const DecPersistBwdBuffers& bf,
@@ -2160,11 +2121,7 @@ int decoder_persist_bwd_launch(const astk_decoder_desc* d, const float* enc, con
   const size_t shm = pdec_bwd_lds_floats(chunk, a.H) * sizeof(float);       // slices + dS/cvS/ds + ds/alpha/fold of the specialised scan
   {
     ProfScope prof(PROF_DEC_BWD, s);
-    const bool special = pdec_special(a.H, chunk);
-    const bool xs = special && chunk > PDEC_RES_ROWS;
-    if (d->n_layers == 1) pdec_launch_bwd<1>(special, xs, shm, s, a);
-    else if (d->n_layers == 2) pdec_launch_bwd<2>(special, xs, shm, s, a);
-    else pdec_launch_bwd<3>(special, xs, shm, s, a);
+    pdec_launch([](auto nc, auto nl, auto xs) { return decoder_persist_bwd<nc, nl, xs>; }, d->n_layers, 150 * 1024, a.H, chunk, shm, s, a);
   }
   ASTK_LAUNCH_CHECK();
   return 0;
@@ -2237,11 +2194,7 @@ int decoder_persist_fwd_launch(const astk_decoder_desc* d, const astk_decoder_pa
   const size_t shm = pdec_lds_floats(chunk, a.H, nsplit) * sizeof(float);
   {
     ProfScope prof(PROF_DEC_FWD, s);
-    const bool special = pdec_special(a.H, chunk);
-    const bool xs = special && chunk > PDEC_RES_ROWS;
-    if (d->n_layers == 1) pdec_launch_fwd<1>(special, xs, shm, s, a);
-    else if (d->n_layers == 2) pdec_launch_fwd<2>(special, xs, shm, s, a);
-    else pdec_launch_fwd<3>(special, xs, shm, s, a);
+    pdec_launch([](auto nc, auto nl, auto xs) { return decoder_persist_fwd<nc, nl, xs, false>; }, d->n_layers, 138 * 1024, a.H, chunk, shm, s, a);
   }
   ASTK_LAUNCH_CHECK();
   // Q[s][b][:] = Wa h_top + ba for all steps (needed by the backward's deferred d_enc product)
@@ -2297,8 +2250,8 @@ size_t greedy_scored_workspace_bytes(const astk_decoder_desc* d, int stop_limit)
 
 // What the launchers of the inference modes (greedy, scored greedy, forced) share.  inference_args: the PDecArgs of a loop of S steps on
 // a greedy plan -- shapes, parameters, hand-off buffers, counters, abort control, the control lines; a mode's own fields (tokens, targets,
-// outputs) are its launcher's.  inference_fill: the one fill launch in front of the loop -- counters, abort word, tile reports and exit
-// count to 0, the stop word to S, the sentinel hand-offs, h0.  inference_launch: the instantiation of the shape.
+// outputs) are its launcher's.  inference_run: everything enqueued for such a loop -- encA = enc . Wa, the one fill launch in front of the
+// loop (counters, abort word, tile reports and exit count to 0, the stop word to S, the sentinel hand-offs, h0), the mode's kernel.
 static PDecArgs inference_args(const astk_decoder_desc* d, const astk_decoder_params* prm, const float* enc, const float* c0, int S,
                                const GreedyPlan& g) {
   PDecArgs a;
@@ -2324,7 +2277,11 @@ static PDecArgs inference_args(const astk_decoder_desc* d, const astk_decoder_pa
   return a;
 }
 
-static int inference_fill(const astk_decoder_desc* d, const PDecArgs& a, const GreedyPlan& g, const float* h0, hipStream_t s) {
+static int inference_run(PDecMode mode, const astk_decoder_desc* d, const astk_decoder_params* prm, const float* enc, const float* h0,
+                         const PDecArgs& a, const GreedyPlan& g, hipStream_t s) {
+  PrecScope prec_scope(d->precision, d->gemm_operands);
+  GemmForwardScope forward_scope;
+  ASTK_TRY(gemm_launch(GEMM_NN, gemm_args(d->B * d->T, d->H, d->H, mat(enc, d->H), mat(prm->Wa, d->H), g.ENCA, d->H), s));   // encA = enc . Wa
   const size_t bh = (size_t)d->B * d->H;
   FillSegs f;
   f.n = 0;
@@ -2338,31 +2295,14 @@ static int inference_fill(const astk_decoder_desc* d, const PDecArgs& a, const G
 #endif
   for (int l = 0; l < d->n_layers; ++l) fill_seg_add_copy(f, g.HR[l], h0 + l * bh, bh * sizeof(float));
   ASTK_TRY(fill_u32_segments(f, PDEC_SENTINEL, s));
-  return 0;
-}
-
-enum InferenceMode { INF_GREEDY, INF_SCORED, INF_FORCED, INF_SAMPLED };
-static void inference_launch(InferenceMode mode, const astk_decoder_desc* d, const PDecArgs& a, const GreedyPlan& g, hipStream_t s) {
   const size_t shm = pdec_lds_floats(g.chunk, a.H, g.nsplit) * sizeof(float);
-  const bool special = pdec_special(a.H, g.chunk);
-  const bool xs = special && g.chunk > PDEC_RES_ROWS;
-  if (mode == INF_FORCED) {
-    if (d->n_layers == 1) pdec_launch_forced<1>(special, xs, shm, s, a);
-    else if (d->n_layers == 2) pdec_launch_forced<2>(special, xs, shm, s, a);
-    else pdec_launch_forced<3>(special, xs, shm, s, a);
-  } else if (mode == INF_SAMPLED) {
-    if (d->n_layers == 1) pdec_launch_sampled<1>(special, xs, shm, s, a);
-    else if (d->n_layers == 2) pdec_launch_sampled<2>(special, xs, shm, s, a);
-    else pdec_launch_sampled<3>(special, xs, shm, s, a);
-  } else if (mode == INF_SCORED) {
-    if (d->n_layers == 1) pdec_launch_scored<1>(special, xs, shm, s, a);
-    else if (d->n_layers == 2) pdec_launch_scored<2>(special, xs, shm, s, a);
-    else pdec_launch_scored<3>(special, xs, shm, s, a);
-  } else {
-    if (d->n_layers == 1) pdec_launch_fwd<1, true>(special, xs, shm, s, a);
-    else if (d->n_layers == 2) pdec_launch_fwd<2, true>(special, xs, shm, s, a);
-    else pdec_launch_fwd<3, true>(special, xs, shm, s, a);
-  }
+  const auto launch = [&](auto pick) { pdec_launch(pick, d->n_layers, 138 * 1024, a.H, g.chunk, shm, s, a); };
+  if (mode == PDEC_FORCED) launch([](auto nc, auto nl, auto xs) { return decoder_persist_forced<nc, nl, xs>; });
+  else if (mode == PDEC_SAMPLED) launch([](auto nc, auto nl, auto xs) { return decoder_persist_sampled<nc, nl, xs>; });
+  else if (mode == PDEC_SCORED) launch([](auto nc, auto nl, auto xs) { return decoder_persist_greedy_scored<nc, nl, xs>; });
+  else launch([](auto nc, auto nl, auto xs) { return decoder_persist_fwd<nc, nl, xs, true>; });
+  ASTK_LAUNCH_CHECK();
+  return 0;
 }
 
 // the scored mode's arguments
@@ -2392,9 +2332,6 @@ static int greedy_launch(const astk_decoder_desc* d, const astk_decoder_params* 
     ASTK_CHECK(!sc->y || sc->ldy >= 1, "greedy_decode_scored: ldy %d < 1", sc->ldy);
   }
   greedy_plan(d, stop_limit, ws, g);
-  PrecScope prec_scope(d->precision, d->gemm_operands);
-  GemmForwardScope forward_scope;
-  ASTK_TRY(gemm_launch(GEMM_NN, gemm_args(d->B * d->T, d->H, d->H, mat(enc, d->H), mat(prm->Wa, d->H), g.ENCA, d->H), s));   // encA = enc . Wa
   PDecArgs a = inference_args(d, prm, enc, c0, stop_limit, g);
   a.PRED = tokens;
   a.go = go; a.eos = eos;
@@ -2403,10 +2340,7 @@ static int greedy_launch(const astk_decoder_desc* d, const astk_decoder_params* 
     a.LSE = sc->logp; a.LOSSROWS = sc->nll; a.ytgt = sc->y; a.L = sc->y ? sc->ldy : 1; a.cw = sc->class_weight;
     a.row_keys = sc->row_keys; a.inv_temp = sc->inv_temp;
   }
-  ASTK_TRY(inference_fill(d, a, g, h0, s));
-  inference_launch(!sc ? INF_GREEDY : (sc->row_keys ? INF_SAMPLED : INF_SCORED), d, a, g, s);
-  ASTK_LAUNCH_CHECK();
-  return 0;
+  return inference_run(!sc ? PDEC_GREEDY : (sc->row_keys ? PDEC_SAMPLED : PDEC_SCORED), d, prm, enc, h0, a, g, s);
 }
 
 int greedy_decode_launch(const astk_decoder_desc* d, const astk_decoder_params* prm, const float* enc, const float* c0, const float* h0, int go,
@@ -2483,17 +2417,11 @@ int forced_score_launch(const astk_decoder_desc* d, const astk_decoder_params* p
   ASTK_CHECK(ws && ws_bytes >= f.bytes, "forced_score: workspace too small (%zu < %zu)", ws_bytes, f.bytes);
   ASTK_CHECK(prm && enc && c0 && h0 && y && logp, "forced_score: null pointer");
   forced_plan(d, S, alpha != nullptr, ws, f);
-  const GreedyPlan& g = f.g;
-  PrecScope prec_scope(d->precision, d->gemm_operands);
-  GemmForwardScope forward_scope;
-  ASTK_TRY(gemm_launch(GEMM_NN, gemm_args(d->B * d->T, d->H, d->H, mat(enc, d->H), mat(prm->Wa, d->H), g.ENCA, d->H), s));   // encA = enc . Wa
-  PDecArgs a = inference_args(d, prm, enc, c0, S, g);
+  PDecArgs a = inference_args(d, prm, enc, c0, S, f.g);
   a.y = y; a.ytgt = y;                  // (a.L = S + 1 = ldy)
   a.LSE = logp; a.LOSSROWS = logp_max; a.PRED = pred; a.ALPHA = f.RAW; a.ML = f.ML;
   a.status_dst = status_dst;            // (of the control lines only the exit count, line 2, is used: the stop word is never read)
-  ASTK_TRY(inference_fill(d, a, g, h0, s));
-  inference_launch(INF_FORCED, d, a, g, s);
-  ASTK_LAUNCH_CHECK();
+  ASTK_TRY(inference_run(PDEC_FORCED, d, prm, enc, h0, a, f.g, s));
   if (alpha) {
     hipLaunchKernelGGL(k_alpha_normalise, dim3(a.S * a.B), dim3(256), 0, s, f.RAW, f.ML, alpha, a.T, a.Tp);
     ASTK_LAUNCH_CHECK();

@@ -2,6 +2,7 @@
 seq2seq_<N>.model, and runs the train step of nn.py:168-194 -- forward_loss -> cleargrads -> backward -> update --
 on the HIP path.  Data-parallel runs (one process per GPU, torchrun) shard every bucketed batch over the ranks and
 all-reduce the flat gradient arena over RCCL before the hooks (ast_amd.dist)."""
+import itertools
 import math
 import os
 import random
@@ -225,6 +226,25 @@ def _init_hyp_from(model, enc_states):
             "attn_v": torch.zeros(1, model.cfg["rnn_config"]["attn_units"], dtype=torch.float32, device=model.device), "attn_history": []}
 
 
+def read_one_batch_late(nn, set_key, labels, enqueue):
+    """The inference loop of an NN over a set, read one batch late like train_epoch's loss: enqueue(batch, slot) starts batch i on the
+    read-back buffers of slot i % 2 (SpeechEncoderDecoder.predict_async) and returns its handle; what the handle holds is read after
+    batch i+1 has been enqueued, so the device never waits for the host.  Yields (utts, padded target length or None, handle.result())."""
+    pending = None
+    with tqdm(total=nn.data_loader.n_utts[set_key], ncols=80, disable=adist.rank() != 0) as pbar:
+        batches = nn.data_loader.get_batch(nn.cfg.train["batch_size"], set_key, train=False, labels=labels)
+        for i, batch in enumerate(itertools.chain(batches, [None])):
+            cur = None
+            if batch is not None:
+                with using_config("train", False):
+                    cur = (batch["utts"], len(batch["X"]), int(batch["y"].shape[1]) if labels else None, enqueue(batch, i % 2))
+            if pending is not None:
+                utts, n, L, handle = pending
+                yield utts, L, handle.result()
+                pbar.update(n)
+            pending = cur
+
+
 class NN:
     def __init__(self, cfg_path, vocab_size=None):
         self.cfg = Config(cfg_path, vocab_size=vocab_size)
@@ -376,24 +396,9 @@ class NN:
     def predict(self, set_key):
         preds = []
         stop_limit = self.cfg.train["data"]["max_pred"]
-        # Like train_epoch's loss: the tokens of batch i are read after batch i+1 has been enqueued (two alternating read-back buffers,
-        # SpeechEncoderDecoder.predict_async), so the device never waits for the host; the predictions are the same.
-        pending = None
-
-        def settle(p):
-            utts, n, handle = p
-            preds.extend(zip(utts, handle.result().tolist()))
-            pbar.update(n)
-        with tqdm(total=self.data_loader.n_utts[set_key], ncols=80, disable=adist.rank() != 0) as pbar:
-            for i, batch in enumerate(self.data_loader.get_batch(self.cfg.train["batch_size"], set_key, train=False, labels=False)):
-                with using_config("train", False):
-                    cur = (batch["utts"], len(batch["X"]),
-                           self.model.predict_async(batch["X"], SYMBOLS.GO_ID, SYMBOLS.EOS_ID, stop_limit, slot=i % 2))
-                if pending is not None:
-                    settle(pending)
-                pending = cur
-            if pending is not None:
-                settle(pending)
+        for utts, _, tokens in read_one_batch_late(self, set_key, False, lambda batch, slot: self.model.predict_async(
+                batch["X"], SYMBOLS.GO_ID, SYMBOLS.EOS_ID, stop_limit, slot=slot)):
+            preds.extend(zip(utts, tokens.tolist()))
         return preds
 
     def predict_scored(self, set_key):
@@ -403,25 +408,11 @@ class NN:
         the hypothesis up to and including its first EOS) pairs.  Read one batch late like predict()."""
         preds, scores, losses = [], [], []
         stop_limit = self.cfg.train["data"]["max_pred"]
-        pending = None
-
-        def settle(p):
-            utts, n, L, handle = p
-            r = handle.result()
+        for utts, L, r in read_one_batch_late(self, set_key, True, lambda batch, slot: self.model.predict_scored_async(
+                batch["X"], SYMBOLS.GO_ID, SYMBOLS.EOS_ID, stop_limit, batch["y"], slot=slot)):
             preds.extend(zip(utts, r.tokens.tolist()))
             scores.extend(zip(utts, r.score.tolist()))
             losses.append(r.loss / L)
-            pbar.update(n)
-        with tqdm(total=self.data_loader.n_utts[set_key], ncols=80, disable=adist.rank() != 0) as pbar:
-            for i, batch in enumerate(self.data_loader.get_batch(self.cfg.train["batch_size"], set_key, train=False, labels=True)):
-                with using_config("train", False):
-                    cur = (batch["utts"], len(batch["X"]), int(batch["y"].shape[1]),
-                           self.model.predict_scored_async(batch["X"], SYMBOLS.GO_ID, SYMBOLS.EOS_ID, stop_limit, batch["y"], slot=i % 2))
-                if pending is not None:
-                    settle(pending)
-                pending = cur
-            if pending is not None:
-                settle(pending)
         return preds, (sum(losses) / len(losses) if losses else 0.0), scores
 
     def sample_set(self, set_key, n, seed, temperature=1.0):
@@ -444,23 +435,9 @@ class NN:
         teacher-forced cross-entropy summed over the steps / the padded target length) -- the normalisation of predict_scored's dev loss,
         so the two are comparable; ppl = exp(-sum of the log-probabilities / sum of the token counts).  Read one batch late like predict()."""
         scores, losses = [], []
-        pending = None
-
-        def settle(p):
-            utts, n, L, handle = p
-            r = handle.result()
+        for utts, L, r in read_one_batch_late(self, set_key, True, lambda batch, slot: self.model.score_async(batch["X"], batch["y"], slot=slot)):
             scores.extend(zip(utts, r.score.tolist(), r.n_tokens.tolist()))
             losses.append(r.loss / L)
-            pbar.update(n)
-        with tqdm(total=self.data_loader.n_utts[set_key], ncols=80, disable=adist.rank() != 0) as pbar:
-            for i, batch in enumerate(self.data_loader.get_batch(self.cfg.train["batch_size"], set_key, train=False, labels=True)):
-                with using_config("train", False):
-                    cur = (batch["utts"], len(batch["X"]), int(batch["y"].shape[1]), self.model.score_async(batch["X"], batch["y"], slot=i % 2))
-                if pending is not None:
-                    settle(pending)
-                pending = cur
-            if pending is not None:
-                settle(pending)
         n_tok = sum(n for _, _, n in scores)
         ppl = math.exp(-sum(lp for _, lp, _ in scores) / n_tok) if n_tok else float("nan")
         return scores, (sum(losses) / len(losses) if losses else 0.0), ppl

@@ -159,19 +159,20 @@ class Loss:
         return float(self.data)
 
 
-class _PendingPredict:
-    """SpeechEncoderDecoder.predict_async on the device path: [n_steps, status word, 2 pad words, tokens (stop_limit, B)] on their way
-    into pinned memory.  result() waits for that copy and returns the (B, n_steps) int32 predictions."""
+class _Pending:
+    """A decode on the device path: its words [.., status word (float), .., results] -- and the float words of a second buffer, forced
+    alpha -- on their way into pinned memory.  result() waits for the copy, raises if the status word (at index `status_at`) reports a
+    timed-out kernel, and returns parse(words, second buffer's words or None).  `keep` holds the launch's device inputs until then."""
 
-    def __init__(self, host, event, B):
-        self.host, self.event, self.B = host, event, B
+    def __init__(self, host, host2, event, status_at, where, parse, keep=None):
+        self.host, self.host2, self.event, self.status_at, self.where, self.parse, self.keep = host, host2, event, status_at, where, parse, keep
 
     def result(self):
         self.event.synchronize()
+        self.keep = None
         v = self.host.numpy()
-        raise_if_aborted(v[1:2].view(np.float32)[0], "predict")
-        n = int(v[0])
-        return v[4:4 + n * self.B].reshape(n, self.B).T.copy()
+        raise_if_aborted(v[self.status_at:self.status_at + 1].view(np.float32)[0], self.where)
+        return self.parse(v, None if self.host2 is None else self.host2.numpy())
 
 
 class ScoredPrediction:
@@ -198,20 +199,6 @@ def scored_from_rows(words, n_steps, B, stop_limit, has_nll, end_token):
     n, sb = int(n_steps), int(stop_limit) * B
     rows = lambda k: words[k * sb:k * sb + n * B].reshape(n, B).T.copy()
     return ScoredPrediction(rows(0), rows(1).view(np.float32), rows(2).view(np.float32) if has_nll else None, end_token)
-
-
-class _PendingScored:
-    """predict_scored_async on the device path: [n_steps, status word, 2 pad words, tokens, logp, nll] on their way into pinned memory."""
-
-    def __init__(self, host, event, B, stop_limit, has_nll, end_token, keep, where="predict_scored"):
-        self.host, self.event, self.args, self.keep, self.where = host, event, (B, stop_limit, has_nll, end_token), keep, where
-
-    def result(self):
-        self.event.synchronize()
-        self.keep = None
-        v = self.host.numpy()
-        raise_if_aborted(v[1:2].view(np.float32)[0], self.where)
-        return scored_from_rows(v[4:], int(v[0]), *self.args)
 
 
 # ---- sampled decoding: the noise contract of include/astk.h ("sampled decoding on the device"), restated on the host
@@ -300,25 +287,6 @@ def checked_targets(y, V):
     return y.astype(np.int32, copy=False)
 
 
-class _PendingForced:
-    """score_async on the device path: [status word, 3 pad words, logp, logp_max, pred] (and alpha, a copy of its own) on their way into
-    pinned memory."""
-
-    def __init__(self, host, host_alpha, event, B, S, weight, keep):
-        self.host, self.host_alpha, self.event, self.args, self.keep = host, host_alpha, event, (B, S, weight), keep
-
-    def result(self):
-        self.event.synchronize()
-        self.keep = None
-        v = self.host.numpy()
-        raise_if_aborted(v[0:1].view(np.float32)[0], "score")
-        B, S, weight = self.args
-        alpha = None
-        if self.host_alpha is not None:
-            alpha = self.host_alpha.numpy().reshape(S, B, -1).transpose(1, 0, 2).copy()
-        return forced_from_rows(v[4:], B, S, weight, alpha)
-
-
 class _Ready:
     def __init__(self, value):
         self.value = value
@@ -393,7 +361,7 @@ class SpeechEncoderDecoder:
         self._side = None
         self._side_by_main = {}
         self.mask_pad_id = None
-        self._greedy_pinned = {}        # predict_async: pinned read-back buffers per slot
+        self._pinned = {}               # pinned read-back buffers of the decode modes, per (mode, slot) (_readback)
         self.last_score_path = None     # "device" (astk_forced_score) | "steps": which path the last score() took
         self.last_predict_path = None   # "device" (astk_greedy_decode) | "steps" (the per-step loop): which path the last predict() took
         # Arithmetic of the batched products, per model (-> the descriptors' `precision` / `gemm_operands` fields): None = the library's
@@ -1014,47 +982,63 @@ class SpeechEncoderDecoder:
     def predict(self, X, start_token, end_token, stop_limit):
         return self.predict_async(X, start_token, end_token, stop_limit).result()
 
+    # What the decode entry points share.  _begin_decode: the eval-mode encoding and decoder state of a batch.  _device_decode: a mode's
+    # one persistent launch with its one-copy read-back, or None for shapes the library does not run on the device loop (it reports a
+    # workspace of 0).  _device_or_steps: that handle, or else the mode's per-step loop, finished on return.
+    def _begin_decode(self, X):
+        X = self._as_input(X)
+        self._cur = None
+        self.encode(X)
+        self.init_decoder_state()
+        return self._cur["B"]
+
+    def _readback(self, key, slot, n, dtype):
+        """n words of the pooled device buffer of (key, slot) and of its pinned twin; both only ever grow."""
+        host = self._pinned.get((key, slot))
+        if host is None or host.numel() < n:
+            host = self._pinned[(key, slot)] = torch.empty(n, dtype=dtype, pin_memory=True)
+        return self._pool(f"{key}_out{slot}", (n,), dtype), host[:n]
+
+    def _device_decode(self, key, slot, nbytes, n, call, args, n_alpha=0, **pending):
+        """`call` = the mode's library entry point, `nbytes` its workspace query; the launch writes n int32 words (and n_alpha floats,
+        forced alpha) that come back in one non-blocking copy each, followed by an event.  args(p, alpha) = the mode's own arguments
+        between the decoder state and the workspace: p(k) is the address of byte k of the words, alpha the float buffer's or None.
+        `pending`: the status word's index, `where`, parse and keep of the _Pending handle returned."""
+        if nbytes == 0:
+            return None
+        ws = self._workspace("decode", nbytes)
+        out, host = self._readback(key, slot, n, torch.int32)
+        alpha, host_alpha = self._readback(key + "_alpha", slot, n_alpha, torch.float32) if n_alpha else (None, None)
+        st, base = self._cur, out.data_ptr()
+        check(call(C.byref(st["dd"]), C.byref(st["dp"]), _vp(st["enc_states"]), _vp(self._dec_c), _vp(self._dec_h),
+                   *args(lambda k: C.c_void_p(base + k), _vp(alpha)), _vp(ws), ws.numel(), self._stream()))
+        host.copy_(out, non_blocking=True)
+        if n_alpha:
+            host_alpha.copy_(alpha, non_blocking=True)
+        ev = torch.cuda.Event()
+        ev.record(torch.cuda.current_stream(self.device))
+        return _Pending(host, host_alpha, ev, **pending)
+
+    def _device_or_steps(self, path_attr, handle, steps):
+        setattr(self, path_attr, "steps" if handle is None else "device")
+        return _Ready(steps()) if handle is None else handle
+
     def predict_async(self, X, start_token, end_token, stop_limit, slot=0):
         """predict() with the read-back left to the caller: returns a handle whose result() is predict()'s array.  On the device path
         (include/astk.h astk_greedy_decode: the whole decode in one persistent launch) the tokens, n_steps and the status word come back
         in ONE copy into pinned buffer `slot` (0 or 1), which result() waits for: a caller that enqueues the next batch before it reads this
         one keeps the device busy (NN.predict alternates the slots).  Shapes the library does not run on the device loop (it reports a
         workspace of 0) take the per-step loop, which finishes before this returns.  `last_predict_path` says which path ran."""
-        with using_config("train", False):
-            X = self._as_input(X)
-            self._cur = None
-            self.encode(X)
-            self.init_decoder_state()
-            handle = self._greedy_device(start_token, end_token, stop_limit, slot)
-            if handle is not None:
-                self.last_predict_path = "device"
-                return handle
-            self.last_predict_path = "steps"
-            return _Ready(self._predict_steps(start_token, end_token, stop_limit))
-
-    def _greedy_device(self, start_token, end_token, stop_limit, slot):
         lib = _lib.load()
-        st = self._cur
-        B = st["B"]
-        nbytes = int(lib.astk_greedy_workspace_bytes(C.byref(st["dd"]), int(stop_limit)))
-        if nbytes == 0:
-            return None
-        ws = self._workspace("greedy", nbytes)
-        # [n_steps, status word (float), 2 pad words, tokens (stop_limit, B)]: one device buffer, read back in one copy
-        n = 4 + int(stop_limit) * B
-        out = self._pool(f"greedy_out{slot}", (n,), torch.int32)
-        host = self._greedy_pinned.get(slot)
-        if host is None or host.numel() < n:
-            host = self._greedy_pinned[slot] = torch.empty(n, dtype=torch.int32, pin_memory=True)
-        host = host[:n]
-        base = out.data_ptr()
-        check(lib.astk_greedy_decode(C.byref(st["dd"]), C.byref(st["dp"]), _vp(st["enc_states"]), _vp(self._dec_c), _vp(self._dec_h),
-                                     int(start_token), int(end_token), int(stop_limit), C.c_void_p(base + 16), C.c_void_p(base),
-                                     C.c_void_p(base + 4), _vp(ws), ws.numel(), self._stream()))
-        host.copy_(out, non_blocking=True)
-        ev = torch.cuda.Event()
-        ev.record(torch.cuda.current_stream(self.device))
-        return _PendingPredict(host, ev, B)
+        go, eos, stop = int(start_token), int(end_token), int(stop_limit)
+        with using_config("train", False):
+            B = self._begin_decode(X)
+            # [n_steps, status word (float), 2 pad words, tokens (stop_limit, B)]
+            handle = self._device_decode(
+                "greedy", slot, int(lib.astk_greedy_workspace_bytes(C.byref(self._cur["dd"]), stop)), 4 + stop * B, lib.astk_greedy_decode,
+                lambda p, _: (go, eos, stop, p(16), p(0), p(4)),
+                status_at=1, where="predict", parse=lambda v, _: v[4:4 + int(v[0]) * B].reshape(int(v[0]), B).T.copy())
+            return self._device_or_steps("last_predict_path", handle, lambda: self._free_steps(start_token, end_token, stop_limit)[0])
 
     def predict_scored(self, X, start_token, end_token, stop_limit, y=None):
         """predict() that also scores what it decodes: a ScoredPrediction (tokens as predict() returns them, the log-probability of each
@@ -1066,76 +1050,40 @@ class SpeechEncoderDecoder:
     def predict_scored_async(self, X, start_token, end_token, stop_limit, y=None, slot=0):
         """predict_scored with the read-back left to the caller, like predict_async: on the device path (astk_greedy_decode_scored) ONE
         copy of [n_steps, status, tokens, logp, nll] into pinned buffer `slot`; otherwise the per-step loop, finished on return."""
+        lib = _lib.load()
+        go, eos, stop = int(start_token), int(end_token), int(stop_limit)
         with using_config("train", False):
-            X = self._as_input(X)
-            self._cur = None
-            self.encode(X)
-            self.init_decoder_state()
+            B = self._begin_decode(X)
             if y is not None:
                 y = torch.as_tensor(y).to(self.device, torch.int32).contiguous()
-                if y.dim() != 2 or y.shape[0] != self._cur["B"] or y.shape[1] < 1:
-                    raise ValueError(f"predict_scored: y must be (B = {self._cur['B']}, L >= 1), got {tuple(y.shape)}")
-            handle = self._greedy_scored_device(start_token, end_token, stop_limit, y, slot)
-            if handle is not None:
-                self.last_predict_path = "device"
-                return handle
-            self.last_predict_path = "steps"
-            return _Ready(self._predict_scored_steps(start_token, end_token, stop_limit, y))
+                if y.dim() != 2 or y.shape[0] != B or y.shape[1] < 1:
+                    raise ValueError(f"predict_scored: y must be (B = {B}, L >= 1), got {tuple(y.shape)}")
+            # [n_steps, status word (float), 2 pad words, tokens | logp | nll, each (stop_limit, B)]
+            sb = stop * B
+            handle = self._device_decode(
+                "greedy_scored", slot, int(lib.astk_greedy_scored_workspace_bytes(C.byref(self._cur["dd"]), stop)),
+                4 + (3 if y is not None else 2) * sb, lib.astk_greedy_decode_scored,
+                lambda p, _: (go, eos, stop, _vp(y), int(y.shape[1]) if y is not None else 0, _vp(self.mask_pad_id), p(16), p(16 + 4 * sb),
+                              p(16 + 8 * sb) if y is not None else None, p(0), p(4)),
+                status_at=1, where="predict_scored", keep=y,
+                parse=lambda v, _: scored_from_rows(v[4:], int(v[0]), B, stop, y is not None, eos))
 
-    def _greedy_scored_device(self, start_token, end_token, stop_limit, y, slot):
-        lib = _lib.load()
-        st = self._cur
-        B = st["B"]
-        nbytes = int(lib.astk_greedy_scored_workspace_bytes(C.byref(st["dd"]), int(stop_limit)))
-        if nbytes == 0:
-            return None
-        ws = self._workspace("greedy", nbytes)
-        # [n_steps, status word (float), 2 pad words, tokens | logp | nll, each (stop_limit, B)]: one device buffer, read back in one copy
-        sb = int(stop_limit) * B
-        n = 4 + (3 if y is not None else 2) * sb
-        out = self._pool(f"greedy_scored_out{slot}", (n,), torch.int32)
-        host = self._greedy_pinned.get(("scored", slot))
-        if host is None or host.numel() < n:
-            host = self._greedy_pinned[("scored", slot)] = torch.empty(n, dtype=torch.int32, pin_memory=True)
-        host = host[:n]
-        base = out.data_ptr()
-        check(lib.astk_greedy_decode_scored(C.byref(st["dd"]), C.byref(st["dp"]), _vp(st["enc_states"]), _vp(self._dec_c), _vp(self._dec_h),
-                                            int(start_token), int(end_token), int(stop_limit), _vp(y), int(y.shape[1]) if y is not None else 0,
-                                            _vp(self.mask_pad_id), C.c_void_p(base + 16), C.c_void_p(base + 16 + 4 * sb),
-                                            C.c_void_p(base + 16 + 8 * sb) if y is not None else None, C.c_void_p(base),
-                                            C.c_void_p(base + 4), _vp(ws), ws.numel(), self._stream()))
-        host.copy_(out, non_blocking=True)
-        ev = torch.cuda.Event()
-        ev.record(torch.cuda.current_stream(self.device))
-        return _PendingScored(host, ev, B, int(stop_limit), y is not None, int(end_token), y)
+            def steps():
+                """Each step's logits scored: a float64 log_softmax on the device, the token's and the target's entries."""
+                w64 = self.mask_pad_id.double()
 
-    def _predict_scored_steps(self, start_token, end_token, stop_limit, y):
-        """_predict_steps with each step's logits scored: a float64 log_softmax on the device, the maximum's and the target's entries."""
-        with using_config("train", False):
-            B = self._cur["B"]
-            ht = torch.zeros(B, self.A, dtype=torch.float32, device=self.device)
-            word = torch.full((B,), start_token, dtype=torch.int32, device=self.device)
-            done = torch.zeros(B, dtype=torch.bool, device=self.device)
-            w64 = self.mask_pad_id.double()
-            rows, lps, nlls, npred = [], [], [], 0
-            while npred < stop_limit:
-                logits, ht, _ = self.decode_step(word, ht)
-                word = logits.argmax(dim=1).to(torch.int32)
-                ls = torch.log_softmax(logits.double(), dim=1)
-                rows.append(word)
-                lps.append(ls.gather(1, word.long()[:, None])[:, 0])
-                if y is not None:
-                    if len(rows) < y.shape[1]:
-                        t = y[:, len(rows)].long().clamp(0, self.V - 1)
-                        nlls.append(-w64[t] * ls.gather(1, t[:, None])[:, 0])
-                    else:
-                        nlls.append(torch.zeros(B, dtype=torch.float64, device=self.device))
-                done |= word == end_token
-                if bool(done.all()):
-                    break
-                npred += 1
-            f32 = lambda r: torch.stack(r, 0).T.float().cpu().numpy()
-            return ScoredPrediction(torch.stack(rows, 0).T.cpu().numpy(), f32(lps), f32(nlls) if y is not None else None, int(end_token))
+                def record(logits, word, s):
+                    ls = torch.log_softmax(logits.double(), dim=1)
+                    lp = ls.gather(1, word.long()[:, None])[:, 0]
+                    if y is None:
+                        return (lp,)
+                    if s + 1 < y.shape[1]:
+                        t = y[:, s + 1].long().clamp(0, self.V - 1)
+                        return lp, -w64[t] * ls.gather(1, t[:, None])[:, 0]
+                    return lp, torch.zeros(B, dtype=torch.float64, device=self.device)
+                tokens, cols = self._free_steps(start_token, end_token, stop_limit, record=record)
+                return ScoredPrediction(tokens, cols[0], cols[1] if y is not None else None, eos)
+            return self._device_or_steps("last_predict_path", handle, steps)
 
     def sample(self, X, start_token, end_token, stop_limit, seed, streams=None, temperature=1.0):
         """Ancestral sampling: predict_scored() with every step's token drawn from softmax(logits / temperature) by the Gumbel-max
@@ -1150,73 +1098,59 @@ class SpeechEncoderDecoder:
         persistent launch) ONE copy of [n_steps, status, tokens, logp] into pinned buffer `slot`; otherwise the per-step loop,
         finished on return.  `last_predict_path` says which path ran."""
         inv_temp = checked_temperature(temperature)
+        lib = _lib.load()
+        go, eos, stop = int(start_token), int(end_token), int(stop_limit)
         with using_config("train", False):
-            X = self._as_input(X)
-            self._cur = None
-            self.encode(X)
-            self.init_decoder_state()
-            B = self._cur["B"]
+            B = self._begin_decode(X)
             streams = list(range(B)) if streams is None else [int(v) for v in streams]
             if len(streams) != B:
                 raise ValueError(f"sample: streams must name B = {B} rows, got {len(streams)}")
             keys = np.array([sample_row_key(seed, v) for v in streams], dtype=np.uint64)
             keys = torch.from_numpy(keys.view(np.int64)).to(self.device)      # (the bit patterns: torch has no uint64 arithmetic to offer)
-            handle = self._sample_device(start_token, end_token, stop_limit, keys, inv_temp, slot)
-            if handle is not None:
-                self.last_predict_path = "device"
-                return handle
-            self.last_predict_path = "steps"
-            return _Ready(self._sample_steps(start_token, end_token, stop_limit, keys, inv_temp))
+            # [n_steps, status word (float), 2 pad words, tokens | logp, each (stop_limit, B)]
+            sb = stop * B
+            handle = self._device_decode(
+                "sample", slot, int(lib.astk_sample_workspace_bytes(C.byref(self._cur["dd"]), stop)), 4 + 2 * sb, lib.astk_sample_decode,
+                lambda p, _: (go, eos, stop, _vp(keys), inv_temp, p(16), p(16 + 4 * sb), p(0), p(4)),
+                status_at=1, where="sample", keep=keys, parse=lambda v, _: scored_from_rows(v[4:], int(v[0]), B, stop, False, eos))
 
-    def _sample_device(self, start_token, end_token, stop_limit, keys, inv_temp, slot):
-        lib = _lib.load()
-        st = self._cur
-        B = st["B"]
-        nbytes = int(lib.astk_sample_workspace_bytes(C.byref(st["dd"]), int(stop_limit)))
-        if nbytes == 0:
-            return None
-        ws = self._workspace("greedy", nbytes)
-        # [n_steps, status word (float), 2 pad words, tokens | logp, each (stop_limit, B)]: one device buffer, read back in one copy
-        sb = int(stop_limit) * B
-        n = 4 + 2 * sb
-        out = self._pool(f"sample_out{slot}", (n,), torch.int32)
-        host = self._greedy_pinned.get(("sample", slot))
-        if host is None or host.numel() < n:
-            host = self._greedy_pinned[("sample", slot)] = torch.empty(n, dtype=torch.int32, pin_memory=True)
-        host = host[:n]
-        base = out.data_ptr()
-        check(lib.astk_sample_decode(C.byref(st["dd"]), C.byref(st["dp"]), _vp(st["enc_states"]), _vp(self._dec_c), _vp(self._dec_h),
-                                     int(start_token), int(end_token), int(stop_limit), _vp(keys), inv_temp, C.c_void_p(base + 16),
-                                     C.c_void_p(base + 16 + 4 * sb), C.c_void_p(base), C.c_void_p(base + 4), _vp(ws), ws.numel(),
-                                     self._stream()))
-        host.copy_(out, non_blocking=True)
-        ev = torch.cuda.Event()
-        ev.record(torch.cuda.current_stream(self.device))
-        return _PendingScored(host, ev, B, int(stop_limit), False, int(end_token), keys, where="sample")
+            def steps():
+                """Per step one astk_gumbel_rows fill, the argmax of logits * inv_temp + g in float32, and the drawn token's entry of a
+                float64 log_softmax of logits * inv_temp."""
+                g = torch.empty(B, self.V, dtype=torch.float32, device=self.device)
 
-    def _sample_steps(self, start_token, end_token, stop_limit, keys, inv_temp):
-        """The per-step sampled loop: decode_step, one astk_gumbel_rows fill, the argmax of logits * inv_temp + g in float32, and the
-        drawn token's entry of a float64 log_softmax of logits * inv_temp."""
-        lib = _lib.load()
+                def pick(logits, s):
+                    check(lib.astk_gumbel_rows(_vp(keys), B, s, self.V, _vp(g), self._stream()))
+                    return (logits * inv_temp + g).argmax(dim=1).to(torch.int32)
+
+                def record(logits, word, s):
+                    return (torch.log_softmax(logits.double() * inv_temp, dim=1).gather(1, word.long()[:, None])[:, 0],)
+                tokens, cols = self._free_steps(start_token, end_token, stop_limit, pick, record)
+                return ScoredPrediction(tokens, cols[0], None, eos)
+            return self._device_or_steps("last_predict_path", handle, steps)
+
+    def _free_steps(self, start_token, end_token, stop_limit, pick=None, record=None):
+        """The free-running per-step loop (seq2seq.py:475-527): one astk_decoder_step_infer, a pick and a host read per token, until
+        every row has emitted `end_token` or at stop_limit.  pick(logits, s) = the int32 tokens of step s (default: the argmax);
+        record(logits, tokens, s) = a tuple of (B,) columns kept beside them.  Returns (tokens (B, n_steps) int32, the recorded columns
+        as (B, n_steps) float32 arrays), on the host."""
         with using_config("train", False):
             B = self._cur["B"]
             ht = torch.zeros(B, self.A, dtype=torch.float32, device=self.device)
             word = torch.full((B,), start_token, dtype=torch.int32, device=self.device)
             done = torch.zeros(B, dtype=torch.bool, device=self.device)
-            g = torch.empty(B, self.V, dtype=torch.float32, device=self.device)
-            rows, lps, npred = [], [], 0
+            rows, cols, npred = [], [], 0
             while npred < stop_limit:
                 logits, ht, _ = self.decode_step(word, ht)
-                check(lib.astk_gumbel_rows(_vp(keys), B, len(rows), self.V, _vp(g), self._stream()))
-                word = (logits * inv_temp + g).argmax(dim=1).to(torch.int32)
-                ls = torch.log_softmax(logits.double() * inv_temp, dim=1)
+                word = logits.argmax(dim=1).to(torch.int32) if pick is None else pick(logits, len(rows))
+                if record is not None:
+                    cols.append(record(logits, word, len(rows)))
                 rows.append(word)
-                lps.append(ls.gather(1, word.long()[:, None])[:, 0])
                 done |= word == end_token
                 if bool(done.all()):
                     break
                 npred += 1
-            return ScoredPrediction(torch.stack(rows, 0).T.cpu().numpy(), torch.stack(lps, 0).T.float().cpu().numpy(), None, int(end_token))
+            return torch.stack(rows, 0).T.cpu().numpy(), [torch.stack(c, 0).T.float().cpu().numpy() for c in zip(*cols)]
 
     def score(self, X, y, return_alpha=False):
         """Forced decoding: the eval-mode model run along the given translations y (B, L) -- step s is fed y[:, s] and scored against
@@ -1229,61 +1163,27 @@ class SpeechEncoderDecoder:
         persistent launch) ONE copy of [status, logp, logp_max, pred] into pinned buffer `slot` (alpha, when asked for, is one more
         copy); shapes the library does not run on the device loop take the per-step loop, finished on return."""
         y_host = checked_targets(y, self.V)
+        lib = _lib.load()
         with using_config("train", False):
-            X = self._as_input(X)
-            self._cur = None
-            self.encode(X)
-            self.init_decoder_state()
-            B = self._cur["B"]
+            B = self._begin_decode(X)
             if y_host.shape[0] != B:
                 raise ValueError(f"score: y must have B = {B} rows, got {tuple(y_host.shape)}")
             weight = (y_host[:, 1:] != 0).astype(np.float32)         # mask_pad_id[y[:, 1:]]: 0 at PAD, else 1 (materialize)
             y_dev = torch.from_numpy(y_host).to(self.device)
-            handle = self._forced_device(y_dev, weight, bool(return_alpha), slot)
-            if handle is not None:
-                self.last_score_path = "device"
-                return handle
-            self.last_score_path = "steps"
-            return _Ready(self._score_steps(y_dev, weight, bool(return_alpha)))
-
-    def _forced_device(self, y, weight, with_alpha, slot):
-        lib = _lib.load()
-        st = self._cur
-        B, S, T2 = st["B"], int(y.shape[1]) - 1, st["T2"]
-        # (0 for shapes off the device loop and for S > ASTK_GREEDY_MAX_STEPS: the per-step loop serves those)
-        nbytes = int(lib.astk_forced_workspace_bytes(C.byref(st["dd"]), S, int(with_alpha)))
-        if nbytes == 0:
-            return None
-        ws = self._workspace("forced", nbytes)
-        # [status word (float), 3 pad words, logp | logp_max | pred, each (S, B)]: one device buffer, read back in one copy
-        sb = S * B
-        n = 4 + 3 * sb
-        out = self._pool(f"forced_out{slot}", (n,), torch.int32)
-        host = self._greedy_pinned.get(("forced", slot))
-        if host is None or host.numel() < n:
-            host = self._greedy_pinned[("forced", slot)] = torch.empty(n, dtype=torch.int32, pin_memory=True)
-        host = host[:n]
-        alpha = host_alpha = None
-        if with_alpha:
-            na = sb * T2
-            alpha = self._pool(f"forced_alpha{slot}", (na,), torch.float32)
-            host_alpha = self._greedy_pinned.get(("forced_alpha", slot))
-            if host_alpha is None or host_alpha.numel() < na:
-                host_alpha = self._greedy_pinned[("forced_alpha", slot)] = torch.empty(na, dtype=torch.float32, pin_memory=True)
-            host_alpha = host_alpha[:na]
-        base = out.data_ptr()
-        check(lib.astk_forced_score(C.byref(st["dd"]), C.byref(st["dp"]), _vp(st["enc_states"]), _vp(self._dec_c), _vp(self._dec_h),
-                                    _vp(y), S + 1, C.c_void_p(base + 16), C.c_void_p(base + 16 + 4 * sb), C.c_void_p(base + 16 + 8 * sb),
-                                    _vp(alpha), C.c_void_p(base), _vp(ws), ws.numel(), self._stream()))
-        host.copy_(out, non_blocking=True)
-        if with_alpha:
-            host_alpha.copy_(alpha, non_blocking=True)
-        ev = torch.cuda.Event()
-        ev.record(torch.cuda.current_stream(self.device))
-        return _PendingForced(host, host_alpha, ev, B, S, weight, y)
+            S, with_alpha = int(y_dev.shape[1]) - 1, bool(return_alpha)
+            # [status word (float), 3 pad words, logp | logp_max | pred, each (S, B)]; alpha (S, B, T'') in a buffer of its own
+            # (a workspace of 0 also for S > ASTK_GREEDY_MAX_STEPS: the per-step loop serves those)
+            sb = S * B
+            handle = self._device_decode(
+                "forced", slot, int(lib.astk_forced_workspace_bytes(C.byref(self._cur["dd"]), S, int(with_alpha))), 4 + 3 * sb,
+                lib.astk_forced_score, lambda p, alpha: (_vp(y_dev), S + 1, p(16), p(16 + 4 * sb), p(16 + 8 * sb), alpha, p(0)),
+                n_alpha=sb * self._cur["T2"] if with_alpha else 0, status_at=0, where="score", keep=y_dev,
+                parse=lambda v, al: forced_from_rows(v[4:], B, S, weight, None if al is None else al.reshape(S, B, -1).transpose(1, 0, 2).copy()))
+            return self._device_or_steps("last_score_path", handle, lambda: self._score_steps(y_dev, weight, with_alpha))
 
     def _score_steps(self, y, weight, with_alpha):
-        """The per-step forced loop: y[:, s] through decode_step, a float64 log_softmax of each step's logits on the device."""
+        """The per-step forced loop: y[:, s] through decode_step, a float64 log_softmax of each step's logits on the device.  (Kept apart
+        from _free_steps: a fixed number of steps, the given token fed, and the attention rows kept.)"""
         with using_config("train", False):
             B, S = self._cur["B"], int(y.shape[1]) - 1
             ht = torch.zeros(B, self.A, dtype=torch.float32, device=self.device)
@@ -1300,24 +1200,6 @@ class SpeechEncoderDecoder:
             f32 = lambda r: torch.stack(r, 0).T.float().cpu().numpy()
             alpha = torch.stack(alphas, 1).cpu().numpy() if with_alpha else None
             return ForcedScore(f32(lps), f32(lpm), torch.stack(preds, 0).T.cpu().numpy(), weight, alpha)
-
-    def _predict_steps(self, start_token, end_token, stop_limit):
-        """The per-step greedy loop (seq2seq.py:475-527): one astk_decoder_step_infer, an argmax and a host read per token."""
-        with using_config("train", False):
-            B = self._cur["B"]
-            ht = torch.zeros(B, self.A, dtype=torch.float32, device=self.device)
-            word = torch.full((B,), start_token, dtype=torch.int32, device=self.device)
-            done = torch.zeros(B, dtype=torch.bool, device=self.device)
-            rows, npred = [], 0
-            while npred < stop_limit:
-                logits, ht, _ = self.decode_step(word, ht)
-                word = logits.argmax(dim=1).to(torch.int32)
-                rows.append(word)
-                done |= word == end_token
-                if bool(done.all()):
-                    break
-                npred += 1
-            return torch.stack(rows, 0).T.cpu().numpy()
 
     def get_encoder_states(self):
         st = self._cur

@@ -16,54 +16,13 @@ import pytest
 import torch
 
 from conftest import tiny_cfg
+from decode_helpers import CFG1, EOS, ES_EN, GO, MID, OUT_SCALE, WIDE, lse64 as _lse64, setup as _setup, targets, tol
 
 pytestmark = pytest.mark.gpu
 
-GO, EOS = 1, 2
-OUT_SCALE = 8.0
-ES_EN = dict(enc_layers=3, dec_layers=3, H=512, E=128, A=512, c0=128, c1=512, V=1098)     # es_en_20h
-CFG1 = dict(enc_layers=3, dec_layers=1, H=512, E=128, A=512, c0=128, c1=512, V=1098)      # BASELINE configs[1]
-WIDE = dict(enc_layers=1, dec_layers=1, H=1024, E=16, A=1024, c0=8, c1=16, V=57)
-MID = dict(enc_layers=2, dec_layers=2, H=64, E=16, A=64, c0=8, c1=16, V=57)
-E_LOOP = 3.7e-6             # tests/test_gpu_greedy_scored.py: the per-step loop's own error against the oracle
 GAP = 1e-3                  # tests/test_gpu_greedy.py: the argmax margin against the oracle
 SHARE = 0.98
-
-
-def tol(value):
-    return np.maximum(2 * E_LOOP, 1e-4 * np.maximum(1.0, np.abs(value)))
-
-
-def _setup(shape, B, T, seed=0, eos_bias=0.0, D=80, **cfg_over):
-    from oracle import ast_ref as R
-    from ast_amd.seq2seq import SpeechEncoderDecoder
-    cfg = tiny_cfg(**shape)
-    for k, v in cfg_over.items():
-        cfg["rnn_config"][k] = v
-    V = shape["V"]
-    P = R.init_params(cfg, D, V, seed=seed, dtype=np.float32)
-    P["out/W"] = (P["out/W"] * OUT_SCALE).astype(np.float32)
-    P["out/b"] = P["out/b"].copy()
-    P["out/b"][EOS] += eos_bias
-    X, _ = R.synth_batch(B, T, D, 3, V, seed=seed + 1, dtype=np.float32)
-    c = copy.deepcopy(cfg)
-    c["rnn_config"]["dec_vocab_size"] = V
-    m = SpeechEncoderDecoder(0, c).materialize(D, values=P)
-    return cfg, P, X, m
-
-
-def _targets(B, L, V, seed):
-    """(B, L) int32 targets, a quarter of the positions PAD (weight 0), column 0 = GO."""
-    rng = np.random.default_rng(seed)
-    y = rng.integers(1, V, size=(B, L)).astype(np.int32)
-    y[rng.random((B, L)) < 0.25] = 0
-    y[:, 0] = GO
-    return y
-
-
-def _lse64(lg):
-    mx = lg.max(axis=1, keepdims=True)
-    return (mx + np.log(np.exp(lg - mx).sum(axis=1, keepdims=True)))[:, 0]
+_targets = functools.partial(targets, go_first=True)
 
 
 def _rows_of(lg, y_next):

@@ -4,7 +4,6 @@ streamed attention slices, state left behind, the shapes that fall back to the l
 
 Token comparisons are exact, guarded by the argmax margin at every compared step: `Wo` is scaled (the goldens' out_scale 8) so that the
 top-2 gap is far above float32 rounding, and the margin is asserted as a precondition, so a comparison can never pass vacuously."""
-import copy
 import ctypes as C
 import types
 
@@ -12,34 +11,9 @@ import numpy as np
 import pytest
 import torch
 
-from conftest import tiny_cfg
+from decode_helpers import CFG1, EOS, ES_EN, GO, MID, WIDE, setup as _setup
 
 pytestmark = pytest.mark.gpu
-
-GO, EOS = 1, 2
-OUT_SCALE = 8.0
-ES_EN = dict(enc_layers=3, dec_layers=3, H=512, E=128, A=512, c0=128, c1=512, V=1098)     # es_en_20h
-CFG1 = dict(enc_layers=3, dec_layers=1, H=512, E=128, A=512, c0=128, c1=512, V=1098)      # BASELINE configs[1] (bench.py cfg1)
-WIDE = dict(enc_layers=1, dec_layers=1, H=1024, E=16, A=1024, c0=8, c1=16, V=57)         # the wide decoder (configs[4]'s H = A = 1024)
-MID = dict(enc_layers=2, dec_layers=2, H=64, E=16, A=64, c0=8, c1=16, V=57)
-
-
-def _setup(shape, B, T, seed=0, eos_bias=0.0, D=80, **cfg_over):
-    from oracle import ast_ref as R
-    from ast_amd.seq2seq import SpeechEncoderDecoder
-    cfg = tiny_cfg(**shape)
-    for k, v in cfg_over.items():
-        cfg["rnn_config"][k] = v
-    V = shape["V"]
-    P = R.init_params(cfg, D, V, seed=seed, dtype=np.float32)
-    P["out/W"] = (P["out/W"] * OUT_SCALE).astype(np.float32)
-    P["out/b"] = P["out/b"].copy()
-    P["out/b"][EOS] += eos_bias
-    X, _ = R.synth_batch(B, T, D, 3, V, seed=seed + 1, dtype=np.float32)
-    c = copy.deepcopy(cfg)
-    c["rnn_config"]["dec_vocab_size"] = V
-    m = SpeechEncoderDecoder(0, c).materialize(D, values=P)
-    return cfg, P, X, m
 
 
 def _loop(m, X, stop_limit, eos_dist=None):

@@ -3,8 +3,7 @@ SpeechEncoderDecoder.predict_scored, NN.predict_scored, train.py --dev-loss) aga
 oracle.minichainer.softmax_cross_entropy, and against the per-step GPU loop; what it must leave untouched; fallbacks and bad arguments.
 
 Token comparisons are exact and guarded by the argmax margin as in test_gpu_greedy.py.  Log-probabilities and loss terms are compared
-under tol(): max(2 * E_LOOP, 1e-4 * max(1, |value|)), see E_LOOP below.  Every test prints its figures before it asserts."""
-import copy
+under tol(): max(2 * E_LOOP, 1e-4 * max(1, |value|)), see E_LOOP in tests/decode_helpers.py.  Every test prints its figures before it asserts."""
 import ctypes as C
 import types
 
@@ -13,57 +12,10 @@ import pytest
 import torch
 
 from conftest import tiny_cfg
+from decode_helpers import (CFG1, EOS, ES_EN, GO, MID, WIDE, guard as _guard, lse64 as _lse64, max_err as _max_err, setup as _setup,
+                            targets as _targets, tol)
 
 pytestmark = pytest.mark.gpu
-
-GO, EOS = 1, 2
-OUT_SCALE = 8.0
-ES_EN = dict(enc_layers=3, dec_layers=3, H=512, E=128, A=512, c0=128, c1=512, V=1098)     # es_en_20h
-CFG1 = dict(enc_layers=3, dec_layers=1, H=512, E=128, A=512, c0=128, c1=512, V=1098)      # BASELINE configs[1]
-WIDE = dict(enc_layers=1, dec_layers=1, H=1024, E=16, A=1024, c0=8, c1=16, V=57)
-MID = dict(enc_layers=2, dec_layers=2, H=64, E=16, A=64, c0=8, c1=16, V=57)
-
-# The largest error of the PER-STEP loop (astk_decoder_step_infer logits in float32, LSE in float64 on the host: the arithmetic the
-# project had before the scored mode) against the float64 oracle, over logp and nll at every guarded position of the full-size cases
-# below (test_scored_matches_oracle_full_size prints it as e_loop): 3.26e-6 on configs[1], 3.68e-6 on es_en_20h, one MI355X.  The device loop gets twice that -- its logits are
-# accumulated per tile in another order and its LSE is float32 -- or the project's bound for float32 log-probabilities against the
-# oracle (tests/test_gpu_model.py:172), whichever is larger.
-E_LOOP = 3.7e-6
-
-
-def tol(value):
-    return np.maximum(2 * E_LOOP, 1e-4 * np.maximum(1.0, np.abs(value)))
-
-
-def _setup(shape, B, T, seed=0, eos_bias=0.0, D=80, **cfg_over):
-    from oracle import ast_ref as R
-    from ast_amd.seq2seq import SpeechEncoderDecoder
-    cfg = tiny_cfg(**shape)
-    for k, v in cfg_over.items():
-        cfg["rnn_config"][k] = v
-    V = shape["V"]
-    P = R.init_params(cfg, D, V, seed=seed, dtype=np.float32)
-    P["out/W"] = (P["out/W"] * OUT_SCALE).astype(np.float32)
-    P["out/b"] = P["out/b"].copy()
-    P["out/b"][EOS] += eos_bias
-    X, _ = R.synth_batch(B, T, D, 3, V, seed=seed + 1, dtype=np.float32)
-    c = copy.deepcopy(cfg)
-    c["rnn_config"]["dec_vocab_size"] = V
-    m = SpeechEncoderDecoder(0, c).materialize(D, values=P)
-    return cfg, P, X, m
-
-
-def _targets(B, L, V, seed):
-    """(B, L) int32 targets, a quarter of the positions PAD (weight 0)."""
-    rng = np.random.default_rng(seed)
-    y = rng.integers(1, V, size=(B, L)).astype(np.int32)
-    y[rng.random((B, L)) < 0.25] = 0
-    return y
-
-
-def _lse64(lg):
-    mx = lg.max(axis=1, keepdims=True)
-    return (mx + np.log(np.exp(lg - mx).sum(axis=1, keepdims=True)))[:, 0]
 
 
 def _score_rows(lg, word, y, step, V):
@@ -147,24 +99,6 @@ def _scored(m, X, stop_limit, y=None, path="device"):
     r = m.predict_scored(torch.from_numpy(X), GO, EOS, stop_limit, y=None if y is None else torch.from_numpy(y))
     assert m.last_predict_path == path, m.last_predict_path
     return r
-
-
-def _guard(ref_tokens, gaps, thr):
-    """(B, n) bool: positions before the row's first step whose top-2 gap is below thr."""
-    B, n = ref_tokens.shape
-    ok = np.zeros((B, n), dtype=bool)
-    for b in range(B):
-        low = np.nonzero(gaps[:, b] < thr)[0]
-        ok[b, :int(low[0]) if len(low) else n] = True
-    return ok
-
-
-def _max_err(name, got, ref, ok):
-    """Prints and returns the largest error and the largest error / tolerance over the positions `ok`."""
-    err = np.abs(got.astype(np.float64) - ref)[ok]
-    rel = err / tol(ref[ok])
-    print(f"  {name}: max abs err {err.max():.3e}, max err / tol {rel.max():.3f}, max |value| {np.abs(ref[ok]).max():.3f}, n {ok.sum()}")
-    return float(err.max()), float(rel.max())
 
 
 # ---------------------------------------------------------------- oracle parity at full size

@@ -6,7 +6,6 @@ what it must leave untouched; fallbacks and bad arguments.
 The recipes are those of tests/test_gpu_greedy_scored.py, restated: token comparisons are exact and guarded by the top-2 gap of the
 PERTURBED scores z = logits * inv_temp + g; log-probabilities are compared under tol(): max(2 * E_LOOP * max(1, 1 / temperature),
 1e-4 * max(1, |value|)) -- logit errors scale with inv_temp.  Every test prints its figures before it asserts."""
-import copy
 import ctypes as C
 
 import numpy as np
@@ -14,40 +13,13 @@ import pytest
 import torch
 
 from conftest import tiny_cfg
+from decode_helpers import (CFG1, EOS, ES_EN, GO, MID, WIDE, guard as _guard, lse64 as _lse64, max_err as _max_err, setup as _setup,
+                            tol)
 from sample_noise_model import noise as _noise, row_key as _row_key
 
 pytestmark = pytest.mark.gpu
 
-GO, EOS = 1, 2
-OUT_SCALE = 8.0
-ES_EN = dict(enc_layers=3, dec_layers=3, H=512, E=128, A=512, c0=128, c1=512, V=1098)     # es_en_20h
-CFG1 = dict(enc_layers=3, dec_layers=1, H=512, E=128, A=512, c0=128, c1=512, V=1098)      # BASELINE configs[1]
-WIDE = dict(enc_layers=1, dec_layers=1, H=1024, E=16, A=1024, c0=8, c1=16, V=57)
-MID = dict(enc_layers=2, dec_layers=2, H=64, E=16, A=64, c0=8, c1=16, V=57)
-E_LOOP = 3.7e-6             # tests/test_gpu_greedy_scored.py: the per-step loop's own error against the oracle
 SEED = 2024
-
-
-def tol(value, temperature=1.0):
-    return np.maximum(2 * E_LOOP * max(1.0, 1.0 / temperature), 1e-4 * np.maximum(1.0, np.abs(value)))
-
-
-def _setup(shape, B, T, seed=0, eos_bias=0.0, D=80, **cfg_over):
-    from oracle import ast_ref as R
-    from ast_amd.seq2seq import SpeechEncoderDecoder
-    cfg = tiny_cfg(**shape)
-    for k, v in cfg_over.items():
-        cfg["rnn_config"][k] = v
-    V = shape["V"]
-    P = R.init_params(cfg, D, V, seed=seed, dtype=np.float32)
-    P["out/W"] = (P["out/W"] * OUT_SCALE).astype(np.float32)
-    P["out/b"] = P["out/b"].copy()
-    P["out/b"][EOS] += eos_bias
-    X, _ = R.synth_batch(B, T, D, 3, V, seed=seed + 1, dtype=np.float32)
-    c = copy.deepcopy(cfg)
-    c["rnn_config"]["dec_vocab_size"] = V
-    m = SpeechEncoderDecoder(0, c).materialize(D, values=P)
-    return cfg, P, X, m
 
 
 def _keys(seed, streams):
@@ -56,11 +28,6 @@ def _keys(seed, streams):
 
 def _inv(temperature):
     return float(np.float32(1.0 / temperature))
-
-
-def _lse64(lg):
-    mx = lg.max(axis=1, keepdims=True)
-    return (mx + np.log(np.exp(lg - mx).sum(axis=1, keepdims=True)))[:, 0]
 
 
 def _draw(lg, keys, step, inv_temp):
@@ -131,24 +98,6 @@ def _sample(m, X, stop_limit, streams=None, temperature=1.0, seed=SEED, path="de
     assert m.last_predict_path == path, m.last_predict_path
     assert r.nll is None and r.loss is None and r.tokens.dtype == np.int32 and r.logp.dtype == np.float32
     return r
-
-
-def _guard(ref_tokens, gaps, thr):
-    """(B, n) bool: positions before the row's first step whose top-2 gap is below thr."""
-    B, n = ref_tokens.shape
-    ok = np.zeros((B, n), dtype=bool)
-    for b in range(B):
-        low = np.nonzero(gaps[:, b] < thr)[0]
-        ok[b, :int(low[0]) if len(low) else n] = True
-    return ok
-
-
-def _max_err(name, got, ref, ok, temperature=1.0):
-    """Prints and returns the largest error and the largest error / tolerance over the positions `ok`."""
-    err = np.abs(got.astype(np.float64) - ref)[ok]
-    rel = err / tol(ref[ok], temperature)
-    print(f"  {name}: max abs err {err.max():.3e}, max err / tol {rel.max():.3f}, max |value| {np.abs(ref[ok]).max():.3f}, n {ok.sum()}")
-    return float(err.max()), float(rel.max())
 
 
 def _status_is_clear():
