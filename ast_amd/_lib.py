@@ -182,6 +182,14 @@ SIGNATURES = {
     "astk_forced_workspace_bytes": (_SZ, [C.POINTER(DecoderDesc), _I, _I]),
     "astk_forced_score": (C.c_int, [C.POINTER(DecoderDesc), C.POINTER(DecoderParams), _VP, _VP, _VP, _VP, _I, _VP, _VP, _VP, _VP, _VP, _VP, _SZ,
                                     _VP]),
+    "astk_greedy_decode_rows": (C.c_int, [C.POINTER(DecoderDesc), C.POINTER(DecoderParams), _VP, _VP, _VP, _I, _I, _I, _VP, _VP, _VP, _VP,
+                                          _SZ, _VP, _VP]),
+    "astk_greedy_decode_scored_rows": (C.c_int, [C.POINTER(DecoderDesc), C.POINTER(DecoderParams), _VP, _VP, _VP, _I, _I, _I, _VP, _I, _VP,
+                                                 _VP, _VP, _VP, _VP, _VP, _VP, _SZ, _VP, _VP]),
+    "astk_sample_decode_rows": (C.c_int, [C.POINTER(DecoderDesc), C.POINTER(DecoderParams), _VP, _VP, _VP, _I, _I, _I, _VP, _F, _VP, _VP, _VP,
+                                          _VP, _VP, _SZ, _VP, _VP]),
+    "astk_forced_score_rows": (C.c_int, [C.POINTER(DecoderDesc), C.POINTER(DecoderParams), _VP, _VP, _VP, _VP, _I, _VP, _VP, _VP, _VP, _VP,
+                                         _VP, _SZ, _VP, _VP]),
     "astk_beam_workspace_bytes": (_SZ, [C.POINTER(BeamDesc), C.POINTER(DecoderDesc)]),
     "astk_beam_step": (C.c_int, [C.POINTER(BeamDesc), C.POINTER(DecoderDesc), C.POINTER(DecoderParams), _VP, C.POINTER(BeamState), _I, _VP,
                                  _SZ, _VP]),

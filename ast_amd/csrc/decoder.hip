@@ -46,20 +46,22 @@ bool decoder_persist_b6_split(const astk_decoder_desc* d);
 // greedy decoding on the persistent loop (decoder_persist.hip)
 size_t greedy_workspace_bytes(const astk_decoder_desc* d, int stop_limit);
 int greedy_decode_launch(const astk_decoder_desc* d, const astk_decoder_params* prm, const float* enc, const float* c0, const float* h0, int go,
-                         int eos, int stop_limit, int32_t* tokens, int32_t* n_steps, float* status_dst, void* ws, size_t ws_bytes, hipStream_t s);
+                         int eos, int stop_limit, int32_t* tokens, int32_t* n_steps, float* status_dst, void* ws, size_t ws_bytes,
+                         const int32_t* row_len, hipStream_t s);
 size_t greedy_scored_workspace_bytes(const astk_decoder_desc* d, int stop_limit);
 int greedy_decode_scored_launch(const astk_decoder_desc* d, const astk_decoder_params* prm, const float* enc, const float* c0, const float* h0,
                                 int go, int eos, int stop_limit, const int32_t* y, int ldy, const float* class_weight, int32_t* tokens,
-                                float* logp, float* nll, int32_t* n_steps, float* status_dst, void* ws, size_t ws_bytes, hipStream_t s);
+                                float* logp, float* nll, int32_t* n_steps, float* status_dst, void* ws, size_t ws_bytes,
+                                const int32_t* row_len, hipStream_t s);
 size_t sample_workspace_bytes(const astk_decoder_desc* d, int stop_limit);
 int sample_decode_launch(const astk_decoder_desc* d, const astk_decoder_params* prm, const float* enc, const float* c0, const float* h0, int go,
                          int eos, int stop_limit, const uint64_t* row_keys, float inv_temp, int32_t* tokens, float* logp, int32_t* n_steps,
-                         float* status_dst, void* ws, size_t ws_bytes, hipStream_t s);
+                         float* status_dst, void* ws, size_t ws_bytes, const int32_t* row_len, hipStream_t s);
 int gumbel_rows_launch(const uint64_t* row_keys, int B, int step, int V, float* out, hipStream_t s);
 size_t forced_workspace_bytes(const astk_decoder_desc* d, int n_steps, int with_alpha);
 int forced_score_launch(const astk_decoder_desc* d, const astk_decoder_params* prm, const float* enc, const float* c0, const float* h0,
                         const int32_t* y, int ldy, float* logp, float* logp_max, int32_t* pred, float* alpha, float* status_dst, void* ws,
-                        size_t ws_bytes, hipStream_t s);
+                        size_t ws_bytes, const int32_t* row_len, hipStream_t s);
 int decoder_persist_bwd_launch(const astk_decoder_desc* d, const float* enc, const float* rnn_masks, const DecPersistBwdBuffers& bf,
                                hipStream_t s);
 
@@ -987,7 +989,13 @@ size_t astk_greedy_workspace_bytes(const astk_decoder_desc* d, int stop_limit) {
 int astk_greedy_decode(const astk_decoder_desc* d, const astk_decoder_params* p, const float* enc, const float* c0, const float* h0,
                        int go, int eos, int stop_limit, int32_t* tokens, int32_t* n_steps, float* status_dst,
                        void* ws, size_t ws_bytes, void* stream) {
-  return greedy_decode_launch(d, p, enc, c0, h0, go, eos, stop_limit, tokens, n_steps, status_dst, ws, ws_bytes, (hipStream_t)stream);
+  return greedy_decode_launch(d, p, enc, c0, h0, go, eos, stop_limit, tokens, n_steps, status_dst, ws, ws_bytes, nullptr, (hipStream_t)stream);
+}
+
+int astk_greedy_decode_rows(const astk_decoder_desc* d, const astk_decoder_params* p, const float* enc, const float* c0, const float* h0,
+                            int go, int eos, int stop_limit, int32_t* tokens, int32_t* n_steps, float* status_dst,
+                            void* ws, size_t ws_bytes, void* stream, const int32_t* row_len) {
+  return greedy_decode_launch(d, p, enc, c0, h0, go, eos, stop_limit, tokens, n_steps, status_dst, ws, ws_bytes, row_len, (hipStream_t)stream);
 }
 
 size_t astk_greedy_scored_workspace_bytes(const astk_decoder_desc* d, int stop_limit) { return greedy_scored_workspace_bytes(d, stop_limit); }
@@ -996,7 +1004,15 @@ int astk_greedy_decode_scored(const astk_decoder_desc* d, const astk_decoder_par
                               int go, int eos, int stop_limit, const int32_t* y, int ldy, const float* class_weight, int32_t* tokens,
                               float* logp, float* nll, int32_t* n_steps, float* status_dst, void* ws, size_t ws_bytes, void* stream) {
   return greedy_decode_scored_launch(d, p, enc, c0, h0, go, eos, stop_limit, y, ldy, class_weight, tokens, logp, nll, n_steps, status_dst, ws,
-                                     ws_bytes, (hipStream_t)stream);
+                                     ws_bytes, nullptr, (hipStream_t)stream);
+}
+
+int astk_greedy_decode_scored_rows(const astk_decoder_desc* d, const astk_decoder_params* p, const float* enc, const float* c0,
+                                   const float* h0, int go, int eos, int stop_limit, const int32_t* y, int ldy, const float* class_weight,
+                                   int32_t* tokens, float* logp, float* nll, int32_t* n_steps, float* status_dst, void* ws,
+                                   size_t ws_bytes, void* stream, const int32_t* row_len) {
+  return greedy_decode_scored_launch(d, p, enc, c0, h0, go, eos, stop_limit, y, ldy, class_weight, tokens, logp, nll, n_steps, status_dst, ws,
+                                     ws_bytes, row_len, (hipStream_t)stream);
 }
 
 size_t astk_sample_workspace_bytes(const astk_decoder_desc* d, int stop_limit) { return sample_workspace_bytes(d, stop_limit); }
@@ -1005,7 +1021,14 @@ int astk_sample_decode(const astk_decoder_desc* d, const astk_decoder_params* p,
                        int go, int eos, int stop_limit, const uint64_t* row_keys, float inv_temp, int32_t* tokens, float* logp,
                        int32_t* n_steps, float* status_dst, void* ws, size_t ws_bytes, void* stream) {
   return sample_decode_launch(d, p, enc, c0, h0, go, eos, stop_limit, row_keys, inv_temp, tokens, logp, n_steps, status_dst, ws, ws_bytes,
-                              (hipStream_t)stream);
+                              nullptr, (hipStream_t)stream);
+}
+
+int astk_sample_decode_rows(const astk_decoder_desc* d, const astk_decoder_params* p, const float* enc, const float* c0, const float* h0,
+                            int go, int eos, int stop_limit, const uint64_t* row_keys, float inv_temp, int32_t* tokens, float* logp,
+                            int32_t* n_steps, float* status_dst, void* ws, size_t ws_bytes, void* stream, const int32_t* row_len) {
+  return sample_decode_launch(d, p, enc, c0, h0, go, eos, stop_limit, row_keys, inv_temp, tokens, logp, n_steps, status_dst, ws, ws_bytes,
+                              row_len, (hipStream_t)stream);
 }
 
 int astk_gumbel_rows(const uint64_t* row_keys, int B, int step, int V, float* out, void* stream) {
@@ -1021,7 +1044,13 @@ size_t astk_forced_workspace_bytes(const astk_decoder_desc* d, int n_steps, int 
 int astk_forced_score(const astk_decoder_desc* d, const astk_decoder_params* p, const float* enc, const float* c0, const float* h0,
                       const int32_t* y, int ldy, float* logp, float* logp_max, int32_t* pred, float* alpha, float* status_dst, void* ws,
                       size_t ws_bytes, void* stream) {
-  return forced_score_launch(d, p, enc, c0, h0, y, ldy, logp, logp_max, pred, alpha, status_dst, ws, ws_bytes, (hipStream_t)stream);
+  return forced_score_launch(d, p, enc, c0, h0, y, ldy, logp, logp_max, pred, alpha, status_dst, ws, ws_bytes, nullptr, (hipStream_t)stream);
+}
+
+int astk_forced_score_rows(const astk_decoder_desc* d, const astk_decoder_params* p, const float* enc, const float* c0, const float* h0,
+                           const int32_t* y, int ldy, float* logp, float* logp_max, int32_t* pred, float* alpha, float* status_dst,
+                           void* ws, size_t ws_bytes, void* stream, const int32_t* row_len) {
+  return forced_score_launch(d, p, enc, c0, h0, y, ldy, logp, logp_max, pred, alpha, status_dst, ws, ws_bytes, row_len, (hipStream_t)stream);
 }
 
 }  // extern "C"

@@ -101,6 +101,9 @@ struct PDecArgs {
   // sampled mode (SM): Gumbel-max draws from softmax(logits * inv_temp); LSE = LOGP [S][B] as in the scored mode
   const uint64_t* row_keys;   // [B] sample_row_key(seed, stream) of every batch row
   float inv_temp;
+  // inference modes (GR): per-row source lengths, 1 <= row_len[b] <= T, or null = every row attends over all T positions.  Read once,
+  // in front of the step loop, by the attention workgroups
+  const int32_t* row_len;
 };
 
 __device__ __forceinline__ unsigned ld_flag(const unsigned* p) { return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
@@ -460,10 +463,17 @@ __device__ __forceinline__ void decoder_persist_fwd_body(const PDecArgs& a) {
     }
   }
   // ---------------- resident slices of enc_states and encA = enc Wa in LDS: rows [t0, t1) of batch row att_b
-  const int t0 = att_sp * a.chunk, t1 = min(T, t0 + a.chunk);
-  const int nrow = has_att ? t1 - t0 : 0;
+  const int t0 = att_sp * a.chunk;
+  int t1 = min(T, t0 + a.chunk);
+  if constexpr (GR) {        // a row with a length: this workgroup's slice ends where the row does, and is EMPTY (nrow = 0) beyond it
+    if (a.row_len) t1 = max(t0, min(t1, min(T, a.row_len[att_b])));
+  }
+  const int nrow0 = has_att ? t1 - t0 : 0;
   const int cres = NC > 0 ? min(a.chunk, PDEC_RES_ROWS) : a.chunk;      // rows of the slice kept in LDS
-  const int nres = min(nrow, cres);
+  const int nres0 = min(nrow0, cres);
+  // GR: the row count is a loaded value now, which a register would have to hold across the whole step loop (the 3-layer kernels have
+  // none to spare): it is kept in LDS (yS[0], otherwise unused in these modes) and P3 reads it back at the top of every step
+  if (GR && tid == 0) yS[0] = nrow0;        // (ordered by the barriers below)
   float* encS = lds;
   float* encAS = lds + cres * H;
   float* ebS = lds + 2 * cres * H;               // [chunk] enc.ba, computed once
@@ -471,13 +481,17 @@ __device__ __forceinline__ void decoder_persist_fwd_body(const PDecArgs& a) {
   const float* gEnc = a.enc + ((long)att_b * T + t0) * H;       // this slice in global memory (rows >= nres are read from here every step)
   const float* gEncA = a.encA + ((long)att_b * T + t0) * H;
   if (has_att) {
-    const int n4 = nres * H / 4;
+    const int n4 = nres0 * H / 4;
     for (int i = tid; i < n4; i += 256) {
       reinterpret_cast<float4*>(encS)[i] = reinterpret_cast<const float4*>(gEnc)[i];
       reinterpret_cast<float4*>(encAS)[i] = reinterpret_cast<const float4*>(gEncA)[i];
     }
+    if constexpr (GR) {
+      if (nrow0 == 0)        // an empty slice: the scans read LDS row 0 with weight 0, so it holds zeros (the partial is then exact zeros)
+        for (int i = tid; i < H; i += 256) encS[i] = encAS[i] = 0.f;
+    }
     __syncthreads();
-    for (int t = tid; t < nrow; t += 256) {       // eb[t] = enc[t,:] . ba  (score = encA.h + eb)
+    for (int t = tid; t < nrow0; t += 256) {      // eb[t] = enc[t,:] . ba  (score = encA.h + eb)
       float d = 0.f;
       for (int k = 0; k < H; ++k) d += gEnc[(long)t * H + k] * a.ba[k];
       ebS[t] = d;
@@ -824,6 +838,8 @@ __device__ __forceinline__ void decoder_persist_fwd_body(const PDecArgs& a) {
     if (has_att) {
       const int b = att_b, bt = b / 16;
       TICK(15)
+      const int nrow = GR ? __builtin_amdgcn_readfirstlane(*(volatile int*)yS) : nrow0;     // (GR: in front of the poll, which hides the read)
+      const int nres = GR ? min(nrow, cres) : nres0;
       const int c4 = (a.chunk + 3) & ~3;
       float* hS = scr;                 // [H]
       float* scS = scr + H;            // [c4] raw scores (tail padded with -inf)
@@ -867,7 +883,8 @@ __device__ __forceinline__ void decoder_persist_fwd_body(const PDecArgs& a) {
         {
           // pass 1: 16 lanes per row; group g owns rows g and g + 16; lane l covers floats 4l + 64c of the row
           const int grp = tid >> 4, l16 = tid & 15;
-          const int ta = min(grp, nres - 1), tb2 = min(grp + 16, nres - 1);
+          const int rlast = GR ? max(nres, 1) - 1 : nres - 1;     // (GR: row 0, which holds zeros, of an empty slice)
+          const int ta = min(grp, rlast), tb2 = min(grp + 16, rlast);
           const float* e1 = encAS + ta * HH + 4 * l16;
           const float* e2 = encAS + tb2 * HH + 4 * l16;
           float4 hv[NC], x1[NC], x2[NC];
@@ -946,7 +963,7 @@ __device__ __forceinline__ void decoder_persist_fwd_body(const PDecArgs& a) {
 #pragma unroll
           for (int i = 0; i < RPT; ++i) {
             const int t = rh + RH * i;
-            const int tc = min(t, nres - 1);
+            const int tc = min(t, GR ? max(nres, 1) - 1 : nres - 1);
             ev[i] = *reinterpret_cast<const float4*>(encS + tc * HH + 4 * cq);
             pv[i] = t < nres ? pS_[t] : 0.f;
           }
@@ -1183,7 +1200,14 @@ __device__ __forceinline__ void decoder_persist_fwd_body(const PDecArgs& a) {
       const float v = reduce16(acc, red);
       const int row = m0 + (tid >> 4), n = n0 + (tid & 15);
       const bool ok = row < B && n < V;
-      const float x = ok ? v + a.bo[n] : -INFINITY;
+      float x = -INFINITY;
+      if constexpr (GR) {      // (the bias address formed here: hoisted out of the step loop it is a 64-bit register pair per tile, and spills)
+        int nn = n;
+        asm volatile("" : "+v"(nn));
+        if (ok) x = v + *ua(a.bo, (unsigned)nn);
+      } else {
+        x = ok ? v + a.bo[n] : -INFINITY;
+      }
       if (!GR) {       // (GR: P6 needs the tile's maximum and its index only)
         if (ok) *ua(a.LOGITS + (long)s * B * a.Vp, (unsigned)(row * a.Vp + n)) = x;
         else if (row < B && n < a.Vp) *ua(a.LOGITS + (long)s * B * a.Vp, (unsigned)(row * a.Vp + n)) = 0.f;
@@ -1314,12 +1338,14 @@ __global__ __launch_bounds__(256, 1) void decoder_persist_forced(PDecArgs a) {
 }
 
 // alpha[r][t] = exp(score[r][t] - M[r]) / L[r], r = (step, row), t < T: the raw scores of the forced loop (rows of Tp floats) into the
-// caller's dense (S, B, T) buffer
+// caller's dense (S, B, T) buffer.  With lengths (row_len[b], b = r % B, or null) the loop stored scores for t < row_len[b] only: alpha is
+// an exact 0 from there on
 __global__ __launch_bounds__(256) void k_alpha_normalise(const float* __restrict__ raw, const float* __restrict__ ml, float* __restrict__ alpha,
-                                                         int T, int Tp) {
+                                                         const int32_t* __restrict__ row_len, int B, int T, int Tp) {
   const long r = blockIdx.x;
   const float M = ml[2 * r], inv = ml[2 * r + 1];
-  for (int t = threadIdx.x; t < T; t += 256) alpha[r * T + t] = expf(raw[r * Tp + t] - M) * inv;
+  const int n = row_len ? min(T, row_len[r % B]) : T;
+  for (int t = threadIdx.x; t < T; t += 256) alpha[r * T + t] = t < n ? expf(raw[r * Tp + t] - M) * inv : 0.f;
 }
 
 // =====================================================================================================================
@@ -2316,7 +2342,7 @@ struct GreedyScoredIO {
 // sc: null for the unscored kernel
 static int greedy_launch(const astk_decoder_desc* d, const astk_decoder_params* prm, const float* enc, const float* c0, const float* h0, int go,
                          int eos, int stop_limit, const GreedyScoredIO* sc, int32_t* tokens, int32_t* n_steps, float* status_dst, void* ws,
-                         size_t ws_bytes, hipStream_t s) {
+                         size_t ws_bytes, const int32_t* row_len, hipStream_t s) {
   ASTK_CHECK_DESC(d, astk_decoder_desc);
   ASTK_CHECK(d->V > 1 && go >= 0 && go < d->V && eos >= 0 && eos < d->V, "greedy_decode: go %d / eos %d outside [0, V = %d)", go, eos, d->V);
   ASTK_CHECK(stop_limit >= 1 && stop_limit <= ASTK_GREEDY_MAX_STEPS, "greedy_decode: stop_limit %d outside [1, %d]", stop_limit, ASTK_GREEDY_MAX_STEPS);
@@ -2336,6 +2362,7 @@ static int greedy_launch(const astk_decoder_desc* d, const astk_decoder_params* 
   a.PRED = tokens;
   a.go = go; a.eos = eos;
   a.n_steps_out = n_steps; a.status_dst = status_dst;
+  a.row_len = row_len;
   if (sc) {
     a.LSE = sc->logp; a.LOSSROWS = sc->nll; a.ytgt = sc->y; a.L = sc->y ? sc->ldy : 1; a.cw = sc->class_weight;
     a.row_keys = sc->row_keys; a.inv_temp = sc->inv_temp;
@@ -2344,15 +2371,17 @@ static int greedy_launch(const astk_decoder_desc* d, const astk_decoder_params* 
 }
 
 int greedy_decode_launch(const astk_decoder_desc* d, const astk_decoder_params* prm, const float* enc, const float* c0, const float* h0, int go,
-                         int eos, int stop_limit, int32_t* tokens, int32_t* n_steps, float* status_dst, void* ws, size_t ws_bytes, hipStream_t s) {
-  return greedy_launch(d, prm, enc, c0, h0, go, eos, stop_limit, nullptr, tokens, n_steps, status_dst, ws, ws_bytes, s);
+                         int eos, int stop_limit, int32_t* tokens, int32_t* n_steps, float* status_dst, void* ws, size_t ws_bytes,
+                         const int32_t* row_len, hipStream_t s) {
+  return greedy_launch(d, prm, enc, c0, h0, go, eos, stop_limit, nullptr, tokens, n_steps, status_dst, ws, ws_bytes, row_len, s);
 }
 
 int greedy_decode_scored_launch(const astk_decoder_desc* d, const astk_decoder_params* prm, const float* enc, const float* c0, const float* h0,
                                 int go, int eos, int stop_limit, const int32_t* y, int ldy, const float* class_weight, int32_t* tokens,
-                                float* logp, float* nll, int32_t* n_steps, float* status_dst, void* ws, size_t ws_bytes, hipStream_t s) {
+                                float* logp, float* nll, int32_t* n_steps, float* status_dst, void* ws, size_t ws_bytes,
+                                const int32_t* row_len, hipStream_t s) {
   const GreedyScoredIO sc{y, ldy, class_weight, logp, nll, nullptr, 1.f};
-  return greedy_launch(d, prm, enc, c0, h0, go, eos, stop_limit, &sc, tokens, n_steps, status_dst, ws, ws_bytes, s);
+  return greedy_launch(d, prm, enc, c0, h0, go, eos, stop_limit, &sc, tokens, n_steps, status_dst, ws, ws_bytes, row_len, s);
 }
 
 // ---------------------------------------------------------------------------------------------------- sampled decoding
@@ -2362,12 +2391,12 @@ size_t sample_workspace_bytes(const astk_decoder_desc* d, int stop_limit) { retu
 
 int sample_decode_launch(const astk_decoder_desc* d, const astk_decoder_params* prm, const float* enc, const float* c0, const float* h0, int go,
                          int eos, int stop_limit, const uint64_t* row_keys, float inv_temp, int32_t* tokens, float* logp, int32_t* n_steps,
-                         float* status_dst, void* ws, size_t ws_bytes, hipStream_t s) {
+                         float* status_dst, void* ws, size_t ws_bytes, const int32_t* row_len, hipStream_t s) {
   ASTK_CHECK(row_keys, "sample_decode: null pointer (row_keys)");
   ASTK_CHECK(logp, "sample_decode: null pointer (logp)");
   ASTK_CHECK(inv_temp > 0.f && inv_temp <= 3.402823466e38f, "sample_decode: inv_temp %g is not a finite number above 0", (double)inv_temp);
   const GreedyScoredIO sc{nullptr, 0, nullptr, logp, nullptr, row_keys, inv_temp};
-  return greedy_launch(d, prm, enc, c0, h0, go, eos, stop_limit, &sc, tokens, n_steps, status_dst, ws, ws_bytes, s);
+  return greedy_launch(d, prm, enc, c0, h0, go, eos, stop_limit, &sc, tokens, n_steps, status_dst, ws, ws_bytes, row_len, s);
 }
 
 int gumbel_rows_launch(const uint64_t* row_keys, int B, int step, int V, float* out, hipStream_t s) {
@@ -2407,7 +2436,7 @@ size_t forced_workspace_bytes(const astk_decoder_desc* d, int n_steps, int with_
 
 int forced_score_launch(const astk_decoder_desc* d, const astk_decoder_params* prm, const float* enc, const float* c0, const float* h0,
                         const int32_t* y, int ldy, float* logp, float* logp_max, int32_t* pred, float* alpha, float* status_dst, void* ws,
-                        size_t ws_bytes, hipStream_t s) {
+                        size_t ws_bytes, const int32_t* row_len, hipStream_t s) {
   ASTK_CHECK_DESC(d, astk_decoder_desc);
   ASTK_CHECK(ldy >= 2 && ldy - 1 <= ASTK_GREEDY_MAX_STEPS, "forced_score: ldy %d outside [2, %d]", ldy, ASTK_GREEDY_MAX_STEPS + 1);
   const int S = ldy - 1;
@@ -2421,9 +2450,10 @@ int forced_score_launch(const astk_decoder_desc* d, const astk_decoder_params* p
   a.y = y; a.ytgt = y;                  // (a.L = S + 1 = ldy)
   a.LSE = logp; a.LOSSROWS = logp_max; a.PRED = pred; a.ALPHA = f.RAW; a.ML = f.ML;
   a.status_dst = status_dst;            // (of the control lines only the exit count, line 2, is used: the stop word is never read)
+  a.row_len = row_len;
   ASTK_TRY(inference_run(PDEC_FORCED, d, prm, enc, h0, a, f.g, s));
   if (alpha) {
-    hipLaunchKernelGGL(k_alpha_normalise, dim3(a.S * a.B), dim3(256), 0, s, f.RAW, f.ML, alpha, a.T, a.Tp);
+    hipLaunchKernelGGL(k_alpha_normalise, dim3(a.S * a.B), dim3(256), 0, s, f.RAW, f.ML, alpha, row_len, a.B, a.T, a.Tp);
     ASTK_LAUNCH_CHECK();
   }
   return 0;

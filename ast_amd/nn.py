@@ -73,11 +73,8 @@ def decode_beam_batch(model, Xs, stop_limit, N, K):
     GO, EOS = SYMBOLS.GO_ID, SYMBOLS.EOS_ID
     with using_config("train", False):
         # ---- every utterance encoded at its own length (no length masks in the encoder, quirk Q2), copied out of the pooled buffers
-        encs, seeds = [], []
-        for X in Xs:
-            model.encode(X)
-            encs.append(model.enc_states[0].clone())
-            seeds.append(model.get_encoder_states())
+        seeds = []
+        encs, _, _ = model._encode_alone(Xs, seeds)
         if stop_limit <= 0:
             return [[_init_hyp_from(model, s)] for s in seeds]
         U, nl, H, A, V = len(Xs), len(model.rnn_dec), model.H, model.A, model.V
@@ -164,8 +161,8 @@ def decode_beam_batch(model, Xs, stop_limit, N, K):
 
 def score_hypotheses(model, X, hyps, return_alpha=False):
     """Forced scores of several token lists for ONE utterance: X (1, T, D) is repeated over the rows and the lists `hyps` (each
-    [GO, t1, .., tn], as beam search returns them) are PAD-padded to one length -- the encoding decode_beam saw, since batches carry no
-    length masks.  Returns (scores, r): scores[i] = the float64 sum of log p(t_k | t_<k) over hypothesis i's own n steps (a PAD id
+    [GO, t1, .., tn], as beam search returns them) are PAD-padded to one length -- the encoding decode_beam saw (score_hypotheses_packed
+    scores several utterances per call).  Returns (scores, r): scores[i] = the float64 sum of log p(t_k | t_<k) over hypothesis i's own n steps (a PAD id
     inside a hypothesis counts like any other token, the padding behind it does not), r = the ForcedScore of the padded batch."""
     import numpy as np
     X = model._as_input(X)
@@ -185,9 +182,105 @@ def cut_at_eos(tokens, end_token=SYMBOLS.EOS_ID):
     return toks[:toks.index(end_token) + 1] if end_token in toks else toks
 
 
+# ---- rows of several utterances in one call (SpeechEncoderDecoder.encode_rows, rows=): every row attends over its own utterance's length
+def plan_row_packs(counts, max_utts=None, max_rows=32):
+    """Packs the rows of consecutive utterances into calls: counts[u] = the rows utterance u needs; returns a list of calls, each a
+    list of (u, lo, hi) -- rows lo..hi-1 of utterance u -- in order, with at most max_rows rows and at most max_utts utterances per
+    call.  An utterance that fits a call is never split: it opens a new call when the current one has no room for all of it.  One with
+    more than max_rows rows opens a call of its own and is split across calls, max_rows at a time; the remainder shares its call with
+    the utterances behind it.  Utterances without rows appear in no call.  Host only."""
+    max_rows = int(max_rows)
+    max_utts = max_rows if max_utts is None else int(max_utts)
+    if max_rows < 1 or max_utts < 1:
+        raise ValueError(f"plan_row_packs: max_rows = {max_rows} and max_utts = {max_utts} must be at least 1")
+    calls, cur, used = [], [], 0
+    for u, n in enumerate(int(c) for c in counts):
+        if n < 0:
+            raise ValueError(f"plan_row_packs: utterance {u} has {n} rows")
+        lo = 0
+        while lo < n:
+            if cur and (len(cur) == max_utts or used == max_rows or (lo == 0 and n > max_rows - used)):
+                calls.append(cur)
+                cur, used = [], 0
+            take = min(n - lo, max_rows - used)
+            cur.append((u, lo, lo + take))
+            used += take
+            lo += take
+    if cur:
+        calls.append(cur)
+    return calls
+
+
+def _pack_rows(model, Xs, call):
+    """The RowBatch of one planned call (each of its utterances encoded once) and rows_of, the call's piece index of every row."""
+    rows_of = [k for k, (_, lo, hi) in enumerate(call) for _ in range(hi - lo)]
+    return model.encode_rows([Xs[u] for u, _, _ in call], rows_of), rows_of
+
+
+def score_hypotheses_packed(model, Xs, hyps_lists, return_alpha=False, max_utts=None):
+    """score_hypotheses for many utterances, their hypotheses packed into calls of up to 32 rows (plan_row_packs; at most max_utts
+    utterances per call): Xs a list of (1, T_u, D) inputs, hyps_lists[u] the token lists of utterance u.  Returns one (scores, r) per
+    utterance as score_hypotheses returns them -- r the ForcedScore of the utterance's own PAD-padded batch, its alpha (n, L_u - 1,
+    T''_u) -- and ([], None) for an utterance without hypotheses."""
+    import numpy as np
+    from .seq2seq import ForcedScore
+    ys = []
+    for hyps in hyps_lists:
+        y = np.zeros((len(hyps), max([2] + [len(h) for h in hyps])), dtype=np.int32)
+        for i, h in enumerate(hyps):
+            y[i, :len(h)] = h
+        ys.append(y)
+    parts = [[] for _ in Xs]
+    for call in plan_row_packs([len(h) for h in hyps_lists], max_utts):
+        rows, _ = _pack_rows(model, Xs, call)
+        L = max(ys[u].shape[1] for u, _, _ in call)
+        y = np.zeros((rows.B, L), dtype=np.int32)
+        at = 0
+        for u, lo, hi in call:
+            y[at:at + hi - lo, :ys[u].shape[1]] = ys[u][lo:hi]
+            at += hi - lo
+        r = model.score(None, y, return_alpha=return_alpha, rows=rows)
+        at = 0
+        for u, lo, hi in call:
+            S, T2 = ys[u].shape[1] - 1, int(rows.lens[at])
+            cut = lambda a: a[at:at + hi - lo, :S]
+            parts[u].append((cut(r.logp), cut(r.logp_max), cut(r.pred), cut(r.alpha)[:, :, :T2] if return_alpha else None))
+            at += hi - lo
+    out = []
+    for u, hyps in enumerate(hyps_lists):
+        if not hyps:
+            out.append(([], None))
+            continue
+        cat = lambda k: np.concatenate([p[k] for p in parts[u]], axis=0)
+        r = ForcedScore(cat(0), cat(1), cat(2), (ys[u][:, 1:] != 0).astype(np.float32), cat(3) if return_alpha else None)
+        out.append(([float(r.logp[i, :len(h) - 1].astype(np.float64).sum()) for i, h in enumerate(hyps)], r))
+    return out
+
+
+def sample_hypotheses_packed(model, Xs, n, stop_limit, seed, temperature=1.0, first_streams=None, max_utts=None):
+    """sample_hypotheses for many utterances, their n rows each packed into calls of up to 32 rows (plan_row_packs; at most max_utts
+    utterances per call).  Utterance k draws from the streams first_streams[k] .. first_streams[k] + n - 1 of `seed` (default k * n:
+    the numbering of NN.sample_set), so packing does not change which samples an utterance gets.  Returns one list per utterance as
+    sample_hypotheses returns it."""
+    n = int(n)
+    first_streams = [k * n for k in range(len(Xs))] if first_streams is None else [int(v) for v in first_streams]
+    if len(first_streams) != len(Xs):
+        raise ValueError(f"sample_hypotheses_packed: first_streams must name {len(Xs)} utterances, got {len(first_streams)}")
+    out = [[] for _ in Xs]
+    for call in plan_row_packs([n] * len(Xs), max_utts):
+        rows, _ = _pack_rows(model, Xs, call)
+        streams = [first_streams[u] + i for u, lo, hi in call for i in range(lo, hi)]
+        r = model.sample(None, SYMBOLS.GO_ID, SYMBOLS.EOS_ID, stop_limit, seed, streams=streams, temperature=temperature, rows=rows)
+        at = 0
+        for u, lo, hi in call:
+            out[u].extend({"hyp": [SYMBOLS.GO_ID] + cut_at_eos(r.tokens[i]), "score": float(r.score[i])} for i in range(at, at + hi - lo))
+            at += hi - lo
+    return out
+
+
 def sample_hypotheses(model, X, n, stop_limit, seed, temperature=1.0, first_stream=0):
     """n samples of ONE utterance X (1, T, D), drawn by SpeechEncoderDecoder.sample from the streams first_stream .. first_stream + n - 1
-    of `seed`: X is repeated over the rows (the encoding decode_beam sees, as in score_hypotheses), at most 32 rows -- the device
+    of `seed`: X is repeated over the rows (the encoding decode_beam sees; sample_hypotheses_packed packs several utterances), at most 32 rows -- the device
     loop's batch -- per call.  Returns a list in stream order of {"hyp": [GO, t1, .., tk], "score": float}, each cut behind its first
     EOS and keeping it, like decode_beam's entries; score = the log-probability of t1..tk under the sampled distribution.  A stream's
     sample does not depend on n or on its row, so a list can be extended later from first_stream = n."""
@@ -415,13 +508,29 @@ class NN:
             losses.append(r.loss / L)
         return preds, (sum(losses) / len(losses) if losses else 0.0), scores
 
-    def sample_set(self, set_key, n, seed, temperature=1.0):
+    def sample_set(self, set_key, n, seed, temperature=1.0, utts_per_call=1):
         """n samples of every utterance of a set (sample_hypotheses; utterance k of the set, in the loader's order, draws from the
         streams k * n .. k * n + n - 1 of `seed`): returns {utt: [(hyp, score, [])]}, the n-best format of beam.py's pickle without
-        attention histories."""
+        attention histories.  utts_per_call = U > 1 packs the rows of up to U utterances into one call (sample_hypotheses_packed):
+        the same streams, so the same samples."""
         out = {}
         stop_limit = self.cfg.train["data"]["max_pred"]
         with tqdm(total=self.data_loader.n_utts[set_key], ncols=80, disable=adist.rank() != 0) as pbar:
+            if utts_per_call > 1:
+                group, k0 = [], 0
+                for utt in itertools.chain(self.data_loader.get_batch(1, set_key, train=False, labels=False), [None]):
+                    if utt is not None:
+                        group.append(utt)
+                    if group and (utt is None or len(group) == utts_per_call):
+                        with using_config("train", False):
+                            lists = sample_hypotheses_packed(self.model, [g["X"] for g in group], n, stop_limit, seed, temperature,
+                                                             first_streams=[(k0 + i) * n for i in range(len(group))], max_utts=utts_per_call)
+                        for g, hyps in zip(group, lists):
+                            out[g["utts"][0]] = [(h["hyp"], h["score"], []) for h in hyps]
+                        pbar.update(len(group))
+                        k0 += len(group)
+                        group = []
+                return out
             for k, utt in enumerate(self.data_loader.get_batch(1, set_key, train=False, labels=False)):
                 with using_config("train", False):
                     hyps = sample_hypotheses(self.model, utt["X"], n, stop_limit, seed, temperature, first_stream=k * n)

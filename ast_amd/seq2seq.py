@@ -287,6 +287,57 @@ def checked_targets(y, V):
     return y.astype(np.int32, copy=False)
 
 
+ROWS_MAX = 32       # the device loop's batch (include/astk.h: B <= 32)
+
+
+def checked_row_lens(lens, B, T):
+    """lens as a (B,) int32 host array; ValueError for another count, a non-integer dtype or a length outside 1..T."""
+    if isinstance(lens, torch.Tensor):
+        lens = lens.detach().cpu().numpy()
+    lens = np.asarray(lens)
+    if lens.ndim != 1 or lens.shape[0] != int(B):
+        raise ValueError(f"RowBatch: lens must name B = {int(B)} rows, got shape {tuple(lens.shape)}")
+    if not np.issubdtype(lens.dtype, np.integer):
+        raise ValueError(f"RowBatch: lens must hold integers, got {lens.dtype}")
+    if int(lens.min()) < 1 or int(lens.max()) > int(T):
+        raise ValueError(f"RowBatch: lengths must lie in 1..T''max = {int(T)}, got [{int(lens.min())}, {int(lens.max())}]")
+    return np.ascontiguousarray(lens.astype(np.int32))
+
+
+class RowBatch:
+    """Rows of DIFFERENT utterances for the decode entry points (`rows=` of predict / predict_scored / sample / score): `enc`
+    (B, T''max, H) the rows' encoder memories, each padded behind its own length, `lens` (B,) int32 on the host, 1 <= lens[b] <= T''max,
+    and the decoder states `c0` / `h0` (n_layers, B, H).  Row b attends over enc[b, :lens[b]] only and decodes as it would alone (what
+    lies behind a row's length is never read into a result).  SpeechEncoderDecoder.encode_rows builds one from utterances; built from
+    tensors directly it takes any lengths.  At most 32 rows: the device loop's batch."""
+
+    def __init__(self, enc, lens, c0, h0):
+        enc, c0, h0 = (torch.as_tensor(t) for t in (enc, c0, h0))
+        if enc.dim() != 3 or enc.shape[0] < 1 or enc.shape[1] < 1:
+            raise ValueError(f"RowBatch: enc must be (B >= 1, T''max >= 1, H), got {tuple(enc.shape)}")
+        B, T, H = (int(v) for v in enc.shape)
+        if B > ROWS_MAX:
+            raise ValueError(f"RowBatch: at most {ROWS_MAX} rows, got {B}")
+        for name, t in (("c0", c0), ("h0", h0)):
+            if t.dim() != 3 or int(t.shape[1]) != B or int(t.shape[2]) != H or t.shape != c0.shape:
+                raise ValueError(f"RowBatch: {name} must be (n_layers, B = {B}, H = {H}), got {tuple(t.shape)}")
+        self.lens = checked_row_lens(lens, B, T)
+        self.enc, self.c0, self.h0 = enc, c0, h0
+
+    @property
+    def B(self):
+        return int(self.enc.shape[0])
+
+    @property
+    def T(self):
+        return int(self.enc.shape[1])
+
+    def row(self, b):
+        """Row b alone, its memory cut at its length."""
+        n = int(self.lens[b])
+        return RowBatch(self.enc[b:b + 1, :n], [n], self.c0[:, b:b + 1], self.h0[:, b:b + 1])
+
+
 class _Ready:
     def __init__(self, value):
         self.value = value
@@ -350,6 +401,7 @@ class SpeechEncoderDecoder:
         self.loss = 0
         self._cur = None
         self._dec_c = self._dec_h = None
+        self._rows_alone = False        # inside the per-step path of a RowBatch: its rows decode one by one, off the device loop
         self.grad_buckets = None        # ast_amd.dist.GradBuckets under data parallelism: ranges are all-reduced as they become final
         self.stat_exchange = None       # ast_amd.dist.StatExchange: BatchNorm statistics over the global batch (train mode only)
         # Work BESIDE the latency-bound encoder recurrences (round 6): an ORDINARY second stream carries (i) the decoder's parameter
@@ -566,22 +618,8 @@ class SpeechEncoderDecoder:
                 lp[k].Wu, lp[k].b, lp[k].Wl = a.p(n + "/upward/W"), a.p(n + "/upward/b"), a.p(n + "/lateral/W")
                 lg[k].dWu, lg[k].db, lg[k].dWl = a.g(n + "/upward/W"), a.g(n + "/upward/b"), a.g(n + "/lateral/W")
         nld = len(self.rnn_dec)
-        dd = DecoderDesc(B, max(L, 2), T2, H, self.E, self.A, self.V, nld, self.n_attn, 0 if self.feed_attn else 1, 1 if self.rnn_ln else 0)
-        dp, dg = DecoderParams(), DecoderGrads()
-        dp.embed, dg.d_embed = a.p("embed_dec/W"), a.g("embed_dec/W")
-        for l, n in enumerate(self.rnn_dec):
-            dp.lstm[l].Wu, dp.lstm[l].b, dp.lstm[l].Wl = a.p(n + "/upward/W"), a.p(n + "/upward/b"), a.p(n + "/lateral/W")
-            dg.lstm[l].dWu, dg.lstm[l].db, dg.lstm[l].dWl = a.g(n + "/upward/W"), a.g(n + "/upward/b"), a.g(n + "/lateral/W")
-            if self.rnn_ln:
-                dp.ln_gamma[l], dp.ln_beta[l] = a.p(n + "_ln/gamma"), a.p(n + "_ln/beta")
-                dg.d_ln_gamma[l], dg.d_ln_beta[l] = a.g(n + "_ln/gamma"), a.g(n + "_ln/beta")
-        for k in range(1, self.n_attn):
-            dp.Wa_x[k - 1], dp.ba_x[k - 1] = a.p(f"attn_Wa{k}/W"), a.p(f"attn_Wa{k}/b")
-            dg.dWa_x[k - 1], dg.dba_x[k - 1] = a.g(f"attn_Wa{k}/W"), a.g(f"attn_Wa{k}/b")
-        dp.Wa, dp.ba, dp.Wc, dp.bc = a.p("attn_Wa/W"), a.p("attn_Wa/b"), a.p("context/W"), a.p("context/b")
-        dp.Wo, dp.bo, dp.class_weight = a.p("out/W"), a.p("out/b"), self.mask_pad_id.data_ptr()
-        dg.dWa, dg.dba, dg.dWc, dg.dbc = a.g("attn_Wa/W"), a.g("attn_Wa/b"), a.g("context/W"), a.g("context/b")
-        dg.dWo, dg.dbo = a.g("out/W"), a.g("out/b")
+        dd = self._decoder_desc(B, max(L, 2), T2)
+        dp, dg = self._decoder_tables()
         S = max(L, 2) - 1
         f32 = dict(dtype=torch.float32, device=dev)
         # pooled first (growing a pool clears the shape cache), then the per-batch-size state, then the views of this shape
@@ -608,6 +646,30 @@ class SpeechEncoderDecoder:
         assert st["ws_cnn"] and st["ws_lstm"] and st["ws_dec"], lib.astk_last_error().decode()
         self._shape_cache[key] = st
         return st
+
+    def _decoder_desc(self, B, L, T2):
+        return DecoderDesc(B, L, T2, self.H, self.E, self.A, self.V, len(self.rnn_dec), self.n_attn, 0 if self.feed_attn else 1,
+                           1 if self.rnn_ln else 0)
+
+    def _decoder_tables(self):
+        """The decoder's parameter and gradient tables (pointers into the arena)."""
+        a = self.arena
+        dp, dg = DecoderParams(), DecoderGrads()
+        dp.embed, dg.d_embed = a.p("embed_dec/W"), a.g("embed_dec/W")
+        for l, n in enumerate(self.rnn_dec):
+            dp.lstm[l].Wu, dp.lstm[l].b, dp.lstm[l].Wl = a.p(n + "/upward/W"), a.p(n + "/upward/b"), a.p(n + "/lateral/W")
+            dg.lstm[l].dWu, dg.lstm[l].db, dg.lstm[l].dWl = a.g(n + "/upward/W"), a.g(n + "/upward/b"), a.g(n + "/lateral/W")
+            if self.rnn_ln:
+                dp.ln_gamma[l], dp.ln_beta[l] = a.p(n + "_ln/gamma"), a.p(n + "_ln/beta")
+                dg.d_ln_gamma[l], dg.d_ln_beta[l] = a.g(n + "_ln/gamma"), a.g(n + "_ln/beta")
+        for k in range(1, self.n_attn):
+            dp.Wa_x[k - 1], dp.ba_x[k - 1] = a.p(f"attn_Wa{k}/W"), a.p(f"attn_Wa{k}/b")
+            dg.dWa_x[k - 1], dg.dba_x[k - 1] = a.g(f"attn_Wa{k}/W"), a.g(f"attn_Wa{k}/b")
+        dp.Wa, dp.ba, dp.Wc, dp.bc = a.p("attn_Wa/W"), a.p("attn_Wa/b"), a.p("context/W"), a.p("context/b")
+        dp.Wo, dp.bo, dp.class_weight = a.p("out/W"), a.p("out/b"), self.mask_pad_id.data_ptr()
+        dg.dWa, dg.dba, dg.dWc, dg.dbc = a.g("attn_Wa/W"), a.g("attn_Wa/b"), a.g("context/W"), a.g("context/b")
+        dg.dWo, dg.dbo = a.g("out/W"), a.g("out/b")
+        return dp, dg
 
     def _rng(self, n):
         off = self._rng_offset
@@ -979,18 +1041,83 @@ class SpeechEncoderDecoder:
                                           self._stream()))
         return logits, ht, alpha.unsqueeze(2)
 
-    def predict(self, X, start_token, end_token, stop_limit):
-        return self.predict_async(X, start_token, end_token, stop_limit).result()
+    def predict(self, X, start_token, end_token, stop_limit, rows=None):
+        return self.predict_async(X, start_token, end_token, stop_limit, rows=rows).result()
 
     # What the decode entry points share.  _begin_decode: the eval-mode encoding and decoder state of a batch.  _device_decode: a mode's
     # one persistent launch with its one-copy read-back, or None for shapes the library does not run on the device loop (it reports a
     # workspace of 0).  _device_or_steps: that handle, or else the mode's per-step loop, finished on return.
-    def _begin_decode(self, X):
+    def _begin_decode(self, X, rows=None):
+        if rows is not None:
+            if X is not None:
+                raise ValueError("decode: give X or rows=, not both")
+            return self._adopt_rows(rows)
+        if X is None:
+            raise ValueError("decode: give X or rows=")
         X = self._as_input(X)
         self._cur = None
         self.encode(X)
         self.init_decoder_state()
         return self._cur["B"]
+
+    def _adopt_rows(self, rows):
+        """A RowBatch in place of an encoded batch: a decoder state of its own (B rows, T = T''max, the lengths uploaded), which the
+        decode entry points read exactly as they read the state _begin_decode leaves."""
+        lib = self._require_gpu()
+        if not isinstance(rows, RowBatch):
+            raise ValueError(f"decode: rows must be a RowBatch, got {type(rows).__name__}")
+        if self.arena is None:
+            raise ValueError("decode: the model has no parameters yet (materialize it, or encode a batch, first)")
+        nl = len(self.rnn_dec)
+        if int(rows.enc.shape[2]) != self.H or int(rows.c0.shape[0]) != nl:
+            raise ValueError(f"decode: rows hold H = {int(rows.enc.shape[2])} and {int(rows.c0.shape[0])} decoder layers, "
+                             f"the model H = {self.H} and {nl}")
+        B, T2 = rows.B, rows.T
+        f32 = dict(device=self.device, dtype=torch.float32)
+        dd = self._decoder_desc(B, 2, T2)
+        dd.precision, dd.gemm_operands = _lib.PREC_BY_NAME[self.gemm_precision], _lib.OPERANDS_BY_NAME[self.gemm_operands]
+        dd.deterministic = 1 if self.deterministic else 0
+        dp, _ = self._decoder_tables()
+        enc = rows.enc.to(**f32).contiguous()
+        self._cur = dict(B=B, T2=T2, dd=dd, dp=dp, enc_states=enc, rows=rows, ws_dec=int(lib.astk_decoder_workspace_bytes(C.byref(dd))),
+                         row_len=torch.from_numpy(rows.lens).to(self.device))
+        self.enc_states = enc
+        self._dec_c, self._dec_h = rows.c0.to(**f32).contiguous().clone(), rows.h0.to(**f32).contiguous().clone()
+        return B
+
+    def encode_rows(self, Xs, rows_of=None):
+        """A RowBatch of utterances: every X of the list Xs ((1, T_u, D) or (T_u, D)) is encoded ALONE, at batch 1 in eval mode -- the
+        encoder has no length masks, so this is the only encoding that does not depend on the batch around it, and the one beam
+        search sees -- and seeds its rows' decoder state as init_decoder_state does.  rows_of[b] = the utterance of row b (default: one
+        row per utterance, in order); at most 32 rows."""
+        rows_of = list(range(len(Xs))) if rows_of is None else [int(u) for u in rows_of]
+        if not rows_of or len(rows_of) > ROWS_MAX:
+            raise ValueError(f"encode_rows: 1..{ROWS_MAX} rows, got {len(rows_of)}")
+        if min(rows_of) < 0 or max(rows_of) >= len(Xs):
+            raise ValueError(f"encode_rows: rows_of names utterances outside 0..{len(Xs) - 1}")
+        encs, c0s, h0s = self._encode_alone(Xs)
+        lens = [int(e.shape[0]) for e in encs]
+        f32 = dict(device=self.device, dtype=torch.float32)
+        enc = torch.zeros(len(rows_of), max(lens[u] for u in rows_of), self.H, **f32)
+        for b, u in enumerate(rows_of):
+            enc[b, :lens[u]] = encs[u]
+        return RowBatch(enc, [lens[u] for u in rows_of], torch.stack([c0s[u] for u in rows_of], 1), torch.stack([h0s[u] for u in rows_of], 1))
+
+    def _encode_alone(self, Xs, seeds=None):
+        """Every utterance of Xs encoded at its own length, copied out of the pooled buffers: its states (T''_u, H) and the decoder
+        state (n_layers, H) of init_decoder_state, c and h.  seeds (a list): also collects get_encoder_states() of every utterance."""
+        encs, c0s, h0s = [], [], []
+        with using_config("train", False):
+            for X in Xs:
+                X = self._as_input(X)
+                self.encode(X[None] if X.dim() == 2 else X)
+                self.init_decoder_state()
+                encs.append(self.enc_states[0].clone())
+                c0s.append(self._dec_c[:, 0].clone())
+                h0s.append(self._dec_h[:, 0].clone())
+                if seeds is not None:
+                    seeds.append(self.get_encoder_states())
+        return encs, c0s, h0s
 
     def _readback(self, key, slot, n, dtype):
         """n words of the pooled device buffer of (key, slot) and of its pinned twin; both only ever grow."""
@@ -1004,14 +1131,18 @@ class SpeechEncoderDecoder:
         forced alpha) that come back in one non-blocking copy each, followed by an event.  args(p, alpha) = the mode's own arguments
         between the decoder state and the workspace: p(k) is the address of byte k of the words, alpha the float buffer's or None.
         `pending`: the status word's index, `where`, parse and keep of the _Pending handle returned."""
-        if nbytes == 0:
+        if nbytes == 0 or self._rows_alone:
             return None
         ws = self._workspace("decode", nbytes)
         out, host = self._readback(key, slot, n, torch.int32)
         alpha, host_alpha = self._readback(key + "_alpha", slot, n_alpha, torch.float32) if n_alpha else (None, None)
         st, base = self._cur, out.data_ptr()
+        lens = st.get("row_len")              # a RowBatch: the mode's _rows entry point, the lengths behind the stream
+        if lens is not None:
+            call, pending["keep"] = getattr(_lib.load(), call.__name__ + "_rows"), (pending.get("keep"), lens, st["enc_states"])
         check(call(C.byref(st["dd"]), C.byref(st["dp"]), _vp(st["enc_states"]), _vp(self._dec_c), _vp(self._dec_h),
-                   *args(lambda k: C.c_void_p(base + k), _vp(alpha)), _vp(ws), ws.numel(), self._stream()))
+                   *args(lambda k: C.c_void_p(base + k), _vp(alpha)), _vp(ws), ws.numel(), self._stream(),
+                   *(() if lens is None else (_vp(lens),))))
         host.copy_(out, non_blocking=True)
         if n_alpha:
             host_alpha.copy_(alpha, non_blocking=True)
@@ -1019,41 +1150,68 @@ class SpeechEncoderDecoder:
         ev.record(torch.cuda.current_stream(self.device))
         return _Pending(host, host_alpha, ev, **pending)
 
-    def _device_or_steps(self, path_attr, handle, steps):
+    def _device_or_steps(self, path_attr, handle, steps, alone=None):
+        """alone(b, rows_b, end, stop) = the same decode of row b of a RowBatch by itself (rows_b: its one-row batch), for the per-step
+        path: the per-step loops have no lengths, so there every row runs ALONE at B = 1 and T = its length."""
         setattr(self, path_attr, "steps" if handle is None else "device")
-        return _Ready(steps()) if handle is None else handle
+        if handle is not None:
+            return handle
+        rows = self._cur.get("rows")
+        if rows is None or (rows.B == 1 and int(rows.lens[0]) == rows.T):
+            return _Ready(steps())
+        prev, self._rows_alone = self._rows_alone, True
+        try:
+            return _Ready(alone(rows))
+        finally:
+            self._rows_alone = prev
+            setattr(self, path_attr, "steps")
 
-    def predict_async(self, X, start_token, end_token, stop_limit, slot=0):
+    def _free_rows_alone(self, rows, end_token, stop_limit, run):
+        """The free-running modes row by row: run(b, rows_b, end, stop) decodes row b alone.  A batch stops when ALL its rows have
+        emitted end_token and every row decodes until then, so a row that stops earlier alone is decoded again, without a stop, for
+        the batch's step count.  Returns the rows' results, each of n_steps columns."""
+        first = [run(b, rows.row(b), end_token, stop_limit) for b in range(rows.B)]
+        width = lambda r: int((r.tokens if isinstance(r, ScoredPrediction) else r).shape[1])
+        n = max(width(r) for r in first)
+        return [r if width(r) == n else run(b, rows.row(b), -1, n) for b, r in enumerate(first)], n
+
+    def predict_async(self, X, start_token, end_token, stop_limit, slot=0, rows=None):
         """predict() with the read-back left to the caller: returns a handle whose result() is predict()'s array.  On the device path
         (include/astk.h astk_greedy_decode: the whole decode in one persistent launch) the tokens, n_steps and the status word come back
         in ONE copy into pinned buffer `slot` (0 or 1), which result() waits for: a caller that enqueues the next batch before it reads this
         one keeps the device busy (NN.predict alternates the slots).  Shapes the library does not run on the device loop (it reports a
-        workspace of 0) take the per-step loop, which finishes before this returns.  `last_predict_path` says which path ran."""
+        workspace of 0) take the per-step loop, which finishes before this returns.  `last_predict_path` says which path ran.
+        rows= (a RowBatch, with X = None) decodes rows of different utterances, each over its own length; so for the other modes."""
         lib = _lib.load()
         go, eos, stop = int(start_token), int(end_token), int(stop_limit)
         with using_config("train", False):
-            B = self._begin_decode(X)
+            B = self._begin_decode(X, rows)
             # [n_steps, status word (float), 2 pad words, tokens (stop_limit, B)]
             handle = self._device_decode(
                 "greedy", slot, int(lib.astk_greedy_workspace_bytes(C.byref(self._cur["dd"]), stop)), 4 + stop * B, lib.astk_greedy_decode,
                 lambda p, _: (go, eos, stop, p(16), p(0), p(4)),
                 status_at=1, where="predict", parse=lambda v, _: v[4:4 + int(v[0]) * B].reshape(int(v[0]), B).T.copy())
-            return self._device_or_steps("last_predict_path", handle, lambda: self._free_steps(start_token, end_token, stop_limit)[0])
+            def alone(rb):
+                out, _ = self._free_rows_alone(rb, end_token, stop_limit, lambda b, r1, end, lim: self.predict(None, start_token, end, lim, rows=r1))
+                return np.concatenate(out, axis=0)
+            return self._device_or_steps("last_predict_path", handle, lambda: self._free_steps(start_token, end_token, stop_limit)[0], alone)
 
-    def predict_scored(self, X, start_token, end_token, stop_limit, y=None):
+    def predict_scored(self, X, start_token, end_token, stop_limit, y=None, rows=None):
         """predict() that also scores what it decodes: a ScoredPrediction (tokens as predict() returns them, the log-probability of each
         emitted token, and -- with targets y (B, L) -- the free-running cross-entropy of every step against y[:, s+1] and its sum, the
         dev loss).  The decode is predict()'s in every case (up to stop_limit steps, all-EOS early stop): steps past L - 1 have no
         target and add 0, so `loss` is the value of the reference's loop, which stops at L - 1 (enc_dec.py:384-385)."""
-        return self.predict_scored_async(X, start_token, end_token, stop_limit, y).result()
+        return self.predict_scored_async(X, start_token, end_token, stop_limit, y, rows=rows).result()
 
-    def predict_scored_async(self, X, start_token, end_token, stop_limit, y=None, slot=0):
+    def predict_scored_async(self, X, start_token, end_token, stop_limit, y=None, slot=0, rows=None):
         """predict_scored with the read-back left to the caller, like predict_async: on the device path (astk_greedy_decode_scored) ONE
         copy of [n_steps, status, tokens, logp, nll] into pinned buffer `slot`; otherwise the per-step loop, finished on return."""
         lib = _lib.load()
         go, eos, stop = int(start_token), int(end_token), int(stop_limit)
         with using_config("train", False):
-            B = self._begin_decode(X)
+            if rows is not None and y is not None and (np.ndim(y) != 2 or int(np.shape(y)[0]) != rows.B):
+                raise ValueError(f"predict_scored: y must be (B = {rows.B}, L >= 1), got {tuple(np.shape(y))}")
+            B = self._begin_decode(X, rows)
             if y is not None:
                 y = torch.as_tensor(y).to(self.device, torch.int32).contiguous()
                 if y.dim() != 2 or y.shape[0] != B or y.shape[1] < 1:
@@ -1083,17 +1241,23 @@ class SpeechEncoderDecoder:
                     return lp, torch.zeros(B, dtype=torch.float64, device=self.device)
                 tokens, cols = self._free_steps(start_token, end_token, stop_limit, record=record)
                 return ScoredPrediction(tokens, cols[0], cols[1] if y is not None else None, eos)
-            return self._device_or_steps("last_predict_path", handle, steps)
 
-    def sample(self, X, start_token, end_token, stop_limit, seed, streams=None, temperature=1.0):
+            def alone(rb):
+                out, _ = self._free_rows_alone(rb, end_token, stop_limit, lambda b, r1, end, lim: self.predict_scored(
+                    None, start_token, end, lim, None if y is None else y[b:b + 1], rows=r1))
+                cat = lambda k: np.concatenate([getattr(r, k) for r in out], axis=0)
+                return ScoredPrediction(cat("tokens"), cat("logp"), cat("nll") if y is not None else None, eos)
+            return self._device_or_steps("last_predict_path", handle, steps, alone)
+
+    def sample(self, X, start_token, end_token, stop_limit, seed, streams=None, temperature=1.0, rows=None):
         """Ancestral sampling: predict_scored() with every step's token drawn from softmax(logits / temperature) by the Gumbel-max
         noise of include/astk.h -- row b draws from (seed, streams[b]) alone (streams defaults to the rows' indices), whatever its
         position and whatever the batch around it.  Returns a ScoredPrediction: tokens (B, n_steps), logp the log-probability of each
         drawn token under the sampled distribution, score cut at the first `end_token`; nll and loss are None.  A row is finished once
         it has drawn `end_token`; the decode stops when every row has, or at stop_limit."""
-        return self.sample_async(X, start_token, end_token, stop_limit, seed, streams, temperature).result()
+        return self.sample_async(X, start_token, end_token, stop_limit, seed, streams, temperature, rows=rows).result()
 
-    def sample_async(self, X, start_token, end_token, stop_limit, seed, streams=None, temperature=1.0, slot=0):
+    def sample_async(self, X, start_token, end_token, stop_limit, seed, streams=None, temperature=1.0, slot=0, rows=None):
         """sample() with the read-back left to the caller, like predict_scored_async: on the device path (astk_sample_decode, one
         persistent launch) ONE copy of [n_steps, status, tokens, logp] into pinned buffer `slot`; otherwise the per-step loop,
         finished on return.  `last_predict_path` says which path ran."""
@@ -1101,7 +1265,9 @@ class SpeechEncoderDecoder:
         lib = _lib.load()
         go, eos, stop = int(start_token), int(end_token), int(stop_limit)
         with using_config("train", False):
-            B = self._begin_decode(X)
+            if rows is not None and streams is not None and len(list(streams)) != rows.B:
+                raise ValueError(f"sample: streams must name B = {rows.B} rows, got {len(list(streams))}")
+            B = self._begin_decode(X, rows)
             streams = list(range(B)) if streams is None else [int(v) for v in streams]
             if len(streams) != B:
                 raise ValueError(f"sample: streams must name B = {B} rows, got {len(streams)}")
@@ -1127,7 +1293,12 @@ class SpeechEncoderDecoder:
                     return (torch.log_softmax(logits.double() * inv_temp, dim=1).gather(1, word.long()[:, None])[:, 0],)
                 tokens, cols = self._free_steps(start_token, end_token, stop_limit, pick, record)
                 return ScoredPrediction(tokens, cols[0], None, eos)
-            return self._device_or_steps("last_predict_path", handle, steps)
+
+            def alone(rb):
+                out, _ = self._free_rows_alone(rb, end_token, stop_limit, lambda b, r1, end, lim: self.sample(
+                    None, start_token, end, lim, seed, [streams[b]], temperature, rows=r1))
+                return ScoredPrediction(np.concatenate([r.tokens for r in out], axis=0), np.concatenate([r.logp for r in out], axis=0), None, eos)
+            return self._device_or_steps("last_predict_path", handle, steps, alone)
 
     def _free_steps(self, start_token, end_token, stop_limit, pick=None, record=None):
         """The free-running per-step loop (seq2seq.py:475-527): one astk_decoder_step_infer, a pick and a host read per token, until
@@ -1152,20 +1323,22 @@ class SpeechEncoderDecoder:
                 npred += 1
             return torch.stack(rows, 0).T.cpu().numpy(), [torch.stack(c, 0).T.float().cpu().numpy() for c in zip(*cols)]
 
-    def score(self, X, y, return_alpha=False):
+    def score(self, X, y, return_alpha=False, rows=None):
         """Forced decoding: the eval-mode model run along the given translations y (B, L) -- step s is fed y[:, s] and scored against
         y[:, s + 1] -- as a ForcedScore: per-token log-probabilities, the argmax and its log-probability, PAD weights, per-row scores,
         the teacher-forced loss and, with return_alpha, the attention rows (B, L - 1, T'').  `last_score_path` says which path ran."""
-        return self.score_async(X, y, return_alpha).result()
+        return self.score_async(X, y, return_alpha, rows=rows).result()
 
-    def score_async(self, X, y, return_alpha=False, slot=0):
+    def score_async(self, X, y, return_alpha=False, slot=0, rows=None):
         """score() with the read-back left to the caller, like predict_scored_async: on the device path (astk_forced_score, one
         persistent launch) ONE copy of [status, logp, logp_max, pred] into pinned buffer `slot` (alpha, when asked for, is one more
         copy); shapes the library does not run on the device loop take the per-step loop, finished on return."""
         y_host = checked_targets(y, self.V)
         lib = _lib.load()
         with using_config("train", False):
-            B = self._begin_decode(X)
+            if rows is not None and y_host.shape[0] != rows.B:
+                raise ValueError(f"score: y must have B = {rows.B} rows, got {tuple(y_host.shape)}")
+            B = self._begin_decode(X, rows)
             if y_host.shape[0] != B:
                 raise ValueError(f"score: y must have B = {B} rows, got {tuple(y_host.shape)}")
             weight = (y_host[:, 1:] != 0).astype(np.float32)         # mask_pad_id[y[:, 1:]]: 0 at PAD, else 1 (materialize)
@@ -1179,7 +1352,16 @@ class SpeechEncoderDecoder:
                 lib.astk_forced_score, lambda p, alpha: (_vp(y_dev), S + 1, p(16), p(16 + 4 * sb), p(16 + 8 * sb), alpha, p(0)),
                 n_alpha=sb * self._cur["T2"] if with_alpha else 0, status_at=0, where="score", keep=y_dev,
                 parse=lambda v, al: forced_from_rows(v[4:], B, S, weight, None if al is None else al.reshape(S, B, -1).transpose(1, 0, 2).copy()))
-            return self._device_or_steps("last_score_path", handle, lambda: self._score_steps(y_dev, weight, with_alpha))
+            def alone(rb):
+                out = [self.score(None, y_host[b:b + 1], with_alpha, rows=rb.row(b)) for b in range(rb.B)]
+                cat = lambda k: np.concatenate([getattr(r, k) for r in out], axis=0)
+                alpha = None
+                if with_alpha:            # (B, S, T''max), zeros beyond each row's length
+                    alpha = np.zeros((rb.B, S, rb.T), dtype=np.float32)
+                    for b, r in enumerate(out):
+                        alpha[b, :, :r.alpha.shape[2]] = r.alpha[0]
+                return ForcedScore(cat("logp"), cat("logp_max"), cat("pred"), weight, alpha)
+            return self._device_or_steps("last_score_path", handle, lambda: self._score_steps(y_dev, weight, with_alpha), alone)
 
     def _score_steps(self, y, weight, with_alpha):
         """The per-step forced loop: y[:, s] through decode_step, a float64 log_softmax of each step's logits on the device.  (Kept apart

@@ -463,6 +463,29 @@ int astk_forced_score(const astk_decoder_desc* d, const astk_decoder_params* p, 
                       const int32_t* y, int ldy, float* logp, float* logp_max, int32_t* pred, float* alpha, float* status_dst,
                       void* ws, size_t ws_bytes, void* stream);
 
+/* ---------------------------------------------------------------- per-row source lengths in the four decode modes
+ * Each *_rows entry point is its counterpart above plus row_len (B int32 on the device, or NULL): row b attends over positions
+ * [0, row_len[b]) of enc[b] only -- a batch of DIFFERENT utterances, each encoded alone and padded to d->T rows, decodes every row as
+ * that row alone would (ast_amd.seq2seq RowBatch).  enc rows at and beyond a row's length enter no sum: whatever finite values they
+ * hold, no output bit depends on them.  astk_forced_score_rows writes alpha[s][b][t] = 0 for t >= row_len[b].  NULL is the
+ * counterpart itself (which forwards here with NULL), and row_len[b] = d->T for every b gives its results to the bit.  Workspaces
+ * are the counterparts' (the same queries, the same bytes), and so is every failure with a message.  The lengths are device data
+ * and are NOT checked here: the caller guarantees 1 <= row_len[b] <= d->T for every b < d->B (ast_amd checks before it uploads); a
+ * length outside that range is clamped to it by the kernel, and a row of length 0 would divide by an empty softmax sum. */
+int astk_greedy_decode_rows(const astk_decoder_desc* d, const astk_decoder_params* p, const float* enc, const float* c0, const float* h0,
+                            int go, int eos, int stop_limit, int32_t* tokens, int32_t* n_steps, float* status_dst,
+                            void* ws, size_t ws_bytes, void* stream, const int32_t* row_len);
+int astk_greedy_decode_scored_rows(const astk_decoder_desc* d, const astk_decoder_params* p, const float* enc, const float* c0,
+                                   const float* h0, int go, int eos, int stop_limit, const int32_t* y, int ldy, const float* class_weight,
+                                   int32_t* tokens, float* logp, float* nll, int32_t* n_steps, float* status_dst, void* ws,
+                                   size_t ws_bytes, void* stream, const int32_t* row_len);
+int astk_sample_decode_rows(const astk_decoder_desc* d, const astk_decoder_params* p, const float* enc, const float* c0, const float* h0,
+                            int go, int eos, int stop_limit, const uint64_t* row_keys, float inv_temp, int32_t* tokens, float* logp,
+                            int32_t* n_steps, float* status_dst, void* ws, size_t ws_bytes, void* stream, const int32_t* row_len);
+int astk_forced_score_rows(const astk_decoder_desc* d, const astk_decoder_params* p, const float* enc, const float* c0, const float* h0,
+                           const int32_t* y, int ldy, float* logp, float* logp_max, int32_t* pred, float* alpha, float* status_dst,
+                           void* ws, size_t ws_bytes, void* stream, const int32_t* row_len);
+
 /* ---------------------------------------------------------------- batched beam search  (nn.py:235-322 over many utterances)
  * U utterances, N hypotheses kept per utterance, K candidates per live hypothesis: every slot is one row of ONE decoder step over
  * R = U*N rows, row u*N + j = slot j of utterance u.  enc is (U, T, H): utterance u's encoder states in enc[u, 0:T''_u] (the rest

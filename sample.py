@@ -1,7 +1,8 @@
 """Ancestral sampling from the command line:
-    python sample.py -m <cfg_dir> -s <set key> -n <N samples> [-t <temperature>] [--seed <S>] [--mbr] [-w <out pickle>]
+    python sample.py -m <cfg_dir> -s <set key> -n <N samples> [-t <temperature>] [--seed <S>] [--mbr] [-w <out pickle>] [-b U]
 Draws N scored samples of every utterance of the set with the newest checkpoint of the experiment (NN.sample_set) and pickles them
 to <cfg_dir>/<set>_sample_N-<N>_T-<T>.p (or -w) in the format of beam.py's n-best pickle, so `score.py --nbest` reads it unchanged.
+-b U packs the rows of up to U utterances into one call (every row attends over its own utterance's length): the same samples.
 --mbr also picks one sample per utterance by minimum Bayes risk (ast_amd.nn.mbr_select: the highest mean sentence BLEU against the
 other samples), scores the choice with corpus BLEU (ast_amd.eval) and writes it beside the pickle as <pickle>.mbr.en."""
 import argparse
@@ -20,6 +21,7 @@ if __name__ == "__main__":
     parser.add_argument("--seed", type=int, default=0, help="seed of the draws (default 0)")
     parser.add_argument("--mbr", action="store_true", help="also choose one sample per utterance by minimum Bayes risk")
     parser.add_argument("-w", "--out", help="pickle to write (default <cfg_dir>/<set>_sample_N-<N>_T-<T>.p)")
+    parser.add_argument("-b", "--batch", type=int, default=1, help="pack the rows of U utterances into one call (default 1)")
     args = vars(parser.parse_args())
     cfg_path, set_key, N, T = args["cfg_path"], args["S"], args["N"], args["temperature"]
     if N < 1:
@@ -28,7 +30,7 @@ if __name__ == "__main__":
     print("-" * 80)
     print("Sampling for: {0:s} set: {1:s} gpu: {2:d}".format(cfg_path, set_key, nn.gpuid))
     print("-" * 80)
-    samples = nn.sample_set(set_key, N, args["seed"], temperature=T)
+    samples = nn.sample_set(set_key, N, args["seed"], temperature=T, utts_per_call=max(1, args["batch"]))
     out_fname = args["out"] or os.path.join(cfg_path, "{0:s}_sample_N-{1:d}_T-{2:.2f}.p".format(set_key, N, T))
     with open(out_fname, "wb") as f:
         pickle.dump(samples, f)

@@ -1,18 +1,20 @@
 """Forced decoding from the command line:
-    python score.py -m <cfg_dir> -s <set key> [--nbest <beam pickle>] [--alignments <out.npz>]
+    python score.py -m <cfg_dir> -s <set key> [--nbest <beam pickle> [-b U]] [--alignments <out.npz>]
 Scores the set's references with the newest checkpoint of the experiment (NN.score_set): log-probability and token count per utterance
 in <cfg_dir>/<set>_scores.txt, the teacher-forced dev loss and the perplexity on the terminal.  --nbest scores every hypothesis of a
 beam.py pickle instead -- each utterance on its own, its X repeated over its hypotheses' rows and the hypotheses PAD-padded, the
 encoding the search itself saw -- writes the model score beside the beam score to <pickle>.scores.txt and prints the largest
-difference.  --alignments also saves the attention rows, one (steps, T'') array per utterance (or per hypothesis: key utt#rank)."""
+difference; -b U packs the hypotheses of up to U utterances into one call (ast_amd.nn.score_hypotheses_packed: every row attends over
+its own utterance's length, so the scores are those of -b 1).  --alignments also saves the attention rows, one (steps, T'') array per utterance (or per hypothesis: key utt#rank)."""
 import argparse
+import itertools
 import os
 import pickle
 
 import numpy as np
 from tqdm import tqdm
 
-from ast_amd.nn import NN, score_hypotheses
+from ast_amd.nn import NN, score_hypotheses, score_hypotheses_packed
 from ast_amd.seq2seq import using_config
 
 
@@ -34,10 +36,29 @@ def score_references(nn, set_key, with_alpha):
     return rows, (sum(losses) / len(losses) if losses else 0.0), ppl, align
 
 
-def score_nbest(nn, set_key, beam, with_alpha):
-    """rows of (utt, rank, beam score, model score, n tokens) for every hypothesis of `beam` (utt -> [(hyp, score, attn_history)])."""
+def score_nbest(nn, set_key, beam, with_alpha, utts_per_call=1):
+    """rows of (utt, rank, beam score, model score, n tokens) for every hypothesis of `beam` (utt -> [(hyp, score, attn_history)]);
+    utts_per_call = U > 1: up to U utterances per call."""
     rows, align = [], {}
     with tqdm(total=len(beam), ncols=80) as pbar:
+        if utts_per_call > 1:
+            group = []
+            for utt in itertools.chain(nn.data_loader.get_batch(1, set_key, train=False, labels=False), [None]):
+                if utt is not None and utt["utts"][0] in beam:
+                    group.append(utt)
+                if group and (utt is None or len(group) == utts_per_call):
+                    names = [g["utts"][0] for g in group]
+                    with using_config("train", False):
+                        res = score_hypotheses_packed(nn.model, [g["X"] for g in group], [[list(h[0]) for h in beam[u]] for u in names],
+                                                      return_alpha=with_alpha, max_utts=utts_per_call)
+                    for u, (scores, r) in zip(names, res):
+                        for k, (h, sc) in enumerate(zip(beam[u], scores)):
+                            rows.append((u, k, float(h[1]), sc, len(h[0]) - 1))
+                            if with_alpha:
+                                align["{0:s}#{1:d}".format(u, k)] = r.alpha[k, :len(h[0]) - 1]
+                    pbar.update(len(group))
+                    group = []
+            return rows, align
         for utt in nn.data_loader.get_batch(1, set_key, train=False, labels=False):
             u = utt["utts"][0]
             if u not in beam:
@@ -59,6 +80,7 @@ if __name__ == "__main__":
     parser.add_argument("-s", "--S", help="dev/dev2/test", required=True)
     parser.add_argument("--nbest", help="a beam.py pickle: score its hypotheses instead of the references")
     parser.add_argument("--alignments", help="write the attention rows to this .npz")
+    parser.add_argument("-b", "--batch", type=int, default=1, help="with --nbest: pack the hypotheses of U utterances into one call (default 1)")
     args = vars(parser.parse_args())
     cfg_path, set_key = args["cfg_path"], args["S"]
     nn = NN(cfg_path)
@@ -68,7 +90,7 @@ if __name__ == "__main__":
     if args["nbest"]:
         with open(args["nbest"], "rb") as f:
             beam = pickle.load(f)
-        rows, align = score_nbest(nn, set_key, beam, bool(args["alignments"]))
+        rows, align = score_nbest(nn, set_key, beam, bool(args["alignments"]), max(1, args["batch"]))
         out_fname = args["nbest"] + ".scores.txt"
         with open(out_fname, "w") as f:
             for u, k, bs, ms, n in rows:
