@@ -220,6 +220,7 @@ SIGNATURES = {
     "astk_device_cu_count": (C.c_int, []),
     "astk_lstm_stack_path": (C.c_int, [C.POINTER(LstmStackDesc)]),
     "astk_lstm_stack_free_cus": (C.c_int, [C.POINTER(LstmStackDesc)]),
+    "astk_lstm_stack_side_plan": (C.c_int, [C.POINTER(LstmStackDesc), C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_int)]),
     "astk_decoder_path": (C.c_int, [C.POINTER(DecoderDesc)]),
     "astk_prof_begin": (C.c_int, []),
     "astk_prof_end": (C.c_int, [C.POINTER(C.c_double)]),
@@ -299,6 +300,13 @@ def set_tuning(key, value):
     check(lib.astk_get_tuning(key.encode(), C.byref(prev)))
     check(lib.astk_set_tuning(key.encode(), float(value)))
     return prev.value
+
+
+def get_tuning(key):
+    """astk_get_tuning (include/astk.h): the value of one of the library's documented knobs."""
+    v = C.c_double()
+    check(load().astk_get_tuning(key.encode(), C.byref(v)))
+    return v.value
 
 
 class tuning:

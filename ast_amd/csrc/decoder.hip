@@ -711,6 +711,9 @@ int astk_decoder_bwd_phase_ex(const astk_decoder_desc* d, const astk_decoder_par
   PrecScope prec_scope(d->precision, d->gemm_operands);
   DetScope det_scope(d->deterministic);
   ASTK_CHECK(phase == ASTK_DEC_BWD_ALL || phase == ASTK_DEC_BWD_CHAIN || phase == ASTK_DEC_BWD_PARAMS, "decoder_bwd: bad phase %d", phase);
+  // the fix-up workspace of the deterministic split tiles serves one launch at a time: a capped phase is one that runs beside other launches
+  ASTK_CHECK(!(deterministic_mode() && d->side_wgs > 0), "decoder_bwd: `deterministic` (the field, or the process default gemm.deterministic) and `side_wgs` = %d "
+             "exclude each other: deterministic calls run on one stream (astk.h)", d->side_wgs);
   {
     SplitPlan sp;
     ASTK_TRY(make_split(d, ws, sp));

@@ -234,13 +234,36 @@ using namespace astk;
 
 extern "C" {
 
+// (the queries resolve the arithmetic like the calls they describe: the descriptor's wish, else the process default)
 int astk_lstm_stack_path(const astk_lstm_stack_desc* d) {
   if (!d || d->struct_size != sizeof(astk_lstm_stack_desc)) return 0;
+  PrecScope prec_scope(d->precision, d->gemm_operands);
   return lstm_persist_applicable(d->T, d->B, d->h, d->n_layers, d->n_dirs) ? (lstm_persist_hoisted(d->h) ? 2 : 1) : 0;
+}
+
+int astk_lstm_stack_side_plan(const astk_lstm_stack_desc* d, int* fwd_head_steps, int* fwd_chunks, int* bwd_chunks) {
+  ASTK_CHECK_DESC(d, astk_lstm_stack_desc);
+  ASTK_CHECK(d->T > 0 && d->B > 0 && d->in_dim > 0 && d->h > 0 && d->n_layers >= 1 && d->n_layers <= ASTK_MAX_RNN_LAYERS && (d->n_dirs == 1 || d->n_dirs == 2),
+             "lstm_stack_side_plan: bad dims");
+  PrecScope prec_scope(d->precision, d->gemm_operands);
+  DetScope det_scope(d->deterministic);      // (for plan_side_bwd only, as in astk_lstm_stack_bwd_on: plan_side_fwd reads the field and the knob itself)
+  SidePlan f = {d->T, 0, 0, 0}, b = {d->T, 0, 0, 0};
+  if (lstm_persist_applicable(d->T, d->B, d->h, d->n_layers, d->n_dirs)) {
+    // the launchers' own derivation (astk_lstm_stack_fwd / _bwd_on with an input gradient and the recurrence on the call's stream)
+    const int rows = lstm_persist_rows(d->B, d->h, d->n_layers, d->n_dirs, d->side_stream != nullptr);
+    const int lpl = lstm_persist_layers_per_launch(d->B, d->h, d->n_layers, d->n_dirs, rows);
+    f = plan_side_fwd(d, rows, lstm_persist_grid_wgs(d->B, d->h, std::min(lpl, d->n_layers), d->n_dirs, rows));
+    if (!lstm_persist_hoisted(d->h)) b = plan_side_bwd(d, rows, lpl, true);
+  }
+  if (fwd_head_steps) *fwd_head_steps = f.s0;
+  if (fwd_chunks) *fwd_chunks = f.n;
+  if (bwd_chunks) *bwd_chunks = b.n;
+  return 0;
 }
 
 int astk_lstm_stack_free_cus(const astk_lstm_stack_desc* d) {
   if (!d || d->struct_size != sizeof(astk_lstm_stack_desc)) return 0;
+  PrecScope prec_scope(d->precision, d->gemm_operands);
   if (!lstm_persist_applicable(d->T, d->B, d->h, d->n_layers, d->n_dirs)) return 0;
   const int rows = lstm_persist_rows(d->B, d->h, d->n_layers, d->n_dirs, d->side_stream != nullptr);
   const int lpl = lstm_persist_layers_per_launch(d->B, d->h, d->n_layers, d->n_dirs, rows);

@@ -1018,7 +1018,16 @@ __device__ __forceinline__ void lstm_bwd_rs_steps(const PBwdArgs& a, const PCell
     __syncthreads();
     if (pending_b && tid == 0) __hip_atomic_fetch_add(ctrB, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);   // down-partials of step t+1
     if (pending_prog) {          // (uniform) dz of the chunk that ended with step t+1: written through a step ago, drained by this step's partial loads
-      if (tid == 0) __hip_atomic_fetch_add(c.prog, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+      // The counter is ONE word per cell, but the workgroup ROWS of a cell (batch tiles) are independent recurrences: nothing keeps a row from
+      // running a chunk ahead, and its arrival for chunk k + 1 would then complete "workgroups x (k + 1)" for a row that has not stored chunk
+      // k.  So every arrival, like the last one, waits until ALL workgroups of the cell have made as many arrivals as this one has: no
+      // workgroup is ever more than one arrival ahead, and the count means what the wait kernel takes it for (tests/protocol_model.py:
+      // progress_counter_procs with rows = 2).  One lane, once per chunk, normally satisfied at the first load.
+      if (tid == 0) {
+        const int made = stepno / c.prog_cs - 1;       // this workgroup's arrivals so far (this one is due at stepno = (made + 1) x prog_cs)
+        if (made > 0) (void)wait_ge(c.prog, (unsigned)(NS * nby * made), ab);
+        __hip_atomic_fetch_add(c.prog, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+      }
       pending_prog = false;
     }
     if (UP_PREFETCH) {

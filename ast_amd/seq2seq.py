@@ -825,7 +825,11 @@ class SpeechEncoderDecoder:
         share one execute in order whatever their events say -- the flag-gated hand-offs between the recurrence kernels and the chunked
         products beside them need true concurrency (in one queue the consumer would sit in front of its producer until its bounded spin
         times out), so every candidate is probed once (a 3 ms spin on one stream, a trivial kernel on the other)."""
-        if not self.side_stream_on or self.enc_variant is not None or self.deterministic:
+        if not self.side_stream_on or self.enc_variant is not None:
+            return None
+        # (the process default counts like the model's own wish: deterministic split tiles share ONE fix-up workspace, astk.h side_wgs)
+        if self.deterministic or _lib.get_tuning("gemm.deterministic") != 0:
+            self._side = None
             return None
         main = torch.cuda.current_stream(self.device)
         if main.cuda_stream == 0:

@@ -225,7 +225,11 @@ typedef struct {
    * for the chunk's flag, bounded spins + abort word like every other hand-off); backward, the input / weight gradient of a chunk starts when the
    * recurrence has passed it.  The capped grids can never keep the recurrence grid from becoming resident.  Both calls join the side stream
    * before they return, so callers see one-stream semantics.  Results are bit-identical to the in-line schedule in the forward pass and
-   * equal up to the order of float atomics in the backward pass (identical under `deterministic`). */
+   * equal up to the order of float atomics in the backward pass (identical under `deterministic`: such calls, and calls under the process
+   * default "gemm.deterministic", run everything in line).  EXCEPTION, ASTK_PREC_FP16X2: capped launches must not use the scheme's scale slots
+   * (a process-wide ring ordered by one stream), so the chunks run on bf16x3 operands while the in-line head runs fp16x2 -- the chunked steps
+   * of a tensor are then the more accurate ones, and the result is within the scheme's accuracy of the in-line schedule, not bit-identical.
+   * astk_lstm_stack_side_plan reports what a descriptor gets. */
   void* side_stream;
   int side_wgs;
   int deterministic;   /* backward call: 1 = bias gradients and split tiles summed in a fixed order (see astk_cnn_desc.deterministic); 0 = process default */
@@ -305,7 +309,10 @@ typedef struct {
   size_t zero_bytes;
   int side_wgs;        /* ASTK_DEC_BWD_PARAMS only: cap on the workgroups of every batched product of the phase (0 = none).  A caller that runs the
                           phase on a second stream beside the encoder's backward recurrence passes the CUs that recurrence leaves free, so that
-                          these launches can never keep its grid from becoming resident */
+                          these launches can never keep its grid from becoming resident.  ONE STREAM for deterministic calls: the fix-up
+                          workspace of the deterministic split tiles is process-wide and serves one launch at a time, so a call for which
+                          `deterministic` resolves to 1 (the field, else "gemm.deterministic") must not run beside other GEMM launches --
+                          astk_decoder_bwd_phase_ex refuses `side_wgs` > 0 together with it */
   int deterministic;   /* backward calls: 1 = weight-gradient split tiles summed in a fixed order (see astk_cnn_desc.deterministic); 0 = process default */
 } astk_decoder_desc;
 
@@ -674,6 +681,12 @@ int astk_lstm_stack_path(const astk_lstm_stack_desc* d);
 /* CUs the persistent recurrence launches of this shape leave FREE on the current device (0: not the persistent path, or none): what a
  * caller may pass as `side_wgs` for work it runs on a second stream beside the recurrences (astk_decoder_desc.side_wgs). */
 int astk_lstm_stack_free_cus(const astk_lstm_stack_desc* d);
+/* What astk_lstm_stack_fwd / _bwd (with an input gradient) would run beside the recurrences for this descriptor -- `side_stream`, `side_wgs`,
+ * `precision` and `deterministic` as the calls would see them -- on the current device, under the tuning table in force: the loop steps of the
+ * layer-0 input projection multiplied in line (T: all of them), the chunks of it on the side stream, and the chunks of the input gradient on
+ * the side stream behind the backward recurrence.  (0, 0 chunks: everything in line.)  Any output pointer may be NULL.  Returns 0, or -1 for
+ * a bad descriptor (astk_last_error). */
+int astk_lstm_stack_side_plan(const astk_lstm_stack_desc* d, int* fwd_head_steps, int* fwd_chunks, int* bwd_chunks);
 int astk_decoder_path(const astk_decoder_desc* d);
 int astk_persist_status(unsigned* mask_out, int reset);
 int astk_device_cu_count(void);

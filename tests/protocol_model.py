@@ -489,31 +489,39 @@ def side_chunk_flag_procs(T=6, s0=2, cs=2, nwg=2, flag_first=False):
 #     counter "A" here).  A consumer (the side stream's wait kernel + the products behind it) takes chunk k when the counter shows
 #     NS (k + 1) arrivals.  last_arrival_fix: the arrival behind the loop first waits for NS (chunks - 1) -- without it an early finisher's
 #     last arrival completes the count for chunk k - 1 while a peer has not stored that chunk's last dz (the round-4 race's shape).
-def progress_counter_procs(NS=2, T=5, cs=2, last_arrival_fix=True):
+def progress_counter_procs(NS=2, T=5, cs=2, last_arrival_fix=True, rows=1, every_arrival_waits=True):
+    """rows: independent workgroup rows (batch tiles) of the cell -- each a recurrence of its own with its own counter "A", nothing couples
+    them -- that arrive on the ONE progress counter of the cell.  every_arrival_waits: a workgroup makes its (k+1)-th arrival only when the
+    counter shows that all `rows x NS` workgroups have made k (the last arrival's rule, for every arrival).  Without it the one-apart
+    argument holds inside a row only: a row that runs a chunk ahead completes the count for a chunk the other row has not stored."""
     tag = lambda s: ("dz", s)
-    mem = {("DZ", s, j): STALE for s in range(T) for j in range(NS)}
+    W = NS * rows
+    mem = {("DZ", s, r, j): STALE for s in range(T) for r in range(rows) for j in range(NS)}
     nch = (T + cs - 1) // cs
     procs = []
-    for j in range(NS):
-        a, pending = [], False
-        for s in range(T):
-            if s > 0:
-                a.append(("wait", [("A", NS * s)]))               # the peers' partials of step s - 1
-            if pending:                                            # behind the step's barrier: the deferred arrival of the chunk that ended with s - 1
-                a.append(("add", "P"))
-                pending = False
-            a.append(("add", "A"))                                 # product-1 partials of step s (what the peers' next step waits for)
-            a.append(("write", ("DZ", s, j), tag(s)))              # dz of step s: behind the product-1 stores in program order
-            if (s + 1) % cs == 0 and s < T - 1:
-                pending = True
-        if last_arrival_fix and nch > 1:
-            a.append(("wait", [("P", NS * (nch - 1))]))
-        a.append(("add", "P"))
-        procs.append(a)
+    for r in range(rows):
+        for j in range(NS):
+            a, pending, made = [], False, 0
+            for s in range(T):
+                if s > 0:
+                    a.append(("wait", [(f"A{r}", NS * s)]))           # the peers' partials of step s - 1 (peers of the same row only)
+                if pending:                                            # behind the step's barrier: the deferred arrival of the chunk that ended with s - 1
+                    if every_arrival_waits and made > 0:
+                        a.append(("wait", [("P", W * made)]))
+                    a.append(("add", "P"))
+                    pending, made = False, made + 1
+                a.append(("add", f"A{r}"))                              # product-1 partials of step s (what the peers' next step waits for)
+                a.append(("write", ("DZ", s, r, j), tag(s)))           # dz of step s: behind the product-1 stores in program order
+                if (s + 1) % cs == 0 and s < T - 1:
+                    pending = True
+            if last_arrival_fix and nch > 1:
+                a.append(("wait", [("P", W * (nch - 1))]))
+            a.append(("add", "P"))
+            procs.append(a)
     cons = []
     for k in range(nch):
-        cons.append(("wait", [("P", NS * (k + 1))]))
+        cons.append(("wait", [("P", W * (k + 1))]))
         for s in range(k * cs, min(T, (k + 1) * cs)):
-            cons += [("read", ("DZ", s, j), tag(s)) for j in range(NS)]
+            cons += [("read", ("DZ", s, r, j), tag(s)) for r in range(rows) for j in range(NS)]
     procs.append(cons)
     return procs, mem

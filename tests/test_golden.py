@@ -152,7 +152,26 @@ def test_oracle_reproduces_fullsize_golden_es_en_20h():
 def test_hip_path_matches_fullsize_golden(case, gemm_scheme):
     """north_star gate at full size, under every arithmetic scheme bench.py times (bf16x3 = the default and the headline, f32, fp16x2):
     loss and clip norm within 1e-4 relative of the float64 oracle; per-tensor gradient norms within 3e-4, sampled gradient entries
-    within 1e-3 of the tensor's largest entry; encoder states (norm 1e-4, entries 2e-4 of the max)."""
+    within 1e-3 of the tensor's largest entry; encoder states (norm 1e-4, entries 2e-4 of the max).  On the legacy default stream:
+    everything in line."""
+    _fullsize_case(case, gemm_scheme, own_stream=False)
+
+
+# What astk_lstm_stack_side_plan reports for T'' = 200 on an MI355X with no knob set -- cfg1 / cfg1_m (batch 32; 64 free CUs, 16 tiles per 128
+# rows): head 136 and 4 chunks of 16 steps under every scheme; cfg1_b64_m: chunks of 8 steps, head 144 and 7 chunks under bf16x3 (the 512-thread
+# recurrence form), head 136 and 8 chunks under f32 and fp16x2; es_en_20h (batch 2): a chunk would be 2560 steps, so the forward pass stays in
+# line (head 200, no chunks) and the side stream carries the decoder's parameter gradients only.  No backward chunks (lstm.side_bwd is off).
+@pytest.mark.gpu
+@pytest.mark.parametrize("case,min_chunks", [("cfg1", 2), ("cfg1_m", 2), ("cfg1_b64_m", 2), ("es_en_20h", 0)])
+def test_hip_path_matches_fullsize_golden_on_a_stream_of_its_own(case, min_chunks, gemm_scheme):
+    """The same gate, same fixtures and assertions, under the schedule NN.train_epoch and bench.py run: the step on a compute stream of its
+    own, the layer-0 input projection in time chunks and the decoder's parameter gradients on the model's second stream beside the
+    recurrences, exactly as the library plans them (no tuning knob)."""
+    _fullsize_case(case, gemm_scheme, own_stream=True, min_chunks=min_chunks)
+
+
+def _fullsize_case(case, gemm_scheme, own_stream, min_chunks=0):
+    import contextlib
     import ctypes
     import torch
     from ast_amd import _lib
@@ -176,9 +195,17 @@ def test_hip_path_matches_fullsize_golden(case, gemm_scheme):
             enc = g.enc_states.cpu().numpy().astype(np.float64)
             if update:
                 opt.update()
-        return loss, grads, enc, opt
+        return loss, grads, enc, opt, g
 
-    loss, grads, enc, opt = evaluate(True)
+    with (torch.cuda.stream(torch.cuda.Stream()) if own_stream else contextlib.nullcontext()):
+        loss, grads, enc, opt, g = evaluate(True)
+        lv = float(loss.data)
+        if own_stream:      # (the schedule under test is this evaluation's; the kink-killed one below only re-derives Conv+BN gradients)
+            from schedule_helpers import require_side, side_plan
+            require_side(g)
+            plan = side_plan(g._cur["ld"])
+            print(f"side plan {case} {gemm_scheme}: head {plan[0]}, forward chunks {plan[1]}, backward chunks {plan[2]}")
+            assert plan[1] >= min_chunks and (min_chunks > 0 or plan[1] == 0), (case, plan)
     # Near-kink Conv+BN units (small-batch fixtures): the fixture NAMES the units whose float64 pre-activation lies within kink_eps of zero
     # -- a float32 evaluation may put them on the other side of the ReLU -- and holds the Conv+BN gradients with the upstream gradient of
     # exactly those units dropped.  A second evaluation on the instrumented build (libastk_test.so) drops the same units
@@ -193,7 +220,6 @@ def test_hip_path_matches_fullsize_golden(case, gemm_scheme):
             finally:
                 torch.cuda.synchronize()
                 _lib.check(tlib.astk_conv_debug_kill_units(None, 0))
-    lv = float(loss.data)
     assert abs(lv - c["loss"]) <= 1e-4 * abs(c["loss"]), (case, lv, c["loss"])
     assert abs(opt.last_grad_norm - c["grad_norm"]) <= 1e-4 * c["grad_norm"], (case, opt.last_grad_norm, c["grad_norm"])
     assert abs(np.sqrt((enc ** 2).sum()) - c["enc_norm"]) <= 1e-4 * c["enc_norm"]
@@ -224,3 +250,6 @@ def test_hip_path_matches_fullsize_golden(case, gemm_scheme):
         #  far end of the chain behind 8 x sharper logits; the reference-width schemes, bf16x3 = the default and f32, are held to 1e-3 everywhere)
         tol = 2e-3 if (gemm_scheme == "fp16x2" and c.get("out_scale")) else 1e-3
         assert err <= tol * max(v["absmax"], 1e-3 * amax), (case, k, err, v["absmax"], v.get("f32_oracle_entry_err_over_absmax"))
+    if own_stream:
+        from schedule_helpers import status_word
+        assert status_word() == 0

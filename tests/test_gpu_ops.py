@@ -339,7 +339,9 @@ def test_lstm_stack(lib, T, B, in_dim, h, nl, masks, gemm_split):
 @pytest.mark.parametrize("form", [1, 2])
 @pytest.mark.parametrize("side", [False, True])
 @pytest.mark.parametrize("T,B,in_dim,h,nl,masks", [(6, 32, 32, 256, 3, True), (23, 33, 16, 64, 3, True), (9, 48, 24, 128, 2, False), (7, 64, 32, 256, 3, True),
-                                                   (5, 17, 16, 256, 1, False), (2, 40, 16, 128, 3, True), (26, 64, 48, 64, 2, False), (12, 200, 16, 64, 3, True)])
+                                                   (5, 17, 16, 256, 1, False), (2, 40, 16, 128, 3, True), (26, 64, 48, 64, 2, False), (12, 200, 16, 64, 3, True),
+                                                   # 70 steps: ten and more 4-step chunks under either 32-row form (SIDE_FWD_CHUNKS)
+                                                   (70, 33, 16, 64, 3, True), (70, 48, 24, 128, 2, False)])
 def test_lstm_stack_32_row_workgroups_and_side_stream(lib, tune, T, B, in_dim, h, nl, masks, side, form, gemm_split):
     """Round 6.  (a) 32 batch rows per recurrence workgroup, both forms -- lstm.rows32 = 1: two 16-row tiles against one set of resident
     weight fragments in a 256-thread workgroup; = 2: two virtual 16-row workgroups in a 512-thread workgroup, two waves per SIMD, lo planes
@@ -348,12 +350,36 @@ def test_lstm_stack_32_row_workgroups_and_side_stream(lib, tune, T, B, in_dim, h
     512-thread workgroup has no rows), 1-3 layers, masks, every arithmetic scheme.  (b) `side`: the layer-0 input projection in time chunks on a second
     stream beside the forward recurrence (astk_lstm_stack_desc.side_stream; chunks of 4 steps here so that small T already has several),
     flag-gated inside the layer-0 cells; and the input gradient in chunks behind the backward recurrence's progress counter (lstm.side_bwd).
-    Same float64 reference as test_lstm_stack."""
+    Same float64 reference as test_lstm_stack.  With `side` the forward plan the library reports (astk_lstm_stack_side_plan) must be the one
+    recorded in SIDE_FWD_CHUNKS -- the short shapes run everything in line, and only the plan tells them from the chunked ones -- and the
+    forward results must be the BITS of the in-line call on the same inputs (astk.h; fp16x2: within the scheme's accuracy, capped launches
+    run on bf16x3 operands)."""
     tune("lstm.rows32", form, lib)
+    chunks = None
     if side:
         tune("lstm.overlap_chunk", 4, lib)
         tune("lstm.side_bwd", -1 if T % 2 else 2, lib)      # every chunk on the side stream / two chunks there and the rest of dx in line behind the recurrence
-    _lstm_stack_case(lib, T, B, in_dim, h, nl, masks, side=side)
+        rows_form = form if (form == 1 or gemm_split == "bf16x3") else 0      # (the 512-thread form is bf16x3's: the other schemes leave the 16-row form)
+        chunks = SIDE_FWD_CHUNKS[(T, B, in_dim, h, nl)][rows_form]
+    _lstm_stack_case(lib, T, B, in_dim, h, nl, masks, side=side, chunks=chunks, exact=gemm_split != "fp16x2")
+
+
+# Forward chunks of 4 steps that plan_side_fwd's rate model puts on the side stream on an MI355X (256 CUs), per shape (T, B, in_dim, h, layers)
+# and recurrence form (0: 16 rows per workgroup, 1 / 2: the 32-row forms), as astk_lstm_stack_side_plan reports them: a chunk of a 16-wide input
+# costs ~15.7 model-us against 2.6-4 per recurrence step, so stacks of a few steps stay in line entirely.  (The counts follow from the device's
+# CU count and the rate model's constants: whoever retunes plan_side_fwd is expected to update this table with what the query then returns.)
+SIDE_FWD_CHUNKS = {(6, 32, 32, 256, 3): (0, 0, 0), (23, 33, 16, 64, 3): (3, 4, 3), (9, 48, 24, 128, 2): (0, 1, 0), (7, 64, 32, 256, 3): (0, 0, 0),
+                   (5, 17, 16, 256, 1): (0, 0, 0), (2, 40, 16, 128, 3): (0, 0, 0), (26, 64, 48, 64, 2): (3, 5, 3), (12, 200, 16, 64, 3): (1, 2, 1),
+                   (70, 33, 16, 64, 3): (11, 16, 12), (70, 48, 24, 128, 2): (10, 16, 12)}
+
+
+def test_lstm_stack_late_side_stream_chunks(lib, tune, gemm_split):
+    """The rate model sizes the in-line head so that no chunk is late; here the side stream is held back by a 1.5 ms spin (half of what the
+    stream probe spins, far below the hand-off bound of seconds) while the recurrence is already running, so EVERY layer-0 cell finds its
+    chunk flag down and takes the waiting branch: the acquire and the re-read of freshly written gates.  Same float64 reference, same bits as
+    the in-line call, clean status word."""
+    tune("lstm.overlap_chunk", 4, lib)
+    _lstm_stack_case(lib, 70, 5, 96, 64, 2, False, side=True, chunks=9, exact=gemm_split != "fp16x2", late=True)
 
 
 def _concurrent_stream(lib, main):
@@ -380,7 +406,9 @@ def _concurrent_stream(lib, main):
     pytest.skip("no pair of concurrently executing streams on this device")
 
 
-def _lstm_stack_case(lib, T, B, in_dim, h, nl, masks, side=False):
+def _lstm_stack_case(lib, T, B, in_dim, h, nl, masks, side=False, chunks=None, exact=True, late=False):
+    """chunks (with side): the forward chunks the library must plan for this case; exact: the side-stream forward results are compared bit for
+    bit with an in-line call (else within close()); late: the side stream is held back (see below)."""
     from ast_amd._lib import LstmGrads, LstmParams, LstmStackDesc
     from oracle.ast_ref_torch import encoder_torch
     rng = np.random.default_rng(T + B)
@@ -427,12 +455,41 @@ def _lstm_stack_case(lib, T, B, in_dim, h, nl, masks, side=False):
     enc_d = torch.zeros(B, T, 2 * h, device="cuda")
     cT_d, hT_d = torch.zeros(2, nl, B, h, device="cuda"), torch.zeros(2, nl, B, h, device="cuda")
     torch.cuda.synchronize()
+    if side and chunks is not None:
+        head, fwd_chunks, bwd_chunks = C.c_int(), C.c_int(), C.c_int()
+        ok(lib, lib.astk_lstm_stack_side_plan(C.byref(d), C.byref(head), C.byref(fwd_chunks), C.byref(bwd_chunks)))
+        plan = (head.value, fwd_chunks.value, bwd_chunks.value)
+        assert plan[1] == chunks, (plan, chunks)
+        assert plan[0] + 4 * plan[1] == T or plan[1] == 0, plan
+    if late:
+        # main spins 3 ms (the host queues the call behind it), the side stream waits for the end of that spin and then spins 1.5 ms itself:
+        # the call orders the side stream behind the main one where it forks, so the spin sits in front of every chunk product
+        ok(lib, lib.astk_spin(3000, None, stream()))
+        go = torch.cuda.Event()
+        go.record(main)
+        side_s.wait_event(go)
+        ok(lib, lib.astk_spin(1500, None, C.c_void_p(side_s.cuda_stream)))
     ok(lib, lib.astk_lstm_stack_fwd(C.byref(d), lp, vp(xd), vp(md), vp(enc_d), vp(cT_d), vp(hT_d), vp(ws), nbytes, stream()))
     torch.cuda.synchronize()
     ws.check("lstm fwd")
     close(enc_d, enc, msg="enc_states")
     close(cT_d, cT, msg="cT")
     close(hT_d, hT, msg="hT")
+    if side:
+        # the in-line call (no side stream in the descriptor) on the same inputs, in a workspace of its own
+        d0 = LstmStackDesc(T, B, in_dim, h, nl, 2)
+        ws0 = GuardedWS(lib.astk_lstm_stack_workspace_bytes(C.byref(d0)))
+        enc_0 = torch.zeros_like(enc_d)
+        cT_0, hT_0 = torch.zeros_like(cT_d), torch.zeros_like(hT_d)
+        torch.cuda.synchronize()
+        ok(lib, lib.astk_lstm_stack_fwd(C.byref(d0), lp, vp(xd), vp(md), vp(enc_0), vp(cT_0), vp(hT_0), vp(ws0), ws0.nbytes, stream()))
+        torch.cuda.synchronize()
+        ws0.check("lstm fwd in line")
+        for got, want, what in ((enc_d, enc_0, "enc_states"), (cT_d, cT_0, "cT"), (hT_d, hT_0, "hT")):
+            if exact:
+                assert torch.equal(got, want), f"{what}: side-stream schedule differs from the in-line one by {float((got - want).abs().max()):.3e}"
+            else:
+                close(got, want, msg=what + " (side stream against in line)")
     dx = torch.zeros(T, B, in_dim, device="cuda")
     ge_d, gc_d, gh_d = dev(g_enc), dev(g_c), dev(g_h)     # keep alive: the call only enqueues work
     torch.cuda.synchronize()
@@ -444,6 +501,9 @@ def _lstm_stack_case(lib, T, B, in_dim, h, nl, masks, side=False):
     for k in P:
         ref_g = Pt[k].grad if Pt[k].grad is not None else torch.zeros_like(Pt[k])   # T=1: lateral.W is never used
         close(grd[k], ref_g, rtol=5e-4, atol=None if float(ref_g.abs().max()) > 0 else 1e-12, msg="grad " + k)
+    if side:
+        mask = C.c_uint(0)
+        assert lib.astk_persist_status(C.byref(mask), 1) == 0 and mask.value == 0, mask.value
 
 
 @pytest.mark.parametrize("nd,nl_enc,n,B,h", [(2, 3, 3, 5, 8), (2, 3, 1, 32, 256), (1, 2, 2, 3, 12), (2, 6, 1, 33, 512)])
@@ -674,6 +734,62 @@ def test_decoder_backward_older_role_layouts(lib, tune, env, B, L, T, H, E, A, V
     s = _dec_setup(lib, B, L, T, H, E, A, V, nl, masks, seed=B + L + 2)
     assert lib.astk_decoder_path(C.byref(s["d"])) & 1, "persistent decoder path not taken"
     _decoder_case(lib, s, B, L, T, H, E, A, V, nl, masks)
+
+
+def test_decoder_backward_refuses_a_capped_phase_in_deterministic_mode(lib):
+    """Argument validation (include/astk.h, astk_decoder_desc.side_wgs): the fix-up workspace of the deterministic split tiles is process-wide
+    and serves one launch at a time, so a parameter-gradient phase that is CAPPED -- meant to run on a second stream beside other launches --
+    is refused when `deterministic` holds, before anything is launched; the same phase without a cap runs, and chain + parameter phases
+    leave the gradients of the one-call backward."""
+    B, L, T, H, E, A, V, nl = 5, 9, 23, 64, 16, 32, 57, 1
+    s = _dec_setup(lib, B, L, T, H, E, A, V, nl, False, seed=B + L + 3)
+    d = s["d"]
+    assert lib.astk_decoder_path(C.byref(d)) & 1, "persistent decoder path not taken"
+    nbytes = lib.astk_decoder_workspace_bytes(C.byref(d))
+    ws = GuardedWS(nbytes)
+    enc_d, c0_d, h0_d = dev(s["enc"]), dev(s["c0"]), dev(s["h0"])
+    y_d, fl_d = dev(s["y"], torch.int32), dev(np.asarray(s["flags"]), torch.int32)
+    loss_d, pred_d = torch.zeros(1, device="cuda"), torch.zeros(s["S"], B, dtype=torch.int32, device="cuda")
+    d_enc = torch.zeros(B, T, H, device="cuda")
+    d_c0, d_h0 = torch.zeros(nl, B, H, device="cuda"), torch.zeros(nl, B, H, device="cuda")
+
+    def fwd():
+        ok(lib, lib.astk_decoder_fwd(C.byref(d), C.byref(s["dp"]), vp(enc_d), vp(c0_d), vp(h0_d), vp(y_d), vp(fl_d), None, None,
+                                     vp(loss_d), vp(pred_d), vp(ws), nbytes, stream()))
+
+    def phase(which):
+        return lib.astk_decoder_bwd_phase_ex(C.byref(d), C.byref(s["dp"]), C.byref(s["dg"]), vp(enc_d), vp(c0_d), vp(h0_d), vp(y_d), None, None, None,
+                                             vp(d_enc), vp(d_c0), vp(d_h0), vp(ws), nbytes, which, stream())
+    d.deterministic = 1
+    fwd()
+    ok(lib, phase(1))                                            # ASTK_DEC_BWD_CHAIN
+    torch.cuda.synchronize()
+    before = {k: v.clone() for k, v in s["grd"].items()}
+    d.side_wgs = 64
+    assert phase(2) != 0                                         # ASTK_DEC_BWD_PARAMS, capped: refused
+    msg = lib.astk_last_error().decode()
+    assert "deterministic" in msg and "side_wgs" in msg, msg
+    torch.cuda.synchronize()
+    assert all(torch.equal(v, before[k]) for k, v in s["grd"].items()), "the refused call launched something"
+    d.side_wgs = 0
+    ok(lib, phase(2))
+    torch.cuda.synchronize()
+    ws.check("decoder bwd, chain + parameter phases")
+    split = {k: v.clone() for k, v in s["grd"].items()}
+    for v in s["grd"].values():
+        v.zero_()
+    fwd()
+    ok(lib, phase(0))                                            # ASTK_DEC_BWD_ALL
+    torch.cuda.synchronize()
+    for k, v in s["grd"].items():
+        assert float((split[k] - v).abs().max()) <= 1e-5 * max(float(v.abs().max()), 1e-30), k
+    d.side_wgs = 64                                              # without `deterministic` the capped phase is what the train step runs
+    d.deterministic = 0
+    fwd()
+    ok(lib, phase(1))
+    ok(lib, phase(2))
+    torch.cuda.synchronize()
+    ws.check("decoder bwd, capped parameter phase")
 
 
 def test_wide_decoder_path_and_bounded_spins(lib, tune):

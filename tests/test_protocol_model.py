@@ -117,3 +117,19 @@ def test_side_stream_chunk_flags_and_progress_counter():
     procs, mem = M.progress_counter_procs(NS=2, T=5, cs=2, last_arrival_fix=False)
     with pytest.raises(M.Violation):
         M.explore(procs, mem)
+
+
+def test_progress_counter_shared_by_independent_workgroup_rows():
+    """The progress counter is one word per cell, but a batch of more than one workgroup row (B > 16 / 32) is several INDEPENDENT recurrences:
+    nothing keeps a row from running a chunk ahead of another, and then `count >= workgroups x (k + 1)` is reached with the fast row's
+    arrival for chunk k + 1 standing in for the slow row's for chunk k -- the side stream's product reads gates where dz should be (seen
+    once on the GPU as an input gradient off by 7 at batch 64 with 32-row workgroups).  With every arrival behind `count >= workgroups x
+    (arrivals made so far)` -- lstm_persist.hip, the rule the last arrival already had -- the count means what the consumer takes it for."""
+    for T, cs, NS in ((6, 2, 1), (5, 2, 1), (4, 2, 2)):
+        procs, mem = M.progress_counter_procs(NS=NS, T=T, cs=cs, rows=2)
+        assert M.explore(procs, mem) > 0
+    procs, mem = M.progress_counter_procs(NS=1, T=6, cs=2, rows=2, every_arrival_waits=False)
+    with pytest.raises(M.Violation):
+        M.explore(procs, mem)
+    procs, mem = M.progress_counter_procs(NS=1, T=6, cs=2, rows=1, every_arrival_waits=False)      # one row: the recurrence itself couples the workgroups
+    assert M.explore(procs, mem) > 0
