@@ -194,6 +194,9 @@ SIGNATURES = {
     "astk_beam_step": (C.c_int, [C.POINTER(BeamDesc), C.POINTER(DecoderDesc), C.POINTER(DecoderParams), _VP, C.POINTER(BeamState), _I, _VP,
                                  _SZ, _VP]),
     "astk_beam_select": (C.c_int, [C.POINTER(BeamDesc), _I, _I, _I, _VP, _VP, _L, _VP, _VP, _VP, C.POINTER(BeamState), _I, _VP]),
+    "astk_beam_decode_workspace_bytes": (_SZ, [C.POINTER(DecoderDesc), _I, _I, _I, _I]),
+    "astk_beam_decode": (C.c_int, [C.POINTER(DecoderDesc), C.POINTER(DecoderParams), _VP, _VP, _VP, _VP, _I, _I, _I, _I, _I, _VP, _VP, _VP, _VP,
+                                   _VP, _VP, _VP, _VP, _VP, _VP, _SZ, _VP]),
     "astk_attn_step_fwd_rows": (C.c_int, [_I, _I, _I, _VP, _VP, _VP, _VP, _VP, _VP, _VP, _SZ, _VP]),
     "astk_spin": (C.c_int, [C.c_uint, _VP, _VP]),
     "astk_softmax_ce_fwd": (C.c_int, [_I, _I, _L, _VP, _VP, _L, _VP, _F, _VP, _VP, _VP]),

@@ -59,6 +59,11 @@ int sample_decode_launch(const astk_decoder_desc* d, const astk_decoder_params* 
                          float* status_dst, void* ws, size_t ws_bytes, const int32_t* row_len, hipStream_t s);
 int gumbel_rows_launch(const uint64_t* row_keys, int B, int step, int V, float* out, hipStream_t s);
 size_t forced_workspace_bytes(const astk_decoder_desc* d, int n_steps, int with_alpha);
+size_t beam_decode_workspace_bytes(const astk_decoder_desc* d, int N, int K, int stop_limit, int with_alpha);
+int beam_decode_launch(const astk_decoder_desc* d, const astk_decoder_params* prm, const float* enc, const float* c0, const float* h0,
+                       const int32_t* row_len, int N, int K, int go, int eos, int stop_limit, int32_t* n_steps, float* status_dst, int32_t* hist,
+                       int32_t* slot_status, double* score, float* c_fin, float* h_fin, float* ht_fin, float* alpha, void* ws, size_t ws_bytes,
+                       hipStream_t s);
 int forced_score_launch(const astk_decoder_desc* d, const astk_decoder_params* prm, const float* enc, const float* c0, const float* h0,
                         const int32_t* y, int ldy, float* logp, float* logp_max, int32_t* pred, float* alpha, float* status_dst, void* ws,
                         size_t ws_bytes, const int32_t* row_len, hipStream_t s);
@@ -1054,6 +1059,18 @@ int astk_forced_score_rows(const astk_decoder_desc* d, const astk_decoder_params
                            const int32_t* y, int ldy, float* logp, float* logp_max, int32_t* pred, float* alpha, float* status_dst,
                            void* ws, size_t ws_bytes, void* stream, const int32_t* row_len) {
   return forced_score_launch(d, p, enc, c0, h0, y, ldy, logp, logp_max, pred, alpha, status_dst, ws, ws_bytes, row_len, (hipStream_t)stream);
+}
+
+size_t astk_beam_decode_workspace_bytes(const astk_decoder_desc* d, int N, int K, int stop_limit, int with_alpha) {
+  return beam_decode_workspace_bytes(d, N, K, stop_limit, with_alpha);
+}
+
+int astk_beam_decode(const astk_decoder_desc* d, const astk_decoder_params* p, const float* enc, const float* c0, const float* h0,
+                     const int32_t* row_len, int N, int K, int go, int eos, int stop_limit, int32_t* n_steps, float* status_dst, int32_t* hist,
+                     int32_t* slot_status, double* score, float* c_fin, float* h_fin, float* ht_fin, float* alpha, void* ws, size_t ws_bytes,
+                     void* stream) {
+  return beam_decode_launch(d, p, enc, c0, h0, row_len, N, K, go, eos, stop_limit, n_steps, status_dst, hist, slot_status, score, c_fin, h_fin,
+                            ht_fin, alpha, ws, ws_bytes, (hipStream_t)stream);
 }
 
 }  // extern "C"

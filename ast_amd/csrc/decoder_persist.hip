@@ -52,6 +52,7 @@ constexpr int PDEC_MAX_LAYERS = 3;
 // 112 KB of enc + encA); a chunk's remaining rows (chunks of up to 60 rows: T'' <= 480 at batch 32, i.e. the loader's longest
 // utterances of 1680 frames) are streamed from L2 / Infinity Cache every step -- they are the same bytes for every step of the loop.
 constexpr int PDEC_RES_ROWS = 28, PDEC_CHUNK_MAX = 60;
+constexpr int PDEC_BEAM_NSPLIT = 8;     // beam mode: attention slices per row, whatever the launch's row count (G / 32 rows)
 constexpr int NPHASE_SLOTS = 8;   // counter lines reserved per batch tile ahead of the abort word and the per-row counters
 // ... and the hand-off between decoder LAYERS the same way (round 5, ASTK_PDEC_SENT_HD=1): HD[l] -- the dropped output of layer l, one slot per
 // step, read by nobody but the cells of layer l + 1 -- sentinel-filled before the launch and polled itself by the waves that multiply it.
@@ -104,6 +105,15 @@ struct PDecArgs {
   // inference modes (GR): per-row source lengths, 1 <= row_len[b] <= T, or null = every row attends over all T positions.  Read once,
   // in front of the step loop, by the attention workgroups
   const int32_t* row_len;
+  // beam mode (BM): bN hypotheses kept and bK expansions per utterance, rows laid out by the tile rule of include/astk.h (astk_beam_decode).
+  // PRED = the token every row feeds at the next step [S][B]; LOGITS = the step's logits [S][B][Vp], kept by P5 for P6's top-K passes
+  int bN, bK;
+  int32_t* PAR;            // [S][B] parent ROW of the slot a row holds after step s (its own row: an empty or padding row)
+  int32_t* BHIST;          // [S][B][4] the history record of astk_beam_state.hist: parent slot, token, carried, 0
+  int32_t* BSTATUS;        // [B] slot status (0 empty, 1 live, 2 finished), double BSCORE [B], and BORG [B] = step * B + row of the cell
+  double* BSCORE;          //     state the slot's hypothesis was last expanded from (-1: none), all rewritten at every step
+  int32_t* BORG;
+  float* CS[PDEC_MAX_LAYERS];   // [S + 1][B][H] c of every step (slot s + 1 = after step s): the final states are gathered behind the loop
 };
 
 __device__ __forceinline__ unsigned ld_flag(const unsigned* p) { return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
@@ -318,6 +328,25 @@ __device__ __forceinline__ int* sm_row_done() {
   return done;
 }
 
+// beam mode: the slot table of the CE role's batch tile and the step's candidates, LDS that only the beam instantiations have.
+// Candidate (row i, k) sits at i * 16 + k: a finished slot's own entry at k = 0, a live slot's k-th expansion at k; ctok = -1: none.
+struct BeamTile {
+  double score[16];
+  double cscore[256];
+  int ctok[256];
+  int status[16], tok[16], org[16], sel[16];
+};
+constexpr int BM_EMPTY = 0, BM_LIVE = 1, BM_DONE = 2;      // (beam.hip's ST_*)
+__device__ __forceinline__ BeamTile* bm_tile() {
+  __shared__ BeamTile t;
+  return &t;
+}
+// ... and the cells' exchange of the register-held c among the rows of their tile: [0, 128) the first cell slot, [128, 256) the second
+__device__ __forceinline__ float* bm_cperm() {
+  __shared__ float c[256];
+  return c;
+}
+
 template <int NB>
 __device__ __forceinline__ void mfma_blocks(f32x4& acc, const float4* a, const float4* w) {
   f32x4 acc2 = {0.f, 0.f, 0.f, 0.f};
@@ -358,10 +387,19 @@ __device__ __forceinline__ void mfma_blocks(f32x4& acc, const float4* a, const f
 // sum cannot overflow) -- the four words of the tile record, as before.  P6 merges the winner by z and the sums relative to the largest
 // reference, stores the token and LOGP = (xs_tok - ref) - logf(se), then runs the greedy branch on the SAMPLED token as it stands: no wait,
 // arrival, counter or exit condition is added.  DESIGN.md section 14.
-enum PDecMode { PDEC_TRAIN, PDEC_GREEDY, PDEC_SCORED, PDEC_FORCED, PDEC_SAMPLED };
+// BM (with GR and SC, without FD and SM): beam search -- every slot of every utterance is one row.  P5 keeps what the scored mode keeps and
+// stores the step's logits; P6 forms, per row, the float32 LSE of the scored mode and the row's K best tokens (K sweeps over the stored
+// logits: higher logit first, equal ones lower id first), lists the candidates of every utterance slot by slot (a finished slot itself,
+// a live slot its K expansions), takes the stable top N by float64 score, and writes -- in front of its PH_CE arrival -- the history
+// record, the token the row feeds next (PRED) and the PARENT row (PAR) of every row.  The cells gather through PAR: they read h and ht of
+// their row's parent row, and permute the register-held c among the rows of their tile through LDS.  The top layer's cells, which wait
+// for no PH_CE in the other modes, wait for PH_CE(s-1) of their tile in front of their recurrent half.  A tile reports once none of its
+// slots is live.  DESIGN.md section 16.
+enum PDecMode { PDEC_TRAIN, PDEC_GREEDY, PDEC_SCORED, PDEC_FORCED, PDEC_SAMPLED, PDEC_BEAM };
 template <int NC, int NL, bool XS, PDecMode MODE>
 __device__ __forceinline__ void decoder_persist_fwd_body(const PDecArgs& a) {
   constexpr bool GR = MODE != PDEC_TRAIN, SC = GR && MODE != PDEC_GREEDY, FD = MODE == PDEC_FORCED, SM = MODE == PDEC_SAMPLED;
+  constexpr bool BM = MODE == PDEC_BEAM;
   constexpr bool STOP = GR && !FD;         // the greedy modes' stop word exists
   constexpr bool SUMS = !GR || SC;         // P5 / P6 keep the sum of exponentials and the target logit
   extern __shared__ __attribute__((aligned(16))) float lds[];   // enc slice [chunk][H], encA slice [chunk][H], scratch
@@ -463,8 +501,15 @@ __device__ __forceinline__ void decoder_persist_fwd_body(const PDecArgs& a) {
     }
   }
   // ---------------- resident slices of enc_states and encA = enc Wa in LDS: rows [t0, t1) of batch row att_b
-  const int t0 = att_sp * a.chunk;
-  int t1 = min(T, t0 + a.chunk);
+  // BM: a row's slices are cut by ITS OWN length -- chunk = ceil(length / PDEC_BEAM_NSPLIT) <= a.chunk, which only sizes the LDS -- so
+  // that its attention arithmetic is the same in every launch; trailing slices of a short row are empty
+  int chunk_r = a.chunk;
+  if constexpr (BM) {
+    if (a.row_len) chunk_r = min(a.chunk, (max(1, min(T, a.row_len[att_b])) + PDEC_BEAM_NSPLIT - 1) / PDEC_BEAM_NSPLIT);
+  }
+  const int t0 = att_sp * chunk_r;
+  int t1 = min(T, t0 + chunk_r);
+  if constexpr (BM) t1 = max(t0, t1);        // (8 slices of ceil(T / 8) may start beyond T: empty, with or without lengths)
   if constexpr (GR) {        // a row with a length: this workgroup's slice ends where the row does, and is EMPTY (nrow = 0) beyond it
     if (a.row_len) t1 = max(t0, min(t1, min(T, a.row_len[att_b])));
   }
@@ -539,9 +584,140 @@ __device__ __forceinline__ void decoder_persist_fwd_body(const PDecArgs& a) {
     if ((tid & 15) == 0) sm_row_done()[tid >> 4] = row_done ? 1 : 0;
   }
   bool tile_done = false;                             // GR, CE role (thread 0): this batch tile has reported
+  if constexpr (BM) {        // step 0: slot 0 of every utterance is live, with score 0 and `go` as its token (ordered by the first wait's barrier)
+    if (has_ce && tid < 16) {
+      BeamTile* t = bm_tile();
+      const bool live = ce_rank * 16 + tid < B && tid < (16 / a.bN) * a.bN && tid % a.bN == 0;
+      t->score[tid] = 0.0; t->status[tid] = live ? BM_LIVE : BM_EMPTY; t->tok[tid] = a.go; t->org[tid] = -1;
+    }
+  }
   auto run_p6 = [&](const int s) -> bool {
       const int bt = ce_rank, m0 = bt * 16;
       const int row = m0 + (tid >> 4), sub = tid & 15;       // 16 threads per row sweep the tiles
+      if constexpr (BM) {
+        BeamTile* const t = bm_tile();
+        // (every per-lane value of this role is formed from `tl` here, behind an empty asm: hoisted out of the step loop they would each
+        //  hold a register over the whole loop, and the multi-layer kernels have none to spare -- sections 12-15)
+        int tl = tid;
+        asm volatile("" : "+v"(tl));
+        const int N = a.bN, K = a.bK, i = tl >> 4, sub = tl & 15, row = m0 + i;
+        if (!wg_wait_sh(CTR(PH_LOG, bt), a.ntile_v, s + 1, a.ab, &s_flag, StopCtl{a.gctl + 3 * CTRS, s, false})) return false;
+        const int rl = min(row, B - 1);
+        // the row's LSE = mx + logf(se): the scored mode's float32 merge of the tile records
+        float mx = -INFINITY, se = 0.f;
+        for (int k = sub; k < a.ntile_v; k += 16) {
+          const float4 cs = ldb128_sc1(r_ces, (((long)s * B + rl) * a.ntile_v + k) * 4);
+          const float nm = fmaxf(mx, cs.x);
+          se = (mx == -INFINITY ? 0.f : se * expf(mx - nm)) + cs.y * expf(cs.x - nm);
+          mx = nm;
+        }
+#pragma unroll
+        for (int o = 8; o > 0; o >>= 1) {
+          const float om = __shfl_xor(mx, o), os = __shfl_xor(se, o);
+          const float nm = fmaxf(mx, om);
+          se = (mx == -INFINITY ? 0.f : se * expf(mx - nm)) + (om == -INFINITY ? 0.f : os * expf(om - nm));
+          mx = nm;
+        }
+        const float lg = logf(se);
+        // the row's K best tokens: sweep k keeps the first logit behind the pick of sweep k-1 (16 lanes per row, 16-byte reads of the
+        // row P5 stored); lane k of the row keeps pick k
+        const __amdgpu_buffer_rsrc_t r_lg = make_rsrc(a.LOGITS);
+        const long lrow = ((long)s * B + rl) * a.Vp;
+        float pv = INFINITY, my_x = 0.f;
+        int pi = -1, my_i = -1;
+        for (int k = 0; k < K; ++k) {
+          float bv = -INFINITY;
+          int bi = -1;
+          for (int j = sub * 4; j < V; j += 64) {
+            const float4 v = ldb128_sc1(r_lg, lrow + j);
+            const float xs[4] = {v.x, v.y, v.z, v.w};
+#pragma unroll
+            for (int e = 0; e < 4; ++e) {
+              const int n = j + e;
+              const float x = xs[e];
+              if (n < V && (pv > x || (pv == x && pi < n)) && (bi < 0 || x > bv || (x == bv && n < bi))) { bv = x; bi = n; }
+            }
+          }
+#pragma unroll
+          for (int o = 8; o > 0; o >>= 1) {
+            const float ov = __shfl_xor(bv, o);
+            const int oi = __shfl_xor(bi, o);
+            if (oi >= 0 && (bi < 0 || ov > bv || (ov == bv && oi < bi))) { bv = ov; bi = oi; }
+          }
+          if (sub == k) { my_x = bv; my_i = bi; }
+          pv = bv; pi = bi;
+        }
+        // candidate (row i, k = sub): float64 score = the slot's + logp, logp = (x - mx) - logf(se) formed without rounding the LSE first
+        const int st_i = t->status[i];
+        const bool valid = row < B && ((st_i == BM_LIVE && sub < K && my_i >= 0) || (st_i == BM_DONE && sub == 0));
+        double cs = -INFINITY;
+        int ct = -1;
+        if (valid) {
+          if (st_i == BM_DONE) { cs = t->score[i]; ct = t->tok[i]; }
+          else { cs = t->score[i] + (double)((my_x - mx) - lg); ct = my_i; }
+          if (cs != cs) cs = -INFINITY;          // (a NaN score ranks last: the ranks below stay a permutation)
+        }
+        t->cscore[tl] = cs;
+        t->ctok[tl] = ct;
+        if (tl < 16) t->sel[tl] = -1;
+        __syncthreads();
+        // stable top N of the utterance's candidates: a candidate lands at its rank (higher score first, equal scores in list order)
+        const int ui = i / N;
+        if (valid) {
+          int rank = 0;
+          const int c0 = ui * N * 16, c1 = c0 + N * 16;
+          for (int c = c0; c < c1; ++c) rank += (t->ctok[c] >= 0 && (t->cscore[c] > cs || (t->cscore[c] == cs && c < tl))) ? 1 : 0;
+          if (rank < N) t->sel[ui * N + rank] = tl;
+        }
+        __syncthreads();
+        // the new slot of row tl < 16: read the old table, barrier, then write
+        int n_par = tl & 15, n_tok = a.eos, n_st = BM_EMPTY, n_org = -1, n_car = 0, h_par = -1;
+        double n_sc = 0.0;
+        if (tl < 16) {
+          const int c = t->sel[tl];
+          if (c >= 0) {
+            n_par = c >> 4;
+            n_car = t->status[n_par] == BM_DONE ? 1 : 0;
+            n_tok = t->ctok[c];
+            n_sc = t->cscore[c];
+            n_st = (n_car || n_tok == a.eos) ? BM_DONE : BM_LIVE;
+            n_org = n_car ? t->org[n_par] : s * B + m0 + n_par;
+            h_par = n_par - (tl / N) * N;
+          }
+        }
+        __syncthreads();
+        if (tl < 16) {
+          t->score[tl] = n_sc; t->status[tl] = n_st; t->tok[tl] = n_tok; t->org[tl] = n_org;
+          if (m0 + tl < B) {
+            const unsigned r = (unsigned)(m0 + tl);
+            sti_sc1(ua(a.PAR + (long)s * B, r), m0 + n_par);
+            sti_sc1(ua(a.PRED + (long)s * B, r), n_tok);
+            *ua(reinterpret_cast<int4*>(a.BHIST + (long)s * B * 4), r) = make_int4(h_par, n_st == BM_EMPTY ? 0 : n_tok, n_car, 0);
+            *ua(a.BSTATUS, r) = n_st;
+            *ua(a.BSCORE, r) = n_sc;
+            *ua(a.BORG, r) = n_org;
+          }
+        }
+        const bool any_live = __any(tl < 16 && n_st == BM_LIVE);
+        if (tl == 0) s_wdone[0] = any_live ? 0 : 1;
+        // the tile's report between the barrier and the arrival, as in the greedy modes: the stop word is written in front of PH_CE(s)
+        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+        __syncthreads();
+        if (tl == 0) {
+          if (!tile_done && s_wdone[0]) {
+            tile_done = true;
+            unsigned* gc = a.gctl;
+            __hip_atomic_fetch_max(gc, (unsigned)s, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+            if (__hip_atomic_fetch_add(gc + CTRS, 1u, __ATOMIC_ACQ_REL, __HIP_MEMORY_SCOPE_AGENT) + 1 == (unsigned)a.nbt) {
+              const unsigned n = __hip_atomic_load(gc, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) + 1;
+              __hip_atomic_store(gc + 3 * CTRS, n, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+              asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+            }
+          }
+          __hip_atomic_fetch_add(CTR(PH_CE, bt), 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        }
+        return true;
+      }
       [[maybe_unused]] bool sc_tgt = false;                  // SC: step s has a target (column s+1 of y); its class weight
       [[maybe_unused]] float sc_w = 0.f;
       if constexpr (SC && !FD && !SM) {       // (read in front of the wait: neither load is on the chain)
@@ -687,6 +863,27 @@ __device__ __forceinline__ void decoder_persist_fwd_body(const PDecArgs& a) {
         tok = *ua(a.y + s, (unsigned)(r * a.L));
       } else tok = truth ? (GR ? a.go : yS[r16 * a.L + s]) : ldi_sc1(ua(a.PRED + (long)(s - 1) * B, (unsigned)brow));
       tok = tok < 0 ? 0 : (tok >= V ? V - 1 : tok);
+      [[maybe_unused]] int prow = brow;           // BM: the row whose h_{s-1} and ht_{s-1} this lane's row continues
+      if constexpr (BM) {
+        if (s > 0) {       // (behind PH_CE(s-1): P6 wrote the parent words in front of that arrival)
+          const int32_t* par = a.PAR + (long)(s - 1) * B;
+          int tl = tid;
+          asm volatile("" : "+v"(tl));         // (the addresses below formed here, not kept over the loop: as in P5)
+          prow = ldi_sc1(ua(par, (unsigned)min(m0 + (tl & 15), B - 1)));
+          const int pr = tl < 128 ? (ldi_sc1(ua(par, (unsigned)min(m0 + ((tl >> 2) & 15), B - 1))) - m0) & 15 : 0;
+          float* cp = bm_cperm();
+          if (tl < 128) {
+            cp[tl] = c_state;
+            if (NL > 2) cp[128 + tl] = c_state2;
+          }
+          __syncthreads();
+          if (tl < 128) {        // (tid = tile * 64 + row * 4 + unit: the parent's c of the same unit)
+            const int src = (tl & ~63) | (pr << 2) | (tl & 3);
+            c_state = cp[src];
+            if (NL > 2) c_state2 = cp[128 + src];
+          }
+        }
+      }
       if (s > 0) { if (!wg_wait_sh(CTR(PH_CELL, bt), H / 8, s, a.ab, &s_flag, sc)) return; }
       f32x4 acc[2] = {{0.f, 0.f, 0.f, 0.f}, {0.f, 0.f, 0.f, 0.f}};
       {
@@ -703,7 +900,7 @@ __device__ __forceinline__ void decoder_persist_fwd_body(const PDecArgs& a) {
           }
           ae[i] = v;
         }
-        aload_sc1<NB_H>(ah, r_hr, ((long)s * B + brow) * H, H, lane, wave);     // h_{s-1}: published a whole step ago (waited above)
+        aload_sc1<NB_H>(ah, r_hr, ((long)s * B + (BM ? prow : brow)) * H, H, lane, wave);     // h_{s-1}: published a whole step ago (waited above)
         __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
         for (int t = 0; t < 2; ++t) {
@@ -722,7 +919,7 @@ __device__ __forceinline__ void decoder_persist_fwd_body(const PDecArgs& a) {
         if (!wg_wait_sh(CTR(PH_CTX, bt), A / 16, s, a.ab, &s_flag, sc)) return;
         TICK(1)
         float4 at[NB_A];
-        if constexpr (GR) aload_sc1<NB_A>(at, r_ht, ((long)s * B + brow) * A, A, lane, wave);     // (HT[s] = ht_{s-1}: no X0)
+        if constexpr (GR) aload_sc1<NB_A>(at, r_ht, ((long)s * B + (BM ? prow : brow)) * A, A, lane, wave);     // (HT[s] = ht_{s-1}: no X0)
         else aload_sc1<NB_A>(at, r_x0, ((long)s * B + brow) * XI + E, A, lane, wave);
         __builtin_amdgcn_sched_barrier(0);
         mfma_blocks<NB_A>(acc[0], at, wreg + W0_A);
@@ -753,6 +950,9 @@ __device__ __forceinline__ void decoder_persist_fwd_body(const PDecArgs& a) {
         *ua(reinterpret_cast<float4*>(a.Gt[0] + (long)s * B * 4 * H), cell_off) = gsave;
         *ua(a.Cst[0] + (long)(s + 1) * B * H, cell_off) = c_state;
       }
+      if constexpr (BM) {
+        if (ev) *ua(a.CS[0] + (long)(s + 1) * B * H, cell_off) = c_state;      // (plain store, off the chain: read behind the loop)
+      }
     }
     // ================= P1b: decoder layers 1..NL-1 (one cell item per workgroup: layer 1 of a 3-layer stack on the lower
     // workgroups, the top layer on the upper ones).  z = Wu hd_{l-1,s} + Wl h_{l,s-1} + b: the recurrent half runs before the wait.
@@ -765,11 +965,30 @@ __device__ __forceinline__ void decoder_persist_fwd_body(const PDecArgs& a) {
         const int l = pass == 0 ? 1 : TOP;
         const int bt = c2_bt, m0 = bt * 16;
         const int brow = min(m0 + r16, B - 1);
+        [[maybe_unused]] int prow = brow;
+        if constexpr (BM) {
+          if (s > 0) {
+            // the top layer's workgroups wait for no P6 in the other modes: here the parent words of step s-1 become visible behind
+            // PH_CE(s-1) of their tile (the mid layer shares the layer-0 workgroup, which has waited and has permuted c_state2 already)
+            if (pass == 1) { if (!wg_wait_sh(CTR(PH_CE, bt), 1, s, a.ab, &s_flag, StopCtl{stopw, s, true})) return; }
+            const int32_t* par = a.PAR + (long)(s - 1) * B;
+            int tl = tid;
+            asm volatile("" : "+v"(tl));       // (as in the layer-0 cells)
+            prow = ldi_sc1(ua(par, (unsigned)min(m0 + (tl & 15), B - 1)));
+            if (pass == 1) {
+              const int pr = tl < 128 ? (ldi_sc1(ua(par, (unsigned)min(m0 + ((tl >> 2) & 15), B - 1))) - m0) & 15 : 0;
+              float* cp = bm_cperm();
+              if (tl < 128) cp[tl] = c_state2;
+              __syncthreads();
+              if (tl < 128) c_state2 = cp[(tl & ~63) | (pr << 2) | (tl & 3)];
+            }
+          }
+        }
         if (s > 0) { if (!wg_wait_sh(CTR(PH_CELL + l, bt), H / 8, s, a.ab, &s_flag, sc)) return; }
         f32x4 acc[2] = {{0.f, 0.f, 0.f, 0.f}, {0.f, 0.f, 0.f, 0.f}};
         {
           float4 ah[NB_H];
-          aload_sc1<NB_H>(ah, make_rsrc(a.HR[l]), ((long)s * B + brow) * H, H, lane, wave);     // h_{l,s-1} (h0 at s = 0)
+          aload_sc1<NB_H>(ah, make_rsrc(a.HR[l]), ((long)s * B + (BM ? prow : brow)) * H, H, lane, wave);     // h_{l,s-1} (h0 at s = 0)
           __builtin_amdgcn_sched_barrier(0);
           mfma_blocks<NB_H>(acc[0], ah, wreg + OFF_C2 + NB_H);
           mfma_blocks<NB_H>(acc[1], ah, wreg + OFF_C2 + CELLW2 + NB_H);
@@ -831,6 +1050,9 @@ __device__ __forceinline__ void decoder_persist_fwd_body(const PDecArgs& a) {
         if (!GR && ev) {
           *ua(reinterpret_cast<float4*>(a.Gt[l] + (long)s * B * 4 * H), c2_off) = gsave;
           *ua(a.Cst[l] + (long)(s + 1) * B * H, c2_off) = c_state2;
+        }
+        if constexpr (BM) {
+          if (ev) *ua(a.CS[l] + (long)(s + 1) * B * H, c2_off) = c_state2;
         }
       }
     }
@@ -1076,7 +1298,7 @@ __device__ __forceinline__ void decoder_persist_fwd_body(const PDecArgs& a) {
       TQ(5)
       if (a.tick_out) tk_att += wall_clock64() - ta0;
       if (!GR && tid < nrow) a.ALPHA[((long)s * B + b) * Tp + t0 + tid] = my_score;   // raw score, normalised by the backward (M, 1/L in ML)
-      if constexpr (FD) {
+      if constexpr (FD || BM) {
         if (a.ALPHA && tid < nrow) {        // raw score, normalised behind the loop (k_alpha_normalise)
           int t = tid;
           asm volatile("" : "+v"(t));
@@ -1132,7 +1354,7 @@ __device__ __forceinline__ void decoder_persist_fwd_body(const PDecArgs& a) {
       publish_sh(CTR(PH_CMB, bt), b - bt * 16);
       TICK(7)
       if (!GR && tid == 0) { a.ML[((long)s * B + b) * 2] = Mx; a.ML[((long)s * B + b) * 2 + 1] = inv; }
-      if constexpr (FD) {
+      if constexpr (FD || BM) {
         if (a.ML && tid == 0) { float* ml = ua(a.ML + ((long)s * B + b) * 2, 0u); ml[0] = Mx; ml[1] = inv; }
       }
     }
@@ -1207,6 +1429,11 @@ __device__ __forceinline__ void decoder_persist_fwd_body(const PDecArgs& a) {
         if (ok) x = v + *ua(a.bo, (unsigned)nn);
       } else {
         x = ok ? v + a.bo[n] : -INFINITY;
+      }
+      if constexpr (BM) {      // (P6 sweeps the row for its K best: written through, in front of the tile's arrival)
+        int rr = row, nn = n;
+        asm volatile("" : "+v"(rr), "+v"(nn));
+        if (ok) st_sc1_u(a.LOGITS + (long)s * B * a.Vp, (unsigned)(rr * a.Vp + nn), x);
       }
       if (!GR) {       // (GR: P6 needs the tile's maximum and its index only)
         if (ok) *ua(a.LOGITS + (long)s * B * a.Vp, (unsigned)(row * a.Vp + n)) = x;
@@ -1316,6 +1543,32 @@ template <int NC, int NL, bool XS>
 __global__ __launch_bounds__(256, 1) void decoder_persist_sampled(PDecArgs a) {
   decoder_persist_fwd_body<NC, NL, XS, PDEC_SAMPLED>(a);
   greedy_last_out(a);
+}
+
+// The beam mode as a kernel of its own, likewise.
+template <int NC, int NL, bool XS>
+__global__ __launch_bounds__(256, 1) void decoder_persist_beam(PDecArgs a) {
+  decoder_persist_fwd_body<NC, NL, XS, PDEC_BEAM>(a);
+  greedy_last_out(a);
+}
+
+// Behind the beam loop: the final state of every slot = c, h and ht of the step and row its hypothesis was last expanded from
+// (org = step * B + row; -1, an empty slot: zeros).  One workgroup per row.
+struct BeamFinalArgs {
+  const int32_t* org;
+  const float *CS[PDEC_MAX_LAYERS], *HR[PDEC_MAX_LAYERS], *HT;
+  float *c_fin, *h_fin, *ht_fin;
+  int B, H, A, nl;
+};
+__global__ __launch_bounds__(256) void k_beam_final_states(BeamFinalArgs a) {
+  const int r = blockIdx.x, o = a.org[r], B = a.B, H = a.H;
+  const long src = o < 0 ? 0 : ((long)(o / B + 1) * B + o % B);
+  for (int l = 0; l < a.nl; ++l)
+    for (int k = threadIdx.x; k < H; k += 256) {
+      a.c_fin[((long)l * B + r) * H + k] = o < 0 ? 0.f : a.CS[l][src * H + k];
+      a.h_fin[((long)l * B + r) * H + k] = o < 0 ? 0.f : a.HR[l][src * H + k];
+    }
+  for (int k = threadIdx.x; k < a.A; k += 256) a.ht_fin[(long)r * a.A + k] = o < 0 ? 0.f : a.HT[src * a.A + k];
 }
 
 // out[b][n] = the Gumbel noise of (row_keys[b], step, n), n < V: one decoder step's draws as a dense (B, V) buffer, through the function
@@ -2326,6 +2579,7 @@ static int inference_run(PDecMode mode, const astk_decoder_desc* d, const astk_d
   if (mode == PDEC_FORCED) launch([](auto nc, auto nl, auto xs) { return decoder_persist_forced<nc, nl, xs>; });
   else if (mode == PDEC_SAMPLED) launch([](auto nc, auto nl, auto xs) { return decoder_persist_sampled<nc, nl, xs>; });
   else if (mode == PDEC_SCORED) launch([](auto nc, auto nl, auto xs) { return decoder_persist_greedy_scored<nc, nl, xs>; });
+  else if (mode == PDEC_BEAM) launch([](auto nc, auto nl, auto xs) { return decoder_persist_beam<nc, nl, xs>; });
   else launch([](auto nc, auto nl, auto xs) { return decoder_persist_fwd<nc, nl, xs, true>; });
   ASTK_LAUNCH_CHECK();
   return 0;
@@ -2454,6 +2708,91 @@ int forced_score_launch(const astk_decoder_desc* d, const astk_decoder_params* p
   ASTK_TRY(inference_run(PDEC_FORCED, d, prm, enc, h0, a, f.g, s));
   if (alpha) {
     hipLaunchKernelGGL(k_alpha_normalise, dim3(a.S * a.B), dim3(256), 0, s, f.RAW, f.ML, alpha, row_len, a.B, a.T, a.Tp);
+    ASTK_LAUNCH_CHECK();
+  }
+  return 0;
+}
+
+// ---------------------------------------------------------------------------------------------------- beam search
+// decoder_persist_beam on the greedy plan, plus the step's logits [S][B][Vp], the fed tokens and parent rows [S][B], the slots' origins
+// [B], c of every step and layer [S + 1][B][H], and -- with an alpha output -- the forced mode's raw scores and (max, 1 / sum) pairs.
+struct BeamPlan {
+  GreedyPlan g;
+  float *LOGITS, *CS[PDEC_MAX_LAYERS], *RAW, *ML;
+  int32_t *FEED, *PAR, *ORG;
+  size_t bytes;
+};
+// the row layout of include/astk.h: N slots of an utterance inside one 16-row tile, B ending with an utterance's last slot
+static bool beam_layout_ok(int B, int N, int K, int V) {
+  if (N < 1 || N > ASTK_BEAM_MAX_N || K < 1 || K > ASTK_BEAM_MAX_K || K > V || B < 1) return false;
+  const int last = (B - 1) % 16 + 1;                 // rows of the last tile
+  return last <= (16 / N) * N && last % N == 0;
+}
+static bool beam_plan(const astk_decoder_desc* d, int N, int K, int stop_limit, int with_alpha, void* ws, BeamPlan& p) {
+  if (!greedy_plan(d, stop_limit, ws, p.g)) return false;
+  if (!beam_layout_ok(d->B, N, K, d->V)) return false;
+  // The attention split of this mode does not depend on the launch's row count or T: PDEC_BEAM_NSPLIT slices per row (the split of a
+  // 32-row launch), each row cut by its own length in the kernel; chunk = the longest slice any row can have.  One scan kernel per H:
+  // H = 512 always takes the specialised scan (T <= 480), so a row never meets the generic one in one launch and the other in the next.
+  p.g.nsplit = d->T < PDEC_BEAM_NSPLIT ? d->T : PDEC_BEAM_NSPLIT;
+  p.g.chunk = (d->T + PDEC_BEAM_NSPLIT - 1) / PDEC_BEAM_NSPLIT;
+  if (p.g.chunk > 256 || (d->H == 512 && !pdec_special(d->H, p.g.chunk))) return false;
+  if (pdec_lds_floats(p.g.chunk, d->H, p.g.nsplit) * sizeof(float) > 136 * 1024) return false;
+  Carver c(ws ? (char*)ws + p.g.bytes : nullptr);
+  const size_t S = stop_limit, B = d->B, H = d->H, Vp = (d->V + 3) / 4 * 4, Tp = (d->T + 3) / 4 * 4;
+  p.g.PART = c.take<float>(S * B * p.g.nsplit * (H + 4));      // (the greedy plan's was sized by its own split)
+  p.LOGITS = c.take<float>(S * B * Vp);
+  for (int l = 0; l < PDEC_MAX_LAYERS; ++l) p.CS[l] = l < d->n_layers ? c.take<float>((S + 1) * B * H) : nullptr;
+  p.FEED = c.take<int32_t>(S * B);
+  p.PAR = c.take<int32_t>(S * B);
+  p.ORG = c.take<int32_t>(B);
+  p.RAW = with_alpha ? c.take<float>(S * B * Tp) : nullptr;
+  p.ML = with_alpha ? c.take<float>(S * B * 2) : nullptr;
+  p.bytes = p.g.bytes + c.total();
+  return true;
+}
+
+size_t beam_decode_workspace_bytes(const astk_decoder_desc* d, int N, int K, int stop_limit, int with_alpha) {
+  BeamPlan p;
+  return beam_plan(d, N, K, stop_limit, with_alpha, nullptr, p) ? p.bytes : 0;
+}
+
+int beam_decode_launch(const astk_decoder_desc* d, const astk_decoder_params* prm, const float* enc, const float* c0, const float* h0,
+                       const int32_t* row_len, int N, int K, int go, int eos, int stop_limit, int32_t* n_steps, float* status_dst, int32_t* hist,
+                       int32_t* slot_status, double* score, float* c_fin, float* h_fin, float* ht_fin, float* alpha, void* ws, size_t ws_bytes,
+                       hipStream_t s) {
+  ASTK_CHECK_DESC(d, astk_decoder_desc);
+  ASTK_CHECK(N >= 1 && N <= ASTK_BEAM_MAX_N && K >= 1 && K <= ASTK_BEAM_MAX_K, "beam_decode: N = %d / K = %d outside 1..%d / 1..%d", N, K,
+             ASTK_BEAM_MAX_N, ASTK_BEAM_MAX_K);
+  ASTK_CHECK(d->V > 1 && K <= d->V && go >= 0 && go < d->V && eos >= 0 && eos < d->V, "beam_decode: go %d / eos %d outside [0, V = %d), or K = %d above V",
+             go, eos, d->V, K);
+  ASTK_CHECK(stop_limit >= 1 && stop_limit <= ASTK_GREEDY_MAX_STEPS, "beam_decode: stop_limit %d outside [1, %d]", stop_limit, ASTK_GREEDY_MAX_STEPS);
+  ASTK_CHECK(beam_layout_ok(d->B, N, K, d->V), "beam_decode: B = %d rows do not end with the last of the N = %d slots of an utterance (%d "
+             "utterances per 16-row tile)", d->B, N, 16 / N);
+  BeamPlan p;
+  ASTK_CHECK(beam_plan(d, N, K, stop_limit, alpha != nullptr, nullptr, p), "beam_decode: B = %d, H = %d, %d layers (or the knob dec.persist = 0) does "
+             "not run on the device loop: astk_beam_decode_workspace_bytes returns 0, decode with astk_beam_step", d->B, d->H, d->n_layers);
+  ASTK_CHECK(ws && ws_bytes >= p.bytes, "beam_decode: workspace too small (%zu < %zu)", ws_bytes, p.bytes);
+  ASTK_CHECK(prm && enc && c0 && h0 && n_steps && hist && slot_status && score && c_fin && h_fin && ht_fin, "beam_decode: null pointer");
+  ASTK_CHECK(((uintptr_t)hist & 15) == 0 && ((uintptr_t)score & 7) == 0, "beam_decode: hist must be 16-byte aligned and score 8-byte aligned");
+  beam_plan(d, N, K, stop_limit, alpha != nullptr, ws, p);
+  PDecArgs a = inference_args(d, prm, enc, c0, stop_limit, p.g);
+  a.PRED = p.FEED; a.PAR = p.PAR; a.LOGITS = p.LOGITS; a.ALPHA = p.RAW; a.ML = p.ML;
+  a.BHIST = hist; a.BSTATUS = slot_status; a.BSCORE = score; a.BORG = p.ORG;
+  for (int l = 0; l < d->n_layers; ++l) a.CS[l] = p.CS[l];
+  a.bN = N; a.bK = K; a.go = go; a.eos = eos;
+  a.n_steps_out = n_steps; a.status_dst = status_dst;
+  a.row_len = row_len;
+  ASTK_TRY(inference_run(PDEC_BEAM, d, prm, enc, h0, a, p.g, s));
+  BeamFinalArgs f;
+  memset(&f, 0, sizeof(f));
+  f.org = p.ORG; f.HT = p.g.HT; f.c_fin = c_fin; f.h_fin = h_fin; f.ht_fin = ht_fin;
+  f.B = d->B; f.H = d->H; f.A = d->A; f.nl = d->n_layers;
+  for (int l = 0; l < d->n_layers; ++l) { f.CS[l] = p.CS[l]; f.HR[l] = p.g.HR[l]; }
+  hipLaunchKernelGGL(k_beam_final_states, dim3(d->B), dim3(256), 0, s, f);
+  ASTK_LAUNCH_CHECK();
+  if (alpha) {
+    hipLaunchKernelGGL(k_alpha_normalise, dim3(a.S * a.B), dim3(256), 0, s, p.RAW, p.ML, alpha, row_len, a.B, a.T, a.Tp);
     ASTK_LAUNCH_CHECK();
   }
   return 0;

@@ -133,20 +133,11 @@ def decode_beam_batch(model, Xs, stop_limit, N, K):
         found, rows_s, rows_r = [], [], []
         for u in range(U):
             lst = []
-            for i in range(N):
-                r = u * N + i
-                if stt[r] == 0:
-                    break
-                toks, arow, j = [], [], i
-                for s in range(steps - 1, -1, -1):
-                    p, t, carried = (int(v) for v in H_[s, u * N + j, :3])
-                    if not carried:
-                        toks.append(t)
-                        arow.append(len(rows_s))
-                        rows_s.append(s)
-                        rows_r.append(u * N + j)
-                    j = p
-                lst.append((r, toks[::-1], arow[::-1]))
+            for i, toks, trace in backtrack_beam_history(H_[:, u * N:(u + 1) * N], stt[u * N:(u + 1) * N]):
+                arow = list(range(len(rows_s), len(rows_s) + len(trace)))
+                rows_s.extend(s for s, _, _ in trace)
+                rows_r.extend(u * N + j for _, j, _ in trace)
+                lst.append((u * N + i, toks, arow))
             found.append(lst)
         alphas = hist_alpha[torch.tensor(rows_s, dtype=torch.long, device=dev), torch.tensor(rows_r, dtype=torch.long, device=dev)].cpu().numpy() \
             if rows_s else np.zeros((0, Tmax), np.float32)
@@ -157,6 +148,156 @@ def decode_beam_batch(model, Xs, stop_limit, N, K):
                          "attn_v": ht[r:r + 1].clone(), "attn_history": [alphas[k, :lens[u]].copy() for k in arow]}
                         for r, toks, arow in lst])
         return out
+
+
+def backtrack_beam_history(hist, status):
+    """The hypotheses of ONE utterance from its history (include/astk.h astk_beam_state.hist): hist (steps, N, >= 3) int -- per step
+    and new slot its parent slot, token and carried flag -- and status (N) of the slots after the last step (0 = empty: the kept slots
+    come first).  Returns [(slot i, tokens, trace)] for every kept slot in order: its tokens without GO, and trace = [(step, slot,
+    parent slot)] of the expansions that produced them, in step order (a carried step adds no token).  The per-step search keeps an
+    expansion's attention row with its new slot, the device loop with its parent row.  Host only."""
+    import numpy as np
+    out = []
+    hist = np.asarray(hist).tolist()          # (plain ints: the walk below touches every step of every kept slot)
+    for i in range(len(status)):
+        if int(status[i]) == 0:
+            break
+        toks, trace, j = [], [], i
+        for s in range(len(hist) - 1, -1, -1):
+            p, t, carried = hist[s][j][:3]
+            if not carried:
+                toks.append(t)
+                trace.append((s, j, p))
+            j = p
+        out.append((i, toks[::-1], trace[::-1]))
+    return out
+
+
+def plan_beam_tiles(n_utts, N, max_rows=32):
+    """The rows of a device beam search (include/astk.h astk_beam_decode): the N slots of an utterance lie inside one 16-row tile, a tile
+    holds 16 // N utterances, a launch max_rows // 16 tiles.  Returns a list of launches, each (B, [(utterance, first row)]) with B =
+    the launch's row count (it ends with the last slot of its last utterance).  Host only."""
+    n_utts, N = int(n_utts), int(N)
+    from . import _lib
+    if not 1 <= N <= _lib.BEAM_MAX_N:
+        raise ValueError(f"plan_beam_tiles: N = {N} outside 1..{_lib.BEAM_MAX_N}: the slots of an utterance must fit one 16-row tile")
+    if n_utts < 0 or max_rows < 16 or max_rows % 16:
+        raise ValueError(f"plan_beam_tiles: {n_utts} utterances, max_rows = {max_rows} (a positive multiple of 16)")
+    per_tile = 16 // N
+    per_launch = per_tile * (max_rows // 16)
+    launches = []
+    for lo in range(0, n_utts, per_launch):
+        rows = [(u, 16 * ((u - lo) // per_tile) + N * ((u - lo) % per_tile)) for u in range(lo, min(n_utts, lo + per_launch))]
+        launches.append((rows[-1][1] + N, rows))
+    return launches
+
+
+def decode_beam_device(model, Xs, stop_limit, N, K):
+    """decode_beam_batch with the whole search of up to 32 rows in ONE persistent launch (include/astk.h astk_beam_decode): the same
+    return value -- keys, types and order.  Utterances are packed into launches by plan_beam_tiles; every launch's results come back
+    in one copy into one of two pinned buffers, read after the next launch has been enqueued.  Shapes the library does not run on
+    the device loop (its workspace query returns 0) go to decode_beam_batch; model.last_beam_path says which ran ("device" / "steps").
+    An utterance's hypotheses and score bits do not depend on the utterances it shares a launch with."""
+    import ctypes as C
+    import numpy as np
+    from . import _lib
+    from .seq2seq import _Pending, _vp
+    if not (1 <= N <= _lib.BEAM_MAX_N and 1 <= K <= _lib.BEAM_MAX_K):
+        raise ValueError(f"decode_beam_device: N = {N} and K = {K} must lie in 1..{_lib.BEAM_MAX_N} / 1..{_lib.BEAM_MAX_K} (use decode_beam)")
+    lib = model._require_gpu()
+    dev = model.device
+    GO, EOS = SYMBOLS.GO_ID, SYMBOLS.EOS_ID
+    stop = int(stop_limit)
+    with using_config("train", False):
+        seeds = []
+        encs, _, _ = model._encode_alone(Xs, seeds)
+        if stop <= 0:
+            model.last_beam_path = None          # (no search ran)
+            return [[_init_hyp_from(model, s)] for s in seeds]
+        nl, H, A = len(model.rnn_dec), model.H, model.A
+        lens = [int(e.shape[0]) for e in encs]
+        launches = plan_beam_tiles(len(Xs), N)
+        dp, _ = model._decoder_tables()
+
+        def desc(B, T2):
+            dd = model._decoder_desc(B, 2, T2)
+            dd.precision, dd.gemm_operands = _lib.PREC_BY_NAME[model.gemm_precision], _lib.OPERANDS_BY_NAME[model.gemm_operands]
+            dd.deterministic = 1 if model.deterministic else 0
+            return dd
+        # (a row's arithmetic does not depend on its launch: the kernel cuts every row's attention by the row's own length)
+        plans = []
+        for B, rows in launches:
+            T2 = max(lens[u] for u, _ in rows)
+            dd = desc(B, T2)
+            plans.append((B, rows, T2, dd, int(lib.astk_beam_decode_workspace_bytes(C.byref(dd), N, K, stop, 1))))
+        if any(p[4] == 0 for p in plans):
+            model.last_beam_path = "steps"
+            return decode_beam_batch(model, Xs, stop_limit, N, K)
+        model.last_beam_path, model.last_beam_steps = "device", []          # (the steps every launch ran: its n_steps)
+        f32 = dict(dtype=torch.float32, device=dev)
+        stream = torch.cuda.current_stream(dev)
+
+        def enqueue(k):
+            B, rows, T2, dd, nbytes = plans[k]
+            enc = torch.zeros(B, T2, H, **f32)
+            c0, h0 = torch.zeros(nl, B, H, **f32), torch.zeros(nl, B, H, **f32)
+            row_len = np.ones(B, dtype=np.int32)          # (padding rows attend over one zero position: finite, never live)
+            for u, r0 in rows:
+                enc[r0:r0 + N, :lens[u]] = encs[u]
+                row_len[r0:r0 + N] = lens[u]
+                sd = seeds[u]          # slot 0: the encoder's final states layer by layer (set_decoder_states(get_encoder_states()))
+                for l in range(min(nl, len(sd["c"]))):
+                    c0[l, r0] = sd["c"][l][0]
+                    h0[l, r0] = sd["h"][l][0]
+            row_len_dev = torch.from_numpy(row_len).to(dev)
+            # words: [n_steps, status word (float), 2 pad | hist (S, B, 4) | slot status (B) | score (B) float64 | c, h (nl, B, H) | ht (B, A)
+            #         | alpha (S, B, T2)]
+            o_hist, o_st = 4, 4 + stop * B * 4
+            o_sc = (o_st + B + 1) // 2 * 2
+            o_c = o_sc + 2 * B
+            o_h, o_ht = o_c + nl * B * H, o_c + 2 * nl * B * H
+            o_al = o_ht + B * A
+            n = o_al + stop * B * T2
+            ws = model._workspace("decode", nbytes)
+            out, host = model._readback("beam_device", k % 2, n, torch.int32)
+            base = out.data_ptr()
+            at = lambda w: C.c_void_p(base + 4 * w)
+            _lib.check(lib.astk_beam_decode(C.byref(dd), C.byref(dp), _vp(enc), _vp(c0), _vp(h0), _vp(row_len_dev), N, K, GO, EOS, stop, at(0),
+                                            at(1), at(o_hist), at(o_st), at(o_sc), at(o_c), at(o_h), at(o_ht), at(o_al), _vp(ws), ws.numel(),
+                                            C.c_void_p(stream.cuda_stream)))
+            host.copy_(out, non_blocking=True)
+            ev = torch.cuda.Event()
+            ev.record(stream)
+
+            def parse(v, _):
+                steps = int(v[0])
+                model.last_beam_steps.append(steps)
+                hist = v[o_hist:o_hist + stop * B * 4].reshape(stop, B, 4)[:steps]
+                stt, sc = v[o_st:o_st + B], v[o_sc:o_sc + 2 * B].view(np.float64)
+                alpha = v[o_al:o_al + stop * B * T2].view(np.float32).reshape(stop, B, T2)
+                # the final states stay on the device: one copy of the launch's (the buffer is reused two launches on), cut into rows
+                dev_f = out.view(torch.float32)[o_c:o_al].clone()
+                state = lambda o, r, w, l=0: dev_f[o - o_c + (l * B + r) * w:o - o_c + (l * B + r) * w + w].reshape(1, w)
+
+                def history(u, r0, trace):          # the alpha of every expansion, from the PARENT row of its step: one gather
+                    if not trace:
+                        return []
+                    return list(alpha[[s for s, _, _ in trace], [r0 + p for _, _, p in trace], :lens[u]])
+                res = []
+                for u, r0 in rows:
+                    res.append([{"hyp": [GO] + toks, "score": float(sc[r0 + i]),
+                                 "dec_state": {"c": [state(o_c, r0 + i, H, l) for l in range(nl)], "h": [state(o_h, r0 + i, H, l) for l in range(nl)]},
+                                 "attn_v": state(o_ht, r0 + i, A), "attn_history": history(u, r0, trace)}
+                                for i, toks, trace in backtrack_beam_history(hist[:, r0:r0 + N], stt[r0:r0 + N])])
+                return res
+            return _Pending(host, None, ev, status_at=1, where="decode_beam_device", parse=parse, keep=(enc, c0, h0, row_len_dev))
+        out_lists, pending = [], None
+        for k in range(len(plans) + 1):
+            cur = enqueue(k) if k < len(plans) else None
+            if pending is not None:
+                out_lists.extend(pending.result())
+            pending = cur
+        return out_lists
 
 
 def score_hypotheses(model, X, hyps, return_alpha=False):
@@ -485,6 +626,9 @@ class NN:
 
     def decode_beam_batch(self, Xs, stop_limit, N, K):
         return decode_beam_batch(self.model, Xs, stop_limit, N, K)
+
+    def decode_beam_device(self, Xs, stop_limit, N, K):
+        return decode_beam_device(self.model, Xs, stop_limit, N, K)
 
     def predict(self, set_key):
         preds = []

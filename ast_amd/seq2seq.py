@@ -415,6 +415,8 @@ class SpeechEncoderDecoder:
         self.mask_pad_id = None
         self._pinned = {}               # pinned read-back buffers of the decode modes, per (mode, slot) (_readback)
         self.last_score_path = None     # "device" (astk_forced_score) | "steps": which path the last score() took
+        self.last_beam_path = None      # "device" (astk_beam_decode) | "steps" (decode_beam_batch): which path the last decode_beam_device took
+        self.last_beam_steps = []       # ... and, on the device path, the steps each of its launches ran (n_steps)
         self.last_predict_path = None   # "device" (astk_greedy_decode) | "steps" (the per-step loop): which path the last predict() took
         # Arithmetic of the batched products, per model (-> the descriptors' `precision` / `gemm_operands` fields): None = the library's
         # process-wide default (bf16x3: exact f32 operands on the 16-bit matrix pipe); "bf16x3" | "f32" | "fp16x2" (narrower, opt-in);

@@ -1,9 +1,10 @@
 """beam.py drop-in (beam.py:46-146 of the reference):
-    python beam.py -m <cfg_dir> -n <N hyps kept> -k <K candidates per step> -s <set key> -w <length weight> [--resume] [-b U]
+    python beam.py -m <cfg_dir> -n <N hyps kept> -k <K candidates per step> -s <set key> -w <length weight> [--resume] [-b U] [--device]
 Beam search over one set with the newest checkpoint of the experiment, n-best lists pickled to
 <cfg_dir>/<set>_beam_N-<N>_K-<K>.p, the length-normalised best hypothesis of each utterance scored with corpus BLEU
 (ast_amd.eval) and written to <cfg_dir>/<set>_beam_N-<N>_K-<K>_W-<W>.en.  -b U decodes U utterances per batched search on the
-GPU (ast_amd.nn.decode_beam_batch): the same utterances and hypotheses, the same files."""
+GPU (ast_amd.nn.decode_beam_batch): the same utterances and hypotheses, the same files.  --device runs the whole search of a group
+of utterances (-b U of them, default 32) in persistent launches on the GPU (ast_amd.nn.decode_beam_device): the same files again."""
 import argparse
 import itertools
 import math
@@ -37,9 +38,12 @@ if __name__ == "__main__":
     parser.add_argument("-w", "--W", help="len normalization weight", required=True)
     parser.add_argument("--resume", action="store_true", help="re-score the saved beam results instead of decoding again")
     parser.add_argument("-b", "--batch", type=int, default=0, help="decode U utterances at once on the GPU (same hypotheses)")
+    parser.add_argument("--device", action="store_true", help="the whole search in persistent launches on the GPU (same hypotheses)")
     args = vars(parser.parse_args())
     cfg_path, N, K, W, set_key = args["cfg_path"], int(args["N"]), int(args["K"]), float(args["W"]), args["S"]
     U = args["batch"]
+    if args["device"] and U < 1:
+        U = 32
     if U >= 1 and not (N <= BEAM_MAX_N and K <= BEAM_MAX_K):
         print("-b {0:d}: N and K above {1:d} / {2:d} are decoded one utterance at a time".format(U, BEAM_MAX_N, BEAM_MAX_K))
         U = 0
@@ -66,7 +70,8 @@ if __name__ == "__main__":
                     if utt is not None:
                         group.append(utt)
                     if group and (utt is None or len(group) == U):
-                        lists = nn.decode_beam_batch([g["X"] for g in group], stop_limit=stop_limit, N=N, K=K)
+                        search = nn.decode_beam_device if args["device"] else nn.decode_beam_batch
+                        lists = search([g["X"] for g in group], stop_limit=stop_limit, N=N, K=K)
                         for g, n_best in zip(group, lists):
                             beam[g["utts"][0]] = [(e["hyp"], e["score"], e["attn_history"]) for e in n_best]
                         pbar.update(len(group))
@@ -76,6 +81,8 @@ if __name__ == "__main__":
                     n_best = nn.decode_beam(utt["X"], stop_limit=stop_limit, N=N, K=K)
                     beam[utt["utts"][0]] = [(e["hyp"], e["score"], e["attn_history"]) for e in n_best]
                     pbar.update(len(utt["X"]))
+        if args["device"] and U >= 1:
+            print("search path: {0:s}".format(str(nn.model.last_beam_path)))
         print("saving hyps")
         with open(beam_fname, "wb") as f:
             pickle.dump(beam, f)

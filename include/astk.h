@@ -539,6 +539,35 @@ int astk_beam_step(const astk_beam_desc* b, const astk_decoder_desc* d, const as
  * states c_new / h_new (n_layers, R, H) and ht_new (R, A) every row computed. */
 int astk_beam_select(const astk_beam_desc* b, int n_layers, int H, int A, const float* logits, const float* alpha, long ld_alpha,
                      const float* c_new, const float* h_new, const float* ht_new, const astk_beam_state* st, int step, void* stream);
+/* ---------------------------------------------------------------- beam search on the device  (the whole search in one launch)
+ * The search of astk_beam_step for up to 32 rows in ONE persistent launch (the persistent decoder loop in its beam mode, after a fill
+ * launch and the encA product, followed by one small launch that gathers the final states and, with alpha, one that normalises it).
+ * Row layout: every slot of every utterance is one row of d->B <= 32 rows.  The N slots of an utterance lie inside one 16-row batch
+ * tile: a tile holds 16 / N (integer division) utterances, utterance i of tile t in rows 16 t + i N .. 16 t + i N + N - 1; the tile's
+ * remaining rows are padding that is never live (6 utterances per launch at N = 5, 2 at N = 16).  d->B ends with the last slot of the
+ * last utterance.  enc is (B, T, H) -- every row holds its utterance's encoder states, as for the *_rows entry points -- and row_len
+ * (B, or NULL) its length; c0 / h0 (n_layers, B, H) seed slot 0 of every utterance (every other row: any finite values, e.g. zeros).
+ * At step 0 only slot 0 of an utterance is live and every row is fed `go`.  Selection is astk_beam_step's rule with two differences
+ * of arithmetic: the K best tokens of a row are ranked by the float32 logit (equal logits: lower id first), and logp = logit - LSE uses
+ * the float32 LSE of astk_greedy_decode_scored; scores accumulate in float64.  The loop stops after the step at which no utterance has
+ * a live slot (n_steps, as astk_greedy_decode; stop_limit otherwise).  Outputs, on the device:
+ *   n_steps, status_dst                   as for astk_greedy_decode
+ *   hist (stop_limit, B, 4)               astk_beam_state.hist's record of every row and step < n_steps; 16-byte aligned (checked)
+ *   slot_status (B), score (B) float64    of the slots after the last step; score 8-byte aligned (checked)
+ *   c_fin, h_fin (n_layers, B, H), ht_fin (B, A)   the state every slot's hypothesis was last expanded from (an empty slot: zeros)
+ *   alpha (stop_limit, B, d->T)           optional: alpha[s][r] is the attention row that ROW r computed at step s; the alpha of the
+ *                                         expansion recorded at hist[s][r] is that of its PARENT row, alpha[s][parent row].
+ *                                         Defined for s < n_steps only: the rows of steps the loop never ran hold no meaningful value
+ * Every row attends through PDEC_BEAM_NSPLIT = 8 slices cut by its OWN length, whatever d->B and d->T: the results of an utterance's
+ * rows are the same to the bit in every launch that holds them, next to whatever other utterances.
+ * astk_beam_decode_workspace_bytes returns 0 where astk_greedy_workspace_bytes does, and for N or K outside 1..16, K > V, a d->B
+ * that the layout above does not produce, or H = 512 with d->T > 480 (one attention kernel per H, see above); the caller then searches with astk_beam_step. */
+size_t astk_beam_decode_workspace_bytes(const astk_decoder_desc* d, int N, int K, int stop_limit, int with_alpha);
+int astk_beam_decode(const astk_decoder_desc* d, const astk_decoder_params* p, const float* enc, const float* c0, const float* h0,
+                     const int32_t* row_len, int N, int K, int go, int eos, int stop_limit, int32_t* n_steps, float* status_dst,
+                     int32_t* hist, int32_t* slot_status, double* score, float* c_fin, float* h_fin, float* ht_fin, float* alpha,
+                     void* ws, size_t ws_bytes, void* stream);
+
 /* The attention scan of astk_attn_step_fwd with per-row encoder slices: row r attends over enc[row_utt[r], 0:row_len[r]] of enc
  * (U, T, H); alpha (R, Tp) is 0 from row_len[r] on.  Workspace: astk_attn_workspace_bytes(R, T, H). */
 int astk_attn_step_fwd_rows(int R, int T, int H, const float* enc, const int32_t* row_utt, const int32_t* row_len, const float* q,
