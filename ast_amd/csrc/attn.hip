@@ -10,7 +10,7 @@
 // Algorithmic bytes per call = B*T*H*4.  Each wave reads whole 4H-byte rows with 16-byte
 // lane loads (1 KiB per instruction); workgroup b + B*split keeps the same batch row on the same XCD
 // (blockIdx % 8) across decoder steps, so enc_states (13 MB at cfg 2) is served from the XCD L2s after step 0.
-#include "common.h"
+#include "handoff.h"
 
 namespace astk {
 
@@ -23,8 +23,6 @@ constexpr int MAX_SPLIT = 128;
 // partials are stored write-through (sc1), every storing wave drains, the workgroup barriers, one lane takes a ticket on the
 // batch row's counter; the workgroup that draws the last ticket re-reads all partials with sc1 loads and finishes the row.
 // The counter is reset by the last arriver, so it is zero again for the next launch on the stream.
-__device__ __forceinline__ void st_sc1(float* p, float v) { __hip_atomic_store(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
-__device__ __forceinline__ float ld_sc1(const float* p) { return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
 __device__ __forceinline__ bool last_arriver(unsigned* cnt, int nsplit, int* s_flag) {
   asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
   __syncthreads();
@@ -36,12 +34,6 @@ __device__ __forceinline__ bool last_arriver(unsigned* cnt, int nsplit, int* s_f
   }
   __syncthreads();
   return *s_flag != 0;
-}
-
-__device__ __forceinline__ float wave_sum(float v) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o);
-  return v;
 }
 
 template <int NCH>

@@ -10,7 +10,8 @@ SRCS="util gemm rowgemm attn conv norm lstm lstm_persist decoder decoder_persist
 HOOKED="gemm conv lstm_persist decoder_persist"        # the translation units with #ifdef ASTK_TEST_HOOKS sections
 mkdir -p ../_obj ../_obj/test
 pids=()
-stale() { [ ! -f $2 ] || [ $1.hip -nt $2 ] || [ common.h -nt $2 ] || [ decoder_wide.h -nt $2 ] || [ ../../include/astk.h -nt $2 ]; }
+# an object is stale when its source, ANY header here or the public header is newer: the headers hold the structs two translation units share
+stale() { [ ! -f $2 ] && return 0; for h in $1.hip *.h ../../include/astk.h; do [ $h -nt $2 ] && return 0; done; return 1; }
 for f in $SRCS; do
   if stale $f ../_obj/$f.o; then hipcc $FLAGS -c $f.hip -o ../_obj/$f.o & pids+=($!); fi
 done

@@ -113,6 +113,12 @@ static inline __host__ __device__ unsigned long long* amax_shard(const unsigned 
 
 typedef float f32x4 __attribute__((ext_vector_type(4)));
 typedef float f32x16 __attribute__((ext_vector_type(16)));
+// sum over the 64 lanes of a wave, in every lane
+__device__ __forceinline__ float wave_sum(float v) {
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o);
+  return v;
+}
 
 // ---- fp16x2 products (device side; gemm.hip describes the scheme): an f32 value times a power-of-two scale is split into two fp16
 // terms, x s = hi + lo, and a product is summed from lo.hi + hi.lo + hi.hi on the fp16 MFMAs with f32 accumulation.

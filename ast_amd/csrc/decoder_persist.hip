@@ -24,19 +24,13 @@
 // (ctx / logits owners), so that no workgroup holds more than 68 float4 (272 VGPRs) of weights.
 // Applicability (else the per-launch path of decoder.hip runs): 1-3 decoder layers, H,A multiples of 16, sizes within the
 // register budgets below, grid of 256 workgroups fully resident.  All spins are bounded (abort word).
-#include "common.h"
+#include "decoder_persist.h"
+#include "handoff.h"
 #include <initializer_list>
 #include <type_traits>
 
 // -DASTK_PDEC_TIMING_ALL=1: the per-phase timers of ASTK_PERSIST_DBG in the multi-layer variants too (16 more registers per lane there)
 // (the timers exist only in the test-hook build, libastk_test.so: the product library's kernels see dbg = 0 as a constant)
-#ifdef ASTK_TEST_HOOKS
-static int persist_dbg_env() { const char* e = getenv("ASTK_PERSIST_DBG"); return e ? atoi(e) : 0; }
-#define PERSIST_DBG(a) ((a).dbg)
-#else
-static int persist_dbg_env() { return 0; }
-#define PERSIST_DBG(a) 0
-#endif
 #ifndef ASTK_PDEC_TIMING_ALL
 #define ASTK_PDEC_TIMING_ALL 0
 #endif
@@ -44,29 +38,19 @@ namespace astk {
 
 namespace {
 
-constexpr int CTRS = 64;          // counter stride in words (256 B)
 constexpr int G = 256;            // workgroups (one per CU)
 enum Phase { PH_CELL = 0 /* + layer: 0..2 */, PH_CELL1, PH_CELL2, PH_CMB, PH_CTX, PH_LOG, PH_CE, PH_N };
-constexpr int PDEC_MAX_LAYERS = 3;
 // Specialised attention phase (H = 512): at most this many rows of a (batch row, time chunk) slice stay resident in LDS (2 x 28 x 2 KB =
 // 112 KB of enc + encA); a chunk's remaining rows (chunks of up to 60 rows: T'' <= 480 at batch 32, i.e. the loader's longest
 // utterances of 1680 frames) are streamed from L2 / Infinity Cache every step -- they are the same bytes for every step of the loop.
 constexpr int PDEC_RES_ROWS = 28, PDEC_CHUNK_MAX = 60;
 constexpr int PDEC_BEAM_NSPLIT = 8;     // beam mode: attention slices per row, whatever the launch's row count (G / 32 rows)
 constexpr int NPHASE_SLOTS = 8;   // counter lines reserved per batch tile ahead of the abort word and the per-row counters
-// ... and the hand-off between decoder LAYERS the same way (round 5, ASTK_PDEC_SENT_HD=1): HD[l] -- the dropped output of layer l, one slot per
-// step, read by nobody but the cells of layer l + 1 -- sentinel-filled before the launch and polled itself by the waves that multiply it.
-// MEASURED AND OFF: es_en_20h (3 layers) 6.79 -> 6.83 ms in a same-box A/B -- 4 waves x 128 workgroups re-reading 8 KB each per poll cost the
-// chain more than the drain + counter they replace (the top cell's hand-off to the attention scan polls 2 KB per workgroup, once).
-#ifndef ASTK_PDEC_SENT_HD
-#define ASTK_PDEC_SENT_HD 0
-#endif
-#ifndef ASTK_PDEC_SENT_H
-#define ASTK_PDEC_SENT_H 1
-#endif
+// The top cell's hand-off to the attention scan is of the sentinel kind: the h half of CVH is filled with this word before the launch and
+// polled itself (2 KB per workgroup, once).  (Rejected: the same between decoder LAYERS, HD[l] sentinel-filled and polled by the waves that
+// multiply it -- es_en_20h, 3 layers, 6.79 -> 6.83 ms in a same-box A/B: 4 waves x 128 workgroups re-reading 8 KB each per poll cost the
+// chain more than the drain + counter they replace.)
 constexpr unsigned PDEC_SENTINEL = 0xffffffffu;
-
-typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
 
 struct PDecArgs {
   int B, S, L, T, Tp, H, E, A, V, Vp, XI, nbt, nsplit, chunk, ntile_v;
@@ -116,9 +100,6 @@ struct PDecArgs {
   float* CS[PDEC_MAX_LAYERS];   // [S + 1][B][H] c of every step (slot s + 1 = after step s): the final states are gathered behind the loop
 };
 
-__device__ __forceinline__ unsigned ld_flag(const unsigned* p) { return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
-__device__ __forceinline__ void st_sc1(float* p, float v) { __hip_atomic_store(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
-__device__ __forceinline__ void sti_sc1(int* p, int v) { __hip_atomic_store(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
 // A UNIFORM base pointer, re-formed where it is used (opaque to loop-invariant code motion).  An element address is then base (scalar
 // registers) + one 32-bit lane offset shared by all arrays of the same shape, instead of a hoisted 64-bit per-lane pointer per array: in the
 // multi-layer kernels (512 registers, the weights resident) ~30 such pointers were spilled, and a scratch reload between two written-through
@@ -139,103 +120,7 @@ __device__ __forceinline__ T* ua(T* base, unsigned i) {
 __device__ __forceinline__ void st_sc1_u(float* base, unsigned i, float v) {
   asm volatile("global_store_dword %0, %1, %2 sc1" ::"v"(i * 4u), "v"(v), "s"(base) : "memory");
 }
-__device__ __forceinline__ float ld_sc1(const float* p) { return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
-__device__ __forceinline__ int ldi_sc1(const int* p) { return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
-__device__ __forceinline__ __amdgpu_buffer_rsrc_t make_rsrc(const void* p) {
-  return __builtin_amdgcn_make_buffer_rsrc(const_cast<void*>(p), 0, 0x7fffffff, 0x00020000);
-}
-__device__ __forceinline__ float4 ldb128_sc1(__amdgpu_buffer_rsrc_t r, long float_off) {
-  const u32x4 v = __builtin_amdgcn_raw_buffer_load_b128(r, (int)(float_off * 4), 0, 16);
-  return make_float4(__uint_as_float(v.x), __uint_as_float(v.y), __uint_as_float(v.z), __uint_as_float(v.w));
-}
-// Greedy decoding's stop (decoder_persist_fwd<.., GR = true>): `word` holds n_steps once every row has emitted EOS (stop_limit until
-// then).  A wait made for decoder step `step` gives up, without raising the abort word, once step >= n_steps: its producer may have left.
-// A wait for a step below n_steps never leaves on it -- every producer finishes all steps below n_steps before it leaves.  The training
-// kernels pass no word (the check folds away).  `recheck`: look once more after the counter is satisfied (the layer-0 cells' wait on
-// their own tile's P6, which writes the word in front of that arrival).
-struct StopCtl { const unsigned* word; int step; bool recheck; };
-__device__ __forceinline__ bool stop_seen(const StopCtl& st) { return st.word && (unsigned)st.step >= ld_flag(st.word); }
-__device__ __forceinline__ bool wait_ge(const unsigned* ctr, unsigned target, const AbortCtl& ab, const StopCtl& st = StopCtl{nullptr, 0, false}) {
-  unsigned spins = 0;
-  while (ld_flag(ctr) < target) {
-    if (++spins > ab.limit) {
-      abort_raise(ab);
-      return false;
-    }
-    if ((spins & 63u) == 0 && (abort_seen(ab) || stop_seen(st))) return false;
-  }
-  return true;
-}
-// workgroup-wide wait: lane 0 polls, everyone learns the outcome
-__device__ __forceinline__ bool wg_wait(const unsigned* ctr, unsigned target, const AbortCtl& ab, int* s_flag,
-                                        const StopCtl& st = StopCtl{nullptr, 0, false}) {
-  if (threadIdx.x == 0) *s_flag = wait_ge(ctr, target, ab, st) ? 1 : 0;
-  __syncthreads();
-  const bool ok = *s_flag != 0;
-  __syncthreads();            // s_flag may be rewritten by the next wait
-  return ok;
-}
-// workgroup-wide wait on `count` (<= 64) counters `stride` words apart: lane i of wave 0 polls counter i
-__device__ __forceinline__ bool wg_wait_multi(const unsigned* base, int stride, int count, unsigned target, const AbortCtl& ab, int* s_flag,
-                                              const StopCtl& st = StopCtl{nullptr, 0, false}) {
-  if (threadIdx.x < 64) {
-    const int lane = threadIdx.x;
-    bool ok = true;
-    unsigned spins = 0;
-    for (;;) {
-      const bool mine = lane < count ? ld_flag(base + (long)lane * stride) >= target : true;
-      if (__all(mine)) break;
-      if (++spins > ab.limit) { abort_raise(ab); ok = false; break; }
-      if ((spins & 63u) == 0 && (abort_seen(ab) || stop_seen(st))) { ok = false; break; }
-    }
-    if (lane == 0) *s_flag = ok ? 1 : 0;
-  }
-  __syncthreads();
-  const bool ok = *s_flag != 0;
-  __syncthreads();
-  return ok;
-}
-// Sharded phase counters: the items of a (phase, batch tile) bump one of NSH words (item % NSH), each on its own 256-byte line, and a
-// waiter polls the NSH words with NSH lanes of one wave.  Same-address atomics retire one after the other (~12 ns each in isolation,
-// far more under load): with 32-128 arrivals per hand-off on ONE word the decoder kernels ran 1.00 / 1.00 ms; 4 / 8 / 16 / 32 / 64 words:
-// 0.84/0.82, 0.80/0.78, 0.79/0.75, 0.78/0.73, 0.78/0.75 ms (forward / backward).
-constexpr int NSH = 32;
-__device__ __forceinline__ bool wg_wait_sh(const unsigned* base, int n_items, int steps, const AbortCtl& ab, int* s_flag,
-                                           const StopCtl& st = StopCtl{nullptr, 0, false}) {
-  if (threadIdx.x < 64) {
-    const int lane = threadIdx.x;
-    const unsigned target = lane < NSH ? (unsigned)(((n_items - lane + NSH - 1) / NSH) * steps) : 0u;   // items with idx % NSH == lane
-    bool ok = true;
-    unsigned spins = 0;
-    for (;;) {
-      const bool mine = (lane < NSH && target > 0) ? ld_flag(base + lane * CTRS) >= target : true;
-      if (__all(mine)) break;
-      if (++spins > ab.limit) { abort_raise(ab); ok = false; break; }
-      if ((spins & 63u) == 0 && (abort_seen(ab) || stop_seen(st))) { ok = false; break; }
-    }
-    if (ok && st.recheck && lane == 0 && stop_seen(st)) ok = false;
-    if (lane == 0) *s_flag = ok ? 1 : 0;
-  }
-  __syncthreads();
-  const bool ok = *s_flag != 0;
-  __syncthreads();
-  return ok;
-}
-__device__ __forceinline__ void publish(unsigned* ctr) {
-  asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-  __syncthreads();
-  if (threadIdx.x == 0) __hip_atomic_fetch_add(ctr, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-}
-__device__ __forceinline__ void publish_sh(unsigned* base, int item) { publish(base + (item & (NSH - 1)) * CTRS); }
 __device__ __forceinline__ float sigm(float x) { return 1.f / (1.f + expf(-x)); }
-// gate / tanh activations on the decoder chain: v_exp_f32 / v_rcp_f32 based (absolute error <= ~2e-7), as in lstm_persist.hip
-__device__ __forceinline__ float sigm_fast(float x) { return __builtin_amdgcn_rcpf(1.f + __expf(-x)); }
-__device__ __forceinline__ float tanh_fast(float x) { return 2.f * __builtin_amdgcn_rcpf(1.f + __expf(-2.f * x)) - 1.f; }
-__device__ __forceinline__ float wave_sum(float v) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o);
-  return v;
-}
 
 // Resident weight fragments (NB k-blocks of 16 floats per wave): MFMA column j = lane&15 -> W row `row`.
 template <int NB>
@@ -258,7 +143,7 @@ __device__ __forceinline__ void aload_sc1(float4* a, __amdgpu_buffer_rsrc_t ra, 
     const int vo = (int)((a_off + kb) * 4);
 #pragma unroll
     for (int i = 0; i < NB; ++i) {
-      const u32x4 v = __builtin_amdgcn_raw_buffer_load_b128(ra, vo + 256 * i, 0, AUX);
+      const u32q v = __builtin_amdgcn_raw_buffer_load_b128(ra, vo + 256 * i, 0, AUX);
       a[i] = make_float4(__uint_as_float(v.x), __uint_as_float(v.y), __uint_as_float(v.z), __uint_as_float(v.w));
     }
   } else {
@@ -266,7 +151,7 @@ __device__ __forceinline__ void aload_sc1(float4* a, __amdgpu_buffer_rsrc_t ra, 
     asm volatile("" : "+v"(kbv));      // (opaque: the NB clamped offsets are formed here, not hoisted out of the step loop as NB live registers)
 #pragma unroll
     for (int i = 0; i < NB; ++i) {
-      const u32x4 v = __builtin_amdgcn_raw_buffer_load_b128(ra, (int)((a_off + min(kbv + 64 * i, K - 4)) * 4), 0, AUX);
+      const u32q v = __builtin_amdgcn_raw_buffer_load_b128(ra, (int)((a_off + min(kbv + 64 * i, K - 4)) * 4), 0, AUX);
       a[i] = make_float4(__uint_as_float(v.x), __uint_as_float(v.y), __uint_as_float(v.z), __uint_as_float(v.w));
     }
   }
@@ -993,37 +878,10 @@ __device__ __forceinline__ void decoder_persist_fwd_body(const PDecArgs& a) {
           mfma_blocks<NB_H>(acc[0], ah, wreg + OFF_C2 + NB_H);
           mfma_blocks<NB_H>(acc[1], ah, wreg + OFF_C2 + CELLW2 + NB_H);
         }
-#if !(ASTK_PDEC_SENT_HD && ASTK_PDEC_SENT_H)
         if (!wg_wait_sh(CTR(PH_CELL + l - 1, bt), H / 8, s + 1, a.ab, &s_flag, sc)) return;
-#endif
         {
           float4 ax[NB_H];
-#if ASTK_PDEC_SENT_HD && ASTK_PDEC_SENT_H
-          // the data is the flag: every wave re-reads ITS fragments of the 16 rows until none of them holds the sentinel -- no drain,
-          // counter, counter poll or barrier between the lower cell's stores and this product
-          {
-            const __amdgpu_buffer_rsrc_t r_hd = make_rsrc(a.HD[l - 1]);
-            unsigned spins = 0;
-            for (;;) {
-              aload_sc1<NB_H>(ax, r_hd, ((long)s * B + brow) * H, H, lane, wave);
-              bool ok = true;
-#pragma unroll
-              for (int i = 0; i < NB_H; ++i)
-                ok = ok & (__float_as_uint(ax[i].x) != PDEC_SENTINEL) & (__float_as_uint(ax[i].y) != PDEC_SENTINEL) &
-                     (__float_as_uint(ax[i].z) != PDEC_SENTINEL) & (__float_as_uint(ax[i].w) != PDEC_SENTINEL);
-              if (__all(ok) || att_dead) break;
-              if (++spins > (a.ab.limit >> 1)) { abort_raise(a.ab); att_dead = true; }
-              else if ((spins & 63u) == 0 && abort_seen(a.ab)) att_dead = true;
-              else if ((spins & 63u) == 0 && __any(stop_seen(sc))) { if (lane == 0) s_stop = 1; break; }
-            }
-          }
-          if constexpr (STOP) {     // (a stop: the whole workgroup leaves, after the barrier that shows every wave's verdict)
-            __syncthreads();
-            if (s_stop) return;
-          }
-#else
           aload_sc1<NB_H>(ax, make_rsrc(a.HD[l - 1]), ((long)s * B + brow) * H, H, lane, wave);  // dropped output of the layer below
-#endif
           __builtin_amdgcn_sched_barrier(0);
           mfma_blocks<NB_H>(acc[0], ax, wreg + OFF_C2);
           mfma_blocks<NB_H>(acc[1], ax, wreg + OFF_C2 + CELLW2);
@@ -1066,12 +924,12 @@ __device__ __forceinline__ void decoder_persist_fwd_body(const PDecArgs& a) {
       float* hS = scr;                 // [H]
       float* scS = scr + H;            // [c4] raw scores (tail padded with -inf)
       float* pS = scr + H + c4;        // [c4] exp(score - m) (tail 0)
-#if ASTK_PDEC_SENT_H
       // The data is the flag (lstm_persist.hip): the h half of CVH is sentinel-filled before the launch and this row's 2 KB are polled
-      // themselves -- no drain, counter, counter poll or barrier between the top cell's stores and the scan.
+      // themselves -- no drain, counter, counter poll or barrier between the top cell's stores and the scan.  (Rejected: waiting on the top
+      // cell's counter here, then one sc1 load -- 0.6 us more per decoder step, 1.55 against 1.53 ms per train step in an A/B inside one call.)
       if (tid < H / 4) {
         const int off = (int)((((long)s * B + b) * 2 * H + H + 4 * tid) * 4);
-        u32x4 v;
+        u32q v;
         unsigned spins = 0;
         for (;;) {
           v = __builtin_amdgcn_raw_buffer_load_b128(r_cvh, off, 0, 16);
@@ -1084,12 +942,6 @@ __device__ __forceinline__ void decoder_persist_fwd_body(const PDecArgs& a) {
       }
       TICK(4)
       const long long ta0 = a.tick_out ? wall_clock64() : 0;
-#else
-      if (!wg_wait_sh(CTR(PH_CELL + TOP, bt), H / 8, s + 1, a.ab, &s_flag, sc)) return;
-      TICK(4)
-      const long long ta0 = a.tick_out ? wall_clock64() : 0;
-      if (tid < H / 4) *reinterpret_cast<float4*>(hS + 4 * tid) = ldb128_sc1(r_cvh, ((long)s * B + b) * 2 * H + H + 4 * tid);
-#endif
       float m, l = 0.f, my_score;
       float* prow = a.PART + (((long)s * B + b) * a.nsplit + att_sp) * (H + 4);
       if constexpr (NC > 0) {
@@ -1217,7 +1069,7 @@ __device__ __forceinline__ void decoder_persist_fwd_body(const PDecArgs& a) {
               const float4 o = fold[(k - 1) * (16 * NC) + cq];
               acc4.x += o.x; acc4.y += o.y; acc4.z += o.z; acc4.w += o.w;
             }
-            u32x4 u;
+            u32q u;
             u.x = __float_as_uint(acc4.x); u.y = __float_as_uint(acc4.y); u.z = __float_as_uint(acc4.z); u.w = __float_as_uint(acc4.w);
             __builtin_amdgcn_raw_buffer_store_b128(u, r_part, (int)((prow - a.PART + 4 + 4 * cq) * 4), 0, 16);
           }
@@ -1347,7 +1199,7 @@ __device__ __forceinline__ void decoder_persist_fwd_body(const PDecArgs& a) {
         }
       }
       if (tid < H / 4) {
-        u32x4 u;
+        u32q u;
         u.x = __float_as_uint(acc4.x * inv); u.y = __float_as_uint(acc4.y * inv); u.z = __float_as_uint(acc4.z * inv); u.w = __float_as_uint(acc4.w * inv);
         __builtin_amdgcn_raw_buffer_store_b128(u, r_cvh, (int)((((long)s * B + b) * 2 * H + 4 * tid) * 4), 0, 16);
       }
@@ -2023,7 +1875,7 @@ __global__ __launch_bounds__(256, 1) void decoder_persist_bwd(PDecBwdArgs a) {
               const float4 o = fold[(k - 1) * (16 * NC) + cq];
               acc4.x += o.x; acc4.y += o.y; acc4.z += o.z; acc4.w += o.w;
             }
-            u32x4 u;
+            u32q u;
             u.x = __float_as_uint(acc4.x); u.y = __float_as_uint(acc4.y); u.z = __float_as_uint(acc4.z); u.w = __float_as_uint(acc4.w);
             __builtin_amdgcn_raw_buffer_store_b128(u, r_dha, (int)(((((long)s * B + b) * a.nsplit + att_sp) * HH + 4 * cq) * 4), 0, 16);
           }
@@ -2150,7 +2002,7 @@ __global__ __launch_bounds__(256, 1) void decoder_persist_bwd(PDecBwdArgs a) {
         const float dh = v + dy * mk;
         const float tc = tanh_fast(ccur);
         const float dcv = dh * g.w * (1.f - tc * tc) + dc_state;
-        u32x4 o;
+        u32q o;
         o.x = __float_as_uint(dcv * g.y * (1.f - g.x * g.x)); o.y = __float_as_uint(dcv * g.x * g.y * (1.f - g.y));
         o.z = __float_as_uint(dcv * cp * g.z * (1.f - g.z)); o.w = __float_as_uint(dh * tc * g.w * (1.f - g.w));
         __builtin_amdgcn_raw_buffer_store_b128(o, r_g, (int)((((long)s * B + row) * K4 + 4 * u) * 4), 0, 16);
@@ -2248,18 +2100,6 @@ __global__ __launch_bounds__(256) void k_decoder_post(const float* __restrict__ 
 
 }  // namespace
 
-struct DecPersistBuffers {
-  int32_t *TOK, *PRED;
-  float *X0, *Q, *ALPHA, *CVH, *HT, *LOGITS, *LOSSROWS;
-  float *G[PDEC_MAX_LAYERS], *C[PDEC_MAX_LAYERS], *HR[PDEC_MAX_LAYERS], *HD[PDEC_MAX_LAYERS];
-  float *LSE, *PART, *CESTAT, *ENCA, *ML;
-  unsigned* ctr;
-  // two small buffers the forward launcher zeroes with its own fill launch (HT of step -1 and the first concat row: decoder.hip)
-  void* zero_a; size_t zero_a_bytes; void* zero_b; size_t zero_b_bytes;
-  // ... and the initial states (n_layers, B, H) it copies into C[l] / HR[l] with the same launch (nullptr: the caller copied them)
-  const float *c0, *h0;
-};
-
 static bool pdec_special(int H, int chunk) { return H == 512 && chunk <= PDEC_CHUNK_MAX; }     // the NC = 8 attention phase
 static int pdec_res_rows(int H, int chunk) { return pdec_special(H, chunk) && chunk > PDEC_RES_ROWS ? PDEC_RES_ROWS : chunk; }
 static size_t pdec_lds_floats(int chunk, int H, int nsplit) {
@@ -2324,17 +2164,6 @@ bool decoder_persist_b6_split(const astk_decoder_desc* d) {
   if (!tune_on(TUNE_DEC_B6_SPLIT)) return false;
   return n5 + n6 + (n1 > n2 ? n1 : n2) <= G;
 }
-
-struct DecPersistBwdBuffers {
-  void* zero_ptr; size_t zero_bytes;      // astk_decoder_desc.zero_ptr: zeroed by the launcher's fill launch
-  void* zero2_ptr; size_t zero2_bytes;    // d_enc: zeroed there too, its two batched products then ADD into it from one grouped launch
-  const float *WoT, *WcT, *ENCA, *CVH, *HT, *LOGITS, *ML;
-  const float *WlT[PDEC_MAX_LAYERS], *WuT[PDEC_MAX_LAYERS], *C[PDEC_MAX_LAYERS];
-  float *G[PDEC_MAX_LAYERS];
-  float *ALPHA, *DPRE, *DCVH, *DS, *DX0, *DHATT, *d_c0;
-  float* DXH;        // [2][S][B][A] or null (no K split of the d_x0 phase)
-  unsigned* ctr;
-};
 
 // The one launcher of the persistent decoder kernels.  pick(nc, nl, xs) names the instantiation <NC, NL, XS> of one kernel template (its
 // arguments are std::integral_constant values); the shape selects among the three of a layer count: generic, NC = 8, NC = 8 streamed.
@@ -2434,15 +2263,12 @@ int decoder_persist_fwd_launch(const astk_decoder_desc* d, const astk_decoder_pa
   a.ab = abort_ctl(bf.ctr + (size_t)NPHASE_SLOTS * NSH * a.nbt * CTRS, PERSIST_DEC_FWD);
   a.dbg = persist_dbg_env();
   a.tick_out = prof_tick_buffer(0);
-#if ASTK_PDEC_SENT_H
+  // (one fill launch, not hipMemsetAsync calls: the counters zeroed, the h half of CVH sentinel-filled, the initial states copied)
   {
     FillSegs f;
     f.n = 0;
     fill_seg_add(f, bf.ctr, ((size_t)NPHASE_SLOTS * NSH * a.nbt + 2 + a.B) * CTRS * sizeof(unsigned), 0u);
     fill_seg_add(f, bf.CVH, (size_t)a.S * a.B * 2 * a.H * sizeof(float));
-#if ASTK_PDEC_SENT_HD
-    for (int l = 0; l + 1 < d->n_layers; ++l) fill_seg_add(f, bf.HD[l], (size_t)a.S * a.B * a.H * sizeof(float));      // (the launch's value: the sentinel)
-#endif
     if (bf.zero_a) fill_seg_add(f, bf.zero_a, bf.zero_a_bytes, 0u);
     if (bf.zero_b) fill_seg_add(f, bf.zero_b, bf.zero_b_bytes, 0u);
     if (bf.c0 && bf.h0) {
@@ -2455,21 +2281,6 @@ int decoder_persist_fwd_launch(const astk_decoder_desc* d, const astk_decoder_pa
     }
     ASTK_TRY(fill_u32_segments(f, PDEC_SENTINEL, s));
   }
-#else
-  if (bf.c0 && bf.h0) {
-    CopySegs cp;
-    cp.n = 0;
-    const size_t bh = (size_t)d->B * d->H;
-    for (int l = 0; l < d->n_layers; ++l) {
-      copy_seg_add(cp, bf.C[l], bf.c0 + l * bh, bh * sizeof(float));
-      copy_seg_add(cp, bf.HR[l], bf.h0 + l * bh, bh * sizeof(float));
-    }
-    ASTK_TRY(copy_segments(cp, s));
-  }
-  ASTK_HIP(hipMemsetAsync(bf.ctr, 0, ((size_t)NPHASE_SLOTS * NSH * a.nbt + 2 + a.B) * CTRS * sizeof(unsigned), s));
-  if (bf.zero_a) ASTK_HIP(hipMemsetAsync(bf.zero_a, 0, bf.zero_a_bytes, s));
-  if (bf.zero_b) ASTK_HIP(hipMemsetAsync(bf.zero_b, 0, bf.zero_b_bytes, s));
-#endif
   const size_t shm = pdec_lds_floats(chunk, a.H, nsplit) * sizeof(float);
   {
     ProfScope prof(PROF_DEC_FWD, s);
@@ -2566,12 +2377,7 @@ static int inference_run(PDecMode mode, const astk_decoder_desc* d, const astk_d
   f.n = 0;
   fill_seg_add(f, g.ctr, (greedy_ctr_lines(d->B) - 1) * CTRS * sizeof(unsigned), 0u);
   fill_seg_add(f, a.gctl + 3 * CTRS, CTRS * sizeof(unsigned), (unsigned)a.S);
-#if ASTK_PDEC_SENT_H
   fill_seg_add(f, g.CVH, (size_t)a.S * a.B * 2 * a.H * sizeof(float));
-#endif
-#if ASTK_PDEC_SENT_HD && ASTK_PDEC_SENT_H
-  for (int l = 0; l + 1 < d->n_layers; ++l) fill_seg_add(f, g.HD[l], (size_t)a.S * bh * sizeof(float));
-#endif
   for (int l = 0; l < d->n_layers; ++l) fill_seg_add_copy(f, g.HR[l], h0 + l * bh, bh * sizeof(float));
   ASTK_TRY(fill_u32_segments(f, PDEC_SENTINEL, s));
   const size_t shm = pdec_lds_floats(g.chunk, a.H, g.nsplit) * sizeof(float);

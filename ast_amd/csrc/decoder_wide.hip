@@ -17,6 +17,7 @@
 // add on a sharded counter; consumers poll, then sc1 loads).  The h part of the next cell product needs only CELL, so it runs while CTX is in
 // flight.  Saved state = decoder.hip's DecPlan, so its per-launch backward runs on it unchanged.  All spins are bounded (abort word).
 #include "decoder_wide.h"
+#include "handoff.h"
 
 namespace astk {
 
@@ -24,14 +25,10 @@ namespace {
 
 constexpr int WH = 1024, WA = 1024, WE = 128, WXI = WE + WA;
 constexpr int WG_ = 256;              // workgroups (one per CU)
-constexpr int CTRS = 64;              // counter stride in words (256 B)
-constexpr int NSH = 32;               // shards of a phase counter
 constexpr int Q0 = 64, CTX0 = 128, CMB0 = 192;   // first workgroup of the Q / CTX / CMB roles
 constexpr int NQ = WH / 16, NCTX = WA / 16;
 enum { C_CELL = 0, C_Q, C_CMB, C_CTX, C_LOG, C_ARG, C_N };
 constexpr int PARTW = WH + 4;
-
-typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
 
 struct WideArgs {
   int B, S, L, T, Tp, V, s0, s1, nsplit, chunk;
@@ -48,81 +45,10 @@ struct WideArgs {
   AbortCtl ab;
 };
 
-__device__ __forceinline__ unsigned ld_flag(const unsigned* p) { return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
-__device__ __forceinline__ void st_sc1(float* p, float v) { __hip_atomic_store(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
-__device__ __forceinline__ float ld_sc1(const float* p) { return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
-__device__ __forceinline__ int ldi_sc1(const int* p) { return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
-__device__ __forceinline__ void sti_sc1(int* p, int v) { __hip_atomic_store(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
-__device__ __forceinline__ __amdgpu_buffer_rsrc_t make_rsrc(const void* p) {
-  return __builtin_amdgcn_make_buffer_rsrc(const_cast<void*>(p), 0, 0x7fffffff, 0x00020000);
-}
-// Handed-off activations are read by every workgroup of an XCD (the 32 rows x 1024 columns of h, ht, [cv; h]: 128-256 KB per workgroup
-// and step).  ASTK_WIDE_SC1 = 1 (default): sc1 loads (every load goes to the memory side, as in decoder_persist.hip); 0: an agent-scope
-// acquire behind every successful wait (invalidates the XCD's L2 copies of such lines) and ordinary loads, so that the 32 workgroups of an
-// XCD share one fetch of each line -- measured: the ten L2 invalidations per step cost more than the shared fetches save (configs[4] shape:
-// 18.7 ms per train step against 17.9 with sc1 loads; 18.7 on the per-launch loop).
-#ifndef ASTK_WIDE_SC1
-#define ASTK_WIDE_SC1 1
-#endif
-__device__ __forceinline__ float4 ldb128_sc1(__amdgpu_buffer_rsrc_t r, long float_off) {
-  const u32x4 v = __builtin_amdgcn_raw_buffer_load_b128(r, (int)(float_off * 4), 0, ASTK_WIDE_SC1 ? 16 : 0);
-  return make_float4(__uint_as_float(v.x), __uint_as_float(v.y), __uint_as_float(v.z), __uint_as_float(v.w));
-}
-__device__ __forceinline__ void acquire_handoff() {
-#if !ASTK_WIDE_SC1
-  __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
-#endif
-}
-// lanes 0..NSH-1 of wave 0 poll the shards of a phase counter until `n_items` items have arrived `steps` times each
-__device__ __forceinline__ bool wait_sh(const unsigned* base, int n_items, int steps, const AbortCtl& ab, int* s_flag) {
-  if (threadIdx.x < 64) {
-    const int lane = threadIdx.x;
-    const unsigned target = lane < NSH ? (unsigned)(((n_items - lane + NSH - 1) / NSH) * steps) : 0u;
-    bool ok = true;
-    unsigned spins = 0;
-    for (;;) {
-      const bool mine = (lane < NSH && target > 0) ? ld_flag(base + lane * CTRS) >= target : true;
-      if (__all(mine)) break;
-      if (++spins > ab.limit) { abort_raise(ab); ok = false; break; }
-      if ((spins & 63u) == 0 && abort_seen(ab)) { ok = false; break; }
-    }
-    if (lane == 0) *s_flag = ok ? 1 : 0;
-  }
-  __syncthreads();
-  const bool ok = *s_flag != 0;
-  __syncthreads();
-  acquire_handoff();
-  return ok;
-}
-__device__ __forceinline__ bool wait_one(const unsigned* ctr, unsigned target, const AbortCtl& ab, int* s_flag) {
-  if (threadIdx.x == 0) {
-    bool ok = true;
-    unsigned spins = 0;
-    while (ld_flag(ctr) < target) {
-      if (++spins > ab.limit) { abort_raise(ab); ok = false; break; }
-      if ((spins & 63u) == 0 && abort_seen(ab)) { ok = false; break; }
-    }
-    *s_flag = ok ? 1 : 0;
-  }
-  __syncthreads();
-  const bool ok = *s_flag != 0;
-  __syncthreads();
-  acquire_handoff();
-  return ok;
-}
-__device__ __forceinline__ void publish(unsigned* ctr) {
-  asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-  __syncthreads();
-  if (threadIdx.x == 0) __hip_atomic_fetch_add(ctr, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-}
-__device__ __forceinline__ float sigm_fast(float x) { return __builtin_amdgcn_rcpf(1.f + __expf(-x)); }
-__device__ __forceinline__ float tanh_fast(float x) { return 2.f * __builtin_amdgcn_rcpf(1.f + __expf(-2.f * x)) - 1.f; }
-__device__ __forceinline__ float wave_sum(float v) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o);
-  return v;
-}
-
+// Handed-off activations are read by every workgroup of an XCD (the 32 rows x 1024 columns of h, ht, [cv; h]: 128-256 KB per workgroup and
+// step) with sc1 loads, as in decoder_persist.hip.  (Rejected: ordinary loads behind an agent-scope acquire after every wait, so that the 32
+// workgroups of an XCD share one fetch of a line -- the ten L2 invalidations per step cost more than the shared fetches save: configs[4]
+// shape, 18.7 ms per train step against 17.9 with sc1 loads.)
 // NB k-blocks of 16 floats per wave (block wave + 4 i): both 16-row batch tiles against the same resident weight fragments.
 // `ra` addresses the activation matrix, off0 / off1 are the float offsets of this lane's row in tile 0 / 1 (incl. 4 q).
 template <int NB>
@@ -222,9 +148,9 @@ __global__ __launch_bounds__(256, 1) void decoder_wide_fwd(WideArgs a) {
     const bool fed_in = s > a.s0 && a.use_truth[s] == 0;      // this step's token is the previous step's argmax, found inside this launch
     // ================= CELL
     f32x4 acc[2] = {{0.f, 0.f, 0.f, 0.f}, {0.f, 0.f, 0.f, 0.f}};
-    if (n > 1 && !wait_sh(c_cell, WG_, n - 1, a.ab, &s_flag)) return;      // h_{s-1} of every unit
+    if (n > 1 && !wg_wait_sh(c_cell, WG_, n - 1, a.ab, &s_flag)) return;      // h_{s-1} of every unit
     mac2<16>(acc, wHh, r_hr, ((long)s * B + row0) * WH + q4, ((long)s * B + row1) * WH + q4, wave);
-    if (fed_in && !wait_sh(c_arg, B, nfed, a.ab, &s_flag)) return;          // the fed-back tokens (ARG of step s - 1)
+    if (fed_in && !wg_wait_sh(c_arg, B, nfed, a.ab, &s_flag)) return;          // the fed-back tokens (ARG of step s - 1)
     {   // embedding part (off the chain unless the token is fed back): rows gathered from the table, times the embedding dropout mask
       int tok[2];
 #pragma unroll
@@ -268,7 +194,7 @@ __global__ __launch_bounds__(256, 1) void decoder_wide_fwd(WideArgs a) {
         }
       }
     }
-    if (n > 1 && !wait_sh(c_ctx, NCTX, n - 1, a.ab, &s_flag)) return;      // ht_{s-1} (input feeding)
+    if (n > 1 && !wg_wait_sh(c_ctx, NCTX, n - 1, a.ab, &s_flag)) return;      // ht_{s-1} (input feeding)
     mac2<16>(acc, wA, r_x0, ((long)s * B + row0) * WXI + WE + q4, ((long)s * B + row1) * WXI + WE + q4, wave);
     {
       float v[2];
@@ -295,7 +221,7 @@ __global__ __launch_bounds__(256, 1) void decoder_wide_fwd(WideArgs a) {
     }
     // ================= Q: q = Wa h + ba
     if (is_q) {
-      if (!wait_sh(c_cell, WG_, n, a.ab, &s_flag)) return;
+      if (!wg_wait_sh(c_cell, WG_, n, a.ab, &s_flag)) return;
       f32x4 aq[2] = {{0.f, 0.f, 0.f, 0.f}, {0.f, 0.f, 0.f, 0.f}};
       mac2<16>(aq, wX, r_cvh, ((long)s * B + row0) * 2 * WH + WH + q4, ((long)s * B + row1) * 2 * WH + WH + q4, wave);
       float v[2];
@@ -311,7 +237,7 @@ __global__ __launch_bounds__(256, 1) void decoder_wide_fwd(WideArgs a) {
     }
     // ================= ATT: scores and partial context of (batch row, chunk)
     if (is_att) {
-      if (!wait_sh(c_q, NQ, n, a.ab, &s_flag)) return;
+      if (!wg_wait_sh(c_q, NQ, n, a.ab, &s_flag)) return;
       float4 qv[4], ac[4];
 #pragma unroll
       for (int c = 0; c < 4; ++c) {
@@ -360,7 +286,7 @@ __global__ __launch_bounds__(256, 1) void decoder_wide_fwd(WideArgs a) {
     if (is_cmb) {
       const int b = w - CMB0;
       // (chunks behind the last frame hold no rows: their partials are (-inf, 0, 0) and weigh nothing)
-      if (!wait_one(c_row + (size_t)b * CTRS, (unsigned)(a.nsplit * n), a.ab, &s_flag)) return;
+      if (!wg_wait(c_row + (size_t)b * CTRS, (unsigned)(a.nsplit * n), a.ab, &s_flag)) return;
       // the chunks' (max, sum) pairs once, through LDS; then every thread merges its 4 columns of all partial sums with independent 16-byte loads
       // (one exposed round trip instead of one per partial)
       const __amdgpu_buffer_rsrc_t r_part = make_rsrc(a.PART + (long)b * a.nsplit * PARTW);
@@ -402,9 +328,9 @@ __global__ __launch_bounds__(256, 1) void decoder_wide_fwd(WideArgs a) {
       f32x4 ax[2] = {{0.f, 0.f, 0.f, 0.f}, {0.f, 0.f, 0.f, 0.f}};
       const long o0 = ((long)s * B + row0) * 2 * WH + q4, o1 = ((long)s * B + row1) * 2 * WH + q4;
       // the h half of [cv; h] (k-blocks wave + 4i, i >= 16: columns [1024, 2048)) is complete since CELL: off the chain, in front of the wait
-      if (!is_att && !wait_sh(c_cell, WG_, n, a.ab, &s_flag)) return;        // (attention workgroups have seen Q, which saw CELL)
+      if (!is_att && !wg_wait_sh(c_cell, WG_, n, a.ab, &s_flag)) return;        // (attention workgroups have seen Q, which saw CELL)
       mac2<16>(ax, wX + 16, r_cvh, o0 + 1024, o1 + 1024, wave);
-      if (!wait_sh(c_cmb, B, n, a.ab, &s_flag)) return;
+      if (!wg_wait_sh(c_cmb, B, n, a.ab, &s_flag)) return;
       mac2<16>(ax, wX, r_cvh, o0, o1, wave);                                  // i < 16: columns [0, 1024), the context vectors
       float v[2];
       reduce2(ax, v, s_red);
@@ -426,7 +352,7 @@ __global__ __launch_bounds__(256, 1) void decoder_wide_fwd(WideArgs a) {
     // (two at V = 8004: 128 KB) from L2 / Infinity Cache, keeps a per-(row, tile) maximum, and one workgroup per batch row picks the class.
     if (s + 1 < a.S && s < a.s1 && a.use_truth[s + 1] == 0) {
       ++nfed;
-      if (!wait_sh(c_ctx, NCTX, n, a.ab, &s_flag)) return;
+      if (!wg_wait_sh(c_ctx, NCTX, n, a.ab, &s_flag)) return;
       for (int t = w; t < a.ntile; t += WG_) {
         f32x4 lg[2] = {{0.f, 0.f, 0.f, 0.f}, {0.f, 0.f, 0.f, 0.f}};
         const float* wrow = a.Wo + (long)min(16 * t + r, a.V - 1) * WA + q4;
@@ -461,7 +387,7 @@ __global__ __launch_bounds__(256, 1) void decoder_wide_fwd(WideArgs a) {
       }
       publish(c_log + (w & (NSH - 1)) * CTRS);
       if (w < B) {
-        if (!wait_sh(c_log, WG_, nfed, a.ab, &s_flag)) return;
+        if (!wg_wait_sh(c_log, WG_, nfed, a.ab, &s_flag)) return;
         float m = -INFINITY;
         int mi = 0x7fffffff;
         for (int t = tid; t < a.ntile; t += 256) {
@@ -565,7 +491,7 @@ __global__ __launch_bounds__(256, 1) void decoder_wide_bwd(WideBwdArgs a) {
     const int n = S - st;                            // arrivals per item up to and including this step
     // ================= P1: d_cvh[st] = d_pre[st] Wc
     if (is_p1) {
-      if (n > 1 && !wait_sh(c_dpre, NTILE, n - 1, a.ab, &s_flag)) return;
+      if (n > 1 && !wg_wait_sh(c_dpre, NTILE, n - 1, a.ab, &s_flag)) return;
       f32x4 acc[2] = {{0.f, 0.f, 0.f, 0.f}, {0.f, 0.f, 0.f, 0.f}};
       mac2<16>(acc, wX, r_dpre, ((long)st * B + row0) * WA + q4, ((long)st * B + row1) * WA + q4, wave);
       float v[2];
@@ -579,7 +505,7 @@ __global__ __launch_bounds__(256, 1) void decoder_wide_bwd(WideBwdArgs a) {
     }
     // ================= ATTB
     if (is_att) {
-      if (!wait_sh(c_p1, NP1, n, a.ab, &s_flag)) return;
+      if (!wg_wait_sh(c_p1, NP1, n, a.ab, &s_flag)) return;
       float4 dcv[4], cvv[4], ac[4];
       float c0 = 0.f;
 #pragma unroll
@@ -616,7 +542,7 @@ __global__ __launch_bounds__(256, 1) void decoder_wide_bwd(WideBwdArgs a) {
     // ================= DQC: dq[b] = sum of the chunks' partials
     if (is_dqc) {
       const int b = w - BDQC;
-      if (!wait_one(c_row + (size_t)b * CTRS, (unsigned)(a.nsplit * n), a.ab, &s_flag)) return;
+      if (!wg_wait(c_row + (size_t)b * CTRS, (unsigned)(a.nsplit * n), a.ab, &s_flag)) return;
       float4 v = make_float4(0.f, 0.f, 0.f, 0.f);
       for (int k0 = 0; k0 < a.nsplit; k0 += 8) {
         float4 p[8];
@@ -632,7 +558,7 @@ __global__ __launch_bounds__(256, 1) void decoder_wide_bwd(WideBwdArgs a) {
     }
     // ================= P3: dh_top = d_cvh[:, H:] + dq Wa
     if (is_p3) {
-      if (!wait_sh(c_dqc, B, n, a.ab, &s_flag)) return;
+      if (!wg_wait_sh(c_dqc, B, n, a.ab, &s_flag)) return;
       f32x4 acc[2] = {{0.f, 0.f, 0.f, 0.f}, {0.f, 0.f, 0.f, 0.f}};
       mac2<16>(acc, wX, r_dq, ((long)st * B + row0) * WH + q4, ((long)st * B + row1) * WH + q4, wave);
       float v[2];
@@ -647,8 +573,8 @@ __global__ __launch_bounds__(256, 1) void decoder_wide_bwd(WideBwdArgs a) {
     }
     // ================= CELLB: pointwise LSTM backward of this workgroup's 4 units
     {
-      if (!wait_sh(c_p3, NP3, n, a.ab, &s_flag)) return;
-      if (n > 1 && !wait_one(c_rec + (size_t)tj * CTRS, (unsigned)(4 * (n - 1)), a.ab, &s_flag)) return;
+      if (!wg_wait_sh(c_p3, NP3, n, a.ab, &s_flag)) return;
+      if (n > 1 && !wg_wait(c_rec + (size_t)tj * CTRS, (unsigned)(4 * (n - 1)), a.ab, &s_flag)) return;
       if (tid < 128 && crow < B) {
         const long bu = (long)crow * WH + cu;
         float dy = ld_sc1(a.DHTOP + bu);
@@ -676,7 +602,7 @@ __global__ __launch_bounds__(256, 1) void decoder_wide_bwd(WideBwdArgs a) {
     if (st == 0) break;
     // ================= DZ: quarter kq of dz_st against the recurrent and the carry weight slices
     {
-      if (!wait_sh(c_cell, WG_, n, a.ab, &s_flag)) return;
+      if (!wg_wait_sh(c_cell, WG_, n, a.ab, &s_flag)) return;
       const long o0 = ((long)st * B + row0) * 4 * WH + 1024 * kq + q4, o1 = ((long)st * B + row1) * 4 * WH + 1024 * kq + q4;
       float4 a0[16], a1[16];
 #pragma unroll
@@ -720,7 +646,7 @@ __global__ __launch_bounds__(256, 1) void decoder_wide_bwd(WideBwdArgs a) {
     // ================= P5R: d_pre[st-1] = (dlogits Wo + carry) (1 - ht_{st-1}^2)
     if (is_p5r) {
       const int j = w - BP5R;
-      if (!wait_one(c_car + (size_t)j * CTRS, (unsigned)(4 * n), a.ab, &s_flag)) return;
+      if (!wg_wait(c_car + (size_t)j * CTRS, (unsigned)(4 * n), a.ab, &s_flag)) return;
       const float* pc = a.PCAR + (long)j * 4 * 512;
 #pragma unroll
       for (int mt = 0; mt < 2; ++mt) {

@@ -79,7 +79,6 @@ __device__ __forceinline__ long rowoff(const MatView& v, int r) {
   return (long)r * v.ld;
 }
 
-typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
 
 // First k-iteration of workgroup w of G (stream-K split of the launch's iteration sequence).  grp.unit = 2 when every product of
 // the launch has an even number of k-iterations per tile: ranges then begin on even k-iterations, i.e. on 128-byte lines of a
@@ -255,7 +254,7 @@ struct Stager {
           __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(v.p + adv), 0, (int)(span - (unsigned)(adv * 4)), 0x00020000);
 #pragma unroll
       for (int p = 0; p < NP; ++p) {
-        const u32x4 u = __builtin_amdgcn_raw_buffer_load_b128(r, (int)voff[p], 0, 0);
+        const u32q u = __builtin_amdgcn_raw_buffer_load_b128(r, (int)voff[p], 0, 0);
         reg[slot][p] = make_float4(__uint_as_float(u.x), __uint_as_float(u.y), __uint_as_float(u.z), __uint_as_float(u.w));
       }
     } else {
@@ -264,7 +263,7 @@ struct Stager {
             __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(v.p + (long)tgrp * v.sg + (long)trem * v.st), 0, 0x7fffffff, 0x00020000);
 #pragma unroll
         for (int p = 0; p < NP; ++p) {
-          const u32x4 u = __builtin_amdgcn_raw_buffer_load_b128(r, (int)voff[p], 0, 0);
+          const u32q u = __builtin_amdgcn_raw_buffer_load_b128(r, (int)voff[p], 0, 0);
           reg[slot][p] = make_float4(__uint_as_float(u.x), __uint_as_float(u.y), __uint_as_float(u.z), __uint_as_float(u.w));
         }
       } else {                   // the tile straddles groups (or runs past kend): per-row offsets, rows clamped to kend - 1
@@ -289,10 +288,10 @@ struct Stager {
         __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(v.p + adv), 0, (int)(span - (unsigned)(adv * 4)), 0x00020000);
 #pragma unroll
     for (int p = 0; p < NP; ++p) {
-      const u32x4 u = __builtin_amdgcn_raw_buffer_load_b128(r, (int)voff[p], 0, 0);
+      const u32q u = __builtin_amdgcn_raw_buffer_load_b128(r, (int)voff[p], 0, 0);
       reg[slot][p] = make_float4(__uint_as_float(u.x), __uint_as_float(u.y), __uint_as_float(u.z), __uint_as_float(u.w));
       if (second) {
-        const u32x4 w = __builtin_amdgcn_raw_buffer_load_b128(r, (int)voff[p] + BK * 4, 0, 0);
+        const u32q w = __builtin_amdgcn_raw_buffer_load_b128(r, (int)voff[p] + BK * 4, 0, 0);
         reg[(slot + 1) % RING][p] = make_float4(__uint_as_float(w.x), __uint_as_float(w.y), __uint_as_float(w.z), __uint_as_float(w.w));
       }
     }
@@ -586,7 +585,7 @@ __global__ __launch_bounds__(gemm_threads(PREC, TLM), gemm_min_waves(TL, PREC, T
               for (int j = 0; j < NA; ++j)
 #pragma unroll
                 for (int q = 0; q < 4; ++q) {
-                  u32x4 o;
+                  u32q o;
                   o.x = __float_as_uint(acc[i][j][4 * q]); o.y = __float_as_uint(acc[i][j][4 * q + 1]);
                   o.z = __float_as_uint(acc[i][j][4 * q + 2]); o.w = __float_as_uint(acc[i][j][4 * q + 3]);
                   __builtin_amdgcn_raw_buffer_store_b128(o, rs, mine + ((i * NA + j) * 4 + q) * 1024, 0, 16);
@@ -612,7 +611,7 @@ __global__ __launch_bounds__(gemm_threads(PREC, TLM), gemm_min_waves(TL, PREC, T
               for (int i = 0; i < NAM; ++i)
 #pragma unroll
                 for (int j = 0; j < NA; ++j) {
-                  u32x4 t[4];
+                  u32q t[4];
 #pragma unroll
                   for (int q = 0; q < 4; ++q) t[q] = __builtin_amdgcn_raw_buffer_load_b128(rs, base + ((i * NA + j) * 4 + q) * 1024, 0, 16);
 #pragma unroll

@@ -12,37 +12,11 @@
 //              dWl, dWu, db and the gradient wrt the layer input.
 // HBM layout (per direction d, layer l, all f32, step-major):
 //   ZG (T,B,4h) gates -> dz | HR (T,B,h) raw h | CC (T,B,h) cell | HD (T,B,h) dropped output (only with masks)
-#include "common.h"
+#include "lstm_persist.h"
 #include <algorithm>
 #include <vector>
 
 namespace astk {
-
-struct PersistCellHost {
-  const float *Wl, *Wu, *bias, *zx, *xin, *mask, *WlT, *d_enc, *d_hT, *d_cT;
-  float *gates, *C, *HR, *HD, *enc;
-  const float* WuT;
-  float *PR, *PD;
-  const float* PD_up;
-  int up_external;
-  int reverse_pos, layer;
-  unsigned long long* amax;
-  float* db;
-  long dy_sb, dy_st;
-  const unsigned* zx_flags; int zx_s0, zx_cs;
-  unsigned* prog; int prog_cs;
-  float* db_part;
-};
-bool lstm_persist_hoisted(int h);
-bool lstm_persist_applicable(int T, int B, int h, int nl, int nd);
-int lstm_persist_rows(int B, int h, int nl, int nd, bool side);
-int lstm_persist_layers_per_launch(int B, int h, int nl, int nd, int rows);
-int lstm_persist_grid_wgs(int B, int h, int layers, int nd, int rows);
-size_t lstm_persist_pr_floats(int B, int h);
-size_t lstm_persist_pd_floats(int T, int B, int h);
-int lstm_persist_fwd_launch(const PersistCellHost* cells, int ncells, int nl, int T, int B, int h, int H, unsigned* counters, int rows, hipStream_t s);
-int lstm_persist_bwd_launch(const PersistCellHost* cells, int ncells, int nl, int T, int B, int h, int H, unsigned* counters, unsigned amax_gen,
-                            int rows, hipStream_t s);
 
 namespace {
 

@@ -20,7 +20,8 @@
 //                        with ONE lane and fetches the partials a step early).  Counters are zeroed before every launch.
 // Every spin is bounded: on time-out a workgroup raises the abort word, every poll loop checks it, and the grid drains.
 // Residency: the launcher only uses this path when the whole grid fits one workgroup per CU (<= 256 workgroups).
-#include "common.h"
+#include "lstm_persist.h"
+#include "handoff.h"
 #include <type_traits>
 
 namespace astk {
@@ -28,17 +29,8 @@ namespace astk {
 namespace {
 
 typedef unsigned long long u64;
-// In-kernel instrumentation (phase timers, bit 8; the dawdling slice of the last-arrival regression test, bit 16) exists only in the
-// test-hook build (libastk_test.so, -DASTK_TEST_HOOKS): there ASTK_PERSIST_DBG is read at every launch; the product library's kernels see
-// the constant 0 and carry none of it.
-#ifdef ASTK_TEST_HOOKS
-static int persist_dbg_env() { const char* e = getenv("ASTK_PERSIST_DBG"); return e ? atoi(e) : 0; }
-#define PERSIST_DBG(a) ((a).dbg)
-#else
-static int persist_dbg_env() { return 0; }
-#define PERSIST_DBG(a) 0
-#endif
-constexpr int CTR_STRIDE = 64;   // arrival counters live 256 bytes apart: pollers of different cells never share a line
+// (ASTK_PERSIST_DBG, test-hook build only -- handoff.h: phase timers, bit 8; the dawdling slice of the last-arrival regression test, bit 16)
+constexpr int CTR_STRIDE = CTRS; // arrival counters live 256 bytes apart: pollers of different cells never share a line
 
 struct PCellF {
   const float* Wl;      // (4h, h)
@@ -104,45 +96,6 @@ struct PBwdArgs {
   unsigned* done;
   AbortCtl ab;
 };
-
-__device__ __forceinline__ unsigned ld_flag(const unsigned* p) {
-  return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-}
-__device__ __forceinline__ void st4_sc1(float* p, float v) {
-  __hip_atomic_store(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-}
-
-// One lane waits until *ctr >= target (or the abort word is raised).  Returns false on abort / time-out.
-__device__ __forceinline__ bool wait_ge(const unsigned* ctr, unsigned target, const AbortCtl& ab) {
-  unsigned spins = 0;
-  while (ld_flag(ctr) < target) {
-    if (++spins > ab.limit) {   // ~seconds: something is wrong (grid not resident); drain instead of hanging
-      abort_raise(ab);
-      return false;
-    }
-    if ((spins & 63u) == 0 && abort_seen(ab)) return false;
-  }
-  return true;
-}
-
-// publish: every storing wave drains its stores, the workgroup barriers, one lane bumps the arrival counter
-// (tid: the caller's thread index inside its -- possibly virtual, see DUO -- workgroup)
-__device__ __forceinline__ void publish(unsigned* ctr, int tid) {
-  asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-  __syncthreads();
-  if (tid == 0) __hip_atomic_fetch_add(ctr, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-}
-
-// Gate activations of the persistent kernels' epilogues (on the recurrence's critical path): v_exp_f32 / v_rcp_f32 based,
-// absolute error <= ~2e-7 (libdevice's tanhf/expf with full-precision division cost ~0.25 us more per step).
-__device__ __forceinline__ float sigm_fast(float x) { return __builtin_amdgcn_rcpf(1.f + __expf(-x)); }
-__device__ __forceinline__ float tanh_fast(float x) { return 2.f * __builtin_amdgcn_rcpf(1.f + __expf(-2.f * x)) - 1.f; }
-
-typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
-// raw buffer descriptor over a hand-off buffer: lets the compiler track 16-byte sc1 loads / stores itself
-__device__ __forceinline__ __amdgpu_buffer_rsrc_t make_rsrc(const void* p) {
-  return __builtin_amdgcn_make_buffer_rsrc(const_cast<void*>(p), 0, 0x7fffffff, 0x00020000);
-}
 
 #define MFMA4(ACC, A4, W4)                                                   \
   ACC = __builtin_amdgcn_mfma_f32_16x16x4f32((A4).x, (W4).x, ACC, 0, 0, 0);  \
@@ -262,12 +215,12 @@ constexpr unsigned SENTINEL = 0xffffffffu;
 #define ASTK_FRAG_WAIT_SWEEP 3
 #endif
 template <int NB>
-__device__ __forceinline__ void frag_issue(__amdgpu_buffer_rsrc_t rs, int byte_off, int wave, u32x4 (&g)[NB]) {
+__device__ __forceinline__ void frag_issue(__amdgpu_buffer_rsrc_t rs, int byte_off, int wave, u32q (&g)[NB]) {
 #pragma unroll
   for (int i = 0; i < NB; ++i) g[i] = __builtin_amdgcn_raw_buffer_load_b128(rs, byte_off + 64 * (wave + 4 * i), 0, 16);   // aux 16 = sc1
 }
 template <int NB>
-__device__ __forceinline__ bool frag_ok(const u32x4 (&g)[NB]) {
+__device__ __forceinline__ bool frag_ok(const u32q (&g)[NB]) {
   // (the sentinel is the largest unsigned word: one running maximum and ONE compare -- a chain of && compiles to a branch per word,
   //  0.25 us per check on the recurrence's critical path)
   unsigned m = 0;
@@ -279,7 +232,7 @@ __device__ __forceinline__ bool frag_ok(const u32x4 (&g)[NB]) {
 // flood the fabric with full sweeps), then re-read everything; repeat until complete.  Bounded; a time-out raises the
 // abort word, which every other spin checks, and the grid drains.
 template <int NB>
-__device__ __forceinline__ void frag_wait(__amdgpu_buffer_rsrc_t rs, int byte_off, int wave, u32x4 (&g)[NB], bool& dead, const AbortCtl& ab) {
+__device__ __forceinline__ void frag_wait(__amdgpu_buffer_rsrc_t rs, int byte_off, int wave, u32q (&g)[NB], bool& dead, const AbortCtl& ab) {
   unsigned spins = 0;
   while (!dead) {
 #if ASTK_FRAG_WAIT_SWEEP
@@ -292,7 +245,7 @@ __device__ __forceinline__ void frag_wait(__amdgpu_buffer_rsrc_t rs, int byte_of
       continue;
     }
 #endif
-    const u32x4 c = __builtin_amdgcn_raw_buffer_load_b128(rs, byte_off + 64 * wave, 0, 16);
+    const u32q c = __builtin_amdgcn_raw_buffer_load_b128(rs, byte_off + 64 * wave, 0, 16);
     if (__all((c.x != SENTINEL) & (c.y != SENTINEL) & (c.z != SENTINEL) & (c.w != SENTINEL))) {
       frag_issue<NB>(rs, byte_off, wave, g);
       if (frag_ok<NB>(g)) return;
@@ -301,7 +254,7 @@ __device__ __forceinline__ void frag_wait(__amdgpu_buffer_rsrc_t rs, int byte_of
     else if ((spins & 63u) == 0 && abort_seen(ab)) dead = true;
   }
 }
-__device__ __forceinline__ float4 frag_vals(const u32x4& g) {
+__device__ __forceinline__ float4 frag_vals(const u32q& g) {
   return make_float4(__uint_as_float(g.x), __uint_as_float(g.y), __uint_as_float(g.z), __uint_as_float(g.w));
 }
 
@@ -420,7 +373,7 @@ __device__ __forceinline__ void lstm_fwd_steps(const PFwdArgs& a, const PCellF& 
 #pragma unroll
   for (int mt = 0; mt < MT; ++mt) c_state[mt] = 0.f;
   const int step_bytes = B * h * 4;
-  u32x4 gx[MT][KB];
+  u32q gx[MT][KB];
   float4 ax[MT][KB];
   Frag axh[MT][X2 ? NPR : 1];
   auto take_x = [&]() {
@@ -518,7 +471,7 @@ __device__ __forceinline__ void lstm_fwd_steps(const PFwdArgs& a, const PCellF& 
     for (int mt = 0; mt < MT; ++mt)
 #pragma unroll
       for (int g = 0; g < 4; ++g) acc[mt][g] = f32x4{0.f, 0.f, 0.f, 0.f};
-    u32x4 gh[MT][KB];
+    u32q gh[MT][KB];
     if (!FIRST) {
 #pragma unroll
       for (int mt = 0; mt < MT; ++mt) frag_issue<KB>(r_own, frag0[mt] + (t - 1) * step_bytes, wave, gh[mt]);   // in flight behind the upward MFMAs
@@ -632,8 +585,8 @@ __device__ __forceinline__ void lstm_fwd_steps(const PFwdArgs& a, const PCellF& 
         // the hand-off: the values themselves, write-through; nothing to drain or signal
         if (evalid[mt]) {
           const long o = ((long)t * B + eb[mt]) * h + eu;
-          st4_sc1(c.HR + o, hh);
-          if (c.HD) st4_sc1(c.HD + o, hd);
+          st_sc1(c.HR + o, hh);
+          if (c.HD) st_sc1(c.HD + o, hd);
         }
         p_gates[mt] = make_float4(ga, gi, gf, go);
         p_hd[mt] = hd; p_c[mt] = c_state[mt];
@@ -854,7 +807,7 @@ __device__ __forceinline__ void lstm_bwd_rs_steps(const PBwdArgs& a, const PCell
 #pragma unroll
       for (int nt = 0; nt < (CAN_DOWN ? KB : 0); ++nt) {
         const int tl = wave * KB + nt;
-        u32x4 o;
+        u32q o;
         o.x = __float_as_uint(acc2[mt][nt][0]); o.y = __float_as_uint(acc2[mt][nt][1]); o.z = __float_as_uint(acc2[mt][nt][2]); o.w = __float_as_uint(acc2[mt][nt][3]);
         __builtin_amdgcn_raw_buffer_store_b128(o, r_pd, (int)((((long)ts * nbt + by * MT + mt) * NS + tl) * cons_stride) + j * tile_bytes + (r16 * 16 + 4 * q) * 4, 0, 16);
       }
@@ -1097,7 +1050,7 @@ __device__ __forceinline__ void lstm_bwd_rs_steps(const PBwdArgs& a, const PCell
         const int tl = wave * KB + nt;
 #pragma unroll
         for (int mt = 0; mt < MT; ++mt) {
-          u32x4 o;
+          u32q o;
           o.x = __float_as_uint(acc[mt][0]); o.y = __float_as_uint(acc[mt][1]); o.z = __float_as_uint(acc[mt][2]); o.w = __float_as_uint(acc[mt][3]);
           __builtin_amdgcn_raw_buffer_store_b128(o, r_pr, (int)((((long)slot * nbt + by * MT + mt) * NS + tl) * cons_stride) + j * tile_bytes + (r16 * 16 + 4 * q) * 4, 0, 16);
         }
@@ -1152,7 +1105,7 @@ __device__ __forceinline__ void lstm_bwd_rs_steps(const PBwdArgs& a, const PCell
 #pragma unroll
     for (int mt = 0; mt < MT; ++mt)
     if (reset_base[mt] >= 0) {   // behind the step's barrier every reader of the slot just consumed is done with it: the sentinel goes back (16 KB in a row)
-      const u32x4 sent = {SENTINEL, SENTINEL, SENTINEL, SENTINEL};
+      const u32q sent = {SENTINEL, SENTINEL, SENTINEL, SENTINEL};
 #pragma unroll
       for (int i = 0; i < NS / 4; ++i) __builtin_amdgcn_raw_buffer_store_b128(sent, r_pr, reset_base[mt] + (i * 256 + tid) * 16, 0, 16);
     }
@@ -1167,7 +1120,7 @@ __device__ __forceinline__ void lstm_bwd_rs_steps(const PBwdArgs& a, const PCell
       if (evalid[mt]) {
         const long tb = (long)t * B + eb[mt];
         if (c.prog) {
-          u32x4 o;
+          u32q o;
           o.x = __float_as_uint(dz[mt].x); o.y = __float_as_uint(dz[mt].y); o.z = __float_as_uint(dz[mt].z); o.w = __float_as_uint(dz[mt].w);
           __builtin_amdgcn_raw_buffer_store_b128(o, r_dz, (int)((tb * K + 4 * eu) * 4), 0, 16);
         } else {
@@ -1285,27 +1238,11 @@ __global__ __launch_bounds__(256, 1) void lstm_persist_bwd_rs(PBwdArgs a) {
 }  // namespace
 
 // ---- launchers (called from lstm.hip).  Return 1 if the persistent path is not applicable (caller falls back).
-struct PersistCellHost {
-  const float *Wl, *Wu, *bias, *zx, *xin, *mask, *WlT, *d_enc, *d_hT, *d_cT;
-  float *gates, *C, *HR, *HD, *enc;
-  const float* WuT;               // backward: this cell's transposed upward weight (layers >= 1)
-  float *PR, *PD;                 // backward, reduce-scatter path: partial-sum buffers of this cell
-  const float* PD_up;
-  int up_external;
-  int reverse_pos, layer;
-  unsigned long long* amax;       // backward: where max |dz| of the cell goes (16 sharded words, gemm_amax_reserve), null: not wanted
-  float* db;                      // backward: bias gradient accumulated by the recurrence kernel itself (null: not wanted)
-  long dy_sb, dy_st;              // backward: strides of d_enc (see PCellB)
-  const unsigned* zx_flags; int zx_s0, zx_cs;      // forward, layer 0: chunk flags of the input projection (see PCellF)
-  unsigned* prog; int prog_cs;                     // backward, layer 0: progress counter for side-stream consumers of dz (see PCellB)
-  float* db_part;                                  // backward: deterministic bias-gradient scratch (see PCellB)
-};
 
 // Layers per launch.  One workgroup per CU must hold a launch's whole grid; a stack with more (direction, layer) cells than fit is
 // run as consecutive launches over groups of layers (all directions of `lpl` layers each): the wavefront overlap between the
 // groups is lost, everything else stays (BASELINE configs[4]: 6 layers x 2 directions x 32 unit slices x 2 batch tiles = 768
 // workgroups -> 3 launches of 2 layers; batch 64 at the shipped width: 2 launches).  0 = not applicable.
-bool lstm_persist_hoisted(int h);
 // Form of the recurrence workgroups (the `rows` argument of everything below): 16 = one 16-row batch tile per 256-thread workgroup;
 // 33 = DUO: two 16-row tiles per 512-thread workgroup as two virtual workgroups, two waves per SIMD (bf16x3 arithmetic, h <= 256);
 // 32 = MT 2: two tiles per 256-thread workgroup against one set of weight fragments (any arithmetic, h <= 256).  Both 32-row forms halve
@@ -1422,7 +1359,6 @@ int lstm_persist_fwd_launch(const PersistCellHost* cells, int ncells, int nl, in
   return 0;
 }
 
-size_t lstm_persist_pr_floats(int B, int h);
 int lstm_persist_bwd_launch(const PersistCellHost* cells, int ncells, int nl, int T, int B, int h, int H, unsigned* counters,
                             unsigned amax_gen, int rows, hipStream_t s) {
   PBwdArgs a;

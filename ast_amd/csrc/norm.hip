@@ -12,11 +12,6 @@ namespace astk {
 
 namespace {
 
-__device__ __forceinline__ float wave_sum(float v) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o);
-  return v;
-}
 
 // one wavefront per row: y = (x - mu) / sqrt(var + eps) * gamma + beta, biased variance (F.layer_normalization)
 __global__ __launch_bounds__(256) void k_layernorm_fwd(int rows, int n, const float* __restrict__ x, long ldx, const float* __restrict__ gamma,
