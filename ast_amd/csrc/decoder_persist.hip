@@ -24,6 +24,8 @@
 // (ctx / logits owners), so that no workgroup holds more than 68 float4 (272 VGPRs) of weights.
 // Applicability (else the per-launch path of decoder.hip runs): 1-3 decoder layers, H,A multiples of 16, sizes within the
 // register budgets below, grid of 256 workgroups fully resident.  All spins are bounded (abort word).
+// Where the forward phases are: decoder_persist_fwd_body -- P6 is its lambda run_p6 (beam branch first), P1, P1b, P3, P3b, P4, P5 the
+// banners of its step loop in that order; lse_merge in front of it.  The backward loop: decoder_persist_bwd.
 #include "decoder_persist.h"
 #include "handoff.h"
 #include <initializer_list>
@@ -245,41 +247,31 @@ __device__ __forceinline__ void mfma_blocks(f32x4& acc, const float4* a, const f
   acc += acc2;
 }
 
+// ---------------------------------------------------------------------------------------------------------------------
+// The forward loop: decoder_persist_fwd_body<NC, NL, XS, MODE>, a prologue (item ownership, resident weights, LDS slices, initial state) and
+// the step loop, whose phases are the blocks under the `// ===== P...` banners; what a mode changes in a phase is described at that banner.
 // NC > 0: H = 64 * NC and chunk <= PDEC_CHUNK_MAX are compile-time facts for the attention phase (fully unrolled, batched reads);
 // NC = 0: generic loops.
 // XS: the slice has more rows than stay resident (chunk > PDEC_RES_ROWS): the streamed-row code is compiled into its own instantiation
 // so that the common short-chunk case keeps its register budget.
-// MODE: what the loop runs (PDecMode); the switches GR, SC, FD and SM below are derived from it at the top of the body.
-// GR: greedy decoding (inference): step 0 feeds `go` to every row, every later step its own argmax; no targets, masks, loss or saved
-// state for a backward pass (Gt, Cst, X0, ALPHA, ML, LOGITS, LSE and loss rows are neither read nor written: the input-feeding part of
-// a cell reads ht_{s-1} from HT).  The CE owner of each batch tile keeps a sticky per-row done flag (padding rows are done); once its
-// tile is all done it reports that step (atomic max, then one arrival), and the tile that completes the count writes the stop word
-// n_steps = max + 1 before its PH_CE arrival of that step.  The layer-0 cells read the stop word behind that arrival and leave at
-// step n_steps; every other wait learns of it in its slow path (StopCtl).  DESIGN.md section 11.
-// SC (with GR): scored greedy decoding.  P5 also keeps the tile's sum of exponentials and, with targets, the target logit; P6 merges the
-// sums as the training mode does and stores, beside the token, the log-probability of that token and the weighted negative
-// log-likelihood of the target (PDecArgs: LSE = LOGP, LOSSROWS = NLL, ytgt / L / cw).  Two more plain stores in front of the vmcnt(0)
-// and the barrier that the token store already had: no wait, arrival, counter or exit condition is added.  DESIGN.md section 12.
-// FD (with GR and SC): forced decoding -- the model run along a given translation.  Step s feeds y[b][s] (read from global memory, clamped),
-// so no step waits for an argmax: the hand-offs are the training loop's with every step teacher-forced (P6 deferred behind the next
-// step's attention partial), and there is no stop: the stop word is never passed to a wait (STOP = false), no tile reports, every
-// workgroup runs all S steps.  P5 keeps what the scored mode keeps; P6 stores LOGP = log p(y[b][s+1]) (PDecArgs: LSE), the confidence
-// max logit - LSE (LOSSROWS, or null) and the argmax (PRED, or null).  With ALPHA / ML given, the attention and combine roles store the
-// raw scores and (max, 1 / sum) as the training mode does; k_alpha_normalise turns them into alpha behind the loop.  DESIGN.md section 13.
-// SM (with GR and SC, without FD): sampled decoding -- ancestral sampling by the Gumbel-max identity.  P5 perturbs the tempered logit
-// xs = x * inv_temp with the noise of (row key, step, class) (common.h sample_gumbel) and keeps the tile's winner by z = xs + g, xs at that
-// winner, and the tile's sum of exp(xs - xs at the winner) (g lies in [-2.9, 16.7]: the winner's xs is within 20 of the tile's largest, the
-// sum cannot overflow) -- the four words of the tile record, as before.  P6 merges the winner by z and the sums relative to the largest
-// reference, stores the token and LOGP = (xs_tok - ref) - logf(se), then runs the greedy branch on the SAMPLED token as it stands: no wait,
-// arrival, counter or exit condition is added.  DESIGN.md section 14.
-// BM (with GR and SC, without FD and SM): beam search -- every slot of every utterance is one row.  P5 keeps what the scored mode keeps and
-// stores the step's logits; P6 forms, per row, the float32 LSE of the scored mode and the row's K best tokens (K sweeps over the stored
-// logits: higher logit first, equal ones lower id first), lists the candidates of every utterance slot by slot (a finished slot itself,
-// a live slot its K expansions), takes the stable top N by float64 score, and writes -- in front of its PH_CE arrival -- the history
-// record, the token the row feeds next (PRED) and the PARENT row (PAR) of every row.  The cells gather through PAR: they read h and ht of
-// their row's parent row, and permute the register-held c among the rows of their tile through LDS.  The top layer's cells, which wait
-// for no PH_CE in the other modes, wait for PH_CE(s-1) of their tile in front of their recurrent half.  A tile reports once none of its
-// slots is live.  DESIGN.md section 16.
+// MODE: what the loop runs (PDecMode); the switches GR, SC, FD, SM, BM, STOP and SUMS are derived from it at the top of the body.
+// TRAIN: teacher forcing by flagS, the saved state of the backward pass, the loss rows.
+// GR (every other mode), greedy decoding (inference): no targets, masks, loss or saved state for a backward pass (Gt, Cst, X0, ALPHA, ML,
+// LOGITS, LSE and loss rows are neither read nor written).  Touches P1 (token, stop), P3 / P3b (no ALPHA / ML), P4 (no X0), P5 and P6 (the
+// stop).  DESIGN.md section 11.
+// SC (with GR), scored greedy decoding: P5 keeps the sums, P6 stores LOGP and NLL.  DESIGN.md section 12.
+// FD (with GR and SC), forced decoding -- the model run along a given translation: P1 feeds y, there is no stop (STOP = false); P5, P6, and
+// the raw scores of P3 / P3b.  DESIGN.md section 13.
+// SM (with GR and SC, without FD), sampled decoding -- ancestral sampling by the Gumbel-max identity: the draw in P5, its merge in P6.
+// DESIGN.md section 14.
+// BM (with GR and SC, without FD and SM), beam search -- every slot of every utterance is one row: P5 keeps the logits, the beam branch of
+// P6 selects, the cells (P1, P1b) follow the parents.  DESIGN.md section 16.
+// Two partial sums of exponentials, `se` relative to m and `os` relative to om, merged relative to nm = max(m, om): a side whose reference
+// is -inf holds nothing (its factor would be exp(nan)).  P6 merges the guarded form three times; its sweep over the tile records, which
+// guards one side only, is another expression and stays where it is.
+__device__ __forceinline__ float lse_merge(float m, float se, float om, float os, float nm) {
+  return (m == -INFINITY ? 0.f : se * expf(m - nm)) + (om == -INFINITY ? 0.f : os * expf(om - nm));
+}
 enum PDecMode { PDEC_TRAIN, PDEC_GREEDY, PDEC_SCORED, PDEC_FORCED, PDEC_SAMPLED, PDEC_BEAM };
 template <int NC, int NL, bool XS, PDecMode MODE>
 __device__ __forceinline__ void decoder_persist_fwd_body(const PDecArgs& a) {
@@ -476,9 +468,23 @@ __device__ __forceinline__ void decoder_persist_fwd_body(const PDecArgs& a) {
       t->score[tid] = 0.0; t->status[tid] = live ? BM_LIVE : BM_EMPTY; t->tok[tid] = a.go; t->org[tid] = -1;
     }
   }
+  // P6 of step s (run in place or deferred: see the P6 banner in the step loop).
+  // GR: the CE owner of each batch tile keeps a sticky per-row done flag (padding rows are done); once its tile is all done it reports that
+  // step (atomic max, then one arrival), and the tile that completes the count writes the stop word n_steps = max + 1 before its PH_CE
+  // arrival of that step.
+  // SC: merges the sums as the training mode does and stores, beside the token, the log-probability of that token and the weighted negative
+  // log-likelihood of the target (PDecArgs: LSE = LOGP, LOSSROWS = NLL, ytgt / L / cw).  Two more plain stores in front of the vmcnt(0) and
+  // the barrier that the token store already had: no wait, arrival, counter or exit condition is added.
+  // FD: stores LOGP = log p(y[b][s+1]) (PDecArgs: LSE), the confidence max logit - LSE (LOSSROWS, or null) and the argmax (PRED, or null).
+  // SM: merges the winner by z and the sums relative to the largest reference, stores the token and LOGP = (xs_tok - ref) - logf(se), then
+  // runs the greedy branch on the SAMPLED token as it stands: no wait, arrival, counter or exit condition is added.
   auto run_p6 = [&](const int s) -> bool {
       const int bt = ce_rank, m0 = bt * 16;
       const int row = m0 + (tid >> 4), sub = tid & 15;       // 16 threads per row sweep the tiles
+      // BM: every slot of every utterance is one row.  Forms, per row, the float32 LSE of the scored mode and the row's K best tokens (K sweeps over
+      // the stored logits: higher logit first, equal ones lower id first), lists the candidates of every utterance slot by slot (a finished slot
+      // itself, a live slot its K expansions), takes the stable top N by float64 score, and writes -- in front of its PH_CE arrival -- the history
+      // record, the token the row feeds next (PRED) and the PARENT row (PAR) of every row.  A tile reports once none of its slots is live.
       if constexpr (BM) {
         BeamTile* const t = bm_tile();
         // (every per-lane value of this role is formed from `tl` here, behind an empty asm: hoisted out of the step loop they would each
@@ -500,7 +506,7 @@ __device__ __forceinline__ void decoder_persist_fwd_body(const PDecArgs& a) {
         for (int o = 8; o > 0; o >>= 1) {
           const float om = __shfl_xor(mx, o), os = __shfl_xor(se, o);
           const float nm = fmaxf(mx, om);
-          se = (mx == -INFINITY ? 0.f : se * expf(mx - nm)) + (om == -INFINITY ? 0.f : os * expf(om - nm));
+          se = lse_merge(mx, se, om, os, nm);
           mx = nm;
         }
         const float lg = logf(se);
@@ -643,12 +649,12 @@ __device__ __forceinline__ void decoder_persist_fwd_body(const PDecArgs& a) {
         if constexpr (SM) {
           const float orf = __shfl_xor(rf, o);
           const float nr = fmaxf(rf, orf);
-          se = (rf == -INFINITY ? 0.f : se * expf(rf - nr)) + (orf == -INFINITY ? 0.f : os * expf(orf - nr));
+          se = lse_merge(rf, se, orf, os, nr);
           rf = nr;
           if (om > mx || (om == mx && oi < mi)) { mi = oi; mx = om; xt = ox; }
         } else {
           const float nm = fmaxf(mx, om);
-          if constexpr (SUMS) se = (mx == -INFINITY ? 0.f : se * expf(mx - nm)) + (om == -INFINITY ? 0.f : os * expf(om - nm));
+          if constexpr (SUMS) se = lse_merge(mx, se, om, os, nm);
           if (om > mx || (om == mx && oi < mi)) mi = oi;
           mx = nm;
           xt += ox;
@@ -735,6 +741,13 @@ __device__ __forceinline__ void decoder_persist_fwd_body(const PDecArgs& a) {
   for (int s = 0; s < S; ++s) {
     const StopCtl sc{stopw, s, false};
     // ================= P1: embed + LSTM cell =================
+    // GR: step 0 feeds `go` to every row, every later step its own argmax; the input-feeding part reads ht_{s-1} from HT.  The layer-0 cells
+    // read the stop word behind their tile's PH_CE arrival and leave at step n_steps; every other wait learns of it in its slow path (StopCtl).
+    // FD: step s feeds y[b][s] (read from global memory, clamped), so no step waits for an argmax: the hand-offs are the training loop's with
+    // every step teacher-forced (P6 deferred behind the next step's attention partial), and there is no stop: the stop word is never passed to
+    // a wait (STOP = false), no tile reports, every workgroup runs all S steps.
+    // BM: the cells gather through PAR: they read h and ht of their row's parent row, and permute the register-held c among the rows of their
+    // tile through LDS.
     if (has_cell) {
       const int bt = cell_bt, m0 = bt * 16;
       const int brow = min(m0 + r16, B - 1);             // this lane's A-operand batch row
@@ -841,6 +854,8 @@ __device__ __forceinline__ void decoder_persist_fwd_body(const PDecArgs& a) {
     }
     // ================= P1b: decoder layers 1..NL-1 (one cell item per workgroup: layer 1 of a 3-layer stack on the lower
     // workgroups, the top layer on the upper ones).  z = Wu hd_{l-1,s} + Wl h_{l,s-1} + b: the recurrent half runs before the wait.
+    // BM: the top layer's cells, which wait for no PH_CE in the other modes, wait for PH_CE(s-1) of their tile in front of their recurrent half,
+    // then gather through PAR as the layer-0 cells do.
     if constexpr (NL > 1) {
 #pragma unroll
       for (int pass = 0; pass < 2; ++pass) {
@@ -915,6 +930,9 @@ __device__ __forceinline__ void decoder_persist_fwd_body(const PDecArgs& a) {
       }
     }
     // ================= P3: attention over the LDS-resident slices: score = encA.h + eb, p = exp(score - max), cv partial =========
+    // GR: the slice's row count is read back from LDS (yS[0]) at the top of every step.  TRAIN stores the raw scores to ALPHA, normalised by the
+    // backward pass; FD, BM: with ALPHA / ML given, the attention and combine roles store the raw scores and (max, 1 / sum) as the training mode
+    // does; k_alpha_normalise turns them into alpha behind the loop.
     if (has_att) {
       const int b = att_b, bt = b / 16;
       TICK(15)
@@ -1164,6 +1182,7 @@ __device__ __forceinline__ void decoder_persist_fwd_body(const PDecArgs& a) {
       p6_pending = -1;
     }
     // ================= P3b: combine the nsplit partials of one batch row =================
+    // TRAIN stores (max, 1 / sum) to ML; FD, BM: with ML given, likewise (k_alpha_normalise reads them behind the loop).
     if (has_cmb) {
       const int b = cmb_b, bt = b / 16;
       const int rows_bt = min(16, B - bt * 16);
@@ -1255,6 +1274,13 @@ __device__ __forceinline__ void decoder_persist_fwd_body(const PDecArgs& a) {
       TICK(9)
     }
     // ================= P5: logits tiles + per-tile softmax statistics =================
+    // TRAIN: the logits are stored; the tile record is (max, sum of exp(x - max), argmax, target logit).  GR: the record holds the maximum and
+    // its index only (SUMS = false), unless SC: the sum and, with targets, the target logit too (the target is read in front of the wait); FD: a
+    // step of this mode always has a target.
+    // SM: perturbs the tempered logit xs = x * inv_temp with the noise of (row key, step, class) (common.h sample_gumbel) and keeps the tile's
+    // winner by z = xs + g, xs at that winner, and the tile's sum of exp(xs - xs at the winner) (g lies in [-2.9, 16.7]: the winner's xs is
+    // within 20 of the tile's largest, the sum cannot overflow) -- the four words of the tile record, as before.
+    // BM: keeps what the scored mode keeps and stores the step's logits for P6's top-K passes.
 #pragma unroll
     for (int t = 0; t < 2; ++t) {
       if (l_item[t] < 0) continue;
