@@ -65,7 +65,7 @@ struct CnnPlan {
   void* zero_fwd_from;
   size_t zero_fwd_amax_bytes;             // the forward slots alone (eval mode: no statistics to zero)
   unsigned* fin_ctr;                      // [layer * 64], inside the forward slots' region
-  float* c0_part;                         // direct layer-0 kernel: [c0_tiles][2][C] sums of y and y^2 over each tile's output steps
+  float* c0_part;                         // direct layer-0 kernel: [c0_tiles][2][C] sums of y - p and (y - p)^2 over each tile's output steps, then the pivots p [C]
   int c0_tiles;
   float* bn[ASTK_MAX_CNN_LAYERS];   // [4][C]: mean, inv_std, scale, shift
   float* G;                         // [rows_max][Cmax] gradient wrt post-ReLU output (row layout)
@@ -121,7 +121,7 @@ int make_plan(const astk_cnn_desc* d, void* ws, CnnPlan& P) {
   P.XF = c.take<float>((size_t)d->B * P.Fc[0] * P.xf_rows * P.JG + 16);
   // fused layer-0 statistics of the direct kernel: one row [2][C] of float sums per tile (C0_TT output steps of one (b, f))
   P.c0_tiles = d->B * P.Fc[0] * cdiv(P.Tc[0], 80);
-  P.c0_part = c.take<float>((size_t)P.c0_tiles * 2 * P.Cn[0]);
+  P.c0_part = c.take<float>((size_t)P.c0_tiles * 2 * P.Cn[0] + P.Cn[0]);
   size_t wd_max = 0;
   for (int i = 0; i < P.n; ++i) {
     P.Y[i] = c.take<float>((size_t)P.rows[i] * P.Cn[i]);
@@ -315,7 +315,11 @@ __global__ __launch_bounds__(256, 2) void k_conv0_fwd_x3(const float* __restrict
   extern __shared__ __attribute__((aligned(16))) unsigned short c0_planes[];      // [3][win] bf16; first the f32 weights [C][kt*kf]
   // BatchNorm statistics of the layer's output on the way out (part != nullptr; k_colstats read the 262 MB back: 19-21 us): per lane and
   // tile, sums over the steps it stores; folded over the 16 step lanes behind the tile's products; one row [2][C] of float sums per TILE,
-  // plain stores -- the statistics kernel behind this one sums 6400 such rows (6.5 MB) instead of the layer's output.
+  // plain stores -- the statistics kernel behind this one sums 6400 such rows (6.5 MB) instead of the layer's output.  The sums are of
+  // DEVIATIONS from a per-channel pivot every workgroup forms alike before its first tile: the channel's tap sum times the mean of the
+  // input's first kf values -- what a constant offset in the features puts on every output of the channel (raw float sums of y^2 lose
+  // (mean / std)^2 of their precision in E[y^2] - mean^2, see k_colstats).  Workgroup 0 leaves the pivots behind the tile rows.
+  __shared__ __attribute__((aligned(16))) float c0_piv[128];
   zero_region(zero_from, zero_bytes);      // the statistics / maximum slots the kernels BEHIND this one accumulate into
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, r = lane & 15, q = lane >> 4;
   const int ch0 = wave * 32;
@@ -339,6 +343,17 @@ __global__ __launch_bounds__(256, 2) void k_conv0_fwd_x3(const float* __restrict
         if (i0 + 256 * u < C * K0) wl[i0 + 256 * u] = w8[u];
     }
     __syncthreads();
+    if (part && tid < 128) {
+      float pv = 0.f;
+      if (tid < C) {
+        float xs = 0.f, ws = 0.f;
+        for (int j = 0; j < kf; ++j) xs += noise ? X[j] * noise[j] : X[j];
+        for (int k = 0; k < K0; ++k) ws += wl[tid * K0 + k];
+        pv = ws * (xs / (float)kf);
+        if (blockIdx.x == 0) part[(long)total * 2 * C + tid] = pv;
+      }
+      c0_piv[tid] = pv;      // (read behind the tile loop's first barrier)
+    }
 #pragma unroll
     for (int ct = 0; ct < 2; ++ct)
 #pragma unroll
@@ -408,7 +423,7 @@ __global__ __launch_bounds__(256, 2) void k_conv0_fwd_x3(const float* __restrict
       x.lo = *reinterpret_cast<const u32q*>(pl + off + 32 * ks);
       return x;
     };
-    float sa[8] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f}, qa[8] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};      // this tile: sum y, sum y^2 of the lane's 8 channels
+    float sa[8] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f}, qa[8] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};      // this tile: sum (y - p), sum (y - p)^2 of the lane's 8 channels
     auto store_y = [&](int ti, const f32x4& a0, const f32x4& a1) {
       const int t1 = t0 + 16 * ti + r;
       if (t1 < T1) {
@@ -417,10 +432,13 @@ __global__ __launch_bounds__(256, 2) void k_conv0_fwd_x3(const float* __restrict
         if (c < C) *reinterpret_cast<float4*>(yr + c) = make_float4(a0[0], a0[1], a0[2], a0[3]);
         if (c + 16 < C) *reinterpret_cast<float4*>(yr + c + 16) = make_float4(a1[0], a1[1], a1[2], a1[3]);
         if (part) {
+          const float4 p0 = *reinterpret_cast<const float4*>(&c0_piv[c]), p1 = *reinterpret_cast<const float4*>(&c0_piv[c + 16]);
+          const float d0[4] = {a0[0] - p0.x, a0[1] - p0.y, a0[2] - p0.z, a0[3] - p0.w};
+          const float d1[4] = {a1[0] - p1.x, a1[1] - p1.y, a1[2] - p1.z, a1[3] - p1.w};
 #pragma unroll
           for (int e = 0; e < 4; ++e) {
-            sa[e] += a0[e]; qa[e] += a0[e] * a0[e];
-            sa[4 + e] += a1[e]; qa[4 + e] += a1[e] * a1[e];
+            sa[e] += d0[e]; qa[e] += d0[e] * d0[e];
+            sa[4 + e] += d1[e]; qa[4 + e] += d1[e] * d1[e];
           }
         }
       }
@@ -554,27 +572,71 @@ __global__ __launch_bounds__(256) void k_phase_w(const float* __restrict__ W, Ph
 __device__ __forceinline__ void colstats_finalize(int C, double* __restrict__ stat, const BnFinalize& fin);
 // column sums of Y and Y^2 ( -> double atomics ), colreduce_block skeleton.  fin.ctr: the block that arrives LAST (every block drains its
 // atomics, then bumps the counter) turns the sums into scale / shift and the running statistics -- k_bn_finalize without its launch.
+// The float accumulators hold sums of DEVIATIONS from a pivot p -- the channel's first row, the same for every block -- and the emit turns
+// them back into the raw sums in double: sum y = s + n p, sum y^2 = q + 2 p s + n p^2 (n = the rows this block summed).  Raw float sums of
+// y^2 lose (mean / std)^2 of their precision in bn_finalize_channel's E[y^2] - mean^2: a channel whose mean lies 100 standard deviations
+// out (features with an offset under centre-heavy taps) came out with a variance 3e-3 off.  `stat` keeps its meaning (raw sums, double:
+// 53 bits carry the subtraction), so the statistics exchange and the finalize are untouched.
 __global__ __launch_bounds__(256) void k_colstats(const float* __restrict__ Y, int rows, int C, double* __restrict__ stat, BnFinalize fin) {
+  // this thread's columns and this block's row count, as colreduce_block deals them
+  const int q4 = (C + 3) >> 2, CL = q4 < COLREDUCE_CL ? q4 : COLREDUCE_CL, NR = 256 / CL, rpc = 4 * NR;
+  const int c4 = (int)blockIdx.x * CL + (int)threadIdx.x % CL;
+  const int c0 = c4 < q4 ? c4 * 4 : 0;
+  const float4 p = *reinterpret_cast<const float4*>(Y + c0);
+  double n = 0.0;
+  for (long k = blockIdx.y; k * rpc < rows; k += gridDim.y) n += (double)(rows - k * rpc < rpc ? rows - k * rpc : rpc);
+  double sdev[4] = {0.0, 0.0, 0.0, 0.0};
   colreduce_block<2>(
       rows, C,
       [&](int r, int c, float4* a) {
-        const float4 v = *reinterpret_cast<const float4*>(Y + (long)r * C + c);
+        float4 v = *reinterpret_cast<const float4*>(Y + (long)r * C + c);
+        v.x -= p.x; v.y -= p.y; v.z -= p.z; v.w -= p.w;
         a[0].x += v.x; a[0].y += v.y; a[0].z += v.z; a[0].w += v.w;
         a[1].x += v.x * v.x; a[1].y += v.y * v.y; a[1].z += v.z * v.z; a[1].w += v.w * v.w;
       },
-      [&](int col, int st, float v) { atomicAdd(&stat[st * C + col], (double)v); });
+      [&](int col, int st, float v) {      // (statistic 0 of the four columns comes first)
+        const int e = col & 3;
+        const double pe = (double)(e == 0 ? p.x : e == 1 ? p.y : e == 2 ? p.z : p.w);
+        if (st == 0) {
+          sdev[e] = (double)v;
+          atomicAdd(&stat[col], (double)v + n * pe);
+        } else {
+          atomicAdd(&stat[C + col], (double)v + 2.0 * pe * sdev[e] + n * pe * pe);
+        }
+      });
   colstats_finalize(C, stat, fin);
 }
-// ... from rows of PRE-SUMMED statistics [rows][2][C] (k_conv0_fwd_x3's per-tile sums): column sums of a (rows, 2 C) matrix land in stat's
-// [2][C] layout as they are
-__global__ __launch_bounds__(256) void k_colstats_tiles(const float* __restrict__ part, int rows, int C, double* __restrict__ stat, BnFinalize fin) {
-  colreduce_block<1>(
-      rows, 2 * C,
+// ... from rows of PRE-SUMMED statistics [rows][2][C] (k_conv0_fwd_x3's per-tile sums of deviations from the pivots behind the rows): a
+// row is a tile, tile x = (group x / tiles_t, steps (x % tiles_t) * C0_TT ..), so the tiles [0, x) hold cum(x) output steps; the emit
+// turns the block's sums back into raw sums in double, as k_colstats does
+__global__ __launch_bounds__(256) void k_colstats_tiles(const float* __restrict__ part, int rows, int C, int tiles_t, int T1,
+                                                        double* __restrict__ stat, BnFinalize fin) {
+  const int q4 = (C + 3) >> 2, CL = q4 < COLREDUCE_CL ? q4 : COLREDUCE_CL, NR = 256 / CL, rpc = 4 * NR;
+  const int c4 = (int)blockIdx.x * CL + (int)threadIdx.x % CL;
+  const int c0 = c4 < q4 ? c4 * 4 : 0;
+  const float4 p = *reinterpret_cast<const float4*>(part + (long)rows * 2 * C + c0);
+  auto cum = [&](long x) { const long g = x / tiles_t, t = (x - g * tiles_t) * C0_TT; return (double)(g * T1 + (t < T1 ? t : T1)); };
+  double n = 0.0;
+  for (long k = blockIdx.y; k * rpc < rows; k += gridDim.y) n += cum((k + 1) * rpc < rows ? (k + 1) * rpc : rows) - cum(k * rpc);
+  double sdev[4] = {0.0, 0.0, 0.0, 0.0};
+  colreduce_block<2>(
+      rows, C,
       [&](int r, int c, float4* a) {
         const float4 v = *reinterpret_cast<const float4*>(part + (long)r * 2 * C + c);
+        const float4 w = *reinterpret_cast<const float4*>(part + (long)r * 2 * C + C + c);
         a[0].x += v.x; a[0].y += v.y; a[0].z += v.z; a[0].w += v.w;
+        a[1].x += w.x; a[1].y += w.y; a[1].z += w.z; a[1].w += w.w;
       },
-      [&](int col, int st, float v) { atomicAdd(&stat[col], (double)v); });
+      [&](int col, int st, float v) {
+        const int e = col & 3;
+        const double pe = (double)(e == 0 ? p.x : e == 1 ? p.y : e == 2 ? p.z : p.w);
+        if (st == 0) {
+          sdev[e] = (double)v;
+          atomicAdd(&stat[col], (double)v + n * pe);
+        } else {
+          atomicAdd(&stat[C + col], (double)v + 2.0 * pe * sdev[e] + n * pe * pe);
+        }
+      });
   colstats_finalize(C, stat, fin);
 }
 __device__ __forceinline__ void colstats_finalize(int C, double* __restrict__ stat, const BnFinalize& fin) {
@@ -1161,7 +1223,7 @@ int astk_conv_bn_relu_fwd_sync(const astk_cnn_desc* d, const astk_cnn_layer_para
       BnFinalize f2 = fin;
       if (fused_fin) f2.ctr = P.fin_ctr + 64 * i;
       if (i == 0 && c0_stats)      // (layer 0, direct path: the tiles' sums came with the convolution -- 6.5 MB to add up instead of 262)
-        hipLaunchKernelGGL(k_colstats_tiles, colreduce_grid(P.c0_tiles, 2 * C), dim3(256), 0, s, P.c0_part, P.c0_tiles, C, P.stat[i], f2);
+        hipLaunchKernelGGL(k_colstats_tiles, colreduce_grid(P.c0_tiles, C), dim3(256), 0, s, P.c0_part, P.c0_tiles, C, cdiv(P.Tc[0], C0_TT), P.Tc[0], P.stat[i], f2);
       else
       hipLaunchKernelGGL(k_colstats, colreduce_grid(rows, C), dim3(256), 0, s, P.Y[i], rows, C, P.stat[i], f2);
       ASTK_LAUNCH_CHECK();

@@ -13,11 +13,20 @@ import torch
 OPT = {"type": 0, "lr": 1e-3, "l2": 1e-4, "grad_clip": 2, "grad_noise_eta": 0, "freeze": []}
 
 
-def make_inputs(cfg, B, T, D, L, V, seed=0):
+def with_offset(X, x_offset):
+    """X + x_offset (0.5 + d / D) per frequency bin d (float32): features that are not mean-normalised -- BatchNorm channels of layer 0
+    whose mean lies far from 0 (tests/range_cases.py cnn_draws uses the same rule)."""
+    if not x_offset:
+        return X
+    D = X.shape[-1]
+    return (X + np.float32(x_offset) * (0.5 + np.arange(D, dtype=np.float32) / D)).astype(np.float32)
+
+
+def make_inputs(cfg, B, T, D, L, V, seed=0, x_offset=0.0):
     from oracle import ast_ref as R
     P = R.init_params(cfg, D, V, seed=seed, dtype=np.float32)
     X, y = R.synth_batch(B, T, D, L, V, seed=seed + 1, dtype=np.float32)
-    return P, X, y
+    return P, with_offset(X, x_offset), y
 
 
 def gpu_model(cfg, P, D, V):
@@ -43,15 +52,15 @@ class _Fixed:
 _ORACLE = {}
 
 
-def oracle_case(name, cfgf, B, T, D, L, V, drop, teach):
+def oracle_case(name, cfgf, B, T, D, L, V, drop, teach, x_offset=0.0):
     """The float64 (reference truth) and float32 (what Chainer-on-NumPy would compute) oracle results of one parity case: computed once per
     process and shared -- by the three arithmetic schemes and by every schedule the case runs under -- and never changed afterwards."""
-    key = (name, B, T, D, L, V, drop, teach)
+    key = (name, B, T, D, L, V, drop, teach, x_offset)
     if key in _ORACLE:
         return _ORACLE[key]
     from oracle import ast_ref as R
     cfg = cfgf(drop)
-    P, X, y = make_inputs(cfg, B, T, D, L, V)
+    P, X, y = make_inputs(cfg, B, T, D, L, V, x_offset=x_offset)
     res = {}
     for dt in (np.float64, np.float32):
         m = R.RefModel(cfg, {k: v.astype(dt) for k, v in P.items()}, V)
@@ -81,6 +90,7 @@ def oracle_case(name, cfgf, B, T, D, L, V, drop, teach):
     more, later = [], []
     for step in range(2):
         X2, y2 = R.synth_batch(B, T, D, L, V, seed=100 + step, dtype=np.float32)
+        X2 = with_offset(X2, x_offset)
         more.append((X2, y2))
         later.append(R.train_step(mo, ref["opt"], X2.astype(np.float64), y2, 1.0, pyrandom=random.Random(1))[0])
     out = dict(cfg=cfg, P=P, X=X, y=y, loss=ref["loss"], gnorm=ref["gnorm"], loss_f32=res[np.float32]["loss"], flags=ref["flags"],
@@ -107,14 +117,15 @@ def assert_first_step_against_oracle(name, o, lv, gnorm, enc, grads):
         assert err <= tol, f"{name}: grad {k}: err {err:.3e} tol {tol:.3e}"
 
 
-def train_step_parity(name, cfgf, B, T, D, L, V, drop, teach, gemm_scheme, stream=None, knobs=None, inspect=None):
+def train_step_parity(name, cfgf, B, T, D, L, V, drop, teach, gemm_scheme, stream=None, knobs=None, inspect=None, x_offset=0.0):
     """One train step of the HIP path against the float64 oracle, two more updates, the parameter deltas and the BatchNorm statistics.
     `stream`: the torch stream the model runs on (None: the current one -- the legacy default stream in the suite); `knobs`: tuning knobs
-    in force for the GPU steps (astk_set_tuning; restored afterwards); `inspect(model)`: called behind the first step, inside the knobs."""
+    in force for the GPU steps (astk_set_tuning; restored afterwards); `inspect(model)`: called behind the first step, inside the knobs;
+    `x_offset`: a per-bin offset on the features (with_offset)."""
     from oracle.ast_ref_torch import masks_from_recording
     from ast_amd import _lib, optimizers as O
     from ast_amd.seq2seq import using_config
-    o = oracle_case(name, cfgf, B, T, D, L, V, drop, teach)
+    o = oracle_case(name, cfgf, B, T, D, L, V, drop, teach, x_offset)
     cfg, P, X, y = o["cfg"], o["P"], o["X"], o["y"]
     on_stream = torch.cuda.stream(stream) if stream is not None else contextlib.nullcontext()
     with _lib.tuning(knobs or {}), on_stream:

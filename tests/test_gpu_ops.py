@@ -8,6 +8,7 @@ import numpy as np
 import pytest
 import torch
 
+import range_cases
 from conftest import tiny_cfg
 
 pytestmark = pytest.mark.gpu
@@ -170,18 +171,16 @@ def _cnn_desc(cfg, B, T, D):
                                          (2, 170, 26, 16, 8), (2, 24, 80, 32, 8)])
 @pytest.mark.parametrize("with_noise", [False, True])
 def test_cnn_fwd_bwd(lib, B, T, D, c0, c1, with_noise, gemm_split):
+    _cnn_case(lib, B, T, D, c0, c1, with_noise)
+
+
+def _cnn_case(lib, B, T, D, c0, c1, with_noise, x_offset=0.0, seed=0, layer1_stats=False, **draw_kw):
+    """x_offset, seed: tests/range_cases.py cnn_draws (the input with a per-bin offset: BatchNorm channels whose mean lies far from 0);
+    layer1_stats: the running statistics of layer 1 are compared too; draw_kw: cnn_draws' ramp / centre_taps."""
     from ast_amd._lib import CnnLayerGrads, CnnLayerParams
-    from oracle.ast_ref import init_params
     from oracle.ast_ref_torch import cnn_torch
-    cfg = tiny_cfg(c0=c0, c1=c1)
-    P = init_params(cfg, D, 11, seed=1, dtype=np.float64)
-    rng = np.random.default_rng(0)
-    for i in range(2):                       # non-trivial BN affine
-        P[f"CNN_{i}_bn/gamma"] = 1 + 0.3 * rng.standard_normal(P[f"CNN_{i}_bn/gamma"].shape)
-        P[f"CNN_{i}_bn/beta"] = 0.2 * rng.standard_normal(P[f"CNN_{i}_bn/beta"].shape)
+    cfg, P, X, noise, rng = range_cases.cnn_draws(B, T, D, c0, c1, with_noise, x_offset=x_offset, seed=seed, **draw_kw)
     Pt = {k: torch.tensor(v, dtype=torch.float64, requires_grad=k.startswith("CNN") and "avg" not in k) for k, v in P.items()}
-    X = rng.standard_normal((B, T, D))
-    noise = rng.normal(1.0, 0.25, X.shape) if with_noise else None
     # Near-kink units: two valid float32 evaluations of one batch can disagree on the SIGN of a post-BatchNorm pre-activation that lies
     # within rounding of zero, and the unit's whole upstream gradient then enters or leaves its channel's sums -- ONE flipped unit moves that
     # channel's weight gradient by ~1 / sqrt(rows) of itself (round 6: a different, equally valid, summation order of the layer-1 forward
@@ -227,6 +226,13 @@ def test_cnn_fwd_bwd(lib, B, T, D, c0, c1, with_noise, gemm_split):
     m = y0.numel() // y0.shape[1]
     close(prm["CNN_0_bn/avg_mean"], 0.1 * y0.mean(dim=(0, 2, 3)), msg="avg_mean")
     close(prm["CNN_0_bn/avg_var"], 0.9 + 0.1 * y0.var(dim=(0, 2, 3), unbiased=False) * m / (m - 1), msg="avg_var")
+    if layer1_stats:
+        l1 = cfg["cnn_config"]["cnn_layers"][1]
+        h1 = torch.relu(torch.nn.functional.batch_norm(y0, None, None, Pt["CNN_0_bn/gamma"].detach(), Pt["CNN_0_bn/beta"].detach(), training=True, eps=2e-5))
+        y1 = torch.nn.functional.conv2d(h1, Pt["CNN_1/W"].detach(), stride=tuple(l1["stride"]), padding=tuple(l1["pad"]))
+        m1 = y1.numel() // y1.shape[1]
+        close(prm["CNN_1_bn/avg_mean"], 0.1 * y1.mean(dim=(0, 2, 3)), msg="avg_mean, layer 1")
+        close(prm["CNN_1_bn/avg_var"], 0.9 + 0.1 * y1.var(dim=(0, 2, 3), unbiased=False) * m1 / (m1 - 1), msg="avg_var, layer 1")
     g = dev(gout)
     ok(lib, lib.astk_conv_bn_relu_bwd(C.byref(cd), cp, cg, vp(g), vp(ws), nbytes, stream()))
     ws.check("cnn bwd")
@@ -406,29 +412,19 @@ def _concurrent_stream(lib, main):
     pytest.skip("no pair of concurrently executing streams on this device")
 
 
-def _lstm_stack_case(lib, T, B, in_dim, h, nl, masks, side=False, chunks=None, exact=True, late=False):
+def _lstm_stack_case(lib, T, B, in_dim, h, nl, masks, side=False, chunks=None, exact=True, late=False, bias_gain=1.0, x_gain=1.0):
     """chunks (with side): the forward chunks the library must plan for this case; exact: the side-stream forward results are compared bit for
-    bit with an in-line call (else within close()); late: the side stream is held back (see below)."""
+    bit with an in-line call (else within close()); late: the side stream is held back (see below); bias_gain, x_gain: tests/range_cases.py
+    lstm_draws (gains on the biases and the input: saturated gates)."""
     from ast_amd._lib import LstmGrads, LstmParams, LstmStackDesc
     from oracle.ast_ref_torch import encoder_torch
-    rng = np.random.default_rng(T + B)
     cfg = {"rnn_config": {"enc_layers": nl}}
-    P, names = {}, []
-    for pat in ("L{}_enc", "L{}_rev_enc"):
-        n_in = in_dim
-        for k in range(nl):
-            n = pat.format(k)
-            names.append(n)
-            P[n + "/upward/W"] = rng.standard_normal((4 * h, n_in)) / np.sqrt(n_in)
-            P[n + "/upward/b"] = rng.standard_normal(4 * h) * 0.3
-            P[n + "/lateral/W"] = rng.standard_normal((4 * h, h)) / np.sqrt(h)
-            n_in = h
-    x = rng.standard_normal((T, B, in_dim))
-    mk = ((rng.random((2, nl, T, B, h)) >= 0.3) / 0.7) if masks else None
+    c = range_cases.lstm_draws(T, B, in_dim, h, nl, masks, bias_gain=bias_gain, x_gain=x_gain)
+    P, names, x, mk, g_enc, g_c, g_h = (c[k] for k in ("P", "names", "x", "mk", "g_enc", "g_c", "g_h"))
     Pt = {k: torch.tensor(v, requires_grad=True) for k, v in P.items()}
     xt = torch.tensor(x, requires_grad=True)
     enc, cT, hT = encoder_torch(cfg, Pt, xt, torch.tensor(mk) if masks else None)
-    g_enc, g_c, g_h = rng.standard_normal(enc.shape), rng.standard_normal(cT.shape), rng.standard_normal(hT.shape)
+    assert g_enc.shape == enc.shape and g_c.shape == cT.shape and g_h.shape == hT.shape
     (enc * torch.tensor(g_enc)).sum().add((cT * torch.tensor(g_c)).sum()).add((hT * torch.tensor(g_h)).sum()).backward()
     d = LstmStackDesc(T, B, in_dim, h, nl, 2)
     if h in (64, 128, 256, 512, 1024):
@@ -626,29 +622,11 @@ def test_attention_step(lib, B, T, H):
 
 
 # ------------------------------------------------------------------ decoder loop
-def _dec_setup(lib, B, L, T, H, E, A, V, nl, masks, seed=0):
+def _dec_setup(lib, B, L, T, H, E, A, V, nl, masks, seed=0, enc_gain=1.0, out_gain=1.0, bias_gain=1.0):
+    """enc_gain, out_gain, bias_gain: tests/range_cases.py dec_draws (wide attention scores, wide logits, saturated gates)."""
     from ast_amd._lib import DecoderDesc, DecoderGrads, DecoderParams
-    rng = np.random.default_rng(seed)
-    P = {"embed_dec/W": rng.standard_normal((V, E)), "attn_Wa/W": rng.standard_normal((H, H)) / np.sqrt(H),
-         "attn_Wa/b": rng.standard_normal(H) * 0.1, "context/W": rng.standard_normal((A, 2 * H)) / np.sqrt(2 * H),
-         "context/b": rng.standard_normal(A) * 0.1, "out/W": rng.standard_normal((V, A)) / np.sqrt(A),
-         "out/b": rng.standard_normal(V) * 0.1}
-    n_in = E + A
-    for k in range(nl):
-        P[f"L{k}_dec/upward/W"] = rng.standard_normal((4 * H, n_in)) / np.sqrt(n_in)
-        P[f"L{k}_dec/upward/b"] = rng.standard_normal(4 * H) * 0.2
-        P[f"L{k}_dec/lateral/W"] = rng.standard_normal((4 * H, H)) / np.sqrt(H)
-        n_in = H
-    enc = rng.standard_normal((B, T, H)) * 0.5
-    c0, h0 = rng.standard_normal((nl, B, H)) * 0.5, np.tanh(rng.standard_normal((nl, B, H)))
-    y = np.zeros((B, L), np.int32)
-    for b in range(B):
-        n = L if (b == 0 or L <= 3) else int(rng.integers(max(L // 2, 3), L + 1))
-        y[b, 0], y[b, 1:n - 1], y[b, n - 1] = 1, rng.integers(4, V, size=n - 2), 2
-    S = L - 1
-    flags = [1] + [int(rng.random() < 0.5) for _ in range(S - 2)] + [1] if S >= 2 else [1] * S
-    em = ((rng.random((S, B, E)) >= 0.3) / 0.7) if masks else None
-    rm = ((rng.random((nl, S, B, H)) >= 0.3) / 0.7) if masks else None
+    c = range_cases.dec_draws(B, L, T, H, E, A, V, nl, masks, seed=seed, enc_gain=enc_gain, out_gain=out_gain, bias_gain=bias_gain)
+    P, enc, c0, h0, y, flags, em, rm, S = (c[k] for k in ("P", "enc", "c0", "h0", "y", "flags", "em", "rm", "S"))
     d = DecoderDesc(B, L, T, H, E, A, V, nl)
     prm = {k: dev(v) for k, v in P.items()}
     grd = {k: torch.zeros_like(v) for k, v in prm.items()}

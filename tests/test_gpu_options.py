@@ -209,14 +209,18 @@ def _stream():
     return C.c_void_p(torch.cuda.current_stream().cuda_stream)
 
 
-@pytest.mark.parametrize("rows,n,ld", [(7, 32, 32), (130, 256, 512), (33, 100, 104), (2000, 512, 512)])
-def test_layernorm_kernels(rows, n, ld):
+# (the rows with an offset: x + 64 -- a row mean 32 standard deviations from 0; the kernels form their variances in two passes, the rows pin that)
+@pytest.mark.parametrize("rows,n,ld,offset", [(7, 32, 32, 0), (130, 256, 512, 0), (33, 100, 104, 0), (2000, 512, 512, 0), (33, 100, 104, 64), (130, 256, 512, 64)],
+                         ids=["7-32-32", "130-256-512", "33-100-104", "2000-512-512", "33-100-104-offset64", "130-256-512-offset64"])
+def test_layernorm_kernels(rows, n, ld, offset):
     """astk_layernorm_fwd / _bwd against a float64 torch restatement of F.layer_normalization (biased variance, eps inside the root),
     strided rows (halves of a wider buffer), accumulating parameter gradients."""
     from ast_amd import _lib
     lib = _lib.load()
     gen = torch.Generator(device="cuda").manual_seed(rows + n)
     x = torch.randn(rows, ld, device="cuda", generator=gen) * 2 + 0.5
+    if offset:
+        x = x + offset
     gamma = torch.randn(n, device="cuda", generator=gen)
     beta = torch.randn(n, device="cuda", generator=gen)
     dy = torch.randn(rows, ld, device="cuda", generator=gen)
@@ -238,14 +242,22 @@ def test_layernorm_kernels(rows, n, ld):
     assert float((dbet.double() - 2 - bd.grad).abs().max()) < 2e-5 * float(bd.grad.abs().max()) + 1e-5
 
 
-@pytest.mark.parametrize("T,B,Cc", [(5, 3, 8), (40, 32, 64), (17, 2, 100)])
-def test_step_batchnorm_relu_kernels(T, B, Cc):
+# (the rows with an offset: z + 64 -- channel means 43 standard deviations from 0.  On (17, 2, 100) a step's statistics come from TWO rows: the
+#  deviation d = (z1 - z2) / 2 carries the rounding of the mean, half an ulp of 64 = 3.8e-6, and the output moves by that over sqrt(d^2 + eps)
+#  -- float32 itself misses this test's 2e-5 where the two rows nearly tie.  Like the CNN test's near-kink rule, the (step, channel) pairs
+#  with |z1 - z2| < 0.5 are left out there -- their outputs are not compared and their upstream gradient is 0 -- which bounds the effect by
+#  3.8e-6 / 0.25 = 1.5e-5 of gamma; tests/test_ranges_host.py shows the float32 restatement inside half the bound on what remains)
+@pytest.mark.parametrize("T,B,Cc,offset", [(5, 3, 8, 0), (40, 32, 64, 0), (17, 2, 100, 0), (17, 2, 100, 64), (40, 32, 64, 64)],
+                         ids=["5-3-8", "40-32-64", "17-2-100", "17-2-100-offset64", "40-32-64-offset64"])
+def test_step_batchnorm_relu_kernels(T, B, Cc, offset):
     """astk_step_bn_relu_fwd / _bwd: per-time-step BatchNorm over the B rows of the step + ReLU, running statistics advanced T times in step
     order with the unbiased-variance factor B / (B - 1) (Chainer-sem A4 on a 2-D input), eval mode on the running statistics."""
     from ast_amd import _lib
     lib = _lib.load()
     gen = torch.Generator(device="cuda").manual_seed(T * B + Cc)
     z = torch.randn(T, B, Cc, device="cuda", generator=gen) * 1.5 + 0.3
+    if offset:
+        z = z + offset
     gamma, beta = torch.randn(Cc, device="cuda", generator=gen), torch.randn(Cc, device="cuda", generator=gen)
     am0, av0 = torch.randn(Cc, device="cuda", generator=gen), torch.rand(Cc, device="cuda", generator=gen) + 0.5
     am, av = am0.clone(), av0.clone()
@@ -256,18 +268,26 @@ def test_step_batchnorm_relu_kernels(T, B, Cc):
     mu = zd.mean(1, keepdim=True)
     var = ((zd - mu) ** 2).mean(1, keepdim=True)
     od = torch.relu((zd - mu) / torch.sqrt(var + 2e-5) * gd + bd)
-    assert float((out.double() - od).abs().max()) < 2e-5 * float(od.abs().max())
+    keep = torch.ones(T, 1, Cc, dtype=torch.float64, device="cuda")
+    if offset and B == 2:
+        keep = ((zd[:, 0] - zd[:, 1]).abs() >= 0.5).double().unsqueeze(1).detach()
+        assert 0.7 < float(keep.mean()) < 1.0
+    assert float(((out.double() - od) * keep).abs().max()) < 2e-5 * float(od.abs().max())
     wm, wv = am0.double(), av0.double()
     for t in range(T):
         wm = 0.9 * wm + 0.1 * mu[t, 0].detach()
         wv = 0.9 * wv + 0.1 * (B / max(B - 1.0, 1.0)) * var[t, 0].detach()
-    assert float((am.double() - wm).abs().max()) < 1e-5 and float((av.double() - wv).abs().max()) < 1e-5 * float(wv.abs().max()) + 1e-5
-    d_out = torch.randn(T, B, Cc, device="cuda", generator=gen)
+    assert float((am.double() - wm).abs().max()) < 1e-5 * max(1.0, offset) and float((av.double() - wv).abs().max()) < 1e-5 * float(wv.abs().max()) + 1e-5
+    d_out = torch.randn(T, B, Cc, device="cuda", generator=gen) * keep.float()
     od.backward(d_out.double())
     dz = torch.empty_like(z)
     dg, db = torch.zeros(Cc, device="cuda"), torch.zeros(Cc, device="cuda")
     _lib.check(lib.astk_step_bn_relu_bwd(T, B, Cc, _vp(z), _vp(stats), _vp(gamma), 2e-5, _vp(out), _vp(d_out), _vp(dz), _vp(dg), _vp(db), _stream()))
-    assert float((dz.double() - zd.grad).abs().max()) < 5e-5 * float(zd.grad.abs().max())
+    # (two rows per step: x_hat = +-(1 - eps / 2 d^2), so dz is a residual of order eps / d^2 <= 3e-4 of gamma dy / sigma and its largest entry
+    #  is ~2e-3; what float32 can hold of it is set by x_hat's rounding, 1.5e-5 (see the parametrisation's note), times |gamma dy| / sigma
+    #  <= 3 * 3 / 0.25: an ABSOLUTE 5e-4 on that row.  Measured on an MI355X: 2.2e-4.)
+    dz_tol = 5e-4 if (offset and B == 2) else 5e-5 * float(zd.grad.abs().max())
+    assert float((dz.double() - zd.grad).abs().max()) < dz_tol
     assert float((dg.double() - gd.grad).abs().max()) < 5e-5 * float(gd.grad.abs().max()) + 1e-5
     assert float((db.double() - bd.grad).abs().max()) < 5e-5 * float(bd.grad.abs().max()) + 1e-5
     # eval mode: the running statistics, no update
