@@ -18,6 +18,8 @@ struct DecPersistBuffers {  // slices of decoder.hip's DecPlan
   const float *c0, *h0;
 };
 bool decoder_persist_applicable(const astk_decoder_desc* d, int* nsplit_out, int* chunk_out);
+// a slice of `chunk` rows at H = 512 takes the specialised (NC = 8) attention phase: astk_decoder_path reports it
+bool pdec_special(int H, int chunk);
 int decoder_persist_fwd_launch(const astk_decoder_desc* d, const astk_decoder_params* prm, const float* enc, const int32_t* y,
                                const int32_t* ytgt, const int32_t* use_truth, const float* emb_mask, const float* rnn_masks, const DecPersistBuffers& bf,
                                float* loss, int32_t* pred_out, hipStream_t s);

@@ -2126,7 +2126,7 @@ __global__ __launch_bounds__(256) void k_decoder_post(const float* __restrict__ 
 
 }  // namespace
 
-static bool pdec_special(int H, int chunk) { return H == 512 && chunk <= PDEC_CHUNK_MAX; }     // the NC = 8 attention phase
+bool pdec_special(int H, int chunk) { return H == 512 && chunk <= PDEC_CHUNK_MAX; }     // the NC = 8 attention phase
 static int pdec_res_rows(int H, int chunk) { return pdec_special(H, chunk) && chunk > PDEC_RES_ROWS ? PDEC_RES_ROWS : chunk; }
 static size_t pdec_lds_floats(int chunk, int H, int nsplit) {
   size_t scratch = (size_t)H + 2 * (size_t)((chunk + 3) & ~3) + 16;

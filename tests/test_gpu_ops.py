@@ -770,6 +770,46 @@ def test_decoder_backward_refuses_a_capped_phase_in_deterministic_mode(lib):
     ws.check("decoder bwd, capped parameter phase")
 
 
+def test_decoder_backward_refuses_a_workspace_whose_forward_took_another_path(lib, tune):
+    """The kernel path and the workspace carve follow the tuning knobs of each call, so a backward call made under other knobs than its
+    forward call would read the saved activations at shifted offsets.  The forward records the path it took on the workspace; a backward
+    call that would take another one (here: dec.persist switched off in between) is refused before anything is launched, and with the
+    knob restored the same workspace serves forward and backward."""
+    B, L, T, H, E, A, V, nl = 5, 9, 23, 64, 16, 32, 57, 1
+    s = _dec_setup(lib, B, L, T, H, E, A, V, nl, False, seed=B + L + 4)
+    d = s["d"]
+    assert lib.astk_decoder_path(C.byref(d)) & 1, "persistent decoder path not taken"
+    nbytes = lib.astk_decoder_workspace_bytes(C.byref(d))
+    ws = GuardedWS(nbytes)
+    enc_d, c0_d, h0_d = dev(s["enc"]), dev(s["c0"]), dev(s["h0"])
+    y_d, fl_d = dev(s["y"], torch.int32), dev(np.asarray(s["flags"]), torch.int32)
+    loss_d, pred_d = torch.zeros(1, device="cuda"), torch.zeros(s["S"], B, dtype=torch.int32, device="cuda")
+    outs = {"d_enc": torch.full((B, T, H), 3.0, device="cuda"), "d_c0": torch.full((nl, B, H), 5.0, device="cuda"),
+            "d_h0": torch.full((nl, B, H), 7.0, device="cuda")}
+    for v in s["grd"].values():
+        v.fill_(2.0)                                             # (a launch that accumulates, stores or zeroes would show)
+    ok(lib, lib.astk_decoder_fwd(C.byref(d), C.byref(s["dp"]), vp(enc_d), vp(c0_d), vp(h0_d), vp(y_d), vp(fl_d), None, None,
+                                 vp(loss_d), vp(pred_d), vp(ws), nbytes, stream()))
+    torch.cuda.synchronize()
+    before = {k: v.clone() for k, v in list(s["grd"].items()) + list(outs.items())}
+    tune("dec.persist", 0, lib)
+    assert not (lib.astk_decoder_path(C.byref(d)) & 1)
+    rc = lib.astk_decoder_bwd(C.byref(d), C.byref(s["dp"]), C.byref(s["dg"]), vp(enc_d), vp(c0_d), vp(h0_d), vp(y_d), None, None,
+                              vp(outs["d_enc"]), vp(outs["d_c0"]), vp(outs["d_h0"]), vp(ws), nbytes, stream())
+    assert rc != 0
+    msg = lib.astk_last_error().decode()
+    assert "took kernel path 1" in msg, msg
+    torch.cuda.synchronize()
+    for k, v in list(s["grd"].items()) + list(outs.items()):
+        assert torch.equal(v, before[k]), f"the refused call launched something ({k})"
+    ws.check("decoder bwd, refused")
+    tune("dec.persist", 1, lib)
+    assert lib.astk_decoder_path(C.byref(d)) & 1
+    for v in s["grd"].values():
+        v.zero_()
+    _decoder_case(lib, s, B, L, T, H, E, A, V, nl, False, ws=ws)
+
+
 def test_wide_decoder_path_and_bounded_spins(lib, tune):
     """configs[4]'s decoder (H = A = 1024, E = 128, one layer, 32 rows, T'' = 200, V = 8004) reports decoder_wide.hip's persistent loops
     (astk_decoder_path bit 4), and their spins are bounded like every other persistent kernel's: with the knob persist.spin_limit = 1 the
@@ -802,7 +842,8 @@ def test_wide_decoder_path_and_bounded_spins(lib, tune):
     ws.check("wide decoder, timed-out launches")
 
 
-def _decoder_case(lib, s, B, L, T, H, E, A, V, nl, masks):
+def _decoder_case(lib, s, B, L, T, H, E, A, V, nl, masks, ws=None):
+    """ws: a GuardedWS of astk_decoder_workspace_bytes to run on (default: a fresh one)."""
     from oracle.ast_ref_torch import decoder_torch
     cfg = {"rnn_config": {"dec_layers": nl, "attn_units": A}}
     Pt = {k: torch.tensor(v, requires_grad=True) for k, v in s["P"].items()}
@@ -812,7 +853,8 @@ def _decoder_case(lib, s, B, L, T, H, E, A, V, nl, masks):
     loss_ref, pred_ref = decoder_torch(cfg, Pt, enc_t, c0_t, h0_t, s["y"], s["flags"], V, tt(s["em"]), tt(s["rm"]))
     loss_ref.backward()
     nbytes = lib.astk_decoder_workspace_bytes(C.byref(s["d"]))
-    ws = GuardedWS(nbytes)
+    ws = ws or GuardedWS(nbytes)
+    assert ws.nbytes == nbytes
     enc_d, c0_d, h0_d = dev(s["enc"]), dev(s["c0"]), dev(s["h0"])
     y_d, fl_d = dev(s["y"], torch.int32), dev(np.asarray(s["flags"]), torch.int32)
     em_d, rm_d = (dev(s["em"]) if masks else None), (dev(s["rm"]) if masks else None)
