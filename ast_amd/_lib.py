@@ -177,6 +177,9 @@ SIGNATURES = {
     "astk_sample_workspace_bytes": (_SZ, [C.POINTER(DecoderDesc), _I]),
     "astk_sample_decode": (C.c_int, [C.POINTER(DecoderDesc), C.POINTER(DecoderParams), _VP, _VP, _VP, _I, _I, _I, _VP, _F, _VP, _VP, _VP, _VP,
                                      _VP, _SZ, _VP]),
+    "astk_sample_topk_workspace_bytes": (_SZ, [C.POINTER(DecoderDesc), _I]),
+    "astk_sample_decode_topk": (C.c_int, [C.POINTER(DecoderDesc), C.POINTER(DecoderParams), _VP, _VP, _VP, _I, _I, _I, _VP, _F, _I, _F, _VP,
+                                          _VP, _VP, _VP, _VP, _VP, _SZ, _VP, _VP]),
     "astk_gumbel_rows": (C.c_int, [_VP, _I, _I, _I, _VP, _VP]),
     "astk_sample_row_key": (_U64, [_U64, _U64]),
     "astk_forced_workspace_bytes": (_SZ, [C.POINTER(DecoderDesc), _I, _I]),

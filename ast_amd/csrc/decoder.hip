@@ -1115,6 +1115,16 @@ int astk_sample_decode_rows(const astk_decoder_desc* d, const astk_decoder_param
                               row_len, (hipStream_t)stream);
 }
 
+size_t astk_sample_topk_workspace_bytes(const astk_decoder_desc* d, int stop_limit) { return sample_topk_workspace_bytes(d, stop_limit); }
+
+int astk_sample_decode_topk(const astk_decoder_desc* d, const astk_decoder_params* p, const float* enc, const float* c0, const float* h0,
+                            int go, int eos, int stop_limit, const uint64_t* row_keys, float inv_temp, int top_k, float top_p,
+                            int32_t* tokens, float* logp, int32_t* n_kept, int32_t* n_steps, float* status_dst, void* ws, size_t ws_bytes,
+                            void* stream, const int32_t* row_len) {
+  return sample_decode_topk_launch(d, p, enc, c0, h0, go, eos, stop_limit, row_keys, inv_temp, top_k, top_p, tokens, logp, n_kept, n_steps,
+                                   status_dst, ws, ws_bytes, row_len, (hipStream_t)stream);
+}
+
 int astk_gumbel_rows(const uint64_t* row_keys, int B, int step, int V, float* out, void* stream) {
   return gumbel_rows_launch(row_keys, B, step, V, out, (hipStream_t)stream);
 }

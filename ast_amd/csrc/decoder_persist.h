@@ -53,6 +53,11 @@ size_t sample_workspace_bytes(const astk_decoder_desc* d, int stop_limit);
 int sample_decode_launch(const astk_decoder_desc* d, const astk_decoder_params* prm, const float* enc, const float* c0, const float* h0, int go,
                          int eos, int stop_limit, const uint64_t* row_keys, float inv_temp, int32_t* tokens, float* logp, int32_t* n_steps,
                          float* status_dst, void* ws, size_t ws_bytes, const int32_t* row_len, hipStream_t s);
+size_t sample_topk_workspace_bytes(const astk_decoder_desc* d, int stop_limit);
+int sample_decode_topk_launch(const astk_decoder_desc* d, const astk_decoder_params* prm, const float* enc, const float* c0, const float* h0,
+                              int go, int eos, int stop_limit, const uint64_t* row_keys, float inv_temp, int top_k, float top_p,
+                              int32_t* tokens, float* logp, int32_t* n_kept, int32_t* n_steps, float* status_dst, void* ws, size_t ws_bytes,
+                              const int32_t* row_len, hipStream_t s);
 int gumbel_rows_launch(const uint64_t* row_keys, int B, int step, int V, float* out, hipStream_t s);
 size_t forced_workspace_bytes(const astk_decoder_desc* d, int n_steps, int with_alpha);
 int forced_score_launch(const astk_decoder_desc* d, const astk_decoder_params* prm, const float* enc, const float* c0, const float* h0,

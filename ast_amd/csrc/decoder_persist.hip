@@ -100,6 +100,11 @@ struct PDecArgs {
   double* BSCORE;          //     state the slot's hypothesis was last expanded from (-1: none), all rewritten at every step
   int32_t* BORG;
   float* CS[PDEC_MAX_LAYERS];   // [S + 1][B][H] c of every step (slot s + 1 = after step s): the final states are gathered behind the loop
+  // truncated sampled mode (TK): the draw among the top_k largest xs = logits * inv_temp, cut to the nucleus of mass top_p (include/astk.h
+  // astk_sample_decode_topk).  LOGITS = the step's xs [S][B][Vp], kept by P5 for P6's top_k sweeps; row_keys, inv_temp, LSE = LOGP as in SM
+  int top_k;
+  float top_p;
+  int32_t* NKEPT;          // [S][B] the kept count m of every draw, or null
 };
 
 // A UNIFORM base pointer, re-formed where it is used (opaque to loop-invariant code motion).  An element address is then base (scalar
@@ -264,19 +269,52 @@ __device__ __forceinline__ void mfma_blocks(f32x4& acc, const float4* a, const f
 // the raw scores of P3 / P3b.  DESIGN.md section 13.
 // SM (with GR and SC, without FD), sampled decoding -- ancestral sampling by the Gumbel-max identity: the draw in P5, its merge in P6.
 // DESIGN.md section 14.
+// TK (with GR and SC, without FD, SM and BM), truncated sampled decoding -- top-k / nucleus: P5 keeps the tempered logits, P6 finds a row's
+// top_k best, cuts them to the nucleus and draws among the kept by the Gumbel-max identity.  DESIGN.md section 20.
 // BM (with GR and SC, without FD and SM), beam search -- every slot of every utterance is one row: P5 keeps the logits, the beam branch of
 // P6 selects, the cells (P1, P1b) follow the parents.  DESIGN.md section 16.
+// A stored row's K best values, by K sweeps on the 16 lanes of the row (beam mode's and the truncated sampled mode's P6): sweep k keeps the
+// first value behind the pick of sweep k-1 -- higher value first, equal ones lower id first -- from 16-byte sc1 reads of the row P5 stored
+// written through at float offset `lrow`; lane k of the row (sub == k) keeps pick k in (my_x, my_i).  K <= 16, K <= V.
+__device__ __forceinline__ void row_top_k(__amdgpu_buffer_rsrc_t r_lg, long lrow, int V, int K, int sub, float& my_x, int& my_i) {
+  float pv = INFINITY;
+  int pi = -1;
+  for (int k = 0; k < K; ++k) {
+    float bv = -INFINITY;
+    int bi = -1;
+    for (int j = sub * 4; j < V; j += 64) {
+      const float4 v = ldb128_sc1(r_lg, lrow + j);
+      const float xs[4] = {v.x, v.y, v.z, v.w};
+#pragma unroll
+      for (int e = 0; e < 4; ++e) {
+        const int n = j + e;
+        const float x = xs[e];
+        if (n < V && (pv > x || (pv == x && pi < n)) && (bi < 0 || x > bv || (x == bv && n < bi))) { bv = x; bi = n; }
+      }
+    }
+#pragma unroll
+    for (int o = 8; o > 0; o >>= 1) {
+      const float ov = __shfl_xor(bv, o);
+      const int oi = __shfl_xor(bi, o);
+      if (oi >= 0 && (bi < 0 || ov > bv || (ov == bv && oi < bi))) { bv = ov; bi = oi; }
+    }
+    if (sub == k) { my_x = bv; my_i = bi; }
+    pv = bv; pi = bi;
+  }
+}
 // Two partial sums of exponentials, `se` relative to m and `os` relative to om, merged relative to nm = max(m, om): a side whose reference
 // is -inf holds nothing (its factor would be exp(nan)).  P6 merges the guarded form three times; its sweep over the tile records, which
 // guards one side only, is another expression and stays where it is.
 __device__ __forceinline__ float lse_merge(float m, float se, float om, float os, float nm) {
   return (m == -INFINITY ? 0.f : se * expf(m - nm)) + (om == -INFINITY ? 0.f : os * expf(om - nm));
 }
-enum PDecMode { PDEC_TRAIN, PDEC_GREEDY, PDEC_SCORED, PDEC_FORCED, PDEC_SAMPLED, PDEC_BEAM };
+enum PDecMode { PDEC_TRAIN, PDEC_GREEDY, PDEC_SCORED, PDEC_FORCED, PDEC_SAMPLED, PDEC_BEAM, PDEC_TOPK };
 template <int NC, int NL, bool XS, PDecMode MODE>
 __device__ __forceinline__ void decoder_persist_fwd_body(const PDecArgs& a) {
   constexpr bool GR = MODE != PDEC_TRAIN, SC = GR && MODE != PDEC_GREEDY, FD = MODE == PDEC_FORCED, SM = MODE == PDEC_SAMPLED;
   constexpr bool BM = MODE == PDEC_BEAM;
+  constexpr bool TK = MODE == PDEC_TOPK;   // (with GR and SC, without SM: the draw is P6's)
+  constexpr bool DRAW = SM || TK;          // the modes that draw: the row keys and the sticky done flags in LDS
   constexpr bool STOP = GR && !FD;         // the greedy modes' stop word exists
   constexpr bool SUMS = !GR || SC;         // P5 / P6 keep the sum of exponentials and the target logit
   extern __shared__ __attribute__((aligned(16))) float lds[];   // enc slice [chunk][H], encA slice [chunk][H], scratch
@@ -289,7 +327,7 @@ __device__ __forceinline__ void decoder_persist_fwd_body(const PDecArgs& a) {
   __shared__ int s_wdone[4];               // GR: per wave of the CE role, all of its rows are done
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   if (GR && tid == 0) s_stop = 0;          // (the first barrier below orders it before every use)
-  if constexpr (SM) {
+  if constexpr (DRAW) {
     if (tid < PDEC_SM_ROWS) sm_row_keys()[tid] = a.row_keys[min(tid, a.B - 1)];     // (ordered by that barrier too; B <= PDEC_SM_ROWS)
   }
   const int wg = blockIdx.x;
@@ -457,7 +495,7 @@ __device__ __forceinline__ void decoder_persist_fwd_body(const PDecArgs& a) {
 #define TICK(i) if (timing) { const long long now_ = wall_clock64(); tk[i] += now_ - tlast; tlast = now_; }
   int p6_pending = -1;
   bool row_done = ce_rank * 16 + (tid >> 4) >= B;     // GR, CE role: sticky "this thread's row has emitted EOS" (padding rows: done)
-  if constexpr (SM) {
+  if constexpr (DRAW) {
     if ((tid & 15) == 0) sm_row_done()[tid >> 4] = row_done ? 1 : 0;
   }
   bool tile_done = false;                             // GR, CE role (thread 0): this batch tile has reported
@@ -478,6 +516,8 @@ __device__ __forceinline__ void decoder_persist_fwd_body(const PDecArgs& a) {
   // FD: stores LOGP = log p(y[b][s+1]) (PDecArgs: LSE), the confidence max logit - LSE (LOSSROWS, or null) and the argmax (PRED, or null).
   // SM: merges the winner by z and the sums relative to the largest reference, stores the token and LOGP = (xs_tok - ref) - logf(se), then
   // runs the greedy branch on the SAMPLED token as it stands: no wait, arrival, counter or exit condition is added.
+  // TK: behind the same wait, the draw among the kept candidates of the stored row (top_k sweeps, the nucleus cut, Gumbel-max), then the
+  // stores of SM plus the kept count, then the greedy branch on the drawn token as SM runs it: no wait, arrival, counter or exit is added.
   auto run_p6 = [&](const int s) -> bool {
       const int bt = ce_rank, m0 = bt * 16;
       const int row = m0 + (tid >> 4), sub = tid & 15;       // 16 threads per row sweep the tiles
@@ -510,34 +550,10 @@ __device__ __forceinline__ void decoder_persist_fwd_body(const PDecArgs& a) {
           mx = nm;
         }
         const float lg = logf(se);
-        // the row's K best tokens: sweep k keeps the first logit behind the pick of sweep k-1 (16 lanes per row, 16-byte reads of the
-        // row P5 stored); lane k of the row keeps pick k
-        const __amdgpu_buffer_rsrc_t r_lg = make_rsrc(a.LOGITS);
-        const long lrow = ((long)s * B + rl) * a.Vp;
-        float pv = INFINITY, my_x = 0.f;
-        int pi = -1, my_i = -1;
-        for (int k = 0; k < K; ++k) {
-          float bv = -INFINITY;
-          int bi = -1;
-          for (int j = sub * 4; j < V; j += 64) {
-            const float4 v = ldb128_sc1(r_lg, lrow + j);
-            const float xs[4] = {v.x, v.y, v.z, v.w};
-#pragma unroll
-            for (int e = 0; e < 4; ++e) {
-              const int n = j + e;
-              const float x = xs[e];
-              if (n < V && (pv > x || (pv == x && pi < n)) && (bi < 0 || x > bv || (x == bv && n < bi))) { bv = x; bi = n; }
-            }
-          }
-#pragma unroll
-          for (int o = 8; o > 0; o >>= 1) {
-            const float ov = __shfl_xor(bv, o);
-            const int oi = __shfl_xor(bi, o);
-            if (oi >= 0 && (bi < 0 || ov > bv || (ov == bv && oi < bi))) { bv = ov; bi = oi; }
-          }
-          if (sub == k) { my_x = bv; my_i = bi; }
-          pv = bv; pi = bi;
-        }
+        // the row's K best tokens (row_top_k: K sweeps over the row P5 stored); lane k of the row keeps pick k
+        float my_x = 0.f;
+        int my_i = -1;
+        row_top_k(make_rsrc(a.LOGITS), ((long)s * B + rl) * a.Vp, V, K, sub, my_x, my_i);
         // candidate (row i, k = sub): float64 score = the slot's + logp, logp = (x - mx) - logf(se) formed without rounding the LSE first
         const int st_i = t->status[i];
         const bool valid = row < B && ((st_i == BM_LIVE && sub < K && my_i >= 0) || (st_i == BM_DONE && sub == 0));
@@ -611,7 +627,7 @@ __device__ __forceinline__ void decoder_persist_fwd_body(const PDecArgs& a) {
       }
       [[maybe_unused]] bool sc_tgt = false;                  // SC: step s has a target (column s+1 of y); its class weight
       [[maybe_unused]] float sc_w = 0.f;
-      if constexpr (SC && !FD && !SM) {       // (read in front of the wait: neither load is on the chain)
+      if constexpr (SC && !FD && !DRAW) {       // (read in front of the wait: neither load is on the chain)
         sc_tgt = a.ytgt && s + 1 < a.L;
         if (sc_tgt && sub == 0 && row < B) {
           int r = row;
@@ -624,7 +640,47 @@ __device__ __forceinline__ void decoder_persist_fwd_body(const PDecArgs& a) {
       float mx = -INFINITY, se = 0.f, xt = 0.f;
       int mi = 0x7fffffff;
       [[maybe_unused]] float rf = -INFINITY;                 // SM: the reference of `se` (the largest winner's xs merged so far)
-      if (row < B)
+      [[maybe_unused]] int tk_m = 0;                         // TK: the kept count of the draw
+      // TK: the draw of include/astk.h (astk_sample_decode_topk) on the row of xs that P5 stored -- the tile records are not used.  Lane j of
+      // the row's 16 holds candidate j; mi = the drawn token, xt = its log-probability among the kept, tk_m = the kept count.
+      if constexpr (TK) {
+        // (every per-lane value formed from `tl` here, behind an empty asm, as in beam mode's P6: the multi-layer kernels have no
+        //  register to hold one over the step loop)
+        int tl = tid;
+        asm volatile("" : "+v"(tl));
+        const int K = a.top_k, j = tl & 15, rl = min(m0 + (tl >> 4), B - 1);
+        float my_x = 0.f;
+        int my_i = -1;
+        row_top_k(make_rsrc(a.LOGITS), ((long)s * B + rl) * a.Vp, V, K, j, my_x, my_i);
+        const bool cand = j < K && my_i >= 0;
+        const float x0 = __shfl(my_x, 0, 16);                // the row's largest xs: the reference of every exponential below
+        const float e = cand ? expf(my_x - x0) : 0.f;
+        // nucleus: q_j = e_j / sum_K e; m = the smallest count whose prefix sum of q reaches top_p (K if none does; top_p == 1: K exactly)
+        float cum = e, tot = e;
+#pragma unroll
+        for (int o = 1; o < 16; o <<= 1) {
+          const float up = __shfl_up(cum, o, 16);
+          if (j >= o) cum += up;
+          tot += __shfl_xor(tot, o);
+        }
+        const unsigned below = (unsigned)(__ballot(cand && cum / tot < a.top_p) >> (tl & 48)) & 0xffffu;
+        tk_m = a.top_p >= 1.f ? K : min(K, __popc(below) + 1);
+        // the draw among the kept: the largest z = xs + g(row key, s, id), equal z: the lower id; the sum of the kept exponentials
+        const bool kept = cand && j < tk_m;
+        mx = kept ? my_x + sample_gumbel(sm_row_keys()[rl & (PDEC_SM_ROWS - 1)], s, my_i) : -INFINITY;
+        mi = kept ? my_i : 0x7fffffff;
+        xt = my_x;
+        se = kept ? e : 0.f;
+#pragma unroll
+        for (int o = 8; o > 0; o >>= 1) {
+          const float om = __shfl_xor(mx, o), ox = __shfl_xor(xt, o);
+          const int oi = __shfl_xor(mi, o);
+          se += __shfl_xor(se, o);
+          if (om > mx || (om == mx && oi < mi)) { mx = om; mi = oi; xt = ox; }
+        }
+        xt = (xt - x0) - logf(se);       // logp = xs_tok - LSE over the kept, formed without rounding an LSE first
+      }
+      if (!TK && row < B)
         for (int k = sub; k < a.ntile_v; k += 16) {
           const float4 cs = ldb128_sc1(r_ces, (((long)s * B + row) * a.ntile_v + k) * 4);
           const float tm = cs.x, ts = cs.y, tx = cs.w;
@@ -644,6 +700,7 @@ __device__ __forceinline__ void decoder_persist_fwd_body(const PDecArgs& a) {
         }
 #pragma unroll
       for (int o = 8; o > 0; o >>= 1) {
+        if constexpr (TK) break;         // (merged above)
         const float om = __shfl_xor(mx, o), os = __shfl_xor(se, o), ox = __shfl_xor(xt, o);
         const int oi = __shfl_xor(mi, o);
         if constexpr (SM) {
@@ -681,12 +738,15 @@ __device__ __forceinline__ void decoder_persist_fwd_body(const PDecArgs& a) {
             if constexpr (SM) {
               // log p(token) under softmax(xs) = xs_tok - lse, lse = rf + logf(se): formed as (xs_tok - rf) - logf(se), likewise
               *ua(a.LSE + (long)s * B, (unsigned)r) = (xt - rf) - lg;
+            } else if constexpr (TK) {
+              *ua(a.LSE + (long)s * B, (unsigned)r) = xt;
+              if (a.NKEPT) *ua(a.NKEPT + (long)s * B, (unsigned)r) = tk_m;
             } else {
               *ua(a.LSE + (long)s * B, (unsigned)r) = -lg;
               if (a.LOSSROWS) *ua(a.LOSSROWS + (long)s * B, (unsigned)r) = sc_tgt ? sc_w * ((mx - xt) + lg) : 0.f;
             }
             sti_sc1(ua(a.PRED + (long)s * B, (unsigned)r), mi);
-            if constexpr (SM) {
+            if constexpr (DRAW) {
               if (mi == a.eos) {
                 int i = tid >> 4;
                 asm volatile("" : "+v"(i));   // (as above: the LDS address formed here, not kept over the loop and spilled)
@@ -700,7 +760,7 @@ __device__ __forceinline__ void decoder_persist_fwd_body(const PDecArgs& a) {
           row_done = row_done || mi == a.eos;
         }
         bool wdone;
-        if constexpr (SM) {
+        if constexpr (DRAW) {
           int i = tid >> 4;
           asm volatile("" : "+v"(i));         // (likewise)
           wdone = __all(sub != 0 || sm_row_done()[i] != 0);
@@ -1281,13 +1341,14 @@ __device__ __forceinline__ void decoder_persist_fwd_body(const PDecArgs& a) {
     // winner by z = xs + g, xs at that winner, and the tile's sum of exp(xs - xs at the winner) (g lies in [-2.9, 16.7]: the winner's xs is
     // within 20 of the tile's largest, the sum cannot overflow) -- the four words of the tile record, as before.
     // BM: keeps what the scored mode keeps and stores the step's logits for P6's top-K passes.
+    // TK: stores the step's tempered logits xs = x * inv_temp for P6 and nothing else: no noise over V, no tile record.
 #pragma unroll
     for (int t = 0; t < 2; ++t) {
       if (l_item[t] < 0) continue;
       const int bt = l_item[t] / a.ntile_v, tile = l_item[t] % a.ntile_v, m0 = bt * 16, n0 = tile * 16;
       TICK(15)
       [[maybe_unused]] int sc_tgt = -1;          // SC: this row's target of step s, read in front of the wait (-1: none)
-      if constexpr (SC && !SM) {
+      if constexpr (SC && !DRAW) {
         int r = m0 + (tid >> 4);
         asm volatile("" : "+v"(r));         // (keeps the address out of the loop-invariant registers: they are full, it would spill)
         if (a.ytgt && s + 1 < a.L && r < B) sc_tgt = *ua(a.ytgt + s + 1, (unsigned)(r * a.L));
@@ -1312,6 +1373,14 @@ __device__ __forceinline__ void decoder_persist_fwd_body(const PDecArgs& a) {
         int rr = row, nn = n;
         asm volatile("" : "+v"(rr), "+v"(nn));
         if (ok) st_sc1_u(a.LOGITS + (long)s * B * a.Vp, (unsigned)(rr * a.Vp + nn), x);
+      }
+      if constexpr (TK) {      // (P6 draws from the row of xs = x * inv_temp: written through, in front of the tile's arrival; no tile record)
+        int rr = row, nn = n;
+        asm volatile("" : "+v"(rr), "+v"(nn));
+        if (ok) st_sc1_u(a.LOGITS + (long)s * B * a.Vp, (unsigned)(rr * a.Vp + nn), x * a.inv_temp);
+        publish_sh(CTR(PH_LOG, bt), tile);
+        TICK(11)
+        continue;
       }
       if (!GR) {       // (GR: P6 needs the tile's maximum and its index only)
         if (ok) *ua(a.LOGITS + (long)s * B * a.Vp, (unsigned)(row * a.Vp + n)) = x;
@@ -1420,6 +1489,13 @@ __global__ __launch_bounds__(256, 1) void decoder_persist_greedy_scored(PDecArgs
 template <int NC, int NL, bool XS>
 __global__ __launch_bounds__(256, 1) void decoder_persist_sampled(PDecArgs a) {
   decoder_persist_fwd_body<NC, NL, XS, PDEC_SAMPLED>(a);
+  greedy_last_out(a);
+}
+
+// The truncated sampled mode (top-k / nucleus) as a kernel of its own, likewise.
+template <int NC, int NL, bool XS>
+__global__ __launch_bounds__(256, 1) void decoder_persist_sampled_topk(PDecArgs a) {
+  decoder_persist_fwd_body<NC, NL, XS, PDEC_TOPK>(a);
   greedy_last_out(a);
 }
 
@@ -2412,6 +2488,7 @@ static int inference_run(PDecMode mode, const astk_decoder_desc* d, const astk_d
   else if (mode == PDEC_SAMPLED) launch([](auto nc, auto nl, auto xs) { return decoder_persist_sampled<nc, nl, xs>; });
   else if (mode == PDEC_SCORED) launch([](auto nc, auto nl, auto xs) { return decoder_persist_greedy_scored<nc, nl, xs>; });
   else if (mode == PDEC_BEAM) launch([](auto nc, auto nl, auto xs) { return decoder_persist_beam<nc, nl, xs>; });
+  else if (mode == PDEC_TOPK) launch([](auto nc, auto nl, auto xs) { return decoder_persist_sampled_topk<nc, nl, xs>; });
   else launch([](auto nc, auto nl, auto xs) { return decoder_persist_fwd<nc, nl, xs, true>; });
   ASTK_LAUNCH_CHECK();
   return 0;
@@ -2424,7 +2501,16 @@ struct GreedyScoredIO {
   float *logp, *nll;               // [stop_limit][B]; nll null iff y is null
   const uint64_t* row_keys;        // sampled mode: [B] row keys (null: the scored greedy mode) and 1 / temperature
   float inv_temp;
+  int top_k;                       // truncated sampled mode (0: untruncated): the candidates, the nucleus mass, the kept counts [stop_limit][B]
+  float top_p;                     // or null -- and the workspace then holds the step's tempered logits behind the greedy plan
+  int32_t* n_kept;
 };
+// truncated sampled mode: the bytes of the xs buffer [stop_limit][B][Vp] behind the greedy plan
+static size_t topk_xs_bytes(const astk_decoder_desc* d, int stop_limit) {
+  Carver c(nullptr);
+  c.take<float>((size_t)stop_limit * d->B * (size_t)((d->V + 3) / 4 * 4));
+  return c.total();
+}
 // sc: null for the unscored kernel
 static int greedy_launch(const astk_decoder_desc* d, const astk_decoder_params* prm, const float* enc, const float* c0, const float* h0, int go,
                          int eos, int stop_limit, const GreedyScoredIO* sc, int32_t* tokens, int32_t* n_steps, float* status_dst, void* ws,
@@ -2435,7 +2521,9 @@ static int greedy_launch(const astk_decoder_desc* d, const astk_decoder_params* 
   GreedyPlan g;
   ASTK_CHECK(greedy_plan(d, stop_limit, nullptr, g), "greedy_decode: B = %d, H = %d, %d layers (or the knob dec.persist = 0) does not run on the "
              "device loop: astk_greedy_workspace_bytes returns 0, decode with astk_decoder_step_infer", d->B, d->H, d->n_layers);
-  ASTK_CHECK(ws && ws_bytes >= g.bytes, "greedy_decode: workspace too small (%zu < %zu)", ws_bytes, g.bytes);
+  const bool topk = sc && sc->top_k != 0;
+  const size_t need = g.bytes + (topk ? topk_xs_bytes(d, stop_limit) : 0);
+  ASTK_CHECK(ws && ws_bytes >= need, "greedy_decode: workspace too small (%zu < %zu)", ws_bytes, need);
   ASTK_CHECK(prm && enc && c0 && h0 && tokens && n_steps, "greedy_decode: null pointer");
   if (sc) {
     ASTK_CHECK(sc->logp, "greedy_decode_scored: null pointer (logp)");
@@ -2452,8 +2540,9 @@ static int greedy_launch(const astk_decoder_desc* d, const astk_decoder_params* 
   if (sc) {
     a.LSE = sc->logp; a.LOSSROWS = sc->nll; a.ytgt = sc->y; a.L = sc->y ? sc->ldy : 1; a.cw = sc->class_weight;
     a.row_keys = sc->row_keys; a.inv_temp = sc->inv_temp;
+    if (topk) { a.top_k = sc->top_k; a.top_p = sc->top_p; a.NKEPT = sc->n_kept; a.LOGITS = (float*)((char*)ws + g.bytes); }
   }
-  return inference_run(!sc ? PDEC_GREEDY : (sc->row_keys ? PDEC_SAMPLED : PDEC_SCORED), d, prm, enc, h0, a, g, s);
+  return inference_run(!sc ? PDEC_GREEDY : (topk ? PDEC_TOPK : (sc->row_keys ? PDEC_SAMPLED : PDEC_SCORED)), d, prm, enc, h0, a, g, s);
 }
 
 int greedy_decode_launch(const astk_decoder_desc* d, const astk_decoder_params* prm, const float* enc, const float* c0, const float* h0, int go,
@@ -2466,7 +2555,7 @@ int greedy_decode_scored_launch(const astk_decoder_desc* d, const astk_decoder_p
                                 int go, int eos, int stop_limit, const int32_t* y, int ldy, const float* class_weight, int32_t* tokens,
                                 float* logp, float* nll, int32_t* n_steps, float* status_dst, void* ws, size_t ws_bytes,
                                 const int32_t* row_len, hipStream_t s) {
-  const GreedyScoredIO sc{y, ldy, class_weight, logp, nll, nullptr, 1.f};
+  const GreedyScoredIO sc{y, ldy, class_weight, logp, nll, nullptr, 1.f, 0, 1.f, nullptr};
   return greedy_launch(d, prm, enc, c0, h0, go, eos, stop_limit, &sc, tokens, n_steps, status_dst, ws, ws_bytes, row_len, s);
 }
 
@@ -2481,7 +2570,31 @@ int sample_decode_launch(const astk_decoder_desc* d, const astk_decoder_params* 
   ASTK_CHECK(row_keys, "sample_decode: null pointer (row_keys)");
   ASTK_CHECK(logp, "sample_decode: null pointer (logp)");
   ASTK_CHECK(inv_temp > 0.f && inv_temp <= 3.402823466e38f, "sample_decode: inv_temp %g is not a finite number above 0", (double)inv_temp);
-  const GreedyScoredIO sc{nullptr, 0, nullptr, logp, nullptr, row_keys, inv_temp};
+  const GreedyScoredIO sc{nullptr, 0, nullptr, logp, nullptr, row_keys, inv_temp, 0, 1.f, nullptr};
+  return greedy_launch(d, prm, enc, c0, h0, go, eos, stop_limit, &sc, tokens, n_steps, status_dst, ws, ws_bytes, row_len, s);
+}
+
+// ---------------------------------------------------------------------------------------------------- truncated sampling
+// decoder_persist_sampled_topk through greedy_launch, as the sampled mode: the greedy plan, plus the step's tempered logits [S][B][Vp] that P5
+// keeps for P6's top_k sweeps (topk_xs_bytes, behind the plan).  Every check of the sampled mode is greedy_launch's and
+// sample_decode_launch's own; this entry adds top_k and top_p.  (The plan's tile-record buffer CESTAT is carried and not used in this mode.)
+size_t sample_topk_workspace_bytes(const astk_decoder_desc* d, int stop_limit) {
+  const size_t g = greedy_workspace_bytes(d, stop_limit);
+  return g ? g + topk_xs_bytes(d, stop_limit) : 0;
+}
+
+int sample_decode_topk_launch(const astk_decoder_desc* d, const astk_decoder_params* prm, const float* enc, const float* c0, const float* h0,
+                              int go, int eos, int stop_limit, const uint64_t* row_keys, float inv_temp, int top_k, float top_p,
+                              int32_t* tokens, float* logp, int32_t* n_kept, int32_t* n_steps, float* status_dst, void* ws, size_t ws_bytes,
+                              const int32_t* row_len, hipStream_t s) {
+  ASTK_CHECK_DESC(d, astk_decoder_desc);
+  ASTK_CHECK(top_k >= 1 && top_k <= ASTK_SAMPLE_MAX_TOPK && top_k <= d->V, "sample_decode_topk: top_k %d outside [1, %d] or above V = %d", top_k,
+             ASTK_SAMPLE_MAX_TOPK, d->V);
+  ASTK_CHECK(top_p > 0.f && top_p <= 1.f, "sample_decode_topk: top_p %g is not a number in (0, 1]", (double)top_p);
+  ASTK_CHECK(row_keys, "sample_decode: null pointer (row_keys)");
+  ASTK_CHECK(logp, "sample_decode: null pointer (logp)");
+  ASTK_CHECK(inv_temp > 0.f && inv_temp <= 3.402823466e38f, "sample_decode: inv_temp %g is not a finite number above 0", (double)inv_temp);
+  const GreedyScoredIO sc{nullptr, 0, nullptr, logp, nullptr, row_keys, inv_temp, top_k, top_p, n_kept};
   return greedy_launch(d, prm, enc, c0, h0, go, eos, stop_limit, &sc, tokens, n_steps, status_dst, ws, ws_bytes, row_len, s);
 }
 

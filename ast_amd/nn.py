@@ -398,11 +398,11 @@ def score_hypotheses_packed(model, Xs, hyps_lists, return_alpha=False, max_utts=
     return out
 
 
-def sample_hypotheses_packed(model, Xs, n, stop_limit, seed, temperature=1.0, first_streams=None, max_utts=None):
+def sample_hypotheses_packed(model, Xs, n, stop_limit, seed, temperature=1.0, first_streams=None, max_utts=None, top_k=None, top_p=1.0):
     """sample_hypotheses for many utterances, their n rows each packed into calls of up to 32 rows (plan_row_packs; at most max_utts
     utterances per call).  Utterance k draws from the streams first_streams[k] .. first_streams[k] + n - 1 of `seed` (default k * n:
     the numbering of NN.sample_set), so packing does not change which samples an utterance gets.  Returns one list per utterance as
-    sample_hypotheses returns it."""
+    sample_hypotheses returns it.  top_k / top_p: truncated sampling (SpeechEncoderDecoder.sample)."""
     n = int(n)
     first_streams = [k * n for k in range(len(Xs))] if first_streams is None else [int(v) for v in first_streams]
     if len(first_streams) != len(Xs):
@@ -411,7 +411,8 @@ def sample_hypotheses_packed(model, Xs, n, stop_limit, seed, temperature=1.0, fi
     for call in plan_row_packs([n] * len(Xs), max_utts):
         rows, _ = _pack_rows(model, Xs, call)
         streams = [first_streams[u] + i for u, lo, hi in call for i in range(lo, hi)]
-        r = model.sample(None, SYMBOLS.GO_ID, SYMBOLS.EOS_ID, stop_limit, seed, streams=streams, temperature=temperature, rows=rows)
+        r = model.sample(None, SYMBOLS.GO_ID, SYMBOLS.EOS_ID, stop_limit, seed, streams=streams, temperature=temperature, rows=rows,
+                         top_k=top_k, top_p=top_p)
         at = 0
         for u, lo, hi in call:
             out[u].extend({"hyp": [SYMBOLS.GO_ID] + cut_at_eos(r.tokens[i]), "score": float(r.score[i])} for i in range(at, at + hi - lo))
@@ -419,12 +420,14 @@ def sample_hypotheses_packed(model, Xs, n, stop_limit, seed, temperature=1.0, fi
     return out
 
 
-def sample_hypotheses(model, X, n, stop_limit, seed, temperature=1.0, first_stream=0):
+def sample_hypotheses(model, X, n, stop_limit, seed, temperature=1.0, first_stream=0, top_k=None, top_p=1.0):
     """n samples of ONE utterance X (1, T, D), drawn by SpeechEncoderDecoder.sample from the streams first_stream .. first_stream + n - 1
     of `seed`: X is repeated over the rows (the encoding decode_beam sees; sample_hypotheses_packed packs several utterances), at most 32 rows -- the device
     loop's batch -- per call.  Returns a list in stream order of {"hyp": [GO, t1, .., tk], "score": float}, each cut behind its first
     EOS and keeping it, like decode_beam's entries; score = the log-probability of t1..tk under the sampled distribution.  A stream's
-    sample does not depend on n or on its row, so a list can be extended later from first_stream = n."""
+    sample does not depend on n or on its row, so a list can be extended later from first_stream = n.
+    top_k / top_p: truncated sampling (SpeechEncoderDecoder.sample) -- the score is then the log-probability under the renormalised
+    kept set that was actually sampled, not the model's full-softmax log-probability (score_hypotheses gives that)."""
     X = model._as_input(X)
     if X.dim() == 2:
         X = X[None]
@@ -432,7 +435,7 @@ def sample_hypotheses(model, X, n, stop_limit, seed, temperature=1.0, first_stre
     for lo in range(0, int(n), 32):
         m = min(32, int(n) - lo)
         r = model.sample(X.expand(m, -1, -1), SYMBOLS.GO_ID, SYMBOLS.EOS_ID, stop_limit, seed,
-                         streams=range(first_stream + lo, first_stream + lo + m), temperature=temperature)
+                         streams=range(first_stream + lo, first_stream + lo + m), temperature=temperature, top_k=top_k, top_p=top_p)
         out.extend({"hyp": [SYMBOLS.GO_ID] + cut_at_eos(r.tokens[i]), "score": float(r.score[i])} for i in range(m))
     return out
 
@@ -652,11 +655,11 @@ class NN:
             losses.append(r.loss / L)
         return preds, (sum(losses) / len(losses) if losses else 0.0), scores
 
-    def sample_set(self, set_key, n, seed, temperature=1.0, utts_per_call=1):
+    def sample_set(self, set_key, n, seed, temperature=1.0, utts_per_call=1, top_k=None, top_p=1.0):
         """n samples of every utterance of a set (sample_hypotheses; utterance k of the set, in the loader's order, draws from the
         streams k * n .. k * n + n - 1 of `seed`): returns {utt: [(hyp, score, [])]}, the n-best format of beam.py's pickle without
         attention histories.  utts_per_call = U > 1 packs the rows of up to U utterances into one call (sample_hypotheses_packed):
-        the same streams, so the same samples."""
+        the same streams, so the same samples.  top_k / top_p: truncated sampling (SpeechEncoderDecoder.sample)."""
         out = {}
         stop_limit = self.cfg.train["data"]["max_pred"]
         with tqdm(total=self.data_loader.n_utts[set_key], ncols=80, disable=adist.rank() != 0) as pbar:
@@ -668,7 +671,8 @@ class NN:
                     if group and (utt is None or len(group) == utts_per_call):
                         with using_config("train", False):
                             lists = sample_hypotheses_packed(self.model, [g["X"] for g in group], n, stop_limit, seed, temperature,
-                                                             first_streams=[(k0 + i) * n for i in range(len(group))], max_utts=utts_per_call)
+                                                             first_streams=[(k0 + i) * n for i in range(len(group))], max_utts=utts_per_call,
+                                                             top_k=top_k, top_p=top_p)
                         for g, hyps in zip(group, lists):
                             out[g["utts"][0]] = [(h["hyp"], h["score"], []) for h in hyps]
                         pbar.update(len(group))
@@ -677,7 +681,7 @@ class NN:
                 return out
             for k, utt in enumerate(self.data_loader.get_batch(1, set_key, train=False, labels=False)):
                 with using_config("train", False):
-                    hyps = sample_hypotheses(self.model, utt["X"], n, stop_limit, seed, temperature, first_stream=k * n)
+                    hyps = sample_hypotheses(self.model, utt["X"], n, stop_limit, seed, temperature, first_stream=k * n, top_k=top_k, top_p=top_p)
                 out[utt["utts"][0]] = [(h["hyp"], h["score"], []) for h in hyps]
                 pbar.update(1)
         return out

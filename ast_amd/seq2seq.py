@@ -181,10 +181,11 @@ class ScoredPrediction:
     step (0 where a step has no target; None without targets), `n_steps`, and the two reductions (float64, on the host):
       loss     = sum over the steps of the mean over the B rows of nll -- the free-running dev loss of the reference's older trainer
                  (enc_dec.py:372-429: rows that have emitted EOS keep contributing, PAD targets weigh 0); None without targets;
-      score[b] = sum of logp[b, :k], k = the position of row b's first `end_token` plus one, or n_steps."""
+      score[b] = sum of logp[b, :k], k = the position of row b's first `end_token` plus one, or n_steps.
+    `kept` (B, n_steps) int32: truncated sampling's kept count m of every draw (sample(top_k=, top_p=)); None on every other path."""
 
-    def __init__(self, tokens, logp, nll, end_token):
-        self.tokens, self.logp, self.nll = tokens, logp, nll
+    def __init__(self, tokens, logp, nll, end_token, kept=None):
+        self.tokens, self.logp, self.nll, self.kept = tokens, logp, nll, kept
         self.n_steps = int(tokens.shape[1])
         self.loss = None if nll is None else float(nll.astype(np.float64).sum(axis=0).sum() / max(tokens.shape[0], 1))
         is_end = tokens == end_token
@@ -193,12 +194,14 @@ class ScoredPrediction:
         self.score = np.where(keep, logp.astype(np.float64), 0.0).sum(axis=1)
 
 
-def scored_from_rows(words, n_steps, B, stop_limit, has_nll, end_token):
+def scored_from_rows(words, n_steps, B, stop_limit, has_nll, end_token, has_kept=False):
     """The read-back words of a scored greedy decode -- step-major [tokens | logp | nll], each (stop_limit, B), the last two float32
-    bit patterns -- cut to the first n_steps steps and reduced (ScoredPrediction)."""
+    bit patterns -- cut to the first n_steps steps and reduced (ScoredPrediction).  has_kept: the third block is truncated sampling's
+    int32 kept counts instead."""
     n, sb = int(n_steps), int(stop_limit) * B
     rows = lambda k: words[k * sb:k * sb + n * B].reshape(n, B).T.copy()
-    return ScoredPrediction(rows(0), rows(1).view(np.float32), rows(2).view(np.float32) if has_nll else None, end_token)
+    return ScoredPrediction(rows(0), rows(1).view(np.float32), rows(2).view(np.float32) if has_nll else None, end_token,
+                            rows(2) if has_kept else None)
 
 
 # ---- sampled decoding: the noise contract of include/astk.h ("sampled decoding on the device"), restated on the host
@@ -243,6 +246,61 @@ def checked_temperature(temperature):
     if not (np.isfinite(inv) and inv > 0):
         raise ValueError(f"sample: 1 / temperature must be a finite positive float32, got temperature {temperature!r} (inverse {inv!r})")
     return inv
+
+
+# ---- truncated sampling: the contract of include/astk.h ("truncated sampling on the device"), top-k and top-p / nucleus
+SAMPLE_MAX_TOPK = 16      # ASTK_SAMPLE_MAX_TOPK
+
+
+def checked_truncation(top_k, top_p, V=None):
+    """(top_k, top_p) as the library takes them, or (None, 1.0) for the untruncated draw; ValueError unless top_p is a number in (0, 1],
+    top_k is None or an integer in 1..16 (and at most V, when given), and top_p < 1 comes with a top_k."""
+    try:
+        p = float(top_p)
+    except (TypeError, ValueError):
+        p = float("nan")
+    if not (np.isfinite(p) and 0.0 < p <= 1.0):
+        raise ValueError(f"sample: top_p must be a number in (0, 1], got {top_p!r}")
+    if top_k is None:
+        if p < 1.0:
+            raise ValueError(f"sample: top_p = {top_p!r} needs top_k: the nucleus is taken among top_k <= {SAMPLE_MAX_TOPK} candidates")
+        return None, 1.0
+    if isinstance(top_k, bool) or not isinstance(top_k, (int, np.integer)) or not 1 <= int(top_k) <= SAMPLE_MAX_TOPK:
+        raise ValueError(f"sample: top_k must be an integer in 1..{SAMPLE_MAX_TOPK}, got {top_k!r}")
+    if V is not None and int(top_k) > int(V):
+        raise ValueError(f"sample: top_k = {int(top_k)} is above the vocabulary size V = {int(V)}")
+    return int(top_k), float(np.float32(p)) if p < 1.0 else 1.0
+
+
+def truncated_pick(logits, g, inv_temp, top_k, top_p):
+    """One step's truncated draw (include/astk.h, "truncated sampling on the device", steps 1 to 5) as a pure function of torch tensors,
+    on any device: logits (B, V) float32, g (B, V) the noise of (row key, step, class id), inv_temp, top_k in 1..16, top_p in (0, 1].
+      1. xs = logits * inv_temp in float32;
+      2. the top_k largest xs are the candidates, by a stable descending sort of the float32 xs: higher values first, among equal
+         values the lower token id first;
+      3. q = exp(xs_j - LSE_K) over the candidates; m = the smallest count >= 1 whose prefix sum of q is >= top_p, K if none reaches it,
+         and K exactly for top_p == 1 (prefix sums and LSE in float64);
+      4. the token is the candidate j < m with the largest z_j = xs_j + g at its id (float32), among equal z the lower token id;
+      5. logp = xs_tok - LSE over the m kept (float64): the log-probability under the distribution actually sampled, NOT the model's
+         full-softmax log-probability (score() gives that).
+    Returns (tokens (B,) int32, logp (B,) float64, kept (B,) int32)."""
+    K = int(top_k)
+    xs = logits.to(torch.float32) * float(inv_temp)
+    vals, ids = torch.sort(xs, dim=1, descending=True, stable=True)
+    vals, ids = vals[:, :K], ids[:, :K]
+    e = torch.exp(vals.double() - vals[:, :1].double())
+    if float(top_p) >= 1.0:
+        m = torch.full((xs.shape[0],), K, dtype=torch.int64, device=xs.device)
+    else:
+        cum = torch.cumsum(e / e.sum(dim=1, keepdim=True), dim=1)
+        m = ((cum < float(top_p)).sum(dim=1) + 1).clamp(max=K)
+    kept = torch.arange(K, device=xs.device)[None, :] < m[:, None]
+    z = torch.where(kept, vals + g.to(torch.float32).gather(1, ids), torch.full_like(vals, float("-inf")))
+    best = z == z.max(dim=1, keepdim=True).values
+    tok = torch.where(best, ids, torch.full_like(ids, xs.shape[1])).min(dim=1).values
+    x_tok = xs.gather(1, tok[:, None])[:, 0].double()
+    logp = (x_tok - vals[:, 0].double()) - torch.log(torch.where(kept, e, torch.zeros_like(e)).sum(dim=1))
+    return tok.to(torch.int32), logp, m.to(torch.int32)
 
 
 class ForcedScore:
@@ -1132,10 +1190,11 @@ class SpeechEncoderDecoder:
             host = self._pinned[(key, slot)] = torch.empty(n, dtype=dtype, pin_memory=True)
         return self._pool(f"{key}_out{slot}", (n,), dtype), host[:n]
 
-    def _device_decode(self, key, slot, nbytes, n, call, args, n_alpha=0, **pending):
+    def _device_decode(self, key, slot, nbytes, n, call, args, n_alpha=0, takes_rows=False, **pending):
         """`call` = the mode's library entry point, `nbytes` its workspace query; the launch writes n int32 words (and n_alpha floats,
         forced alpha) that come back in one non-blocking copy each, followed by an event.  args(p, alpha) = the mode's own arguments
         between the decoder state and the workspace: p(k) is the address of byte k of the words, alpha the float buffer's or None.
+        takes_rows: `call` itself ends with row_len (NULL allowed) and has no _rows twin.
         `pending`: the status word's index, `where`, parse and keep of the _Pending handle returned."""
         if nbytes == 0 or self._rows_alone:
             return None
@@ -1145,10 +1204,11 @@ class SpeechEncoderDecoder:
         st, base = self._cur, out.data_ptr()
         lens = st.get("row_len")              # a RowBatch: the mode's _rows entry point, the lengths behind the stream
         if lens is not None:
-            call, pending["keep"] = getattr(_lib.load(), call.__name__ + "_rows"), (pending.get("keep"), lens, st["enc_states"])
+            call = call if takes_rows else getattr(_lib.load(), call.__name__ + "_rows")
+            pending["keep"] = (pending.get("keep"), lens, st["enc_states"])
         check(call(C.byref(st["dd"]), C.byref(st["dp"]), _vp(st["enc_states"]), _vp(self._dec_c), _vp(self._dec_h),
                    *args(lambda k: C.c_void_p(base + k), _vp(alpha)), _vp(ws), ws.numel(), self._stream(),
-                   *(() if lens is None else (_vp(lens),))))
+                   *(() if lens is None and not takes_rows else (_vp(lens),))))
         host.copy_(out, non_blocking=True)
         if n_alpha:
             host_alpha.copy_(alpha, non_blocking=True)
@@ -1255,19 +1315,28 @@ class SpeechEncoderDecoder:
                 return ScoredPrediction(cat("tokens"), cat("logp"), cat("nll") if y is not None else None, eos)
             return self._device_or_steps("last_predict_path", handle, steps, alone)
 
-    def sample(self, X, start_token, end_token, stop_limit, seed, streams=None, temperature=1.0, rows=None):
+    def sample(self, X, start_token, end_token, stop_limit, seed, streams=None, temperature=1.0, rows=None, top_k=None, top_p=1.0):
         """Ancestral sampling: predict_scored() with every step's token drawn from softmax(logits / temperature) by the Gumbel-max
         noise of include/astk.h -- row b draws from (seed, streams[b]) alone (streams defaults to the rows' indices), whatever its
         position and whatever the batch around it.  Returns a ScoredPrediction: tokens (B, n_steps), logp the log-probability of each
         drawn token under the sampled distribution, score cut at the first `end_token`; nll and loss are None.  A row is finished once
-        it has drawn `end_token`; the decode stops when every row has, or at stop_limit."""
-        return self.sample_async(X, start_token, end_token, stop_limit, seed, streams, temperature, rows=rows).result()
+        it has drawn `end_token`; the decode stops when every row has, or at stop_limit.
+        top_k (1..16) / top_p in (0, 1]: truncated sampling, the contract of include/astk.h ("truncated sampling on the device") -- the
+        top_k largest xs = logits * inv_temp are the candidates (higher values first, among equal values the lower token id first),
+        cut to the smallest prefix whose renormalised mass reaches top_p (top_p == 1: no cut), and the token is drawn among the kept
+        by the same noise.  logp is then the log-probability under the distribution actually sampled -- the renormalised kept set --
+        NOT the model's full-softmax log-probability; score() gives that.  `kept` holds the kept count of every draw.  top_p < 1
+        needs a top_k: the nucleus is taken among top_k <= 16 candidates.  top_k = None and top_p = 1 is the untruncated draw."""
+        return self.sample_async(X, start_token, end_token, stop_limit, seed, streams, temperature, rows=rows, top_k=top_k, top_p=top_p).result()
 
-    def sample_async(self, X, start_token, end_token, stop_limit, seed, streams=None, temperature=1.0, slot=0, rows=None):
+    def sample_async(self, X, start_token, end_token, stop_limit, seed, streams=None, temperature=1.0, slot=0, rows=None, top_k=None,
+                     top_p=1.0):
         """sample() with the read-back left to the caller, like predict_scored_async: on the device path (astk_sample_decode, one
         persistent launch) ONE copy of [n_steps, status, tokens, logp] into pinned buffer `slot`; otherwise the per-step loop,
-        finished on return.  `last_predict_path` says which path ran."""
+        finished on return.  `last_predict_path` says which path ran.  With top_k / top_p (astk_sample_decode_topk) the copy is
+        [n_steps, status, tokens, logp, kept]."""
         inv_temp = checked_temperature(temperature)
+        top_k, top_p = checked_truncation(top_k, top_p, getattr(self, "V", None))
         lib = _lib.load()
         go, eos, stop = int(start_token), int(end_token), int(stop_limit)
         with using_config("train", False):
@@ -1281,29 +1350,47 @@ class SpeechEncoderDecoder:
             keys = torch.from_numpy(keys.view(np.int64)).to(self.device)      # (the bit patterns: torch has no uint64 arithmetic to offer)
             # [n_steps, status word (float), 2 pad words, tokens | logp, each (stop_limit, B)]
             sb = stop * B
-            handle = self._device_decode(
-                "sample", slot, int(lib.astk_sample_workspace_bytes(C.byref(self._cur["dd"]), stop)), 4 + 2 * sb, lib.astk_sample_decode,
-                lambda p, _: (go, eos, stop, _vp(keys), inv_temp, p(16), p(16 + 4 * sb), p(0), p(4)),
-                status_at=1, where="sample", keep=keys, parse=lambda v, _: scored_from_rows(v[4:], int(v[0]), B, stop, False, eos))
+            if top_k is None:
+                handle = self._device_decode(
+                    "sample", slot, int(lib.astk_sample_workspace_bytes(C.byref(self._cur["dd"]), stop)), 4 + 2 * sb, lib.astk_sample_decode,
+                    lambda p, _: (go, eos, stop, _vp(keys), inv_temp, p(16), p(16 + 4 * sb), p(0), p(4)),
+                    status_at=1, where="sample", keep=keys, parse=lambda v, _: scored_from_rows(v[4:], int(v[0]), B, stop, False, eos))
+            else:
+                # [n_steps, status word (float), 2 pad words, tokens | logp | kept, each (stop_limit, B)]
+                handle = self._device_decode(
+                    "sample_topk", slot, int(lib.astk_sample_topk_workspace_bytes(C.byref(self._cur["dd"]), stop)), 4 + 3 * sb,
+                    lib.astk_sample_decode_topk,
+                    lambda p, _: (go, eos, stop, _vp(keys), inv_temp, top_k, top_p, p(16), p(16 + 4 * sb), p(16 + 8 * sb), p(0), p(4)),
+                    takes_rows=True, status_at=1, where="sample", keep=keys,
+                    parse=lambda v, _: scored_from_rows(v[4:], int(v[0]), B, stop, False, eos, has_kept=True))
 
             def steps():
                 """Per step one astk_gumbel_rows fill, the argmax of logits * inv_temp + g in float32, and the drawn token's entry of a
                 float64 log_softmax of logits * inv_temp."""
                 g = torch.empty(B, self.V, dtype=torch.float32, device=self.device)
 
+                drawn = {}
+
                 def pick(logits, s):
                     check(lib.astk_gumbel_rows(_vp(keys), B, s, self.V, _vp(g), self._stream()))
-                    return (logits * inv_temp + g).argmax(dim=1).to(torch.int32)
+                    if top_k is None:
+                        return (logits * inv_temp + g).argmax(dim=1).to(torch.int32)
+                    # truncated: the pure pick function on this step's logits and noise; its logp and kept count are this step's record
+                    word, drawn["logp"], drawn["kept"] = truncated_pick(logits, g, inv_temp, top_k, top_p)
+                    return word
 
                 def record(logits, word, s):
+                    if top_k is not None:
+                        return drawn["logp"], drawn["kept"].double()
                     return (torch.log_softmax(logits.double() * inv_temp, dim=1).gather(1, word.long()[:, None])[:, 0],)
                 tokens, cols = self._free_steps(start_token, end_token, stop_limit, pick, record)
-                return ScoredPrediction(tokens, cols[0], None, eos)
+                return ScoredPrediction(tokens, cols[0], None, eos, None if top_k is None else np.rint(cols[1]).astype(np.int32))
 
             def alone(rb):
                 out, _ = self._free_rows_alone(rb, end_token, stop_limit, lambda b, r1, end, lim: self.sample(
-                    None, start_token, end, lim, seed, [streams[b]], temperature, rows=r1))
-                return ScoredPrediction(np.concatenate([r.tokens for r in out], axis=0), np.concatenate([r.logp for r in out], axis=0), None, eos)
+                    None, start_token, end, lim, seed, [streams[b]], temperature, rows=r1, top_k=top_k, top_p=top_p))
+                cat = lambda k: np.concatenate([getattr(r, k) for r in out], axis=0)
+                return ScoredPrediction(cat("tokens"), cat("logp"), None, eos, None if top_k is None else cat("kept"))
             return self._device_or_steps("last_predict_path", handle, steps, alone)
 
     def _free_steps(self, start_token, end_token, stop_limit, pick=None, record=None):

@@ -451,6 +451,37 @@ int astk_sample_decode(const astk_decoder_desc* d, const astk_decoder_params* p,
 int astk_gumbel_rows(const uint64_t* row_keys, int B, int step, int V, float* out, void* stream);
 uint64_t astk_sample_row_key(uint64_t seed, uint64_t stream);
 
+/* ---------------------------------------------------------------- truncated sampling on the device  (top-k and top-p / nucleus)
+ * astk_sample_decode with every draw restricted to a few of the best tokens.  The noise contract above stays as it is.  One draw per
+ * row b and step s, from the float32 logits x_n; the parameters are inv_temp > 0, top_k in 1..ASTK_SAMPLE_MAX_TOPK (= 16), top_k <= V,
+ * and top_p in (0, 1]:
+ *   1. Scaled logits.   xs_n = x_n * inv_temp in float32, as in the sampled mode.
+ *   2. Candidates.      The top_k largest xs_n form the candidates (xs_j, id_j), j = 0..K-1: higher values first, among equal values
+ *                       the lower token id first (beam mode's order).  The rank is taken on the float32 xs.
+ *   3. Nucleus.         q_j = exp(xs_j - LSE_K) over the K candidates; m is the smallest count >= 1 whose prefix sum of q is >= top_p,
+ *                       m = K if no prefix reaches top_p, and top_p == 1 skips the cut: m = K exactly, whatever the rounding.  So
+ *                       top-p is applied to the renormalised top-k survivors: the order the common toolkits use when both are given.
+ *   4. Draw.            tokens[s][b] = the id_j with the largest z_j = xs_j + g(b, s, id_j), j < m: g is the noise function above, of
+ *                       (row key, step, class id); among equal z the lower token id wins.
+ *   5. Log-probability. logp[s][b] = xs_tok - LSE over the m kept, formed as (xs_tok - xs_0) - logf(sum_j exp(xs_j - xs_0)), without
+ *                       rounding an LSE first.  This is the log-probability under the distribution actually sampled.  It is NOT the
+ *                       model's full-softmax log-probability; forced scoring (astk_forced_score) gives that.
+ * Consequences: top_k = 1 gives the greedy tokens and logp == 0; a row's draws depend on (seed, stream, s, its own logits) alone; the
+ * stop rule is the sampled mode's: a row is finished once it has DRAWN eos.
+ * astk_sample_decode_topk is astk_sample_decode_rows plus top_k, top_p and n_kept ((stop_limit, B) int32 on the device, the kept count
+ * m of every draw, rows [0, *n_steps) defined; NULL = none); row_len as for the *_rows entry points below, NULL allowed.  The
+ * persistent loop keeps each step's xs and finds the candidates in its combine phase: no noise is evaluated beyond the kept ids.
+ * The workspace is the greedy plan plus that buffer; astk_sample_topk_workspace_bytes returns 0 exactly where
+ * astk_greedy_workspace_bytes does (such shapes sample step by step).  Fails with a message (and launches nothing) for everything
+ * astk_sample_decode refuses, for top_k outside 1..ASTK_SAMPLE_MAX_TOPK or above V, for a top_p that is not finite, is <= 0 or > 1,
+ * and for a workspace below the query. */
+#define ASTK_SAMPLE_MAX_TOPK 16
+size_t astk_sample_topk_workspace_bytes(const astk_decoder_desc* d, int stop_limit);
+int astk_sample_decode_topk(const astk_decoder_desc* d, const astk_decoder_params* p, const float* enc, const float* c0, const float* h0,
+                            int go, int eos, int stop_limit, const uint64_t* row_keys, float inv_temp, int top_k, float top_p,
+                            int32_t* tokens, float* logp, int32_t* n_kept, int32_t* n_steps, float* status_dst, void* ws, size_t ws_bytes,
+                            void* stream, const int32_t* row_len);
+
 /* ---------------------------------------------------------------- forced decoding on the device  (score a given translation)
  * The eval-mode decoder run along given tokens in ONE persistent launch (the persistent decoder loop in its forced mode, after a fill
  * launch and the encA product): step s feeds y[b][s] to row b and scores y[b][s+1], for s in [0, S), S = ldy - 1 (ids are clamped to

@@ -4,11 +4,14 @@ scored greedy mode, in the same process, alternating, and n-best lists from samp
     python scratch/sample_throughput.py                      # the per-step cost on both shapes, then the hypotheses per second
     python scratch/sample_throughput.py --part step          # only the per-step cost (scored greedy / sampled, alternating)
     python scratch/sample_throughput.py --part nbest         # only hypotheses per second (sample_hypotheses n = 32 / decode_beam_batch)
+    python scratch/sample_throughput.py --part step --top-k 1,5,16 [--top-p 0.9]
+                                                             # the truncated loop beside the untruncated one
 
 Per-step cost: the models and the four loader-bucketed fisher_dev batches of scratch/greedy_throughput.py --scored (32 rows, EOS never
 wins: both modes run all --stop steps), a warm-up of every shape, then --reps repetitions alternating predict_scored (no targets) and
 sample, each call timed to a device synchronise; per batch the median; per decoder step = (batch time - the batch's encoder pass) /
-steps.  The yardstick is scored greedy re-measured in this call.
+steps.  The yardstick is scored greedy re-measured in this call.  --top-k K[,K..] adds one truncated sampled loop per K (with --top-p)
+to the alternation: the same batches, the same repetitions, their per-step cost beside the untruncated sampled loop's of the same run.
 Hypotheses per second: the es_en_20h model and the 64 utterances of scratch/beam_throughput.py, stop_limit 175, EOS not forced:
 sample_hypotheses(n = 32) utterance by utterance against decode_beam_batch(N = K = 5, U = 32), both timed to a device synchronise
 after a warm-up.  The two searches do different things; the figure records what an n-best list costs either way."""
@@ -42,15 +45,18 @@ def timed(fn):
     return time.perf_counter() - t, out
 
 
-def run_step_cost(name, shape, Xs, stop, reps, temperature):
+def run_step_cost(name, shape, Xs, stop, reps, temperature, top_ks=(), top_p=1.0):
     m = gt.model(shape, 0.0)
     gt.set_eos_bias(m, -1e4)
     scored = lambda X: m.predict_scored(X, GO, EOS, stop)
     sampled = lambda X: m.sample(X, GO, EOS, stop, 2024, temperature=temperature)
+    trunc = {f"topk{k}": (lambda X, k=k: m.sample(X, GO, EOS, stop, 2024, temperature=temperature, top_k=k, top_p=top_p)) for k in top_ks}
     for X in Xs:
         scored(X)
         sampled(X)
-    t = {"scored": [[] for _ in Xs], "sampled": [[] for _ in Xs]}
+        for fn in trunc.values():
+            fn(X)
+    t = {"scored": [[] for _ in Xs], "sampled": [[] for _ in Xs], **{k: [[] for _ in Xs] for k in trunc}}
     te = [[] for _ in Xs]
     for _ in range(reps):
         for i, X in enumerate(Xs):
@@ -60,6 +66,10 @@ def run_step_cost(name, shape, Xs, stop, reps, temperature):
             dt, r1 = timed(lambda: sampled(X))
             assert m.last_predict_path == "device" and r1.n_steps == stop
             t["sampled"][i].append(dt)
+            for k, fn in trunc.items():
+                dt, r2 = timed(lambda: fn(X))
+                assert m.last_predict_path == "device" and r2.n_steps == stop
+                t[k][i].append(dt)
             te[i].append(gt.timed_encode(m, X))
     enc = np.array([np.median(v) for v in te])
     res = dict(part="step", shape=name, reps=reps, temperature=temperature, frames=[int(X.shape[1]) for X in Xs], steps=stop,
@@ -71,6 +81,10 @@ def run_step_cost(name, shape, Xs, stop, reps, temperature):
         res["us_per_step_by_batch_" + k] = [round(1e6 * float(x), 2) for x in (med - enc) / stop]
         res["spread_" + k] = round(float(np.mean([(max(b) - min(b)) / np.median(b) for b in v])), 3)
     res["ratio_per_step"] = round(res["us_per_step_sampled"] / res["us_per_step_scored"], 3)
+    if trunc:
+        res["top_p"] = top_p
+    for k in trunc:
+        res["ratio_per_step_" + k] = round(res["us_per_step_" + k] / res["us_per_step_sampled"], 3)
     print(json.dumps(res), flush=True)
 
 
@@ -103,6 +117,8 @@ def main():
     ap.add_argument("--stop", type=int, default=175)
     ap.add_argument("--reps", type=int, default=7)
     ap.add_argument("--temperature", type=float, default=1.0)
+    ap.add_argument("--top-k", default="", help="comma-separated top_k values: also time the truncated sampled loop at each")
+    ap.add_argument("--top-p", type=float, default=1.0)
     ap.add_argument("--utts", type=int, default=64)
     ap.add_argument("-n", type=int, default=32)
     a = ap.parse_args()
@@ -112,7 +128,7 @@ def main():
         rng = np.random.default_rng(1)
         Xs = [torch.from_numpy(rng.standard_normal((plan[i][0], plan[i][1], 80)).astype(np.float32)).cuda() for i in idx]
         for name, shape in gt.SHAPES.items():
-            run_step_cost(name, shape, Xs, a.stop, a.reps, a.temperature)
+            run_step_cost(name, shape, Xs, a.stop, a.reps, a.temperature, [int(k) for k in a.top_k.split(",") if k], a.top_p)
         del Xs
     if a.part in ("", "nbest"):
         run_nbest(a.utts, a.stop, a.n)
