@@ -204,10 +204,10 @@ SIGNATURES = {
     "astk_spin": (C.c_int, [C.c_uint, _VP, _VP]),
     "astk_softmax_ce_fwd": (C.c_int, [_I, _I, _L, _VP, _VP, _L, _VP, _F, _VP, _VP, _VP]),
     "astk_grad_sqnorm": (C.c_int, [_VP, _VP, _F, _SZ, _VP, _VP]),
-    "astk_decay_clip_amsgrad_step": (C.c_int, [_VP, _VP, _VP, _VP, _VP, _SZ, _F, _F, _VP, _F, _F, _F, _F, _I, _VP]),
+    "astk_decay_clip_amsgrad_step": (C.c_int, [_VP, _VP, _VP, _VP, _VP, _SZ, _F, _F, _VP, _F, C.c_double, C.c_double, _F, _I, _VP]),
     "astk_decay_clip_sgd_step": (C.c_int, [_VP, _VP, _SZ, _F, _F, _VP, _F, _VP]),
     "astk_grad_sqnorm_scaled": (C.c_int, [_VP, _VP, _F, _F, _SZ, _VP, _VP]),
-    "astk_decay_clip_amsgrad_step_scaled": (C.c_int, [_VP, _VP, _VP, _VP, _VP, _SZ, _F, _F, _F, _VP, _F, _F, _F, _F, _I, _VP]),
+    "astk_decay_clip_amsgrad_step_scaled": (C.c_int, [_VP, _VP, _VP, _VP, _VP, _SZ, _F, _F, _F, _VP, _F, C.c_double, C.c_double, _F, _I, _VP]),
     "astk_decay_clip_sgd_step_scaled": (C.c_int, [_VP, _VP, _SZ, _F, _F, _F, _VP, _F, _VP]),
     "astk_decay_clip_noise": (C.c_int, [_VP, _VP, _SZ, _F, _F, _F, _VP, _F, _U64, _U64, _VP]),
     "astk_fill_dropout_mask": (C.c_int, [_VP, _SZ, _F, _U64, _U64, _VP]),

@@ -366,6 +366,13 @@ __global__ void k_zero_frames_draws(int T, const int32_t* len, double rate, uint
 }
 
 // ---- optimizer
+// The decayed gradient g gsc + l2 p with BOTH products rounded to float32 before the sum: what a separate scaling pass followed by the
+// unscaled call computes, bit for bit, and what plain float32 code computes.  Contraction is switched off by hand: __fmul_rn is a plain
+// multiply here, and the compiler fused it into the sum (fma(gsc, g, l2 p)), so the scaled gradient was never rounded.
+__device__ __forceinline__ float decayed_grad(float g, float gsc, float l2, float p) {
+#pragma clang fp contract(off)
+  return g * gsc + l2 * p;
+}
 constexpr unsigned SQNORM_BLOCKS = 512;
 __device__ double g_sq_part[SQNORM_BLOCKS];
 __device__ unsigned g_sq_ctr;
@@ -378,8 +385,7 @@ __global__ void k_sqnorm(const float* g, const float* p, float gsc, float l2, si
   // (one double atomic per block at the end: same-address atomics retire one after the other, so few blocks with several loads in
   //  flight each -- 2048 blocks spent more time in that queue than reading the two arrays)
   auto term = [&](const float4& a, const float4& b) {
-    // __fmul_rn: the scaled gradient is rounded before the decay term is added, exactly as if the buffer had been scaled first
-    const float x = __fmul_rn(a.x, gsc) + l2 * b.x, y = __fmul_rn(a.y, gsc) + l2 * b.y, z = __fmul_rn(a.z, gsc) + l2 * b.z, w = __fmul_rn(a.w, gsc) + l2 * b.w;
+    const float x = decayed_grad(a.x, gsc, l2, b.x), y = decayed_grad(a.y, gsc, l2, b.y), z = decayed_grad(a.z, gsc, l2, b.z), w = decayed_grad(a.w, gsc, l2, b.w);
     return (double)(x * x + y * y) + (double)(z * z + w * w);
   };
   const size_t stride = (size_t)gridDim.x * blockDim.x;
@@ -391,7 +397,7 @@ __global__ void k_sqnorm(const float* g, const float* p, float gsc, float l2, si
   }
   for (; i < n4; i += stride) s += term(g4[i], p4[i]);
   if (blockIdx.x == 0 && threadIdx.x == 0)
-    for (size_t i = n4 * 4; i < n; ++i) { float x = __fmul_rn(g[i], gsc) + l2 * p[i]; s += (double)x * x; }
+    for (size_t i = n4 * 4; i < n; ++i) { float x = decayed_grad(g[i], gsc, l2, p[i]); s += (double)x * x; }
   for (int o = 32; o > 0; o >>= 1) s += __shfl_xor(s, o);
   if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = s;
   __syncthreads();
@@ -418,7 +424,7 @@ __global__ void k_sqnorm(const float* g, const float* p, float gsc, float l2, si
 }
 
 __global__ void k_amsgrad(float* p, const float* g, float* m, float* v, float* vhat, size_t n, float gsc, float l2, float clip,
-                          const double* sqnorm, float lr_t, float b1, float b2, float eps, int amsgrad, const unsigned* status) {
+                          const double* sqnorm, float lr_t, float omb1, float omb2, float eps, int amsgrad, const unsigned* status) {
   // a persistent kernel of this step timed out (sticky status word): its loss and gradients are garbage, the host finds out when it
   // reads the loss back one step later -- the parameters and moments must not have moved by then
   if (status && *status != 0u) return;
@@ -426,9 +432,9 @@ __global__ void k_amsgrad(float* p, const float* g, float* m, float* v, float* v
   const float rate = clip / norm;                    // A7: r = c / n, applied only when r < 1
   const float gs = rate < 1.f ? rate : 1.f;
   auto one = [&](float& pi, float gi_raw, float& mi, float& vi, float& vh) {      // vh: in = vhat (amsgrad), out = the denominator's v
-    const float gi = (__fmul_rn(gi_raw, gsc) + l2 * pi) * gs;
-    mi += (1.f - b1) * (gi - mi);
-    vi += (1.f - b2) * (gi * gi - vi);
+    const float gi = decayed_grad(gi_raw, gsc, l2, pi) * gs;
+    mi += omb1 * (gi - mi);
+    vi += omb2 * (gi * gi - vi);
     vh = amsgrad ? fmaxf(vh, vi) : vi;
     pi = pi - lr_t * mi / (sqrtf(vh) + eps);
   };
@@ -474,8 +480,8 @@ __global__ void k_decay_clip_noise(float* g, const float* p, size_t n, float gsc
     const float r = sqrtf(-2.f * logf(u1));
     float sn, cs;
     sincosf(6.2831853071795864f * u2, &sn, &cs);
-    g[2 * i] = (__fmul_rn(g[2 * i], gsc) + l2 * p[2 * i]) * gs + sigma * r * cs;
-    if (2 * i + 1 < n) g[2 * i + 1] = (__fmul_rn(g[2 * i + 1], gsc) + l2 * p[2 * i + 1]) * gs + sigma * r * sn;
+    g[2 * i] = decayed_grad(g[2 * i], gsc, l2, p[2 * i]) * gs + sigma * r * cs;
+    if (2 * i + 1 < n) g[2 * i + 1] = decayed_grad(g[2 * i + 1], gsc, l2, p[2 * i + 1]) * gs + sigma * r * sn;
   }
 }
 
@@ -485,7 +491,7 @@ __global__ void k_sgd(float* p, const float* g, size_t n, float gsc, float l2, f
   const float rate = clip / norm;
   const float gs = rate < 1.f ? rate : 1.f;
   for (size_t i = blockIdx.x * (size_t)blockDim.x + threadIdx.x; i < n; i += (size_t)gridDim.x * blockDim.x)
-    p[i] -= lr * (__fmul_rn(g[i], gsc) + l2 * p[i]) * gs;
+    p[i] -= lr * decayed_grad(g[i], gsc, l2, p[i]) * gs;
 }
 
 inline unsigned grid_for(size_t n, int per = 256) {
@@ -663,17 +669,20 @@ int astk_grad_sqnorm_scaled(const float* g, const float* p, float grad_scale, fl
 }
 
 int astk_decay_clip_amsgrad_step(float* p, const float* g, float* m, float* v, float* vhat, size_t n, float l2, float clip,
-                                 const double* sqnorm, float lr_t, float beta1, float beta2, float eps, int amsgrad,
+                                 const double* sqnorm, float lr_t, double beta1, double beta2, float eps, int amsgrad,
                                  void* stream) {
   return astk_decay_clip_amsgrad_step_scaled(p, g, m, v, vhat, n, 1.f, l2, clip, sqnorm, lr_t, beta1, beta2, eps, amsgrad, stream);
 }
 int astk_decay_clip_amsgrad_step_scaled(float* p, const float* g, float* m, float* v, float* vhat, size_t n, float grad_scale, float l2,
-                                        float clip, const double* sqnorm, float lr_t, float beta1, float beta2, float eps, int amsgrad,
+                                        float clip, const double* sqnorm, float lr_t, double beta1, double beta2, float eps, int amsgrad,
                                         void* stream) {
   ASTK_CHECK(p && g && m && v && sqnorm && (vhat || !amsgrad), "amsgrad_step: null pointer");
   if (n == 0) return 0;
+  // the moment rates are float32(1 - beta), the subtraction in double: what Chainer multiplies its float32 arrays with.  (1.f - 0.999f is
+  // 0.99998713e-3: betas handed over as float put v, and with it every step, 1.3e-5 off.)
+  const float omb1 = (float)(1.0 - beta1), omb2 = (float)(1.0 - beta2);
   hipLaunchKernelGGL(k_amsgrad, dim3(grid_for(n)), dim3(256), 0, (hipStream_t)stream, p, g, m, v, vhat, n, grad_scale, l2, clip, sqnorm,
-                     lr_t, beta1, beta2, eps, amsgrad, (const unsigned*)persist_status_ptr());
+                     lr_t, omb1, omb2, eps, amsgrad, (const unsigned*)persist_status_ptr());
   ASTK_LAUNCH_CHECK();
   return 0;
 }

@@ -30,7 +30,7 @@
 extern "C" {
 #endif
 
-#define ASTK_VERSION 107
+#define ASTK_VERSION 108
 #define ASTK_MAX_CNN_LAYERS 4
 #define ASTK_MAX_RNN_LAYERS 8
 #define ASTK_MAX_ATTN 4
@@ -634,14 +634,15 @@ int astk_softmax_ce_fwd(int B, int V, long ld, float* logits_inout, const int32_
  * be ordered on one stream at a time -- which a train step's single optimizer is; astk_persist_status(.., reset = 1) also re-arms it.
  * sqnorm[0] = sum (g + l2*p)^2 in float64 (the clip norm of hook order
  * WeightDecay -> GradientClipping); the step applies decay, the clip rate min(1, clip/sqrt(sqnorm)) and
- * AMSGrad-Adam with lr_t = alpha*sqrt(1-b2^t)/(1-b1^t) computed by the caller.  Both update kernels leave p (and the moments)
+ * AMSGrad-Adam with lr_t = alpha*sqrt(1-b2^t)/(1-b1^t) computed by the caller; beta1 / beta2 are doubles because the kernel multiplies with
+ * float32(1 - beta), the subtraction done in double (as a float, 0.999 has a complement 1.3e-5 off 0.001).  Both update kernels leave p (and the moments)
  * untouched while the persistent kernels' sticky status word is non-zero (a kernel of the step timed out: the gradients are
  * garbage, and the host only learns of it when it reads the loss back).  The word stays set until astk_persist_status(.., reset = 1):
  * a caller must read the status next to the loss at least once per step (the Python shim's loss.data / float(loss) do, and raise) --
  * one that never looks would silently drop every later update while its own step counter advances. */
 int astk_grad_sqnorm(const float* g, const float* p, float l2, size_t n, double* sqnorm, void* stream);
 int astk_decay_clip_amsgrad_step(float* p, const float* g, float* m, float* v, float* vhat, size_t n,
-                                 float l2, float clip, const double* sqnorm, float lr_t, float beta1, float beta2,
+                                 float l2, float clip, const double* sqnorm, float lr_t, double beta1, double beta2,
                                  float eps, int amsgrad, void* stream);
 int astk_decay_clip_sgd_step(float* p, const float* g, size_t n, float l2, float clip, const double* sqnorm,
                              float lr, void* stream);
@@ -650,7 +651,7 @@ int astk_decay_clip_sgd_step(float* p, const float* g, size_t n, float l2, float
  * the decay term is added, exactly as a separate scaling pass would round it). */
 int astk_grad_sqnorm_scaled(const float* g, const float* p, float grad_scale, float l2, size_t n, double* sqnorm, void* stream);
 int astk_decay_clip_amsgrad_step_scaled(float* p, const float* g, float* m, float* v, float* vhat, size_t n, float grad_scale,
-                                        float l2, float clip, const double* sqnorm, float lr_t, float beta1, float beta2,
+                                        float l2, float clip, const double* sqnorm, float lr_t, double beta1, double beta2,
                                         float eps, int amsgrad, void* stream);
 int astk_decay_clip_sgd_step_scaled(float* p, const float* g, size_t n, float grad_scale, float l2, float clip,
                                     const double* sqnorm, float lr, void* stream);

@@ -473,7 +473,11 @@ class RefOptimizer:
 
     def update(self):
         c = self.cfg
-        plist = [(k, p) for k, p in self.model.params() if k not in self.frozen]
+        # Chainer's hooks iterate target.params() without looking at update_rule.enabled (A7): WeightDecay, GradientClipping (norm and
+        # rate) and GradientNoise run over EVERY parameter with a gradient; disable_update() only stops the update rule, so frozen
+        # parameters never get moments either.  (ast_amd/optimizers.py: the norm over the whole arena, the update over enabled_ranges().)
+        plist = list(self.model.params())
+        enabled = [(k, p) for k, p in plist if k not in self.frozen]
         for _, p in plist:                         # reallocate_cleared_grads
             if p.grad is None:
                 p.grad = np.zeros_like(p.data)
@@ -504,7 +508,7 @@ class RefOptimizer:
         if c["type"] == 0:
             b1, b2, eps, alpha = 0.9, 0.999, 1e-8, c["lr"]
             lr_t = alpha * np.sqrt(1.0 - b2 ** self.t) / (1.0 - b1 ** self.t)
-            for k, p in plist:
+            for k, p in enabled:
                 st = self.state.setdefault(k, {n: np.zeros_like(p.data) for n in ("m", "v", "vhat")})
                 dt = p.dtype.type
                 g = p.grad
@@ -513,7 +517,7 @@ class RefOptimizer:
                 np.maximum(st["vhat"], st["v"], out=st["vhat"])
                 p.data -= dt(lr_t) * st["m"] / (np.sqrt(st["vhat"]) + dt(eps))
         else:
-            for _, p in plist:
+            for _, p in enabled:
                 p.data -= p.dtype.type(c["lr"]) * p.grad
 
 

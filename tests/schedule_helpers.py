@@ -52,10 +52,16 @@ class _Fixed:
 _ORACLE = {}
 
 
-def oracle_case(name, cfgf, B, T, D, L, V, drop, teach, x_offset=0.0):
+def _opt_key(opt_cfg):
+    return tuple(sorted((k, tuple(v) if isinstance(v, list) else v) for k, v in opt_cfg.items()))
+
+
+def oracle_case(name, cfgf, B, T, D, L, V, drop, teach, x_offset=0.0, opt_cfg=None):
     """The float64 (reference truth) and float32 (what Chainer-on-NumPy would compute) oracle results of one parity case: computed once per
-    process and shared -- by the three arithmetic schemes and by every schedule the case runs under -- and never changed afterwards."""
-    key = (name, B, T, D, L, V, drop, teach, x_offset)
+    process and shared -- by the three arithmetic schemes and by every schedule the case runs under -- and never changed afterwards.
+    `opt_cfg`: the optimizer section of the experiment config (None: OPT); part of the cache key."""
+    opt_cfg = OPT if opt_cfg is None else opt_cfg
+    key = (name, B, T, D, L, V, drop, teach, x_offset, _opt_key(opt_cfg))
     if key in _ORACLE:
         return _ORACLE[key]
     from oracle import ast_ref as R
@@ -68,7 +74,7 @@ def oracle_case(name, cfgf, B, T, D, L, V, drop, teach, x_offset=0.0):
         if rec:
             m.masks = rec
         noise = np.random.default_rng(9).normal(1.0, 0.25, X.shape).astype(np.float32) if drop > 0 else None
-        opt = R.RefOptimizer(m, OPT)
+        opt = R.RefOptimizer(m, opt_cfg)
         rnd = random.Random("seed-ast-20h")
         loss, _ = R.train_step(m, opt, X.astype(dt), y, teach, add_noise=0.25 if drop > 0 else 0, noise=noise, pyrandom=rnd)
         res[dt] = dict(loss=loss, gnorm=opt.last_grad_norm, model=m, opt=opt, flags=list(m.use_truth), rec=rec, noise=noise,
@@ -117,15 +123,35 @@ def assert_first_step_against_oracle(name, o, lv, gnorm, enc, grads):
         assert err <= tol, f"{name}: grad {k}: err {err:.3e} tol {tol:.3e}"
 
 
-def train_step_parity(name, cfgf, B, T, D, L, V, drop, teach, gemm_scheme, stream=None, knobs=None, inspect=None, x_offset=0.0):
+def gpu_optimizer(model, opt_cfg):
+    """init_optimizer (nn.py:81-119) on the HIP path from the optimizer section of the experiment config: Adam (AMSGrad) for type 0, SGD
+    otherwise; WeightDecay, GradientClipping, GradientNoise in the reference's order; disable_update() on the frozen links."""
+    from ast_amd import optimizers as O
+    opt = O.Adam(alpha=opt_cfg["lr"], beta1=0.9, beta2=0.999, eps=1e-8, amsgrad=True) if opt_cfg["type"] == 0 else O.SGD(lr=opt_cfg["lr"])
+    opt.setup(model)
+    if opt_cfg["l2"] > 0:
+        opt.add_hook(O.WeightDecay(opt_cfg["l2"]))
+    opt.add_hook(O.GradientClipping(opt_cfg["grad_clip"]))
+    if opt_cfg.get("grad_noise_eta", 0) > 0:
+        opt.add_hook(O.GradientNoise(opt_cfg["grad_noise_eta"]))
+    for link in opt_cfg.get("freeze", []):
+        model[link].disable_update()
+    return opt
+
+
+def train_step_parity(name, cfgf, B, T, D, L, V, drop, teach, gemm_scheme, stream=None, knobs=None, inspect=None, x_offset=0.0,
+                      opt_cfg=None):
     """One train step of the HIP path against the float64 oracle, two more updates, the parameter deltas and the BatchNorm statistics.
     `stream`: the torch stream the model runs on (None: the current one -- the legacy default stream in the suite); `knobs`: tuning knobs
     in force for the GPU steps (astk_set_tuning; restored afterwards); `inspect(model)`: called behind the first step, inside the knobs;
-    `x_offset`: a per-bin offset on the features (with_offset)."""
+    `x_offset`: a per-bin offset on the features (with_offset); `opt_cfg`: the optimizer section of the experiment config (None: OPT),
+    for the oracle and for the HIP path alike -- frozen links must come out of the three updates bit for bit as they went in."""
     from oracle.ast_ref_torch import masks_from_recording
-    from ast_amd import _lib, optimizers as O
+    from ast_amd import _lib
     from ast_amd.seq2seq import using_config
-    o = oracle_case(name, cfgf, B, T, D, L, V, drop, teach, x_offset)
+    opt_cfg = OPT if opt_cfg is None else opt_cfg
+    assert opt_cfg.get("grad_noise_eta", 0) == 0, "the oracle's gradient noise is another random stream: no parity to check"
+    o = oracle_case(name, cfgf, B, T, D, L, V, drop, teach, x_offset, opt_cfg)
     cfg, P, X, y = o["cfg"], o["P"], o["X"], o["y"]
     on_stream = torch.cuda.stream(stream) if stream is not None else contextlib.nullcontext()
     with _lib.tuning(knobs or {}), on_stream:
@@ -138,10 +164,7 @@ def train_step_parity(name, cfgf, B, T, D, L, V, drop, teach, gemm_scheme, strea
             g.inject = {k: torch.from_numpy(v) for k, v in packed.items()}
             g.inject["noise"] = torch.from_numpy(o["noise"])
         g.inject["use_truth"] = o["flags"]
-        opt = O.Adam(alpha=1e-3, beta1=0.9, beta2=0.999, eps=1e-8, amsgrad=True)
-        opt.setup(g)
-        opt.add_hook(O.WeightDecay(1e-4))
-        opt.add_hook(O.GradientClipping(2))
+        opt = gpu_optimizer(g, opt_cfg)
         with using_config("train", True):
             loss = g.forward_loss(X=torch.from_numpy(X), y=torch.from_numpy(y), teach_ratio=teach, random_out=0,
                                   add_noise=0.25 if drop > 0 else 0)
@@ -169,6 +192,8 @@ def train_step_parity(name, cfgf, B, T, D, L, V, drop, teach, gemm_scheme, strea
         after = g.arena.to_numpy()
     num = den = 0.0
     for k, p in o["after"].items():
+        if k.split("/")[0] in opt_cfg.get("freeze", []):
+            assert np.array_equal(after[k].view(np.uint32), P[k].view(np.uint32)) and np.array_equal(p, P[k]), f"{name}: frozen {k} moved"
         num += float(((after[k].astype(np.float64) - p) ** 2).sum())
         den += float(((p - P[k]) ** 2).sum())
     # AMSGrad's first steps move every weight by ~lr*sign(g): elements whose gradient is below f32 noise may flip

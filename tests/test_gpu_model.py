@@ -59,6 +59,19 @@ def test_train_step_parity(name, cfgf, B, T, D, L, V, drop, teach, gemm_scheme):
     train_step_parity(name, cfgf, B, T, D, L, V, drop, teach, gemm_scheme, x_offset=16.0 if name.endswith("-offset") else 0.0)
 
 
+@pytest.mark.parametrize("opt_cfg", [
+    {"type": 1, "lr": 0.05, "l2": 1e-4, "grad_clip": 2, "grad_noise_eta": 0, "freeze": []},
+    {"type": 0, "lr": 1e-3, "l2": 1e-4, "grad_clip": 2, "grad_noise_eta": 0, "freeze": ["L0_enc", "out"]},
+], ids=["sgd", "adam-freeze"])
+def test_train_step_parity_under_sgd_and_with_frozen_links(opt_cfg):
+    """The "tiny" case of test_train_step_parity (bf16x3) with the optimizer section of the config varied: SGD, and Adam with two frozen
+    links -- whose gradients still count in the clip norm (Chainer's hooks run over every parameter) while their weights stay put bit for
+    bit.  Same assertions and bounds as the default case."""
+    from schedule_helpers import train_step_parity
+    g = train_step_parity("tiny", lambda d: tiny_cfg(c1=8, drop=d), 3, 21, 26, 6, 11, 0.0, 1.0, "bf16x3", opt_cfg=opt_cfg)
+    assert len(g.enabled_ranges()) == (2 if opt_cfg["freeze"] else 1)      # CNN | (L0_enc) | L1_enc .. L1_dec | (out)
+
+
 def test_predict_greedy_matches_oracle():
     from oracle import ast_ref as R
     cfg = _mid_cfg(0.3)

@@ -961,6 +961,7 @@ def test_softmax_ce_loss_rows_are_read_before_the_gradient_overwrites_the_logits
 
 def test_optimizer_step_matches_reference(lib):
     from oracle.ast_ref import RefOptimizer
+    from optimizer_model import TOL
     from oracle import minichainer as F
     rng = np.random.default_rng(2)
     n = 10007
@@ -979,6 +980,7 @@ def test_optimizer_step_matches_reference(lib):
     p[:n] = dev(p0)
     mm, vv, vh = torch.zeros_like(p), torch.zeros_like(p), torch.zeros_like(p)
     sq = torch.zeros(1, dtype=torch.float64, device="cuda")
+    above = 0.0
     for t, g0 in enumerate(grads, 1):
         m.p["a/W"].grad = g0.copy()
         ref.update()
@@ -990,6 +992,12 @@ def test_optimizer_step_matches_reference(lib):
         ok(lib, lib.astk_decay_clip_amsgrad_step(vp(p), vp(g), vp(mm), vp(vv), vp(vh), npad, 1e-4, 2.0, vp(sq), lr_t, 0.9, 0.999, 1e-8, 1,
                                                  stream()))
         close(p[:n], m.p["a/W"].data, rtol=1e-5, msg=f"params after step {t}")
+        # the moments too, at the tolerances tests/optimizer_model.py derives: p alone cannot tell AMSGrad from plain Adam
+        for q, got in (("m", mm), ("v", vv), ("vhat", vh)):
+            close(got[:n], ref.state["a/W"][q], rtol=TOL[q], msg=f"{q} after step {t}")
+        st = ref.state["a/W"]
+        above = max(above, float(np.mean(st["vhat"] > st["v"])))
+    assert above > 0.25, "the draws must make AMSGrad's maximum matter at some step"
     assert float(p[n:].abs().max()) == 0.0
 
 

@@ -150,6 +150,40 @@ def test_hooks_and_amsgrad_A7_A8():
     assert st["vhat"][0] == pytest.approx(v1[2]) and st["v"][0] == pytest.approx(0.999 * v1[2])
 
 
+@pytest.mark.parametrize("kind", [1, 0])
+def test_frozen_parameters_still_count_in_decay_norm_and_clip_A7(kind):
+    """Chainer's hooks iterate target.params() whether or not a link's update is enabled; disable_update() only stops the update rule.
+    a = [3, 4] frozen, b = [1], gradients equal to the values, l2 = 0, clip = 2: the norm is sqrt(9 + 16 + 1) = sqrt(26) (not 1), the
+    clip factor 2 / sqrt(26) = 0.392, and only b moves."""
+    class M:
+        def __init__(self):
+            self.p = {"a/W": F.Parameter(np.array([3.0, 4.0])), "b/W": F.Parameter(np.array([1.0]))}
+
+        def params(self):
+            return list(self.p.items())
+    m = M()
+    opt = R.RefOptimizer(m, {"type": kind, "lr": 0.1, "l2": 0, "grad_clip": 2, "grad_noise_eta": 0, "freeze": ["a"]})
+    m.p["a/W"].grad, m.p["b/W"].grad = np.array([3.0, 4.0]), np.array([1.0])
+    opt.update()
+    r = 2 / np.sqrt(26)
+    assert abs(opt.last_grad_norm - np.sqrt(26)) < 1e-12
+    assert list(m.p["a/W"].data) == [3.0, 4.0] and "a/W" not in opt.state
+    np.testing.assert_allclose(m.p["a/W"].grad, np.array([3.0, 4.0]) * r, rtol=1e-15)      # the hooks did run over the frozen gradient
+    if kind == 1:       # SGD: b = 1 - 0.1 * 0.392 = 0.9608
+        assert m.p["b/W"].data[0] == pytest.approx(1 - 0.1 * r, abs=1e-15) and abs(m.p["b/W"].data[0] - 0.9608) < 5e-5
+    else:               # Adam, first step: m = 0.1 g, v = 0.001 g^2, lr_1 = lr sqrt(0.001) / 0.1 -> a step of lr g / (|g| + eps sqrt(1000))
+        g = r
+        lr1 = 0.1 * np.sqrt(1 - 0.999) / (1 - 0.9)
+        assert m.p["b/W"].data[0] == pytest.approx(1 - lr1 * 0.1 * g / (np.sqrt(0.001 * g * g) + 1e-8), abs=1e-14)
+        assert opt.state["b/W"]["vhat"][0] == pytest.approx(0.001 * g * g, rel=1e-12)
+    # with a decay: the frozen weights feed the norm through l2 * p as well
+    m2 = M()
+    opt2 = R.RefOptimizer(m2, {"type": kind, "lr": 0.1, "l2": 1.0, "grad_clip": 2, "grad_noise_eta": 0, "freeze": ["a"]})
+    m2.p["a/W"].grad, m2.p["b/W"].grad = np.array([0.0, 0.0]), np.array([0.0])
+    opt2.update()
+    assert abs(opt2.last_grad_norm - np.sqrt(26)) < 1e-12
+
+
 def test_batchnorm_train_and_running_stats_A4():
     rng = np.random.default_rng(0)
     x = rng.standard_normal((2, 3, 4, 5)) * 2 + 1
