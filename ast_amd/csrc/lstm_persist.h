@@ -6,9 +6,8 @@ namespace astk {
 
 // one (direction, layer) cell of a launch, as lstm.hip's plan describes it; the launchers copy it into the kernels' PCellF / PCellB
 struct PersistCellHost {
-  const float *Wl, *Wu, *bias, *zx, *xin, *mask, *WlT, *d_enc, *d_hT, *d_cT;
+  const float *Wl, *Wu, *bias, *zx, *xin, *mask, *d_enc, *d_hT, *d_cT;
   float *gates, *C, *HR, *HD, *enc;
-  const float* WuT;               // backward: this cell's transposed upward weight (layers >= 1)
   float *PR, *PD;                 // backward, reduce-scatter path: partial-sum buffers of this cell
   const float* PD_up;
   int up_external;
@@ -27,6 +26,11 @@ bool lstm_persist_applicable(int T, int B, int h, int nl, int nd);
 // Form of the recurrence workgroups (the `rows` argument of everything below): 16 = one 16-row batch tile per 256-thread workgroup;
 // 33 = DUO: two 16-row tiles per 512-thread workgroup; 32 = MT 2: two tiles per 256-thread workgroup (lstm_persist.hip has the measurements)
 int lstm_persist_rows(int B, int h, int nl, int nd, bool side);
+// (Virtual) workgroup rows of a cell under form `rows`: 16-row batch tiles at 16; at 33 two virtual workgroups per 32 rows, so an EVEN number
+// of 16-row tiles (what lstm.hip sizes the workspace for, whatever the form); at 32 one workgroup per 32 rows.  The grid has as many rows at 16
+// and 32, half as many at 33.  Rows of the arrival counters (the abort word sits behind them), arrivals per unit slice on a progress counter,
+// rows of the deterministic bias-gradient sums.
+int lstm_persist_wg_rows(int B, int rows);
 // Layers per launch: one workgroup per CU must hold a launch's whole grid.  0 = not applicable.
 int lstm_persist_layers_per_launch(int B, int h, int nl, int nd, int rows);
 // workgroups of one launch over `layers` layers of all directions

@@ -1251,21 +1251,29 @@ __global__ __launch_bounds__(256, 1) void lstm_persist_bwd_rs(PBwdArgs a) {
 // other -- a step is only ~40 % hand-off latency -- 4.4 / 5.3 us per step against 2.9 / 3.6; DUO overlaps one tile's vector-ALU work with the
 // other's MFMAs and hand-off wait.  Knob lstm.rows32: -1 (default) = DUO where available when it spares launches or the caller runs
 // side-stream work, MT 2 when it spares launches and DUO is not available; 0 = always 16; 1 = MT 2 / 2 = DUO whenever possible.
-static bool duo_available(int h) { return h <= 256 && gemm_precision_mode() == 1 && tune_on(TUNE_LSTM_X3) && tune_on(TUNE_LSTM_X4); }
+// Arithmetic of the recurrences' products: the mode in force for this call (2 = fp16x2: two-term fp16 splits; 3 = bf16x3: three-term bf16
+// splits where the weight fragments fit the registers, h <= 256; 4 = bf16x3 with the weights' lo plane in LDS, h >= 512; 0 = f32 MFMAs: f32
+// mode, "lstm.x3" 0 under bf16x3, or "lstm.x4" 0 at h >= 512).
+static int recurrence_xs(int h) {
+  const int mode = gemm_precision_mode();
+  const bool x3_off = !tune_on(TUNE_LSTM_X3), x4_off = !tune_on(TUNE_LSTM_X4);
+  return mode == 0 ? 2 : (mode == 1 && !x3_off ? (h <= 256 ? 3 : (x4_off ? 0 : 4)) : 0);
+}
+static bool duo_available(int h) { return recurrence_xs(h) == 3 && tune_on(TUNE_LSTM_X4); }
+int lstm_persist_wg_rows(int B, int rows) { return rows == 16 ? (B + 15) / 16 : rows == 33 ? 2 * ((B + 31) / 32) : (B + 31) / 32; }
 int lstm_persist_rows(int B, int h, int nl, int nd, bool side) {
   const int knob = (int)tune(TUNE_LSTM_ROWS32);
   if (knob == 0 || h > 256 || B <= 16) return 16;
   if (knob == 1) return 32;
   if (knob >= 2) return duo_available(h) ? 33 : 16;
   const long cus = device_cu_count();
-  const long wg16 = (long)(h / 16) * ((B + 15) / 16) * nd * nl, wg32 = (long)(h / 16) * ((B + 31) / 32) * nd * nl;
+  const long wg16 = (long)(h / 16) * lstm_persist_wg_rows(B, 16) * nd * nl, wg32 = (long)(h / 16) * lstm_persist_wg_rows(B, 32) * nd * nl;
   const long launches16 = (wg16 + cus - 1) / cus, launches32 = (wg32 + cus - 1) / cus;
   if (launches32 < launches16) return duo_available(h) ? 33 : 32;
   return side && duo_available(h) && tune_on(TUNE_LSTM_DUO_SIDE) ? 33 : 16;
 }
 int lstm_persist_layers_per_launch(int B, int h, int nl, int nd, int rows) {
-  const int rw = rows == 16 ? 16 : 32;
-  const long per_layer = (long)(h / 16) * ((B + rw - 1) / rw) * nd;
+  const long per_layer = lstm_persist_grid_wgs(B, h, 1, nd, rows);
   const long cus = device_cu_count();
   if (per_layer < 1 || per_layer > cus) return 0;
   long lpl = cus / per_layer;
@@ -1276,7 +1284,7 @@ int lstm_persist_layers_per_launch(int B, int h, int nl, int nd, int rows) {
 }
 
 // workgroups of one launch over `layers` layers of all directions
-int lstm_persist_grid_wgs(int B, int h, int layers, int nd, int rows) { const int rw = rows == 16 ? 16 : 32; return (h / 16) * ((B + rw - 1) / rw) * nd * layers; }
+int lstm_persist_grid_wgs(int B, int h, int layers, int nd, int rows) { return (h / 16) * lstm_persist_wg_rows(B, rows == 16 ? 16 : 32) * nd * layers; }
 
 // Hoisted form (h = 1024): the weight fragments of one product fill a workgroup's registers, so every layer runs as a launch of its
 // own over cells that get their input projection from a batched GEMM in front of it (forward) and leave the gradient for the layer below
@@ -1291,9 +1299,45 @@ bool lstm_persist_applicable(int T, int B, int h, int nl, int nd) {
   }
   if (lstm_persist_layers_per_launch(B, h, nl, nd, lstm_persist_rows(B, h, nl, nd, false)) < 1) return false;
   // hand-off buffers are addressed with 32-bit byte offsets
-  if ((long)T * B * h * 16 >= (1L << 31) || (long)T * (2 * ((B + 31) / 32)) * (h / 16) * (h / 16) * 1024 >= (1L << 31)) return false;
+  if ((long)T * B * h * 16 >= (1L << 31) || (long)T * lstm_persist_wg_rows(B, 33) * (h / 16) * (h / 16) * 1024 >= (1L << 31)) return false;
   if (!tune_on(TUNE_LSTM_PERSIST)) return false;
   return true;
+}
+
+// The kernel of a launch: form (rows), width (h) and arithmetic (recurrence_xs) choose among the instantiations of K's two kernel templates.
+struct FwdKernels {
+  using Args = PFwdArgs;
+  static constexpr const char* name = "lstm_persist_fwd";
+  template <int KB, int XS, int MT> static void (*g())(PFwdArgs) { return lstm_persist_fwd_g<KB, XS, MT>; }
+  template <int KB> static void (*duo())(PFwdArgs) { return lstm_persist_fwd_duo<KB>; }
+};
+struct BwdKernels {
+  using Args = PBwdArgs;
+  static constexpr const char* name = "lstm_persist_bwd";
+  template <int KB, int XS, int MT> static void (*g())(PBwdArgs) { return lstm_persist_bwd_rs<KB, XS, MT>; }
+  template <int KB> static void (*duo())(PBwdArgs) { return lstm_persist_bwd_duo<KB>; }
+};
+// h <= 256: fp16x2, bf16x3 or f32, one or two batch tiles per workgroup; h >= 512: fp16x2, bf16x3 with the lo plane in LDS or f32, one tile
+template <class K, int KB> static void (*narrow_kernel(int xs, int rows))(typename K::Args) {
+  if (rows == 32) return xs == 2 ? K::template g<KB, 2, 2>() : xs == 3 ? K::template g<KB, 3, 2>() : K::template g<KB, 0, 2>();
+  return xs == 2 ? K::template g<KB, 2, 1>() : xs == 3 ? K::template g<KB, 3, 1>() : K::template g<KB, 0, 1>();
+}
+template <class K, int KB> static void (*wide_kernel(int xs))(typename K::Args) {
+  return xs == 2 ? K::template g<KB, 2, 1>() : xs == 4 ? K::template g<KB, 4, 1>() : K::template g<KB, 0, 1>();
+}
+template <class K> static int launch_recurrence(const typename K::Args& a, int h, int rows, dim3 grid, hipStream_t s) {
+  const int xs = recurrence_xs(h);
+  void (*k)(typename K::Args);
+  if (rows == 33) {
+    ASTK_CHECK(xs == 3 && tune_on(TUNE_LSTM_X4), "%s: the two-waves-per-SIMD form needs the bf16x3 arithmetic", K::name);
+    k = h == 64 ? K::template duo<1>() : h == 128 ? K::template duo<2>() : K::template duo<4>();
+  } else {
+    k = h == 64 ? narrow_kernel<K, 1>(xs, rows) : h == 128 ? narrow_kernel<K, 2>(xs, rows) : h == 256 ? narrow_kernel<K, 4>(xs, rows)
+        : h == 512 ? wide_kernel<K, 8>(xs) : wide_kernel<K, 16>(xs);
+  }
+  hipLaunchKernelGGL(k, grid, dim3(rows == 33 ? 512 : 256), 0, s, a);
+  ASTK_LAUNCH_CHECK();
+  return 0;
 }
 
 int lstm_persist_fwd_launch(const PersistCellHost* cells, int ncells, int nl, int T, int B, int h, int H, unsigned* counters, int rows,
@@ -1301,9 +1345,8 @@ int lstm_persist_fwd_launch(const PersistCellHost* cells, int ncells, int nl, in
   PFwdArgs a;
   memset(&a, 0, sizeof(a));
   ASTK_CHECK(rows == 16 || ((rows == 32 || rows == 33) && h <= 256), "lstm_persist_fwd: form %d at h = %d", rows, h);
-  const bool duo = rows == 33;
-  const int nby = (B + (rows == 16 ? 16 : 32) - 1) / (rows == 16 ? 16 : 32);      // workgroup rows of the grid
-  const int nbt = duo ? 2 * nby : nby;                                            // (virtual) workgroup rows the counters are laid out for
+  const int nbt = lstm_persist_wg_rows(B, rows);      // (virtual) workgroup rows the counters are laid out for
+  const int nby = rows == 33 ? nbt / 2 : nbt;         // workgroup rows of the grid
   for (int i = 0; i < ncells; ++i) {
     const PersistCellHost& c = cells[i];
     PCellF& d = a.c[i];
@@ -1315,7 +1358,6 @@ int lstm_persist_fwd_launch(const PersistCellHost* cells, int ncells, int nl, in
   a.dbg = persist_dbg_env();
   a.done = counters;
   a.ab = abort_ctl(counters + (size_t)ncells * nbt * 64, PERSIST_ENC_FWD);
-  dim3 grid(h / 16, nby, ncells), blk(duo ? 512 : 256);
   {
     // hand-off buffers = the saved activations themselves: sentinel-filled before every launch (the counters / abort word ride along, zeroed)
     FillSegs f;
@@ -1329,34 +1371,7 @@ int lstm_persist_fwd_launch(const PersistCellHost* cells, int ncells, int nl, in
     ASTK_TRY(fill_u32_segments(f, 0xffffffffu, s));
   }
   ProfScope prof(PROF_CELL, s);
-  // arithmetic of the recurrences' products: the mode in force for this call (fp16x2: two-term fp16 splits; bf16x3: three-term bf16 splits
-  // where the weight fragments fit the registers, h <= 256; f32, or bf16x3 at h = 512: f32 MFMAs).  "lstm.x3" 0 keeps f32 MFMAs under bf16x3.
-  const int mode = gemm_precision_mode();
-  const bool x3_off = !tune_on(TUNE_LSTM_X3), x4_off = !tune_on(TUNE_LSTM_X4);
-  const int xs = mode == 0 ? 2 : (mode == 1 && !x3_off ? (h <= 256 ? 3 : (x4_off ? 0 : 4)) : 0);       // (4: bf16x3 with the weights' lo plane in LDS)
-  if (duo) {
-    ASTK_CHECK(xs == 3 && !x4_off, "lstm_persist_fwd: the two-waves-per-SIMD form needs the bf16x3 arithmetic");
-    switch (h) {
-      case 64: hipLaunchKernelGGL((lstm_persist_fwd_duo<1>), grid, blk, 0, s, a); break;
-      case 128: hipLaunchKernelGGL((lstm_persist_fwd_duo<2>), grid, blk, 0, s, a); break;
-      default: hipLaunchKernelGGL((lstm_persist_fwd_duo<4>), grid, blk, 0, s, a); break;
-    }
-    ASTK_LAUNCH_CHECK();
-    return 0;
-  }
-#define ASTK_LSTM_FWD_(KB_, XS_, MT_) hipLaunchKernelGGL((lstm_persist_fwd_g<KB_, XS_, MT_>), grid, blk, 0, s, a)
-#define ASTK_LSTM_FWD_XS_(KB_, MT_) { if (xs == 2) ASTK_LSTM_FWD_(KB_, 2, MT_); else if (xs == 3) ASTK_LSTM_FWD_(KB_, 3, MT_); else ASTK_LSTM_FWD_(KB_, 0, MT_); }
-  switch (h) {
-    case 64: if (rows == 32) ASTK_LSTM_FWD_XS_(1, 2) else ASTK_LSTM_FWD_XS_(1, 1) break;
-    case 128: if (rows == 32) ASTK_LSTM_FWD_XS_(2, 2) else ASTK_LSTM_FWD_XS_(2, 1) break;
-    case 256: if (rows == 32) ASTK_LSTM_FWD_XS_(4, 2) else ASTK_LSTM_FWD_XS_(4, 1) break;
-    case 512: if (xs == 2) ASTK_LSTM_FWD_(8, 2, 1); else if (xs == 4) ASTK_LSTM_FWD_(8, 4, 1); else ASTK_LSTM_FWD_(8, 0, 1); break;
-    default: if (xs == 2) ASTK_LSTM_FWD_(16, 2, 1); else if (xs == 4) ASTK_LSTM_FWD_(16, 4, 1); else ASTK_LSTM_FWD_(16, 0, 1); break;
-  }
-#undef ASTK_LSTM_FWD_XS_
-#undef ASTK_LSTM_FWD_
-  ASTK_LAUNCH_CHECK();
-  return 0;
+  return launch_recurrence<FwdKernels>(a, h, rows, dim3(h / 16, nby, ncells), s);
 }
 
 int lstm_persist_bwd_launch(const PersistCellHost* cells, int ncells, int nl, int T, int B, int h, int H, unsigned* counters,
@@ -1364,9 +1379,8 @@ int lstm_persist_bwd_launch(const PersistCellHost* cells, int ncells, int nl, in
   PBwdArgs a;
   memset(&a, 0, sizeof(a));
   ASTK_CHECK(rows == 16 || ((rows == 32 || rows == 33) && h <= 256), "lstm_persist_bwd: form %d at h = %d", rows, h);
-  const bool duo = rows == 33;
-  const int nby = (B + (rows == 16 ? 16 : 32) - 1) / (rows == 16 ? 16 : 32);      // workgroup rows of the grid
-  const int nbt = duo ? 2 * nby : nby;                                            // (virtual) workgroup rows: the counters are per (virtual) workgroup row
+  const int nbt = lstm_persist_wg_rows(B, rows);      // (virtual) workgroup rows: the counters are per (virtual) workgroup row
+  const int nby = rows == 33 ? nbt / 2 : nbt;         // workgroup rows of the grid
   for (int i = 0; i < ncells; ++i) {
     const PersistCellHost& c = cells[i];
     PCellB& d = a.c[i];
@@ -1400,39 +1414,13 @@ int lstm_persist_bwd_launch(const PersistCellHost* cells, int ncells, int nl, in
   } else {
     ASTK_HIP(hipMemsetAsync(counters, 0, ((size_t)2 * ncells * nbt + 1) * 64 * sizeof(unsigned), s));
   }
-  dim3 grid(h / 16, nby, ncells), blk(duo ? 512 : 256);
   ProfScope prof(PROF_CELL, s);
-  const int mode = gemm_precision_mode();      // (see lstm_persist_fwd_launch)
-  const bool x3_off = !tune_on(TUNE_LSTM_X3), x4_off = !tune_on(TUNE_LSTM_X4);
-  const int xs = mode == 0 ? 2 : (mode == 1 && !x3_off ? (h <= 256 ? 3 : (x4_off ? 0 : 4)) : 0);
-  if (duo) {
-    ASTK_CHECK(xs == 3 && !x4_off, "lstm_persist_bwd: the two-waves-per-SIMD form needs the bf16x3 arithmetic");
-    switch (h) {
-      case 64: hipLaunchKernelGGL((lstm_persist_bwd_duo<1>), grid, blk, 0, s, a); break;
-      case 128: hipLaunchKernelGGL((lstm_persist_bwd_duo<2>), grid, blk, 0, s, a); break;
-      default: hipLaunchKernelGGL((lstm_persist_bwd_duo<4>), grid, blk, 0, s, a); break;
-    }
-    ASTK_LAUNCH_CHECK();
-    return 0;
-  }
-#define ASTK_LSTM_BWD_(KB_, XS_, MT_) hipLaunchKernelGGL((lstm_persist_bwd_rs<KB_, XS_, MT_>), grid, blk, 0, s, a)
-#define ASTK_LSTM_BWD_XS_(KB_, MT_) { if (xs == 2) ASTK_LSTM_BWD_(KB_, 2, MT_); else if (xs == 3) ASTK_LSTM_BWD_(KB_, 3, MT_); else ASTK_LSTM_BWD_(KB_, 0, MT_); }
-  switch (h) {
-    case 64: if (rows == 32) ASTK_LSTM_BWD_XS_(1, 2) else ASTK_LSTM_BWD_XS_(1, 1) break;
-    case 128: if (rows == 32) ASTK_LSTM_BWD_XS_(2, 2) else ASTK_LSTM_BWD_XS_(2, 1) break;
-    case 256: if (rows == 32) ASTK_LSTM_BWD_XS_(4, 2) else ASTK_LSTM_BWD_XS_(4, 1) break;
-    case 512: if (xs == 2) ASTK_LSTM_BWD_(8, 2, 1); else if (xs == 4) ASTK_LSTM_BWD_(8, 4, 1); else ASTK_LSTM_BWD_(8, 0, 1); break;
-    default: if (xs == 2) ASTK_LSTM_BWD_(16, 2, 1); else if (xs == 4) ASTK_LSTM_BWD_(16, 4, 1); else ASTK_LSTM_BWD_(16, 0, 1); break;
-  }
-#undef ASTK_LSTM_BWD_XS_
-#undef ASTK_LSTM_BWD_
-  ASTK_LAUNCH_CHECK();
-  return 0;
+  return launch_recurrence<BwdKernels>(a, h, rows, dim3(h / 16, nby, ncells), s);
 }
 
 // bytes of the reduce-scatter partial buffers of one cell (lstm.hip sizes the workspace with these)
 // (sized for an EVEN number of 16-row tiles: a 32-row workgroup addresses tiles 2 by and 2 by + 1 whether the second one has rows or not)
-size_t lstm_persist_pr_floats(int B, int h) { return (size_t)PR_RING * (2 * ((B + 31) / 32)) * (h / 16) * (h / 16) * 256; }
-size_t lstm_persist_pd_floats(int T, int B, int h) { return (size_t)T * (2 * ((B + 31) / 32)) * (h / 16) * (h / 16) * 256; }
+size_t lstm_persist_pr_floats(int B, int h) { return (size_t)PR_RING * lstm_persist_wg_rows(B, 33) * (h / 16) * (h / 16) * 256; }
+size_t lstm_persist_pd_floats(int T, int B, int h) { return (size_t)T * lstm_persist_wg_rows(B, 33) * (h / 16) * (h / 16) * 256; }
 
 }  // namespace astk

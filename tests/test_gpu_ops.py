@@ -370,6 +370,24 @@ def test_lstm_stack_32_row_workgroups_and_side_stream(lib, tune, T, B, in_dim, h
     _lstm_stack_case(lib, T, B, in_dim, h, nl, masks, side=side, chunks=chunks, exact=gemm_split != "fp16x2")
 
 
+@pytest.mark.parametrize("T,B,in_dim,h,nl,masks,knob", [(5, 17, 16, 64, 2, True, "lstm.persist"), (3, 4, 16, 1024, 2, False, "lstm.hoist")])
+def test_lstm_stack_per_step_loop_at_the_persistent_widths(lib, T, B, in_dim, h, nl, masks, knob, gemm_split):
+    """The route's per-step branch at widths where every other test takes a persistent path: "lstm.persist" 0 at h = 64 (two batch tiles, the
+    second ragged) and "lstm.hoist" 0 at h = 1024.  astk_lstm_stack_path returns 0 and the per-step loop runs on a workspace whose
+    row-sized buffers (counters, bias-gradient rows) are carved all the same.  Same float64 reference and tolerances as test_lstm_stack."""
+    _lstm_stack_case(lib, T, B, in_dim, h, nl, masks, knobs={knob: 0}, path=0)
+
+
+@pytest.mark.parametrize("form", [0, 1, 2])
+def test_lstm_stack_deterministic_bias_gradients_over_workgroup_rows(lib, form, gemm_split):
+    """astk_lstm_stack_desc.deterministic = 1: the persistent backward kernel leaves its bias-gradient sums per (virtual) workgroup row and
+    k_fold_db adds the rows in order.  33 batch rows are 3 rows of 16 under "lstm.rows32" 0, 2 rows of 32 under 1 and 4 virtual rows (the
+    last without batch rows) under 2 -- which is bf16x3's: under the other schemes the knob leaves the 16-row form, as in
+    test_lstm_stack_32_row_workgroups_and_side_stream -- with a ragged last tile each.  Within the usual tolerance of the float64 reference,
+    and two calls on zeroed gradients give every db bit-equal."""
+    _lstm_stack_case(lib, 6, 33, 16, 64, 2, True, knobs={"lstm.rows32": form}, path=1, deterministic=True)
+
+
 # Forward chunks of 4 steps that plan_side_fwd's rate model puts on the side stream on an MI355X (256 CUs), per shape (T, B, in_dim, h, layers)
 # and recurrence form (0: 16 rows per workgroup, 1 / 2: the 32-row forms), as astk_lstm_stack_side_plan reports them: a chunk of a 16-wide input
 # costs ~15.7 model-us against 2.6-4 per recurrence step, so stacks of a few steps stay in line entirely.  (The counts follow from the device's
@@ -412,10 +430,26 @@ def _concurrent_stream(lib, main):
     pytest.skip("no pair of concurrently executing streams on this device")
 
 
-def _lstm_stack_case(lib, T, B, in_dim, h, nl, masks, side=False, chunks=None, exact=True, late=False, bias_gain=1.0, x_gain=1.0):
+def _lstm_stack_case(lib, *args, knobs=None, **kw):
+    """knobs: tuning knobs (astk_set_tuning) in force for this case only; everything else: _lstm_stack_body."""
+    prev = {}
+    try:
+        for k, v in (knobs or {}).items():
+            prev[k] = C.c_double()
+            assert lib.astk_get_tuning(k.encode(), C.byref(prev[k])) == 0 and lib.astk_set_tuning(k.encode(), float(v)) == 0, k
+        _lstm_stack_body(lib, *args, **kw)
+    finally:
+        for k, v in prev.items():
+            lib.astk_set_tuning(k.encode(), v.value)
+
+
+def _lstm_stack_body(lib, T, B, in_dim, h, nl, masks, side=False, chunks=None, exact=True, late=False, bias_gain=1.0, x_gain=1.0, path=None,
+                     deterministic=False):
     """chunks (with side): the forward chunks the library must plan for this case; exact: the side-stream forward results are compared bit for
     bit with an in-line call (else within close()); late: the side stream is held back (see below); bias_gain, x_gain: tests/range_cases.py
-    lstm_draws (gains on the biases and the input: saturated gates)."""
+    lstm_draws (gains on the biases and the input: saturated gates); path: what astk_lstm_stack_path must return (default: 1 / 2 at the
+    widths of the persistent / hoisted kernels); deterministic: the descriptor's field -- a second forward and backward on zeroed gradients
+    must then give the bits of the first in every bias gradient."""
     from ast_amd._lib import LstmGrads, LstmParams, LstmStackDesc
     from oracle.ast_ref_torch import encoder_torch
     cfg = {"rnn_config": {"enc_layers": nl}}
@@ -427,7 +461,10 @@ def _lstm_stack_case(lib, T, B, in_dim, h, nl, masks, side=False, chunks=None, e
     assert g_enc.shape == enc.shape and g_c.shape == cT.shape and g_h.shape == hT.shape
     (enc * torch.tensor(g_enc)).sum().add((cT * torch.tensor(g_c)).sum()).add((hT * torch.tensor(g_h)).sum()).backward()
     d = LstmStackDesc(T, B, in_dim, h, nl, 2)
-    if h in (64, 128, 256, 512, 1024):
+    d.deterministic = 1 if deterministic else 0
+    if path is not None:
+        assert lib.astk_lstm_stack_path(C.byref(d)) == path, "encoder path"
+    elif h in (64, 128, 256, 512, 1024):
         assert lib.astk_lstm_stack_path(C.byref(d)) == (2 if h == 1024 else 1), "persistent encoder path not taken"
     main, side_s = None, None
     if side:                            # the op on a stream of its own + a second one for the chunked products (joined inside the calls)
@@ -497,6 +534,18 @@ def _lstm_stack_case(lib, T, B, in_dim, h, nl, masks, side=False, chunks=None, e
     for k in P:
         ref_g = Pt[k].grad if Pt[k].grad is not None else torch.zeros_like(Pt[k])   # T=1: lateral.W is never used
         close(grd[k], ref_g, rtol=5e-4, atol=None if float(ref_g.abs().max()) > 0 else 1e-12, msg="grad " + k)
+    if deterministic:
+        first = {k: grd[k].clone() for k in P if k.endswith("/upward/b")}
+        for v in grd.values():
+            v.zero_()
+        ok(lib, lib.astk_lstm_stack_fwd(C.byref(d), lp, vp(xd), vp(md), vp(enc_d), vp(cT_d), vp(hT_d), vp(ws), nbytes, stream()))
+        ok(lib, lib.astk_lstm_stack_bwd(C.byref(d), lp, lg, vp(xd), vp(md), vp(ge_d), vp(gc_d), vp(gh_d), vp(dx), vp(ws),
+                                        nbytes, stream()))
+        torch.cuda.synchronize()
+        ws.check("lstm fwd + bwd again")
+        assert len(first) == 2 * nl
+        for k, v in first.items():
+            assert torch.equal(grd[k], v), f"grad {k}: two deterministic calls differ by {float((grd[k] - v).abs().max()):.3e}"
     if side:
         mask = C.c_uint(0)
         assert lib.astk_persist_status(C.byref(mask), 1) == 0 and mask.value == 0, mask.value
