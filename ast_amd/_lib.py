@@ -84,7 +84,8 @@ class DecoderDesc(_Sized, C.Structure):
                 ("A", C.c_int), ("V", C.c_int), ("n_layers", C.c_int),
                 ("n_attn", C.c_int), ("no_feed_attn", C.c_int), ("ln", C.c_int), ("loss_rows", C.c_int),
                 ("use_truth_host", C.POINTER(C.c_int32)), ("precision", C.c_int), ("gemm_operands", C.c_int), ("status_dst", C.c_void_p),
-                ("zero_ptr", C.c_void_p), ("zero_bytes", C.c_size_t), ("side_wgs", C.c_int), ("deterministic", C.c_int)]
+                ("zero_ptr", C.c_void_p), ("zero_bytes", C.c_size_t), ("side_wgs", C.c_int), ("deterministic", C.c_int),
+                ("label_smoothing", C.c_float)]
 
 
 
@@ -203,6 +204,7 @@ SIGNATURES = {
     "astk_attn_step_fwd_rows": (C.c_int, [_I, _I, _I, _VP, _VP, _VP, _VP, _VP, _VP, _VP, _SZ, _VP]),
     "astk_spin": (C.c_int, [C.c_uint, _VP, _VP]),
     "astk_softmax_ce_fwd": (C.c_int, [_I, _I, _L, _VP, _VP, _L, _VP, _F, _VP, _VP, _VP]),
+    "astk_softmax_ce_fwd_ex": (C.c_int, [_I, _I, _L, _VP, _VP, _L, _VP, _F, _F, _VP, _VP, _VP]),
     "astk_grad_sqnorm": (C.c_int, [_VP, _VP, _F, _SZ, _VP, _VP]),
     "astk_decay_clip_amsgrad_step": (C.c_int, [_VP, _VP, _VP, _VP, _VP, _SZ, _F, _F, _VP, _F, C.c_double, C.c_double, _F, _I, _VP]),
     "astk_decay_clip_sgd_step": (C.c_int, [_VP, _VP, _SZ, _F, _F, _VP, _F, _VP]),

@@ -127,12 +127,15 @@ DecRoute dec_route(const astk_decoder_desc* d, bool has_out_mask) {
   return r;
 }
 
+bool label_smoothing_ok(float eps) { return std::isfinite(eps) && eps >= 0.f && eps < 1.f; }
+
 int dec_validate(const astk_decoder_desc* d) {
   ASTK_CHECK_DESC(d, astk_decoder_desc);
   ASTK_CHECK(d && d->B > 0 && d->L >= 2 && d->T > 0 && d->V > 1, "decoder: bad dims");
   ASTK_CHECK(d->n_layers >= 1 && d->n_layers <= ASTK_MAX_RNN_LAYERS, "decoder: layers");
   ASTK_CHECK((d->H % 4) == 0 && (d->E % 4) == 0 && (d->A % 4) == 0, "decoder: H, E, A must be multiples of 4");
   ASTK_CHECK(d->n_attn >= 0 && d->n_attn <= ASTK_MAX_ATTN, "decoder: n_attn %d (max %d)", d->n_attn, ASTK_MAX_ATTN);
+  ASTK_CHECK(label_smoothing_ok(d->label_smoothing), "decoder: label_smoothing %g (finite, 0 <= eps < 1)", (double)d->label_smoothing);
   return 0;
 }
 
@@ -191,7 +194,8 @@ void make_plan(const astk_decoder_desc* d, const DecRoute& r, void* ws, DecPlan&
   P.CESTAT = c.take<float>(pp ? S * B * (size_t)((P.V + 15) / 16) * 4 : 4);
   P.ENCA = c.take<float>(pp ? B * (size_t)P.T * H : 4);
   P.MLB = c.take<float>(pp ? S * B * 2 : 4);
-  P.PCTR = c.take<unsigned>(pp ? (size_t)(8 * 32 * ((P.B + 15) / 16) + 2 + P.B) * 64 : 4);   // sharded phase counters, abort word, per-row counters
+  P.PCTR = c.take<unsigned>(pp ? (size_t)(8 * 32 * ((P.B + 15) / 16) + 2 + P.B + 1) * 64 : 4);   // sharded phase counters, abort word, per-row
+                                                                                                 // counters, k_decoder_post's arrival counter
   P.DXH = c.take<float>(pp ? 2 * S * B * (size_t)P.A : 4);
   P.bytes = c.total();
 }
@@ -291,11 +295,14 @@ __global__ void k_embed_bwd_det(float* __restrict__ d_embed, const int32_t* __re
 // (one decoder step: rows_per_step = B and `targets` points at the step's column).  argmax_only: feedback tokens of a step whose loss is
 // scored later (the batched pass); fed_flags (the loop's use_truth, n_steps entries): that batched pass leaves the argmax of the steps
 // whose token was fed back (flag of the NEXT step 0) as the loop wrote it.
+// eps > 0: label smoothing (astk_decoder_desc.label_smoothing).  The uniform term LSE - mean(x) is formed as
+// log(se) - mean(x - mx) from the deviations the sum of exponentials reads anyway (all <= 0: no cancellation, whatever the offset of the
+// row); eps == 0 runs the arithmetic this kernel always had.
 __global__ __launch_bounds__(256) void k_softmax_ce(int V, long ld, float* logits, const int32_t* __restrict__ targets,
-                                                    long t_stride, int rows_per_step, const float* __restrict__ cw, float inv_count,
+                                                    long t_stride, int rows_per_step, const float* __restrict__ cw, float inv_count, float eps,
                                                     float* __restrict__ loss_rows, int32_t* __restrict__ argmax, int argmax_only,
                                                     const int32_t* __restrict__ fed_flags, int n_steps) {
-  __shared__ float sv[4];
+  __shared__ float sv[4], sd[4];
   __shared__ int si[4];
   const int b = blockIdx.x;
   const int step = b / rows_per_step, brow = b - step * rows_per_step;
@@ -322,12 +329,19 @@ __global__ __launch_bounds__(256) void k_softmax_ce(int V, long ld, float* logit
     if (threadIdx.x == 0 && argmax) argmax[b] = mi;
     return;
   }
-  float sum = 0.f;
-  for (int v = threadIdx.x; v < V; v += 256) sum += expf(x[v] - mx);
+  float sum = 0.f, dev = 0.f;
+  for (int v = threadIdx.x; v < V; v += 256) {
+    const float dv = x[v] - mx;
+    sum += expf(dv);
+    dev += dv;
+  }
   for (int o = 32; o > 0; o >>= 1) sum += __shfl_xor(sum, o);
-  if (lane == 0) sv[wave] = sum;
+  if (eps > 0.f)
+    for (int o = 32; o > 0; o >>= 1) dev += __shfl_xor(dev, o);
+  if (lane == 0) { sv[wave] = sum; sd[wave] = dev; }
   __syncthreads();
   sum = sv[0] + sv[1] + sv[2] + sv[3];
+  dev = (sd[0] + sd[1]) + (sd[2] + sd[3]);
   const float lse = mx + logf(sum);
   int t = targets[(long)brow * t_stride + step];
   const bool ignore = t < 0;                      // ignore_label = -1 never occurs on this path (PAD is 0)
@@ -340,12 +354,27 @@ __global__ __launch_bounds__(256) void k_softmax_ce(int V, long ld, float* logit
   // Now: no __restrict__ on the row, a volatile load, and the loss row is finished in front of the barrier.
   const float xt = *reinterpret_cast<const volatile float*>(&x[t]);
   if (threadIdx.x == 0) {
-    if (loss_rows) loss_rows[b] = -(xt - lse) * w * inv_count;
+    if (loss_rows) {
+      if (eps > 0.f) loss_rows[b] = w * inv_count * ((1.f - eps) * (lse - xt) + eps * (logf(sum) - dev / (float)V));
+      else loss_rows[b] = -(xt - lse) * w * inv_count;
+    }
     const bool fed = fed_flags && step + 1 < n_steps && fed_flags[step + 1] == 0;
     if (argmax && !fed) argmax[b] = mi;
   }
   __syncthreads();
   const float scale = w * inv_count;
+  if (eps > 0.f) {
+    const float uni = eps / (float)V, hot = (1.f - eps) * scale;
+    for (int v = threadIdx.x; v < ld; v += 256) {
+      float g = 0.f;
+      if (v < V) {
+        g = (expf(x[v] - lse) - uni) * scale;
+        if (v == t) g -= hot;
+      }
+      x[v] = g;
+    }
+    return;
+  }
   for (int v = threadIdx.x; v < ld; v += 256) {
     float g = 0.f;
     if (v < V) {
@@ -588,7 +617,7 @@ int fwd_score_all(const DecFwdCall& f, const DecPlan& P) {
   ASTK_TRY(gemm_launch(GEMM_NT, gemm_args(S * B, V, A, mat(P.HT + (size_t)B * A, A), mat(f.prm->Wo, A), P.LOGITS, P.Vp, f.prm->bo), f.s));
   if (f.out_mask) ASTK_TRY(mul_rows_launch(P.LOGITS, P.Vp, f.out_mask, V, S * B, V, f.s));
   hipLaunchKernelGGL(k_softmax_ce, dim3(S * B), dim3(256), 0, f.s, V, (long)P.Vp, P.LOGITS, f.tgt + 1, (long)P.L, B, f.prm->class_weight, inv_count,
-                     P.LOSSROWS, P.PRED, 0, f.use_truth, S);
+                     f.d->label_smoothing, P.LOSSROWS, P.PRED, 0, f.use_truth, S);
   ASTK_LAUNCH_CHECK();
   if (f.out_mask) ASTK_TRY(mul_rows_launch(P.LOGITS, P.Vp, f.out_mask, V, S * B, V, f.s));
   return 0;
@@ -646,10 +675,11 @@ int fwd_steps(const DecFwdCall& f, const DecPlan& P) {
       if (om) ASTK_TRY(mul_rows_launch(lg, P.Vp, om, V, B, V, s));
       if (uth) {
         hipLaunchKernelGGL(k_softmax_ce, dim3(B), dim3(256), 0, s, V, (long)P.Vp, lg, f.tgt + st + 1, (long)P.L, B, (const float*)nullptr, 1.f,
-                           (float*)nullptr, P.PRED + (size_t)st * B, 1, (const int32_t*)nullptr, 0);
+                           0.f, (float*)nullptr, P.PRED + (size_t)st * B, 1, (const int32_t*)nullptr, 0);
         ASTK_LAUNCH_CHECK();
       } else {
-        ASTK_TRY(softmax_ce_launch(B, V, P.Vp, lg, f.tgt + st + 1, P.L, prm->class_weight, inv_count, P.LOSSROWS + (size_t)st * B, P.PRED + (size_t)st * B, s));
+        ASTK_TRY(softmax_ce_launch(B, V, P.Vp, lg, f.tgt + st + 1, P.L, prm->class_weight, inv_count, f.d->label_smoothing, P.LOSSROWS + (size_t)st * B,
+                                  P.PRED + (size_t)st * B, s));
         if (om) ASTK_TRY(mul_rows_launch(lg, P.Vp, om, V, B, V, s));
       }
     }
@@ -923,9 +953,10 @@ int bwd_params(const DecBwdCall& b, const DecPlan& P, const DecRoute& r) {
 }  // namespace
 
 int softmax_ce_launch(int B, int V, long ld, float* logits, const int32_t* targets, long t_stride, const float* cw, float inv_count,
-                      float* loss_rows, int32_t* argmax, hipStream_t s) {
+                      float eps, float* loss_rows, int32_t* argmax, hipStream_t s) {
   ASTK_CHECK(B > 0 && V > 0 && ld >= V && logits && targets, "softmax_ce: bad arguments");
-  hipLaunchKernelGGL(k_softmax_ce, dim3(B), dim3(256), 0, s, V, ld, logits, targets, t_stride, B, cw, inv_count, loss_rows, argmax, 0,
+  ASTK_CHECK(label_smoothing_ok(eps), "softmax_ce: label_smoothing %g (finite, 0 <= eps < 1)", (double)eps);
+  hipLaunchKernelGGL(k_softmax_ce, dim3(B), dim3(256), 0, s, V, ld, logits, targets, t_stride, B, cw, inv_count, eps, loss_rows, argmax, 0,
                      (const int32_t*)nullptr, 0);
   ASTK_LAUNCH_CHECK();
   return 0;
@@ -965,7 +996,13 @@ size_t astk_decoder_workspace_bytes(const astk_decoder_desc* d) {
 
 int astk_softmax_ce_fwd(int B, int V, long ld, float* logits_inout, const int32_t* targets, long t_stride, const float* class_weight,
                         float inv_count, float* loss_rows, int32_t* argmax, void* stream) {
-  return softmax_ce_launch(B, V, ld, logits_inout, targets, t_stride, class_weight, inv_count, loss_rows, argmax, (hipStream_t)stream);
+  return astk_softmax_ce_fwd_ex(B, V, ld, logits_inout, targets, t_stride, class_weight, inv_count, 0.f, loss_rows, argmax, stream);
+}
+
+int astk_softmax_ce_fwd_ex(int B, int V, long ld, float* logits_inout, const int32_t* targets, long t_stride, const float* class_weight,
+                           float inv_count, float label_smoothing, float* loss_rows, int32_t* argmax, void* stream) {
+  return softmax_ce_launch(B, V, ld, logits_inout, targets, t_stride, class_weight, inv_count, label_smoothing, loss_rows, argmax,
+                           (hipStream_t)stream);
 }
 
 int astk_decoder_fwd(const astk_decoder_desc* d, const astk_decoder_params* prm, const float* enc, const float* c0, const float* h0,
@@ -1212,7 +1249,7 @@ int decoder_step_run(const astk_decoder_desc* d, const astk_decoder_params* prm,
   if (io.argmax) {
     // argmax only: run the CE kernel on a scratch copy so that `logits` stays intact
     ASTK_TRY(copy2d_f32(P.LOGITS, P.Vp, io.logits, V, B, V, P.Vp, s));
-    ASTK_TRY(softmax_ce_launch(B, V, P.Vp, P.LOGITS, io.tokens, 1, nullptr, 1.f, nullptr, io.argmax, s));
+    ASTK_TRY(softmax_ce_launch(B, V, P.Vp, P.LOGITS, io.tokens, 1, nullptr, 1.f, 0.f, nullptr, io.argmax, s));
   }
   return 0;
 }

@@ -2152,13 +2152,32 @@ __global__ __launch_bounds__(256, 1) void decoder_persist_bwd(PDecBwdArgs a) {
 //   * TOK[s][b] (the token that was fed) and X0[s][b][:E] = embed[TOK] * mask for the backward's wgrad / scatter,
 //   * dlogits = w[t] (softmax - onehot) / B in place of the saved logits,
 //   * the copy of the prediction; block 0 also sums the per-row losses (in double).
+// eps > 0 (astk_decoder_desc.label_smoothing): the sweep that forms the gradient also accumulates sum_v (x_v - lse)
+// -- deviations of one sign, whatever the offset of the row -- and the block replaces its loss row (the loop's P6 wrote w c (LSE - x_t)) by
+// (1-eps) row + eps w c (-(1/V) sum).  Block 0 can then no longer sum rows that other blocks of this launch rewrite: every block stores its
+// row, fences and arrives ONCE on `done_ctr` (a word the forward launcher's fill zeroes); the block whose arrival completes S*B sums all
+// rows the way block 0 does.  No block waits for another, nothing spins, and there are no float atomics: the sum is the same whichever
+// block comes last.  eps == 0 is the code this kernel always ran.
+template <bool ATOMIC_LOADS>
+__device__ __forceinline__ void post_sum_rows(const float* rows, int n, float* loss, double* red) {
+  double acc = 0.0;
+  for (int i = threadIdx.x; i < n; i += 256)
+    acc += (double)(ATOMIC_LOADS ? __hip_atomic_load(rows + i, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) : rows[i]);
+  for (int o = 32; o > 0; o >>= 1) acc += __shfl_xor(acc, o);
+  if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = acc;
+  __syncthreads();
+  if (threadIdx.x == 0) *loss = (float)(red[0] + red[1] + red[2] + red[3]);
+}
+
 __global__ __launch_bounds__(256) void k_decoder_post(const float* __restrict__ embed, const int32_t* __restrict__ y, const int32_t* __restrict__ ytgt,
                                                       const int32_t* __restrict__ use_truth,
                                                       const int32_t* __restrict__ pred, const float* __restrict__ emb_mask, int32_t* __restrict__ tok_out,
                                                       float* __restrict__ x0, float* __restrict__ logits, const float* __restrict__ lse,
-                                                      const float* __restrict__ cw, const float* __restrict__ lossrows, float* __restrict__ loss,
+                                                      const float* __restrict__ cw, float* lossrows, float* __restrict__ loss,
                                                       int32_t* __restrict__ pred_out, int S, int B, int L, int E, int XI, int V, int Vp, float inv_count,
-                                                      const unsigned* __restrict__ status, float* __restrict__ status_dst) {
+                                                      float eps, unsigned* done_ctr, const unsigned* __restrict__ status,
+                                                      float* __restrict__ status_dst) {
+  __shared__ double red[4];
   const int r = blockIdx.x, s = r / B, b = r % B;
   if (r == 0 && threadIdx.x == 0 && status_dst) *status_dst = (float)(*status);      // (astk_decoder_desc.status_dst: the snapshot without its launch)
   {
@@ -2180,6 +2199,35 @@ __global__ __launch_bounds__(256) void k_decoder_post(const float* __restrict__ 
     const float scale = (cw ? cw[t] : 1.f) * inv_count;
     const float ls = lse[r];
     float* x = logits + (long)r * Vp;
+    if (eps > 0.f) {
+      __shared__ float sdev[4];
+      __shared__ int s_last;
+      const float uni = eps / (float)V, hot = (1.f - eps) * scale;
+      float dev = 0.f;
+      for (int v = threadIdx.x; v < Vp; v += 256) {
+        float g = 0.f;
+        if (v < V) {
+          const float dv = x[v] - ls;
+          dev += dv;
+          g = (expf(dv) - uni) * scale;
+          if (v == t) g -= hot;
+        }
+        x[v] = g;
+      }
+      for (int o = 32; o > 0; o >>= 1) dev += __shfl_xor(dev, o);
+      if ((threadIdx.x & 63) == 0) sdev[threadIdx.x >> 6] = dev;
+      __syncthreads();
+      if (threadIdx.x == 0) {
+        dev = (sdev[0] + sdev[1]) + (sdev[2] + sdev[3]);
+        const float row = (1.f - eps) * lossrows[r] + eps * scale * (-(dev / (float)V));
+        __hip_atomic_store(lossrows + r, row, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        // release: the row is visible to the device before the arrival; acquire: the last block sees every other block's row
+        s_last = __hip_atomic_fetch_add(done_ctr, 1u, __ATOMIC_ACQ_REL, __HIP_MEMORY_SCOPE_AGENT) + 1u == (unsigned)(S * B);
+      }
+      __syncthreads();
+      if (s_last && loss) post_sum_rows<true>(lossrows, S * B, loss, red);
+      return;
+    }
     for (int v = threadIdx.x; v < Vp; v += 256) {
       float g = 0.f;
       if (v < V) {
@@ -2189,15 +2237,7 @@ __global__ __launch_bounds__(256) void k_decoder_post(const float* __restrict__ 
       x[v] = g;
     }
   }
-  if (r == 0 && loss) {
-    __shared__ double red[4];
-    double acc = 0.0;
-    for (int i = threadIdx.x; i < S * B; i += 256) acc += (double)lossrows[i];
-    for (int o = 32; o > 0; o >>= 1) acc += __shfl_xor(acc, o);
-    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = acc;
-    __syncthreads();
-    if (threadIdx.x == 0) *loss = (float)(red[0] + red[1] + red[2] + red[3]);
-  }
+  if (r == 0 && loss) post_sum_rows<false>(lossrows, S * B, loss, red);
 }
 
 }  // namespace
@@ -2369,7 +2409,8 @@ int decoder_persist_fwd_launch(const astk_decoder_desc* d, const astk_decoder_pa
   {
     FillSegs f;
     f.n = 0;
-    fill_seg_add(f, bf.ctr, ((size_t)NPHASE_SLOTS * NSH * a.nbt + 2 + a.B) * CTRS * sizeof(unsigned), 0u);
+    // (... and one more line behind the per-row counters: k_decoder_post's arrival counter, `post_ctr` below)
+    fill_seg_add(f, bf.ctr, ((size_t)NPHASE_SLOTS * NSH * a.nbt + 2 + a.B + 1) * CTRS * sizeof(unsigned), 0u);
     fill_seg_add(f, bf.CVH, (size_t)a.S * a.B * 2 * a.H * sizeof(float));
     if (bf.zero_a) fill_seg_add(f, bf.zero_a, bf.zero_a_bytes, 0u);
     if (bf.zero_b) fill_seg_add(f, bf.zero_b, bf.zero_b_bytes, 0u);
@@ -2391,8 +2432,10 @@ int decoder_persist_fwd_launch(const astk_decoder_desc* d, const astk_decoder_pa
   ASTK_LAUNCH_CHECK();
   // Q[s][b][:] = Wa h_top + ba for all steps (needed by the backward's deferred d_enc product)
   ASTK_TRY(gemm_launch(GEMM_NT, gemm_args(a.S * a.B, a.H, a.H, mat(bf.CVH + a.H, 2 * a.H), mat(prm->Wa, a.H), bf.Q, a.H, prm->ba), s));
+  unsigned* post_ctr = bf.ctr + ((size_t)NPHASE_SLOTS * NSH * a.nbt + 2 + a.B) * CTRS;
   hipLaunchKernelGGL(k_decoder_post, dim3(a.S * a.B), dim3(256), 0, s, prm->embed, y, ytgt ? ytgt : y, use_truth, bf.PRED, emb_mask, bf.TOK, bf.X0, bf.LOGITS, bf.LSE,
-                     prm->class_weight, bf.LOSSROWS, loss, pred_out, a.S, a.B, a.L, a.E, a.XI, a.V, a.Vp, a.inv_count, persist_status_word(), d->status_dst);
+                     prm->class_weight, bf.LOSSROWS, loss, pred_out, a.S, a.B, a.L, a.E, a.XI, a.V, a.Vp, a.inv_count, d->label_smoothing, post_ctr,
+                     persist_status_word(), d->status_dst);
   ASTK_LAUNCH_CHECK();
   return 0;
 }

@@ -14,7 +14,7 @@ from . import dist as adist
 from . import optimizers, serializers
 from .config import Config
 from .dataloader import SYMBOLS, FisherDataLoader, GlobalPhoneDataLoader, SyntheticDataLoader
-from .seq2seq import SpeechEncoderDecoder, raise_if_aborted, using_config
+from .seq2seq import SpeechEncoderDecoder, checked_label_smoothing, raise_if_aborted, using_config
 
 _ADAM = 0
 _SGD = 1
@@ -485,6 +485,9 @@ def read_one_batch_late(nn, set_key, labels, enqueue):
 class NN:
     def __init__(self, cfg_path, vocab_size=None):
         self.cfg = Config(cfg_path, vocab_size=vocab_size)
+        # extension key: extras.label_smoothing = eps of the TRAINING loss (default 0 = the reference's loss).  The
+        # training loop alone passes it: dev loss, predict_scored and score never smooth, so dev losses compare across runs with different eps.
+        self.label_smoothing = checked_label_smoothing(self.cfg.train.get("extras", {}).get("label_smoothing", 0.0), "extras.label_smoothing")
         self.model_dir = self.cfg.model["model_dir"]
         self.gpuid = self.cfg.train["gpuid"]
         if adist.is_distributed():
@@ -604,7 +607,7 @@ class NN:
                 with using_config("train", True):
                     loss = self.model.forward_loss(X=batch["X"], y=batch["y"], teach_ratio=ex["teach_ratio"],
                                                    random_out=ex["random_out"], add_noise=ex["speech_noise"],
-                                                   y_global=batch.get("y_global"))
+                                                   y_global=batch.get("y_global"), label_smoothing=self.label_smoothing)
                     self.model.cleargrads()
                     loss.backward()
                     self.optimizer.update()

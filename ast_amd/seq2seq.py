@@ -345,6 +345,17 @@ def checked_targets(y, V):
     return y.astype(np.int32, copy=False)
 
 
+def checked_label_smoothing(eps, what="label_smoothing"):
+    """eps as a float; ValueError for anything but a finite number with 0 <= eps < 1 (a bool or a string is no number)."""
+    import numbers
+    if isinstance(eps, bool) or not isinstance(eps, (numbers.Real, np.floating, np.integer)):
+        raise ValueError(f"{what} must be a number with 0 <= eps < 1, got {eps!r}")
+    eps = float(eps)
+    if not np.isfinite(eps) or eps < 0.0 or eps >= 1.0:
+        raise ValueError(f"{what} must be finite with 0 <= eps < 1, got {eps!r}")
+    return eps
+
+
 ROWS_MAX = 32       # the device loop's batch (include/astk.h: B <= 32)
 
 
@@ -946,10 +957,12 @@ class SpeechEncoderDecoder:
         dst.copy_(buf[:len(flags)], non_blocking=True)
         ev.record(torch.cuda.current_stream(self.device))
 
-    def forward_loss(self, X, y, teach_ratio, random_out=0, add_noise=0, y_global=None):
-        """seq2seq.py:399-473.  y_global (data parallelism with random_out > 0 only): the targets of the WHOLE unsharded batch as a host
+    def forward_loss(self, X, y, teach_ratio, random_out=0, add_noise=0, y_global=None, label_smoothing=0.0):
+        """seq2seq.py:399-473.  label_smoothing (extension): eps of the training loss, uniform over all classes and
+        weighted by the target's class weight; 0 = the reference's loss.  Predictions and fed-back tokens do not depend on it.  y_global (data parallelism with random_out > 0 only): the targets of the WHOLE unsharded batch as a host
         array, global row b * world + r = row b of rank r -- the loader has them before it shards (`batch["y_global"]`); without it the
         ranks' targets are all-gathered, a host-blocking collective in front of every step."""
+        label_smoothing = checked_label_smoothing(label_smoothing)
         lib = self._require_gpu()
         X = self._as_input(X)
         if isinstance(y, np.ndarray):
@@ -996,6 +1009,7 @@ class SpeechEncoderDecoder:
             self._upload_flags(st["flags"], flags)
         st["flags_host"] = (C.c_int32 * S)(*flags)          # the per-launch loop scores the teacher-forced steps behind the loop (astk.h)
         st["dd"].use_truth_host = C.cast(st["flags_host"], C.POINTER(C.c_int32))
+        st["dd"].label_smoothing = label_smoothing          # read by the forward call only (include/astk.h)
         st["y"] = y
         st["targets"] = targets
         dr = self.cfg["dropout"]

@@ -314,6 +314,11 @@ typedef struct {
                           `deterministic` resolves to 1 (the field, else "gemm.deterministic") must not run beside other GEMM launches --
                           astk_decoder_bwd_phase_ex refuses `side_wgs` > 0 together with it */
   int deterministic;   /* backward calls: 1 = weight-gradient split tiles summed in a fixed order (see astk_cnn_desc.deterministic); 0 = process default */
+  float label_smoothing; /* eps of the training loss, finite and 0 <= eps < 1 (0 = the plain cross-entropy):
+                          row = w[t]/count ((1-eps)(LSE - x_t) + eps (LSE - mean_v x_v)), uniform over all V classes and weighted by the TARGET's
+                          class weight.  Read by astk_decoder_fwd(_ex) only, on every path: the gradient of the logits is formed in the forward
+                          call, so the backward calls need nothing.  The greedy, scored, sampled, forced, beam and step-infer entry points
+                          ignore it (they only validate it with the rest of the descriptor); argmax and `pred` do not depend on it. */
 } astk_decoder_desc;
 
 typedef struct {
@@ -627,6 +632,12 @@ int astk_step_bn_relu_bwd(int T, int B, int C, const float* z, const float* stat
  * place of logits; argmax (first maximum) written when non-NULL.  (Chainer-sem A6) */
 int astk_softmax_ce_fwd(int B, int V, long ld, float* logits_inout, const int32_t* targets, long t_stride,
                         const float* class_weight, float inv_count, float* loss_rows, int32_t* argmax, void* stream);
+/* ... with label smoothing eps (finite, 0 <= eps < 1; astk_decoder_desc.label_smoothing):
+ * loss_rows[b] = w[t_b]/B ((1-eps)(LSE - x_t) + eps (LSE - mean_v x_v)); dlogits = w[t_b](softmax - (1-eps) onehot - eps/V)/B.
+ * astk_softmax_ce_fwd is this call with eps = 0. */
+int astk_softmax_ce_fwd_ex(int B, int V, long ld, float* logits_inout, const int32_t* targets, long t_stride,
+                           const float* class_weight, float inv_count, float label_smoothing, float* loss_rows, int32_t* argmax,
+                           void* stream);
 
 /* ---------------------------------------------------------------- optimizer  (nn.py:81-119, Chainer-sem A7/A8)
  * One flat parameter / gradient buffer.  ONE norm launch at a time per process: astk_grad_sqnorm(_scaled) folds its per-block partial
