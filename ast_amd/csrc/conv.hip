@@ -77,7 +77,8 @@ struct CnnPlan {
   size_t bytes;
 };
 
-int conv_out(int n, int k, int s, int p) { return (n + 2 * p - k) / s + 1; }
+// (0 when the padded input is shorter than the kernel: C's division truncates towards zero, -1 / 2 + 1 would come out as one output step)
+int conv_out(int n, int k, int s, int p) { return n + 2 * p < k ? 0 : (n + 2 * p - k) / s + 1; }
 
 int make_plan(const astk_cnn_desc* d, void* ws, CnnPlan& P) {
   ASTK_CHECK_DESC(d, astk_cnn_desc);
@@ -230,9 +231,13 @@ constexpr int C0_JP = 20;
 constexpr int C0_TT = 80;
 constexpr int C0_NKS = 6;           // 32-k MFMA steps over kt * JP <= 192 (kt <= 9)
 static int conv0_win_elems(int st) { return st * C0_JP * (C0_TT - 1) + 32 * C0_NKS + 40; }    // (+ the rows the last tile of a group owns in XF)
+// A pooled layer 0 takes im2col + GEMM: its BatchNorm normalises the POOLED rows, the direct kernel's fused statistics are sums over the
+// un-pooled output.  Windows 0 and 1 mean no pooling; -1 (the whole extent) pools like any window > 1 (make_plan).
+static bool conv0_pooled(const astk_cnn_desc* d) {
+  return (d->pool_t[0] != 0 && d->pool_t[0] != 1) || (d->pool_f[0] != 0 && d->pool_f[0] != 1);
+}
 static bool conv0_direct_shape(const astk_cnn_desc* d) {
-  return conv0_win_elems(d->st[0]) <= 512 * 8 && (size_t)d->C[0] * d->kt[0] * d->kf[0] * 4 <= 64 * 1024 && d->kt[0] * C0_JP <= 32 * C0_NKS && d->kf[0] <= 14 && (d->st[0] % 2) == 0 && d->C[0] <= 128 && (d->C[0] % 16) == 0 && d->pool_t[0] <= 1 &&
-         d->pool_f[0] <= 1;
+  return conv0_win_elems(d->st[0]) <= 512 * 8 && (size_t)d->C[0] * d->kt[0] * d->kf[0] * 4 <= 64 * 1024 && d->kt[0] * C0_JP <= 32 * C0_NKS && d->kf[0] <= 14 && (d->st[0] % 2) == 0 && d->C[0] <= 128 && (d->C[0] % 16) == 0 && !conv0_pooled(d);
 }
 // the direct path is taken for the shipped layer-0 shapes under the default arithmetic (bf16x3, f32 operands); forward and backward decide
 // alike (same descriptor, same process default).  astk_set_tuning("conv.direct0", 0): the im2col + GEMM path always.

@@ -115,7 +115,16 @@ int astk_debug_gemm_group(int layout, int n, const int* M, const int* N, const i
 /* ---------------------------------------------------------------- CNN front-end  (seq2seq.py:158-180)
  * [Conv2D(no bias) -> (max-pool) -> BatchNorm(train: batch stats) -> ReLU] x n_layers (or, with no_bn, [Conv2D(bias) -> ReLU]), then the (T'',B,C*F') time-major
  * re-layout with feature index c*F'+f (quirk Q9).  Layer 0: in_channels 1, kernel (kt,kf), stride (st,sf),
- * pad (pt,0).  Layers >= 1: kernel (kt,1), stride (st,1), pad (pt,0) -- the shipped cnn_config. */
+ * pad (pt,0).  Layers >= 1: kernel (kt,1), stride (st,1), pad (pt,0) -- the shipped cnn_config.
+ *
+ * Supported geometry: 1..ASTK_MAX_CNN_LAYERS layers; every C a multiple of 4; layer 0 any 1 <= kf <= D, sf >= 1 (sf != kf included:
+ * overlapping frequency windows or bins no window covers); every layer kt >= st >= 1 and pt >= 0; no frequency padding, no dilation;
+ * every layer's padded input at least kt long.  Anything else is refused by every entry point with a message naming the cause,
+ * before a launch.  The shipped stack is (9,13)/(2,13)/4 then (9,1)/(2,1)/4; tests/test_gpu_cnn_geometry.py runs fourteen other
+ * stacks (1, 2, 3 and 4 layers, kt 2..13, kf 1..16, st 1..13, pt 0..6, sf below / equal to / above kf) against the float64 reference
+ * under the three arithmetic schemes, and the refusals.  Layer-0 shapes with st = 2, kt <= 9, kf <= 14, C a multiple of 16 up to 128
+ * and no pooling run as a direct convolution under the default arithmetic; every other shape, and every pooled layer 0, as
+ * im2col + GEMM. */
 typedef struct {
   size_t struct_size;  /* sizeof(astk_cnn_desc) of the header the caller was built against: every entry point refuses a descriptor whose size
                           differs from its own (the descriptors carry pointers the library writes through -- status_dst here, zero_ptr in the

@@ -77,17 +77,38 @@ def cnn_cfg(c0, c1):
     return tiny_cfg(c0=c0, c1=c1)
 
 
-def cnn_draws(B, T, D, c0, c1, with_noise, x_offset=0.0, seed=0, ramp=True, centre_taps=False):
+def cnn_geometry_cfg(layers, pool=None):
+    """tiny_cfg with its convolution stack replaced: layers = [(C, kt, kf, st, sf, pt), ...] (no frequency padding); pool: the optional
+    per-layer (time, frequency) max-pooling windows of the old path (cnn_config["cnn_pool"])."""
+    from conftest import tiny_cfg
+    cfg = tiny_cfg()
+    cfg["cnn_config"]["cnn_layers"] = [{"in_channels": None, "out_channels": C, "ksize": [kt, kf], "stride": [st, sf], "pad": [pt, 0]}
+                                       for C, kt, kf, st, sf, pt in layers]
+    if pool is not None:
+        cfg["cnn_config"]["cnn_pool"] = [list(w) for w in pool]
+    return cfg
+
+
+def shipped_layers(c0, c1):
+    """The shipped two-layer geometry as a `layers` list."""
+    return [(c0, 9, 13, 2, 13, 4), (c1, 9, 1, 2, 1, 4)]
+
+
+def cnn_draws(B, T, D, c0, c1, with_noise, x_offset=0.0, seed=0, ramp=True, centre_taps=False, layers=None, pool=None):
     """-> cfg, P (float64), X, noise, rng (the generator behind the draws: the upstream gradient comes from it once the output shape is known).
     x_offset: X = N(0, 1) + x_offset * (0.5 + d / D) per frequency bin d (ramp = False: + x_offset on every bin); seed: of the weights
     (seed + 1) and of everything else; centre_taps: the layer-0 weights keep their centre time tap only (the other time taps are 0), so
     that no output step loses taps to the zero padding in time -- with ramp = False every output of a channel then carries the same
-    offset x_offset * (tap sum) and the channel's spread is the noise's alone."""
+    offset x_offset * (tap sum) and the channel's spread is the noise's alone.  layers: None = the shipped two layers with (c0, c1)
+    channels; else the stack as cnn_geometry_cfg takes it (c0, c1 are not used then), the draws in the same order: weights, then per layer
+    gamma and beta, then X, then the noise.  pool: cnn_geometry_cfg's."""
     from oracle.ast_ref import init_params
-    cfg = cnn_cfg(c0, c1)
+    cfg = cnn_cfg(c0, c1) if layers is None else cnn_geometry_cfg(layers)
+    if pool is not None:
+        cfg["cnn_config"]["cnn_pool"] = [list(w) for w in pool]
     P = init_params(cfg, D, 11, seed=seed + 1, dtype=np.float64)
     rng = np.random.default_rng(seed)
-    for i in range(2):                       # non-trivial BN affine
+    for i in range(len(cfg["cnn_config"]["cnn_layers"])):      # non-trivial BN affine, every layer
         P[f"CNN_{i}_bn/gamma"] = 1 + 0.3 * rng.standard_normal(P[f"CNN_{i}_bn/gamma"].shape)
         P[f"CNN_{i}_bn/beta"] = 0.2 * rng.standard_normal(P[f"CNN_{i}_bn/beta"].shape)
     X = rng.standard_normal((B, T, D))
@@ -284,6 +305,58 @@ CNN_CASES = [((2, 170, 26, 16, 8), False, 8.0, 1, False, False), ((2, 16, 13, 4,
              ((2, 50, 80, 8, 12), True, 8.0, 0, True, False)]
 
 
+# CNN front-end geometries (tests/test_gpu_cnn_geometry.py): (id, B, T, D, layers [(C, kt, kf, st, sf, pt), ...], seed without noise, seed with noise).
+# Every other CNN case of the suite runs the shipped geometry (kernel (9, 13) stride (2, 13) pad 4, then (9, 1) (2, 1) 4, two layers), where
+# sf == kf, st = 2, kt = 9, pt = 4 -- a frequency offset f * kf for f * sf, or stride-phase arithmetic right for two phases only, would pass.
+# The seeds: cnn_draws' convention; the smallest at which the float64 reference has NO post-BatchNorm pre-activation within 2e-5 of the
+# ReLU's kink in any layer (searched on the CPU, asserted by the GPU test and by tests/test_ranges_host.py), so that every gradient is held
+# to the tight 5e-4.  What each row reaches:
+#   kt5-kf8-l1s1     direct kernel with kt * JP = 100, even kf (JG = 8), F' = 10; layer 1 with stride 1 (one phase)
+#   kf14-sf7-pt0     kf = the direct kernel's maximum (no pad column in XF), overlapping frequency windows, no time padding, even kt above
+#   gaps-pt6-l1s3    sf > kf (input bins no window covers), pt = kt - 1, an uncovered trailing input row; three stride phases above
+#   kt2-st2          kt == st at both layers (one tap per phase), F' = 1
+#   kf1              kf = 1 (JG = 2)
+#   two-tiles        three direct-kernel tiles per (b, f) (167 output steps, ragged last), C0 = 48 (the second wave holds half its channels)
+#   kt11-st3-kf16    im2col under every scheme: kt > 9, kf > 14, odd stride
+#   st1-l1s13        layer-0 stride 1; 13 stride phases over 12 phase-weight buffers (the flush); 5 uncovered input rows
+#   one-layer        layer 0 is the last layer
+#   three-layers     a middle layer (consumes and produces padded buffers)
+#   four-layers      ASTK_MAX_CNN_LAYERS
+#   one-layer-c64    layer 0 is the last layer AND has the 64 channels the tiled sequence re-layout / its fused BatchNorm backward need
+#   f10-c64-last     those tiled kernels at F' = 10 (6 (t, b) pairs per 64-slot block iteration, 4 slots idle)
+#   f20-kf4          F' = 20 > 16: the un-tiled re-layout and the row-layout BatchNorm backward behind a direct layer 0 with kf = 4
+CNN_GEOMETRY_CASES = [
+    ("kt5-kf8-l1s1", 3, 45, 80, [(16, 5, 8, 2, 8, 2), (8, 3, 1, 1, 1, 1)], 0, 0),
+    ("kf14-sf7-pt0", 2, 51, 40, [(32, 9, 14, 2, 7, 0), (12, 4, 1, 2, 1, 0)], 0, 0),
+    ("gaps-pt6-l1s3", 2, 64, 26, [(16, 7, 5, 2, 9, 6), (8, 6, 1, 3, 1, 2)], 0, 0),
+    ("kt2-st2", 3, 37, 13, [(16, 2, 13, 2, 13, 0), (8, 2, 1, 2, 1, 0)], 0, 0),
+    ("kf1", 2, 40, 6, [(16, 9, 1, 2, 1, 4), (4, 9, 1, 2, 1, 4)], 0, 0),
+    ("two-tiles", 2, 333, 26, [(48, 7, 12, 2, 12, 3), (8, 5, 1, 2, 1, 2)], 2, 4),
+    ("kt11-st3-kf16", 2, 70, 80, [(8, 11, 16, 3, 16, 5), (8, 5, 1, 3, 1, 1)], 0, 0),
+    ("st1-l1s13", 2, 60, 20, [(4, 4, 5, 1, 3, 0), (4, 13, 1, 13, 1, 0)], 1, 0),
+    ("one-layer", 3, 50, 80, [(16, 9, 13, 2, 13, 4)], 0, 4),
+    ("three-layers", 2, 90, 80, [(16, 9, 13, 2, 13, 4), (12, 9, 1, 2, 1, 4), (8, 3, 1, 1, 1, 1)], 0, 0),
+    ("four-layers", 2, 120, 26, [(16, 9, 13, 2, 13, 4), (8, 9, 1, 2, 1, 4), (8, 4, 1, 3, 1, 0), (4, 5, 1, 2, 1, 2)], 0, 0),
+    ("one-layer-c64", 2, 50, 80, [(64, 9, 13, 2, 13, 4)], 0, 0),
+    ("f10-c64-last", 2, 45, 80, [(16, 5, 8, 2, 8, 2), (64, 3, 1, 1, 1, 1)], 1, 1),
+    ("f20-kf4", 2, 30, 80, [(16, 5, 4, 2, 4, 2), (8, 3, 1, 2, 1, 1)], 0, 0),
+]
+# Max-pooling on a layer 0 that is otherwise eligible for the direct kernel (the shipped geometry with 16 channels): (B, T, D, c0, c1, pool).
+# A pooled layer's BatchNorm sees the POOLED rows; the direct kernel's fused statistics are sums over the un-pooled ones.
+CNN_POOL_DIRECT_CASES = [(2, 30, 26, 16, 8, [[-1, 1], [1, 1]]), (2, 42, 80, 16, 8, [[1, -1], [1, 1]]), (3, 42, 80, 16, 8, [[2, 1], [1, 1]])]
+
+
+def conv0_direct_shape(layers, pool=None):
+    """conv.hip's conv0_direct_shape restated: the layer-0 shapes the direct convolution takes (under the default arithmetic, bf16x3) --
+    the LDS window of an 80-step tile fits 4096 elements (stride 2 only, with the even-stride rule), the f32 weights fit 64 KiB, kt rows
+    of 20 columns fit six 32-wide MFMA steps (kt <= 9), kf <= 14, up to 128 channels in multiples of 16, and the layer does not pool."""
+    C, kt, kf, st, sf, pt = layers[0]
+    win = st * 20 * 79 + 32 * 6 + 40
+    pooled = pool is not None and any(w not in (0, 1) for w in pool[0])
+    return (win <= 512 * 8 and C * kt * kf * 4 <= 64 * 1024 and kt * 20 <= 32 * 6 and kf <= 14 and st % 2 == 0 and C <= 128
+            and C % 16 == 0 and not pooled)
+
+
 def cnn_case_kw(centre):
     return dict(ramp=False, centre_taps=True) if centre else {}
 
@@ -373,20 +446,42 @@ def cnn_layer0_ratio(cfg, P, X, noise):
     return float((y.mean(dim=(0, 2, 3)).abs() / y.std(dim=(0, 2, 3), unbiased=False)).max())
 
 
-def cnn_near_kink(cfg, P, X, noise):
-    """Per layer, the units whose post-BatchNorm pre-activation lies within 2e-5 of the ReLU's kink on the float64 reference (the operator
-    test's near-kink rule): layer 0 as (B, C, T', F), the last layer in the output's (T'', B, C F') layout."""
+def cnn_bn_inputs(cfg, P, X, noise):
+    """Per layer, on the float64 reference: (what the layer's BatchNorm sees -- its convolution's output, max-pooled where the layer
+    pools -- as (B, C, T_i, F_i), the post-BatchNorm pre-activation of the ReLU), batch statistics throughout."""
     import torch
+    TF = torch.nn.functional
+    out = []
     with torch.no_grad():
-        hh, near = torch.tensor(X * (noise if noise is not None else 1.0)).unsqueeze(1), []
+        hh = torch.tensor(X * (noise if noise is not None else 1.0)).unsqueeze(1)
         for i, l in enumerate(cfg["cnn_config"]["cnn_layers"]):
-            hh = torch.nn.functional.conv2d(hh, torch.tensor(P[f"CNN_{i}/W"]), stride=tuple(l["stride"]), padding=tuple(l["pad"]))
-            hh = torch.nn.functional.batch_norm(hh, None, None, torch.tensor(P[f"CNN_{i}_bn/gamma"]), torch.tensor(P[f"CNN_{i}_bn/beta"]),
-                                                training=True, eps=2e-5)
-            near.append(hh.abs() < 2e-5)
-            hh = torch.relu(hh)
-    Bc, Cc, T2, F2 = near[1].shape
-    return near[0].numpy(), near[1].permute(2, 0, 1, 3).reshape(T2, Bc, Cc * F2).numpy()
+            y = TF.conv2d(hh, torch.tensor(P[f"CNN_{i}/W"]), stride=tuple(l["stride"]), padding=tuple(l["pad"]))
+            if "cnn_pool" in cfg["cnn_config"]:
+                kt, kf = cfg["cnn_config"]["cnn_pool"][i]
+                k = (y.shape[2] if kt == -1 else max(kt, 1), y.shape[3] if kf == -1 else max(kf, 1))
+                y = TF.max_pool2d(y, k, stride=k, ceil_mode=True)
+            z = TF.batch_norm(y, None, None, torch.tensor(P[f"CNN_{i}_bn/gamma"]), torch.tensor(P[f"CNN_{i}_bn/beta"]), training=True, eps=2e-5)
+            out.append((y, z))
+            hh = torch.relu(z)
+    return out
+
+
+def cnn_near_kink_layers(cfg, P, X, noise):
+    """Per layer, the units whose post-BatchNorm pre-activation lies within 2e-5 of the ReLU's kink on the float64 reference (the operator
+    test's near-kink rule), each as a bool tensor (B, C, T_i, F_i)."""
+    return [z.abs() < 2e-5 for _, z in cnn_bn_inputs(cfg, P, X, noise)]
+
+
+def seq_layout(a):
+    """(B, C, T'', F') -> the output's (T'', B, C F') layout, feature index c F' + f."""
+    Bc, Cc, T2, F2 = a.shape
+    return a.permute(2, 0, 1, 3).reshape(T2, Bc, Cc * F2)
+
+
+def cnn_near_kink(cfg, P, X, noise):
+    """The near-kink units of layer 0 as (B, C, T', F) and of the last layer in the output's (T'', B, C F') layout."""
+    near = cnn_near_kink_layers(cfg, P, X, noise)
+    return near[0].numpy(), seq_layout(near[-1]).numpy()
 
 
 def attn_upstream(B, T, H):

@@ -102,7 +102,8 @@ def oracle_case(name, cfgf, B, T, D, L, V, drop, teach, x_offset=0.0, opt_cfg=No
     out = dict(cfg=cfg, P=P, X=X, y=y, loss=ref["loss"], gnorm=ref["gnorm"], loss_f32=res[np.float32]["loss"], flags=ref["flags"],
                rec=ref["rec"], noise=ref["noise"], enc=ref["enc"], grads=grads, more=more, later=later,
                after={k: p.data.copy() for k, p in mo.params()},
-               bn={f"CNN_{i}_bn/{s}": np.array(mo.p[f"CNN_{i}_bn/{s}"]) for i in range(2) for s in ("avg_mean", "avg_var")})
+               bn={f"CNN_{i}_bn/{s}": np.array(mo.p[f"CNN_{i}_bn/{s}"]) for i in range(len(cfg["cnn_config"]["cnn_layers"]))
+                   for s in ("avg_mean", "avg_var")})
     _ORACLE[key] = out
     return out
 

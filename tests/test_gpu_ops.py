@@ -174,45 +174,52 @@ def test_cnn_fwd_bwd(lib, B, T, D, c0, c1, with_noise, gemm_split):
     _cnn_case(lib, B, T, D, c0, c1, with_noise)
 
 
-def _cnn_case(lib, B, T, D, c0, c1, with_noise, x_offset=0.0, seed=0, layer1_stats=False, **draw_kw):
+def _cnn_case(lib, B, T, D, c0, c1, with_noise, x_offset=0.0, seed=0, layer1_stats=False, layers=None, pool=None, all_stats=False,
+              kink_free=False, expect_direct=None, **draw_kw):
     """x_offset, seed: tests/range_cases.py cnn_draws (the input with a per-bin offset: BatchNorm channels whose mean lies far from 0);
-    layer1_stats: the running statistics of layer 1 are compared too; draw_kw: cnn_draws' ramp / centre_taps."""
+    layer1_stats: the running statistics of layer 1 are compared too; draw_kw: cnn_draws' ramp / centre_taps.
+    layers: None = the shipped two layers with (c0, c1) channels, else the stack [(C, kt, kf, st, sf, pt), ...] (range_cases.cnn_geometry_cfg);
+    pool: per-layer (time, frequency) max-pooling windows; all_stats: the running statistics of EVERY layer are compared;
+    kink_free: the reference must have no near-kink unit in any layer (asserted: every gradient is then held to 5e-4);
+    expect_direct: not None = the layer-0 path probe -- with the "conv.direct0" knob off the backward call on the forward's workspace is
+    refused, before anything is launched, if and only if the forward took the direct kernel; the answer must equal expect_direct."""
     from ast_amd._lib import CnnLayerGrads, CnnLayerParams
     from oracle.ast_ref_torch import cnn_torch
-    cfg, P, X, noise, rng = range_cases.cnn_draws(B, T, D, c0, c1, with_noise, x_offset=x_offset, seed=seed, **draw_kw)
+    cfg, P, X, noise, rng = range_cases.cnn_draws(B, T, D, c0, c1, with_noise, x_offset=x_offset, seed=seed, layers=layers, pool=pool, **draw_kw)
+    cc = cfg["cnn_config"]["cnn_layers"]
+    n = len(cc)
     Pt = {k: torch.tensor(v, dtype=torch.float64, requires_grad=k.startswith("CNN") and "avg" not in k) for k, v in P.items()}
     # Near-kink units: two valid float32 evaluations of one batch can disagree on the SIGN of a post-BatchNorm pre-activation that lies
     # within rounding of zero, and the unit's whole upstream gradient then enters or leaves its channel's sums -- ONE flipped unit moves that
     # channel's weight gradient by ~1 / sqrt(rows) of itself (round 6: a different, equally valid, summation order of the layer-1 forward
     # product -- pre-activations 4e-6 apart -- flipped units of the (16, 400, 13, 128, 512) case: CNN_1/W 3.7e-2, CNN_0/W 3.5e-3 of the
     # largest entry).  With ~10^6 units the float64 reference always has some within 1e-5 of the kink, whatever the draw.  So: the
-    # upstream gradient is ZERO at the last layer's near-kink units (their sign then cannot matter), and the tensors of a layer BELOW one with
-    # near-kink units are held to what a flipped unit can move (5e-3).  The exact comparison with named units dropped on both sides is
-    # tests/test_golden.py's.
-    with torch.no_grad():
-        hh, near = (torch.tensor(X * (noise if with_noise else 1.0))).unsqueeze(1), []
-        for i, l in enumerate(cfg["cnn_config"]["cnn_layers"]):
-            hh = torch.nn.functional.conv2d(hh, Pt[f"CNN_{i}/W"], stride=tuple(l["stride"]), padding=tuple(l["pad"]))
-            hh = torch.nn.functional.batch_norm(hh, None, None, Pt[f"CNN_{i}_bn/gamma"], Pt[f"CNN_{i}_bn/beta"], training=True, eps=2e-5)
-            near.append(hh.abs() < 2e-5)                      # (B, C, T_i, F_i)
-            hh = torch.relu(hh)
-    grad_rtol = {"CNN_0": 5e-3 if bool(near[0].any()) else 5e-4, "CNN_1": 5e-4}
+    # upstream gradient is ZERO at the last layer's near-kink units (their sign then cannot matter), and the tensors of a layer at or BELOW
+    # one (other than the last) with near-kink units are held to what a flipped unit can move (5e-3).  The exact comparison with named units
+    # dropped on both sides is tests/test_golden.py's.
+    bn_in = range_cases.cnn_bn_inputs(cfg, P, X, noise)       # per layer: (what its BatchNorm sees, the ReLU's pre-activation), float64
+    near = [z.abs() < 2e-5 for _, z in bn_in]                 # (B, C, T_i, F_i)
+    if kink_free:
+        assert [int(m.sum()) for m in near] == [0] * n, "the case's seed must leave no unit within 2e-5 of the ReLU's kink"
+    names = [f"CNN_{i}" for i in range(n)]
+    grad_rtol = {names[i]: 5e-3 if any(bool(near[j].any()) for j in range(i, n - 1)) else 5e-4 for i in range(n)}
     out_ref = cnn_torch(cfg, Pt, torch.tensor(X), torch.tensor(noise) if with_noise else None)
     gout = rng.standard_normal(out_ref.shape)
-    gout[near[1].permute(2, 0, 1, 3).reshape(out_ref.shape).numpy()] = 0.0          # (T'', B, C F') with feature index c F' + f
+    gout[range_cases.seq_layout(near[-1]).numpy()] = 0.0          # (T'', B, C F') with feature index c F' + f
     out_ref.backward(torch.tensor(gout))
     cd = _cnn_desc(cfg, B, T, D)
+    for i, (wt, wf) in enumerate(pool or []):
+        cd.pool_t[i], cd.pool_f[i] = wt, wf
     t2, f2, feat = C.c_int(), C.c_int(), C.c_int()
     ok(lib, lib.astk_conv_bn_relu_out_dims(C.byref(cd), C.byref(t2), C.byref(f2), C.byref(feat)))
     assert (t2.value, B, feat.value) == tuple(out_ref.shape)
-    names = ["CNN_0", "CNN_1"]
-    prm = {n + s: dev(P[n + s]) for n in names for s in ("/W", "_bn/gamma", "_bn/beta", "_bn/avg_mean", "_bn/avg_var")}
+    prm = {n_ + s: dev(P[n_ + s]) for n_ in names for s in ("/W", "_bn/gamma", "_bn/beta", "_bn/avg_mean", "_bn/avg_var")}
     grd = {k: torch.zeros_like(v) for k, v in prm.items()}
-    cp, cg = (CnnLayerParams * 2)(), (CnnLayerGrads * 2)()
-    for i, n in enumerate(names):
-        cp[i].W, cp[i].gamma, cp[i].beta = prm[n + "/W"].data_ptr(), prm[n + "_bn/gamma"].data_ptr(), prm[n + "_bn/beta"].data_ptr()
-        cp[i].avg_mean, cp[i].avg_var = prm[n + "_bn/avg_mean"].data_ptr(), prm[n + "_bn/avg_var"].data_ptr()
-        cg[i].dW, cg[i].dgamma, cg[i].dbeta = grd[n + "/W"].data_ptr(), grd[n + "_bn/gamma"].data_ptr(), grd[n + "_bn/beta"].data_ptr()
+    cp, cg = (CnnLayerParams * n)(), (CnnLayerGrads * n)()
+    for i, n_ in enumerate(names):
+        cp[i].W, cp[i].gamma, cp[i].beta = prm[n_ + "/W"].data_ptr(), prm[n_ + "_bn/gamma"].data_ptr(), prm[n_ + "_bn/beta"].data_ptr()
+        cp[i].avg_mean, cp[i].avg_var = prm[n_ + "_bn/avg_mean"].data_ptr(), prm[n_ + "_bn/avg_var"].data_ptr()
+        cg[i].dW, cg[i].dgamma, cg[i].dbeta = grd[n_ + "/W"].data_ptr(), grd[n_ + "_bn/gamma"].data_ptr(), grd[n_ + "_bn/beta"].data_ptr()
     nbytes = lib.astk_conv_bn_relu_workspace_bytes(C.byref(cd))
     ws = GuardedWS(nbytes)
     out = torch.empty(t2.value, B, feat.value, device="cuda")
@@ -220,26 +227,37 @@ def _cnn_case(lib, B, T, D, c0, c1, with_noise, x_offset=0.0, seed=0, layer1_sta
     ok(lib, lib.astk_conv_bn_relu_fwd(C.byref(cd), cp, vp(xd), vp(nd), vp(out), vp(ws), nbytes, 1, stream()))
     ws.check("cnn fwd")
     close(out, out_ref, msg="cnn out")
-    # running statistics (A4): mean 0.1*mu, var 0.9 + 0.1*var*m/(m-1)
-    h = torch.tensor(X * (noise if with_noise else 1.0)).unsqueeze(1)
-    y0 = torch.nn.functional.conv2d(h, Pt["CNN_0/W"].detach(), stride=(2, 13), padding=(4, 0))
-    m = y0.numel() // y0.shape[1]
-    close(prm["CNN_0_bn/avg_mean"], 0.1 * y0.mean(dim=(0, 2, 3)), msg="avg_mean")
-    close(prm["CNN_0_bn/avg_var"], 0.9 + 0.1 * y0.var(dim=(0, 2, 3), unbiased=False) * m / (m - 1), msg="avg_var")
-    if layer1_stats:
-        l1 = cfg["cnn_config"]["cnn_layers"][1]
-        h1 = torch.relu(torch.nn.functional.batch_norm(y0, None, None, Pt["CNN_0_bn/gamma"].detach(), Pt["CNN_0_bn/beta"].detach(), training=True, eps=2e-5))
-        y1 = torch.nn.functional.conv2d(h1, Pt["CNN_1/W"].detach(), stride=tuple(l1["stride"]), padding=tuple(l1["pad"]))
-        m1 = y1.numel() // y1.shape[1]
-        close(prm["CNN_1_bn/avg_mean"], 0.1 * y1.mean(dim=(0, 2, 3)), msg="avg_mean, layer 1")
-        close(prm["CNN_1_bn/avg_var"], 0.9 + 0.1 * y1.var(dim=(0, 2, 3), unbiased=False) * m1 / (m1 - 1), msg="avg_var, layer 1")
+    # running statistics (A4): mean 0.1*mu, var 0.9 + 0.1*var*m/(m-1), of what each layer's BatchNorm sees (its own stride / pad / pooling)
+    for i in range(n if all_stats else (2 if layer1_stats else 1)):
+        y = bn_in[i][0]
+        m = y.numel() // y.shape[1]
+        tag = "" if i == 0 else f", layer {i}"
+        close(prm[f"CNN_{i}_bn/avg_mean"], 0.1 * y.mean(dim=(0, 2, 3)), msg="avg_mean" + tag)
+        close(prm[f"CNN_{i}_bn/avg_var"], 0.9 + 0.1 * y.var(dim=(0, 2, 3), unbiased=False) * m / (m - 1), msg="avg_var" + tag)
     g = dev(gout)
-    ok(lib, lib.astk_conv_bn_relu_bwd(C.byref(cd), cp, cg, vp(g), vp(ws), nbytes, stream()))
+    probed = False
+    if expect_direct is not None:
+        prev = C.c_double()
+        assert lib.astk_get_tuning(b"conv.direct0", C.byref(prev)) == 0 and prev.value == 1
+        assert lib.astk_set_tuning(b"conv.direct0", 0.0) == 0
+        try:
+            rc = lib.astk_conv_bn_relu_bwd(C.byref(cd), cp, cg, vp(g), vp(ws), nbytes, stream())
+        finally:
+            assert lib.astk_set_tuning(b"conv.direct0", prev.value) == 0
+        if rc != 0:        # refused in front of every launch: the forward took the direct kernel, this call would have taken im2col
+            msg = lib.astk_last_error().decode()
+            assert "took the direct-convolution layer-0 path" in msg, msg
+            assert all(float(v.abs().max()) == 0.0 for v in grd.values()), "a refused backward call wrote gradients"
+        else:              # im2col on both sides: the knob changed nothing, and this WAS the backward call
+            probed = True
+        assert (rc != 0) == expect_direct, f"layer 0 ran on the {'direct' if rc != 0 else 'im2col'} path"
+    if not probed:
+        ok(lib, lib.astk_conv_bn_relu_bwd(C.byref(cd), cp, cg, vp(g), vp(ws), nbytes, stream()))
     ws.check("cnn bwd")
     assert torch.equal(xd, dev(X)), "input clobbered"
-    for n in names:
+    for n_ in names:
         for s in ("/W", "_bn/gamma", "_bn/beta"):
-            close(grd[n + s], Pt[n + s].grad, rtol=grad_rtol[n], msg="grad " + n + s)
+            close(grd[n_ + s], Pt[n_ + s].grad, rtol=grad_rtol[n_], msg="grad " + n_ + s)
     # A second backward call on the SAME forward pass, then a fresh forward + backward: the same gradients every time.  (Round 5: the
     # forward's last kernel zeroes the backward's accumulators -- statistics, maximum slots, weight-gradient scratch -- on its way out and
     # the library remembers that per workspace; the backward call that finds the mark taken has to fill them itself.)
@@ -252,18 +270,21 @@ def _cnn_case(lib, B, T, D, c0, c1, with_noise, x_offset=0.0, seed=0, layer1_sta
         g = dev(gout)
         ok(lib, lib.astk_conv_bn_relu_bwd(C.byref(cd), cp, cg, vp(g), vp(ws), nbytes, stream()))
         ws.check("cnn bwd again")
-        for k in ("CNN_0/W", "CNN_1/W", "CNN_0_bn/gamma", "CNN_1_bn/gamma", "CNN_0_bn/beta", "CNN_1_bn/beta"):
+        for k in [n_ + s for s in ("/W", "_bn/gamma", "_bn/beta") for n_ in names]:
             close(grd[k], first[k].double().cpu().numpy(), rtol=2e-5, msg=f"backward call {rep + 2}: {k}")
     # eval mode uses the running statistics
     ok(lib, lib.astk_conv_bn_relu_fwd(C.byref(cd), cp, vp(xd), None, vp(out), vp(ws), nbytes, 0, stream()))
     hh = torch.tensor(X).unsqueeze(1)
-    for i, l in enumerate(cfg["cnn_config"]["cnn_layers"]):
+    for i, l in enumerate(cc):
         hh = torch.nn.functional.conv2d(hh, Pt[f"CNN_{i}/W"].detach(), stride=tuple(l["stride"]), padding=tuple(l["pad"]))
+        if pool:
+            wt, wf = pool[i]
+            k = (hh.shape[2] if wt == -1 else max(wt, 1), hh.shape[3] if wf == -1 else max(wf, 1))
+            hh = torch.nn.functional.max_pool2d(hh, k, stride=k, ceil_mode=True)
         hh = torch.nn.functional.batch_norm(hh, prm[f"CNN_{i}_bn/avg_mean"].cpu().double(), prm[f"CNN_{i}_bn/avg_var"].cpu().double(),
                                             Pt[f"CNN_{i}_bn/gamma"].detach(), Pt[f"CNN_{i}_bn/beta"].detach(), training=False, eps=2e-5)
         hh = torch.relu(hh)
-    Bc, Cc, T2, F2 = hh.shape
-    close(out, hh.permute(2, 0, 1, 3).reshape(T2, B, Cc * F2), msg="eval-mode out")
+    close(out, range_cases.seq_layout(hh), msg="eval-mode out")
 
 
 @pytest.mark.parametrize("B,T,D,c0,c1,pool", [(3, 42, 80, 4, 8, [[2, 1], [1, 1]]), (2, 50, 80, 8, 12, [[3, 2], [2, -1]]),

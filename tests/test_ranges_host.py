@@ -201,6 +201,36 @@ def test_cnn_offset_rungs_are_feasible(shape, with_noise, x_offset, seed, centre
     assert cnn_within(res, near0), res
 
 
+def cnn_geometry_feasibility(B, T, D, layers, with_noise, seed):
+    """A geometry case of RC.CNN_GEOMETRY_CASES on the CPU: oracle.ast_ref_torch.cnn_torch in float32 against its float64 self -> (near-kink
+    units per layer on the float64 reference, output error, worst gradient error), errors as fractions of the reference tensor's maximum."""
+    from oracle.ast_ref_torch import cnn_torch
+    cfg, P, X, noise, rng = RC.cnn_draws(B, T, D, None, None, with_noise, seed=seed, layers=layers)
+    near = [int(m.sum()) for m in RC.cnn_near_kink_layers(cfg, P, X, noise)]
+    res, gout = {}, None
+    for dt in (torch.float64, torch.float32):
+        Pt = {k: torch.tensor(v, dtype=dt, requires_grad=True) for k, v in P.items() if k.startswith("CNN") and "avg" not in k}
+        out = cnn_torch(cfg, Pt, torch.tensor(X, dtype=dt), None if noise is None else torch.tensor(noise, dtype=dt))
+        if gout is None:
+            gout = rng.standard_normal(tuple(out.shape))
+        out.backward(torch.tensor(gout, dtype=dt))
+        res[dt] = (out.detach().numpy(), {k: p.grad.numpy() for k, p in Pt.items()})
+    o64, g64 = res[torch.float64]
+    o32, g32 = res[torch.float32]
+    return near, frac(o32, o64), max(frac(g32[k], g64[k]) for k in g64)
+
+
+@pytest.mark.parametrize("with_noise", [False, True])
+@pytest.mark.parametrize("cid,B,T,D,layers,seed,seed_noisy", RC.CNN_GEOMETRY_CASES, ids=[c[0] for c in RC.CNN_GEOMETRY_CASES])
+def test_cnn_geometry_cases_are_kink_free_and_feasible(cid, B, T, D, layers, seed, seed_noisy, with_noise):
+    """The committed seeds leave no unit of any layer within 2e-5 of the ReLU's kink on the float64 reference (so the GPU test holds every
+    gradient to 5e-4), and the plain float32 restatement meets a quarter of the GPU test's bounds on every case."""
+    near, out, grad = cnn_geometry_feasibility(B, T, D, layers, with_noise, seed_noisy if with_noise else seed)
+    print(f"{cid} noise {with_noise}: near {near} out {out:.1e} grad {grad:.1e}")
+    assert near == [0] * len(layers), near
+    assert out <= FWD / 4 and grad <= GRAD / 4, (out, grad)
+
+
 # ------------------------------------------------------------------ attention and softmax-CE value cases (operator level)
 def attn_f32(enc, q, dt=torch.float32, subtract_max=True):
     e, qq = torch.tensor(enc, dtype=dt), torch.tensor(q, dtype=dt)
