@@ -119,6 +119,32 @@ class BeamState(_Sized, C.Structure):
                 ("n_frozen", C.c_void_p), ("hist", C.c_void_p), ("hist_alpha", C.c_void_p)]
 
 
+# the row-panel launchers' mirror structs (include/astk.h, the ASTK_TEST_HOOKS section; libastk_test.so only)
+class DebugRowPair(C.Structure):
+    _fields_ = [("A", C.c_void_p), ("lda", C.c_long), ("W", C.c_void_p), ("ldw", C.c_long), ("K", C.c_int)]
+
+
+class DebugRowGemmArgs(_Sized, C.Structure):
+    _fields_ = [("struct_size", C.c_size_t), ("p", DebugRowPair * 2), ("npairs", C.c_int), ("M", C.c_int), ("N", C.c_int),
+                ("bias", C.c_void_p), ("addend", C.c_void_p), ("ld_add", C.c_long), ("out", C.c_void_p), ("ld_out", C.c_long),
+                ("out2", C.c_void_p), ("ld_out2", C.c_long), ("act", C.c_int), ("carry", C.c_void_p), ("ld_carry", C.c_long),
+                ("carry_aux", C.c_void_p), ("ld_carry_aux", C.c_long), ("carry_col0", C.c_int)]
+
+
+class DebugCellFwdArgs(_Sized, C.Structure):
+    _fields_ = [("struct_size", C.c_size_t), ("p", DebugRowPair * 2), ("npairs", C.c_int), ("B", C.c_int), ("h", C.c_int),
+                ("zx", C.c_void_p), ("ld_zx", C.c_long), ("bias", C.c_void_p), ("c_prev", C.c_void_p), ("gates", C.c_void_p),
+                ("ld_g", C.c_long), ("c_out", C.c_void_p), ("h_out", C.c_void_p), ("mask", C.c_void_p), ("hd_out", C.c_void_p),
+                ("ld_hd", C.c_long), ("hd_out2", C.c_void_p), ("ld_hd2", C.c_long)]
+
+
+class DebugCellBwdArgs(_Sized, C.Structure):
+    _fields_ = [("struct_size", C.c_size_t), ("p", DebugRowPair * 2), ("npairs", C.c_int), ("B", C.c_int), ("h", C.c_int),
+                ("dh_add", C.c_void_p), ("dy", C.c_void_p), ("ld_dy", C.c_long), ("dy2", C.c_void_p), ("ld_dy2", C.c_long),
+                ("mask", C.c_void_p), ("dc_next", C.c_void_p), ("c_prev", C.c_void_p), ("c_cur", C.c_void_p), ("gates_dz", C.c_void_p),
+                ("ld_g", C.c_long), ("dc_prev", C.c_void_p)]
+
+
 # every symbol include/astk.h declares: name -> (restype, argtypes)
 _VP, _I, _L, _SZ, _F, _U64 = C.c_void_p, C.c_int, C.c_long, C.c_size_t, C.c_float, C.c_uint64
 SIGNATURES = {
@@ -240,6 +266,9 @@ TEST_HOOK_SIGNATURES = {
     "astk_conv_debug_preact": (C.c_int, [C.POINTER(CnnDesc), _VP, _SZ, _I, _VP, _VP]),
     "astk_conv_debug_kill_units": (C.c_int, [_VP, _I]),
     "astk_debug_gemm_group": (C.c_int, [_I, _I, c_int_p, c_int_p, c_int_p, C.POINTER(C.c_void_p), C.POINTER(C.c_void_p), C.POINTER(C.c_void_p), _I, _I, _VP]),
+    "astk_debug_rowgemm": (C.c_int, [C.POINTER(DebugRowGemmArgs), c_int_p, _VP]),
+    "astk_debug_lstm_cell_fwd": (C.c_int, [C.POINTER(DebugCellFwdArgs), _I, c_int_p, _VP]),
+    "astk_debug_lstm_cell_bwd": (C.c_int, [C.POINTER(DebugCellBwdArgs), _I, c_int_p, _VP]),
 }
 
 _lib = None

@@ -464,7 +464,7 @@ struct RowPair {
   long ldw;
   int K;
 };
-enum RowAct { ACT_NONE = 0, ACT_TANH = 1, ACT_DTANH = 2 };
+enum RowAct { ACT_NONE = 0, ACT_TANH = 1 };
 struct RowGemmArgs {
   RowPair p[2];
   int npairs;
@@ -472,8 +472,6 @@ struct RowGemmArgs {
   const float* bias;    // [N] or null
   const float* addend;  // [M][N] (ld_add) or null
   long ld_add;
-  const float* aux;     // ACT_DTANH: y = tanh output, out = (acc+addend)*(1-y*y)
-  long ld_aux;
   float* out;
   long ld_out;
   float* out2;          // optional second copy of the result (e.g. into the input-feeding concat buffer)

@@ -143,10 +143,6 @@ __global__ __launch_bounds__(64 * NW) void rowgemm_kernel(RowGemmArgs a) {
     if (a.bias) v += a.bias[n];
     if (a.addend) v += a.addend[(long)row * a.ld_add + n];
     if (a.act == ACT_TANH) v = tanhf(v);
-    else if (a.act == ACT_DTANH) {
-      const float y = a.aux[(long)row * a.ld_aux + n];
-      v *= (1.f - y * y);
-    }
     a.out[(long)row * a.ld_out + n] = v;
     if (a.out2) a.out2[(long)row * a.ld_out2 + n] = v;
     if (a.carry && n >= a.carry_col0) {
@@ -268,12 +264,45 @@ __global__ __launch_bounds__(64 * NW) void lstm_cell_bwd_kernel(CellBwdBatch bat
   }
 }
 
-// eight waves share K once a four-wave workgroup would need more than two exposed round trips per wave (astk_set_tuning("row.longk") overrides the
-// threshold, 0 = never: for A/B runs)
-bool long_k(int k) {
-  const int thr = (int)tune(TUNE_ROW_LONGK);
-  return thr > 0 && k >= thr;
+// The ONE decision of the three launchers: which <MT, NW> instantiation runs and over which grid.  Pure: everything it depends on is an
+// argument (col_tiles: workgroups along the output columns; rows: M or B; cells: grid.z; k: the K the kernel is keyed on -- the sum over
+// the pairs for rowgemm and the forward cell, whose pairs share one accumulator chain, the maximum for the backward cell, whose pairs
+// are separate products; cu: device_cu_count(); longk: the row.longk knob).
+//   two row tiles per workgroup halve the weight traffic but also the number of workgroups: only above 16 rows and when the chip stays full;
+//   eight waves share K once a four-wave workgroup would need more than two exposed round trips per wave (astk_set_tuning("row.longk")
+//   overrides the threshold, 0 = never: for A/B runs).
+struct RowRoute {
+  bool two_tiles, eight_waves;
+  dim3 grid;
+};
+
+RowRoute row_route(int col_tiles, int rows, int cells, int k, int cu, int longk) {
+  RowRoute r;
+  r.two_tiles = rows > 16 && (long)col_tiles * cdiv(rows, 32) * cells >= cu;
+  r.eight_waves = longk > 0 && k >= longk;
+  r.grid = dim3(col_tiles, cdiv(rows, r.two_tiles ? 32 : 16), cells);
+  return r;
 }
+
+#ifdef ASTK_TEST_HOOKS
+thread_local RowRoute g_route_taken;      // what the last launcher of this thread decided (read back by the astk_debug_* entry points)
+#define ROW_ROUTE_TAKEN(r) g_route_taken = (r)
+#else
+#define ROW_ROUTE_TAKEN(r) ((void)0)
+#endif
+
+// launches KERNEL<MT, NW> of the route over its grid
+#define ROW_LAUNCH(KERNEL, rt, s, arg)                                                               \
+  do {                                                                                               \
+    ROW_ROUTE_TAKEN(rt);                                                                             \
+    if ((rt).eight_waves) {                                                                          \
+      if ((rt).two_tiles) hipLaunchKernelGGL((KERNEL<2, 8>), (rt).grid, dim3(512), 0, s, arg);       \
+      else hipLaunchKernelGGL((KERNEL<1, 8>), (rt).grid, dim3(512), 0, s, arg);                      \
+    } else {                                                                                         \
+      if ((rt).two_tiles) hipLaunchKernelGGL((KERNEL<2, 4>), (rt).grid, dim3(256), 0, s, arg);       \
+      else hipLaunchKernelGGL((KERNEL<1, 4>), (rt).grid, dim3(256), 0, s, arg);                      \
+    }                                                                                                \
+  } while (0)
 
 int check_pair(const RowPair& p, const char* who) {
   if (p.K <= 0) return 0;
@@ -287,19 +316,12 @@ int check_pair(const RowPair& p, const char* who) {
 
 int rowgemm_launch(const RowGemmArgs& a, hipStream_t s) {
   ASTK_CHECK(a.M > 0 && a.N > 0 && a.out && a.npairs >= 1 && a.npairs <= 2, "rowgemm: bad arguments");
+  ASTK_CHECK(!a.carry || (a.carry_aux && a.carry_col0 >= 0), "rowgemm: a carry needs carry_aux and carry_col0 >= 0");
   for (int p = 0; p < a.npairs; ++p) ASTK_TRY(check_pair(a.p[p], "rowgemm"));
-  // two row tiles per workgroup halve the weight traffic but also the number of workgroups: only when the chip stays full
-  const bool two = a.M > 16 && (long)cdiv(a.N, 16) * cdiv(a.M, 32) >= device_cu_count();
   int ktot = 0;
   for (int p = 0; p < a.npairs; ++p) ktot += a.p[p].K;
-  const dim3 grid(cdiv(a.N, 16), cdiv(a.M, two ? 32 : 16));
-  if (long_k(ktot)) {
-    if (two) hipLaunchKernelGGL((rowgemm_kernel<2, 8>), grid, dim3(512), 0, s, a);
-    else hipLaunchKernelGGL((rowgemm_kernel<1, 8>), grid, dim3(512), 0, s, a);
-  } else {
-    if (two) hipLaunchKernelGGL((rowgemm_kernel<2, 4>), grid, dim3(256), 0, s, a);
-    else hipLaunchKernelGGL((rowgemm_kernel<1, 4>), grid, dim3(256), 0, s, a);
-  }
+  const RowRoute rt = row_route(cdiv(a.N, 16), a.M, 1, ktot, device_cu_count(), (int)tune(TUNE_ROW_LONGK));
+  ROW_LAUNCH(rowgemm_kernel, rt, s, a);
   ASTK_LAUNCH_CHECK();
   return 0;
 }
@@ -309,6 +331,7 @@ int lstm_cell_fwd_launch(const LstmCellFwdArgs* cells, int ncells, hipStream_t s
   CellFwdBatch batch;
   for (int i = 0; i < ncells; ++i) {
     const LstmCellFwdArgs& c = cells[i];
+    ASTK_CHECK(c.B > 0 && c.h > 0 && c.npairs >= 0 && c.npairs <= 2, "lstm_cell_fwd: bad arguments");
     ASTK_CHECK(c.B == cells[0].B && c.h == cells[0].h, "lstm_cell_fwd: cells of one launch must share B and h");
     ASTK_CHECK(c.gates && c.c_out && c.h_out && (c.ld_g % 4) == 0 && aligned16(c.gates), "lstm_cell_fwd: bad outputs");
     ASTK_CHECK(!c.zx || ((c.ld_zx % 4) == 0 && aligned16(c.zx)), "lstm_cell_fwd: zx alignment");
@@ -317,17 +340,10 @@ int lstm_cell_fwd_launch(const LstmCellFwdArgs* cells, int ncells, hipStream_t s
     batch.c[i] = c;
   }
   ProfScope prof(PROF_CELL, s);
-  const bool two = cells[0].B > 16 && (long)cdiv(cells[0].h, 4) * cdiv(cells[0].B, 32) * ncells >= device_cu_count();
-  const dim3 grid(cdiv(cells[0].h, 4), cdiv(cells[0].B, two ? 32 : 16), ncells);
   int ktot = 0;
   for (int p = 0; p < cells[0].npairs; ++p) ktot += cells[0].p[p].K;
-  if (long_k(ktot)) {
-    if (two) hipLaunchKernelGGL((lstm_cell_fwd_kernel<2, 8>), grid, dim3(512), 0, s, batch);
-    else hipLaunchKernelGGL((lstm_cell_fwd_kernel<1, 8>), grid, dim3(512), 0, s, batch);
-  } else {
-    if (two) hipLaunchKernelGGL((lstm_cell_fwd_kernel<2, 4>), grid, dim3(256), 0, s, batch);
-    else hipLaunchKernelGGL((lstm_cell_fwd_kernel<1, 4>), grid, dim3(256), 0, s, batch);
-  }
+  const RowRoute rt = row_route(cdiv(cells[0].h, 4), cells[0].B, ncells, ktot, device_cu_count(), (int)tune(TUNE_ROW_LONGK));
+  ROW_LAUNCH(lstm_cell_fwd_kernel, rt, s, batch);
   ASTK_LAUNCH_CHECK();
   return 0;
 }
@@ -337,25 +353,100 @@ int lstm_cell_bwd_launch(const LstmCellBwdArgs* cells, int ncells, hipStream_t s
   CellBwdBatch batch;
   for (int i = 0; i < ncells; ++i) {
     const LstmCellBwdArgs& c = cells[i];
+    ASTK_CHECK(c.B > 0 && c.h > 0 && c.npairs >= 1 && c.npairs <= 2, "lstm_cell_bwd: bad arguments");
     ASTK_CHECK(c.B == cells[0].B && c.h == cells[0].h, "lstm_cell_bwd: cells of one launch must share B and h");
     ASTK_CHECK(c.gates_dz && c.c_cur && c.dc_prev && (c.ld_g % 4) == 0 && aligned16(c.gates_dz), "lstm_cell_bwd: bad buffers");
     for (int p = 0; p < c.npairs; ++p) ASTK_TRY(check_pair(c.p[p], "lstm_cell_bwd"));
     batch.c[i] = c;
   }
   ProfScope prof(PROF_CELL, s);
-  const bool two = cells[0].B > 16 && (long)cdiv(cells[0].h, 16) * cdiv(cells[0].B, 32) * ncells >= device_cu_count();
-  const dim3 grid(cdiv(cells[0].h, 16), cdiv(cells[0].B, two ? 32 : 16), ncells);
   int kmax = 0;
   for (int p = 0; p < cells[0].npairs; ++p) kmax = cells[0].p[p].K > kmax ? cells[0].p[p].K : kmax;
-  if (long_k(kmax)) {
-    if (two) hipLaunchKernelGGL((lstm_cell_bwd_kernel<2, 8>), grid, dim3(512), 0, s, batch);
-    else hipLaunchKernelGGL((lstm_cell_bwd_kernel<1, 8>), grid, dim3(512), 0, s, batch);
-  } else {
-    if (two) hipLaunchKernelGGL((lstm_cell_bwd_kernel<2, 4>), grid, dim3(256), 0, s, batch);
-    else hipLaunchKernelGGL((lstm_cell_bwd_kernel<1, 4>), grid, dim3(256), 0, s, batch);
-  }
+  const RowRoute rt = row_route(cdiv(cells[0].h, 16), cells[0].B, ncells, kmax, device_cu_count(), (int)tune(TUNE_ROW_LONGK));
+  ROW_LAUNCH(lstm_cell_bwd_kernel, rt, s, batch);
   ASTK_LAUNCH_CHECK();
   return 0;
 }
 
 }  // namespace astk
+
+#ifdef ASTK_TEST_HOOKS
+// libastk_test.so only: the three launchers behind public mirror structs (include/astk.h), for shapes and epilogues no op of the step
+// produces.  Each copies its descriptors into the internal argument structs, calls the REAL launcher on `stream` and reports the route that
+// launcher took: route[0] bit 0 = two row tiles per workgroup, bit 1 = eight waves; route[1..3] = the grid's x, y, z.  A refused call
+// leaves route at zeros.
+namespace {
+
+astk::RowPair row_pair(const astk_debug_row_pair& q) {
+  astk::RowPair p;
+  p.A = q.A; p.lda = q.lda; p.W = q.W; p.ldw = q.ldw; p.K = q.K;
+  return p;
+}
+
+void report_route(int* route) {
+  const astk::RowRoute& r = astk::g_route_taken;
+  route[0] = (r.two_tiles ? 1 : 0) | (r.eight_waves ? 2 : 0);
+  route[1] = (int)r.grid.x; route[2] = (int)r.grid.y; route[3] = (int)r.grid.z;
+}
+
+}  // namespace
+
+extern "C" int astk_debug_rowgemm(const astk_debug_rowgemm_args* d, int* route, void* stream) {
+  using namespace astk;
+  ASTK_CHECK_DESC(d, astk_debug_rowgemm_args);
+  ASTK_CHECK(route, "debug_rowgemm: null route");
+  route[0] = route[1] = route[2] = route[3] = 0;
+  RowGemmArgs a;
+  memset(&a, 0, sizeof(a));
+  a.p[0] = row_pair(d->p[0]); a.p[1] = row_pair(d->p[1]);
+  a.npairs = d->npairs; a.M = d->M; a.N = d->N;
+  a.bias = d->bias; a.addend = d->addend; a.ld_add = d->ld_add;
+  a.out = d->out; a.ld_out = d->ld_out; a.out2 = d->out2; a.ld_out2 = d->ld_out2; a.act = d->act;
+  a.carry = d->carry; a.ld_carry = d->ld_carry; a.carry_aux = d->carry_aux; a.ld_carry_aux = d->ld_carry_aux; a.carry_col0 = d->carry_col0;
+  ASTK_TRY(rowgemm_launch(a, (hipStream_t)stream));
+  report_route(route);
+  return 0;
+}
+
+extern "C" int astk_debug_lstm_cell_fwd(const astk_debug_cell_fwd_args* cells, int ncells, int* route, void* stream) {
+  using namespace astk;
+  ASTK_CHECK(cells && route, "debug_lstm_cell_fwd: null argument");
+  route[0] = route[1] = route[2] = route[3] = 0;
+  ASTK_CHECK(ncells >= 1 && ncells <= 8, "debug_lstm_cell_fwd: 1..8 cells per launch");
+  LstmCellFwdArgs c[8];
+  memset(c, 0, sizeof(c));
+  for (int i = 0; i < ncells; ++i) {
+    const astk_debug_cell_fwd_args* d = cells + i;
+    ASTK_CHECK_DESC(d, astk_debug_cell_fwd_args);
+    c[i].p[0] = row_pair(d->p[0]); c[i].p[1] = row_pair(d->p[1]);
+    c[i].npairs = d->npairs; c[i].B = d->B; c[i].h = d->h;
+    c[i].zx = d->zx; c[i].ld_zx = d->ld_zx; c[i].bias = d->bias; c[i].c_prev = d->c_prev;
+    c[i].gates = d->gates; c[i].ld_g = d->ld_g; c[i].c_out = d->c_out; c[i].h_out = d->h_out; c[i].mask = d->mask;
+    c[i].hd_out = d->hd_out; c[i].ld_hd = d->ld_hd; c[i].hd_out2 = d->hd_out2; c[i].ld_hd2 = d->ld_hd2;
+  }
+  ASTK_TRY(lstm_cell_fwd_launch(c, ncells, (hipStream_t)stream));
+  report_route(route);
+  return 0;
+}
+
+extern "C" int astk_debug_lstm_cell_bwd(const astk_debug_cell_bwd_args* cells, int ncells, int* route, void* stream) {
+  using namespace astk;
+  ASTK_CHECK(cells && route, "debug_lstm_cell_bwd: null argument");
+  route[0] = route[1] = route[2] = route[3] = 0;
+  ASTK_CHECK(ncells >= 1 && ncells <= 8, "debug_lstm_cell_bwd: 1..8 cells per launch");
+  LstmCellBwdArgs c[8];
+  memset(c, 0, sizeof(c));
+  for (int i = 0; i < ncells; ++i) {
+    const astk_debug_cell_bwd_args* d = cells + i;
+    ASTK_CHECK_DESC(d, astk_debug_cell_bwd_args);
+    c[i].p[0] = row_pair(d->p[0]); c[i].p[1] = row_pair(d->p[1]);
+    c[i].npairs = d->npairs; c[i].B = d->B; c[i].h = d->h;
+    c[i].dh_add = d->dh_add; c[i].dy = d->dy; c[i].ld_dy = d->ld_dy; c[i].dy2 = d->dy2; c[i].ld_dy2 = d->ld_dy2;
+    c[i].mask = d->mask; c[i].dc_next = d->dc_next; c[i].c_prev = d->c_prev; c[i].c_cur = d->c_cur;
+    c[i].gates_dz = d->gates_dz; c[i].ld_g = d->ld_g; c[i].dc_prev = d->dc_prev;
+  }
+  ASTK_TRY(lstm_cell_bwd_launch(c, ncells, (hipStream_t)stream));
+  report_route(route);
+  return 0;
+}
+#endif

@@ -772,6 +772,81 @@ int astk_decoder_path(const astk_decoder_desc* d);
 int astk_persist_status(unsigned* mask_out, int reset);
 int astk_device_cu_count(void);
 
+#ifdef ASTK_TEST_HOOKS
+/* Test hooks (libastk_test.so only): the row-panel launchers of rowgemm.hip -- the per-launch decoder loop, the eval-mode decoder step, the
+ * beam search steps, the LayerNorm / projection variants, the per-step encoder loop -- which no other entry point exposes by themselves.
+ * The structs mirror the library's internal argument structs field by field (the meaning of each: RowGemmArgs, LstmCellFwdArgs,
+ * LstmCellBwdArgs in csrc/common.h); ZERO-INITIALISE, set struct_size, then the fields used.  Every call runs the real launcher on `stream`
+ * and writes the route that launcher took to route[4]: route[0] bit 0 = two 16-row tiles per workgroup, bit 1 = eight waves per
+ * workgroup; route[1..3] = the grid's x, y, z.  Returns 0, or nonzero with a message (nothing launched, route zeroed). */
+typedef struct {
+  const float* A;  /* [rows][K], row stride lda */
+  long lda;
+  const float* W;  /* [cols][K], row stride ldw */
+  long ldw;
+  int K;           /* multiple of 4; 0 = pair unused (A, W may be NULL then) */
+} astk_debug_row_pair;
+typedef struct {
+  size_t struct_size;
+  astk_debug_row_pair p[2];
+  int npairs;           /* 1 or 2: out = sum_p A_p W_p^T */
+  int M, N;
+  const float* bias;    /* [N] or NULL */
+  const float* addend;  /* [M][N], row stride ld_add, or NULL */
+  long ld_add;
+  float* out;
+  long ld_out;
+  float* out2;          /* optional second copy, row stride ld_out2 */
+  long ld_out2;
+  int act;              /* 0 none, 1 tanh */
+  float* carry;         /* optional: for n >= carry_col0, j = n - carry_col0: carry[r][j] = (out[r][n] + carry[r][j]) * (1 - carry_aux[r][j]^2) */
+  long ld_carry;
+  const float* carry_aux;
+  long ld_carry_aux;
+  int carry_col0;
+} astk_debug_rowgemm_args;
+typedef struct {
+  size_t struct_size;
+  astk_debug_row_pair p[2];  /* W_p: [4h][K_p], gate rows interleaved 4j + k, k = a, i, f, o */
+  int npairs;                /* 0..2 */
+  int B, h;
+  const float* zx;           /* [B][4h], row stride ld_zx, or NULL */
+  long ld_zx;
+  const float* bias;         /* [4h] or NULL */
+  const float* c_prev;       /* [B][h] or NULL (zeros) */
+  float* gates;              /* [B][4h], row stride ld_g: the activated gates (may alias zx) */
+  long ld_g;
+  float* c_out;              /* [B][h] */
+  float* h_out;              /* [B][h] */
+  const float* mask;         /* [B][h] or NULL: applied to the dropped outputs only */
+  float* hd_out;             /* optional, row stride ld_hd */
+  long ld_hd;
+  float* hd_out2;            /* optional, row stride ld_hd2 */
+  long ld_hd2;
+} astk_debug_cell_fwd_args;
+typedef struct {
+  size_t struct_size;
+  astk_debug_row_pair p[2];  /* p[0] -> dh_rec (unmasked); p[1] -> joins dy, dy2 under the mask; W_p: [h][K_p] */
+  int npairs;                /* 1 or 2 (K of p[0] may be 0: the last step) */
+  int B, h;
+  const float* dh_add;       /* [B][h] or NULL, unmasked */
+  const float* dy;           /* row stride ld_dy, or NULL */
+  long ld_dy;
+  const float* dy2;          /* row stride ld_dy2, or NULL */
+  long ld_dy2;
+  const float* mask;         /* [B][h] or NULL */
+  const float* dc_next;      /* [B][h] or NULL */
+  const float* c_prev;       /* [B][h] or NULL (zeros) */
+  const float* c_cur;        /* [B][h] */
+  float* gates_dz;           /* [B][4h], row stride ld_g: in the activated gates, out dz */
+  long ld_g;
+  float* dc_prev;            /* [B][h] */
+} astk_debug_cell_bwd_args;
+int astk_debug_rowgemm(const astk_debug_rowgemm_args* args, int* route, void* stream);
+int astk_debug_lstm_cell_fwd(const astk_debug_cell_fwd_args* cells, int ncells, int* route, void* stream);
+int astk_debug_lstm_cell_bwd(const astk_debug_cell_bwd_args* cells, int ncells, int* route, void* stream);
+#endif
+
 /* Optional per-kernel HIP-event timing on the launch stream (bench.py's roofline legs; off by default).
  * astk_prof_end: res[0..1] attention-scan fwd (ms, launches); [2..3] attention-scan bwd; [4..6] GEMMs (ms, launches, flops);
  * [7..8] fused LSTM cells (ms, launches); [9..11] attention-scan phase inside the persistent decoder forward measured with
