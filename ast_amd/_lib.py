@@ -11,6 +11,7 @@ TEST_LIB_PATH = os.path.join(_HERE, "libastk_test.so")     # the same library bu
 MAX_CNN = 4
 MAX_RNN = 8
 MAX_ATTN = 4
+ENCODE_ROWS_MAX = 32      # astk.h ASTK_ENCODE_ROWS_MAX: rows of one astk_*_fwd_rows encoder call
 # astk.h: arithmetic of an op's products (descriptor field `precision`) and operand mode (`gemm_operands`)
 PREC_DEFAULT, PREC_FP16X2, PREC_BF16X3, PREC_F32 = 0, 1, 2, 3
 OPERANDS_DEFAULT, OPERANDS_F32, OPERANDS_FP16 = 0, 1, 2
@@ -169,6 +170,9 @@ SIGNATURES = {
     "astk_conv_bn_relu_fwd_sync": (C.c_int, [C.POINTER(CnnDesc), C.POINTER(CnnLayerParams), _VP, _VP, _VP, _VP, _SZ, _I, _VP, _VP, _I, _VP]),
     "astk_conv_bn_relu_bwd_sync": (C.c_int, [C.POINTER(CnnDesc), C.POINTER(CnnLayerParams), C.POINTER(CnnLayerGrads), _VP, _VP, _SZ, _VP, _VP,
                                              _I, _VP]),
+    "astk_conv_bn_relu_fwd_rows": (C.c_int, [C.POINTER(CnnDesc), C.POINTER(CnnLayerParams), _VP, _VP, _VP, _VP, _VP, _SZ, _VP]),
+    "astk_lstm_stack_rows_workspace_bytes": (_SZ, [C.POINTER(LstmStackDesc)]),
+    "astk_lstm_stack_fwd_rows": (C.c_int, [C.POINTER(LstmStackDesc), C.POINTER(LstmParams), _VP, _VP, _VP, _VP, _VP, _VP, _SZ, _VP]),
     "astk_lstm_stack_workspace_bytes": (_SZ, [C.POINTER(LstmStackDesc)]),
     "astk_lstm_stack_fwd": (C.c_int, [C.POINTER(LstmStackDesc), C.POINTER(LstmParams), _VP, _VP, _VP, _VP, _VP, _VP, _SZ, _VP]),
     "astk_lstm_stack_bwd": (C.c_int, [C.POINTER(LstmStackDesc), C.POINTER(LstmParams), C.POINTER(LstmGrads), _VP, _VP, _VP, _VP,

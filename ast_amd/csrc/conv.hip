@@ -754,6 +754,68 @@ __global__ __launch_bounds__(256) void k_bn_relu_to_seq(const float* __restrict_
   for (int i = threadIdx.x; i < n; i += blockDim.x) o[i] = tile[i];
   if (amax) amax_emit_block(amax, mx, red4);
 }
+// ---- per-row frame counts (astk_conv_bn_relu_fwd_rows; evaluation mode).  Row b of the zero-padded batch holds row_len[b] frames; layer i
+// gives it T_i(b) output steps by the formula of conv_out.  What a layer writes for row b at t >= T_i(b) -- relu(shift) plus partial
+// windows -- is replaced by zero where the activation is written, so the layer above reads the zero time padding the lone utterance has.
+struct RowsGeom { int n; int kt[ASTK_MAX_CNN_LAYERS], st[ASTK_MAX_CNN_LAYERS], pt[ASTK_MAX_CNN_LAYERS]; };
+// (the host has checked every row: no layer's padded input is shorter than its kernel)
+__device__ __forceinline__ int rows_len_at(const RowsGeom& g, int len, int layer) {
+  for (int i = 0; i <= layer; ++i) len = (len + 2 * g.pt[i] - g.kt[i]) / g.st[i] + 1;
+  return len;
+}
+// k_bn_relu_rows with the mask: rows m = (b, f, t) with t >= T_layer(b) are written as zeros
+__global__ __launch_bounds__(256) void k_bn_relu_rows_len(const float* __restrict__ Y, const float* __restrict__ bn, float* __restrict__ dst, int rows, int C,
+                                                          int Tn, int pad, unsigned long long* amax, const int* __restrict__ row_len, RowsGeom g,
+                                                          int layer, int F) {
+  __shared__ float red4[4];
+  const long n4 = (long)rows * C / 4;
+  const int C4 = C / 4;
+  float mx = 0.f;
+  for (long i = blockIdx.x * (long)blockDim.x + threadIdx.x; i < n4; i += (long)gridDim.x * blockDim.x) {
+    const int m = (int)(i / C4), c = (int)(i % C4) * 4;
+    const int grp = m / Tn, t = m % Tn;
+    float4 o = make_float4(0.f, 0.f, 0.f, 0.f);
+    if (t < rows_len_at(g, row_len[grp / F], layer)) {
+      const float4 y = *reinterpret_cast<const float4*>(Y + (long)m * C + c);
+      const float4 sc = *reinterpret_cast<const float4*>(bn + 2 * C + c);
+      const float4 sh = *reinterpret_cast<const float4*>(bn + 3 * C + c);
+      o.x = fmaxf(y.x * sc.x + sh.x, 0.f); o.y = fmaxf(y.y * sc.y + sh.y, 0.f);
+      o.z = fmaxf(y.z * sc.z + sh.z, 0.f); o.w = fmaxf(y.w * sc.w + sh.w, 0.f);
+    }
+    const long pr = (long)grp * (Tn + 2 * pad) + pad + t;
+    *reinterpret_cast<float4*>(dst + pr * C + c) = o;
+    mx = fmaxf(fmaxf(mx, fmaxf(o.x, o.y)), fmaxf(o.z, o.w));
+  }
+  if (pad > 0) zero_pad_rows(dst, rows / Tn, Tn, pad, pad, C);
+  if (amax) amax_emit_block(amax, mx, red4);
+}
+// k_bn_relu_to_seq with the mask: out[t >= T''(b)][b][:] = 0; the blocks of t = 0 leave T''(b) in out_len
+__global__ __launch_bounds__(256) void k_bn_relu_to_seq_len(const float* __restrict__ Y, const float* __restrict__ bn, float* __restrict__ out,
+                                                            int B, int F, int Tn, int C, unsigned long long* amax, const int* __restrict__ row_len,
+                                                            RowsGeom g, int* __restrict__ out_len) {
+  extern __shared__ float tile[];   // [C*F]
+  __shared__ float red4[4];
+  const int t = blockIdx.x, b = blockIdx.y;
+  const int n = C * F;
+  const int len = rows_len_at(g, row_len[b], g.n - 1);
+  if (out_len && t == 0 && threadIdx.x == 0) out_len[b] = len;
+  float* o = out + ((long)t * B + b) * n;
+  float mx = 0.f;
+  if (t < len) {             // (uniform over the block)
+    for (int i = threadIdx.x; i < n; i += blockDim.x) {
+      const int f = i / C, c = i % C;
+      const float y = Y[(((long)b * F + f) * Tn + t) * C + c];
+      const float v = fmaxf(y * bn[2 * C + c] + bn[3 * C + c], 0.f);
+      tile[c * F + f] = v;
+      mx = fmaxf(mx, v);
+    }
+    __syncthreads();
+    for (int i = threadIdx.x; i < n; i += blockDim.x) o[i] = tile[i];
+  } else {
+    for (int i = threadIdx.x; i < n; i += blockDim.x) o[i] = 0.f;
+  }
+  if (amax) amax_emit_block(amax, mx, red4);
+}
 // G[(b,f,t)][c] = d_out[t][b][c*F+f]
 __global__ __launch_bounds__(256) void k_seq_to_rows(const float* __restrict__ d_out, float* __restrict__ G, int B, int F, int Tn, int C) {
   extern __shared__ float tile[];
@@ -1110,6 +1172,14 @@ inline unsigned gridn(size_t n) {
   return (unsigned)b;
 }
 
+RowsGeom rows_geom(const astk_cnn_desc* d) {
+  RowsGeom g;
+  memset(&g, 0, sizeof(g));
+  g.n = d->n_layers;
+  for (int i = 0; i < d->n_layers; ++i) { g.kt[i] = d->kt[i]; g.st[i] = d->st[i]; g.pt[i] = d->pt[i]; }
+  return g;
+}
+
 int ksplit_for(long tiles, long K) {
   // aim for ~512 workgroups, at least 256 of K per split
   long s = 512 / (tiles > 0 ? tiles : 1);
@@ -1148,6 +1218,10 @@ size_t astk_conv_bn_relu_workspace_bytes(const astk_cnn_desc* d) {
   return P.bytes;
 }
 
+static int conv_fwd(const astk_cnn_desc* d, const astk_cnn_layer_params* L, const float* X, const float* noise, float* out, void* ws,
+                    size_t ws_bytes, int train, astk_stat_exchange_fn exchange, void* user, int world, void* stream, const int* row_len,
+                    int* out_len);
+
 int astk_conv_bn_relu_fwd(const astk_cnn_desc* d, const astk_cnn_layer_params* L, const float* X, const float* noise, float* out,
                           void* ws, size_t ws_bytes, int train, void* stream) {
   return astk_conv_bn_relu_fwd_sync(d, L, X, noise, out, ws, ws_bytes, train, nullptr, nullptr, 1, stream);
@@ -1156,6 +1230,14 @@ int astk_conv_bn_relu_fwd(const astk_cnn_desc* d, const astk_cnn_layer_params* L
 int astk_conv_bn_relu_fwd_sync(const astk_cnn_desc* d, const astk_cnn_layer_params* L, const float* X, const float* noise, float* out,
                                void* ws, size_t ws_bytes, int train, astk_stat_exchange_fn exchange, void* user, int world,
                                void* stream) {
+  return conv_fwd(d, L, X, noise, out, ws, ws_bytes, train, exchange, user, world, stream, nullptr, nullptr);
+}
+
+// The forward pass of every entry point.  row_len (device, B frame counts; evaluation mode, checked by astk_conv_bn_relu_fwd_rows): the
+// two activation-writing launches are the masked kernels; NULL: the call of always.
+static int conv_fwd(const astk_cnn_desc* d, const astk_cnn_layer_params* L, const float* X, const float* noise, float* out, void* ws,
+                    size_t ws_bytes, int train, astk_stat_exchange_fn exchange, void* user, int world, void* stream, const int* row_len,
+                    int* out_len) {
   hipStream_t s = (hipStream_t)stream;
   ASTK_CHECK_DESC(d, astk_cnn_desc);
   PrecScope prec_scope(d->precision, d->gemm_operands);
@@ -1241,8 +1323,18 @@ int astk_conv_bn_relu_fwd_sync(const astk_cnn_desc* d, const astk_cnn_layer_para
     }
     if (i < P.n - 1) {
       // (k_bn_relu_rows zeroes the pad rows of HP[i] itself)
+      if (row_len)
+        hipLaunchKernelGGL(k_bn_relu_rows_len, dim3(gridn((size_t)rows * C / 4)), dim3(256), 0, s, P.Y[i], P.bn[i], P.HP[i], rows, C,
+                           P.Tn[i], P.padA[i], P.a_hp_s[i], row_len, rows_geom(d), i, F);
+      else
       hipLaunchKernelGGL(k_bn_relu_rows, dim3(gridn((size_t)rows * C / 4)), dim3(256), 0, s, P.Y[i], P.bn[i], P.HP[i], rows, C,
                          P.Tn[i], P.padA[i], P.a_hp_s[i]);
+      ASTK_LAUNCH_CHECK();
+    } else if (row_len) {
+      const size_t shm = (size_t)C * F * sizeof(float);
+      ASTK_CHECK(shm <= 64 * 1024, "cnn: C*F' too large for the re-layout tile (%zu bytes)", shm);
+      hipLaunchKernelGGL(k_bn_relu_to_seq_len, dim3(P.Tn[i], B), dim3(256), shm, s, P.Y[i], P.bn[i], out, B, F, P.Tn[i], C, P.a_out, row_len,
+                         rows_geom(d), out_len);
       ASTK_LAUNCH_CHECK();
     } else {
       const bool tiled_off = !tune_on(TUNE_CONV_SEQ_FWD);
@@ -1260,6 +1352,28 @@ int astk_conv_bn_relu_fwd_sync(const astk_cnn_desc* d, const astk_cnn_layer_para
   }
   if (seq_out_zeroes) conv0_path_record(ws, conv0_direct(d), true);      // every launch of the call went out: its last kernel zeroes the backward's region
   return 0;
+}
+
+int astk_conv_bn_relu_fwd_rows(const astk_cnn_desc* d, const astk_cnn_layer_params* L, const float* X, const int32_t* row_len, float* out,
+                               int32_t* out_len, void* ws, size_t ws_bytes, void* stream) {
+  if (!row_len) return astk_conv_bn_relu_fwd(d, L, X, nullptr, out, ws, ws_bytes, 0, stream);
+  CnnPlan P;
+  ASTK_TRY(make_plan(d, nullptr, P));
+  for (int i = 0; i < P.n; ++i) ASTK_CHECK(!P.pooled[i], "conv_bn_relu_fwd_rows: pooled layers (cnn_pool) take no row lengths (layer %d)", i);
+  ASTK_CHECK(P.B <= ASTK_ENCODE_ROWS_MAX, "conv_bn_relu_fwd_rows: at most %d rows, got %d", ASTK_ENCODE_ROWS_MAX, P.B);
+  // the lengths are read back before anything is launched: a row the library would refuse alone is refused here
+  int32_t len[ASTK_ENCODE_ROWS_MAX];
+  ASTK_CHECK(hipMemcpyAsync(len, row_len, (size_t)P.B * sizeof(int32_t), hipMemcpyDeviceToHost, (hipStream_t)stream) == hipSuccess &&
+             hipStreamSynchronize((hipStream_t)stream) == hipSuccess, "conv_bn_relu_fwd_rows: reading row_len failed");
+  for (int b = 0; b < P.B; ++b) {
+    ASTK_CHECK(len[b] >= 1 && len[b] <= P.T, "conv_bn_relu_fwd_rows: row_len[%d] = %d outside 1..T = %d", b, len[b], P.T);
+    int t = len[b];
+    for (int i = 0; i < P.n; ++i) {
+      t = conv_out(t, d->kt[i], d->st[i], d->pt[i]);
+      ASTK_CHECK(t >= 1, "conv_bn_relu_fwd_rows: row %d (%d frames) is too short for layer %d", b, len[b], i);
+    }
+  }
+  return conv_fwd(d, L, X, nullptr, out, ws, ws_bytes, 0, nullptr, nullptr, 1, stream, row_len, out_len);
 }
 
 const void* astk_conv_out_amax(const astk_cnn_desc* d, void* ws, size_t ws_bytes) {

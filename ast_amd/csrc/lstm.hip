@@ -259,6 +259,45 @@ __global__ void k_gather_rows(float* __restrict__ dst, const float* __restrict__
   }
 }
 
+// ---- per-row lengths (astk_lstm_stack_fwd_rows).  Row b holds n = row_len[b] frames (host-checked: 1..T).
+// k_perm_rows per row: loop step i < n of direction 1 reads frame (n - i) % n of its own row -- the lone utterance's permutation; a step
+// i >= n reads frame i (in range; both directions are causal in loop-step order, so no step < n sees it).  Only the forward table.
+__global__ void k_perm_rows_len(int* rows_perm, int T, int B, const int* __restrict__ row_len, const unsigned long long* fold_src,
+                                unsigned long long* fold_dst, unsigned* zflags, int nzf) {
+  if (fold_src && blockIdx.x == 0 && threadIdx.x < 64) amax_compact(fold_src, fold_dst);
+  if (zflags && blockIdx.x == 0 && (int)threadIdx.x < nzf) __hip_atomic_store(zflags + threadIdx.x * 64, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+  const int i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i < T * B) {
+    const int st = i / B, b = i % B, n = row_len[b];
+    rows_perm[i] = (st < n ? (n - st) % n : st) * B + b;
+  }
+}
+// enc_states[b][p][dd * h + :] = the top layer's h of loop step (dd == 0 ? p : n - 1 - p) for p < n, zero behind  (float4 columns)
+struct RowsTop { const float* HR[2]; };
+__global__ void k_rows_place_enc(float* __restrict__ enc, RowsTop top, const int* __restrict__ row_len, int T, int B, int h, int nd) {
+  const int h4 = h / 4;
+  const long total = (long)B * T * nd * h4;
+  for (long i = blockIdx.x * (long)blockDim.x + threadIdx.x; i < total; i += (long)gridDim.x * blockDim.x) {
+    const int c = (int)(i % h4), dd = (int)(i / h4 % nd), p = (int)(i / ((long)h4 * nd) % T), b = (int)(i / ((long)h4 * nd * T));
+    const int n = row_len[b];
+    float4 v = make_float4(0.f, 0.f, 0.f, 0.f);
+    if (p < n) v = reinterpret_cast<const float4*>(top.HR[dd] + ((long)(dd == 0 ? p : n - 1 - p) * B + b) * h)[c];
+    reinterpret_cast<float4*>(enc)[i] = v;      // ((b * T + p) * nd + dd) * h4 + c: the (B,T,nd*h) layout
+  }
+}
+// cT / hT [cell][b][:] = the cell's CC / HR at loop step row_len[b] - 1
+struct RowsCells { int n; const float* CC[16]; const float* HR[16]; };
+__global__ void k_rows_final_states(float* __restrict__ cT, float* __restrict__ hT, RowsCells cells, const int* __restrict__ row_len, int B, int h) {
+  const int h4 = h / 4;
+  const long total = (long)cells.n * B * h4;
+  for (long i = blockIdx.x * (long)blockDim.x + threadIdx.x; i < total; i += (long)gridDim.x * blockDim.x) {
+    const int c = (int)(i % h4), b = (int)(i / h4 % B), q = (int)(i / ((long)h4 * B));
+    const long src = ((long)(row_len[b] - 1) * B + b) * h4 + c;
+    if (cT) reinterpret_cast<float4*>(cT)[i] = reinterpret_cast<const float4*>(cells.CC[q])[src];
+    if (hT) reinterpret_cast<float4*>(hT)[i] = reinterpret_cast<const float4*>(cells.HR[q])[src];
+  }
+}
+
 // ---- what the functions of one call share
 struct LstmCall {
   const astk_lstm_stack_desc* d;
@@ -272,6 +311,7 @@ struct LstmCall {
 struct LstmFwdCall : LstmCall {
   float *enc_states, *cT, *hT;
   SidePlan side;
+  const int* row_len;                  // astk_lstm_stack_fwd_rows: the rows' lengths (device), else null
 };
 struct LstmBwdCall : LstmCall {
   const astk_lstm_grads* gr;
@@ -430,13 +470,30 @@ int fwd_final_states(const LstmFwdCall& c) {
   return copy_segments(cp, c.s);
 }
 
+// calls with row lengths: the recurrences have left every step's h and c in the workspace (and, in enc_states, the batch's placement, which
+// is overwritten here); one launch places both halves of enc_states per row, one gathers every cell's states at the row's last step
+int fwd_rows_outputs(const LstmFwdCall& c) {
+  const LstmPlan& P = c.P;
+  RowsTop top = {{P.HR[0][P.nl - 1], P.nd > 1 ? P.HR[1][P.nl - 1] : nullptr}};
+  hipLaunchKernelGGL(k_rows_place_enc, dim3(std::min(2048, cdiv(P.B * P.T * P.nd * (P.h / 4), 256))), dim3(256), 0, c.s, c.enc_states, top, c.row_len, P.T, P.B, P.h, P.nd);
+  ASTK_LAUNCH_CHECK();
+  if (!c.cT && !c.hT) return 0;
+  RowsCells cells;
+  cells.n = P.nd * P.nl;
+  for (int dd = 0; dd < P.nd; ++dd)
+    for (int l = 0; l < P.nl; ++l) { cells.CC[dd * P.nl + l] = P.CC[dd][l]; cells.HR[dd * P.nl + l] = P.HR[dd][l]; }
+  hipLaunchKernelGGL(k_rows_final_states, dim3(std::min(2048, cdiv(cells.n * P.B * (P.h / 4), 256))), dim3(256), 0, c.s, c.cT, c.hT, cells, c.row_len, P.B, P.h);
+  ASTK_LAUNCH_CHECK();
+  return 0;
+}
+
 // persistent and hoisted paths: layer-0 upward projection batched over time, then the recurrence launches
 int fwd_persist(LstmFwdCall& c) {
   PersistCellHost cells[16];
   ASTK_TRY(persist_fwd_cells(c, cells));
   ASTK_TRY(fwd_project_layer0(c, cells));
   ASTK_TRY(c.R.path == LSTM_HOISTED ? fwd_hoisted_launches(c, cells) : fwd_grouped_launches(c, cells));
-  return fwd_final_states(c);
+  return c.row_len ? fwd_rows_outputs(c) : fwd_final_states(c);
 }
 
 // per-step path: per layer the upward projection of each direction, T cell launches, the final states
@@ -486,12 +543,12 @@ int fwd_steps(const LstmFwdCall& c) {
       }
       ASTK_TRY(lstm_cell_fwd_launch(cells, P.nd, c.s));
     }
-    for (int dd = 0; dd < P.nd; ++dd) {
+    for (int dd = 0; dd < P.nd && !c.row_len; ++dd) {
       if (c.cT) ASTK_TRY(copy_f32(c.cT + ((size_t)dd * P.nl + l) * bh, P.CC[dd][l] + (size_t)(T - 1) * bh, bh, c.s));
       if (c.hT) ASTK_TRY(copy_f32(c.hT + ((size_t)dd * P.nl + l) * bh, P.HR[dd][l] + (size_t)(T - 1) * bh, bh, c.s));
     }
   }
-  return 0;
+  return c.row_len ? fwd_rows_outputs(c) : 0;
 }
 
 // ---- backward
@@ -802,22 +859,55 @@ size_t astk_lstm_stack_workspace_bytes(const astk_lstm_stack_desc* d) {
   return make_plan(d, nullptr, R, P) != 0 ? 0 : P.bytes;
 }
 
-int astk_lstm_stack_fwd(const astk_lstm_stack_desc* d, const astk_lstm_params* prm, const float* x, const float* masks,
-                        float* enc_states, float* cT, float* hT, void* ws, size_t ws_bytes, void* stream) {
+// the forward pass of both entry points; row_len (device, host-checked by astk_lstm_stack_fwd_rows): the per-row index table and outputs
+static int lstm_fwd(const astk_lstm_stack_desc* d, const astk_lstm_params* prm, const float* x, const float* masks, const int* row_len,
+                    float* enc_states, float* cT, float* hT, void* ws, size_t ws_bytes, void* stream) {
   ASTK_CHECK_DESC(d, astk_lstm_stack_desc);
   PrecScope prec_scope(d->precision, d->gemm_operands);
   GemmForwardScope forward_scope;      // split tiles of this op's products have at most two contributors (reproducible forward pass)
   LstmFwdCall c;
   c.d = d; c.prm = prm; c.x = x; c.masks = masks; c.enc_states = enc_states; c.cT = cT; c.hT = hT; c.s = (hipStream_t)stream;
+  c.row_len = row_len;
   ASTK_TRY(make_plan(d, ws, c.R, c.P));
   const LstmPlan& P = c.P;
   ASTK_CHECK(ws && ws_bytes >= P.bytes, "lstm_stack_fwd: workspace too small (%zu < %zu)", ws_bytes, P.bytes);
   ASTK_CHECK(prm && x && enc_states, "lstm_stack_fwd: null pointer");
   c.side = plan_side_fwd(d, c.R);
+  const unsigned long long* fold_src = x_amax_strided(d) ? (const unsigned long long*)d->x_amax : nullptr;
+  if (row_len)
+    hipLaunchKernelGGL(k_perm_rows_len, dim3(cdiv(P.T * P.B, 256)), dim3(256), 0, c.s, P.rows_perm, P.T, P.B, row_len, fold_src, P.ax,
+                       c.side.n > 0 ? P.zflags : nullptr, c.side.n + 2);
+  else
   hipLaunchKernelGGL(k_perm_rows, dim3(cdiv(P.T * P.B, 256)), dim3(256), 0, c.s, P.perm, P.inv, P.rows_perm, P.rows_inv, P.T, P.B,
-                     x_amax_strided(d) ? (const unsigned long long*)d->x_amax : nullptr, P.ax, c.side.n > 0 ? P.zflags : nullptr, c.side.n + 2);
+                     fold_src, P.ax, c.side.n > 0 ? P.zflags : nullptr, c.side.n + 2);
   ASTK_LAUNCH_CHECK();
   return c.R.path == LSTM_PER_STEP ? fwd_steps(c) : fwd_persist(c);
+}
+
+int astk_lstm_stack_fwd(const astk_lstm_stack_desc* d, const astk_lstm_params* prm, const float* x, const float* masks,
+                        float* enc_states, float* cT, float* hT, void* ws, size_t ws_bytes, void* stream) {
+  return lstm_fwd(d, prm, x, masks, nullptr, enc_states, cT, hT, ws, ws_bytes, stream);
+}
+
+// (every route keeps each step's h and c of every cell in the workspace, which is all the per-row outputs need: no route reports 0;
+//  what does is a batch above the rows limit, and a descriptor astk_lstm_stack_workspace_bytes refuses)
+size_t astk_lstm_stack_rows_workspace_bytes(const astk_lstm_stack_desc* d) {
+  if (!d || d->struct_size != sizeof(astk_lstm_stack_desc) || d->B > ASTK_ENCODE_ROWS_MAX) return 0;
+  return astk_lstm_stack_workspace_bytes(d);
+}
+
+int astk_lstm_stack_fwd_rows(const astk_lstm_stack_desc* d, const astk_lstm_params* prm, const float* x, const int32_t* row_len,
+                             float* enc_states, float* cT, float* hT, void* ws, size_t ws_bytes, void* stream) {
+  if (!row_len) return astk_lstm_stack_fwd(d, prm, x, nullptr, enc_states, cT, hT, ws, ws_bytes, stream);
+  ASTK_CHECK_DESC(d, astk_lstm_stack_desc);
+  ASTK_CHECK(d->B >= 1 && d->B <= ASTK_ENCODE_ROWS_MAX, "lstm_stack_fwd_rows: 1..%d rows, got %d", ASTK_ENCODE_ROWS_MAX, d->B);
+  // the lengths index the workspace: read back and checked before anything is launched
+  int32_t len[ASTK_ENCODE_ROWS_MAX];
+  ASTK_CHECK(hipMemcpyAsync(len, row_len, (size_t)d->B * sizeof(int32_t), hipMemcpyDeviceToHost, (hipStream_t)stream) == hipSuccess &&
+             hipStreamSynchronize((hipStream_t)stream) == hipSuccess, "lstm_stack_fwd_rows: reading row_len failed");
+  for (int b = 0; b < d->B; ++b)
+    ASTK_CHECK(len[b] >= 1 && len[b] <= d->T, "lstm_stack_fwd_rows: row_len[%d] = %d outside 1..T = %d", b, len[b], d->T);
+  return lstm_fwd(d, prm, x, nullptr, row_len, enc_states, cT, hT, ws, ws_bytes, stream);
 }
 
 int astk_lstm_stack_bwd(const astk_lstm_stack_desc* d, const astk_lstm_params* prm, const astk_lstm_grads* gr, const float* x,

@@ -74,7 +74,7 @@ def decode_beam_batch(model, Xs, stop_limit, N, K):
     with using_config("train", False):
         # ---- every utterance encoded at its own length (no length masks in the encoder, quirk Q2), copied out of the pooled buffers
         seeds = []
-        encs, _, _ = model._encode_alone(Xs, seeds)
+        encs, _, _ = model._encode_utts(Xs, seeds)      # (model.batch_encode: padded batches with per-row lengths)
         if stop_limit <= 0:
             return [[_init_hyp_from(model, s)] for s in seeds]
         U, nl, H, A, V = len(Xs), len(model.rnn_dec), model.H, model.A, model.V
@@ -210,7 +210,7 @@ def decode_beam_device(model, Xs, stop_limit, N, K):
     stop = int(stop_limit)
     with using_config("train", False):
         seeds = []
-        encs, _, _ = model._encode_alone(Xs, seeds)
+        encs, _, _ = model._encode_utts(Xs, seeds)      # (model.batch_encode: padded batches with per-row lengths)
         if stop <= 0:
             model.last_beam_path = None          # (no search ran)
             return [[_init_hyp_from(model, s)] for s in seeds]

@@ -373,6 +373,29 @@ def checked_row_lens(lens, B, T):
     return np.ascontiguousarray(lens.astype(np.int32))
 
 
+def cnn_out_lens(cnn_layers, n):
+    """Output steps of every CNN layer for an utterance of n frames (the time formula of astk_conv_bn_relu_out_dims, no pooling):
+    [T_0, .., T''].  ValueError where the library would refuse the utterance alone (a padded input shorter than the kernel)."""
+    out, t = [], int(n)
+    for i, l in enumerate(cnn_layers):
+        kt, st, pt = int(l["ksize"][0]), int(l["stride"][0]), int(l["pad"][0])
+        if t < 1 or t + 2 * pt < kt:
+            raise ValueError(f"cnn_out_lens: {int(n)} frames are too short for layer {i} (kt = {kt}, pad = {pt}, input {t})")
+        t = (t + 2 * pt - kt) // st + 1
+        out.append(t)
+    return out
+
+
+def plan_encode_batches(lens, max_rows=ROWS_MAX):
+    """Utterances -> encoder calls of at most max_rows rows: the indices ordered by length, longest first (ties in index order), cut
+    into consecutive batches, so that a batch pads its rows to a length close to their own.  Host only."""
+    max_rows = int(max_rows)
+    if max_rows < 1:
+        raise ValueError(f"plan_encode_batches: max_rows = {max_rows} must be at least 1")
+    order = sorted(range(len(lens)), key=lambda u: (-int(lens[u]), u))
+    return [order[i:i + max_rows] for i in range(0, len(order), max_rows)]
+
+
 class RowBatch:
     """Rows of DIFFERENT utterances for the decode entry points (`rows=` of predict / predict_scored / sample / score): `enc`
     (B, T''max, H) the rows' encoder memories, each padded behind its own length, `lens` (B,) int32 on the host, 1 <= lens[b] <= T''max,
@@ -487,6 +510,10 @@ class SpeechEncoderDecoder:
         self.last_beam_path = None      # "device" (astk_beam_decode) | "steps" (decode_beam_batch): which path the last decode_beam_device took
         self.last_beam_steps = []       # ... and, on the device path, the steps each of its launches ran (n_steps)
         self.last_predict_path = None   # "device" (astk_greedy_decode) | "steps" (the per-step loop): which path the last predict() took
+        # Evaluation-mode encodings of several utterances (encode_rows, decode_beam_batch / _device): False = every utterance alone at
+        # batch 1; True = the distinct utterances in padded batches with per-row lengths (astk_*_fwd_rows), each row what it gives alone.
+        self.batch_encode = False
+        self.last_encode_path = None    # "batched" | "alone": which of the two the last such encoding took
         # Arithmetic of the batched products, per model (-> the descriptors' `precision` / `gemm_operands` fields): None = the library's
         # process-wide default (bf16x3: exact f32 operands on the 16-bit matrix pipe); "bf16x3" | "f32" | "fp16x2" (narrower, opt-in);
         # gemm_operands "fp16" = single-term fp16 operands for the eligible products (BASELINE configs[4]; reduced precision).
@@ -1163,23 +1190,104 @@ class SpeechEncoderDecoder:
         self._dec_c, self._dec_h = rows.c0.to(**f32).contiguous().clone(), rows.h0.to(**f32).contiguous().clone()
         return B
 
-    def encode_rows(self, Xs, rows_of=None):
-        """A RowBatch of utterances: every X of the list Xs ((1, T_u, D) or (T_u, D)) is encoded ALONE, at batch 1 in eval mode -- the
-        encoder has no length masks, so this is the only encoding that does not depend on the batch around it, and the one beam
-        search sees -- and seeds its rows' decoder state as init_decoder_state does.  rows_of[b] = the utterance of row b (default: one
-        row per utterance, in order); at most 32 rows."""
+    def encode_rows(self, Xs, rows_of=None, batch_encode=None):
+        """A RowBatch of utterances: every X of the list Xs ((1, T_u, D) or (T_u, D)) is encoded as it is ALONE, at batch 1 in eval mode
+        -- the reference's encoder has no length masks, so this is the only encoding that does not depend on the batch around it, and
+        the one beam search sees -- and seeds its rows' decoder state as init_decoder_state does.  rows_of[b] = the utterance of row b
+        (default: one row per utterance, in order); at most 32 rows.
+        batch_encode (default: the model's attribute, False): the distinct utterances of rows_of go through the encoder in padded
+        batches of up to 32 with per-row lengths (_encode_batched) instead of one call each; last_encode_path says which ran."""
         rows_of = list(range(len(Xs))) if rows_of is None else [int(u) for u in rows_of]
         if not rows_of or len(rows_of) > ROWS_MAX:
             raise ValueError(f"encode_rows: 1..{ROWS_MAX} rows, got {len(rows_of)}")
         if min(rows_of) < 0 or max(rows_of) >= len(Xs):
             raise ValueError(f"encode_rows: rows_of names utterances outside 0..{len(Xs) - 1}")
-        encs, c0s, h0s = self._encode_alone(Xs)
-        lens = [int(e.shape[0]) for e in encs]
+        encs, c0s, h0s = self._encode_utts(Xs, batch_encode=batch_encode, only=sorted(set(rows_of)))
+        lens = {u: int(encs[u].shape[0]) for u in set(rows_of)}
         f32 = dict(device=self.device, dtype=torch.float32)
         enc = torch.zeros(len(rows_of), max(lens[u] for u in rows_of), self.H, **f32)
         for b, u in enumerate(rows_of):
             enc[b, :lens[u]] = encs[u]
         return RowBatch(enc, [lens[u] for u in rows_of], torch.stack([c0s[u] for u in rows_of], 1), torch.stack([h0s[u] for u in rows_of], 1))
+
+    def _encode_utts(self, Xs, seeds=None, batch_encode=None, only=None):
+        """What encode_rows and the batched beam searches share: _encode_alone, or -- batch_encode, default the model's attribute -- the
+        same lists from _encode_batched, which encodes the utterances `only` names (default all; the other entries are None).  Models
+        the batched calls do not serve (an encoder variant, cnn_pool, a workspace query of 0) take _encode_alone silently."""
+        on = self.batch_encode if batch_encode is None else bool(batch_encode)
+        out = self._encode_batched(Xs, seeds, only) if on else None
+        self.last_encode_path = "alone" if out is None else "batched"
+        return self._encode_alone(Xs, seeds) if out is None else out
+
+    def _batch_encode_served(self):
+        return self.enc_variant is None and not self.cfg["cnn_config"].get("cnn_pool")
+
+    def _encode_batched(self, Xs, seeds=None, only=None):
+        """_encode_alone's lists from padded batches: the utterances, longest first, in batches of at most 32 (plan_encode_batches), each
+        batch through _encode_batch.  None (nothing launched) when the model or a batch's shape is not served."""
+        if not self._batch_encode_served():
+            return None
+        Xs = [self._as_input(X) for X in Xs]
+        Xs = [X[0] if X.dim() == 3 else X for X in Xs]
+        only = list(range(len(Xs))) if only is None else list(only)
+        frames = [int(Xs[u].shape[0]) for u in only]
+        if min(frames) < 1:
+            raise ValueError("encode_rows: an utterance has no frames")
+        batches = [[only[k] for k in batch] for batch in plan_encode_batches(frames)]
+        encs, c0s, h0s = [None] * len(Xs), [None] * len(Xs), [None] * len(Xs)
+        sd = [None] * len(Xs)
+        with using_config("train", False):
+            plans = [self._plan_encode_batch([Xs[u] for u in batch]) for batch in batches]
+            if any(p is None for p in plans):
+                return None
+            for batch, plan in zip(batches, plans):
+                e, c, h, s_ = self._encode_batch([Xs[u] for u in batch], plan)
+                for k, u in enumerate(batch):
+                    encs[u], c0s[u], h0s[u], sd[u] = e[k], c[k], h[k], s_[k]
+        if seeds is not None:
+            seeds.extend(sd)
+        return encs, c0s, h0s
+
+    def _plan_encode_batch(self, Xs):
+        """Shape state and row lengths of one padded batch, or None when the library does not serve its LSTM shape with row lengths."""
+        lib = self._require_gpu()
+        B, T, D = len(Xs), max(int(X.shape[0]) for X in Xs), int(Xs[0].shape[1])
+        st = self._shape_state(B, T, D, 2)
+        if int(lib.astk_lstm_stack_rows_workspace_bytes(C.byref(st["ld"]))) == 0:
+            return None
+        lens = np.asarray([int(X.shape[0]) for X in Xs], dtype=np.int32)
+        lens2 = np.asarray([cnn_out_lens(self.cfg["cnn_config"]["cnn_layers"], n)[-1] for n in lens], dtype=np.int32)
+        return st, lens, lens2
+
+    def _encode_batch(self, Xs, plan):
+        """One padded batch (<= 32 utterances (T_u, D) on the device) through astk_conv_bn_relu_fwd_rows and astk_lstm_stack_fwd_rows and
+        the bridge of init_decoder_state: per utterance its states (T''_u, H), decoder c and h (n_layers, H) and its
+        get_encoder_states()."""
+        lib = self._require_gpu()
+        st, lens, lens2 = plan
+        B, T = st["B"], st["T"]
+        X = torch.zeros(B, T, st["D"], dtype=torch.float32, device=self.device)      # zeros behind every row's frames: the entry point's contract
+        for b, Xu in enumerate(Xs):
+            X[b, :int(lens[b])] = Xu
+        row_len, row_len2 = torch.from_numpy(lens).to(self.device), torch.from_numpy(lens2).to(self.device)
+        self._cur = st
+        s = self._stream()
+        wc = self._workspace("cnn", st["ws_cnn"])
+        check(lib.astk_conv_bn_relu_fwd_rows(C.byref(st["cd"]), st["cp"], _vp(X), _vp(row_len), _vp(st["xlstm"]), None, _vp(wc), wc.numel(), s))
+        st["ld"].x_amax = lib.astk_conv_out_amax(C.byref(st["cd"]), _vp(wc), wc.numel())
+        wl = self._workspace("lstm", st["ws_lstm"])
+        side = self._side_stream()
+        st["ld"].side_stream = side.cuda_stream if side is not None else None
+        check(lib.astk_lstm_stack_fwd_rows(C.byref(st["ld"]), st["lp"], _vp(st["xlstm"]), _vp(row_len2), _vp(st["enc_states"]),
+                                           _vp(st["cT"]), _vp(st["hT"]), _vp(wl), wl.numel(), s))
+        self.enc_states = st["enc_states"]
+        self._bridge_states(st, st["c0"], st["h0"], st["cT"], st["hT"], True)
+        nd = self.n_dirs
+        encs = [st["enc_states"][b, :int(lens2[b])].clone() for b in range(B)]
+        c0s, h0s = [st["c0"][:, b].clone() for b in range(B)], [st["h0"][:, b].clone() for b in range(B)]
+        seeds = [{k: [torch.cat([st[k + "T"][d_, l, b:b + 1] for d_ in range(nd)], 1) for l in range(len(self.rnn_enc))] for k in ("c", "h")}
+                 for b in range(B)]
+        return encs, c0s, h0s, seeds
 
     def _encode_alone(self, Xs, seeds=None):
         """Every utterance of Xs encoded at its own length, copied out of the pooled buffers: its states (T''_u, H) and the decoder

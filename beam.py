@@ -1,5 +1,5 @@
 """beam.py drop-in (beam.py:46-146 of the reference):
-    python beam.py -m <cfg_dir> -n <N hyps kept> -k <K candidates per step> -s <set key> -w <length weight> [--resume] [-b U] [--device]
+    python beam.py -m <cfg_dir> -n <N hyps kept> -k <K candidates per step> -s <set key> -w <length weight> [--resume] [-b U] [--device] [--batch-encode]
 Beam search over one set with the newest checkpoint of the experiment, n-best lists pickled to
 <cfg_dir>/<set>_beam_N-<N>_K-<K>.p, the length-normalised best hypothesis of each utterance scored with corpus BLEU
 (ast_amd.eval) and written to <cfg_dir>/<set>_beam_N-<N>_K-<K>_W-<W>.en.  -b U decodes U utterances per batched search on the
@@ -39,6 +39,8 @@ if __name__ == "__main__":
     parser.add_argument("--resume", action="store_true", help="re-score the saved beam results instead of decoding again")
     parser.add_argument("-b", "--batch", type=int, default=0, help="decode U utterances at once on the GPU (same hypotheses)")
     parser.add_argument("--device", action="store_true", help="the whole search in persistent launches on the GPU (same hypotheses)")
+    parser.add_argument("--batch-encode", dest="batch_encode", action="store_true",
+                        help="encode the utterances of a call in one padded batch with per-row lengths instead of one by one (same encodings; effective with -b U / --device)")
     args = vars(parser.parse_args())
     cfg_path, N, K, W, set_key = args["cfg_path"], int(args["N"]), int(args["K"]), float(args["W"]), args["S"]
     U = args["batch"]
@@ -48,6 +50,7 @@ if __name__ == "__main__":
         print("-b {0:d}: N and K above {1:d} / {2:d} are decoded one utterance at a time".format(U, BEAM_MAX_N, BEAM_MAX_K))
         U = 0
     nn = NN(cfg_path)
+    nn.model.batch_encode = bool(args["batch_encode"])
     metrics = Eval(os.path.join(nn.cfg.train["data"]["refs_path"], set_key), nn.cfg.train["data"]["n_evals"])
     random.seed("meh")
     print("-" * 80)

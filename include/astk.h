@@ -182,6 +182,17 @@ int astk_conv_bn_relu_fwd(const astk_cnn_desc* d, const astk_cnn_layer_params* l
  * kernel, conv.hip) follows from them. */
 int astk_conv_bn_relu_bwd(const astk_cnn_desc* d, const astk_cnn_layer_params* layers,
                           const astk_cnn_layer_grads* grads, float* d_out, void* ws, size_t ws_bytes, void* stream);
+/* Evaluation mode with PER-ROW frame counts: X (B,T,D) is a batch of utterances of different lengths, row b holding
+ * row_len[b] frames (B device int32, 1..T) and ZEROS behind them -- the caller pads; that is a contract, not checked.  Running
+ * statistics, no noise.  Every layer's activation of row b is written as zero from the row's own output length on, so
+ * out[t < T''(b), b] is what the utterance gives alone (B = 1, T = row_len[b], train = 0) and out[t >= T''(b), b] is exactly 0.
+ * out_len (device, B int32; may be NULL) receives T''(b), the T_out astk_conv_bn_relu_out_dims reports for T = row_len[b].
+ * At most ASTK_ENCODE_ROWS_MAX rows.  The call reads row_len back and SYNCHRONISES `stream` before its first launch (not capturable)
+ * and refuses, before any launch: pooled layers, a length outside 1..T, a row whose lone geometry the library would refuse (a
+ * padded input shorter than kt).  Workspace: astk_conv_bn_relu_workspace_bytes.  row_len == NULL: astk_conv_bn_relu_fwd(train = 0). */
+#define ASTK_ENCODE_ROWS_MAX 32
+int astk_conv_bn_relu_fwd_rows(const astk_cnn_desc* d, const astk_cnn_layer_params* layers, const float* X, const int32_t* row_len,
+                               float* out, int32_t* out_len, void* ws, size_t ws_bytes, void* stream);
 /* Where the forward call leaves the absolute maximum of `out` (16 64-bit words inside ws; taken by the kernel that writes `out`):
  * pass it on as astk_lstm_stack_desc.x_amax.  Valid from the forward call until ws is reused.  NULL: bad arguments. */
 const void* astk_conv_out_amax(const astk_cnn_desc* d, void* ws, size_t ws_bytes);
@@ -262,6 +273,16 @@ size_t astk_lstm_stack_workspace_bytes(const astk_lstm_stack_desc* d);
 int astk_lstm_stack_fwd(const astk_lstm_stack_desc* d, const astk_lstm_params* params, const float* x,
                         const float* masks, float* enc_states, float* cT, float* hT,
                         void* ws, size_t ws_bytes, void* stream);
+/* The forward pass (no dropout masks) with PER-ROW lengths: row b of x (T,B,in) holds row_len[b] frames (B device
+ * int32, 1..T); what lies behind them is never read into a result.  Row b comes out as the utterance does alone (B = 1, T = row_len[b]):
+ * the reverse direction reads its frames 0, n-1, ..., 1 (quirk Q1 with n = row_len[b]), enc_states[b, p < n] holds both halves at the
+ * row's own positions, enc_states[b, p >= n] is exactly 0, and cT / hT are the states behind the row's last step.  At most
+ * ASTK_ENCODE_ROWS_MAX rows.  Reads row_len back and SYNCHRONISES `stream` before its first launch (not capturable); a length outside
+ * 1..T is refused before any launch.  astk_lstm_stack_rows_workspace_bytes: the workspace, or 0 for a descriptor the call does not
+ * serve.  row_len == NULL: astk_lstm_stack_fwd without masks. */
+size_t astk_lstm_stack_rows_workspace_bytes(const astk_lstm_stack_desc* d);
+int astk_lstm_stack_fwd_rows(const astk_lstm_stack_desc* d, const astk_lstm_params* params, const float* x, const int32_t* row_len,
+                             float* enc_states, float* cT, float* hT, void* ws, size_t ws_bytes, void* stream);
 /* d_enc_states (B,T,n_dirs*h); d_cT,d_hT (n_dirs,n_layers,B,h) or NULL; dx (T,B,in) written (may be NULL). */
 int astk_lstm_stack_bwd(const astk_lstm_stack_desc* d, const astk_lstm_params* params, const astk_lstm_grads* grads,
                         const float* x, const float* masks, const float* d_enc_states, const float* d_cT,

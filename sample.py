@@ -27,6 +27,8 @@ def build_parser():
     parser.add_argument("--mbr", action="store_true", help="also choose one sample per utterance by minimum Bayes risk")
     parser.add_argument("-w", "--out", help="pickle to write (default <cfg_dir>/<set>_sample_N-<N>_T-<T>.p)")
     parser.add_argument("-b", "--batch", type=int, default=1, help="pack the rows of U utterances into one call (default 1)")
+    parser.add_argument("--batch-encode", dest="batch_encode", action="store_true",
+                        help="encode the utterances of a call in one padded batch with per-row lengths instead of one by one (same encodings; effective with -b U)")
     parser.add_argument("-k", "--top-k", dest="top_k", type=int, default=None, help="draw among the top_k (1..16) best tokens only")
     parser.add_argument("-p", "--top-p", dest="top_p", type=float, default=1.0,
                         help="... cut to the smallest set of them holding a mass top_p in (0, 1] (needs -k; default 1: no cut)")
@@ -50,6 +52,7 @@ if __name__ == "__main__":
     except ValueError as e:
         parser.error(str(e))
     nn = NN(cfg_path)
+    nn.model.batch_encode = bool(args["batch_encode"])
     print("-" * 80)
     print("Sampling for: {0:s} set: {1:s} gpu: {2:d}".format(cfg_path, set_key, nn.gpuid))
     print("-" * 80)

@@ -81,9 +81,12 @@ if __name__ == "__main__":
     parser.add_argument("--nbest", help="a beam.py pickle: score its hypotheses instead of the references")
     parser.add_argument("--alignments", help="write the attention rows to this .npz")
     parser.add_argument("-b", "--batch", type=int, default=1, help="with --nbest: pack the hypotheses of U utterances into one call (default 1)")
+    parser.add_argument("--batch-encode", dest="batch_encode", action="store_true",
+                        help="encode the utterances of a call in one padded batch with per-row lengths instead of one by one (same encodings; effective with -b U)")
     args = vars(parser.parse_args())
     cfg_path, set_key = args["cfg_path"], args["S"]
     nn = NN(cfg_path)
+    nn.model.batch_encode = bool(args["batch_encode"])
     print("-" * 80)
     print("Scoring: {0:s} set: {1:s} gpu: {2:d}".format(cfg_path, set_key, nn.gpuid))
     print("-" * 80)
