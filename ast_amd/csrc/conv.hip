@@ -1,9 +1,13 @@
 // CNN front-end of the speech encoder (seq2seq.py:158-180):
-//   [Conv2D(nobias) -> BatchNorm(batch statistics) -> ReLU] x n, then the (T'',B,C*F') re-layout (Q9).
+//   [Conv2D(nobias) -> [max-pool] -> BatchNorm(batch statistics) -> ReLU] x n, then the (T'',B,C*F') re-layout (Q9).
 //
 // Data layout in HBM (all f32):
-//   layer 0 : X (B,T,D) [* noise] --im2col--> P0 [(b,f,t1)][kt*kf padded to 4]  (coalesced reads of the padded
-//             (T,D) frame matrix: one workgroup streams whole frame rows) -> Y0 = P0 W0^T  (MFMA GEMM)
+//   layer 0 : two paths (CnnRoute::direct0)
+//             direct : X (B,T,D) [* noise] -> Y0 by k_conv0_fwd_x3, a direct convolution on the bf16 matrix pipe (default arithmetic, the
+//                      shapes of conv0_direct_shape): no patch matrix; the kernel leaves the noisy input as XF[(b,f)][pt + T + pt][JG],
+//                      which the weight gradient reads as a zero-copy window matrix, and the layer's BatchNorm sums per tile
+//             im2col : X [* noise] --im2col--> P0 [(b,f,t1)][kt*kf padded to 4]  (coalesced reads of the padded (T,D) frame matrix: one
+//                      workgroup streams whole frame rows) -> Y0 = P0 W0^T  (MFMA GEMM); every other scheme or shape, pooled layer 0
 //   layer i : activations are kept channels-last and time-padded, HP[(b,f)][pt + T_i + pt][C_i]; because the
 //             frequency kernel/stride of layers >= 1 is 1, the im2col row of output (b,f,t) is the CONTIGUOUS
 //             window HP[(b,f)][t*st .. t*st+kt)[:] -- the conv runs as a zero-copy "window" GEMM (two-level row
@@ -12,6 +16,11 @@
 //             time-padded dY (transposed convolution without col2im scatter).
 //   BatchNorm: column statistics of the raw conv output [rows][C] in float64 atomics, then one fused
 //             scale/shift/ReLU pass that writes the next layer's padded layout (or the LSTM layout).
+//
+// Host code: every entry point plans (make_plan: geometry and workspace slices), then routes ONCE (cnn_route, under the call's PrecScope:
+// layer-0 path, fused layer-0 statistics, the forms of the sequence re-layout and of the last layer's BatchNorm backward, the effective
+// statistics exchange, who zeroes what), then runs a dispatcher (conv_fwd, astk_conv_bn_relu_bwd_sync) over one function per stage
+// (fwd_*, bwd_*); the stage functions read the plan, the route and the call's CnnCall and decide no path themselves.
 #include "common.h"
 #include <atomic>
 #include <mutex>
@@ -77,17 +86,22 @@ struct CnnPlan {
   size_t bytes;
 };
 
+// the direct layer-0 kernel's tile (k_conv0_fwd_x3, below): LDS row width, output steps per tile, 32-k MFMA steps
+constexpr int C0_JP = 20;
+constexpr int C0_TT = 80;
+constexpr int C0_NKS = 6;           // 32-k MFMA steps over kt * JP <= 192 (kt <= 9)
+
 // (0 when the padded input is shorter than the kernel: C's division truncates towards zero, -1 / 2 + 1 would come out as one output step)
 int conv_out(int n, int k, int s, int p) { return n + 2 * p < k ? 0 : (n + 2 * p - k) / s + 1; }
 
-int make_plan(const astk_cnn_desc* d, void* ws, CnnPlan& P) {
+// the descriptor's checks and every extent that follows from it alone
+int plan_geometry(const astk_cnn_desc* d, CnnPlan& P) {
   ASTK_CHECK_DESC(d, astk_cnn_desc);
   ASTK_CHECK(d && d->n_layers >= 1 && d->n_layers <= ASTK_MAX_CNN_LAYERS, "cnn: 1..%d layers", ASTK_MAX_CNN_LAYERS);
   ASTK_CHECK(d->B > 0 && d->T > 0 && d->D > 0, "cnn: bad input dims");
   P.n = d->n_layers; P.B = d->B; P.T = d->T; P.D = d->D;
   ASTK_CHECK(d->kf[0] >= 1 && d->kf[0] <= d->D && d->sf[0] >= 1, "cnn: bad layer-0 frequency kernel");
   int t = d->T, f = conv_out(d->D, d->kf[0], d->sf[0], 0);
-  size_t cmax = 0, rowsmax_c = 0;
   for (int i = 0; i < P.n; ++i) {
     ASTK_CHECK(d->kt[i] >= 1 && d->st[i] >= 1 && d->pt[i] >= 0 && d->C[i] >= 1, "cnn: bad layer %d", i);
     ASTK_CHECK(i == 0 || (d->kf[i] == 1 && d->sf[i] == 1), "cnn: layers >= 1 must have a (kt,1) kernel and frequency stride 1");
@@ -106,12 +120,15 @@ int make_plan(const astk_cnn_desc* d, void* ws, CnnPlan& P) {
     P.Tn[i] = t; P.Fn[i] = f;
     P.Cn[i] = d->C[i];
     P.rows[i] = d->B * f * t;
-    cmax = cmax > (size_t)d->C[i] ? cmax : (size_t)d->C[i];
-    size_t rc = (size_t)P.rows[i] * d->C[i];
-    rowsmax_c = rowsmax_c > rc ? rowsmax_c : rc;
   }
   P.K0 = d->kt[0] * d->kf[0];
   P.K0p = (P.K0 + 3) / 4 * 4;
+  return 0;
+}
+
+// geometry, then the workspace slices in their fixed order (ws == nullptr: sizes only)
+int make_plan(const astk_cnn_desc* d, void* ws, CnnPlan& P) {
+  ASTK_TRY(plan_geometry(d, P));
   Carver c(ws);
   P.P0 = c.take<float>((size_t)P.rowsc[0] * P.K0p);
   // direct layer-0 convolution (k_conv0_fwd_x3): the noisy input in frequency-blocked, time-padded form [(b, f)][pt + T + pt][JG], which
@@ -121,7 +138,7 @@ int make_plan(const astk_cnn_desc* d, void* ws, CnnPlan& P) {
   P.xf_rows = (d->T + 2 * d->pt[0] + 1) & ~1;      // (even: the group stride of the window view must be a multiple of 4 floats)
   P.XF = c.take<float>((size_t)d->B * P.Fc[0] * P.xf_rows * P.JG + 16);
   // fused layer-0 statistics of the direct kernel: one row [2][C] of float sums per tile (C0_TT output steps of one (b, f))
-  P.c0_tiles = d->B * P.Fc[0] * cdiv(P.Tc[0], 80);
+  P.c0_tiles = d->B * P.Fc[0] * cdiv(P.Tc[0], C0_TT);
   P.c0_part = c.take<float>((size_t)P.c0_tiles * 2 * P.Cn[0] + P.Cn[0]);
   size_t wd_max = 0;
   for (int i = 0; i < P.n; ++i) {
@@ -183,6 +200,8 @@ int make_plan(const astk_cnn_desc* d, void* ws, CnnPlan& P) {
     P.dWr[i] = c.take<float>(i == 0 ? (size_t)d->C[0] * std::max(P.K0p, (P.K0g + 3) & ~3) : (size_t)P.Cn[i] * d->kt[i] * P.Cn[i - 1]);
   P.zero_fwd_bytes = off_abwd - off_afwd;       // forward: the forward slots and the statistics
   P.zero_bwd_bytes = c.off - off_stat;          // backward: statistics, backward slots, dWr scratch
+  size_t rowsmax_c = 0;
+  for (int i = 0; i < P.n; ++i) rowsmax_c = std::max(rowsmax_c, (size_t)P.rows[i] * P.Cn[i]);
   P.G = c.take<float>(rowsmax_c);
   // one phase-weight buffer per stride phase of a grouped dgrad launch
   int st_max = 1;
@@ -227,9 +246,6 @@ __global__ __launch_bounds__(256) void k_im2col0(const float* __restrict__ X, co
 // 32 w .. 32 w + 31, their weight fragments resident in registers as three bf16 planes); Y^T = W P^T, so a lane ends up with four
 // CONSECUTIVE channels of one output row (16-byte stores).  It also leaves the noisy input in the frequency-blocked, time-padded f32
 // form XF[(b, f)][pt + T + pt][JG] that the weight gradient reads as a zero-copy window matrix (the P0 patches are not built at all).
-constexpr int C0_JP = 20;
-constexpr int C0_TT = 80;
-constexpr int C0_NKS = 6;           // 32-k MFMA steps over kt * JP <= 192 (kt <= 9)
 static int conv0_win_elems(int st) { return st * C0_JP * (C0_TT - 1) + 32 * C0_NKS + 40; }    // (+ the rows the last tile of a group owns in XF)
 // A pooled layer 0 takes im2col + GEMM: its BatchNorm normalises the POOLED rows, the direct kernel's fused statistics are sums over the
 // un-pooled output.  Windows 0 and 1 mean no pooling; -1 (the whole extent) pools like any window > 1 (make_plan).
@@ -255,23 +271,28 @@ struct Conv0PathRecord { const void* ws; int direct; int bwd_clean; };
 static std::mutex g_conv0_mu;
 static Conv0PathRecord g_conv0_ring[64];
 static unsigned g_conv0_next = 0;
+static Conv0PathRecord* conv0_ring_find(const void* ws) {      // (the caller holds g_conv0_mu)
+  for (auto& r : g_conv0_ring)
+    if (r.ws == ws) return &r;
+  return nullptr;
+}
 static void conv0_path_record(const void* ws, bool direct, bool bwd_clean) {
   std::lock_guard<std::mutex> lock(g_conv0_mu);
-  for (auto& r : g_conv0_ring)
-    if (r.ws == ws) { r.direct = direct ? 1 : 0; r.bwd_clean = bwd_clean ? 1 : 0; return; }
-  g_conv0_ring[g_conv0_next++ % 64] = Conv0PathRecord{ws, direct ? 1 : 0, bwd_clean ? 1 : 0};
+  Conv0PathRecord* r = conv0_ring_find(ws);
+  if (!r) r = &g_conv0_ring[g_conv0_next++ % 64];
+  *r = Conv0PathRecord{ws, direct ? 1 : 0, bwd_clean ? 1 : 0};
 }
 static int conv0_path_lookup(const void* ws) {      // -1: no forward call recorded for this workspace
   std::lock_guard<std::mutex> lock(g_conv0_mu);
-  for (auto& r : g_conv0_ring)
-    if (r.ws == ws) return r.direct;
-  return -1;
+  const Conv0PathRecord* r = conv0_ring_find(ws);
+  return r ? r->direct : -1;
 }
 static bool conv_take_bwd_clean(const void* ws) {   // true once per marked forward call
   std::lock_guard<std::mutex> lock(g_conv0_mu);
-  for (auto& r : g_conv0_ring)
-    if (r.ws == ws) { const bool c = r.bwd_clean != 0; r.bwd_clean = 0; return c; }
-  return false;
+  Conv0PathRecord* r = conv0_ring_find(ws);
+  const bool c = r && r->bwd_clean != 0;
+  if (r) r->bwd_clean = 0;
+  return c;
 }
 // Every thread of the calling grid: zero `bytes` (a multiple of 4) from the 16-byte aligned p.  A fill launch of its own costs ~5 us of
 // stream time; the kernels in front of the consumers do it on their way in / out instead.
@@ -1191,11 +1212,424 @@ int ksplit_for(long tiles, long K) {
   return (int)s;
 }
 
+// ------------------------------------------------------------------ the route of a call
+// Every path decision of one forward or backward call, taken ONCE from the descriptor, the plan's geometry and the knobs, after the call's
+// PrecScope is in force (conv0_direct reads the thread's arithmetic).  cnn_route is the only caller of conv0_direct (and through it of
+// conv0_direct_shape and conv0_pooled), of seq_bwd_applicable and of the conv.direct0 / conv.seq_fwd / conv.seq_bwd knobs; the dispatchers,
+// the stage functions, the path record and the backward's refusal check read the struct.  (The block-count knobs conv.seq_stats_blocks /
+// conv.seq_apply_blocks size a grid and choose no path: read at their launches.)
+enum SeqFwd { SEQ_FWD_TILED, SEQ_FWD_PLAIN, SEQ_FWD_MASKED };
+struct CnnRoute {
+  bool direct0;       // layer 0: k_conv0_fwd_x3 and the window weight gradient over XF | im2col + GEMM over P0 (both passes)
+  bool c0_stats;      // forward: the direct kernel leaves per-tile BatchNorm sums, k_colstats_tiles adds them up
+  SeqFwd seq_fwd;     // forward: the last launch -- k_bn_relu_to_seq_tiled | k_bn_relu_to_seq | (row_len) k_bn_relu_to_seq_len; MASKED also
+                      // puts k_bn_relu_rows_len in the place of k_bn_relu_rows
+  bool seq_bwd;       // backward: the last layer's BatchNorm backward reads d_out itself (k_bn_bwd_*_seq) | k_seq_to_rows + the row kernels
+                      // (shapes the seq kernels do not take, conv.seq_bwd 0, and the kill-units test hook, which edits G)
+  astk_stat_exchange_fn exchange;      // the statistics exchange in effect: null with one rank and without BatchNorm
+  int world;          // ranks whose rows the statistics cover (1 without exchange)
+  bool fused_fin;     // forward: the statistics kernel's last block finalizes (training without exchange) | k_bn_finalize
+  // who zeroes what: the forward's region (maximum slots; training: and the statistics), zero_fwd bytes from P.zero_fwd_from, by the
+  // direct layer-0 kernel on its way in, else (fwd_fill) by a fill launch in front of layer 0; the backward's region (statistics, backward
+  // maximum slots, dWr scratch), P.zero_bwd_bytes from zero_bwd_from, by the forward's last kernel on its way out (training; null = not
+  // at all), which spares the backward call its fill (Conv0PathRecord::bwd_clean)
+  bool fwd_fill;
+  size_t zero_fwd;
+  void* zero_bwd_from;
+};
+CnnRoute cnn_route(const astk_cnn_desc* d, const CnnPlan& P, int train, astk_stat_exchange_fn exchange, int world, const int* row_len) {
+  CnnRoute R;
+  const int l = P.n - 1;
+  const bool seq_shape = seq_bwd_applicable(P.Cn[l], P.Fn[l], (long)P.Tn[l] * P.B);
+  R.direct0 = conv0_direct(d);
+  R.c0_stats = R.direct0 && train && !d->no_bn;
+  R.seq_fwd = row_len ? SEQ_FWD_MASKED : (tune_on(TUNE_CONV_SEQ_FWD) && seq_shape) ? SEQ_FWD_TILED : SEQ_FWD_PLAIN;
+  R.seq_bwd = tune_on(TUNE_CONV_SEQ_BWD) && seq_shape;
+#ifdef ASTK_TEST_HOOKS
+  if (g_kill_n > 0) R.seq_bwd = false;
+#endif
+  R.exchange = (world == 1 || d->no_bn) ? nullptr : exchange;
+  R.world = R.exchange ? world : 1;
+  R.fused_fin = train && !R.exchange;
+  R.fwd_fill = !R.direct0;
+  R.zero_fwd = train ? P.zero_fwd_bytes : P.zero_fwd_amax_bytes;
+  R.zero_bwd_from = train ? (void*)P.stat[0] : nullptr;
+  return R;
+}
+
+// What a call was given, for the stage functions (forward: X .. out_len; backward: Gr, d_out).
+struct CnnCall {
+  const astk_cnn_desc* d;
+  const astk_cnn_layer_params* L;
+  const astk_cnn_layer_grads* Gr;
+  hipStream_t s;
+  void* user;               // of the statistics exchange
+  const float *X, *noise;
+  float* out;
+  int train;
+  const int* row_len;       // device, B frame counts (astk_conv_bn_relu_fwd_rows; evaluation mode) | null
+  int* out_len;
+  const float* d_out;
+};
+
+// ------------------------------------------------------------------ forward stages
+// layer 0, direct convolution (bf16x3 on the matrix pipe): zeroes the forward's region on its way in, leaves XF for the weight gradient and,
+// under R.c0_stats, the layer's BatchNorm statistics as per-tile sums
+int fwd_layer0_direct(const CnnPlan& P, const CnnRoute& R, const CnnCall& c) {
+  const astk_cnn_desc* d = c.d;
+  const int tiles_t = cdiv(P.Tc[0], C0_TT), total = P.B * P.Fc[0] * tiles_t, win = conv0_win_elems(d->st[0]);
+  const int grid = std::min(total, 2 * device_cu_count());
+  const size_t lds0 = std::max((size_t)3 * win * sizeof(unsigned short), (size_t)P.Cn[0] * P.K0 * sizeof(float));
+  hipLaunchKernelGGL(k_conv0_fwd_x3, dim3(grid), dim3(256), lds0, c.s, c.X, c.noise, c.L[0].W, P.YC[0], P.XF, P.B, P.T, P.D, P.Fc[0], P.Tc[0],
+                     P.Cn[0], d->kt[0], d->kf[0], d->st[0], d->sf[0], d->pt[0], P.JG, P.xf_rows, tiles_t, total, win, P.zero_fwd_from, R.zero_fwd,
+                     R.c0_stats ? P.c0_part : nullptr);
+  ASTK_LAUNCH_CHECK();
+  return 0;
+}
+// layer 0, im2col + GEMM
+int fwd_layer0_im2col(const CnnPlan& P, const CnnCall& c) {
+  const astk_cnn_desc* d = c.d;
+  hipLaunchKernelGGL(k_im2col0, dim3(P.Tc[0], P.B), dim3(256), 0, c.s, c.X, c.noise, P.P0, P.B, P.T, P.D, P.Fc[0], P.Tc[0], d->kt[0], d->kf[0],
+                     d->st[0], d->sf[0], d->pt[0], P.K0p);
+  ASTK_LAUNCH_CHECK();
+  ASTK_TRY(copy2d_f32(P.Wr[0], P.K0p, c.L[0].W, P.K0, P.Cn[0], P.K0, P.K0p, c.s));
+  return gemm_launch(GEMM_NT, gemm_args(P.rowsc[0], P.Cn[0], P.K0p, mat(P.P0, P.K0p), mat(P.Wr[0], P.K0p), P.YC[0], P.Cn[0]), c.s);
+}
+// layer i >= 1: the weight re-pack (which also folds the activations' strided maximum slot), then the window GEMM (K6)
+int fwd_window_gemm(const CnnPlan& P, const CnnCall& c, int i) {
+  const int C = P.Cn[i], Ci = P.Cn[i - 1], KT = c.d->kt[i];
+  hipLaunchKernelGGL(k_repack_w, dim3(gridn((size_t)C * Ci * KT / 8)), dim3(256), 0, c.s, c.L[i].W, P.Wr[i], C, Ci, KT, P.a_wr[i],
+                     (const unsigned long long*)P.a_hp_s[i - 1], P.a_hp[i - 1]);
+  ASTK_LAUNCH_CHECK();
+  const long prow = (long)(P.Tn[i - 1] + 2 * P.padA[i - 1]) * Ci;
+  GemmArgs g = gemm_args(P.rowsc[i], C, KT * Ci, mat2(P.HP[i - 1], P.Tc[i], prow, (long)c.d->st[i] * Ci), mat(P.Wr[i], (long)KT * Ci), P.YC[i], C);
+  // (both operands' maxima were taken by the kernels that wrote them: no absolute-maximum pass in front of this launch)
+  return gemm_launch(GEMM_NT, with_amax_b(with_amax_a(lowp(g), P.a_hp[i - 1]), P.a_wr[i]), c.s);
+}
+// old-path extra: max-pool in front of the BatchNorm (enc_dec.py:444-456)
+int fwd_pool(const CnnPlan& P, const CnnCall& c, int i) {
+  const int C = P.Cn[i];
+  hipLaunchKernelGGL(k_maxpool, dim3(gridn((size_t)P.rows[i] * C / 4)), dim3(256), 0, c.s, P.YC[i], P.Y[i], P.IDX[i], P.B, P.Fc[i], P.Tc[i], P.Fn[i],
+                     P.Tn[i], P.pwf[i], P.pwt[i], C);
+  ASTK_LAUNCH_CHECK();
+  return 0;
+}
+// scale / shift of layer i into P.bn[i].  no_bn: from the bias.  Training: batch statistics (layer 0 under R.c0_stats: the tiles' sums came
+// with the convolution -- 6.5 MB to add up instead of 262), [exchange], and the finalize either by the statistics kernel's last block
+// (R.fused_fin) or as a launch of its own; evaluation: the finalize launch alone, from the running statistics.
+int fwd_bn_scale_shift(const CnnPlan& P, const CnnRoute& R, const CnnCall& c, int i) {
+  const astk_cnn_desc* d = c.d;
+  const astk_cnn_layer_params& L = c.L[i];
+  const int C = P.Cn[i], rows = P.rows[i];
+  if (d->no_bn) {
+    ASTK_CHECK(L.bias, "conv_bn_relu_fwd: no_bn needs a bias (layer %d)", i);
+    hipLaunchKernelGGL(k_bias_affine, dim3(cdiv(C, 256)), dim3(256), 0, c.s, L.bias, C, P.bn[i]);
+    ASTK_LAUNCH_CHECK();
+    return 0;
+  }
+  BnFinalize fin{nullptr, (double)rows * R.world, L.gamma, L.beta, L.avg_mean, L.avg_var, P.bn[i], d->bn_eps, d->bn_decay};
+  if (c.train) {
+    BnFinalize f2 = fin;
+    if (R.fused_fin) f2.ctr = P.fin_ctr + 64 * i;
+    if (i == 0 && R.c0_stats)
+      hipLaunchKernelGGL(k_colstats_tiles, colreduce_grid(P.c0_tiles, C), dim3(256), 0, c.s, P.c0_part, P.c0_tiles, C, cdiv(P.Tc[0], C0_TT), P.Tc[0],
+                         P.stat[i], f2);
+    else
+      hipLaunchKernelGGL(k_colstats, colreduce_grid(rows, C), dim3(256), 0, c.s, P.Y[i], rows, C, P.stat[i], f2);
+    ASTK_LAUNCH_CHECK();
+    if (R.exchange) ASTK_CHECK(R.exchange(c.user, P.stat[i], 2 * C, (void*)c.s) == 0, "conv_bn_relu_fwd: statistics exchange failed (layer %d)", i);
+  }
+  if (!R.fused_fin) {
+    hipLaunchKernelGGL(k_bn_finalize, dim3(cdiv(C, 256)), dim3(256), 0, c.s, P.stat[i], C, fin, c.train);
+    ASTK_LAUNCH_CHECK();
+  }
+  return 0;
+}
+// BatchNorm + ReLU of a layer below the last into the next layer's padded layout (the kernels zero the pad rows of HP[i] themselves)
+int fwd_to_rows(const CnnPlan& P, const CnnRoute& R, const CnnCall& c, int i) {
+  const int C = P.Cn[i], rows = P.rows[i];
+  const dim3 grid(gridn((size_t)rows * C / 4));
+  if (R.seq_fwd == SEQ_FWD_MASKED)
+    hipLaunchKernelGGL(k_bn_relu_rows_len, grid, dim3(256), 0, c.s, P.Y[i], P.bn[i], P.HP[i], rows, C, P.Tn[i], P.padA[i], P.a_hp_s[i], c.row_len,
+                       rows_geom(c.d), i, P.Fn[i]);
+  else
+    hipLaunchKernelGGL(k_bn_relu_rows, grid, dim3(256), 0, c.s, P.Y[i], P.bn[i], P.HP[i], rows, C, P.Tn[i], P.padA[i], P.a_hp_s[i]);
+  ASTK_LAUNCH_CHECK();
+  return 0;
+}
+// BatchNorm + ReLU of the last layer into the (T'', B, C*F') frames: the call's last launch, which (training) zeroes the backward's region
+int fwd_to_seq(const CnnPlan& P, const CnnRoute& R, const CnnCall& c) {
+  const int i = P.n - 1, C = P.Cn[i], F = P.Fn[i], B = P.B;
+  if (R.seq_fwd == SEQ_FWD_TILED) {
+    const int pp = seq_pp(F), gy = std::max(1, std::min(2048 / (C / SEQ_CH), cdiv(P.Tn[i] * B, pp)));
+    hipLaunchKernelGGL(k_bn_relu_to_seq_tiled, dim3(C / SEQ_CH, gy), dim3(256), (size_t)pp * SEQ_CH * F * sizeof(float), c.s, P.Y[i], P.bn[i], c.out, B, F,
+                       P.Tn[i], C, pp, P.a_out, R.zero_bwd_from, P.zero_bwd_bytes);
+  } else {
+    const size_t shm = (size_t)C * F * sizeof(float);
+    ASTK_CHECK(shm <= 64 * 1024, "cnn: C*F' too large for the re-layout tile (%zu bytes)", shm);
+    if (R.seq_fwd == SEQ_FWD_MASKED)
+      hipLaunchKernelGGL(k_bn_relu_to_seq_len, dim3(P.Tn[i], B), dim3(256), shm, c.s, P.Y[i], P.bn[i], c.out, B, F, P.Tn[i], C, P.a_out, c.row_len,
+                         rows_geom(c.d), c.out_len);
+    else
+      hipLaunchKernelGGL(k_bn_relu_to_seq, dim3(P.Tn[i], B), dim3(256), shm, c.s, P.Y[i], P.bn[i], c.out, B, F, P.Tn[i], C, P.a_out, R.zero_bwd_from,
+                         P.zero_bwd_bytes);
+  }
+  ASTK_LAUNCH_CHECK();
+  return 0;
+}
+// astk_conv_bn_relu_fwd_rows: no pooled layer, and the lengths are read back before anything is launched -- a row the library would refuse
+// alone is refused here
+int fwd_check_row_len(const CnnPlan& P, const CnnCall& c) {
+  const astk_cnn_desc* d = c.d;
+  for (int i = 0; i < P.n; ++i) ASTK_CHECK(!P.pooled[i], "conv_bn_relu_fwd_rows: pooled layers (cnn_pool) take no row lengths (layer %d)", i);
+  ASTK_CHECK(P.B <= ASTK_ENCODE_ROWS_MAX, "conv_bn_relu_fwd_rows: at most %d rows, got %d", ASTK_ENCODE_ROWS_MAX, P.B);
+  int32_t len[ASTK_ENCODE_ROWS_MAX];
+  ASTK_CHECK(hipMemcpyAsync(len, c.row_len, (size_t)P.B * sizeof(int32_t), hipMemcpyDeviceToHost, c.s) == hipSuccess &&
+             hipStreamSynchronize(c.s) == hipSuccess, "conv_bn_relu_fwd_rows: reading row_len failed");
+  for (int b = 0; b < P.B; ++b) {
+    ASTK_CHECK(len[b] >= 1 && len[b] <= P.T, "conv_bn_relu_fwd_rows: row_len[%d] = %d outside 1..T = %d", b, len[b], P.T);
+    int t = len[b];
+    for (int i = 0; i < P.n; ++i) {
+      t = conv_out(t, d->kt[i], d->st[i], d->pt[i]);
+      ASTK_CHECK(t >= 1, "conv_bn_relu_fwd_rows: row %d (%d frames) is too short for layer %d", b, len[b], i);
+    }
+  }
+  return 0;
+}
+// The forward pass of every entry point.  c.row_len (checked here, against the call's one plan): the two activation-writing launches are
+// the masked kernels; null: the call of always.
+int conv_fwd(const CnnCall& c, void* ws, size_t ws_bytes, astk_stat_exchange_fn exchange, int world) {
+  const astk_cnn_desc* d = c.d;
+  ASTK_CHECK_DESC(d, astk_cnn_desc);
+  PrecScope prec_scope(d->precision, d->gemm_operands);
+  GemmForwardScope forward_scope;      // split tiles of this op's products have at most two contributors (reproducible forward pass)
+  gemm_amax_step_boundary(c.s);       // the first op of a step: no operand-maximum handle is live here
+  ASTK_CHECK(world >= 1, "conv_bn_relu_fwd: world %d", world);
+  CnnPlan P;
+  ASTK_TRY(make_plan(d, ws, P));
+  if (c.row_len) ASTK_TRY(fwd_check_row_len(P, c));      // (in front of the size check: a pooled stack is refused as such, whatever its workspace)
+  ASTK_CHECK(ws && ws_bytes >= P.bytes, "conv_bn_relu_fwd: workspace too small (%zu < %zu)", ws_bytes, P.bytes);
+  ASTK_CHECK(c.X && c.out && c.L, "conv_bn_relu_fwd: null pointer");
+  const CnnRoute R = cnn_route(d, P, c.train, exchange, world, c.row_len);
+  // the statistics of every layer (train) and the maximum slots the producing kernels fill: one fill (the direct layer-0 kernel does it on
+  // its way in)
+  if (R.fwd_fill) ASTK_TRY(fill_zero(P.zero_fwd_from, R.zero_fwd, c.s));
+  // (the layer-0 path is recorded now -- the backward must refuse a workspace whose forward took the other path even if this call fails
+  //  half-way --, the "backward region is clean" mark only behind the LAST launch below: a forward call that fails before its last kernel
+  //  was enqueued must not leave a mark that spares the backward its own zero fill; round-5 advice)
+  conv0_path_record(ws, R.direct0, false);
+  ASTK_TRY(R.direct0 ? fwd_layer0_direct(P, R, c) : fwd_layer0_im2col(P, c));
+  for (int i = 0; i < P.n; ++i) {
+    if (i > 0) ASTK_TRY(fwd_window_gemm(P, c, i));
+    if (P.pooled[i]) ASTK_TRY(fwd_pool(P, c, i));
+    ASTK_TRY(fwd_bn_scale_shift(P, R, c, i));
+    ASTK_TRY(i < P.n - 1 ? fwd_to_rows(P, R, c, i) : fwd_to_seq(P, R, c));
+  }
+  if (R.zero_bwd_from) conv0_path_record(ws, R.direct0, true);      // every launch of the call went out: its last kernel zeroes the backward's region
+  return 0;
+}
+
+// ------------------------------------------------------------------ backward stages
+// the last layer's upstream gradient re-ordered into rows (G), for the row-layout BatchNorm backward
+int bwd_seq_to_rows(const CnnPlan& P, const CnnCall& c) {
+  const int i = P.n - 1;
+  const size_t shm = (size_t)P.Cn[i] * P.Fn[i] * sizeof(float);
+  hipLaunchKernelGGL(k_seq_to_rows, dim3(P.Tn[i], P.B), dim3(256), shm, c.s, c.d_out, P.G, P.B, P.Fn[i], P.Tn[i], P.Cn[i]);
+  ASTK_LAUNCH_CHECK();
+  return 0;
+}
+// What k_bn_bwd_apply and k_bn_bwd_apply_seq are told alike.  Pooled layers: the gradient wrt the POOLED output goes to DYP (plain rows),
+// k_unpool spreads it over the padded dY of the convolution and takes its maximum.  dgamma / dbeta: the apply kernel adds them unless an
+// exchange took them from the local sums first (k_bn_param_grads) or there is no BatchNorm.  no_bn: the ReLU mask alone -- scale 1 and a
+// zero 1/m switch the BatchNorm terms off.
+struct BnApplyArgs {
+  float* dY;
+  int padF, padB;
+  float *dgamma, *dbeta;
+  float invm;
+  unsigned long long* amax;
+};
+BnApplyArgs bn_apply_args(const CnnPlan& P, const CnnRoute& R, const CnnCall& c, int i) {
+  const bool pooled = P.pooled[i], own_grads = !R.exchange && !c.d->no_bn;
+  BnApplyArgs a;
+  a.dY = pooled ? P.DYP[i] : P.DY[i];
+  a.padF = pooled ? 0 : P.dF[i];
+  a.padB = pooled ? 0 : P.dB[i];
+  a.dgamma = own_grads ? c.Gr[i].dgamma : nullptr;
+  a.dbeta = own_grads ? c.Gr[i].dbeta : nullptr;
+  a.invm = c.d->no_bn ? 0.f : 1.f / ((float)P.rows[i] * R.world);
+  a.amax = (i > 0 && !pooled) ? P.a_dy_s[i] : nullptr;
+  return a;
+}
+// ReLU + BatchNorm backward of layer i: G (or, seq: d_out), the gradient wrt the post-ReLU output -> DY[i], the gradient wrt the raw
+// convolution output, time-padded for the products below.  Statistics; [exchange: dgamma / dbeta from the local sums, then the
+// exchange]; [pooled: pad rows of DY -- un-pooled layers' apply kernels zero the pads of the dY they write]; apply; [un-pool]; [no_bn: the
+// column sums of g are the bias gradient].
+int bwd_bn_relu(const CnnPlan& P, const CnnRoute& R, const CnnCall& c, int i) {
+  const astk_cnn_desc* d = c.d;
+  const int C = P.Cn[i], rows = P.rows[i], B = P.B, Fn = P.Fn[i], Tn = P.Tn[i];
+  const bool seq = R.seq_bwd && i == P.n - 1;
+  const int seq_gx = C / SEQ_CH;
+  auto seq_grid = [&](TuneKey blocks) { return dim3(seq_gx, std::max(1, std::min((int)tune(blocks) / seq_gx, cdiv(Tn * B, seq_pp(Fn))))); };
+  if (seq) {
+    hipLaunchKernelGGL(k_bn_bwd_stats_seq, seq_grid(TUNE_CONV_SEQ_STATS_BLOCKS), dim3(256), seq_tile_bytes(Fn), c.s, P.Y[i], c.d_out, P.bn[i], B, Fn, Tn, C, seq_pp(Fn),
+                       P.stat[i]);
+  } else {
+    hipLaunchKernelGGL(k_bn_bwd_stats, colreduce_grid(rows, C), dim3(256), 0, c.s, P.Y[i], P.G, P.bn[i], rows, C, P.stat[i]);
+  }
+  ASTK_LAUNCH_CHECK();
+  if (R.exchange) {
+    hipLaunchKernelGGL(k_bn_param_grads, dim3(cdiv(C, 256)), dim3(256), 0, c.s, P.stat[i], C, c.Gr[i].dgamma, c.Gr[i].dbeta);
+    ASTK_LAUNCH_CHECK();
+    ASTK_CHECK(R.exchange(c.user, P.stat[i], 2 * C, (void*)c.s) == 0, "conv_bn_relu_bwd: statistics exchange failed (layer %d)", i);
+  }
+  const int pads = P.dF[i] + P.dB[i];
+  if (pads > 0 && P.pooled[i]) {
+    hipLaunchKernelGGL(k_zero_pads, dim3(gridn((size_t)B * P.Fc[i] * pads * C / 4)), dim3(256), 0, c.s, P.DY[i], B * P.Fc[i], P.Tc[i], P.dF[i], P.dB[i], C);
+    ASTK_LAUNCH_CHECK();
+  }
+  const BnApplyArgs a = bn_apply_args(P, R, c, i);
+  if (seq) {
+    hipLaunchKernelGGL(k_bn_bwd_apply_seq, seq_grid(TUNE_CONV_SEQ_APPLY_BLOCKS), dim3(256), seq_tile_bytes(Fn), c.s, P.Y[i], c.d_out, P.bn[i], P.stat[i], a.dY, B, Fn, Tn, C,
+                       seq_pp(Fn), a.padF, a.padB, a.dgamma, a.dbeta, a.invm, a.amax);
+  } else {
+    hipLaunchKernelGGL(k_bn_bwd_apply, dim3(gridn((size_t)rows * C / 4)), dim3(256), 0, c.s, P.Y[i], P.G, P.bn[i], P.stat[i], a.dY, rows, C, Tn, a.padF,
+                       a.padB, a.dgamma, a.dbeta, a.invm, a.amax);
+  }
+  ASTK_LAUNCH_CHECK();
+  if (P.pooled[i]) {
+    hipLaunchKernelGGL(k_unpool, dim3(gridn((size_t)P.rowsc[i] * C / 4)), dim3(256), 0, c.s, P.DYP[i], P.IDX[i], P.DY[i], B, P.Fc[i], P.Tc[i], Fn, Tn,
+                       P.pwf[i], P.pwt[i], C, P.dF[i], P.dB[i], i > 0 ? P.a_dy_s[i] : nullptr);
+    ASTK_LAUNCH_CHECK();
+  }
+  if (d->no_bn) {
+    ASTK_CHECK(c.Gr[i].dbias, "conv_bn_relu_bwd: no_bn needs a bias gradient (layer %d)", i);
+    hipLaunchKernelGGL(k_bias_grad, dim3(cdiv(C, 256)), dim3(256), 0, c.s, P.stat[i], C, c.Gr[i].dbias);
+    ASTK_LAUNCH_CHECK();
+  }
+  return 0;
+}
+// The re-packed weight gradients on their way back into the parameters' layouts: gathered per layer, one k_unpack_dw launch behind the loop
+struct UnpackList {
+  UnpackJobs j;
+  size_t max_elems = 0;
+  void add(const float* src, float* dW, int Co, int Ci, int KT, int JG, int ldg) {
+    const int k = j.n++;
+    j.src[k] = src; j.dW[k] = dW; j.Co[k] = Co; j.Ci[k] = Ci; j.KT[k] = KT; j.JG[k] = JG; j.ldg[k] = ldg;
+    max_elems = std::max(max_elems, (size_t)Co * Ci * KT);
+  }
+};
+// weight gradient of layer 0, direct path: dWg[C0][kt * JG] = DY0^T XF-windows -- the patches as a zero-copy window matrix over XF: row
+// (b, f, t1) = the kt * JG floats from row st * t1 of group (b, f) on
+int bwd_wgrad0_direct(const CnnPlan& P, const CnnCall& c, UnpackList& U) {
+  const astk_cnn_desc* d = c.d;
+  const int C = P.Cn[0], ldg = (P.K0g + 3) & ~3;
+  MatView Bm = mat2(P.XF, P.Tc[0], (long)P.xf_rows * P.JG, (long)d->st[0] * P.JG);
+  ASTK_TRY(gemm_launch(GEMM_TN, gemm_args(C, P.K0g, P.rowsc[0], mat(P.DY[0], C), Bm, P.dWr[0], ldg, nullptr, GEMM_ATOMIC, ksplit_for(1, P.rowsc[0])), c.s));
+  U.add(P.dWr[0], c.Gr[0].dW, C, d->kf[0], d->kt[0], P.JG, ldg);
+  return 0;
+}
+// ... im2col path: dW0p[C0][K0p] = DY0^T P0, added to dW at once
+int bwd_wgrad0_im2col(const CnnPlan& P, const CnnCall& c) {
+  const int C = P.Cn[0];
+  ASTK_TRY(gemm_launch(GEMM_TN, gemm_args(C, P.K0p, P.rowsc[0], mat(P.DY[0], C), mat(P.P0, P.K0p), P.dWr[0], P.K0p, nullptr, GEMM_ATOMIC,
+                                          ksplit_for(1, P.rowsc[0])), c.s));
+  return add2d_f32(c.Gr[0].dW, P.K0, P.dWr[0], P.K0p, C, P.K0, c.s);
+}
+// The input gradient of layer i >= 1: one window GEMM per stride phase rho of the input position t_in = rho + st * j over the padded dY,
+// against that phase's weights Wd.  The padded dY feeds the weight gradient and every phase product; its maximum (fp16x2 GEMM scale) was
+// taken by the kernel that wrote it, into the STRIDED slot a_dy_s[i].  The first k_phase_w launch of the layer folds that slot into the
+// plain a_dy[i] (hence: in front of the weight gradient); every product queued here is launched behind such a launch and reads a_dy[i];
+// when no phase kernel ran (no tap reaches any phase) the weight gradient reads the strided slot itself -- dy_amax().
+struct DgradPhases {
+  GemmArgs ph[GEMM_GROUP_MAX];      // the products queued for the next grouped launch
+  int nph = 0;
+  PhaseWJobs pj;                    // the phase weights not yet built (wd buffers nph - pj.n .. nph - 1)
+  int na_max = 0;
+  bool folded = false;
+  DgradPhases() { pj.n = 0; }
+  int launch_weights(const CnnPlan& P, const CnnCall& c, int i) {
+    if (pj.n == 0) return 0;
+    const int C = P.Cn[i], Ci = P.Cn[i - 1];
+    hipLaunchKernelGGL(k_phase_w, dim3(gridn((size_t)Ci * na_max * C / 8), pj.n), dim3(256), 0, c.s, c.L[i].W, pj, C, Ci, c.d->kt[i], c.d->st[i],
+                       folded ? nullptr : (const unsigned long long*)P.a_dy_s[i], P.a_dy[i]);
+    folded = true;
+    pj.n = 0;
+    na_max = 0;
+    ASTK_LAUNCH_CHECK();
+    return 0;
+  }
+  int launch_products(const CnnCall& c) {
+    if (nph > 0) ASTK_TRY(gemm_launch_group(GEMM_NT, ph, nph, c.s));
+    nph = 0;
+    return 0;
+  }
+  const unsigned long long* dy_amax(const CnnPlan& P, int i) const { return folded ? P.a_dy[i] : P.a_dy_s[i]; }
+};
+// dgrad, part 1: gathers the phases' weights and products and launches the weights (more phases than wd buffers: a flush of both in
+// between); the products still queued in D go out behind the weight gradient
+int bwd_dgrad_phases(const CnnPlan& P, const CnnCall& c, int i, DgradPhases& D) {
+  const astk_cnn_desc* d = c.d;
+  const int C = P.Cn[i], Ci = P.Cn[i - 1], KT = d->kt[i], st = d->st[i], pt = d->pt[i], Tin = P.Tn[i - 1];
+  const long dyrow = (long)(P.Tc[i] + P.dF[i] + P.dB[i]) * C;      // per (b,f) group of the padded dY
+  for (int rho = 0; rho < st && rho < Tin; ++rho) {
+    const int r = (rho + pt) % st;
+    const int na = (KT - r + st - 1) / st;
+    if (na <= 0) continue;      // no tap reaches this phase: gradient is zero
+    const int nj = (Tin - rho + st - 1) / st;
+    const int q0 = (rho + pt) / st;
+    if (D.nph == P.wd_copies) {      // (more phases than buffers: flush)
+      ASTK_TRY(D.launch_weights(P, c, i));
+      ASTK_TRY(D.launch_products(c));
+    }
+    float* wd = P.Wd + (size_t)D.nph * P.wd_stride;
+    // (a_wd[k] is zeroed once per backward call: a slot that is reused -- more phases than buffers, a deeper stack -- keeps the larger
+    //  of its users' maxima, i.e. a slightly conservative scale for phase weights of similar magnitude)
+    PhaseWJobs& pj = D.pj;
+    pj.wd[pj.n] = wd; pj.r[pj.n] = r; pj.na[pj.n] = na; pj.amax[pj.n] = P.a_wd[D.nph];
+    ++pj.n;
+    D.na_max = std::max(D.na_max, na);
+    const long start = (long)(q0 - na + 1 + P.dF[i]);
+    ASTK_CHECK(start >= 0, "cnn dgrad: negative window start");
+    GemmArgs g = gemm_args(P.B * P.Fc[i] * nj, Ci, na * C, mat2(P.DY[i] + start * C, nj, dyrow, C), mat(wd, (long)na * C), P.G + (long)rho * Ci, Ci);
+    g.c_tn = nj;
+    g.c_sg = (long)Tin * Ci;
+    g.c_st = (long)st * Ci;
+    D.ph[D.nph] = with_amax_b(with_amax_a(lowp(g), P.a_dy[i]), P.a_wd[D.nph]);
+    ++D.nph;
+  }
+  return D.launch_weights(P, c, i);
+}
+// weight gradient of layer i >= 1: dWr[co][kt*Ci+ci] = sum_rows DY[row][co] * window(row)[k]  (the activations' maximum was taken by
+// k_bn_relu_rows in the forward pass)
+int bwd_wgrad(const CnnPlan& P, const CnnCall& c, int i, const unsigned long long* dy_amax, UnpackList& U) {
+  const int C = P.Cn[i], Ci = P.Cn[i - 1], KT = c.d->kt[i];
+  const long dyrow = (long)(P.Tc[i] + P.dF[i] + P.dB[i]) * C;       // per (b,f) group of the padded dY
+  const long hprow = (long)(P.Tn[i - 1] + 2 * P.padA[i - 1]) * Ci;  // per (b,f) group of HP[i-1]
+  MatView A = mat2(P.DY[i] + (long)P.dF[i] * C, P.Tc[i], dyrow, C);
+  MatView Bm = mat2(P.HP[i - 1], P.Tc[i], hprow, (long)c.d->st[i] * Ci);
+  const long tiles = (long)cdiv(C, 128) * cdiv(KT * Ci, 128);
+  GemmArgs g = gemm_args(C, KT * Ci, P.rowsc[i], A, Bm, P.dWr[i], (long)KT * Ci, nullptr, GEMM_ATOMIC, ksplit_for(tiles, P.rowsc[i]));
+  ASTK_TRY(gemm_launch(GEMM_TN, with_amax_b(with_amax_a(lowp(g), dy_amax), P.a_hp[i - 1]), c.s));
+  U.add(P.dWr[i], c.Gr[i].dW, C, Ci, KT, 0, 0);
+  return 0;
+}
+// the weight gradients of every layer back in the parameters' layouts (and the status word, astk_cnn_desc.status_dst)
+int bwd_unpack(const CnnCall& c, const UnpackList& U) {
+  if (U.j.n > 0) {
+    hipLaunchKernelGGL(k_unpack_dw, dim3(gridn(U.max_elems), U.j.n), dim3(256), 0, c.s, U.j, persist_status_word(), c.d->status_dst);
+    ASTK_LAUNCH_CHECK();
+  } else if (c.d->status_dst) {
+    ASTK_TRY(status_snapshot_launch(c.d->status_dst, c.s));
+  }
+  return 0;
+}
+
 }  // namespace
 
 int cnn_out_dims(const astk_cnn_desc* d, int* T_out, int* F_out, int* feat) {
   CnnPlan P;
-  ASTK_TRY(make_plan(d, nullptr, P));
+  ASTK_TRY(plan_geometry(d, P));
   if (T_out) *T_out = P.Tn[P.n - 1];
   if (F_out) *F_out = P.Fn[P.n - 1];
   if (feat) *feat = P.Cn[P.n - 1] * P.Fn[P.n - 1];
@@ -1218,10 +1652,6 @@ size_t astk_conv_bn_relu_workspace_bytes(const astk_cnn_desc* d) {
   return P.bytes;
 }
 
-static int conv_fwd(const astk_cnn_desc* d, const astk_cnn_layer_params* L, const float* X, const float* noise, float* out, void* ws,
-                    size_t ws_bytes, int train, astk_stat_exchange_fn exchange, void* user, int world, void* stream, const int* row_len,
-                    int* out_len);
-
 int astk_conv_bn_relu_fwd(const astk_cnn_desc* d, const astk_cnn_layer_params* L, const float* X, const float* noise, float* out,
                           void* ws, size_t ws_bytes, int train, void* stream) {
   return astk_conv_bn_relu_fwd_sync(d, L, X, noise, out, ws, ws_bytes, train, nullptr, nullptr, 1, stream);
@@ -1230,150 +1660,15 @@ int astk_conv_bn_relu_fwd(const astk_cnn_desc* d, const astk_cnn_layer_params* L
 int astk_conv_bn_relu_fwd_sync(const astk_cnn_desc* d, const astk_cnn_layer_params* L, const float* X, const float* noise, float* out,
                                void* ws, size_t ws_bytes, int train, astk_stat_exchange_fn exchange, void* user, int world,
                                void* stream) {
-  return conv_fwd(d, L, X, noise, out, ws, ws_bytes, train, exchange, user, world, stream, nullptr, nullptr);
-}
-
-// The forward pass of every entry point.  row_len (device, B frame counts; evaluation mode, checked by astk_conv_bn_relu_fwd_rows): the
-// two activation-writing launches are the masked kernels; NULL: the call of always.
-static int conv_fwd(const astk_cnn_desc* d, const astk_cnn_layer_params* L, const float* X, const float* noise, float* out, void* ws,
-                    size_t ws_bytes, int train, astk_stat_exchange_fn exchange, void* user, int world, void* stream, const int* row_len,
-                    int* out_len) {
-  hipStream_t s = (hipStream_t)stream;
-  ASTK_CHECK_DESC(d, astk_cnn_desc);
-  PrecScope prec_scope(d->precision, d->gemm_operands);
-  GemmForwardScope forward_scope;      // split tiles of this op's products have at most two contributors (reproducible forward pass)
-  gemm_amax_step_boundary(s);         // the first op of a step: no operand-maximum handle is live here
-  ASTK_CHECK(world >= 1, "conv_bn_relu_fwd: world %d", world);
-  if (world == 1 || d->no_bn) exchange = nullptr;
-  CnnPlan P;
-  ASTK_TRY(make_plan(d, ws, P));
-  ASTK_CHECK(ws && ws_bytes >= P.bytes, "conv_bn_relu_fwd: workspace too small (%zu < %zu)", ws_bytes, P.bytes);
-  ASTK_CHECK(X && out && L, "conv_bn_relu_fwd: null pointer");
-  const int B = P.B;
-  // the statistics of every layer (train) and the maximum slots the producing kernels fill: one fill
-  const size_t zero_fwd = train ? P.zero_fwd_bytes : P.zero_fwd_amax_bytes;
-  if (!conv0_direct(d)) ASTK_TRY(fill_zero(P.zero_fwd_from, zero_fwd, s));       // (the direct layer-0 kernel does it on its way in)
-  // the backward's region: zeroed by this call's last kernel (train) -- a fill launch less in the backward call
-  const bool seq_out_zeroes = train != 0;
-  // (the layer-0 path is recorded now -- the backward must refuse a workspace whose forward took the other path even if this call fails
-  //  half-way --, the "backward region is clean" mark only behind the LAST launch below: a forward call that fails before its last kernel
-  //  was enqueued must not leave a mark that spares the backward its own zero fill; round-5 advice)
-  conv0_path_record(ws, conv0_direct(d), false);
-  void* const zb_from = seq_out_zeroes ? (void*)P.stat[0] : nullptr;
-  bool c0_stats = false;
-  if (conv0_direct(d)) {
-    // ---- layer 0: direct convolution (bf16x3 on the matrix pipe), leaves XF for the weight gradient
-    const int tiles_t = cdiv(P.Tc[0], C0_TT), total = B * P.Fc[0] * tiles_t, win = conv0_win_elems(d->st[0]);
-    const int grid = std::min(total, 2 * device_cu_count());
-    const size_t lds0 = std::max((size_t)3 * win * sizeof(unsigned short), (size_t)P.Cn[0] * P.K0 * sizeof(float));
-    // the layer's BatchNorm statistics inside the kernel (and, without a statistics exchange, scale / shift and the running statistics)
-    c0_stats = train && !d->no_bn && total == P.c0_tiles;      // the layer's BatchNorm statistics: per-tile sums out of the kernel
-    hipLaunchKernelGGL(k_conv0_fwd_x3, dim3(grid), dim3(256), lds0, s, X, noise, L[0].W, P.YC[0], P.XF, B, P.T, P.D,
-                       P.Fc[0], P.Tc[0], P.Cn[0], d->kt[0], d->kf[0], d->st[0], d->sf[0], d->pt[0], P.JG, P.xf_rows, tiles_t, total, win,
-                       P.zero_fwd_from, zero_fwd, c0_stats ? P.c0_part : nullptr);
-    ASTK_LAUNCH_CHECK();
-  } else {
-  // ---- layer 0: im2col + GEMM
-  hipLaunchKernelGGL(k_im2col0, dim3(P.Tc[0], B), dim3(256), 0, s, X, noise, P.P0, B, P.T, P.D, P.Fc[0], P.Tc[0], d->kt[0], d->kf[0],
-                     d->st[0], d->sf[0], d->pt[0], P.K0p);
-  ASTK_LAUNCH_CHECK();
-  ASTK_TRY(copy2d_f32(P.Wr[0], P.K0p, L[0].W, P.K0, P.Cn[0], P.K0, P.K0p, s));
-  ASTK_TRY(gemm_launch(GEMM_NT, gemm_args(P.rowsc[0], P.Cn[0], P.K0p, mat(P.P0, P.K0p), mat(P.Wr[0], P.K0p), P.YC[0], P.Cn[0]), s));
-  }
-  for (int i = 0; i < P.n; ++i) {
-    const int C = P.Cn[i], rows = P.rows[i], F = P.Fn[i];
-    if (i > 0) {
-      const int Ci = P.Cn[i - 1], KT = d->kt[i];
-      hipLaunchKernelGGL(k_repack_w, dim3(gridn((size_t)C * Ci * KT / 8)), dim3(256), 0, s, L[i].W, P.Wr[i], C, Ci, KT, P.a_wr[i],
-                         (const unsigned long long*)P.a_hp_s[i - 1], P.a_hp[i - 1]);
-      ASTK_LAUNCH_CHECK();
-      const long prow = (long)(P.Tn[i - 1] + 2 * P.padA[i - 1]) * Ci;
-      GemmArgs g = gemm_args(P.rowsc[i], C, KT * Ci, mat2(P.HP[i - 1], P.Tc[i], prow, (long)d->st[i] * Ci), mat(P.Wr[i], (long)KT * Ci),
-                             P.YC[i], C);
-      // (both operands' maxima were taken by the kernels that wrote them: no absolute-maximum pass in front of this launch)
-      ASTK_TRY(gemm_launch(GEMM_NT, with_amax_b(with_amax_a(lowp(g), P.a_hp[i - 1]), P.a_wr[i]), s));            // K6
-    }
-    if (P.pooled[i]) {     // old-path extra: max-pool in front of the BatchNorm (enc_dec.py:444-456)
-      hipLaunchKernelGGL(k_maxpool, dim3(gridn((size_t)rows * C / 4)), dim3(256), 0, s, P.YC[i], P.Y[i], P.IDX[i], B, P.Fc[i], P.Tc[i], P.Fn[i], P.Tn[i],
-                         P.pwf[i], P.pwt[i], C);
-      ASTK_LAUNCH_CHECK();
-    }
-    // ---- batch statistics -> scale/shift
-    if (d->no_bn) {
-      ASTK_CHECK(L[i].bias, "conv_bn_relu_fwd: no_bn needs a bias (layer %d)", i);
-      hipLaunchKernelGGL(k_bias_affine, dim3(cdiv(C, 256)), dim3(256), 0, s, L[i].bias, C, P.bn[i]);
-      ASTK_LAUNCH_CHECK();
-    } else {
-    BnFinalize fin{nullptr, (double)rows * (exchange ? world : 1), L[i].gamma, L[i].beta, L[i].avg_mean, L[i].avg_var, P.bn[i], d->bn_eps, d->bn_decay};
-    const bool fused_fin = train && !exchange;        // the statistics kernel's last block finalizes
-    if (train) {
-      BnFinalize f2 = fin;
-      if (fused_fin) f2.ctr = P.fin_ctr + 64 * i;
-      if (i == 0 && c0_stats)      // (layer 0, direct path: the tiles' sums came with the convolution -- 6.5 MB to add up instead of 262)
-        hipLaunchKernelGGL(k_colstats_tiles, colreduce_grid(P.c0_tiles, C), dim3(256), 0, s, P.c0_part, P.c0_tiles, C, cdiv(P.Tc[0], C0_TT), P.Tc[0], P.stat[i], f2);
-      else
-      hipLaunchKernelGGL(k_colstats, colreduce_grid(rows, C), dim3(256), 0, s, P.Y[i], rows, C, P.stat[i], f2);
-      ASTK_LAUNCH_CHECK();
-      if (exchange) ASTK_CHECK(exchange(user, P.stat[i], 2 * C, stream) == 0, "conv_bn_relu_fwd: statistics exchange failed (layer %d)", i);
-    }
-    if (!fused_fin) {
-      hipLaunchKernelGGL(k_bn_finalize, dim3(cdiv(C, 256)), dim3(256), 0, s, P.stat[i], C, fin, train);
-      ASTK_LAUNCH_CHECK();
-    }
-    }
-    if (i < P.n - 1) {
-      // (k_bn_relu_rows zeroes the pad rows of HP[i] itself)
-      if (row_len)
-        hipLaunchKernelGGL(k_bn_relu_rows_len, dim3(gridn((size_t)rows * C / 4)), dim3(256), 0, s, P.Y[i], P.bn[i], P.HP[i], rows, C,
-                           P.Tn[i], P.padA[i], P.a_hp_s[i], row_len, rows_geom(d), i, F);
-      else
-      hipLaunchKernelGGL(k_bn_relu_rows, dim3(gridn((size_t)rows * C / 4)), dim3(256), 0, s, P.Y[i], P.bn[i], P.HP[i], rows, C,
-                         P.Tn[i], P.padA[i], P.a_hp_s[i]);
-      ASTK_LAUNCH_CHECK();
-    } else if (row_len) {
-      const size_t shm = (size_t)C * F * sizeof(float);
-      ASTK_CHECK(shm <= 64 * 1024, "cnn: C*F' too large for the re-layout tile (%zu bytes)", shm);
-      hipLaunchKernelGGL(k_bn_relu_to_seq_len, dim3(P.Tn[i], B), dim3(256), shm, s, P.Y[i], P.bn[i], out, B, F, P.Tn[i], C, P.a_out, row_len,
-                         rows_geom(d), out_len);
-      ASTK_LAUNCH_CHECK();
-    } else {
-      const bool tiled_off = !tune_on(TUNE_CONV_SEQ_FWD);
-      if (!tiled_off && seq_bwd_applicable(C, F, (long)P.Tn[i] * B)) {
-        const int pp = seq_pp(F), gy = std::max(1, std::min(2048 / (C / SEQ_CH), cdiv(P.Tn[i] * B, pp)));
-        hipLaunchKernelGGL(k_bn_relu_to_seq_tiled, dim3(C / SEQ_CH, gy), dim3(256), (size_t)pp * SEQ_CH * F * sizeof(float), s, P.Y[i], P.bn[i], out, B, F,
-                           P.Tn[i], C, pp, P.a_out, zb_from, P.zero_bwd_bytes);
-      } else {
-      const size_t shm = (size_t)C * F * sizeof(float);
-      ASTK_CHECK(shm <= 64 * 1024, "cnn: C*F' too large for the re-layout tile (%zu bytes)", shm);
-      hipLaunchKernelGGL(k_bn_relu_to_seq, dim3(P.Tn[i], B), dim3(256), shm, s, P.Y[i], P.bn[i], out, B, F, P.Tn[i], C, P.a_out, zb_from, P.zero_bwd_bytes);
-      }
-      ASTK_LAUNCH_CHECK();
-    }
-  }
-  if (seq_out_zeroes) conv0_path_record(ws, conv0_direct(d), true);      // every launch of the call went out: its last kernel zeroes the backward's region
-  return 0;
+  const CnnCall c{d, L, nullptr, (hipStream_t)stream, user, X, noise, out, train, nullptr, nullptr, nullptr};
+  return conv_fwd(c, ws, ws_bytes, exchange, world);
 }
 
 int astk_conv_bn_relu_fwd_rows(const astk_cnn_desc* d, const astk_cnn_layer_params* L, const float* X, const int32_t* row_len, float* out,
                                int32_t* out_len, void* ws, size_t ws_bytes, void* stream) {
   if (!row_len) return astk_conv_bn_relu_fwd(d, L, X, nullptr, out, ws, ws_bytes, 0, stream);
-  CnnPlan P;
-  ASTK_TRY(make_plan(d, nullptr, P));
-  for (int i = 0; i < P.n; ++i) ASTK_CHECK(!P.pooled[i], "conv_bn_relu_fwd_rows: pooled layers (cnn_pool) take no row lengths (layer %d)", i);
-  ASTK_CHECK(P.B <= ASTK_ENCODE_ROWS_MAX, "conv_bn_relu_fwd_rows: at most %d rows, got %d", ASTK_ENCODE_ROWS_MAX, P.B);
-  // the lengths are read back before anything is launched: a row the library would refuse alone is refused here
-  int32_t len[ASTK_ENCODE_ROWS_MAX];
-  ASTK_CHECK(hipMemcpyAsync(len, row_len, (size_t)P.B * sizeof(int32_t), hipMemcpyDeviceToHost, (hipStream_t)stream) == hipSuccess &&
-             hipStreamSynchronize((hipStream_t)stream) == hipSuccess, "conv_bn_relu_fwd_rows: reading row_len failed");
-  for (int b = 0; b < P.B; ++b) {
-    ASTK_CHECK(len[b] >= 1 && len[b] <= P.T, "conv_bn_relu_fwd_rows: row_len[%d] = %d outside 1..T = %d", b, len[b], P.T);
-    int t = len[b];
-    for (int i = 0; i < P.n; ++i) {
-      t = conv_out(t, d->kt[i], d->st[i], d->pt[i]);
-      ASTK_CHECK(t >= 1, "conv_bn_relu_fwd_rows: row %d (%d frames) is too short for layer %d", b, len[b], i);
-    }
-  }
-  return conv_fwd(d, L, X, nullptr, out, ws, ws_bytes, 0, nullptr, nullptr, 1, stream, row_len, out_len);
+  const CnnCall c{d, L, nullptr, (hipStream_t)stream, nullptr, X, nullptr, out, 0, row_len, out_len, nullptr};
+  return conv_fwd(c, ws, ws_bytes, nullptr, 1);
 }
 
 const void* astk_conv_out_amax(const astk_cnn_desc* d, void* ws, size_t ws_bytes) {
@@ -1405,192 +1700,50 @@ int astk_conv_bn_relu_bwd(const astk_cnn_desc* d, const astk_cnn_layer_params* L
   return astk_conv_bn_relu_bwd_sync(d, L, Gr, d_out, ws, ws_bytes, nullptr, nullptr, 1, stream);
 }
 
+// The backward pass of every entry point: layers from the top; per layer the ReLU + BatchNorm backward, then the products -- layer 0 its
+// weight gradient alone; layer i >= 1 the phase weights (in FRONT of the weight gradient: the first of them folds dY's maximum slot), the
+// weight gradient, then the grouped input-gradient launch, which writes G for the layer below.
 int astk_conv_bn_relu_bwd_sync(const astk_cnn_desc* d, const astk_cnn_layer_params* L, const astk_cnn_layer_grads* Gr, float* d_out,
                                void* ws, size_t ws_bytes, astk_stat_exchange_fn exchange, void* user, int world, void* stream) {
-  hipStream_t s = (hipStream_t)stream;
+  const CnnCall c{d, L, Gr, (hipStream_t)stream, user, nullptr, nullptr, nullptr, 1, nullptr, nullptr, d_out};
   ASTK_CHECK_DESC(d, astk_cnn_desc);
   PrecScope prec_scope(d->precision, d->gemm_operands);
   DetScope det_scope(d->deterministic);
   ASTK_CHECK(world >= 1, "conv_bn_relu_bwd: world %d", world);
-  if (world == 1 || d->no_bn) exchange = nullptr;      // (no statistics to exchange without BatchNorm)
   CnnPlan P;
   ASTK_TRY(make_plan(d, ws, P));
   ASTK_CHECK(ws && ws_bytes >= P.bytes, "conv_bn_relu_bwd: workspace too small");
   ASTK_CHECK(d_out && L && Gr, "conv_bn_relu_bwd: null pointer");
+  const CnnRoute R = cnn_route(d, P, 1, exchange, world, nullptr);
   {
-    const int fwd_direct = conv0_path_lookup(ws), bwd_direct = conv0_direct(d) ? 1 : 0;
+    const int fwd_direct = conv0_path_lookup(ws), bwd_direct = R.direct0 ? 1 : 0;
     ASTK_CHECK(fwd_direct < 0 || fwd_direct == bwd_direct, "conv_bn_relu_bwd: the forward call on this workspace took the %s layer-0 path, this call "
                "would take the %s one (the process-default arithmetic changed between the two calls while the descriptor's precision is DEFAULT?)",
                fwd_direct ? "direct-convolution" : "im2col", bwd_direct ? "direct-convolution" : "im2col");
   }
-  const int B = P.B;
-  // the last layer's BatchNorm backward reads d_out in its (T'', B, C*F') layout itself (k_bn_bwd_*_seq); shapes those kernels do not take
-  // (and the test hook that edits G) go through the re-ordered copy G as before.  astk_set_tuning("conv.seq_bwd", 0): always the copy.
-  const bool seq_off = !tune_on(TUNE_CONV_SEQ_BWD);
-  bool seq_last = !seq_off && seq_bwd_applicable(P.Cn[P.n - 1], P.Fn[P.n - 1], (long)P.Tn[P.n - 1] * B);
-#ifdef ASTK_TEST_HOOKS
-  if (g_kill_n > 0) seq_last = false;
-#endif
-  if (!seq_last) {
-    const int i = P.n - 1;
-    const size_t shm = (size_t)P.Cn[i] * P.Fn[i] * sizeof(float);
-    hipLaunchKernelGGL(k_seq_to_rows, dim3(P.Tn[i], B), dim3(256), shm, s, d_out, P.G, B, P.Fn[i], P.Tn[i], P.Cn[i]);
-    ASTK_LAUNCH_CHECK();
-  }
-  UnpackJobs uj;
-  uj.n = 0;
-  size_t uj_max = 0;
-  auto unpack_add = [&](const float* src, float* dW, int Co, int Ci, int KT, int JG, int ldg) {
-    uj.src[uj.n] = src; uj.dW[uj.n] = dW; uj.Co[uj.n] = Co; uj.Ci[uj.n] = Ci; uj.KT[uj.n] = KT; uj.JG[uj.n] = JG; uj.ldg[uj.n] = ldg;
-    ++uj.n;
-    uj_max = std::max(uj_max, (size_t)Co * Ci * KT);
-  };
+  if (!R.seq_bwd) ASTK_TRY(bwd_seq_to_rows(P, c));
+  UnpackList U;
+  U.j.n = 0;
   for (int i = P.n - 1; i >= 0; --i) {
-    const int C = P.Cn[i], rows = P.rows[i];
 #ifdef ASTK_TEST_HOOKS
     if (g_kill_n > 0) {      // test instrumentation (astk_conv_debug_kill_units): drop the upstream gradient of the listed units
-      hipLaunchKernelGGL(k_kill_units, dim3(cdiv(g_kill_n, 256)), dim3(256), 0, s, P.G, g_kill_units, g_kill_n, i, rows, C);
+      hipLaunchKernelGGL(k_kill_units, dim3(cdiv(g_kill_n, 256)), dim3(256), 0, c.s, P.G, g_kill_units, g_kill_n, i, P.rows[i], P.Cn[i]);
       ASTK_LAUNCH_CHECK();
     }
 #endif
-    // ---- ReLU + BatchNorm backward: G (grad wrt post-ReLU) -> DY[i] (grad wrt raw conv output)
     // statistics and dWr scratch of every layer: zeroed by the forward call's last kernel (conv0_path_record), else here
-    if (i == P.n - 1 && !conv_take_bwd_clean(ws)) ASTK_TRY(fill_zero(P.stat[0], P.zero_bwd_bytes, s));
-    const bool seq = seq_last && i == P.n - 1;
-    const int seq_gx = C / SEQ_CH;
-    if (seq) {
-      const int sb = (int)tune(TUNE_CONV_SEQ_STATS_BLOCKS);
-      const int gy = std::max(1, std::min(sb / seq_gx, cdiv(P.Tn[i] * B, seq_pp(P.Fn[i]))));
-      hipLaunchKernelGGL(k_bn_bwd_stats_seq, dim3(seq_gx, gy), dim3(256), seq_tile_bytes(P.Fn[i]), s, P.Y[i], d_out, P.bn[i], B, P.Fn[i], P.Tn[i], C,
-                         seq_pp(P.Fn[i]), P.stat[i]);
-    } else
-      hipLaunchKernelGGL(k_bn_bwd_stats, colreduce_grid(rows, C), dim3(256), 0, s, P.Y[i], P.G, P.bn[i], rows, C, P.stat[i]);
-    ASTK_LAUNCH_CHECK();
-    if (exchange) {
-      hipLaunchKernelGGL(k_bn_param_grads, dim3(cdiv(C, 256)), dim3(256), 0, s, P.stat[i], C, Gr[i].dgamma, Gr[i].dbeta);
-      ASTK_LAUNCH_CHECK();
-      ASTK_CHECK(exchange(user, P.stat[i], 2 * C, stream) == 0, "conv_bn_relu_bwd: statistics exchange failed (layer %d)", i);
-    }
-    const int F = P.Fc[i];             // (b, f) groups of this layer's convolution output = of its input
-    const int Tp = P.Tc[i] + P.dF[i] + P.dB[i];
-    if (P.dF[i] + P.dB[i] > 0 && P.pooled[i]) {       // (un-pooled layers: the apply kernel zeroes the pad rows of the dY it writes)
-      hipLaunchKernelGGL(k_zero_pads, dim3(gridn((size_t)B * F * (P.dF[i] + P.dB[i]) * C / 4)), dim3(256), 0, s, P.DY[i], B * F, P.Tc[i], P.dF[i],
-                         P.dB[i], C);
-      ASTK_LAUNCH_CHECK();
-    }
-    // (no_bn: the ReLU mask alone -- scale 1 and a zero 1/m switch the BatchNorm terms off; the column sums of g are the bias gradient)
-    // pooled layers: the gradient wrt the POOLED output goes to DYP (plain rows), k_unpool spreads it over the padded dY of the convolution
-    if (seq) {
-      const int ab = (int)tune(TUNE_CONV_SEQ_APPLY_BLOCKS);
-      const int gy = std::max(1, std::min(ab / seq_gx, cdiv(P.Tn[i] * B, seq_pp(P.Fn[i]))));
-      hipLaunchKernelGGL(k_bn_bwd_apply_seq, dim3(seq_gx, gy), dim3(256), seq_tile_bytes(P.Fn[i]), s, P.Y[i], d_out, P.bn[i], P.stat[i],
-                         P.pooled[i] ? P.DYP[i] : P.DY[i], B, P.Fn[i], P.Tn[i], C, seq_pp(P.Fn[i]), P.pooled[i] ? 0 : P.dF[i], P.pooled[i] ? 0 : P.dB[i],
-                         (exchange || d->no_bn) ? nullptr : Gr[i].dgamma, (exchange || d->no_bn) ? nullptr : Gr[i].dbeta,
-                         d->no_bn ? 0.f : 1.f / ((float)rows * (exchange ? world : 1)), (i > 0 && !P.pooled[i]) ? P.a_dy_s[i] : nullptr);
-    } else
-    hipLaunchKernelGGL(k_bn_bwd_apply, dim3(gridn((size_t)rows * C / 4)), dim3(256), 0, s, P.Y[i], P.G, P.bn[i], P.stat[i], P.pooled[i] ? P.DYP[i] : P.DY[i],
-                       rows, C, P.Tn[i], P.pooled[i] ? 0 : P.dF[i], P.pooled[i] ? 0 : P.dB[i], (exchange || d->no_bn) ? nullptr : Gr[i].dgamma,
-                       (exchange || d->no_bn) ? nullptr : Gr[i].dbeta, d->no_bn ? 0.f : 1.f / ((float)rows * (exchange ? world : 1)),
-                       (i > 0 && !P.pooled[i]) ? P.a_dy_s[i] : nullptr);
-    ASTK_LAUNCH_CHECK();
-    if (P.pooled[i]) {
-      hipLaunchKernelGGL(k_unpool, dim3(gridn((size_t)P.rowsc[i] * C / 4)), dim3(256), 0, s, P.DYP[i], P.IDX[i], P.DY[i], B, P.Fc[i], P.Tc[i], P.Fn[i],
-                         P.Tn[i], P.pwf[i], P.pwt[i], C, P.dF[i], P.dB[i], i > 0 ? P.a_dy_s[i] : nullptr);
-      ASTK_LAUNCH_CHECK();
-    }
-    if (d->no_bn) {
-      ASTK_CHECK(Gr[i].dbias, "conv_bn_relu_bwd: no_bn needs a bias gradient (layer %d)", i);
-      hipLaunchKernelGGL(k_bias_grad, dim3(cdiv(C, 256)), dim3(256), 0, s, P.stat[i], C, Gr[i].dbias);
-      ASTK_LAUNCH_CHECK();
-    }
+    if (i == P.n - 1 && !conv_take_bwd_clean(ws)) ASTK_TRY(fill_zero(P.stat[0], P.zero_bwd_bytes, c.s));
+    ASTK_TRY(bwd_bn_relu(P, R, c, i));
     if (i == 0) {
-      // ---- wgrad layer 0: dW0p[C0][K0p] = DY0^T P0
-      const int ks = ksplit_for(1, P.rowsc[0]);
-      if (conv0_direct(d)) {
-        // the patches as a zero-copy window matrix over XF: row (b, f, t1) = the kt * JG floats from row st * t1 of group (b, f) on
-        const int ldg = (P.K0g + 3) & ~3;
-        MatView Bm = mat2(P.XF, P.Tc[0], (long)P.xf_rows * P.JG, (long)d->st[0] * P.JG);
-        ASTK_TRY(gemm_launch(GEMM_TN, gemm_args(C, P.K0g, P.rowsc[0], mat(P.DY[0], C), Bm, P.dWr[0], ldg, nullptr, GEMM_ATOMIC, ks), s));
-        unpack_add(P.dWr[0], Gr[0].dW, C, d->kf[0], d->kt[0], P.JG, ldg);
-      } else {
-      ASTK_TRY(gemm_launch(GEMM_TN, gemm_args(C, P.K0p, P.rowsc[0], mat(P.DY[0], C), mat(P.P0, P.K0p), P.dWr[0], P.K0p, nullptr, GEMM_ATOMIC, ks), s));
-      ASTK_TRY(add2d_f32(Gr[0].dW, P.K0, P.dWr[0], P.K0p, C, P.K0, s));
-      }
+      ASTK_TRY(R.direct0 ? bwd_wgrad0_direct(P, c, U) : bwd_wgrad0_im2col(P, c));
     } else {
-      const int Ci = P.Cn[i - 1], KT = d->kt[i], st = d->st[i], pt = d->pt[i];
-      const long dyrow = (long)Tp * C;                                  // per (b,f) group of the padded dY
-      const long hprow = (long)(P.Tn[i - 1] + 2 * P.padA[i - 1]) * Ci;  // per (b,f) group of HP[i-1]
-      // the padded dY feeds the weight gradient and every stride phase of the input gradient: its maximum (fp16x2 GEMM scale) was taken
-      // by k_bn_bwd_apply when it wrote it; the activations' by k_bn_relu_rows in the forward pass
-      const unsigned long long* ady = P.a_dy[i];
-      // ---- dgrad, part 1: the phase weights of the stride phases rho of the input position t_in = rho + st*j (the first of these small
-      // kernels also folds dY's strided maximum slot into the plain one both products read, hence in front of the weight gradient)
-      GemmArgs ph[GEMM_GROUP_MAX];
-      int nph = 0;
-      bool folded = false;
-      PhaseWJobs pj;
-      pj.n = 0;
-      int pj_na_max = 0;
-      auto launch_phase_w = [&]() {      // the phase weights gathered so far (wd buffers 0 .. pj.n-1)
-        if (pj.n == 0) return;
-        hipLaunchKernelGGL(k_phase_w, dim3(gridn((size_t)Ci * pj_na_max * C / 8), pj.n), dim3(256), 0, s, L[i].W, pj, C, Ci, KT, st,
-                           folded ? nullptr : (const unsigned long long*)P.a_dy_s[i], P.a_dy[i]);
-        folded = true;
-        pj.n = 0;
-        pj_na_max = 0;
-      };
-      for (int rho = 0; rho < st && rho < P.Tn[i - 1]; ++rho) {
-        const int r = (rho + pt) % st;
-        const int na = (KT - r + st - 1) / st;
-        if (na <= 0) {   // no tap reaches this phase: gradient is zero
-          continue;
-        }
-        const int nj = (P.Tn[i - 1] - rho + st - 1) / st;
-        const int q0 = (rho + pt) / st;
-        if (nph == P.wd_copies) {      // (more phases than buffers: flush)
-          launch_phase_w();
-          ASTK_LAUNCH_CHECK();
-          ASTK_TRY(gemm_launch_group(GEMM_NT, ph, nph, s));
-          nph = 0;
-        }
-        float* wd = P.Wd + (size_t)nph * P.wd_stride;
-        // (a_wd[k] is zeroed once per backward call: a slot that is reused -- more phases than buffers, a deeper stack -- keeps the larger
-        //  of its users' maxima, i.e. a slightly conservative scale for phase weights of similar magnitude)
-        pj.wd[pj.n] = wd; pj.r[pj.n] = r; pj.na[pj.n] = na; pj.amax[pj.n] = P.a_wd[nph];
-        ++pj.n;
-        pj_na_max = std::max(pj_na_max, na);
-        const long start = (long)(q0 - na + 1 + P.dF[i]);
-        ASTK_CHECK(start >= 0, "cnn dgrad: negative window start");
-        GemmArgs g = gemm_args(B * F * nj, Ci, na * C, mat2(P.DY[i] + start * C, nj, dyrow, C), mat(wd, (long)na * C),
-                               P.G + (long)rho * Ci, Ci);
-        g.c_tn = nj;
-        g.c_sg = (long)P.Tn[i - 1] * Ci;
-        g.c_st = (long)st * Ci;
-        ph[nph] = with_amax_b(with_amax_a(lowp(g), ady), P.a_wd[nph]);
-        ++nph;
-      }
-      launch_phase_w();
-      ASTK_LAUNCH_CHECK();
-      if (!folded) ady = P.a_dy_s[i];      // (no phase kernel ran: the products read the strided slot itself)
-      // ---- wgrad: dWr[co][kt*Ci+ci] = sum_rows DY[row][co] * window(row)[k]
-      {
-        MatView A = mat2(P.DY[i] + (long)P.dF[i] * C, P.Tc[i], dyrow, C);
-        MatView Bm = mat2(P.HP[i - 1], P.Tc[i], hprow, (long)st * Ci);
-        const long tiles = (long)cdiv(C, 128) * cdiv(KT * Ci, 128);
-        ASTK_TRY(gemm_launch(GEMM_TN, with_amax_b(with_amax_a(lowp(gemm_args(C, KT * Ci, P.rowsc[i], A, Bm, P.dWr[i], (long)KT * Ci, nullptr, GEMM_ATOMIC, ksplit_for(tiles, P.rowsc[i]))), ady), P.a_hp[i - 1]), s));
-      }
-      unpack_add(P.dWr[i], Gr[i].dW, C, Ci, KT, 0, 0);
-      // ---- dgrad, part 2: one window GEMM per stride phase, all phases in one grouped launch
-      if (nph > 0) ASTK_TRY(gemm_launch_group(GEMM_NT, ph, nph, s));
+      DgradPhases D;
+      ASTK_TRY(bwd_dgrad_phases(P, c, i, D));
+      ASTK_TRY(bwd_wgrad(P, c, i, D.dy_amax(P, i), U));
+      ASTK_TRY(D.launch_products(c));      // dgrad, part 2: one window GEMM per stride phase, all phases in one grouped launch
     }
   }
-  if (uj.n > 0) {
-    hipLaunchKernelGGL(k_unpack_dw, dim3(gridn(uj_max), uj.n), dim3(256), 0, s, uj, persist_status_word(), d->status_dst);
-    ASTK_LAUNCH_CHECK();
-  } else if (d->status_dst) {
-    ASTK_TRY(status_snapshot_launch(d->status_dst, s));
-  }
-  return 0;
+  return bwd_unpack(c, U);
 }
 
 }  // extern "C"

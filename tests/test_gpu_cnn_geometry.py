@@ -7,7 +7,9 @@ and a fresh forward + backward, eval mode) runs on the geometries of tests/range
 schemes -- bf16x3 puts the direct-eligible layer-0 shapes on the direct kernel (proved by the path probe), f32 / fp16x2 put the same
 geometry on im2col + GEMM -- with the suite's bounds: 2e-4 output and statistics, 5e-4 every gradient (the cases' seeds leave no unit near
 the ReLU's kink, asserted), 2e-5 between repeated backward calls.  Then: max-pooling on a direct-eligible layer 0, the descriptor's
-refusals, and three whole train steps on other stacks against the float64 oracle."""
+refusals, and three whole train steps on other stacks against the float64 oracle.  The two geometries whose last layer takes the tiled
+sequence re-layout and the sequence-layout BatchNorm backward also run with those routes switched off ("conv.seq_fwd", "conv.seq_bwd")."""
+import contextlib
 import ctypes as C
 
 import numpy as np
@@ -45,6 +47,75 @@ def test_cnn_max_pool_on_a_direct_eligible_layer0(lib, B, T, D, c0, c1, pool, ge
     layers = RC.shipped_layers(c0, c1)
     assert RC.conv0_direct_shape(layers) and not RC.conv0_direct_shape(layers, pool)
     _cnn_case(lib, B, T, D, c0, c1, False, pool=pool, all_stats=True, expect_direct=False)
+
+
+# ------------------------------------------------------------------ the last layer's routes with their knobs off
+SEQ_IDS = ["one-layer-c64", "f10-c64-last"]             # the geometries that take k_bn_relu_to_seq_tiled and k_bn_bwd_*_seq by default
+SEQ_KNOBS_OFF = [("conv.seq_fwd",), ("conv.seq_bwd",), ("conv.seq_fwd", "conv.seq_bwd")]
+
+
+def _geometry(cid):
+    return next(c for c in RC.CNN_GEOMETRY_CASES if c[0] == cid)
+
+
+@contextlib.contextmanager
+def _knobs_off(lib, names):
+    prev = {k: C.c_double() for k in names}
+    try:
+        for k, v in prev.items():
+            assert lib.astk_get_tuning(k.encode(), C.byref(v)) == 0 and v.value == 1, k
+            assert lib.astk_set_tuning(k.encode(), 0.0) == 0, k
+        yield
+    finally:
+        for k, v in prev.items():
+            assert lib.astk_set_tuning(k.encode(), v.value) == 0, k
+
+
+@pytest.mark.parametrize("off", SEQ_KNOBS_OFF, ids=["+".join(k.split(".")[1] for k in ks) + "-off" for ks in SEQ_KNOBS_OFF])
+@pytest.mark.parametrize("cid", SEQ_IDS)
+def test_cnn_seq_routes_with_knobs_off(lib, cid, off, gemm_split):
+    """The un-tiled re-layout (k_bn_relu_to_seq) and the row-layout BatchNorm backward (k_seq_to_rows + k_bn_bwd_stats / _apply) on shapes
+    that take the tiled / sequence-layout kernels by default -- the routes no other operator test reaches: the same operator case, the
+    same float64 reference, the same bounds."""
+    _, B, T, D, layers, seed, _ = _geometry(cid)
+    with _knobs_off(lib, off):
+        _cnn_case(lib, B, T, D, None, None, False, seed=seed, layers=layers, all_stats=True, kink_free=True,
+                  expect_direct=gemm_split == "bf16x3")
+
+
+@pytest.mark.parametrize("cid", SEQ_IDS)
+def test_cnn_tiled_relayout_equals_untiled(lib, cid, gemm_split):
+    """k_bn_relu_to_seq_tiled and k_bn_relu_to_seq apply the same per-element scale / shift / ReLU to the same convolution output: the
+    frames are equal bit for bit, in evaluation mode (scale / shift from the same running statistics) and in training mode (from the
+    batch statistics, which both calls form with the same launches)."""
+    from ast_amd._lib import CnnLayerParams
+    from test_gpu_ops import GuardedWS, dev, ok, stream, vp
+    _, B, T, D, layers, seed, _ = _geometry(cid)
+    cfg, P, X, _, _ = RC.cnn_draws(B, T, D, None, None, False, seed=seed, layers=layers)
+    n = len(layers)
+    cd = _cnn_desc(cfg, B, T, D)
+    t2, f2, feat = C.c_int(), C.c_int(), C.c_int()
+    ok(lib, lib.astk_conv_bn_relu_out_dims(C.byref(cd), C.byref(t2), C.byref(f2), C.byref(feat)))
+    sfx = ("/W", "_bn/gamma", "_bn/beta", "_bn/avg_mean", "_bn/avg_var")
+    nbytes = lib.astk_conv_bn_relu_workspace_bytes(C.byref(cd))
+    xd = dev(X)
+
+    def frames(train, knobs):
+        prm = {f"CNN_{i}{s}": dev(P[f"CNN_{i}{s}"]) for i in range(n) for s in sfx}      # (fresh running statistics for every call)
+        cp = (CnnLayerParams * n)()
+        for i in range(n):
+            cp[i].W, cp[i].gamma, cp[i].beta, cp[i].avg_mean, cp[i].avg_var = (prm[f"CNN_{i}{s}"].data_ptr() for s in sfx)
+        ws = GuardedWS(nbytes)
+        out = torch.full((t2.value, B, feat.value), 7.0, device="cuda")
+        with _knobs_off(lib, knobs):
+            ok(lib, lib.astk_conv_bn_relu_fwd(C.byref(cd), cp, vp(xd), None, vp(out), vp(ws), nbytes, train, stream()))
+        ws.check("cnn fwd")
+        return out
+
+    for train in (0, 1):
+        tiled, plain = frames(train, ()), frames(train, ("conv.seq_fwd",))
+        assert float(tiled.abs().max()) > 0 and float((tiled == 7.0).sum()) == 0
+        assert torch.equal(tiled, plain), f"train = {train}: the tiled re-layout differs from the un-tiled one by {float((tiled - plain).abs().max()):.3e}"
 
 
 # ------------------------------------------------------------------ the descriptor's refusals
