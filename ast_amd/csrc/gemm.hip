@@ -1230,6 +1230,22 @@ static unsigned* tick_table(hipStream_t s, size_t words) {
   return t->p;
 }
 
+// The spans of one operand slice, in floats from v.p.  `addr`: to the end of the last element the k loop addresses with its 32-bit
+// offsets -- what gemm_prepare bounds and stores as spanA / spanB (0 for two-level K-major rows, which use 64-bit offsets).
+// `contig`: the contiguous range the absolute-maximum pass reads when the rows are no plain r * ld; differs from `addr` only there.
+struct OperandSpan { long addr, contig; };
+static OperandSpan operand_span(const MatView& v, bool kr, int rows, int K) {
+  const long k4 = (K + 3) & ~3L, r4 = (rows + 3) & ~3L;      // padded to the 16-byte granule (leading dimensions are multiples of 4)
+  if (kr && v.tn > 0) return {0, (long)((K - 1) / v.tn) * v.sg + (long)((K - 1) % v.tn) * v.st + r4};
+  long n;
+  if (kr) n = (long)(K - 1) * v.ld + r4;
+  else if (v.rowidx) n = (v.idx_rows > 0 ? v.idx_rows : (long)rows) * v.ld;      // indexed rows: a permutation of [0, rows), or any rows of an array of idx_rows rows
+  else if (v.tn > 0) n = (long)((rows - 1) / v.tn) * v.sg + (long)(v.tn - 1) * v.st + k4;
+  else n = (long)(rows - 1) * v.ld + k4;
+  return {n, n};
+}
+
+// The one place that checks an operand; fills the per-product part of the work decomposition for TLM x TL tiles.
 static int gemm_prepare(int layout, const GemmArgs& g, GemmArgs& a, bool& twolvl, int TLM, int TL) {
   ASTK_CHECK(g.A.p && g.B.p && g.C, "gemm: null operand");
   ASTK_CHECK(aligned16(g.A.p) && aligned16(g.B.p), "gemm: A/B must be 16-byte aligned");
@@ -1240,14 +1256,7 @@ static int gemm_prepare(int layout, const GemmArgs& g, GemmArgs& a, bool& twolvl
   a = g;
   const bool a_kr = layout == GEMM_TN, b_kr = layout != GEMM_NT;
   // the k loop addresses an operand as (uniform pointer) + (32-bit byte offset): each batch slice has to span less than 4 GiB
-  auto span = [&](const MatView& v, bool kr, int rows) -> long {   // floats from v.p to the end of the last element touched
-    const long k4 = (g.K + 3) & ~3L, r4 = (rows + 3) & ~3L;      // padded to the 16-byte granule (leading dimensions are multiples of 4)
-    if (kr) return v.tn > 0 ? 0 : (long)(g.K - 1) * v.ld + r4;   // two-level K-major rows use 64-bit offsets
-    if (v.rowidx) return (v.idx_rows > 0 ? v.idx_rows : (long)rows) * v.ld;      // indexed rows: a permutation of [0, rows), or any rows of an array of idx_rows rows
-    if (v.tn > 0) return (long)((rows - 1) / v.tn) * v.sg + (long)(v.tn - 1) * v.st + k4;
-    return (long)(rows - 1) * v.ld + k4;
-  };
-  const long spa = span(g.A, a_kr, g.M), spb = span(g.B, b_kr, g.N);
+  const long spa = operand_span(g.A, a_kr, g.M, g.K).addr, spb = operand_span(g.B, b_kr, g.N, g.K).addr;
   ASTK_CHECK(spa < (1L << 30) && spb < (1L << 30), "gemm: an operand slice spans more than 4 GiB (M=%d N=%d K=%d lda=%ld ldb=%ld)",
              g.M, g.N, g.K, g.A.ld, g.B.ld);
   ASTK_CHECK(!(a_kr && g.A.tn > 0 && (long)BK * g.A.st + g.M >= (1L << 29)) && !(b_kr && g.B.tn > 0 && (long)BK * g.B.st + g.N >= (1L << 29)),
@@ -1295,7 +1304,10 @@ PrecScope::PrecScope(int precision, int operands) : prev_p(tl_prec), prev_l(tl_l
   else if (operands == ASTK_OPERANDS_FP16) tl_lowp = 1;
 }
 PrecScope::~PrecScope() { tl_prec = prev_p; tl_lowp = prev_l; }
-int gemm_precision_mode() { const int p = default_prec(); return p == PREC_F32 ? 2 : (p == PREC_BF16X3 ? 1 : 0); }
+// the public numbering of the schemes (astk_set_gemm_precision): 0 fp16x2, 1 bf16x3, 2 f32
+static int prec_to_mode(int p) { return p == PREC_F32 ? 2 : (p == PREC_BF16X3 ? 1 : 0); }
+static int mode_to_prec(int mode) { return mode == 2 ? PREC_F32 : (mode == 1 ? PREC_BF16X3 : PREC_F16X2); }
+int gemm_precision_mode() { return prec_to_mode(default_prec()); }
 static unsigned long long* amax_ring() {
   static unsigned long long* ring = nullptr;
   if (!ring && hipGetSymbolAddress((void**)&ring, HIP_SYMBOL(g_amax_ring)) != hipSuccess) ring = nullptr;
@@ -1318,8 +1330,7 @@ constexpr unsigned AMAX_GEN_WRAP = 0xFFFFFF00u;
 constexpr unsigned AMAX_GEN_SOFT = 0xFFF00000u;       // ~1M generations (tens of thousands of steps) in front of the hard limit
 static std::mutex g_amax_wrap_mutex;
 static void amax_restart_locked(hipStream_t s) {
-  unsigned long long* ring = nullptr;
-  if (hipGetSymbolAddress((void**)&ring, HIP_SYMBOL(g_amax_ring)) == hipSuccess && ring) (void)hipMemsetAsync(ring, 0, sizeof(unsigned long long) * AMAX_SLOTS, s);
+  if (unsigned long long* ring = amax_ring()) (void)hipMemsetAsync(ring, 0, sizeof(unsigned long long) * AMAX_SLOTS, s);
   g_amax_counter.store(2);
 }
 void gemm_amax_step_boundary(hipStream_t s) {
@@ -1339,6 +1350,9 @@ static unsigned next_amax_gen(hipStream_t s) {
 }
 // slots [0, AMAX_SLOTS / 2) serve the launches' own passes, [AMAX_SLOTS / 2, AMAX_SLOTS) the callers' handles (gemm_amax)
 static std::atomic<unsigned> g_amax_handle{0};
+static unsigned long long* amax_take_handle(unsigned long long* ring) {
+  return ring + AMAX_SLOTS / 2 + (size_t)(g_amax_handle.fetch_add(1) % (AMAX_RING_SLOTS / 2)) * AMAX_SLOT_WORDS;
+}
 
 // Adds the region(s) of one operand: exact rows x inner when the rows are plain (r * ld), the contiguous span from p to the slice's end
 // when they are two-level windows or indexed (every byte of the span is activation data or zero padding of the same array; the
@@ -1368,180 +1382,373 @@ static void amax_add(AmaxJobs& J, const MatView& v, bool kr, int rows, int K, in
   }
 }
 
-int gemm_launch_group(int layout, const GemmArgs* list, int n, hipStream_t s) {
-  ASTK_CHECK(layout == GEMM_NT || layout == GEMM_NN || layout == GEMM_TN, "gemm: bad layout %d", layout);
-  ASTK_CHECK(n >= 0 && n <= GEMM_GROUP_MAX, "gemm: group of %d products (max %d)", n, GEMM_GROUP_MAX);
-  GemmGroup grp;
-  bool twolvl = false, any_store = false;
-  long tiles = 0;
-  double flops = 0;
-  int min_kt = 0x7fffffff;
-  // Tile edge: 128 unless the whole launch is too small to keep the chip busy with 128-tiles (fewer k-iterations than the stream-K
-  // threshold below, and either too few tiles for the CUs or tiles so shallow that their ramp dominates): then 64-tiles give 4x the
-  // workgroups, each a quarter of the work.  astk_set_tuning("gemm.tile", 64 | 128 | 256) forces one.
-  const int force_tl = (int)tune(TUNE_GEMM_TILE);
-  // operand scheme of the launch (default_prec: fp16x2 unless the environment asks for bf16x3 or f32)
-  int prec = default_prec();
-  if (low_precision_gemms() != 0 && n > 0) {        // fp16 operands only if every product of the launch is marked eligible by its caller
+// ---- The launcher: gemm_env (the state of the call, read once) -> gemm_plan (a pure function of the arguments and that state) ->
+// gemm_log -> gemm_execute (everything that touches the device).
+
+// Everything a grouped launch reads from outside its arguments.  gemm_env is the only reader: nothing below gemm_launch_group calls
+// tune(), default_prec() or low_precision_gemms(), or reads a tl_* variable.
+struct GemmEnv {
+  int prec;               // default operand scheme: the thread's PrecScope, else the process default (bf16x3 unless astk_set_gemm_precision)
+  int lowp;               // fp16-operand mode (PrecScope, else astk_set_low_precision_gemms)
+  int forward, det;       // inside a GemmForwardScope / a DetScope that asks for fixed-order sums
+  int wg_cap;             // GemmWgCap: workgroups, 0 = none
+  double small_flops;     // astk_set_gemm_bf16_split_below
+  int force_tl;           // "gemm.tile": 64 | 128 | 256, else chosen per launch
+  double t256_above;      // "gemm.t256_above"
+  int force_g;            // "gemm.grid": > 0 forces the grid
+  bool hybrid, chunk;     // "gemm.hybrid", "gemm.chunk"
+  int chunk_div;          // "gemm.chunk_div"
+  double forward_pairs;   // "gemm.forward_pairs": != 0 the two-contributor cap, >= 2 the forward rule for every launch
+  bool ticket, log;       // "gemm.ticket" (ASTK_GEMM_TICKET builds only), "gemm.log"
+};
+static GemmEnv gemm_env() {
+  GemmEnv e;
+  e.prec = default_prec();
+  e.lowp = low_precision_gemms();
+  e.forward = tl_forward; e.det = tl_det; e.wg_cap = tl_wg_cap;
+  e.small_flops = g_small_flops.load();
+  e.force_tl = (int)tune(TUNE_GEMM_TILE);
+  e.t256_above = tune(TUNE_GEMM_T256_ABOVE);
+  e.force_g = (int)tune(TUNE_GEMM_GRID);
+  e.hybrid = tune_on(TUNE_GEMM_HYBRID); e.chunk = tune_on(TUNE_GEMM_CHUNK);
+  e.chunk_div = (int)tune(TUNE_GEMM_CHUNK_DIV);
+  e.forward_pairs = tune(TUNE_GEMM_FORWARD_PAIRS);
+  e.ticket = tune_on(TUNE_GEMM_TICKET); e.log = tune_on(TUNE_GEMM_LOG);
+  return e;
+}
+
+// What one grouped launch will do: the kernel's argument and every decision around it.  Printable (gemm_plan_line).
+struct GemmPlan {
+  GemmGroup grp;          // the kernel's argument (grp.n == 0: nothing to launch); execute adds the ticket table and the maximum slots
+  int prec;               // final operand scheme
+  int TL, TLM;            // tile: TLM rows x TL columns
+  long G;                 // workgroups
+  bool aligned;           // workgroup boundaries fall on tile boundaries
+  bool twolvl, fixup;     // the TWOLVL / FIX instantiations
+  bool need_zero, zero_vec;               // split tiles of GEMM_STORE products zeroed in front of the launch, with 16-byte stores
+  bool want_ticket; long ticket_tiles;    // ... or handed over by tickets: the table's tile count
+  long tiles; double flops;
+  // group-wide facts, taken once where the group is filled
+  bool any_store, any_accum, uniform_kt;
+  int min_kt, max_kt;
+  bool a_kr, b_kr;        // K-major operands of the layout
+};
+
+static bool gemm_skipped(const GemmArgs& g) { return g.M <= 0 || g.N <= 0 || g.K <= 0 || g.batch <= 0; }
+
+// Step 1: operand scheme of the launch, as the tile choice sees it.
+static int plan_scheme(const GemmArgs* list, int n, const GemmEnv& env) {
+  int prec = env.prec;
+  if (env.lowp != 0 && n > 0) {        // fp16 operands only if every product of the launch is marked eligible by its caller
     bool all = true;
     for (int i = 0; i < n; ++i) all = all && list[i].lowp != 0;
     if (all) prec = PREC_F16;
   }
   // launches capped to share the CUs with a recurrence kernel are the ones a caller puts on a SIDE stream: the scale slots of the
   // fp16x2 scheme are a process-wide ring ordered by one stream, so these launches take the scheme that needs none
-  if (prec == PREC_F16X2 && tl_wg_cap > 0) prec = PREC_BF16X3;
+  if (prec == PREC_F16X2 && env.wg_cap > 0) prec = PREC_BF16X3;
   // deterministic calls: split launches run on the 128 x 128 bf16x3 kernel, the one the fix-up epilogue is instantiated for (fp16x2 asks
   // for less accuracy than that, so it may have it); the f32 and single-term-fp16 schemes keep their kernels with one whole tile per workgroup
-  const bool det = tl_det != 0;
-  if (det && prec == PREC_F16X2) prec = PREC_BF16X3;
-  int TL = 128, TLM = 128;
-  for (int pass = 0; pass < 3; ++pass) {
-    memset(&grp, 0, sizeof(grp));
-    twolvl = any_store = false;
-    tiles = 0; flops = 0; min_kt = 0x7fffffff;
-    bool tall_ok = true;       // 256-row tiles waste at most 10 % more rows than 128-row tiles on every problem
-    for (int i = 0; i < n; ++i) {
-      const GemmArgs& g = list[i];
-      if (g.M <= 0 || g.N <= 0 || g.K <= 0 || g.batch <= 0) continue;
-      GemmArgs& a = grp.g[grp.n];
-      bool tl = false;
-      ASTK_TRY(gemm_prepare(layout, g, a, tl, TLM, TL));
-      twolvl = twolvl || tl;
-      grp.iter_start[grp.n] = grp.iters_total;
-      grp.iters_total += a.iters_total;
-      tiles += (long)a.tiles_mn * g.batch;
-      flops += 2.0 * g.M * g.N * (double)g.K * g.batch;
-      any_store = any_store || g.mode == GEMM_STORE;
-      min_kt = std::min(min_kt, a.kt);
-      tall_ok = tall_ok && cdiv(g.M, 256) * 256 * 10 <= cdiv(g.M, 128) * 128 * 11;
-      ++grp.n;
-    }
-    if (pass > 0) break;        // pass 0 sizes the launch with 128-tiles and picks; pass 1 re-plans with the chosen tile
-    // (measured, scratch/gemm_bench.py: 40 tiles x 32 k-iterations 33 -> 18 us, 1 tile x 4800 57 -> 38 us, 600 tiles x 8 42 -> 38 us;
-    //  200 tiles x 32 is 5 % faster with 128-tiles)
-    int max_kt = 0;
-    for (int i = 0; i < grp.n; ++i) max_kt = std::max(max_kt, grp.g[i].kt);
-    bool small = grp.iters_total < 256L * wgs_per_cu(128) * 10 * (32 / BK) && (tiles < 192 || max_kt <= 12 * (16 / BK > 0 ? 16 / BK : 1));
-    // (a capped launch -- work beside a recurrence kernel on a side stream -- is "small" only if its 128-tiles cannot fill the CAPPED grid:
-    //  a chunk of the layer-0 projection is 64 tiles for 64 workgroups, one whole tile each; as 64-tiles it ran 240 us instead of 140)
-    if (tl_wg_cap > 0) small = small && 2 * tiles < tl_wg_cap;
-    // 256 x 128 tiles on the 12-wave kernel (round 5): launches of 20 GFLOP and more whose M extents waste at most 10 % more rows than
-    // with 128-row tiles -- measured per launch of the train step (scratch/r5_gemm_t256.sh): 3-6 % faster on every launch above 200 us,
-    // slower on the small ones (6400 x 512 x 512: 40 -> 58 us)
-    const double big_flops = tune(TUNE_GEMM_T256_ABOVE);
-    const bool big = prec == PREC_BF16X3 && BK == 16 && tall_ok && flops >= big_flops && !small;
-    int want = force_tl == 64 || force_tl == 128 || force_tl == 256 ? force_tl : (small ? 64 : (big ? 256 : 128));
-    if (det && prec == PREC_BF16X3) want = 128;
-    if (want == 256 && (prec != PREC_BF16X3 || BK != 16)) want = 128;
-    if (want == 64 && prec == PREC_F16) want = 128;        // (the fp16 variant is instantiated for 128-tiles only)
-    if (want == 128) break;
-    TLM = want;
-    TL = want == 256 ? 128 : want;
+  if (env.det && prec == PREC_F16X2) prec = PREC_BF16X3;
+  return prec;
+}
+
+// Step 2: tile choice.  tiles_mn and iters_total depend on the tile, kt does not: the launch is sized with 128-tiles (no operand is
+// checked here), the tile chosen, and the group then filled once with the chosen tile.
+struct GemmSize128 { long tiles, iters; int max_kt; double flops; bool tall_ok; };
+static GemmSize128 plan_size128(const GemmArgs* list, int n) {
+  GemmSize128 z = {0, 0, 0, 0.0, true};
+  for (int i = 0; i < n; ++i) {
+    const GemmArgs& g = list[i];
+    if (gemm_skipped(g)) continue;
+    const int tiles_mn = cdiv(g.M, 128) * cdiv(g.N, 128), kt = cdiv(g.K, BK);
+    z.tiles += (long)tiles_mn * g.batch;
+    z.iters += (long)tiles_mn * g.batch * kt;
+    z.max_kt = std::max(z.max_kt, kt);
+    z.flops += 2.0 * g.M * g.N * (double)g.K * g.batch;
+    z.tall_ok = z.tall_ok && cdiv(g.M, 256) * 256 * 10 <= cdiv(g.M, 128) * 128 * 11;      // 256-row tiles waste at most 10 % more rows
   }
-  // A small launch does not repay an absolute-maximum pass (a launch of its own, 6 us at least): three-term bf16 operands need no scales
-  if (prec == PREC_F16X2 && flops < g_small_flops.load()) {
-    bool given = true;      // ... unless the caller supplied every maximum already
-    for (int i = 0; i < grp.n; ++i) given = given && grp.g[i].amaxA && grp.g[i].amaxB;
-    if (!given) prec = PREC_BF16X3;
+  return z;
+}
+// Tile edge: 128 unless the whole launch is too small to keep the chip busy with 128-tiles (fewer k-iterations than the stream-K
+// threshold of plan_grid, and either too few tiles for the CUs or tiles so shallow that their ramp dominates): then 64-tiles give 4x the
+// workgroups, each a quarter of the work.  astk_set_tuning("gemm.tile", 64 | 128 | 256) forces one.  Returns TLM; TL = min(TLM, 128).
+static int plan_tile(const GemmSize128& z, int prec, const GemmEnv& env) {
+  // (measured, scratch/gemm_bench.py: 40 tiles x 32 k-iterations 33 -> 18 us, 1 tile x 4800 57 -> 38 us, 600 tiles x 8 42 -> 38 us;
+  //  200 tiles x 32 is 5 % faster with 128-tiles)
+  bool small = z.iters < 256L * wgs_per_cu(128) * 10 * (32 / BK) && (z.tiles < 192 || z.max_kt <= 12 * (16 / BK > 0 ? 16 / BK : 1));
+  // (a capped launch -- work beside a recurrence kernel on a side stream -- is "small" only if its 128-tiles cannot fill the CAPPED grid:
+  //  a chunk of the layer-0 projection is 64 tiles for 64 workgroups, one whole tile each; as 64-tiles it ran 240 us instead of 140)
+  if (env.wg_cap > 0) small = small && 2 * z.tiles < env.wg_cap;
+  // 256 x 128 tiles on the 12-wave kernel (round 5): launches of 20 GFLOP and more whose M extents waste at most 10 % more rows than
+  // with 128-row tiles -- measured per launch of the train step (scratch/r5_gemm_t256.sh): 3-6 % faster on every launch above 200 us,
+  // slower on the small ones (6400 x 512 x 512: 40 -> 58 us)
+  const bool big = prec == PREC_BF16X3 && BK == 16 && z.tall_ok && z.flops >= env.t256_above && !small;
+  const int f = env.force_tl;
+  int want = f == 64 || f == 128 || f == 256 ? f : (small ? 64 : (big ? 256 : 128));
+  if (env.det && prec == PREC_BF16X3) want = 128;
+  if (want == 256 && (prec != PREC_BF16X3 || BK != 16)) want = 128;
+  if (want == 64 && prec == PREC_F16) want = 128;        // (the fp16 variant is instantiated for 128-tiles only)
+  return want;
+}
+
+// Step 3: fill the group with P.TLM x P.TL tiles and take the group-wide facts.  Products with a non-positive extent are skipped.
+// (`prec` only decides the stream-K granule: f32 or not, which the small-launch downgrade behind this step cannot change.)
+static int plan_fill(int layout, const GemmArgs* list, int n, int prec, GemmPlan& P) {
+  GemmGroup& grp = P.grp;
+  memset(&grp, 0, sizeof(grp));
+  P.a_kr = layout == GEMM_TN; P.b_kr = layout != GEMM_NT;
+  P.twolvl = P.any_store = P.any_accum = false;
+  P.uniform_kt = true;
+  P.tiles = 0; P.flops = 0; P.min_kt = 0x7fffffff; P.max_kt = 0;
+  for (int i = 0; i < n; ++i) {
+    const GemmArgs& g = list[i];
+    if (gemm_skipped(g)) continue;
+    GemmArgs& a = grp.g[grp.n];
+    bool tl = false;
+    ASTK_TRY(gemm_prepare(layout, g, a, tl, P.TLM, P.TL));
+    a.cs = 0; a.chunk_iters = 0;
+    P.twolvl = P.twolvl || tl;
+    grp.iter_start[grp.n] = grp.iters_total;
+    grp.iters_total += a.iters_total;
+    P.tiles += (long)a.tiles_mn * g.batch;
+    P.flops += 2.0 * g.M * g.N * (double)g.K * g.batch;
+    P.any_store = P.any_store || g.mode == GEMM_STORE;
+    P.any_accum = P.any_accum || g.mode == GEMM_ACCUM;
+    P.uniform_kt = P.uniform_kt && a.kt == grp.g[0].kt;
+    P.min_kt = std::min(P.min_kt, a.kt);
+    P.max_kt = std::max(P.max_kt, a.kt);
+    ++grp.n;
   }
-  const int WGS_PER_CU = wgs_per_cu(TL, prec);
-  if (grp.n == 0) return 0;
   for (int i = grp.n; i <= GEMM_GROUP_MAX; ++i) grp.iter_start[i] = grp.iters_total;
   grp.unit = prec != PREC_F32 ? 2 : 1;
   for (int i = 0; i < grp.n; ++i)
     if (grp.g[i].kt & 1) grp.unit = 1;
-  if (twolvl) {   // a plain operand next to a two-level one: express it as one group of INT_MAX rows
-    const bool a_kr = layout == GEMM_TN, b_kr = layout != GEMM_NT;
+  if (P.twolvl) {   // a plain operand next to a two-level one: express it as one group of INT_MAX rows
     for (int i = 0; i < grp.n; ++i) {
       GemmArgs& a = grp.g[i];
-      if (a_kr && a.A.tn <= 0) { a.A.tn = 0x7fffffff; a.A.sg = 0; a.A.st = a.A.ld; }
-      if (b_kr && a.B.tn <= 0) { a.B.tn = 0x7fffffff; a.B.sg = 0; a.B.st = a.B.ld; }
+      if (P.a_kr && a.A.tn <= 0) { a.A.tn = 0x7fffffff; a.A.sg = 0; a.A.st = a.A.ld; }
+      if (P.b_kr && a.B.tn <= 0) { a.B.tn = 0x7fffffff; a.B.sg = 0; a.B.st = a.B.ld; }
     }
   }
-  // Grid (measured on MI355X, scratch/gemm_bench.py): a launch with enough k-iterations is split evenly over 256 * wgs_per_cu
-  // workgroups (co-resident workgroups hide each other's LDS-store / barrier phases; the grid must be a multiple of 256 or the
-  // CUs are loaded unevenly: 600 workgroups for 1200 tiles ran 12 % slower than 768) -- 100-125 TFLOP/s on the train step's big
-  // shapes against 60-93 for one-tile-per-workgroup launches.  Smaller products keep one tile per workgroup unless they have too
-  // few tiles to occupy the chip; then their k range is split as well.
-  const int force_g = (int)tune(TUNE_GEMM_GRID);   // tuning hook
+  return 0;
+}
+
+// A small launch does not repay an absolute-maximum pass (a launch of its own, 6 us at least): three-term bf16 operands need no scales
+// ... unless the caller supplied every maximum already.  Behind the tile choice, in front of the grid.
+static int plan_scheme_small(const GemmPlan& P, const GemmEnv& env) {
+  if (P.prec != PREC_F16X2 || !(P.flops < env.small_flops)) return P.prec;
+  bool given = true;
+  for (int i = 0; i < P.grp.n; ++i) given = given && P.grp.g[i].amaxA && P.grp.g[i].amaxB;
+  return given ? P.prec : PREC_BF16X3;
+}
+
+// Step 4: grid (measured on MI355X, scratch/gemm_bench.py): a launch with enough k-iterations is split evenly over 256 * wgs_per_cu
+// workgroups (co-resident workgroups hide each other's LDS-store / barrier phases; the grid must be a multiple of 256 or the
+// CUs are loaded unevenly: 600 workgroups for 1200 tiles ran 12 % slower than 768) -- 100-125 TFLOP/s on the train step's big
+// shapes against 60-93 for one-tile-per-workgroup launches.  Smaller products keep one tile per workgroup unless they have too
+// few tiles to occupy the chip; then their k range is split as well.
+static void plan_grid(GemmPlan& P, const GemmEnv& env) {
+  const GemmGroup& grp = P.grp;
+  const int wgs = wgs_per_cu(P.TL, P.prec);
+  long G = P.tiles;
+  bool aligned = true;
+  if (grp.iters_total >= 256L * wgs * 10 * (32 / BK)) { G = 256 * wgs; aligned = false; }
+  else if (P.tiles < 160) {
+    const long g2 = std::min(256L, grp.iters_total / (4 * (32 / BK)));
+    if (g2 > P.tiles) { G = g2; aligned = false; }
+  }
+  if (env.force_g > 0) { G = std::min<long>(env.force_g, grp.iters_total); aligned = false; }
+  if (env.wg_cap > 0 && G > env.wg_cap) { G = env.wg_cap; aligned = false; }
+  if (env.det && P.prec != PREC_BF16X3) { G = P.tiles; aligned = true; }        // no fix-up kernel for these schemes: whole tiles only
+  if (env.det && !aligned && G > FIX_WGS) G = FIX_WGS;
+  // one tile per workgroup needs boundaries on tile boundaries: only true for uniform kt; otherwise fall back to an even split
+  if (aligned && grp.n > 1 && !P.uniform_kt) { G = std::min(256L * wgs, std::max(1L, grp.iters_total / std::max(1, P.min_kt))); aligned = false; }
+  P.G = G; P.aligned = aligned;
+}
+
+// Step 5: hybrid schedule (kernel: "Hybrid schedule"): a stream-K launch of the split schemes whose tiles all have the same depth and
+// outnumber the grid runs floor(tiles / G) data-parallel waves of whole tiles in XCD-local blocks first; only the rest is split stream-K.
+// ("gemm.hybrid" 0: everything stream-K in row-major tile order, the schedule of rounds 1-4.)
+static void plan_hybrid(GemmPlan& P, const GemmEnv& env, bool forward_rule) {
+  GemmGroup& grp = P.grp;
+  grp.dp_waves = 0; grp.dp_kt = 0; grp.rem_start = 0;
+  if (!env.hybrid || P.prec == PREC_F32 || P.aligned || (P.G % 8) != 0 || P.tiles < P.G) return;
+  // (C += AB goes out as atomic adds: in data-parallel waves all workgroups reach their epilogues together and the atomics arrive in
+  //  bursts -- 6400 x 3072 x 1024: 247 -> 271 us; those launches stay all stream-K, where the epilogues are staggered)
+  if (!P.uniform_kt || P.any_accum) return;
+  grp.dp_waves = (int)(P.tiles / P.G);
+  // (forward launches: one wave fewer -- the remainder then has >= G tiles, every stream-K range >= one tile, <= 2 contributors per split
+  //  tile: run-to-run reproducible sums, see GemmForwardScope)
+  if (forward_rule && grp.dp_waves > 0) --grp.dp_waves;
+  grp.dp_kt = grp.g[0].kt;
+  grp.rem_start = (long)grp.dp_waves * P.G * grp.dp_kt;
+  const int chunk = (int)(P.G / 8);          // tiles of one XCD and wave
+  for (int i = 0; i < grp.n; ++i) {
+    GemmArgs& a = grp.g[i];
+    const int tiles_n = cdiv(a.N, P.TL);
+    int cols = 1;                            // block width: a power of two <= tiles_n, near sqrt(chunk) from above (rows + cols minimal)
+    while (cols * 2 <= tiles_n && cols * 2 * cols * 2 <= 2 * chunk) cols *= 2;
+    a.bm = std::max(1, chunk / cols);
+  }
+}
+
+// Step 6: forward launches outside the hybrid branch (fewer tiles than workgroups, mixed depths in a group, a capped or odd grid): the same
+// guarantee -- at most TWO contributors per split tile, so that the float atomics commute and the forward pass is bit-reproducible whatever
+// shapes occur -- by shrinking the grid until every stream-K range is at least as deep as the deepest tile, or to exactly two half-tile
+// ranges per tile where the depths allow it (round-5 advice: the guarantee used to depend on which shapes happened to come by).
+static void plan_forward_cap(GemmPlan& P, const GemmEnv& env, bool forward_rule) {
+  if (!forward_rule || P.aligned || P.grp.dp_waves != 0 || env.forward_pairs == 0.0) return;
+  const long gmax = std::max(1L, P.grp.iters_total / std::max(1, P.max_kt));
+  if (P.G > gmax) P.G = (P.uniform_kt && P.max_kt % (2 * P.grp.unit) == 0 && P.G >= 2 * P.tiles) ? 2 * P.tiles : gmax;
+}
+
+// Step 7: few tiles, deep K, accumulating output (the weight gradients: TN 512 x 1152 x 38400 is 18 tiles of 2400 k-iterations):
+// chunk-major order, chunk = the even divisor of kt nearest to a workgroup's share.  ("gemm.chunk" 0: tile-major always.)
+static void plan_chunk_major(GemmPlan& P, const GemmEnv& env) {
+  GemmArgs& a = P.grp.g[0];
+  if (!env.chunk || env.det || P.grp.n != 1 || P.aligned || P.grp.dp_waves != 0 || a.mode == GEMM_STORE || P.prec == PREC_F32) return;
+  if (!(P.tiles * env.chunk_div <= P.G) || a.kt < 128) return;
+  const long share = P.grp.iters_total / P.G;      // k-iterations per workgroup
+  int best = 0;
+  for (int c = 2; c <= a.kt; c += 2)
+    if (a.kt % c == 0 && c >= share / 2 && c <= share * 2 && (best == 0 || labs(c - share) < labs(best - share))) best = c;
+  if (best > 0 && best < a.kt) { a.cs = best; a.chunk_iters = P.tiles * (long)best; }
+}
+
+// Step 8: split tiles.  Deterministic launches sum them in the fix-up epilogue; otherwise the tiles of GEMM_STORE products that several
+// workgroups accumulate into are zeroed first (with the maximum pass when there is one).  (Builds with -DASTK_GEMM_TICKET=1: the ticket
+// protocol instead -- kernel: "Split tiles without a zeroing launch", measured, off.)
+static void plan_split_tiles(GemmPlan& P, const GemmEnv& env) {
+  GemmGroup& grp = P.grp;
+  P.fixup = env.det && !P.aligned && P.prec == PREC_BF16X3 && P.TL == 128 && P.TLM == 128;
+  P.need_zero = !P.aligned && P.any_store && P.G > 1 && !P.fixup;
+  P.want_ticket = false; P.ticket_tiles = 0;
+  if (P.need_zero && ASTK_GEMM_TICKET && env.ticket) {
+    long ntiles = 0;
+    bool fits = true;
+    for (int i = 0; i < grp.n; ++i) {
+      grp.tick_base[i] = (int)ntiles;
+      ntiles += (grp.iter_start[i + 1] - grp.iter_start[i]) / grp.g[i].kt;
+      fits = fits && grp.g[i].kt < (int)TICK_DONE;
+    }
+    if (fits && ntiles < (1L << 27)) { P.want_ticket = true; P.ticket_tiles = ntiles; P.need_zero = false; }
+  }
+  P.zero_vec = true;
+  for (int i = 0; i < grp.n; ++i) {
+    const GemmArgs& a = grp.g[i];
+    P.zero_vec = P.zero_vec && aligned16(a.C) && (a.sC % 4) == 0 && (a.c_tn > 0 ? (a.c_sg % 4) == 0 && (a.c_st % 4) == 0 : (a.ldc % 4) == 0);
+  }
+}
+
+// The plan of one grouped launch.  Pure: no HIP call, no static, no atomic; writes `plan` and, on failure, the error text.
+static int gemm_plan(int layout, const GemmArgs* list, int n, const GemmEnv& env, GemmPlan& P) {
+  ASTK_CHECK(layout == GEMM_NT || layout == GEMM_NN || layout == GEMM_TN, "gemm: bad layout %d", layout);
+  ASTK_CHECK(n >= 0 && n <= GEMM_GROUP_MAX, "gemm: group of %d products (max %d)", n, GEMM_GROUP_MAX);
+  P.prec = plan_scheme(list, n, env);
+  P.TLM = plan_tile(plan_size128(list, n), P.prec, env);
+  P.TL = P.TLM == 256 ? 128 : P.TLM;
+  ASTK_TRY(plan_fill(layout, list, n, P.prec, P));
+  if (P.grp.n == 0) return 0;
+  P.prec = plan_scheme_small(P, env);
   // (forward ops open a GemmForwardScope; "gemm.forward_pairs" 2 applies their two-contributor rule to EVERY launch of the process -- plain
   //  astk_gemm_f32 calls included: how the tests reach it on the product library with shapes no op produces)
-  const bool forward_rule = tl_forward != 0 || tune(TUNE_GEMM_FORWARD_PAIRS) >= 2;
-  long G = tiles;
-  bool aligned = true;   // workgroup boundaries fall on tile boundaries
-  if (grp.iters_total >= 256L * WGS_PER_CU * 10 * (32 / BK)) { G = 256 * WGS_PER_CU; aligned = false; }
-  else if (tiles < 160) {
-    const long g2 = std::min(256L, grp.iters_total / (4 * (32 / BK)));
-    if (g2 > tiles) { G = g2; aligned = false; }
-  }
-  if (force_g > 0) { G = std::min<long>(force_g, grp.iters_total); aligned = false; }
-  if (tl_wg_cap > 0 && G > tl_wg_cap) { G = tl_wg_cap; aligned = false; }
-  if (det && prec != PREC_BF16X3) { G = tiles; aligned = true; }        // no fix-up kernel for these schemes: whole tiles only
-  if (det && !aligned && G > FIX_WGS) G = FIX_WGS;
-  if (aligned && grp.n > 1) {
-    // one tile per workgroup needs boundaries on tile boundaries: only true for uniform kt; otherwise fall back to an even split
-    bool uniform = true;
-    for (int i = 1; i < grp.n; ++i) uniform = uniform && grp.g[i].kt == grp.g[0].kt;
-    if (!uniform) { G = std::min(256L * WGS_PER_CU, std::max(1L, grp.iters_total / std::max(1, min_kt))); aligned = false; }
-  }
-  // Hybrid schedule (kernel: "Hybrid schedule"): a stream-K launch of the split schemes whose tiles all have the same depth and outnumber
-  // the grid runs floor(tiles / G) data-parallel waves of whole tiles in XCD-local blocks first; only the rest is split stream-K.
-  // ("gemm.hybrid" 0: everything stream-K in row-major tile order, the schedule of rounds 1-4.)
-  const bool hybrid_on = tune_on(TUNE_GEMM_HYBRID);
-  grp.dp_waves = 0; grp.dp_kt = 0; grp.rem_start = 0;
-  if (hybrid_on && prec != PREC_F32 && !aligned && (G % 8) == 0 && tiles >= G) {
-    bool uniform = true;
-    for (int i = 1; i < grp.n; ++i) uniform = uniform && grp.g[i].kt == grp.g[0].kt;
-    // (C += AB goes out as atomic adds: in data-parallel waves all workgroups reach their epilogues together and the atomics arrive in
-    //  bursts -- 6400 x 3072 x 1024: 247 -> 271 us; those launches stay all stream-K, where the epilogues are staggered)
-    for (int i = 0; i < grp.n; ++i) uniform = uniform && grp.g[i].mode != GEMM_ACCUM;
-    if (uniform) {
-      grp.dp_waves = (int)(tiles / G);
-      // (forward launches: one wave fewer -- the remainder then has >= G tiles, every stream-K range >= one tile, <= 2 contributors per split
-      //  tile: run-to-run reproducible sums, see GemmForwardScope)
-      if (forward_rule && grp.dp_waves > 0) --grp.dp_waves;
-      grp.dp_kt = grp.g[0].kt;
-      grp.rem_start = (long)grp.dp_waves * G * grp.dp_kt;
-      const int chunk = (int)(G / 8);          // tiles of one XCD and wave
-      for (int i = 0; i < grp.n; ++i) {
-        GemmArgs& a = grp.g[i];
-        const int tiles_n = cdiv(a.N, TL);
-        int cols = 1;                          // block width: a power of two <= tiles_n, near sqrt(chunk) from above (rows + cols minimal)
-        while (cols * 2 <= tiles_n && cols * 2 * cols * 2 <= 2 * chunk) cols *= 2;
-        a.bm = std::max(1, chunk / cols);
-      }
+  const bool forward_rule = env.forward != 0 || env.forward_pairs >= 2;
+  plan_grid(P, env);
+  plan_hybrid(P, env, forward_rule);
+  plan_forward_cap(P, env, forward_rule);
+  plan_chunk_major(P, env);
+  plan_split_tiles(P, env);
+  return 0;
+}
+
+// One line per product: the "gemm.log" text and what astk_debug_gemm_plan returns (scratch/gemm_step_trace.py parses the prefix up to kt).
+static int gemm_plan_line(char* buf, size_t cap, const GemmPlan& P, int layout, int i) {
+  const GemmArgs& a = P.grp.g[i];
+  return snprintf(buf, cap, "astk_gemm layout=%d M=%d N=%d K=%d batch=%d mode=%d twolvl=%d group=%d/%d G=%ld kt=%d tile=%d dp_waves=%d bm=%d cs=%d "
+                  "prec=%d unit=%d aligned=%d rem_start=%ld chunk_iters=%ld zero=%d zero_vec=%d fix=%d ticket=%ld\n", layout, a.M, a.N, a.K, a.batch,
+                  a.mode, (int)P.twolvl, i, P.grp.n, P.G, a.kt, P.TLM * 1000 + P.TL, P.grp.dp_waves, a.bm, a.cs, P.prec, P.grp.unit, (int)P.aligned,
+                  P.grp.rem_start, a.chunk_iters, (int)P.need_zero, (int)P.zero_vec, (int)P.fixup, P.want_ticket ? P.ticket_tiles : 0L);
+}
+static void gemm_log(const GemmPlan& P, int layout) {
+  char line[512];
+  for (int i = 0; i < P.grp.n; ++i)
+    if (gemm_plan_line(line, sizeof(line), P, layout, i) > 0) fputs(line, stderr);
+}
+
+// fp16x2: one absolute-maximum pass over both operands of every product whose maximum the caller did not supply (part of the GEMM's cost,
+// inside its timing scope); with the split tiles' zeroing in the same launch when both are needed.  One generation per launch.
+static int gemm_absmax_pass(GemmPlan& P, bool log, hipStream_t s, int& amax_blocks) {
+  GemmGroup& grp = P.grp;
+  unsigned long long* ring = amax_ring();
+  ASTK_CHECK(ring != nullptr, "gemm: no absmax ring");
+  AmaxJobs J;
+  memset(&J, 0, sizeof(J));
+  const unsigned gen = next_amax_gen(s);
+  J.gen = gen;
+  auto list_view = [](MatView v) { if (v.tn == 0x7fffffff) v.tn = 0; return v; };    // (a plain operand dressed as one group: plan_fill)
+  for (int i = 0; i < grp.n; ++i) {
+    GemmArgs& a = grp.g[i];
+    unsigned long long* sl = ring + (((size_t)gen * (2 * GEMM_GROUP_MAX) + 2 * i) % (AMAX_RING_SLOTS / 2)) * AMAX_SLOT_WORDS;
+    unsigned long long* slB = sl + AMAX_SLOT_WORDS;
+    const MatView A = list_view(a.A), B = list_view(a.B);
+    if (!a.amaxA) {          // (a caller that uses an operand in several launches passes its maximum in: gemm_amax)
+      a.amaxA = sl;
+      amax_add(J, A, P.a_kr, a.M, a.K, a.batch, a.sA, operand_span(A, P.a_kr, a.M, a.K).contig, sl);
+    }
+    if (!a.amaxB) {
+      a.amaxB = slB;
+      amax_add(J, B, P.b_kr, a.N, a.K, a.batch, a.sB, operand_span(B, P.b_kr, a.N, a.K).contig, slB);
     }
   }
-  // Forward launches outside the hybrid branch (fewer tiles than workgroups, mixed depths in a group, a capped or odd grid): the same
-  // guarantee -- at most TWO contributors per split tile, so that the float atomics commute and the forward pass is bit-reproducible whatever
-  // shapes occur -- by shrinking the grid until every stream-K range is at least as deep as the deepest tile, or to exactly two half-tile
-  // ranges per tile where the depths allow it (round-5 advice: the guarantee used to depend on which shapes happened to come by).
-  if (forward_rule && !aligned && grp.dp_waves == 0 && tune_on(TUNE_GEMM_FORWARD_PAIRS)) {
-    int max_kt = 0;
-    bool uniform = true;
-    for (int i = 0; i < grp.n; ++i) { max_kt = std::max(max_kt, grp.g[i].kt); uniform = uniform && grp.g[i].kt == grp.g[0].kt; }
-    const long gmax = std::max(1L, grp.iters_total / std::max(1, max_kt));
-    if (G > gmax) G = (uniform && max_kt % (2 * grp.unit) == 0 && G >= 2 * tiles) ? 2 * tiles : gmax;
+  if (log)
+    for (int i = 0; i < J.n; ++i)
+      fprintf(stderr, "astk_gemm absmax region %d/%d: %ld x %ld rows (ld %ld) x %d floats = %.1f MB, %d blocks\n", i, J.n, J.r[i].nb, J.r[i].rows, J.r[i].ld,
+              J.r[i].inner, 4e-6 * J.r[i].nb * J.r[i].rows * J.r[i].inner, J.blk_start[i + 1] - J.blk_start[i]);
+  amax_blocks = J.n > 0 ? J.blk_start[J.n] : 0;
+  if (amax_blocks > 0) {
+    if (P.need_zero) hipLaunchKernelGGL(k_absmax_zero, dim3((unsigned)(amax_blocks + (P.G - 1) * ZERO_PARTS)), dim3(256), 0, s, J, grp, (int)P.G, P.TLM, P.TL, P.zero_vec ? 1 : 0);
+    else hipLaunchKernelGGL(k_absmax, dim3((unsigned)amax_blocks), dim3(256), 0, s, J);
   }
-  // Few tiles, deep K, accumulating output (the weight gradients: TN 512 x 1152 x 38400 is 18 tiles of 2400 k-iterations): chunk-major order,
-  // chunk = the divisor of kt nearest to a workgroup's share.  ("gemm.chunk" 0: tile-major always.)
-  const bool chunk_on = tune_on(TUNE_GEMM_CHUNK);
-  const int chunk_div = (int)tune(TUNE_GEMM_CHUNK_DIV);      // (tuning hook: tiles * div <= G)
-  for (int i = 0; i < grp.n; ++i) { grp.g[i].cs = 0; grp.g[i].chunk_iters = 0; }
-  if (chunk_on && !det && grp.n == 1 && !aligned && grp.dp_waves == 0 && grp.g[0].mode != GEMM_STORE && prec != PREC_F32 && tiles * chunk_div <= G && grp.g[0].kt >= 128) {
-    GemmArgs& a = grp.g[0];
-    const long share = grp.iters_total / G;      // k-iterations per workgroup
-    int best = 0;
-    for (int c = 2; c <= a.kt; c += 2)
-      if (a.kt % c == 0 && c >= share / 2 && c <= share * 2 && (best == 0 || labs(c - share) < labs(best - share))) best = c;
-    if (best > 0 && best < a.kt) { a.cs = best; a.chunk_iters = tiles * (long)best; }
+  return 0;
+}
+
+// The kernel of one <tile, scheme, rows, fix-up> choice for the launch's layout.  (NT has no K-major operand, hence no TWOLVL variant.)
+template <int TL, int PREC, int TLM, bool FIX = false>
+static void gemm_dispatch(int layout, bool twolvl, dim3 grid, hipStream_t s, const GemmGroup& grp) {
+  const dim3 block(gemm_threads(PREC, TLM));
+  switch (layout) {
+    case GEMM_NT: hipLaunchKernelGGL((gemm_f32_kernel<TL, true, true, false, PREC, TLM, FIX>), grid, block, 0, s, grp); break;
+    case GEMM_NN:
+      if (twolvl) hipLaunchKernelGGL((gemm_f32_kernel<TL, true, false, true, PREC, TLM, FIX>), grid, block, 0, s, grp);
+      else hipLaunchKernelGGL((gemm_f32_kernel<TL, true, false, false, PREC, TLM, FIX>), grid, block, 0, s, grp);
+      break;
+    default:
+      if (twolvl) hipLaunchKernelGGL((gemm_f32_kernel<TL, false, false, true, PREC, TLM, FIX>), grid, block, 0, s, grp);
+      else hipLaunchKernelGGL((gemm_f32_kernel<TL, false, false, false, PREC, TLM, FIX>), grid, block, 0, s, grp);
+      break;
   }
-  const bool log_shapes = tune_on(TUNE_GEMM_LOG);
-  if (log_shapes)
-    for (int i = 0; i < grp.n; ++i)
-      fprintf(stderr, "astk_gemm layout=%d M=%d N=%d K=%d batch=%d mode=%d twolvl=%d group=%d/%d G=%ld kt=%d tile=%d dp_waves=%d bm=%d cs=%d\n", layout, grp.g[i].M,
-              grp.g[i].N, grp.g[i].K, grp.g[i].batch, grp.g[i].mode, (int)twolvl, i, grp.n, G, grp.g[i].kt, TLM * 1000 + TL, grp.dp_waves, grp.g[i].bm, grp.g[i].cs);
-  ProfScope prof(PROF_GEMM, s, flops);
+}
+static void gemm_launch_kernel(const GemmPlan& P, int layout, hipStream_t s) {
+  const dim3 grid((unsigned)P.G, 1, 1);
+  const GemmGroup& grp = P.grp;
+  const bool tw = P.twolvl, t64 = P.TL == 64;
+  if (P.prec == PREC_F32) {
+    if (t64) gemm_dispatch<64, PREC_F32, 64>(layout, tw, grid, s, grp); else gemm_dispatch<128, PREC_F32, 128>(layout, tw, grid, s, grp);
+  } else if (P.prec == PREC_F16) { gemm_dispatch<128, PREC_F16, 128>(layout, tw, grid, s, grp);
+  } else if (P.prec == PREC_F16X2) {
+    if (t64) gemm_dispatch<64, PREC_F16X2, 64>(layout, tw, grid, s, grp); else gemm_dispatch<128, PREC_F16X2, 128>(layout, tw, grid, s, grp);
+  } else if (P.TLM == 256) {
+    if constexpr (BK == 16) gemm_dispatch<128, PREC_BF16X3, 256>(layout, tw, grid, s, grp);      // (three 256-row stages of a 32-deep tile do not fit LDS)
+  } else if (t64) { gemm_dispatch<64, PREC_BF16X3, 64>(layout, tw, grid, s, grp);
+  } else if (P.fixup) { gemm_dispatch<128, PREC_BF16X3, 128, true>(layout, tw, grid, s, grp);
+  } else { gemm_dispatch<128, PREC_BF16X3, 128>(layout, tw, grid, s, grp); }
+}
+
+// Everything of a planned launch that touches the device.  (`log`: "gemm.log", for the regions of the maximum pass.)
+static int gemm_execute(GemmPlan& P, int layout, bool log, hipStream_t s) {
+  GemmGroup& grp = P.grp;
+  ProfScope prof(PROF_GEMM, s, P.flops);
   if (prof_enabled()) {       // algorithmic bytes of the launch: every operand element read once, every result element written once
     double bytes = 0;
     for (int i = 0; i < grp.n; ++i) {
@@ -1550,105 +1757,27 @@ int gemm_launch_group(int layout, const GemmArgs* list, int n, hipStream_t s) {
     }
     prof_add_bytes(PROF_GEMM, bytes);
   }
-  dim3 grid((unsigned)G, 1, 1);
-  // GEMM_STORE + split tiles: the tiles several workgroups accumulate into are zeroed first (with the maximum pass when there is one).
-  // (Builds with -DASTK_GEMM_TICKET=1: the ticket protocol instead -- kernel: "Split tiles without a zeroing launch", measured, off.)
-  const bool ticket_on = ASTK_GEMM_TICKET && tune_on(TUNE_GEMM_TICKET);
   grp.tick = nullptr;
-  const bool fixup = det && !aligned && prec == PREC_BF16X3 && TL == 128 && TLM == 128;
-  bool need_zero = !aligned && any_store && G > 1 && !fixup;
-  if (need_zero && ticket_on) {
-    long ntiles = 0;
-    bool fits = true;
-    for (int i = 0; i < grp.n; ++i) {
-      grp.tick_base[i] = (int)ntiles;
-      ntiles += (grp.iter_start[i + 1] - grp.iter_start[i]) / grp.g[i].kt;
-      fits = fits && grp.g[i].kt < (int)TICK_DONE;
-    }
-    if (fits && ntiles < (1L << 27)) {
-      grp.tick = tick_table(s, (size_t)ntiles * TICK_WAVES);
-      ASTK_CHECK(grp.tick != nullptr, "gemm: no ticket table");
-      need_zero = false;
-    }
-  }
-  bool zero_vec = true;
-  for (int i = 0; i < grp.n; ++i) {
-    const GemmArgs& a = grp.g[i];
-    zero_vec = zero_vec && aligned16(a.C) && (a.sC % 4) == 0 && (a.c_tn > 0 ? (a.c_sg % 4) == 0 && (a.c_st % 4) == 0 : (a.ldc % 4) == 0);
+  if (P.want_ticket) {
+    grp.tick = tick_table(s, (size_t)P.ticket_tiles * TICK_WAVES);
+    ASTK_CHECK(grp.tick != nullptr, "gemm: no ticket table");
   }
   int amax_blocks = 0;
-  if (prec == PREC_F16X2) {
-    // one absolute-maximum pass over both operands of every product (part of the GEMM's cost, inside its timing scope)
-    unsigned long long* ring = amax_ring();
-    ASTK_CHECK(ring != nullptr, "gemm: no absmax ring");
-    AmaxJobs J;
-    memset(&J, 0, sizeof(J));
-    const unsigned gen = next_amax_gen(s);
-    J.gen = gen;
-    const bool a_kr = layout == GEMM_TN, b_kr = layout != GEMM_NT;
-    auto list_view = [](MatView v) { if (v.tn == 0x7fffffff) v.tn = 0; return v; };    // (a plain operand dressed as one group, see above)
-    for (int i = 0; i < grp.n; ++i) {
-      GemmArgs& a = grp.g[i];
-      unsigned long long* sl = ring + (((size_t)gen * (2 * GEMM_GROUP_MAX) + 2 * i) % (AMAX_RING_SLOTS / 2)) * AMAX_SLOT_WORDS;
-      unsigned long long* slB = sl + AMAX_SLOT_WORDS;
-      const long spa = a.A.tn > 0 && a.A.tn != 0x7fffffff && a_kr ? (long)((a.K - 1) / a.A.tn) * a.A.sg + (long)((a.K - 1) % a.A.tn) * a.A.st + ((a.M + 3) & ~3L) : a.spanA / 4;
-      const long spb = a.B.tn > 0 && a.B.tn != 0x7fffffff && b_kr ? (long)((a.K - 1) / a.B.tn) * a.B.sg + (long)((a.K - 1) % a.B.tn) * a.B.st + ((a.N + 3) & ~3L) : a.spanB / 4;
-      if (!a.amaxA) {          // (a caller that uses an operand in several launches passes its maximum in: gemm_amax)
-        a.amaxA = sl;
-        amax_add(J, list_view(a.A), a_kr, a.M, a.K, a.batch, a.sA, spa, sl);
-      }
-      if (!a.amaxB) {
-        a.amaxB = slB;
-        amax_add(J, list_view(a.B), b_kr, a.N, a.K, a.batch, a.sB, spb, slB);
-      }
-    }
-    if (log_shapes)
-      for (int i = 0; i < J.n; ++i)
-        fprintf(stderr, "astk_gemm absmax region %d/%d: %ld x %ld rows (ld %ld) x %d floats = %.1f MB, %d blocks\n", i, J.n, J.r[i].nb, J.r[i].rows, J.r[i].ld,
-                J.r[i].inner, 4e-6 * J.r[i].nb * J.r[i].rows * J.r[i].inner, J.blk_start[i + 1] - J.blk_start[i]);
-    amax_blocks = J.n > 0 ? J.blk_start[J.n] : 0;
-    if (amax_blocks > 0) {
-      if (need_zero) hipLaunchKernelGGL(k_absmax_zero, dim3((unsigned)(amax_blocks + (G - 1) * ZERO_PARTS)), dim3(256), 0, s, J, grp, (int)G, TLM, TL, zero_vec ? 1 : 0);
-      else hipLaunchKernelGGL(k_absmax, dim3((unsigned)amax_blocks), dim3(256), 0, s, J);
-    }
-  }
-  if (need_zero && amax_blocks == 0) hipLaunchKernelGGL(k_zero_split_tiles, dim3((unsigned)((G - 1) * ZERO_PARTS)), dim3(256), 0, s, grp, (int)G, TLM, TL, zero_vec ? 1 : 0);
-#define ASTK_GEMM_LAUNCH(T_, P_, M_)                                                                                              \
-  switch (layout) {                                                                                                               \
-    case GEMM_NT: hipLaunchKernelGGL((gemm_f32_kernel<T_, true, true, false, P_, M_>), grid, dim3(gemm_threads(P_, M_)), 0, s, grp); break;  \
-    case GEMM_NN:                                                                                                                 \
-      if (twolvl) hipLaunchKernelGGL((gemm_f32_kernel<T_, true, false, true, P_, M_>), grid, dim3(gemm_threads(P_, M_)), 0, s, grp);  \
-      else hipLaunchKernelGGL((gemm_f32_kernel<T_, true, false, false, P_, M_>), grid, dim3(gemm_threads(P_, M_)), 0, s, grp);        \
-      break;                                                                                                                      \
-    default:                                                                                                                      \
-      if (twolvl) hipLaunchKernelGGL((gemm_f32_kernel<T_, false, false, true, P_, M_>), grid, dim3(gemm_threads(P_, M_)), 0, s, grp); \
-      else hipLaunchKernelGGL((gemm_f32_kernel<T_, false, false, false, P_, M_>), grid, dim3(gemm_threads(P_, M_)), 0, s, grp);       \
-      break;                                                                                                                      \
-  }
-  if (prec == PREC_F32) {
-    if (TL == 64) { ASTK_GEMM_LAUNCH(64, PREC_F32, 64) } else { ASTK_GEMM_LAUNCH(128, PREC_F32, 128) }
-  } else if (prec == PREC_F16) { ASTK_GEMM_LAUNCH(128, PREC_F16, 128)
-  } else if (prec == PREC_F16X2) {
-    if (TL == 64) { ASTK_GEMM_LAUNCH(64, PREC_F16X2, 64) } else { ASTK_GEMM_LAUNCH(128, PREC_F16X2, 128) }
-  } else if (TLM == 256) {
-    if constexpr (BK == 16) { ASTK_GEMM_LAUNCH(128, PREC_BF16X3, 256) }      // (three 256-row stages of a 32-deep tile do not fit LDS)
-  } else if (TL == 64) { ASTK_GEMM_LAUNCH(64, PREC_BF16X3, 64)
-  } else if (fixup) {
-    switch (layout) {
-      case GEMM_NT: hipLaunchKernelGGL((gemm_f32_kernel<128, true, true, false, PREC_BF16X3, 128, true>), grid, dim3(gemm_threads(PREC_BF16X3, 128)), 0, s, grp); break;
-      case GEMM_NN:
-        if (twolvl) hipLaunchKernelGGL((gemm_f32_kernel<128, true, false, true, PREC_BF16X3, 128, true>), grid, dim3(gemm_threads(PREC_BF16X3, 128)), 0, s, grp);
-        else hipLaunchKernelGGL((gemm_f32_kernel<128, true, false, false, PREC_BF16X3, 128, true>), grid, dim3(gemm_threads(PREC_BF16X3, 128)), 0, s, grp);
-        break;
-      default:
-        if (twolvl) hipLaunchKernelGGL((gemm_f32_kernel<128, false, false, true, PREC_BF16X3, 128, true>), grid, dim3(gemm_threads(PREC_BF16X3, 128)), 0, s, grp);
-        else hipLaunchKernelGGL((gemm_f32_kernel<128, false, false, false, PREC_BF16X3, 128, true>), grid, dim3(gemm_threads(PREC_BF16X3, 128)), 0, s, grp);
-        break;
-    }
-  } else { ASTK_GEMM_LAUNCH(128, PREC_BF16X3, 128) }
-#undef ASTK_GEMM_LAUNCH
+  if (P.prec == PREC_F16X2) ASTK_TRY(gemm_absmax_pass(P, log, s, amax_blocks));
+  if (P.need_zero && amax_blocks == 0)
+    hipLaunchKernelGGL(k_zero_split_tiles, dim3((unsigned)((P.G - 1) * ZERO_PARTS)), dim3(256), 0, s, grp, (int)P.G, P.TLM, P.TL, P.zero_vec ? 1 : 0);
+  gemm_launch_kernel(P, layout, s);
   ASTK_LAUNCH_CHECK();
   return 0;
+}
+
+int gemm_launch_group(int layout, const GemmArgs* list, int n, hipStream_t s) {
+  const GemmEnv env = gemm_env();
+  GemmPlan P;
+  ASTK_TRY(gemm_plan(layout, list, n, env, P));
+  if (P.grp.n == 0) return 0;
+  if (env.log) gemm_log(P, layout);
+  return gemm_execute(P, layout, env.log, s);
 }
 
 int gemm_launch(int layout, const GemmArgs& g, hipStream_t s) { return gemm_launch_group(layout, &g, 1, s); }
@@ -1669,7 +1798,7 @@ void gemm_amax_many(const AmaxMatrix* m, int n, const unsigned long long** out, 
       memset(&J, 0, sizeof(J));
       J.gen = gen;
     }
-    unsigned long long* slot = ring + AMAX_SLOTS / 2 + (size_t)(g_amax_handle.fetch_add(1) % (AMAX_RING_SLOTS / 2)) * AMAX_SLOT_WORDS;
+    unsigned long long* slot = amax_take_handle(ring);
     amax_add(J, mat(m[i].p, m[i].ld), false, (int)m[i].rows, m[i].inner, 1, 0, 0, slot);
     out[i] = slot;
   }
@@ -1680,8 +1809,7 @@ void gemm_amax_reserve(int n, unsigned long long** slots, unsigned* gen, hipStre
   unsigned long long* ring = amax_ring();
   const bool on = default_prec() == PREC_F16X2 && ring != nullptr;
   *gen = on ? next_amax_gen(s) : 0;
-  for (int i = 0; i < n; ++i)
-    slots[i] = on ? ring + AMAX_SLOTS / 2 + (size_t)(g_amax_handle.fetch_add(1) % (AMAX_RING_SLOTS / 2)) * AMAX_SLOT_WORDS : nullptr;
+  for (int i = 0; i < n; ++i) slots[i] = on ? amax_take_handle(ring) : nullptr;
 }
 
 // constant maxima (bounded matrices): 8 slots of 16 words; word 0 of a slot holds the bound, the others stay 0
@@ -1729,15 +1857,9 @@ extern "C" int astk_set_low_precision_gemms(int mode) {
 extern "C" int astk_get_low_precision_gemms(void) { return astk::g_lowp_mode; }
 extern "C" int astk_set_gemm_precision(int mode) {
   if (mode < 0 || mode > 2) { astk::set_error("set_gemm_precision: mode must be 0 (fp16x2), 1 (bf16x3) or 2 (f32)"); return -1; }
-  const int p = astk::g_prec.load();
-  const int prev = p == astk::PREC_F32 ? 2 : (p == astk::PREC_BF16X3 ? 1 : 0);
-  astk::g_prec.store(mode == 2 ? astk::PREC_F32 : (mode == 1 ? astk::PREC_BF16X3 : astk::PREC_F16X2));
-  return prev;
+  return astk::prec_to_mode(astk::g_prec.exchange(astk::mode_to_prec(mode)));
 }
-extern "C" int astk_get_gemm_precision(void) {
-  const int p = astk::g_prec.load();
-  return p == astk::PREC_F32 ? 2 : (p == astk::PREC_BF16X3 ? 1 : 0);
-}
+extern "C" int astk_get_gemm_precision(void) { return astk::prec_to_mode(astk::g_prec.load()); }
 #ifdef ASTK_TEST_HOOKS
 extern "C" int astk_debug_set_amax_generation(unsigned gen) { astk::g_amax_counter.store(gen ? gen : 1u); return 0; }
 // libastk_test.so only: ONE grouped launch of n products C_i = A_i B_i (dense row-major operands, leading dimension = inner extent of the
@@ -1756,9 +1878,41 @@ extern "C" int astk_debug_gemm_group(int layout, int n, const int* M, const int*
   if (forward) { GemmForwardScope fs; return gemm_launch_group(layout, g, n, (hipStream_t)stream); }
   return gemm_launch_group(layout, g, n, (hipStream_t)stream);
 }
+// libastk_test.so only: what ONE grouped launch of n dense row-major products would do, as text (one gemm.log line per product, "" for a
+// group with nothing to launch) in out[0, out_bytes).  Opens the scopes an op would open, reads the state of the call and runs gemm_plan
+// only: no operand is touched (their addresses are made up) and no HIP call is made, so it runs on a machine without a GPU.
+extern "C" int astk_debug_gemm_plan(int layout, int n, const int* M, const int* N, const int* K, const int* batch, const int* mode, const int* lowp,
+                                    const int* given, int forward, int precision, int gemm_operands, int deterministic, int wg_cap, int pad_ld,
+                                    char* out, size_t out_bytes) {
+  using namespace astk;
+  ASTK_CHECK(n >= 0 && n <= GEMM_GROUP_MAX && out && out_bytes > 0, "debug_gemm_plan: bad arguments");
+  out[0] = 0;
+  PrecScope prec_scope(precision, gemm_operands);
+  DetScope det_scope(deterministic);
+  GemmWgCap cap_scope(wg_cap);
+  GemmEnv env;
+  if (forward) { GemmForwardScope fs; env = gemm_env(); } else env = gemm_env();
+  static const unsigned long long* const maximum = (const unsigned long long*)(uintptr_t)0x4000;
+  GemmArgs g[GEMM_GROUP_MAX];
+  for (int i = 0; i < n; ++i) {
+    auto ld = [&](int inner) { return pad_ld ? (inner + 3L) / 4 * 4 : (long)inner; };      // (the GEMM tests pad their rows to 16 bytes)
+    const long lda = ld(layout == GEMM_TN ? M[i] : K[i]), ldb = ld(layout == GEMM_NT ? K[i] : N[i]), ldc = ld(N[i]);
+    g[i] = gemm_args(M[i], N[i], K[i], mat((const float*)(uintptr_t)0x1000, lda), mat((const float*)(uintptr_t)0x2000, ldb), (float*)(uintptr_t)0x3000, ldc,
+                     nullptr, mode[i]);
+    g[i].batch = batch[i];
+    g[i].sA = (layout == GEMM_TN ? K[i] : M[i]) * lda; g[i].sB = (layout == GEMM_NT ? N[i] : K[i]) * ldb; g[i].sC = M[i] * ldc;
+    g[i].lowp = lowp[i];
+    if (given[i]) { g[i].amaxA = maximum; g[i].amaxB = maximum; }
+  }
+  GemmPlan P;
+  ASTK_TRY(gemm_plan(layout, g, n, env, P));
+  size_t used = 0;
+  for (int i = 0; i < P.grp.n; ++i) {
+    const int w = gemm_plan_line(out + used, out_bytes - used, P, layout, i);
+    ASTK_CHECK(w > 0 && (size_t)w < out_bytes - used, "debug_gemm_plan: the text needs more than %zu bytes", out_bytes);
+    used += (size_t)w;
+  }
+  return 0;
+}
 #endif
 extern "C" double astk_set_gemm_bf16_split_below(double flops) { return astk::g_small_flops.exchange(flops < 0 ? 0.0 : flops); }
-
-namespace astk {
-
-}  // namespace astk

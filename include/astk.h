@@ -110,6 +110,15 @@ int astk_debug_set_amax_generation(unsigned gen);
  * issues it -- under the forward ops' two-contributor rule when `forward` is set -- for shapes no op of the step produces. */
 int astk_debug_gemm_group(int layout, int n, const int* M, const int* N, const int* K, const float* const* A, const float* const* B,
                           float* const* C, int forward, int precision, void* stream);
+/* Test hook (libastk_test.so only): what ONE grouped launch of n dense row-major products (leading dimensions as in astk_debug_gemm_group;
+ * per product M, N, K, batch, mode 0 store / 1 accumulate / 2 atomic, the fp16-operand mark `lowp`, and `given` = the caller supplies both
+ * operands' maxima) WOULD do under `forward`, the descriptor fields `precision` / `gemm_operands` / `deterministic`, a workgroup cap
+ * (0 = none), leading dimensions rounded up to a multiple of 4 floats when `pad_ld` is set, and the astk_set_tuning knobs in force:
+ * the launcher's plan as text, one "gemm.log" line per product that is launched, in out[0, out_bytes).  Plans only: no operand is touched, nothing is launched, no device is needed.  Returns 0, or -1 and the
+ * usual error text where the launch would be refused. */
+int astk_debug_gemm_plan(int layout, int n, const int* M, const int* N, const int* K, const int* batch, const int* mode, const int* lowp,
+                         const int* given, int forward, int precision, int gemm_operands, int deterministic, int wg_cap, int pad_ld,
+                         char* out, size_t out_bytes);
 #endif
 
 /* ---------------------------------------------------------------- CNN front-end  (seq2seq.py:158-180)

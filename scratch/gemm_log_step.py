@@ -1,9 +1,9 @@
-"""One train step of bench.py's model with ASTK_GEMM_LOG=1: every GEMM launch and absolute-maximum region of the step (stderr)."""
+"""One train step of bench.py's model with the "gemm.log" knob on: every GEMM launch and absolute-maximum region of the step (stderr)."""
 import os, sys, copy, random
-os.environ["ASTK_GEMM_LOG"] = "1"
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import torch, bench
-from ast_amd import optimizers as O
+from ast_amd import _lib, optimizers as O
+_lib.set_tuning("gemm.log", 1)
 from ast_amd.seq2seq import SpeechEncoderDecoder, using_config
 cfg = copy.deepcopy(bench.MODEL_CFG)
 B, T, D, L, V = 32, 800, 80, 40, 1098

@@ -1,5 +1,5 @@
 """Per-launch GEMM table of one train step.  Two phases:
-  python scratch/gemm_step_trace.py run      (under: ASTK_GEMM_LOG=1 rocprofv3 --kernel-trace --output-format csv -d DIR -- python3 scratch/gemm_step_trace.py run 2> DIR/gemm.log)
+  python scratch/gemm_step_trace.py run      (sets "gemm.log"; under: rocprofv3 --kernel-trace --output-format csv -d DIR -- python3 scratch/gemm_step_trace.py run 2> DIR/gemm.log)
   python scratch/gemm_step_trace.py join DIR (joins the kernel trace with the logged shapes of the LAST step)
 """
 import csv, glob, os, re, sys
@@ -10,6 +10,8 @@ def run():
     from ast_amd.seq2seq import SpeechEncoderDecoder, using_config
     from ast_amd import optimizers as O
     from oracle.ast_ref import synth_batch
+    from ast_amd import _lib
+    _lib.set_tuning("gemm.log", 1)
     cfg = copy.deepcopy(bench.MODEL_CFG)
     B, T, D, L, V = 32, 800, 80, 40, cfg["rnn_config"]["dec_vocab_size"]
     m = SpeechEncoderDecoder(0, cfg).materialize(D, seed=0)

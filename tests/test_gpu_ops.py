@@ -1374,6 +1374,77 @@ def test_gemm_twelve_wave_256x128_kernel_on_a_big_ragged_product(lib, layout):
 
 
 @pytest.mark.parametrize("layout", [0, 1, 2])
+@pytest.mark.parametrize("knob,value,K,rtol", [("gemm.tile", 64, 100, 2e-5), ("gemm.tile", 128, 100, 2e-5), ("gemm.tile", 256, 100, 2e-5),
+                                               ("gemm.grid", 24, 1000, 3e-5)])
+def test_gemm_forced_tile_and_forced_grid_on_a_ragged_product(lib, tune, layout, knob, value, K, rtol):
+    """The launcher's tuning overrides, which no other test sets: "gemm.tile" 64 | 128 | 256 on a ragged 300 x 260 x 100 product that would
+    take 64-tiles by itself (tests/test_gemm_plan_host.py force64 / force128 / force256: 25, 9 and 6 whole tiles), and "gemm.grid" 24 on
+    300 x 260 x 1000 (forced-grid: 24 workgroups over 25 tiles of 63 k-iterations, every tile split, zeroed first).  Store mode into a
+    poisoned buffer, against float64 at the bounds of the 12-wave test and of the split-tile tests."""
+    assert lib.astk_get_gemm_precision() == 1
+    tune(knob, value, lib)
+    M, N = 300, 260
+    rng = np.random.default_rng(900 + layout + K)
+    pad4 = lambda n: (n + 3) // 4 * 4
+    A = rng.standard_normal((M, K)).astype(np.float32)
+    B = rng.standard_normal((N, K)).astype(np.float32)
+    ref = (torch.from_numpy(A).double() @ torch.from_numpy(B).double().T).numpy()
+
+    def store(X, transpose):
+        X = X.T if transpose else X
+        P = np.full((X.shape[0], pad4(X.shape[1]) + 4), np.nan, np.float32)
+        P[:, :X.shape[1]] = X
+        return P
+    Ad, Bd = store(A, layout == 2), store(B, layout != 0)
+    a, b = dev(Ad), dev(Bd)
+    ldc = pad4(N) + 4
+    c = torch.full((M, ldc), float("nan"), device="cuda")
+    ok(lib, lib.astk_gemm_f32(layout, M, N, K, vp(a), Ad.shape[1], vp(b), Bd.shape[1], vp(c), ldc, None, 0, 1, 1, 0, 0, 0, stream()))
+    close(c[:, :N], ref, rtol=rtol, msg=f"{knob} {value} layout {layout}")
+    assert bool(torch.isnan(c[:, N:]).all()), "wrote outside N"
+
+
+@pytest.mark.parametrize("variant", ["scalar-zeroing", "det-clipped-grid", "det-f32-whole-tiles"])
+def test_gemm_split_tile_handling_no_other_test_launches(lib, tune, variant):
+    """Three split-tile decisions of the launcher on 4100 x 1150 x 332 (NT, store mode; tests/test_gemm_plan_host.py zero-scalar,
+    det-clipped, det-f32), each one launch shape no other test produces.  "scalar-zeroing": an output whose ldc (1150) is no multiple
+    of 4 -- the split tiles are zeroed with scalar stores (zero_vec = 0); every other split-tile test pads ldc to 16 bytes.
+    "det-clipped-grid": deterministic mode with "gemm.grid" 512 -- the grid is clipped to the 256 workgroups the fix-up workspace
+    serves.  "det-f32-whole-tiles": deterministic mode under the f32 scheme, which has no fix-up kernel -- one whole tile per
+    workgroup.  Store into a NaN-poisoned buffer with a guard band behind it, against float64 at the split-tile tests' bound; the
+    deterministic variants four times, bit for bit."""
+    from ast_amd import _lib as L_
+    assert lib.astk_get_gemm_precision() == 1
+    M, N, K = 4100, 1150, 332
+    rng = np.random.default_rng(4100 + 1150 + 332)
+    A = rng.standard_normal((M, K)).astype(np.float32)
+    B = rng.standard_normal((N, K)).astype(np.float32)
+    ref = (torch.from_numpy(A).double() @ torch.from_numpy(B).double().T).numpy()
+    a, b = dev(A), dev(B)
+    det = variant != "scalar-zeroing"
+    if det:
+        tune("gemm.deterministic", 1, lib)
+    if variant == "det-clipped-grid":
+        tune("gemm.grid", 512, lib)
+    ldc = N if variant == "scalar-zeroing" else (N + 3) // 4 * 4 + 4
+    prec = L_.PREC_F32 if variant == "det-f32-whole-tiles" else L_.PREC_DEFAULT
+    guard = 4096
+    first = None
+    for rep in range(4 if det else 2):
+        buf = torch.full((M * ldc + guard,), float("nan"), device="cuda")
+        c = buf[:M * ldc].view(M, ldc)
+        ok(lib, lib.astk_gemm_f32_ex(0, M, N, K, vp(a), K, vp(b), K, vp(c), ldc, None, 0, 1, 1, 0, 0, 0, prec, stream()))
+        assert bool(torch.isnan(buf[M * ldc:]).all()) and bool(torch.isnan(c[:, N:]).all()), "wrote outside the result"
+        if first is None:
+            first = c.clone()
+            close(c[:, :N], ref, rtol=3e-5, msg=variant)
+        elif det:
+            assert torch.equal(c[:, :N], first[:, :N]), (variant, rep, float((c[:, :N] - first[:, :N]).abs().max()))
+        else:
+            close(c[:, :N], ref, rtol=3e-5, msg=f"{variant} launch {rep}")
+
+
+@pytest.mark.parametrize("layout", [0, 1, 2])
 @pytest.mark.parametrize("sa,sb", [(1e-20, 1e15), (3e7, 2e-3), (1.0, 1e-30)])
 def test_gemm_operand_magnitudes(lib, layout, sa, sb, gemm_split):
     """The default GEMM splits every operand into two fp16 terms behind a per-operand power-of-two scale taken from an absolute-maximum
