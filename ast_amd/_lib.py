@@ -16,6 +16,7 @@ ENCODE_ROWS_MAX = 32      # astk.h ASTK_ENCODE_ROWS_MAX: rows of one astk_*_fwd_
 PREC_DEFAULT, PREC_FP16X2, PREC_BF16X3, PREC_F32 = 0, 1, 2, 3
 OPERANDS_DEFAULT, OPERANDS_F32, OPERANDS_FP16 = 0, 1, 2
 OPERANDS_BY_NAME = {None: OPERANDS_DEFAULT, "default": OPERANDS_DEFAULT, "f32": OPERANDS_F32, "fp16": OPERANDS_FP16}
+SPEC_FILL_ZERO, SPEC_FILL_MEAN, SPEC_MAX_MASKS, SPEC_MAX_BINS = 0, 1, 8, 1024      # astk.h ASTK_SPEC_*
 PREC_BY_NAME = {None: PREC_DEFAULT, "default": PREC_DEFAULT, "fp16x2": PREC_FP16X2, "bf16x3": PREC_BF16X3, "f32": PREC_F32}
 
 c_float_p = C.POINTER(C.c_float)
@@ -121,6 +122,11 @@ class BeamState(_Sized, C.Structure):
 
 
 # the row-panel launchers' mirror structs (include/astk.h, the ASTK_TEST_HOOKS section; libastk_test.so only)
+class SpecAugmentDesc(_Sized, C.Structure):
+    _fields_ = [("struct_size", C.c_uint32), ("n_freq", C.c_int), ("freq_width", C.c_int), ("n_time", C.c_int), ("time_width", C.c_int),
+                ("time_ratio", C.c_double), ("fill", C.c_int)]
+
+
 class DebugRowPair(C.Structure):
     _fields_ = [("A", C.c_void_p), ("lda", C.c_long), ("W", C.c_void_p), ("ldw", C.c_long), ("K", C.c_int)]
 
@@ -252,6 +258,7 @@ SIGNATURES = {
     "astk_colsum_add_f32": (C.c_int, [_VP, _VP, _L, _I, _I, _VP]),
     "astk_zero_frames": (C.c_int, [_VP, _I, _I, _I, _VP, C.c_double, _U64, _U64, _VP]),
     "astk_zero_frames_draws": (C.c_int, [_I, _I, _VP, C.c_double, _U64, _U64, _VP, _I, _VP, _VP]),
+    "astk_spec_augment": (C.c_int, [_VP, _I, _I, _I, _VP, _VP, _U64, _U64, _U64, _VP]),
     "astk_persist_status_snapshot": (C.c_int, [_VP, _VP]),
     "astk_persist_status_merge": (C.c_int, [_VP, _VP]),
     "astk_persist_status": (C.c_int, [C.POINTER(C.c_uint), _I]),

@@ -365,6 +365,88 @@ __global__ void k_zero_frames_draws(int T, const int32_t* len, double rate, uint
   for (int i = threadIdx.x; i < n && i < max_draws; i += blockDim.x) idx[(size_t)b * max_draws + i] = zero_frames_draw(seed, offset, b, T, i, nb);
 }
 
+// SpecAugment of the training loader (include/astk.h astk_spec_augment holds the draw contract).  One workgroup
+// per utterance: the means of the mean fill must come from the row as it is on entry, and a workgroup that owns the whole row gets
+// that from one barrier between its reads and its writes.
+//   mean fill, reads : thread (r, d) = (tid / D, tid % D) sums bin d over the frames r, r + R, r + 2R, ... (R = 1024 / D whole frames
+//                      per pass: the workgroup reads R * D consecutive floats at a time) in four interleaved partial sums, folded as
+//                      (a0 + a1) + (a2 + a3); thread d < D then adds the R partial sums of its bin in the order r = 0, 1, ...
+//                      The order is a function of (len, D) alone.
+//   writes           : a time span is one contiguous run of t * D floats; a frequency span is f floats in each of len frames.
+//                      Overlapping spans store the same value to a cell, so their order does not matter.
+// The zero fill skips the reads (and the barrier's wait for them).  Plain dword stores: rows with D = 13 are not 16-byte aligned.
+constexpr int SPEC_THREADS = 1024;
+static_assert(ASTK_SPEC_MAX_BINS <= SPEC_THREADS, "one thread per bin folds the partial sums");
+struct SpecArgs {
+  int n_freq, freq_width, n_time, time_width, fill;
+  double time_ratio;
+  uint64_t seed, counter0, counter_stride;
+};
+__device__ __forceinline__ uint64_t spec_word(uint64_t key, int c, int i, int r) {
+  return mix64(key ^ (((uint64_t)c << 32) | ((uint64_t)i << 1) | (uint64_t)r)) >> 11;
+}
+__global__ __launch_bounds__(SPEC_THREADS) void k_spec_augment(float* X, int T, int D, const int32_t* len, SpecArgs a) {
+  __shared__ float part[SPEC_THREADS];
+  __shared__ float fillv[ASTK_SPEC_MAX_BINS];
+  __shared__ int span[2][ASTK_SPEC_MAX_MASKS][2];      // [kind][mask] = (start, width)
+  const int b = blockIdx.x, tid = threadIdx.x;
+  const int n = min(max(len[b], 0), T);
+  if (n == 0) return;
+  float* xb = X + (size_t)b * T * D;
+  if (tid < 2 * ASTK_SPEC_MAX_MASKS) {
+    const int c = tid / ASTK_SPEC_MAX_MASKS, i = tid % ASTK_SPEC_MAX_MASKS;
+    const uint64_t key = mix64(a.seed ^ mix64(a.counter0 + (uint64_t)b * a.counter_stride));
+    const int extent = c == 0 ? D : n;
+    const int cap = c == 0 ? min(a.freq_width, D) : min(a.time_width, (int)(a.time_ratio * (double)n));
+    const int w = (int)(spec_word(key, c, i, 0) % (uint64_t)(cap + 1));
+    span[c][i][0] = (int)(spec_word(key, c, i, 1) % (uint64_t)(extent - w + 1));
+    span[c][i][1] = i < (c == 0 ? a.n_freq : a.n_time) ? w : 0;
+  }
+  if (a.fill == ASTK_SPEC_FILL_MEAN) {
+    const int R = SPEC_THREADS / D, r = tid / D, d = tid - r * D;
+    float s = 0.f;
+    if (r < R) {
+      float a0 = 0.f, a1 = 0.f, a2 = 0.f, a3 = 0.f;
+      const float* p = xb + d;
+      int t = r;
+      for (; t + 3 * R < n; t += 4 * R) {
+        a0 += p[(size_t)t * D];
+        a1 += p[(size_t)(t + R) * D];
+        a2 += p[(size_t)(t + 2 * R) * D];
+        a3 += p[(size_t)(t + 3 * R) * D];
+      }
+      if (t < n) a0 += p[(size_t)t * D];
+      if (t + R < n) a1 += p[(size_t)(t + R) * D];
+      if (t + 2 * R < n) a2 += p[(size_t)(t + 2 * R) * D];
+      s = (a0 + a1) + (a2 + a3);
+    }
+    part[tid] = s;
+    __syncthreads();
+    if (tid < D) {
+      float m = 0.f;
+      for (int k = 0; k < R; ++k) m += part[k * D + tid];
+      fillv[tid] = m / (float)n;
+    }
+  } else {
+    for (int d = tid; d < D; d += SPEC_THREADS) fillv[d] = 0.f;
+  }
+  __syncthreads();       // every read of the row lies in front of this barrier, every write behind it
+  for (int i = 0; i < a.n_time; ++i) {
+    const int t0 = span[1][i][0], cells = span[1][i][1] * D;
+    float* dst = xb + (size_t)t0 * D;
+    for (int e = tid; e < cells; e += SPEC_THREADS) dst[e] = fillv[e % D];
+  }
+  for (int i = 0; i < a.n_freq; ++i) {
+    const int f0 = span[0][i][0], f = span[0][i][1];
+    if (f == 0) continue;
+    const int cells = n * f;
+    for (int e = tid; e < cells; e += SPEC_THREADS) {
+      const int t = e / f, j = e - t * f;
+      xb[(size_t)t * D + f0 + j] = fillv[f0 + j];
+    }
+  }
+}
+
 // ---- optimizer
 // The decayed gradient g gsc + l2 p with BOTH products rounded to float32 before the sum: what a separate scaling pass followed by the
 // unscaled call computes, bit for bit, and what plain float32 code computes.  Contraction is switched off by hand: __fmul_rn is a plain
@@ -769,6 +851,27 @@ int astk_zero_frames(float* X, int B, int T, int D, const int32_t* lengths, doub
   ASTK_CHECK(X && lengths && B > 0 && T > 0 && D > 0 && rate >= 0. && rate <= 1., "zero_frames: bad arguments");
   if (rate == 0.) return 0;
   hipLaunchKernelGGL(k_zero_frames, dim3(B), dim3(256), 0, (hipStream_t)stream, X, T, D, lengths, rate, seed, offset);
+  ASTK_LAUNCH_CHECK();
+  return 0;
+}
+
+int astk_spec_augment(float* X, int B, int T, int D, const int32_t* lengths, const astk_spec_augment_desc* d, uint64_t seed,
+                      uint64_t counter0, uint64_t counter_stride, void* stream) {
+  ASTK_CHECK(X, "spec_augment: X is null");
+  ASTK_CHECK(lengths, "spec_augment: lengths is null");
+  ASTK_CHECK_DESC(d, astk_spec_augment_desc);
+  ASTK_CHECK(B > 0 && T > 0, "spec_augment: B and T must be positive, got B = %d, T = %d", B, T);
+  ASTK_CHECK(D > 0 && D <= ASTK_SPEC_MAX_BINS, "spec_augment: D must be 1..%d, got %d", ASTK_SPEC_MAX_BINS, D);
+  ASTK_CHECK((long)T * D <= 0x7fffffffL, "spec_augment: T * D must fit 31 bits, got T = %d, D = %d", T, D);
+  ASTK_CHECK(d->n_freq >= 0 && d->n_freq <= ASTK_SPEC_MAX_MASKS, "spec_augment: n_freq must be 0..%d, got %d", ASTK_SPEC_MAX_MASKS, d->n_freq);
+  ASTK_CHECK(d->n_time >= 0 && d->n_time <= ASTK_SPEC_MAX_MASKS, "spec_augment: n_time must be 0..%d, got %d", ASTK_SPEC_MAX_MASKS, d->n_time);
+  ASTK_CHECK(d->freq_width >= 0, "spec_augment: freq_width must not be negative, got %d", d->freq_width);
+  ASTK_CHECK(d->time_width >= 0, "spec_augment: time_width must not be negative, got %d", d->time_width);
+  ASTK_CHECK(d->time_ratio >= 0. && d->time_ratio <= 1., "spec_augment: time_ratio must be finite and in [0, 1], got %g", d->time_ratio);
+  ASTK_CHECK(d->fill == ASTK_SPEC_FILL_ZERO || d->fill == ASTK_SPEC_FILL_MEAN, "spec_augment: unknown fill %d (0 zero, 1 mean)", d->fill);
+  if (d->n_freq == 0 && d->n_time == 0) return 0;
+  SpecArgs a{d->n_freq, d->freq_width, d->n_time, d->time_width, d->fill, d->time_ratio, seed, counter0, counter_stride};
+  hipLaunchKernelGGL(k_spec_augment, dim3(B), dim3(SPEC_THREADS), 0, (hipStream_t)stream, X, T, D, lengths, a);
   ASTK_LAUNCH_CHECK();
   return 0;
 }

@@ -88,6 +88,10 @@ class DataLoader:
         self.n_utts = {}
         # data-parallel sharding of every batch (ast_amd.dist): rank r takes rows r::world of each bucketed batch
         self.rank, self.world = 0, 1
+        # SpecAugment of the training batches (ast_amd.spec_augment): a checked_spec_augment dict, or None = off.
+        # spec_counter is the presentation counter of the next training batch's first utterance (its position in the unsharded plan).
+        self.spec_augment = None
+        self.spec_counter = 0
 
     def _count(self):
         self.n_utts = {k: sum(len(b) for b in v["buckets"]) for k, v in self.buckets.items()}
@@ -152,6 +156,9 @@ class DataLoader:
         rng_state = random.getstate() if (self.world > 1 and not train) else None
         if rng_state is not None:
             kept = [list(b) for b in bk["buckets"]]          # batch_plan shuffles the bucket lists in place
+        # SpecAugment masks training batches only; utterance g of a batch's unsharded list is presented as number base + g, and every
+        # rank advances the loader's counter by the whole (cut) batch: masks do not depend on the shard or the world size
+        spec = self.spec_augment if (train and "train" in set_key) else None
         base_plan = self.batch_plan(batch_size, set_key)
         if rng_state is not None:
             random.setstate(rng_state)
@@ -163,6 +170,9 @@ class DataLoader:
                 # the others take, and their all-reduce would wait for it forever)
                 utts = utts[:len(utts) // world * world]
             mine = list(utts[self.rank::world]) if world > 1 else list(utts)
+            spec_base = self.spec_counter
+            if spec is not None:
+                self.spec_counter += len(utts)
             if not mine:
                 continue
             pads = None
@@ -181,14 +191,17 @@ class DataLoader:
                         t_ = self._targets(u, set_key)
                         yg[g_, :len(t_)] = np.asarray(t_, dtype=np.int32)
                     pads = (t_pad, l_pad, yg)
-            plan.append((mine, pads))
+            plan.append((mine, pads, spec_base))
 
         def padded(arrays, n_min):
             return max(max(len(a) for a in arrays), n_min)
         if self.device.type != "cuda":
             self._zero_on_device = False
-            for utts, pads in plan:
+            for utts, pads, spec_base in plan:
                 xs = [self._speech(u, set_key, max_sp) for u in utts]
+                if spec is not None:
+                    from . import spec_augment as SA
+                    xs = [SA.apply_host(x, spec_base + b * world + self.rank, spec) for b, x in enumerate(xs)]
                 out = {"X": pad_batch(xs, torch.float32, self.device, pads[0] if pads else 0), "utts": utts}
                 if labels:
                     out["y"] = pad_batch([self._targets(u, set_key) for u in utts], torch.int32, self.device, pads[1] if pads else 0)
@@ -204,12 +217,12 @@ class DataLoader:
         self._zero_on_device = zero_rate > 0 and os.environ.get("ASTK_ZERO_FRAMES_ON_HOST", "0") != "1"
 
         def stage(k):
-            (utts, pads), slot = plan[k], k % ring.depth
+            (utts, pads, _), slot = plan[k], k % ring.depth
             ring.wait_free(slot)
             xs = [self._speech(u, set_key, max_sp) for u in utts]
             n = padded(xs, pads[0] if pads else 0)
             host = {"X": _pad_into(ring.host(slot, "X", (len(xs), n) + tuple(xs[0].shape[1:]), torch.float32), xs)}
-            if self._zero_on_device:
+            if self._zero_on_device or spec is not None:        # the true frame counts, for the kernels that work on the uploaded batch
                 lens = ring.host(slot, "len", (len(xs),), torch.int32)
                 lens.copy_(torch.tensor([len(x) for x in xs], dtype=torch.int32))
                 host["len"] = lens
@@ -219,20 +232,24 @@ class DataLoader:
             return host
         with ThreadPoolExecutor(max_workers=1) as pool:
             nxt = pool.submit(stage, 0) if plan else None
-            for k, (utts, _) in enumerate(plan):
+            for k, (utts, _, spec_base) in enumerate(plan):
                 host = nxt.result()
                 nxt = pool.submit(stage, k + 1) if k + 1 < len(plan) else None
                 out = {name: h.to(self.device, non_blocking=True) for name, h in host.items()}
                 if "len" in out:
-                    import ctypes as C
-                    from . import _lib
                     X = out["X"]
-                    seed = getattr(self, "zero_seed", 0x2E50F4A3E5)
-                    off = self.__dict__.get("_zero_counter", 0)
-                    self._zero_counter = off + X.shape[0] * X.shape[1]
-                    _lib.check(_lib.load().astk_zero_frames(C.c_void_p(X.data_ptr()), X.shape[0], X.shape[1], int(X[0, 0].numel()),
-                                                            C.c_void_p(out["len"].data_ptr()), zero_rate, seed, off,
-                                                            C.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)))
+                    if self._zero_on_device:
+                        import ctypes as C
+                        from . import _lib
+                        seed = getattr(self, "zero_seed", 0x2E50F4A3E5)
+                        off = self.__dict__.get("_zero_counter", 0)
+                        self._zero_counter = off + X.shape[0] * X.shape[1]
+                        _lib.check(_lib.load().astk_zero_frames(C.c_void_p(X.data_ptr()), X.shape[0], X.shape[1], int(X[0, 0].numel()),
+                                                                C.c_void_p(out["len"].data_ptr()), zero_rate, seed, off,
+                                                                C.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)))
+                    if spec is not None:        # behind the frame zeroing: the mean fill takes its means from the zeroed batch
+                        from . import spec_augment as SA
+                        SA.apply_device(X, out["len"], spec_base + self.rank, world, spec, torch.cuda.current_stream(self.device).cuda_stream)
                     del out["len"]
                 ring.mark_in_flight(k % ring.depth)
                 out["utts"] = utts

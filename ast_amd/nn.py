@@ -15,6 +15,7 @@ from . import optimizers, serializers
 from .config import Config
 from .dataloader import SYMBOLS, FisherDataLoader, GlobalPhoneDataLoader, SyntheticDataLoader
 from .seq2seq import SpeechEncoderDecoder, checked_label_smoothing, raise_if_aborted, using_config
+from .spec_augment import checked_spec_augment
 
 _ADAM = 0
 _SGD = 1
@@ -500,6 +501,13 @@ class NN:
         if adist.is_distributed():
             self.data_loader.rank, self.data_loader.world = adist.rank(), adist.world_size()
         self.get_model()
+        # extension key: extras.spec_augment = {"freq_masks", "freq_width", "time_masks", "time_width", "time_ratio", "fill", "seed"} masks
+        # the TRAINING batches inside the loader (ast_amd.spec_augment); absent, null or {} = off.  Evaluation
+        # batches are never masked.  A resumed run starts its presentation counter behind every counter of the epochs already trained.
+        self.data_loader.spec_augment = checked_spec_augment(self.cfg.train.get("extras", {}).get("spec_augment"), "extras.spec_augment")
+        self.data_loader.spec_counter = self.max_epoch << 40
+        if self.data_loader.spec_augment is not None:
+            print("SpecAugment: {0}".format(self.data_loader.spec_augment))
         # extension key (BASELINE configs[4], "fp16 MFMA GEMMs"): extras.gemm_operands = "fp16" runs the batched products of the CNN
         # layers >= 1 and of the encoder's input projection with fp16 operands / f32 accumulation; default "f32" (f32-accurate products)
         # extras.gemm_precision = "bf16x3" (library default: exact f32 operands as three bf16 terms) | "f32" (f32-input MFMAs) | "fp16x2"

@@ -30,7 +30,7 @@
 extern "C" {
 #endif
 
-#define ASTK_VERSION 108
+#define ASTK_VERSION 109
 #define ASTK_MAX_CNN_LAYERS 4
 #define ASTK_MAX_RNN_LAYERS 8
 #define ASTK_MAX_ATTN 4
@@ -757,6 +757,45 @@ int astk_zero_frames(float* X, int B, int T, int D, const int32_t* lengths, doub
  * Lets a test feed the device's stream to the oracle's _drop_frames (oracle/loader_ref.py) and compare whole batches bit for bit. */
 int astk_zero_frames_draws(int B, int T, const int32_t* lengths, double rate, uint64_t seed, uint64_t offset, int32_t* idx, int max_draws,
                            int32_t* counts, void* stream);
+/* SpecAugment of the training loader: contiguous frequency and time masks on the padded device batch X (B,T,D),
+ * in place, one launch, stream-ordered, no allocation, no synchronisation.  Not in the reference: off unless a caller asks for it.
+ * The masks are a contract, a pure function of (seed, presentation counter n of the utterance, D, len) that a host can restate
+ * (ast_amd.spec_augment.spec_spans).  All integer arithmetic is uint64; mix64 is the splitmix64 finaliser quoted with the sampled
+ * decode's noise contract above (Python: ast_amd.seq2seq.mix64).
+ *   key(seed, n)      = mix64(seed ^ mix64(n))                      n = counter0 + b * counter_stride for row b of the call
+ *   word(key,c,i,r)   = mix64(key ^ ((c << 32) | (i << 1) | r))     c: 0 frequency, 1 time; i: mask index; r: 0 width, 1 start
+ *   frequency mask i  : cap = min(freq_width, D);  f = (word(key,0,i,0) >> 11) % (cap + 1);  f0 = (word(key,0,i,1) >> 11) % (D - f + 1)
+ *                       masks bins [f0, f0 + f) of frames [0, len)
+ *   time mask i       : cap = min(time_width, int(time_ratio * len)), the product in double, as Python evaluates it
+ *                       t = (word(key,1,i,0) >> 11) % (cap + 1);  t0 = (word(key,1,i,1) >> 11) % (len - t + 1)
+ *                       masks frames [t0, t0 + t), all D bins
+ * len = lengths[b] clamped to [0, T]; a row with len == 0 is left alone, and the frames at and behind len (the padding) are never
+ * written.  A width of 0 is a legal draw; an utterance may end up fully masked (freq_width >= D): that is the definition.  The modulo
+ * of a 53-bit word over at most a few thousand values is biased by about 1e-12.  (key(2024, 0) = row_key(2024, 0) =
+ * 0xEE8C6C05E85E6BD6; with D = 80, len = 800, two masks of each kind, freq_width 15, time_width 40, time_ratio 0.2 the (start, width)
+ * spans of n = 0 are frequency (56,10) (51,11), time (680,34) (211,9).)
+ * fill = ASTK_SPEC_FILL_ZERO: masked cells become +0.0f; X is not read.
+ * fill = ASTK_SPEC_FILL_MEAN: a masked cell of bin d becomes the float32 mean over frames [0, len) of X[b, t, d] AS IT IS ON ENTRY to
+ *   the call, before any mask of this call: overlapping masks are order-free, every masked cell of bin d of a row holds the same value.
+ *   The sum is float32 in a fixed order that depends on (len, D) alone -- not on B, T or the row's position -- and is divided by
+ *   (float)len: the same call twice gives the same bits, and so does the same utterance in another batch.
+ * An utterance's masks depend on (seed, n, D, len) alone.  The loader gives row b of rank r the utterance's position in the epoch's
+ * unsharded plan (counter0 = base + r, counter_stride = world size), so they do not depend on B, T, the shard or the world size.
+ * Fails with a message that names the field, and launches nothing, for: a null X, lengths or descriptor; a wrong struct_size; B, T < 1
+ * or D outside 1..ASTK_SPEC_MAX_BINS; n_freq or n_time outside 0..ASTK_SPEC_MAX_MASKS; a negative freq_width or time_width; a
+ * time_ratio outside [0, 1] or not finite; an unknown fill.  With n_freq == n_time == 0 it returns 0 and launches nothing. */
+#define ASTK_SPEC_FILL_ZERO 0
+#define ASTK_SPEC_FILL_MEAN 1
+#define ASTK_SPEC_MAX_MASKS 8
+#define ASTK_SPEC_MAX_BINS 1024
+typedef struct {
+  uint32_t struct_size;  /* = sizeof(astk_spec_augment_desc) */
+  int n_freq, freq_width, n_time, time_width;
+  double time_ratio;
+  int fill;
+} astk_spec_augment_desc;
+int astk_spec_augment(float* X, int B, int T, int D, const int32_t* lengths, const astk_spec_augment_desc* d, uint64_t seed,
+                      uint64_t counter0, uint64_t counter_stride, void* stream);
 /* One wavefront that keeps `stream` busy for `usec` microseconds (<= 100 000) and then increments *flag (may be NULL).  For probing
  * whether two streams really execute concurrently: HIP multiplexes streams onto a few hardware queues (GPU_MAX_HW_QUEUES, 4 by
  * default), and two streams that share one are serialised whatever their events say (ast_amd/seq2seq.py:_cu_streams). */
