@@ -121,6 +121,14 @@ class BeamState(_Sized, C.Structure):
                 ("n_frozen", C.c_void_p), ("hist", C.c_void_p), ("hist_alpha", C.c_void_p)]
 
 
+CTC_MAX_LABELS = 255                   # astk.h ASTK_CTC_MAX_LABELS
+
+
+class CtcDesc(_Sized, C.Structure):
+    _fields_ = [("struct_size", C.c_size_t), ("B", C.c_int), ("T", C.c_int), ("V", C.c_int), ("ldv", C.c_long), ("L", C.c_int),
+                ("ldy", C.c_long), ("first_label", C.c_int), ("blank", C.c_int)]
+
+
 # the row-panel launchers' mirror structs (include/astk.h, the ASTK_TEST_HOOKS section; libastk_test.so only)
 class SpecAugmentDesc(_Sized, C.Structure):
     _fields_ = [("struct_size", C.c_uint32), ("n_freq", C.c_int), ("freq_width", C.c_int), ("n_time", C.c_int), ("time_width", C.c_int),
@@ -259,6 +267,11 @@ SIGNATURES = {
     "astk_zero_frames": (C.c_int, [_VP, _I, _I, _I, _VP, C.c_double, _U64, _U64, _VP]),
     "astk_zero_frames_draws": (C.c_int, [_I, _I, _VP, C.c_double, _U64, _U64, _VP, _I, _VP, _VP]),
     "astk_spec_augment": (C.c_int, [_VP, _I, _I, _I, _VP, _VP, _U64, _U64, _U64, _VP]),
+    "astk_ctc_workspace_bytes": (_SZ, [C.POINTER(CtcDesc)]),
+    "astk_ctc_loss": (C.c_int, [C.POINTER(CtcDesc), _VP, _VP, _VP, _F, _VP, _VP, _VP, _VP, _VP, _SZ, _VP]),
+    "astk_ctc_greedy": (C.c_int, [C.POINTER(CtcDesc), _VP, _VP, _VP, _VP]),
+    "astk_ctc_head_fwd": (C.c_int, [_I, _I, _I, _VP, _VP, _VP, _VP, _L, _I, _VP]),
+    "astk_ctc_head_bwd": (C.c_int, [_I, _I, _I, _VP, _L, _VP, _VP, _VP, _VP, _VP, _I, _I, _VP]),
     "astk_persist_status_snapshot": (C.c_int, [_VP, _VP]),
     "astk_persist_status_merge": (C.c_int, [_VP, _VP]),
     "astk_persist_status": (C.c_int, [C.POINTER(C.c_uint), _I]),

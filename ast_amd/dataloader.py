@@ -92,6 +92,9 @@ class DataLoader:
         # spec_counter is the presentation counter of the next training batch's first utterance (its position in the unsharded plan).
         self.spec_augment = None
         self.spec_counter = 0
+        # True (NN sets it for extras.ctc_weight > 0): training batches carry batch["x_len"], a host int32 array of the rows' true frame
+        # counts -- what the auxiliary CTC loss masks the padding with.  False: the batch dict has the keys it always had.
+        self.keep_lens = False
 
     def _count(self):
         self.n_utts = {k: sum(len(b) for b in v["buckets"]) for k, v in self.buckets.items()}
@@ -159,6 +162,7 @@ class DataLoader:
         # SpecAugment masks training batches only; utterance g of a batch's unsharded list is presented as number base + g, and every
         # rank advances the loader's counter by the whole (cut) batch: masks do not depend on the shard or the world size
         spec = self.spec_augment if (train and "train" in set_key) else None
+        keep_lens = bool(self.keep_lens and train and labels)
         base_plan = self.batch_plan(batch_size, set_key)
         if rng_state is not None:
             random.setstate(rng_state)
@@ -207,6 +211,8 @@ class DataLoader:
                     out["y"] = pad_batch([self._targets(u, set_key) for u in utts], torch.int32, self.device, pads[1] if pads else 0)
                 if pads and len(pads) > 2:
                     out["y_global"] = pads[2]
+                if keep_lens:
+                    out["x_len"] = np.asarray([len(x) for x in xs], dtype=np.int32)
                 yield out
             return
         # device batches: loading and padding of batch k+1 run on a helper thread while batch k trains; frame zeroing
@@ -229,11 +235,11 @@ class DataLoader:
             if labels:
                 ys = [self._targets(u, set_key) for u in utts]
                 host["y"] = _pad_into(ring.host(slot, "y", (len(ys), padded(ys, pads[1] if pads else 0)), torch.int32), ys)
-            return host
+            return host, (np.asarray([len(x) for x in xs], dtype=np.int32) if keep_lens else None)
         with ThreadPoolExecutor(max_workers=1) as pool:
             nxt = pool.submit(stage, 0) if plan else None
             for k, (utts, _, spec_base) in enumerate(plan):
-                host = nxt.result()
+                host, x_len = nxt.result()
                 nxt = pool.submit(stage, k + 1) if k + 1 < len(plan) else None
                 out = {name: h.to(self.device, non_blocking=True) for name, h in host.items()}
                 if "len" in out:
@@ -255,6 +261,8 @@ class DataLoader:
                 out["utts"] = utts
                 if plan[k][1] and len(plan[k][1]) > 2:
                     out["y_global"] = plan[k][1][2]
+                if x_len is not None:
+                    out["x_len"] = x_len                      # (stays on the host: forward_loss maps it through the CNN's time formula)
                 yield out
 
     def get_hyps(self, preds):

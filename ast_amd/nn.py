@@ -14,7 +14,8 @@ from . import dist as adist
 from . import optimizers, serializers
 from .config import Config
 from .dataloader import SYMBOLS, FisherDataLoader, GlobalPhoneDataLoader, SyntheticDataLoader
-from .seq2seq import SpeechEncoderDecoder, checked_label_smoothing, raise_if_aborted, using_config
+from .seq2seq import (SpeechEncoderDecoder, checked_ctc_weight, checked_label_smoothing, ctc_count_of, raise_if_aborted,
+                      using_config)
 from .spec_augment import checked_spec_augment
 
 _ADAM = 0
@@ -489,6 +490,11 @@ class NN:
         # extension key: extras.label_smoothing = eps of the TRAINING loss (default 0 = the reference's loss).  The
         # training loop alone passes it: dev loss, predict_scored and score never smooth, so dev losses compare across runs with different eps.
         self.label_smoothing = checked_label_smoothing(self.cfg.train.get("extras", {}).get("label_smoothing", 0.0), "extras.label_smoothing")
+        # extension key: extras.ctc_weight = weight of the auxiliary CTC loss on the encoder states in the TRAINING loss (default 0 = off;
+        # needs model_cfg.json rnn_config.ctc).  Evaluation (dev loss, forced dev loss, beam, score, sample) never sees it.
+        self.ctc_weight = checked_ctc_weight(self.cfg.train.get("extras", {}).get("ctc_weight", 0.0),
+                                             bool(self.cfg.model["rnn_config"].get("ctc", False)), "extras.ctc_weight")
+        self.ctc_epoch = None                          # (mean CTC term per utterance, rows without a path) of the last train_epoch
         self.model_dir = self.cfg.model["model_dir"]
         self.gpuid = self.cfg.train["gpuid"]
         if adist.is_distributed():
@@ -508,6 +514,9 @@ class NN:
         self.data_loader.spec_counter = self.max_epoch << 40
         if self.data_loader.spec_augment is not None:
             print("SpecAugment: {0}".format(self.data_loader.spec_augment))
+        if self.ctc_weight > 0:
+            self.data_loader.keep_lens = True          # training batches carry batch["x_len"], the rows' true frame counts
+            print("CTC weight: {0:g}".format(self.ctc_weight))
         # extension key (BASELINE configs[4], "fp16 MFMA GEMMs"): extras.gemm_operands = "fp16" runs the batched products of the CNN
         # layers >= 1 and of the encoder's input projection with fp16 operands / f32 accumulation; default "f32" (f32-accurate products)
         # extras.gemm_precision = "bf16x3" (library default: exact f32 operands as three bf16 terms) | "f32" (f32-input MFMAs) | "fp16x2"
@@ -595,11 +604,16 @@ class NN:
         # nn.py:189 reads the loss back after every step (a device sync).  Here the read of step i happens after step i+1 has been
         # enqueued, so the device never waits for the host; the reported numbers are the same, the progress bar lags by one batch.
         pending = None
+        ctc_sum = [0.0, 0]                     # extras.ctc_weight > 0: sum of the steps' CTC terms / batch size, rows without a path
+        kw = {}
 
         def settle(p):
             nonlocal total_loss, n_batches, avg_loss
             vals = p[0].tolist()                                       # [loss, status word of the persistent kernels]
             raise_if_aborted(vals[1], "NN.train_epoch")
+            if len(vals) > 2:                                          # ... rows without a CTC path (int32), the attention term alone
+                ctc_sum[0] += (vals[0] - vals[3]) / p[1]
+                ctc_sum[1] += ctc_count_of(vals[2])
             loss_val = vals[0] / p[1]                                  # quirk Q5: divided by the batch size
             n_batches += 1
             total_loss += loss_val
@@ -612,20 +626,24 @@ class NN:
         torch.cuda.synchronize(self.model.device)
         with tqdm(total=n_utts, ncols=80, disable=adist.rank() != 0) as pbar, torch.cuda.stream(self._compute_stream):
             for batch in self.data_loader.get_batch(self.cfg.train["batch_size"], set_key, train=True, labels=True):
+                if self.ctc_weight > 0:
+                    kw = {"ctc_weight": self.ctc_weight, "x_lens": batch.get("x_len")}
                 with using_config("train", True):
                     loss = self.model.forward_loss(X=batch["X"], y=batch["y"], teach_ratio=ex["teach_ratio"],
                                                    random_out=ex["random_out"], add_noise=ex["speech_noise"],
-                                                   y_global=batch.get("y_global"), label_smoothing=self.label_smoothing)
+                                                   y_global=batch.get("y_global"), label_smoothing=self.label_smoothing, **kw)
                     self.model.cleargrads()
                     loss.backward()
                     self.optimizer.update()
-                cur = (loss.pair.clone(), len(batch["y"]), len(batch["X"]))   # the loss buffer is reused by the next step
+                # the loss buffer is reused by the next step
+                cur = ((loss.quad if loss.quad is not None else loss.pair).clone(), len(batch["y"]), len(batch["X"]))
                 if pending is not None:
                     settle(pending)
                 pending = cur
             if pending is not None:
                 settle(pending)
         torch.cuda.synchronize(self.model.device)      # later default-stream work (predict, checkpoint) sees the epoch's updates
+        self.ctc_epoch = (ctc_sum[0] / max(n_batches, 1), ctc_sum[1]) if self.ctc_weight > 0 else None
         return avg_loss
 
     # ---- nn.py:235-322

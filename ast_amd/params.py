@@ -79,6 +79,9 @@ def param_shapes(cfg, in_dim, vocab_size=None):
         n_in = H
     train["out/W"] = (V, A)
     train["out/b"] = (V,)
+    if rc.get("ctc", False):                                # extension: the CTC head on the encoder states, LAST,
+        train["ctc_out/W"] = (V, H)                         # so that every other name, offset and checkpoint is what it is without the key
+        train["ctc_out/b"] = (V,)
     return train, persist
 
 

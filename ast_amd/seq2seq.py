@@ -106,21 +106,31 @@ def draw_flags_and_targets(yh, teach_ratio, random_out, V, randint, rank=None, w
     return flags, tg
 
 
+def ctc_count_of(word):
+    """The int32 that astk_ctc_loss wrote into a float slot of the loss buffer (read back as a Python float)."""
+    return int(np.float32(word).view(np.int32))
+
+
 class LossData:
     """`loss.data` (nn.py:189: `float(loss.data)`): the 0-d device scalar, read through the persistent kernels' status word.  float(),
     .item(), .tolist() and NumPy conversion all read the [loss, status] pair in ONE copy and raise AstkError when a kernel of the step
     timed out -- a drop-in caller that only ever touches `.data` cannot train on with garbage.  `.tensor` is the raw 0-d tensor (no
     check, no synchronisation) for callers that keep the value on the device."""
 
-    def __init__(self, pair):
+    def __init__(self, pair, quad=None, model=None):
         self._pair = pair
+        self._quad, self._model = quad, model     # a step with the CTC branch: [loss, status, rows without a path (int32), attention loss]
 
     @property
     def tensor(self):
         return self._pair[0]
 
     def _checked(self):
-        v = self._pair.tolist()
+        if self._quad is not None:
+            v = self._quad.tolist()               # the same one copy, 16 bytes instead of 8
+            self._model.ctc_infeasible = ctc_count_of(v[2])
+        else:
+            v = self._pair.tolist()
         raise_if_aborted(v[1])
         return v[0]
 
@@ -147,10 +157,11 @@ class Loss:
     (nn.py:175-189).  `.pair` = [loss, status] on the device: the status word of the persistent kernels rides next to the scalar, so one
     read-back serves both."""
 
-    def __init__(self, model, pair):
+    def __init__(self, model, pair, quad=None):
         self._model = model
         self.pair = pair
-        self.data = LossData(pair)
+        self.quad = quad          # None, or (a step with ctc_weight > 0) [loss, status, int32 count of rows without a CTC path, attention loss]
+        self.data = LossData(pair, quad, model)
 
     def backward(self):
         self._model._backward()
@@ -356,6 +367,38 @@ def checked_label_smoothing(eps, what="label_smoothing"):
     return eps
 
 
+def checked_ctc_weight(weight, has_head, what="ctc_weight"):
+    """weight of the auxiliary CTC loss as a float; ValueError for anything but a finite number >= 0 (a bool or a string is no number),
+    and for a positive weight on a model without the head (model_cfg.json: rnn_config.ctc)."""
+    import numbers
+    if isinstance(weight, bool) or not isinstance(weight, (numbers.Real, np.floating, np.integer)):
+        raise ValueError(f"{what} must be a number >= 0, got {weight!r}")
+    weight = float(weight)
+    if not np.isfinite(weight) or weight < 0.0:
+        raise ValueError(f"{what} must be finite and >= 0, got {weight!r}")
+    if weight > 0.0 and not has_head:
+        raise ValueError(f"{what} = {weight!r} needs the CTC head: set rnn_config.ctc = true in model_cfg.json")
+    return weight
+
+
+def checked_x_lens(x_lens, B, T):
+    """Frames per row in front of the CNN as a (B,) int64 host array; ValueError for another count, a non-integer dtype or a length
+    outside 1..T.  A host array by contract: the lengths are mapped through the CNN's time formula on the host."""
+    if isinstance(x_lens, torch.Tensor):
+        if x_lens.device.type != "cpu":
+            raise ValueError("x_lens must be a host array (the loader has the true lengths on the host)")
+        x_lens = x_lens.numpy()
+    x_lens = np.asarray(x_lens)
+    if x_lens.ndim != 1 or x_lens.shape[0] != int(B):
+        raise ValueError(f"x_lens must name B = {int(B)} rows, got shape {tuple(x_lens.shape)}")
+    if not np.issubdtype(x_lens.dtype, np.integer):
+        raise ValueError(f"x_lens must hold integers, got {x_lens.dtype}")
+    if int(x_lens.min()) < 1 or int(x_lens.max()) > int(T):
+        raise ValueError(f"x_lens must lie in 1..T = {int(T)}, got [{int(x_lens.min())}, {int(x_lens.max())}]")
+    return x_lens.astype(np.int64)
+
+
+PAD_ID, GO_ID, EOS_ID, UNK_ID = 0, 1, 2, 3      # the vocabulary's reserved ids (the CTC branch: blank = PAD_ID, labels from UNK_ID on)
 ROWS_MAX = 32       # the device loop's batch (include/astk.h: B <= 32)
 
 
@@ -524,6 +567,12 @@ class SpeechEncoderDecoder:
         # bias sums, no side-stream work.  A few per cent slower; two runs over the same batches are then bit-identical in EVERY gradient,
         # which is what lets a soak see a hand-off race in the backward half of the step (train_cfg.json: extras.deterministic).
         self.deterministic = False
+        # Auxiliary CTC loss on the encoder states (extension): rnn_config.ctc adds the head ctc_out/W, ctc_out/b;
+        # forward_loss(ctc_weight=) trains on loss_attention + ctc_weight * mean_b nll_b.  Off (no head, or weight 0): nothing is
+        # allocated and nothing is launched.
+        self.ctc_head = bool(rc.get("ctc", False))
+        self.ctc_nll = None             # (B,) device tensor: the rows' -log p of the last step with ctc_weight > 0 (+inf: no path)
+        self.ctc_infeasible = 0         # rows without a path in that step: read with the loss, in the same copy (LossData)
 
     # ------------------------------------------------------------------ parameters
     def materialize(self, in_dim, values=None, seed=0):
@@ -576,7 +625,10 @@ class SpeechEncoderDecoder:
                 "encoder": "layer-by-layer one-layer stacks + " + ("Linear/BatchNorm/ReLU projections" if self.rnn_linear_proj else "LayerNorm kernels")
                 if self.enc_variant is not None else "one stack call (persistent wavefront kernels when the shape fits)",
                 "decoder": "per-launch loop (optional features)" if (self.rnn_ln or self.n_attn > 1 or not self.feed_attn or self.cfg["dropout"].get("out", 0))
-                else "persistent loop when the shape fits"}
+                else "persistent loop when the shape fits",
+                "ctc": "head ctc_out: one product + astk_ctc_loss behind the decoder forward, astk_ctc_head_bwd in front of the encoder backward, "
+                       "when forward_loss gets ctc_weight > 0; nothing is launched at 0" if self.ctc_head
+                else "off (no rnn_config.ctc head): nothing is allocated, nothing is launched"}
 
     def to_gpu(self, gpuid=None):
         if gpuid is not None and gpuid != self.gpuid:
@@ -730,7 +782,11 @@ class SpeechEncoderDecoder:
             bs = dict(cT=torch.zeros(nd, nl, B, h, **f32), hT=torch.zeros(nd, nl, B, h, **f32),
                       d_cT=torch.zeros(nd, nl, B, h, **f32), d_hT=torch.zeros(nd, nl, B, h, **f32),
                       c0=torch.zeros(nld, B, H, **f32), h0=torch.zeros(nld, B, H, **f32),
-                      d_c0=torch.zeros(nld, B, H, **f32), d_h0=torch.zeros(nld, B, H, **f32), loss=torch.zeros(2, **f32))
+                      d_c0=torch.zeros(nld, B, H, **f32), d_h0=torch.zeros(nld, B, H, **f32))
+            # [loss, status word] is the pair every reader knows; behind it, in the same 16 bytes, the CTC branch's count of rows
+            # without a path (an int32), so that ONE copy reads all three (LossData)
+            bs["loss4"] = torch.zeros(4, **f32)
+            bs["loss"] = bs["loss4"][:2]
             self._bstate[B] = bs
         st = dict(key=key, B=B, T=T, D=D, L=L, T2=T2, feat=feat, S=S, cd=cd, cp=cp, cg=cg, ld=ld, lp=lp, lg=lg, dd=dd, dp=dp, dg=dg,
                   ws_cnn=int(lib.astk_conv_bn_relu_workspace_bytes(C.byref(cd))),
@@ -967,14 +1023,14 @@ class SpeechEncoderDecoder:
         self._side = None
         self._side_by_main = {}
 
-    def _upload_flags(self, dst, flags):
+    def _upload_flags(self, dst, flags, ring="flag_ring"):
         """Host -> device copy of the teacher-forcing flags WITHOUT a host sync: a copy from pageable memory would make the host wait
         for the encoder of this step, and the GPU then idles while the host catches up at the start of the next one.  The flags
         go through a small ring of pinned buffers; a slot is reused only after the copy that read it has executed."""
-        ring = self._ws.get("flag_ring")
+        ring_key, ring = ring, self._ws.get(ring)           # (the CTC branch's row lengths travel the same way, through a ring of their own)
         if ring is None or ring["bufs"][0][0].numel() < len(flags):
             ring = {"i": 0, "bufs": [(torch.empty(max(64, len(flags)), dtype=torch.int32).pin_memory(), torch.cuda.Event()) for _ in range(8)]}
-            self._ws["flag_ring"] = ring
+            self._ws[ring_key] = ring
         buf, ev = ring["bufs"][ring["i"]]
         ring["i"] = (ring["i"] + 1) % len(ring["bufs"])
         ev.synchronize()                       # returns at once unless the host is 8 steps ahead
@@ -984,14 +1040,22 @@ class SpeechEncoderDecoder:
         dst.copy_(buf[:len(flags)], non_blocking=True)
         ev.record(torch.cuda.current_stream(self.device))
 
-    def forward_loss(self, X, y, teach_ratio, random_out=0, add_noise=0, y_global=None, label_smoothing=0.0):
-        """seq2seq.py:399-473.  label_smoothing (extension): eps of the training loss, uniform over all classes and
+    def forward_loss(self, X, y, teach_ratio, random_out=0, add_noise=0, y_global=None, label_smoothing=0.0, ctc_weight=0.0, x_lens=None):
+        """seq2seq.py:399-473.  ctc_weight (extension): weight of the auxiliary CTC loss of the `ctc_out` head on the
+        encoder states, loss = loss_attention + ctc_weight * mean_b nll_b; needs rnn_config.ctc; 0 = the reference's loss, and nothing
+        of the branch is launched.  The labels of a row are its targets from UNK_ID on (PAD, GO and EOS dropped), the blank is PAD_ID.
+        x_lens: host array of the rows' true frame counts in front of the CNN (None: every row has all T frames); read with
+        ctc_weight > 0 only.  The attention term, `pred` and every decoder gradient do not depend on either.  label_smoothing (extension): eps of the training loss, uniform over all classes and
         weighted by the target's class weight; 0 = the reference's loss.  Predictions and fed-back tokens do not depend on it.  y_global (data parallelism with random_out > 0 only): the targets of the WHOLE unsharded batch as a host
         array, global row b * world + r = row b of rank r -- the loader has them before it shards (`batch["y_global"]`); without it the
         ranks' targets are all-gathered, a host-blocking collective in front of every step."""
         label_smoothing = checked_label_smoothing(label_smoothing)
+        ctc_weight = checked_ctc_weight(ctc_weight, self.ctc_head)
         lib = self._require_gpu()
         X = self._as_input(X)
+        if ctc_weight > 0:
+            if x_lens is not None:
+                x_lens = checked_x_lens(x_lens, X.shape[0], X.shape[1])
         if isinstance(y, np.ndarray):
             y = torch.from_numpy(y)
         if hasattr(y, "data") and not isinstance(y, torch.Tensor):
@@ -1000,6 +1064,8 @@ class SpeechEncoderDecoder:
         y = y.to(self.device, torch.int32).contiguous()
         B, L = y.shape
         assert L >= 2, "targets need at least GO and EOS"
+        if ctc_weight > 0 and L > _lib.CTC_MAX_LABELS:
+            raise ValueError(f"ctc_weight > 0: targets of padded length {L} exceed ASTK_CTC_MAX_LABELS = {_lib.CTC_MAX_LABELS}")
         S = L - 1
         # quirk Q4: one Python-`random` coin per step for 0 < i < L-2, truth otherwise (seq2seq.py:431-436).  With random_out > 0
         # (seq2seq.py:456-465) the SAME stream also decides, behind each step's coin, which targets >= 4 are replaced (draw ABOVE
@@ -1048,9 +1114,84 @@ class SpeechEncoderDecoder:
                                       _vp(y), _vp(st["flags"]), _vp(st["emb_mask"]), _vp(st["rnn_masks"]), _vp(st["out_mask"]), _vp(targets),
                                       _vp(st["loss"]), _vp(st["pred"]), _vp(wd), wd.numel(), self._stream()))
         # (loss[1] = the persistent kernels' status word: written by the op itself, astk_decoder_desc.status_dst)
+        st["ctc"] = self._ctc_forward(st, y, ctc_weight, x_lens) if ctc_weight > 0 else None
         st["pending_backward"] = True
-        self.loss = Loss(self, st["loss"])
+        self.loss = Loss(self, st["loss"], st["loss4"] if st["ctc"] is not None else None)
         return self.loss
+
+    # ------------------------------------------------------------------ auxiliary CTC loss on the encoder states
+    def _t2_lens(self, st, x_lens):
+        """Device (B,) int32 of the rows' frames behind the CNN (the host maps the true lengths through cnn_out_lens), or None."""
+        if x_lens is None:
+            return None
+        cc = self.cfg["cnn_config"]["cnn_layers"]
+        t2 = [min(cnn_out_lens(cc, int(n))[-1], st["T2"]) for n in x_lens]
+        dst = self._pool("ctc_lens", (len(t2),), torch.int32)
+        self._upload_flags(dst, t2, ring="ctc_len_ring")
+        return dst
+
+    def _ctc_logits(self, st, s):
+        """logits (B T'', Vp) = enc_states W^T + b of the head, one product under the model's arithmetic, into a pooled buffer."""
+        lib = _lib.load()
+        rows, V, a = st["B"] * st["T2"], self.V, self.arena
+        Vp = (V + 3) // 4 * 4
+        logits = self._pool("ctc_logits", (rows, Vp))
+        check(lib.astk_ctc_head_fwd(rows, V, self.H, _vp(st["enc_states"]), a.p("ctc_out/W"), a.p("ctc_out/b"), _vp(logits), Vp,
+                                    _lib.PREC_BY_NAME[self.gemm_precision], s))
+        return logits, Vp
+
+    def _ctc_forward(self, st, y, weight, x_lens):
+        """Behind the decoder forward, on its stream: the head's logits, then astk_ctc_loss, which adds weight / B * sum_b nll_b to the
+        loss word the decoder wrote and leaves weight / B * d(sum nll) / d logits in place of the logits for _backward."""
+        lib = _lib.load()
+        s = self._stream()
+        B, T2, L = st["B"], st["T2"], int(y.shape[1])
+        lens = self._t2_lens(st, x_lens)
+        logits, Vp = self._ctc_logits(st, s)
+        cdesc = _lib.CtcDesc(B, T2, self.V, Vp, L, L, UNK_ID, PAD_ID)
+        nbytes = int(lib.astk_ctc_workspace_bytes(C.byref(cdesc)))
+        if not nbytes:
+            raise _lib.AstkError(lib.astk_last_error().decode())
+        ws = self._workspace("ctc", nbytes)
+        self.ctc_nll = self._pool("ctc_nll", (B,))
+        quad = st["loss4"]
+        quad[3:4].copy_(quad[0:1])                          # the attention term alone, for the log (nn.py: the epoch's mean CTC term)
+        check(lib.astk_ctc_loss(C.byref(cdesc), _vp(logits), _vp(y), _vp(lens), weight / B, _vp(self.ctc_nll), _vp(quad),
+                                _vp(logits), C.c_void_p(quad.data_ptr() + 8), _vp(ws), ws.numel(), s))
+        return dict(dlogits=logits, Vp=Vp)
+
+    def _ctc_backward(self, st, s):
+        """Between the decoder's chain phase (which wrote d_enc and performed the deferred zero fill of the gradient arena) and the
+        encoder's backward: d_enc += dlogits W, ctc_out/W.grad += dlogits^T enc, ctc_out/b.grad += column sums; main stream."""
+        c, a = st["ctc"], self.arena
+        check(_lib.load().astk_ctc_head_bwd(st["B"] * st["T2"], self.V, self.H, _vp(c["dlogits"]), c["Vp"], a.p("ctc_out/W"),
+                                            _vp(st["enc_states"]), _vp(st["d_enc"]), a.g("ctc_out/W"), a.g("ctc_out/b"),
+                                            _lib.PREC_BY_NAME[self.gemm_precision], 1 if self.deterministic else 0, s))
+
+    def ctc_predict(self, X, x_lens=None):
+        """Greedy decode of the CTC head (eval mode): encode the batch, the head's logits, the per-frame argmax over each row's valid
+        frames (astk_ctc_greedy), then on the host repeats collapsed and blanks dropped.  Returns a list of token lists."""
+        if not self.ctc_head:
+            raise ValueError("ctc_predict needs the CTC head: set rnn_config.ctc = true in model_cfg.json")
+        lib = self._require_gpu()
+        X = self._as_input(X)
+        if x_lens is not None:
+            x_lens = checked_x_lens(x_lens, X.shape[0], X.shape[1])
+        with using_config("train", False):
+            self._cur = None
+            self.encode(X)
+        st, s = self._cur, self._stream()
+        lens = self._t2_lens(st, x_lens)
+        logits, Vp = self._ctc_logits(st, s)
+        B, T2 = st["B"], st["T2"]
+        cdesc = _lib.CtcDesc(B, T2, self.V, Vp, 1, 1, UNK_ID, PAD_ID)
+        best = self._pool("ctc_best", (B, T2), torch.int32)
+        check(lib.astk_ctc_greedy(C.byref(cdesc), _vp(logits), _vp(lens), _vp(best), s))
+        out = []
+        for row in best.cpu().numpy():
+            prev = np.concatenate(([-1], row[:-1]))
+            out.append([int(c) for c in row[(row != prev) & (row != PAD_ID)]])
+        return out
 
     def _backward(self):
         lib = _lib.load()
@@ -1089,6 +1230,8 @@ class SpeechEncoderDecoder:
             st["dd"].side_wgs = 0
         else:
             dec_bwd(0, s)
+        if st.get("ctc") is not None:
+            self._ctc_backward(st, s)                        # behind the chain phase on the main stream: d_enc and the arena's zero fill are done
         # The decoder's gradient range is final here, but its all-reduce is NOT launched yet: an RCCL kernel holds its CUs until every
         # peer has arrived, and the encoder's backward recurrence (next) needs up to 192 CUs to itself to become resident -- a peer
         # that is late would turn into a time-out of the recurrence's bounded spins.  Both ranges go out behind the recurrence and

@@ -42,7 +42,16 @@ def load_npz(path, model, optimizer=None):
             model.V = int(z["out/W"].shape[0])
             model.cfg["rnn_config"]["dec_vocab_size"] = model.V
             model.materialize(infer_in_dim(model.cfg, z["L0_enc/upward/W"].shape[1]))
+        head = [k for k in model.arena.views if k.startswith("ctc_out/")]
+        headless = bool(head) and not any(k in keys for k in head)
+        if headless:
+            # a checkpoint from a model without the CTC head (the reference's own ASR -> AST copy_params.py flow): the head starts from
+            # its initial values; Adam moments of another arena size do not fit and are left alone too
+            print(f"{path}: no ctc_out head in the checkpoint; {', '.join(head)} keep their initial values")
+            optimizer = None
         for k, v in model.arena.views.items():
+            if headless and k in head:
+                continue
             if k not in keys:
                 raise KeyError(f"{path}: missing parameter {k}")
             v.copy_(torch.from_numpy(np.asarray(z[k], dtype=np.float32)).reshape(v.shape))

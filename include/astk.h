@@ -796,6 +796,48 @@ typedef struct {
 } astk_spec_augment_desc;
 int astk_spec_augment(float* X, int B, int T, int D, const int32_t* lengths, const astk_spec_augment_desc* d, uint64_t seed,
                       uint64_t counter0, uint64_t counter_stride, void* stream);
+/* ---------------------------------------------------------------- CTC loss on the encoder states
+ * Joint CTC-attention training: standard CTC over logits (B, T, V) with row stride ldv >= V, the given blank id, float32 in the log
+ * domain.  Not in the reference: off unless a caller asks for it.
+ *   labels of row b     the entries of y[b][0 .. L) (int32, row stride ldy) with id >= first_label, in order (ids >= V are read as V - 1);
+ *                       U of them, the extended sequence has S' = 2U + 1 states; U = 0 is allowed (only the all-blank path remains)
+ *   input_len           (B) valid frames per row, clamped to [0, T]; NULL = T for every row
+ *   row_nll[b]          -log p(labels_b | logits_b[0 : input_len[b]])
+ *   dlogits             scale * d(sum of the feasible rows' nll) / d logits = scale * (softmax - posterior occupancy); every valid frame's
+ *                       gradient sums to zero over v; frames at t >= input_len[b] and the columns V .. ldv of every frame are set to 0.
+ *                       May alias logits.
+ *   infeasible rows     input_len[b] < U + (number of adjacent equal labels): row_nll = +inf, nothing added to loss_acc, dlogits all
+ *                       zero, counted in *n_infeasible (NULL or one int32, overwritten)
+ *   loss_acc            NULL or one float: += scale * sum of the feasible rows' nll, by one thread in row order, in stream order behind
+ *                       whatever wrote it before
+ * No floating-point atomics: row_nll, loss_acc and dlogits are bit-identical from run to run.  Four launches, no allocation, no
+ * synchronisation; ws of astk_ctc_workspace_bytes (16-byte aligned; alpha and the gathered emissions, 2 T (2L + 1) floats per row).
+ * Refused from the descriptor alone, before any launch, with a message: a wrong struct_size; B, T, L < 1; V < 2; ldv < V; ldy < L; a
+ * blank outside [0, V); first_label <= blank; L > ASTK_CTC_MAX_LABELS (a row holds at most L labels, and the rows' label counts are
+ * device data: the bound on L is what keeps every U within ASTK_CTC_MAX_LABELS; the shipped max_pred is 175).
+ * astk_ctc_greedy: best[b][t] = the argmax class of frame t (ties: the lowest index) for t < input_len[b], the blank behind it.
+ * astk_ctc_head_fwd: the linear head, logits (rows, V; row stride ldv) = enc (rows, H) W^T + b, as ONE product under the forward ops'
+ *   two-contributor rule (bit-identical from run to run) and the given arithmetic; astk_gemm_f32_ex otherwise.
+ * astk_ctc_head_bwd: its backward under one arithmetic / deterministic setting, three launches:
+ *   d_enc (rows, H) += dlogits W;  dW (V, H) += dlogits^T enc;  db (V) += column sums of dlogits.   (rows = B T; ldv, H multiples of 4) */
+#define ASTK_CTC_MAX_LABELS 255
+typedef struct {
+  size_t struct_size;   /* = sizeof(astk_ctc_desc) */
+  int B, T, V;
+  long ldv;
+  int L;
+  long ldy;
+  int first_label;
+  int blank;
+} astk_ctc_desc;
+size_t astk_ctc_workspace_bytes(const astk_ctc_desc* d);      /* 0 for a descriptor the calls refuse (astk_last_error) */
+int astk_ctc_loss(const astk_ctc_desc* d, const float* logits, const int32_t* y, const int32_t* input_len, float scale, float* row_nll,
+                  float* loss_acc, float* dlogits, int32_t* n_infeasible, void* ws, size_t ws_bytes, void* stream);
+int astk_ctc_greedy(const astk_ctc_desc* d, const float* logits, const int32_t* input_len, int32_t* best, void* stream);
+int astk_ctc_head_fwd(int rows, int V, int H, const float* enc, const float* W, const float* b, float* logits, long ldv, int precision,
+                      void* stream);
+int astk_ctc_head_bwd(int rows, int V, int H, const float* dlogits, long ldv, const float* W, const float* enc, float* d_enc, float* dW,
+                      float* db, int precision, int deterministic, void* stream);
 /* One wavefront that keeps `stream` busy for `usec` microseconds (<= 100 000) and then increments *flag (may be NULL).  For probing
  * whether two streams really execute concurrently: HIP multiplexes streams onto a few hardware queues (GPU_MAX_HW_QUEUES, 4 by
  * default), and two streams that share one are serialised whatever their events say (ast_amd/seq2seq.py:_cu_streams). */
