@@ -35,13 +35,13 @@ constexpr int SIDE_CHUNKS_MAX = 60;
 enum LstmPath { LSTM_PER_STEP = 0, LSTM_PERSIST = 1, LSTM_HOISTED = 2 };      // what astk_lstm_stack_path returns
 struct LstmRoute {
   LstmPath path;
-  int rows;        // form of the recurrence workgroups (lstm_persist.h: 16, 32 or 33); 16 on the hoisted path
+  int rows;        // form of the recurrence workgroups (lstm_persist.h: LSTM_ROWS_16, _MT2 or _DUO); 16 on the hoisted path
   int lpl;         // layers per launch: groups start at multiples of it (<= n_layers; 1 on the hoisted path)
   int wgs_first;   // workgroups of the first launch: what the side-stream plans leave to the recurrence
   int wg_rows;     // (virtual) workgroup rows of a cell: rows of the counters, arrivals per unit slice, rows of the db sums
 };
 LstmRoute lstm_route(const astk_lstm_stack_desc* d) {
-  LstmRoute R = {LSTM_PER_STEP, 16, 0, 0, lstm_persist_wg_rows(d->B, 16)};
+  LstmRoute R = {LSTM_PER_STEP, LSTM_ROWS_16, 0, 0, lstm_persist_wg_rows(d->B, LSTM_ROWS_16)};
   if (!lstm_persist_applicable(d->T, d->B, d->h, d->n_layers, d->n_dirs)) return R;
   R.path = lstm_persist_hoisted(d->h) ? LSTM_HOISTED : LSTM_PERSIST;
   R.rows = lstm_persist_rows(d->B, d->h, d->n_layers, d->n_dirs, d->side_stream != nullptr);
@@ -73,7 +73,7 @@ SidePlan plan_side_fwd(const astk_lstm_stack_desc* d, const LstmRoute& R) {
   if (cs <= 0) cs = tile_rows * 128 / d->B;
   if (cs < 4 || d->T < 3 * cs / 2) return sp;
   const double t_chunk = ((d->in_dim + 15) / 16) * 0.66 + 15.0;           // one tile pass (every workgroup of a chunk launch does one)
-  const double r_step = (d->h > 256 ? 3.8 : R.rows == 32 ? 4.4 : R.rows == 33 ? 3.3 : 2.9) * 0.9; // (10 % margin)
+  const double r_step = (d->h > 256 ? 3.8 : R.rows == LSTM_ROWS_MT2 ? 4.4 : R.rows == LSTM_ROWS_DUO ? 3.3 : 2.9) * 0.9; // (10 % margin)
   // (the side stream starts together with the in-line head, so the chunks have the head's time -- ~190 TFLOP/s on the whole chip -- on top)
   const double head_step = 0.8 * d->n_dirs * 2.0 * d->B * 4.0 * d->h * d->in_dim / 190e6;
   for (int n = std::min(SIDE_CHUNKS_MAX, (d->T - 2) / cs); n >= 1; --n) {
@@ -194,7 +194,7 @@ int make_plan(const astk_lstm_stack_desc* d, void* ws, LstmRoute& R, LstmPlan& P
   Carver c(ws);
   const size_t tb = (size_t)P.T * P.B;
   // what is sized by the workgroup rows holds an EVEN number of 16-row tiles, whatever form a call takes: the 512-thread form's count
-  const size_t wg_rows_max = (size_t)lstm_persist_wg_rows(P.B, 33);
+  const size_t wg_rows_max = (size_t)lstm_persist_wg_rows(P.B, LSTM_ROWS_DUO);
   P.perm = c.take<int>(P.T);
   P.inv = c.take<int>(P.T);
   for (int dd = 0; dd < P.nd; ++dd) {

@@ -25,6 +25,10 @@ bool lstm_persist_hoisted(int h);
 bool lstm_persist_applicable(int T, int B, int h, int nl, int nd);
 // Form of the recurrence workgroups (the `rows` argument of everything below): 16 = one 16-row batch tile per 256-thread workgroup;
 // 33 = DUO: two 16-row tiles per 512-thread workgroup; 32 = MT 2: two tiles per 256-thread workgroup (lstm_persist.hip has the measurements)
+constexpr int LSTM_ROWS_16 = 16, LSTM_ROWS_MT2 = 32, LSTM_ROWS_DUO = 33;
+// Arithmetic of the recurrences' products (the kernels' template argument XS, so the values are fixed): f32 MFMAs; fp16x2 = two-term fp16
+// splits; bf16x3 = three-term bf16 splits, resident weights in registers (h <= 256); bf16x3 with the weights' lo plane in LDS (h >= 512)
+constexpr int LSTM_XS_F32 = 0, LSTM_XS_FP16X2 = 2, LSTM_XS_BF16X3 = 3, LSTM_XS_BF16X3_LDS = 4;
 int lstm_persist_rows(int B, int h, int nl, int nd, bool side);
 // (Virtual) workgroup rows of a cell under form `rows`: 16-row batch tiles at 16; at 33 two virtual workgroups per 32 rows, so an EVEN number
 // of 16-row tiles (what lstm.hip sizes the workspace for, whatever the form); at 32 one workgroup per 32 rows.  The grid has as many rows at 16

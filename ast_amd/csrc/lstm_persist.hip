@@ -20,6 +20,16 @@
 //                        with ONE lane and fetches the partials a step early).  Counters are zeroed before every launch.
 // Every spin is bounded: on time-out a workgroup raises the abort word, every poll loop checks it, and the grid drains.
 // Residency: the launcher only uses this path when the whole grid fits one workgroup per CU (<= 256 workgroups).
+//
+// Where things are.  Every kernel is one of two step functions, instantiated over width (KB = h / 64), arithmetic (XS) and form (MT, DUO);
+// their phases are the blocks under the `// ===== F... / B...` banners:
+//   lstm_fwd_steps     F0 resident weights, F1 set-up, F2 prologue; per step F3 top (h loads issued, upward product, x taken over), F4 the
+//                      wait W_t, F5 recurrent product, F6 off-path traffic, F7 LDS reduction + gates + hand-off stores
+//   lstm_bwd_rs_steps  B0 resident weights, B1 set-up; per step B2 partials from above, B3 own partials, B4 gate epilogue, B5 barrier +
+//                      deferred arrivals + fetches, B6 product 1, B7 / B8 product 2 around the slot reset and the dz stores; B9 behind the loop
+// What the phases share stands once in front of them: fwd_gate_products / bwd_tile_product (the arithmetic ladder of each product shape),
+// resident_frag, frag_issue / frag_ok / frag_wait, SPIN_TAIL; DESIGN.md section 29 says what the register figures kept in line.  The
+// launchers and the choice of kernel (form, width, arithmetic -> instantiation) are at the end of the file.
 #include "lstm_persist.h"
 #include "handoff.h"
 #include <type_traits>
@@ -103,13 +113,6 @@ struct PBwdArgs {
   ACC = __builtin_amdgcn_mfma_f32_16x16x4f32((A4).z, (W4).z, ACC, 0, 0, 0);  \
   ACC = __builtin_amdgcn_mfma_f32_16x16x4f32((A4).w, (W4).w, ACC, 0, 0, 0);
 
-// four independent accumulators (the gates) interleaved so that no MFMA waits on the previous one's result
-#define MFMA4G(ACC, A4, W)                                                                    \
-  _Pragma("unroll") for (int g_ = 0; g_ < 4; ++g_) ACC[g_] = __builtin_amdgcn_mfma_f32_16x16x4f32((A4).x, (W)[g_].x, ACC[g_], 0, 0, 0); \
-  _Pragma("unroll") for (int g_ = 0; g_ < 4; ++g_) ACC[g_] = __builtin_amdgcn_mfma_f32_16x16x4f32((A4).y, (W)[g_].y, ACC[g_], 0, 0, 0); \
-  _Pragma("unroll") for (int g_ = 0; g_ < 4; ++g_) ACC[g_] = __builtin_amdgcn_mfma_f32_16x16x4f32((A4).z, (W)[g_].z, ACC[g_], 0, 0, 0); \
-  _Pragma("unroll") for (int g_ = 0; g_ < 4; ++g_) ACC[g_] = __builtin_amdgcn_mfma_f32_16x16x4f32((A4).w, (W)[g_].w, ACC[g_], 0, 0, 0);
-
 // fp16x2 form of the recurrences' products (template parameter X2): the weights a workgroup keeps in registers are split ONCE
 // into fp16 hi / lo fragments behind a per-workgroup power-of-two scale, the 16 x K activation fragments of a step are split when they
 // arrive (scale 2^10: |h| < 1 and a dropped-out input is at most 1 / (1 - p)), and 32 k of a product are three
@@ -122,44 +125,7 @@ struct PBwdArgs {
 // XS (0 f32 MFMAs, 2 fp16x2, 3 bf16x3) is a template parameter of both kernels: the launchers pick it from the arithmetic in force for the call
 // (descriptor precision, else the process default), so that one process can time the step under every arithmetic.
 constexpr float ACT_SCALE = 1024.f, ACT_SCALE_INV = 1.f / 1024.f;
-// four independent accumulators (the gates) interleaved, three term products of 32 k each
-#define MFMA32HG(ACC, A, W)                                                                                                     \
-  _Pragma("unroll") for (int g_ = 0; g_ < 4; ++g_)                                                                              \
-    ACC[g_] = __builtin_amdgcn_mfma_f32_16x16x32_f16(__builtin_bit_cast(h16x8, (A).lo), __builtin_bit_cast(h16x8, (W)[g_].hi), ACC[g_], 0, 0, 0); \
-  _Pragma("unroll") for (int g_ = 0; g_ < 4; ++g_)                                                                              \
-    ACC[g_] = __builtin_amdgcn_mfma_f32_16x16x32_f16(__builtin_bit_cast(h16x8, (A).hi), __builtin_bit_cast(h16x8, (W)[g_].lo), ACC[g_], 0, 0, 0); \
-  _Pragma("unroll") for (int g_ = 0; g_ < 4; ++g_)                                                                              \
-    ACC[g_] = __builtin_amdgcn_mfma_f32_16x16x32_f16(__builtin_bit_cast(h16x8, (A).hi), __builtin_bit_cast(h16x8, (W)[g_].hi), ACC[g_], 0, 0, 0);
-// bf16x3: four independent accumulators (the gates) interleaved, six term products of 32 k each (smallest first)
-#define MFMA32BG_T_(ACC, AP, W, WP) _Pragma("unroll") for (int g_ = 0; g_ < 4; ++g_) { MFMA_B16_(ACC[g_], AP, (W)[g_].WP) }
-#define MFMA32BG(ACC, A, W)          \
-  MFMA32BG_T_(ACC, (A).lo, W, hi)    \
-  MFMA32BG_T_(ACC, (A).hi, W, lo)    \
-  MFMA32BG_T_(ACC, (A).mid, W, mid)  \
-  MFMA32BG_T_(ACC, (A).mid, W, hi)   \
-  MFMA32BG_T_(ACC, (A).hi, W, mid)   \
-  MFMA32BG_T_(ACC, (A).hi, W, hi)
 // fragment type and helpers of a split scheme XS (2: fp16 hi / lo behind a scale, 3: bf16 hi / mid / lo)
-// XS = 4 forms of the two macros above: W holds hi / mid, LOP points at this thread's lo fragments in LDS (gate g at LOP[g * 256])
-#define MFMA32BG4_T_(ACC, AP, WEXPR) _Pragma("unroll") for (int g_ = 0; g_ < 4; ++g_) { MFMA_B16_(ACC[g_], AP, WEXPR) }
-#define MFMA32BG4(ACC, A, W, LOP)              \
-  {                                            \
-    u32q lo_[4];                               \
-    _Pragma("unroll") for (int g_ = 0; g_ < 4; ++g_) lo_[g_] = (LOP)[g_ * 256]; \
-    MFMA32BG4_T_(ACC, (A).lo, (W)[g_].hi)      \
-    MFMA32BG4_T_(ACC, (A).hi, lo_[g_])         \
-    MFMA32BG4_T_(ACC, (A).mid, (W)[g_].mid)    \
-    MFMA32BG4_T_(ACC, (A).mid, (W)[g_].hi)     \
-    MFMA32BG4_T_(ACC, (A).hi, (W)[g_].mid)     \
-    MFMA32BG4_T_(ACC, (A).hi, (W)[g_].hi)      \
-  }
-#define MFMA32B4(ACC, A, W, LOV)   \
-  MFMA_B16_(ACC, (A).lo, (W).hi)  \
-  MFMA_B16_(ACC, (A).hi, LOV)     \
-  MFMA_B16_(ACC, (A).mid, (W).mid) \
-  MFMA_B16_(ACC, (A).mid, (W).hi) \
-  MFMA_B16_(ACC, (A).hi, (W).mid) \
-  MFMA_B16_(ACC, (A).hi, (W).hi)
 template <int XS> struct FragOf { typedef HL8 type; };
 template <> struct FragOf<3> { typedef HML8 type; };
 template <> struct FragOf<4> { typedef HML8 type; };
@@ -176,6 +142,51 @@ template <int XS>
 __device__ __forceinline__ typename FragOf<XS>::type split_frag(const float4& a, const float4& b, float scl) {
   if constexpr (XS == 3 || XS == 4) return split8b(a, b);
   else return split8(a, b, scl);
+}
+// One 32-k fragment of a RESIDENT weight (all four weights: forward lateral / upward, backward recurrent / down) in the form XS keeps:
+// hi / lo behind the workgroup's scale (2), hi / mid / lo (3), hi / mid with the lo fragment handed back in `lo` for this thread's LDS slot (4).
+// (The caller stores `lo`: with the store in here, through a pointer, the five forward XS = 4 kernels came out different)
+template <int XS>
+__device__ __forceinline__ typename WFragOf<XS>::type resident_frag(const float4& a, const float4& b, float wscl, u32q& lo) {
+  if constexpr (XS == 4) {
+    const HML8 t = split8b(a, b);
+    lo = t.lo;
+    return HM8{t.hi, t.mid};
+  } else {
+    return split_frag<XS>(a, b, wscl);
+  }
+}
+// The four gates' products of ONE activation fragment against ONE k block of resident weight fragments, under arithmetic XS (both forward
+// products: upward and recurrent).  Four independent accumulators (the gates) interleaved so that no MFMA waits on the previous one's result.
+//   XS = 0: a = 16 k as f32, w = the four gates' f32 fragments: four v_mfma_f32_16x16x4_f32 per gate
+//   XS = 2: a = 32 k as fp16 hi / lo: three term products
+//   XS = 3: a = 32 k as bf16 hi / mid / lo: six term products (smallest first)
+//   XS = 4: as 3; w holds hi / mid, `lo` points at this thread's lo fragments in LDS (gate g at lo[g * 256])
+// (The activation fragment BY VALUE: taken by const reference, the three h = 128 kernels fwd_duo<2>, fwd_g<2, 2, 1> and fwd_g<2, 3, 1> came
+//  out with four v_mov_b64 in other places)
+template <int XS, class A, class W>
+__device__ __forceinline__ void fwd_gate_products(f32x4 (&acc)[4], const A a, const W (&w)[4], const u32q* lo) {
+#define GATES_ _Pragma("unroll") for (int g_ = 0; g_ < 4; ++g_)
+  if constexpr (XS == 0) {
+    GATES_ acc[g_] = __builtin_amdgcn_mfma_f32_16x16x4f32(a.x, w[g_].x, acc[g_], 0, 0, 0);
+    GATES_ acc[g_] = __builtin_amdgcn_mfma_f32_16x16x4f32(a.y, w[g_].y, acc[g_], 0, 0, 0);
+    GATES_ acc[g_] = __builtin_amdgcn_mfma_f32_16x16x4f32(a.z, w[g_].z, acc[g_], 0, 0, 0);
+    GATES_ acc[g_] = __builtin_amdgcn_mfma_f32_16x16x4f32(a.w, w[g_].w, acc[g_], 0, 0, 0);
+  } else if constexpr (XS == 2) {
+    GATES_ acc[g_] = __builtin_amdgcn_mfma_f32_16x16x32_f16(__builtin_bit_cast(h16x8, a.lo), __builtin_bit_cast(h16x8, w[g_].hi), acc[g_], 0, 0, 0);
+    GATES_ acc[g_] = __builtin_amdgcn_mfma_f32_16x16x32_f16(__builtin_bit_cast(h16x8, a.hi), __builtin_bit_cast(h16x8, w[g_].lo), acc[g_], 0, 0, 0);
+    GATES_ acc[g_] = __builtin_amdgcn_mfma_f32_16x16x32_f16(__builtin_bit_cast(h16x8, a.hi), __builtin_bit_cast(h16x8, w[g_].hi), acc[g_], 0, 0, 0);
+  } else {
+    u32q wlo[4];
+    GATES_ { if constexpr (XS == 4) wlo[g_] = lo[g_ * 256]; else wlo[g_] = w[g_].lo; }
+    GATES_ { MFMA_B16_(acc[g_], a.lo, w[g_].hi) }
+    GATES_ { MFMA_B16_(acc[g_], a.hi, wlo[g_]) }
+    GATES_ { MFMA_B16_(acc[g_], a.mid, w[g_].mid) }
+    GATES_ { MFMA_B16_(acc[g_], a.mid, w[g_].hi) }
+    GATES_ { MFMA_B16_(acc[g_], a.hi, w[g_].mid) }
+    GATES_ { MFMA_B16_(acc[g_], a.hi, w[g_].hi) }
+  }
+#undef GATES_
 }
 // workgroup-wide maximum of a per-thread value (256 threads; `red` = 4 floats of LDS scratch; ends with a barrier)
 __device__ __forceinline__ float wg_max(float m, float* red) {
@@ -211,9 +222,7 @@ __device__ __forceinline__ float amax4f(float m, const float4& v) { return fmaxf
 // word is the sentinel.  4-byte stores are single-copy atomic, nothing is reused within a launch, so no tag, no flag, no
 // drain, no barrier is needed, and the buffers double as the saved activations the later launches read.
 constexpr unsigned SENTINEL = 0xffffffffu;
-#ifndef ASTK_FRAG_WAIT_SWEEP
-#define ASTK_FRAG_WAIT_SWEEP 3
-#endif
+constexpr unsigned FRAG_WAIT_SWEEPS = 3;      // whole sweeps a slow path makes before it polls one word per lane (frag_wait)
 template <int NB>
 __device__ __forceinline__ void frag_issue(__amdgpu_buffer_rsrc_t rs, int byte_off, int wave, u32q (&g)[NB]) {
 #pragma unroll
@@ -228,6 +237,12 @@ __device__ __forceinline__ bool frag_ok(const u32q (&g)[NB]) {
   for (int i = 0; i < NB; ++i) m = max(max(m, g[i].x), max(max(g[i].y, g[i].z), g[i].w));
   return __all(m != SENTINEL);
 }
+// Tail of every bounded spin of this file (frag_wait, the forward chunk-flag wait, the backward sweep's slow path): count the poll; past the
+// bound raise the abort word and give up; look at the abort word every 64th poll.
+// (A macro: as a function -- bool result, or void with `dead` by reference -- it changed the figures of 25 to 36 kernels)
+#define SPIN_TAIL(SPINS, DEAD, AB)                                   \
+  if (++(SPINS) > ((AB).limit >> 1)) { abort_raise(AB); (DEAD) = true; } \
+  else if (((SPINS) & 63u) == 0 && abort_seen(AB)) (DEAD) = true;
 // Slow path: some fragment was not there yet.  Poll ONE fragment per lane until it is complete (waiting waves must not
 // flood the fabric with full sweeps), then re-read everything; repeat until complete.  Bounded; a time-out raises the
 // abort word, which every other spin checks, and the grid drains.
@@ -235,28 +250,27 @@ template <int NB>
 __device__ __forceinline__ void frag_wait(__amdgpu_buffer_rsrc_t rs, int byte_off, int wave, u32q (&g)[NB], bool& dead, const AbortCtl& ab) {
   unsigned spins = 0;
   while (!dead) {
-#if ASTK_FRAG_WAIT_SWEEP
     // the first retries are whole sweeps: a miss then costs one more round trip, not two (poll, then re-read); a producer that is
     // really late is polled with one fragment per lane as before
-    if (spins < ASTK_FRAG_WAIT_SWEEP) {
+    if (spins < FRAG_WAIT_SWEEPS) {
       frag_issue<NB>(rs, byte_off, wave, g);
       if (frag_ok<NB>(g)) return;
       ++spins;
       continue;
     }
-#endif
     const u32q c = __builtin_amdgcn_raw_buffer_load_b128(rs, byte_off + 64 * wave, 0, 16);
     if (__all((c.x != SENTINEL) & (c.y != SENTINEL) & (c.z != SENTINEL) & (c.w != SENTINEL))) {
       frag_issue<NB>(rs, byte_off, wave, g);
       if (frag_ok<NB>(g)) return;
     }
-    if (++spins > (ab.limit >> 1)) { abort_raise(ab); dead = true; }
-    else if ((spins & 63u) == 0 && abort_seen(ab)) dead = true;
+    SPIN_TAIL(spins, dead, ab)
   }
 }
 __device__ __forceinline__ float4 frag_vals(const u32q& g) {
   return make_float4(__uint_as_float(g.x), __uint_as_float(g.y), __uint_as_float(g.z), __uint_as_float(g.w));
 }
+// ... and the way back: 16 bytes of results as the words raw_buffer_store_b128 takes
+template <class V> __device__ __forceinline__ u32q as_u32q(const V v) { return __builtin_bit_cast(u32q, v); }      // (f32x4 or float4)
 
 // Schedule of one step t (wave view).  vmcnt retires in issue order and the compiler cannot count memory operations
 // across branches, so every wait in the loop is in effect "everything issued so far"; the schedule is therefore built so
@@ -291,6 +305,7 @@ __device__ __forceinline__ void lstm_fwd_steps(const PFwdArgs& a, const PCellF& 
   const int m0 = bt * 16 * MT;
   bool dead = false;
 
+  // ================= F0: resident weights -- this workgroup's slices of W_l (and W_u), loaded and split ONCE per launch =================
   auto wl_at = [&](int i, int g) { return *reinterpret_cast<const float4*>(c.Wl + (long)(4 * (j0 + r) + g) * h + 16 * (wave + 4 * i) + 4 * q); };
   auto wu_at = [&](int i, int g) { return *reinterpret_cast<const float4*>(c.Wu + (long)(4 * (j0 + r) + g) * h + 16 * (wave + 4 * i) + 4 * q); };
   // X2: the resident weights as fp16 hi / lo fragments of v_mfma_f32_16x16x32_f16: 16-k blocks i, i+1 of this wave form one 32-k operand
@@ -322,18 +337,12 @@ __device__ __forceinline__ void lstm_fwd_steps(const PFwdArgs& a, const PCellF& 
     for (int p = 0; p < NPR; ++p)
 #pragma unroll
       for (int g = 0; g < 4; ++g) {
-        if constexpr (XS == 4) {
-          const HML8 t = split8b(wl_at(2 * p, g), 2 * p + 1 < KB ? wl_at(2 * p + 1, g) : zero4);
-          wlh[p][g].hi = t.hi; wlh[p][g].mid = t.mid;
-          lo_l[(p * 4 + g) * 256] = t.lo;
-          if constexpr (HAS_UP) {
-            const HML8 u = split8b(wu_at(2 * p, g), 2 * p + 1 < KB ? wu_at(2 * p + 1, g) : zero4);
-            wuh[p][g].hi = u.hi; wuh[p][g].mid = u.mid;
-            lo_u[(p * 4 + g) * 256] = u.lo;
-          }
-        } else {
-        wlh[p][g] = split_frag<XS>(wl_at(2 * p, g), 2 * p + 1 < KB ? wl_at(2 * p + 1, g) : zero4, wscl);
-        if constexpr (HAS_UP) wuh[p][g] = split_frag<XS>(wu_at(2 * p, g), 2 * p + 1 < KB ? wu_at(2 * p + 1, g) : zero4, wscl);
+        u32q lo;
+        wlh[p][g] = resident_frag<XS>(wl_at(2 * p, g), 2 * p + 1 < KB ? wl_at(2 * p + 1, g) : zero4, wscl, lo);
+        if constexpr (XS == 4) lo_l[(p * 4 + g) * 256] = lo;
+        if constexpr (HAS_UP) {
+          wuh[p][g] = resident_frag<XS>(wu_at(2 * p, g), 2 * p + 1 < KB ? wu_at(2 * p + 1, g) : zero4, wscl, lo);
+          if constexpr (XS == 4) lo_u[(p * 4 + g) * 256] = lo;
         }
       }
   } else {
@@ -345,6 +354,7 @@ __device__ __forceinline__ void lstm_fwd_steps(const PFwdArgs& a, const PCellF& 
         if constexpr (HAS_UP) wu[i][g] = wu_at(i, g);
       }
   }
+  // ================= F1: set-up -- buffer resources, epilogue ownership, chunk flags of the input projection, the deferred stores =======
   const __amdgpu_buffer_rsrc_t r_own = make_rsrc(c.HR);
   const __amdgpu_buffer_rsrc_t r_below = make_rsrc(HAS_UP ? c.xin : c.HR);
   // layer 0: the input projection of all time steps comes from a batched product; with time-chunked products on a side stream
@@ -400,8 +410,7 @@ __device__ __forceinline__ void lstm_fwd_steps(const PFwdArgs& a, const PCellF& 
     unsigned spins = 0;
     while (seen == 0u && !dead) {
       seen = ld_flag(fp);
-      if (++spins > (ab.limit >> 1)) { abort_raise(ab); dead = true; }
-      else if ((spins & 63u) == 0 && abort_seen(ab)) dead = true;
+      SPIN_TAIL(spins, dead, ab)
     }
   };
   auto zx_enter = [&](int ts) {              // (uniform) the rows of step ts are about to be loaded
@@ -436,7 +445,7 @@ __device__ __forceinline__ void lstm_fwd_steps(const PFwdArgs& a, const PCellF& 
   const bool timing = (dbg & 8) != 0;
 #define TICK(i, t0) if (timing) { __builtin_amdgcn_sched_barrier(0); const long long now_ = wall_clock64(); tk[i] += now_ - t0; t0 = now_; __builtin_amdgcn_sched_barrier(0); }
 
-  // ---- prologue: inputs of step 0; x_0 into registers, x_1 in flight
+  // ================= F2: prologue -- inputs of step 0; x_0 into registers, x_1 in flight =================
   float4 zadd[MT], zadd_n[MT];
   float mk_raw[MT], mk_raw_n[MT];
   if (!HAS_UP && zflags) {
@@ -465,6 +474,7 @@ __device__ __forceinline__ void lstm_fwd_steps(const PFwdArgs& a, const PCellF& 
   // One step.  FIRST: no recurrent part (h_{-1} = 0).
   auto step = [&](auto first_tag, int t) {
     constexpr bool FIRST = decltype(first_tag)::value;
+    // ================= F3: top of the step -- h_{t-1} loads issued, upward product from registers, x_{t+1} taken over =================
     long long t0 = timing ? wall_clock64() : 0;
     f32x4 acc[MT][4];
 #pragma unroll
@@ -483,14 +493,12 @@ __device__ __forceinline__ void lstm_fwd_steps(const PFwdArgs& a, const PCellF& 
 #pragma unroll
         for (int p = 0; p < NPR; ++p)
 #pragma unroll
-          for (int mt = 0; mt < MT; ++mt) {
-            if constexpr (XS == 4) { MFMA32BG4(acc[mt], axh[mt][p], wuh[p], lo_u + p * 4 * 256) } else if constexpr (XS == 3) { MFMA32BG(acc[mt], axh[mt][p], wuh[p]) } else { MFMA32HG(acc[mt], axh[mt][p], wuh[p]) }
-          }
+          for (int mt = 0; mt < MT; ++mt) fwd_gate_products<XS>(acc[mt], axh[mt][p], wuh[p], lo_u + p * 4 * 256);
       } else {
 #pragma unroll
         for (int i = 0; i < KB; ++i)
 #pragma unroll
-          for (int mt = 0; mt < MT; ++mt) { MFMA4G(acc[mt], ax[mt][i], wu[i]) }
+          for (int mt = 0; mt < MT; ++mt) fwd_gate_products<XS>(acc[mt], ax[mt][i], wu[i], nullptr);
       }
     }
     const int t1 = min(t + 1, T - 1), t2 = min(t + 2, T - 1);
@@ -504,7 +512,7 @@ __device__ __forceinline__ void lstm_fwd_steps(const PFwdArgs& a, const PCellF& 
     }
     __builtin_amdgcn_sched_barrier(0);
     TICK(0, t0)
-    // ---- W_t
+    // ================= F4: W_t, the step's ONE wait point -- h_{t-1} complete? (slow path: frag_wait) =================
     if (!FIRST) {
 #pragma unroll
       for (int mt = 0; mt < MT; ++mt)
@@ -516,6 +524,7 @@ __device__ __forceinline__ void lstm_fwd_steps(const PFwdArgs& a, const PCellF& 
     // loads issued next.
     __builtin_amdgcn_s_waitcnt(0x0F70);
     { const long long b2_ = tk[2]; TICK(2, t0) if (timing && tk[2] - b2_ > 100) { big2 += tk[2] - b2_; ++nbig2; } }
+    // ================= F5: recurrent product, h_{t-1} W_l^T =================
     if (!FIRST) {
       if constexpr (X2) {
 #pragma unroll
@@ -523,7 +532,7 @@ __device__ __forceinline__ void lstm_fwd_steps(const PFwdArgs& a, const PCellF& 
 #pragma unroll
           for (int mt = 0; mt < MT; ++mt) {
             const Frag ah = split_frag<XS>(frag_vals(gh[mt][2 * p]), 2 * p + 1 < KB ? frag_vals(gh[mt][2 * p + 1 < KB ? 2 * p + 1 : 0]) : zero4, ACT_SCALE);
-            if constexpr (XS == 4) { MFMA32BG4(acc[mt], ah, wlh[p], lo_l + p * 4 * 256) } else if constexpr (XS == 3) { MFMA32BG(acc[mt], ah, wlh[p]) } else { MFMA32HG(acc[mt], ah, wlh[p]) }
+            fwd_gate_products<XS>(acc[mt], ah, wlh[p], lo_l + p * 4 * 256);
           }
       } else {
 #pragma unroll
@@ -531,12 +540,13 @@ __device__ __forceinline__ void lstm_fwd_steps(const PFwdArgs& a, const PCellF& 
 #pragma unroll
           for (int mt = 0; mt < MT; ++mt) {
             const float4 ah = frag_vals(gh[mt][i]);
-            MFMA4G(acc[mt], ah, wl[i])
+            fwd_gate_products<XS>(acc[mt], ah, wl[i], nullptr);
           }
       }
     }
     __builtin_amdgcn_sched_barrier(0);
-    // ---- off-path traffic: issued BEHIND the recurrent MFMAs (they run in the matrix pipe meanwhile; in front of them these loads, stores and their
+    // ================= F6: off-path traffic -- x_{t+2}, zx / mask of step t+1, the saved gates / cell state of step t-1 =================
+    // issued BEHIND the recurrent MFMAs (they run in the matrix pipe meanwhile; in front of them these loads, stores and their
     // address arithmetic were 0.18 us of the chain)
     if (HAS_UP) {
 #pragma unroll
@@ -555,7 +565,7 @@ __device__ __forceinline__ void lstm_fwd_steps(const PFwdArgs& a, const PCellF& 
     if (!FIRST) store_saved(t - 1);
     __builtin_amdgcn_sched_barrier(0);
     TICK(3, t0)
-    // ---- 4-wave K reduction through LDS (double-buffered: one barrier per step)
+    // ================= F7: 4-wave K reduction through LDS (double-buffered: one barrier per step), gates, hand-off stores of h_t =========
     float* rd = (t & 1) ? red1 : red0;
 #pragma unroll
     for (int mt = 0; mt < MT; ++mt)
@@ -642,19 +652,44 @@ __global__ __launch_bounds__(256, 1) void lstm_persist_fwd_g(PFwdArgs a) {
 // 16-byte pieces, are read back with fully coalesced 4-byte loads.  Counter protocol (R1): partials are written through (sc1),
 // drained, one arrival per workgroup and step on counter A (own cell) and, after the second product, counter B (layer below).
 constexpr int PR_RING = 4;
-// Own-cell hand-off of lstm_persist_bwd_rs (the partial dh_rec tiles, on the recurrence's critical path).  1: the data is the flag, as in
+// Own-cell hand-off of lstm_persist_bwd_rs (the partial dh_rec tiles, on the recurrence's critical path).  true: the data is the flag, as in
 // the forward kernel -- the ring is sentinel-filled before the launch, a consumer polls its 16 KB of partial words themselves and puts the
 // sentinel back behind its read; a slot comes round again PR_RING steps later, and the consumer's per-step vmcnt(0) orders its reset in
-// front of everything its peers can have seen of it since.  No drain, barrier, counter or counter poll on the chain.  0: counter A.
+// front of everything its peers can have seen of it since.  No drain, barrier, counter or counter poll on the chain.  false: counter A.
 // Used up to h = 256 (KB <= 4): at h = 512 a consumer's slice is 32 KB per step and the counter form is the faster one (BASELINE
 // configs[4] shape: 22.0 against 22.5 ms per train step).
-#ifndef ASTK_BWD_SENTINEL
-#define ASTK_BWD_SENTINEL 1
-#endif
-#ifndef ASTK_BWD_SENTINEL_MAXKB
-#define ASTK_BWD_SENTINEL_MAXKB 4
-#endif
-constexpr bool bwd_sentinel(int KB) { return ASTK_BWD_SENTINEL && KB <= ASTK_BWD_SENTINEL_MAXKB; }
+constexpr bool bwd_sentinel(int KB) { return KB <= 4; }
+// One 16 x 16 output tile of a backward product (product 1: partial dh_rec, product 2: partial dx) against the step's 16 x 64 dz tile, under
+// arithmetic XS: `af` the tile as f32 fragments (XS = 0), `afh` its two split 32-k operands; `wh` / `w` the resident weight fragments of the
+// tile in the form XS keeps (the other one is not looked at); l0, l1 the weights' lo fragments read back from LDS (XS = 4); pscale =
+// 1 / (weight scale x dz scale) (XS = 2).  XS = 4: W holds hi / mid, the lo plane enters ONE of the six term products (smallest first).
+template <int XS>
+__device__ __forceinline__ void bwd_tile_product(f32x4& acc, const float4 (&af)[4], const typename FragOf<XS>::type (&afh)[2],
+                                                 const typename WFragOf<XS>::type (&wh)[2], const float4 (&w)[4], const u32q& l0, const u32q& l1,
+                                                 float pscale) {
+  if constexpr (XS == 4) {
+#pragma unroll
+    for (int p = 0; p < 2; ++p) {
+      const u32q lo = p == 0 ? l0 : l1;
+      MFMA_B16_(acc, afh[p].lo, wh[p].hi)
+      MFMA_B16_(acc, afh[p].hi, lo)
+      MFMA_B16_(acc, afh[p].mid, wh[p].mid)
+      MFMA_B16_(acc, afh[p].mid, wh[p].hi)
+      MFMA_B16_(acc, afh[p].hi, wh[p].mid)
+      MFMA_B16_(acc, afh[p].hi, wh[p].hi)
+    }
+  } else if constexpr (XS == 2) {
+    MFMA32H(acc, afh[0], wh[0])
+    MFMA32H(acc, afh[1], wh[1])
+    acc *= pscale;
+  } else if constexpr (XS == 3) {
+    MFMA32B(acc, afh[0], wh[0])
+    MFMA32B(acc, afh[1], wh[1])
+  } else {
+#pragma unroll
+    for (int s4 = 0; s4 < 4; ++s4) { MFMA4(acc, af[s4], w[s4]) }
+  }
+}
 // HAS_UP: the cell has a layer above it in this stack (a template parameter so that the loads of that layer's partials are unconditional
 // code: a conditionally issued load becomes a phi whose copy makes hipcc wait for the load where it is issued)
 // Row stride of the 16 x 64 dz tile in LDS: 68 floats, not 64.  Writers (unit u = tid >> 4, row r = tid & 15) and readers (row r16 = lane & 15,
@@ -689,6 +724,7 @@ __device__ __forceinline__ void lstm_bwd_rs_steps(const PBwdArgs& a, const PCell
   const int m0 = by * 16 * MT;
   (void)HH;
 
+  // ================= B0: resident weights -- this slice's rows of W_l (and of W_u for the layer below), loaded and split ONCE per launch =====
   // resident weight fragments: product tile tl = wave*KB + nt covers output units 16 tl .. 16 tl + 15; K = this slice's 64 gate columns
   // (read straight from the (4h, h) parameters: four 4-byte loads per fragment quad, 16 consecutive lanes on 64 consecutive bytes, once per
   //  launch -- the transposed copies a launch of its own used to make every step, 8 us, are gone)
@@ -721,18 +757,12 @@ __device__ __forceinline__ void lstm_bwd_rs_steps(const PBwdArgs& a, const PCell
     for (int nt = 0; nt < KB; ++nt)
 #pragma unroll
       for (int p = 0; p < 2; ++p) {
-        if constexpr (XS == 4) {
-          const HML8 t = split8b(wl_at(nt, 2 * p), wl_at(nt, 2 * p + 1));
-          wlh[nt][p].hi = t.hi; wlh[nt][p].mid = t.mid;
-          lo_l[(nt * 2 + p) * 256] = t.lo;
-          if constexpr (CAN_DOWN) {
-            const HML8 u = split8b(wd_at(nt, 2 * p), wd_at(nt, 2 * p + 1));
-            wdh[nt][p].hi = u.hi; wdh[nt][p].mid = u.mid;
-            lo_d[(nt * 2 + p) * 256] = u.lo;
-          }
-        } else {
-        wlh[nt][p] = split_frag<XS>(wl_at(nt, 2 * p), wl_at(nt, 2 * p + 1), wscl);
-        if constexpr (CAN_DOWN) wdh[nt][p] = split_frag<XS>(wd_at(nt, 2 * p), wd_at(nt, 2 * p + 1), wscl);
+        u32q lo;
+        wlh[nt][p] = resident_frag<XS>(wl_at(nt, 2 * p), wl_at(nt, 2 * p + 1), wscl, lo);
+        if constexpr (XS == 4) lo_l[(nt * 2 + p) * 256] = lo;
+        if constexpr (CAN_DOWN) {
+          wdh[nt][p] = resident_frag<XS>(wd_at(nt, 2 * p), wd_at(nt, 2 * p + 1), wscl, lo);
+          if constexpr (XS == 4) lo_d[(nt * 2 + p) * 256] = lo;
         }
       }
   } else {
@@ -741,6 +771,7 @@ __device__ __forceinline__ void lstm_bwd_rs_steps(const PBwdArgs& a, const PCell
 #pragma unroll
       for (int s4 = 0; s4 < 4; ++s4) { wl[nt][s4] = wl_at(nt, s4); if constexpr (CAN_DOWN) wd[nt][s4] = wd_at(nt, s4); }
   }
+  // ================= B1: set-up -- buffer resources, epilogue ownership, the first partials of the layer above, store_down, fetch_inputs =====
   const __amdgpu_buffer_rsrc_t r_pr = make_rsrc(c.PR);
   const __amdgpu_buffer_rsrc_t r_pd = make_rsrc(has_down ? c.PD : c.PR);
   const __amdgpu_buffer_rsrc_t r_pu = make_rsrc(has_up ? c.PD_up : c.PR);
@@ -773,10 +804,7 @@ __device__ __forceinline__ void lstm_bwd_rs_steps(const PBwdArgs& a, const PCell
   // In front of the barrier of step t one lane makes sure that the layer above has published step t-1 (asked when the step begins, the
   // answer is a memory round trip away; it blocks only while the pipeline fills), behind the barrier everybody fetches.
   constexpr bool SENT = bwd_sentinel(KB);
-#ifndef ASTK_BWD_UP_PREFETCH
-#define ASTK_BWD_UP_PREFETCH 1
-#endif
-  constexpr bool UP_PREFETCH = ASTK_BWD_UP_PREFETCH && SENT && HAS_UP && KB <= 4;      // (32 more live registers do not fit the h = 512 kernel)
+  constexpr bool UP_PREFETCH = SENT && HAS_UP && KB <= 4;      // (32 more live registers do not fit the h = 512 kernel)
   float pu[MT][NS];
   bool alive = true;
   if (UP_PREFETCH) {
@@ -807,9 +835,7 @@ __device__ __forceinline__ void lstm_bwd_rs_steps(const PBwdArgs& a, const PCell
 #pragma unroll
       for (int nt = 0; nt < (CAN_DOWN ? KB : 0); ++nt) {
         const int tl = wave * KB + nt;
-        u32q o;
-        o.x = __float_as_uint(acc2[mt][nt][0]); o.y = __float_as_uint(acc2[mt][nt][1]); o.z = __float_as_uint(acc2[mt][nt][2]); o.w = __float_as_uint(acc2[mt][nt][3]);
-        __builtin_amdgcn_raw_buffer_store_b128(o, r_pd, (int)((((long)ts * nbt + by * MT + mt) * NS + tl) * cons_stride) + j * tile_bytes + (r16 * 16 + 4 * q) * 4, 0, 16);
+        __builtin_amdgcn_raw_buffer_store_b128(as_u32q(acc2[mt][nt]), r_pd, (int)((((long)ts * nbt + by * MT + mt) * NS + tl) * cons_stride) + j * tile_bytes + (r16 * 16 + 4 * q) * 4, 0, 16);
       }
   };
 
@@ -852,8 +878,9 @@ __device__ __forceinline__ void lstm_bwd_rs_steps(const PBwdArgs& a, const PCell
       g[mt] = in_g[mt]; ccur[mt] = in_cc[mt]; cp[mt] = t > 0 ? in_cp[mt] : 0.f; mk[mt] = in_mk[mt]; dye[mt] = in_dye[mt];
       v1[mt] = 0.f; v0[mt] = 0.f;
     }
+    // ================= B2: partials handed down by the layer above -> v1 (fetched a step early, or waited for and loaded here) =================
     unsigned up_seen = 0;
-    if (has_up) {                            // partials handed down by the layer above (it runs ahead)
+    if (has_up) {                        // partials handed down by the layer above (it runs ahead)
       if (!UP_PREFETCH) {
         if (!c.up_external) {
           if (tid == 0) s_ok1[0] = wait_ge(upB, (unsigned)(NS * (stepno + 1)), ab) ? 1 : 0;
@@ -874,6 +901,7 @@ __device__ __forceinline__ void lstm_bwd_rs_steps(const PBwdArgs& a, const PCell
       if (UP_PREFETCH && !c.up_external && tid == 0) up_seen = ld_flag(upB);
     }
     TICK(0, t0)
+    // ================= B3: own-cell partial dh_rec of step t+1 -> v0: sentinel sweep of the ring slot, or counter A (h >= 512) ==========
     int reset_base[MT];
 #pragma unroll
     for (int mt = 0; mt < MT; ++mt) reset_base[mt] = -1;
@@ -900,13 +928,11 @@ __device__ __forceinline__ void lstm_bwd_rs_steps(const PBwdArgs& a, const PCell
         // slow path: poll ONE word per lane (its first missing one) until the wave has them all, then re-read everything; bounded
         unsigned spins = 0;
         while (!dead) {
-#if ASTK_FRAG_WAIT_SWEEP
-          if (spins < ASTK_FRAG_WAIT_SWEEP) {      // the first retries are whole sweeps (see frag_wait)
+          if (spins < FRAG_WAIT_SWEEPS) {      // the first retries are whole sweeps (see frag_wait)
             if (sweep()) break;
             ++spins;
             continue;
           }
-#endif
           int moff = base[0];
 #pragma unroll
           for (int mt = MT - 1; mt >= 0; --mt)
@@ -916,8 +942,7 @@ __device__ __forceinline__ void lstm_bwd_rs_steps(const PBwdArgs& a, const PCell
           if (__all(cw != SENTINEL)) {
             if (sweep()) break;
           }
-          if (++spins > (ab.limit >> 1)) { abort_raise(ab); dead = true; }
-          else if ((spins & 63u) == 0 && abort_seen(ab)) dead = true;
+          SPIN_TAIL(spins, dead, ab)
         }
       }
       TICK(1, t0)
@@ -943,14 +968,11 @@ __device__ __forceinline__ void lstm_bwd_rs_steps(const PBwdArgs& a, const PCell
       }
     }
     TICK(2, t0)
+    // ================= B4: gate epilogue -- dh, dc, dz of this thread's (row, unit); the dz tile into LDS =================
     // every vector memory operation of this wave up to the partial loads has completed (they were just consumed, vmcnt retires in
     // order; the previous step's down-partials and sentinel resets went out a whole step ago): this is the drain the deferred
     // publish of counter B needs, and what orders a reset in front of the slot's next use
-#ifdef ASTK_BWD_DRAIN_B
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-#else
     if constexpr (!SENT) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-#endif
     float4 dz[MT];
 #pragma unroll
     for (int mt = 0; mt < MT; ++mt) {
@@ -964,6 +986,7 @@ __device__ __forceinline__ void lstm_bwd_rs_steps(const PBwdArgs& a, const PCell
       dzmax = fmaxf(fmaxf(dzmax, fmaxf(fabsf(dz[mt].x), fabsf(dz[mt].y))), fmaxf(fabsf(dz[mt].z), fabsf(dz[mt].w)));   // (rows past B repeat row B-1)
     }
     TICK(3, t0)
+    // ================= B5: the step's barrier; the deferred arrivals (counter B, progress counter); the fetches for step t-1 =================
     if (UP_PREFETCH && !c.up_external && tid == 0) {
       const unsigned want = (unsigned)(NS * (stepno + 2));
       s_ok1[stepno & 1] = (t == 0 || up_seen >= want || wait_ge(upB, want, ab)) ? 1 : 0;
@@ -993,6 +1016,7 @@ __device__ __forceinline__ void lstm_bwd_rs_steps(const PBwdArgs& a, const PCell
       }
     }
     fetch_inputs(max(t - 1, 0));
+    // ================= B6: the dz tile as A fragments (split under XS); product 1 and its write-through stores =================
     float4 af[MT][4];
 #pragma unroll
     for (int mt = 0; mt < MT; ++mt)
@@ -1024,33 +1048,14 @@ __device__ __forceinline__ void lstm_bwd_rs_steps(const PBwdArgs& a, const PCell
         f32x4 acc[MT];
 #pragma unroll
         for (int mt = 0; mt < MT; ++mt) acc[mt] = f32x4{0.f, 0.f, 0.f, 0.f};
-        if constexpr (XS == 4) {
-          const u32q l0 = lo_l[(nt * 2) * 256], l1 = lo_l[(nt * 2 + 1) * 256];
+        u32q l0 = {0u, 0u, 0u, 0u}, l1 = {0u, 0u, 0u, 0u};
+        if constexpr (XS == 4) { l0 = lo_l[(nt * 2) * 256]; l1 = lo_l[(nt * 2 + 1) * 256]; }
 #pragma unroll
-          for (int mt = 0; mt < MT; ++mt) {
-            MFMA32B4(acc[mt], afh[mt][0], wlh[nt][0], l0)
-            MFMA32B4(acc[mt], afh[mt][1], wlh[nt][1], l1)
-          }
-        } else {
-#pragma unroll
-          for (int mt = 0; mt < MT; ++mt) {
-            if constexpr (XS == 2) {
-              MFMA32H(acc[mt], afh[mt][0], wlh[nt][0])
-              MFMA32H(acc[mt], afh[mt][1], wlh[nt][1])
-              acc[mt] *= pscale[mt];
-            } else if constexpr (XS == 3) {
-              MFMA32B(acc[mt], afh[mt][0], wlh[nt][0])
-              MFMA32B(acc[mt], afh[mt][1], wlh[nt][1])
-            } else {
-#pragma unroll
-              for (int s4 = 0; s4 < 4; ++s4) { MFMA4(acc[mt], af[mt][s4], wl[nt][s4]) }
-            }
-          }
-        }
+        for (int mt = 0; mt < MT; ++mt) bwd_tile_product<XS>(acc[mt], af[mt], afh[mt], wlh[X2 ? nt : 0], wl[X2 ? 0 : nt], l0, l1, pscale[mt]);
         const int tl = wave * KB + nt;
 #pragma unroll
         for (int mt = 0; mt < MT; ++mt) {
-          u32q o;
+          u32q o;       // (as_u32q written out: with the call, lstm_persist_bwd_rs<4, 2, 2> came out with two scalar registers swapped)
           o.x = __float_as_uint(acc[mt][0]); o.y = __float_as_uint(acc[mt][1]); o.z = __float_as_uint(acc[mt][2]); o.w = __float_as_uint(acc[mt][3]);
           __builtin_amdgcn_raw_buffer_store_b128(o, r_pr, (int)((((long)slot * nbt + by * MT + mt) * NS + tl) * cons_stride) + j * tile_bytes + (r16 * 16 + 4 * q) * 4, 0, 16);
         }
@@ -1062,6 +1067,7 @@ __device__ __forceinline__ void lstm_bwd_rs_steps(const PBwdArgs& a, const PCell
       const long long until = wall_clock64() + 3000;
       while (wall_clock64() < until) __builtin_amdgcn_s_sleep(8);
     }
+    // ================= B7: first half of product 2; sentinel back into the consumed slot (or publish of counter A) =================
     // ---- product 2 (partial dx for the layer below): its MFMAs run while the product-1 stores land; its own stores go out
     // behind the publish of counter A and counter B is bumped at the next step's drain point.  (Measured alternatives: product 2
     // behind the publish, with or without holding its stores back: 0.3-0.4 us per step slower -- the peers see counter A only
@@ -1069,30 +1075,12 @@ __device__ __forceinline__ void lstm_bwd_rs_steps(const PBwdArgs& a, const PCell
     constexpr int KB1 = (KB + 1) / 2;     // first half of product 2 hides the drain, second half runs behind the publish
     auto product2 = [&](const int nt) {
       if constexpr (CAN_DOWN) {
-        if constexpr (XS == 4) {
-          const u32q l0 = lo_d[(nt * 2) * 256], l1 = lo_d[(nt * 2 + 1) * 256];
+        u32q l0 = {0u, 0u, 0u, 0u}, l1 = {0u, 0u, 0u, 0u};
+        if constexpr (XS == 4) { l0 = lo_d[(nt * 2) * 256]; l1 = lo_d[(nt * 2 + 1) * 256]; }
 #pragma unroll
-          for (int mt = 0; mt < MT; ++mt) {
-            acc2[mt][nt] = f32x4{0.f, 0.f, 0.f, 0.f};
-            MFMA32B4(acc2[mt][nt], afh[mt][0], wdh[nt][0], l0)
-            MFMA32B4(acc2[mt][nt], afh[mt][1], wdh[nt][1], l1)
-          }
-        } else {
-#pragma unroll
-          for (int mt = 0; mt < MT; ++mt) {
-            acc2[mt][nt] = f32x4{0.f, 0.f, 0.f, 0.f};
-            if constexpr (XS == 2) {
-              MFMA32H(acc2[mt][nt], afh[mt][0], wdh[nt][0])
-              MFMA32H(acc2[mt][nt], afh[mt][1], wdh[nt][1])
-              acc2[mt][nt] *= pscale[mt];
-            } else if constexpr (XS == 3) {
-              MFMA32B(acc2[mt][nt], afh[mt][0], wdh[nt][0])
-              MFMA32B(acc2[mt][nt], afh[mt][1], wdh[nt][1])
-            } else {
-#pragma unroll
-              for (int s4 = 0; s4 < 4; ++s4) { MFMA4(acc2[mt][nt], af[mt][s4], wd[nt][s4]) }
-            }
-          }
+        for (int mt = 0; mt < MT; ++mt) {
+          acc2[mt][nt] = f32x4{0.f, 0.f, 0.f, 0.f};
+          bwd_tile_product<XS>(acc2[mt][nt], af[mt], afh[mt], wdh[X2 ? nt : 0], wd[X2 ? 0 : nt], l0, l1, pscale[mt]);
         }
       }
     };
@@ -1113,6 +1101,7 @@ __device__ __forceinline__ void lstm_bwd_rs_steps(const PBwdArgs& a, const PCell
       publish(ctrA, tid);      // drain (product-1 stores only), barrier, one arrival
     }
     TICK(5, t0)
+    // ================= B8: dz out, bias sums; second half of product 2 and the down-partial stores =================
     // dz for the batched products: behind the launch (plain stores), or -- layer 0 with side-stream consumers -- beside it, chunk by chunk:
     // written through (sc1), the chunk's arrival on the progress counter follows at the next step's drain point
 #pragma unroll
@@ -1120,9 +1109,7 @@ __device__ __forceinline__ void lstm_bwd_rs_steps(const PBwdArgs& a, const PCell
       if (evalid[mt]) {
         const long tb = (long)t * B + eb[mt];
         if (c.prog) {
-          u32q o;
-          o.x = __float_as_uint(dz[mt].x); o.y = __float_as_uint(dz[mt].y); o.z = __float_as_uint(dz[mt].z); o.w = __float_as_uint(dz[mt].w);
-          __builtin_amdgcn_raw_buffer_store_b128(o, r_dz, (int)((tb * K + 4 * eu) * 4), 0, 16);
+          __builtin_amdgcn_raw_buffer_store_b128(as_u32q(dz[mt]), r_dz, (int)((tb * K + 4 * eu) * 4), 0, 16);
         } else {
           *reinterpret_cast<float4*>(c.gates_dz + tb * K + 4 * eu) = dz[mt];
         }
@@ -1138,6 +1125,7 @@ __device__ __forceinline__ void lstm_bwd_rs_steps(const PBwdArgs& a, const PCell
     }
     TICK(6, t0)
   }
+  // ================= B9: behind the loop -- the last arrivals (counter B, progress counter), bias gradient, max |dz| =================
   if (pending_b) {
     // The LAST arrival on counter B (step 0's down partials) needs nothing from the peers, all earlier ones do: a workgroup reaches the
     // barrier of step s only behind its peers' partials of step s+1, i.e. behind their arrival for step s+2, so the 4 KB slices of a
@@ -1243,7 +1231,8 @@ __global__ __launch_bounds__(256, 1) void lstm_persist_bwd_rs(PBwdArgs a) {
 // run as consecutive launches over groups of layers (all directions of `lpl` layers each): the wavefront overlap between the
 // groups is lost, everything else stays (BASELINE configs[4]: 6 layers x 2 directions x 32 unit slices x 2 batch tiles = 768
 // workgroups -> 3 launches of 2 layers; batch 64 at the shipped width: 2 launches).  0 = not applicable.
-// Form of the recurrence workgroups (the `rows` argument of everything below): 16 = one 16-row batch tile per 256-thread workgroup;
+// Form of the recurrence workgroups (the `rows` argument of everything below; LSTM_ROWS_16 / _DUO / _MT2 of lstm_persist.h, like the
+// arithmetic's LSTM_XS_*): 16 = one 16-row batch tile per 256-thread workgroup;
 // 33 = DUO: two 16-row tiles per 512-thread workgroup as two virtual workgroups, two waves per SIMD (bf16x3 arithmetic, h <= 256);
 // 32 = MT 2: two tiles per 256-thread workgroup against one set of weight fragments (any arithmetic, h <= 256).  Both 32-row forms halve
 // the grid -- batch 64 at the shipped width runs as ONE launch, a batch of 32 leaves 160 CUs free for side-stream work instead of 64.
@@ -1257,20 +1246,24 @@ __global__ __launch_bounds__(256, 1) void lstm_persist_bwd_rs(PBwdArgs a) {
 static int recurrence_xs(int h) {
   const int mode = gemm_precision_mode();
   const bool x3_off = !tune_on(TUNE_LSTM_X3), x4_off = !tune_on(TUNE_LSTM_X4);
-  return mode == 0 ? 2 : (mode == 1 && !x3_off ? (h <= 256 ? 3 : (x4_off ? 0 : 4)) : 0);
+  return mode == 0 ? LSTM_XS_FP16X2 : (mode == 1 && !x3_off ? (h <= 256 ? LSTM_XS_BF16X3 : (x4_off ? LSTM_XS_F32 : LSTM_XS_BF16X3_LDS)) : LSTM_XS_F32);
 }
-static bool duo_available(int h) { return recurrence_xs(h) == 3 && tune_on(TUNE_LSTM_X4); }
-int lstm_persist_wg_rows(int B, int rows) { return rows == 16 ? (B + 15) / 16 : rows == 33 ? 2 * ((B + 31) / 32) : (B + 31) / 32; }
+// the DUO form runs where the arithmetic is bf16x3 with the weights in registers (h <= 256) and the lo plane may live in LDS
+static bool duo_available(int xs) { return xs == LSTM_XS_BF16X3 && tune_on(TUNE_LSTM_X4); }
+int lstm_persist_wg_rows(int B, int rows) {
+  return rows == LSTM_ROWS_16 ? (B + 15) / 16 : rows == LSTM_ROWS_DUO ? 2 * ((B + 31) / 32) : (B + 31) / 32;
+}
 int lstm_persist_rows(int B, int h, int nl, int nd, bool side) {
   const int knob = (int)tune(TUNE_LSTM_ROWS32);
-  if (knob == 0 || h > 256 || B <= 16) return 16;
-  if (knob == 1) return 32;
-  if (knob >= 2) return duo_available(h) ? 33 : 16;
+  if (knob == 0 || h > 256 || B <= 16) return LSTM_ROWS_16;
+  if (knob == 1) return LSTM_ROWS_MT2;
+  const bool duo = duo_available(recurrence_xs(h));
+  if (knob >= 2) return duo ? LSTM_ROWS_DUO : LSTM_ROWS_16;
   const long cus = device_cu_count();
-  const long wg16 = (long)(h / 16) * lstm_persist_wg_rows(B, 16) * nd * nl, wg32 = (long)(h / 16) * lstm_persist_wg_rows(B, 32) * nd * nl;
+  const long wg16 = (long)(h / 16) * lstm_persist_wg_rows(B, LSTM_ROWS_16) * nd * nl, wg32 = (long)(h / 16) * lstm_persist_wg_rows(B, LSTM_ROWS_MT2) * nd * nl;
   const long launches16 = (wg16 + cus - 1) / cus, launches32 = (wg32 + cus - 1) / cus;
-  if (launches32 < launches16) return duo_available(h) ? 33 : 32;
-  return side && duo_available(h) && tune_on(TUNE_LSTM_DUO_SIDE) ? 33 : 16;
+  if (launches32 < launches16) return duo ? LSTM_ROWS_DUO : LSTM_ROWS_MT2;
+  return side && duo && tune_on(TUNE_LSTM_DUO_SIDE) ? LSTM_ROWS_DUO : LSTM_ROWS_16;
 }
 int lstm_persist_layers_per_launch(int B, int h, int nl, int nd, int rows) {
   const long per_layer = lstm_persist_grid_wgs(B, h, 1, nd, rows);
@@ -1284,7 +1277,7 @@ int lstm_persist_layers_per_launch(int B, int h, int nl, int nd, int rows) {
 }
 
 // workgroups of one launch over `layers` layers of all directions
-int lstm_persist_grid_wgs(int B, int h, int layers, int nd, int rows) { return (h / 16) * lstm_persist_wg_rows(B, rows == 16 ? 16 : 32) * nd * layers; }
+int lstm_persist_grid_wgs(int B, int h, int layers, int nd, int rows) { return (h / 16) * lstm_persist_wg_rows(B, rows == LSTM_ROWS_16 ? LSTM_ROWS_16 : LSTM_ROWS_MT2) * nd * layers; }
 
 // Hoisted form (h = 1024): the weight fragments of one product fill a workgroup's registers, so every layer runs as a launch of its
 // own over cells that get their input projection from a batched GEMM in front of it (forward) and leave the gradient for the layer below
@@ -1299,7 +1292,7 @@ bool lstm_persist_applicable(int T, int B, int h, int nl, int nd) {
   }
   if (lstm_persist_layers_per_launch(B, h, nl, nd, lstm_persist_rows(B, h, nl, nd, false)) < 1) return false;
   // hand-off buffers are addressed with 32-bit byte offsets
-  if ((long)T * B * h * 16 >= (1L << 31) || (long)T * lstm_persist_wg_rows(B, 33) * (h / 16) * (h / 16) * 1024 >= (1L << 31)) return false;
+  if ((long)T * B * h * 16 >= (1L << 31) || (long)T * lstm_persist_wg_rows(B, LSTM_ROWS_DUO) * (h / 16) * (h / 16) * 1024 >= (1L << 31)) return false;
   if (!tune_on(TUNE_LSTM_PERSIST)) return false;
   return true;
 }
@@ -1319,23 +1312,24 @@ struct BwdKernels {
 };
 // h <= 256: fp16x2, bf16x3 or f32, one or two batch tiles per workgroup; h >= 512: fp16x2, bf16x3 with the lo plane in LDS or f32, one tile
 template <class K, int KB> static void (*narrow_kernel(int xs, int rows))(typename K::Args) {
-  if (rows == 32) return xs == 2 ? K::template g<KB, 2, 2>() : xs == 3 ? K::template g<KB, 3, 2>() : K::template g<KB, 0, 2>();
-  return xs == 2 ? K::template g<KB, 2, 1>() : xs == 3 ? K::template g<KB, 3, 1>() : K::template g<KB, 0, 1>();
+  if (rows == LSTM_ROWS_MT2)
+    return xs == LSTM_XS_FP16X2 ? K::template g<KB, LSTM_XS_FP16X2, 2>() : xs == LSTM_XS_BF16X3 ? K::template g<KB, LSTM_XS_BF16X3, 2>() : K::template g<KB, LSTM_XS_F32, 2>();
+  return xs == LSTM_XS_FP16X2 ? K::template g<KB, LSTM_XS_FP16X2, 1>() : xs == LSTM_XS_BF16X3 ? K::template g<KB, LSTM_XS_BF16X3, 1>() : K::template g<KB, LSTM_XS_F32, 1>();
 }
 template <class K, int KB> static void (*wide_kernel(int xs))(typename K::Args) {
-  return xs == 2 ? K::template g<KB, 2, 1>() : xs == 4 ? K::template g<KB, 4, 1>() : K::template g<KB, 0, 1>();
+  return xs == LSTM_XS_FP16X2 ? K::template g<KB, LSTM_XS_FP16X2, 1>() : xs == LSTM_XS_BF16X3_LDS ? K::template g<KB, LSTM_XS_BF16X3_LDS, 1>() : K::template g<KB, LSTM_XS_F32, 1>();
 }
 template <class K> static int launch_recurrence(const typename K::Args& a, int h, int rows, dim3 grid, hipStream_t s) {
   const int xs = recurrence_xs(h);
   void (*k)(typename K::Args);
-  if (rows == 33) {
-    ASTK_CHECK(xs == 3 && tune_on(TUNE_LSTM_X4), "%s: the two-waves-per-SIMD form needs the bf16x3 arithmetic", K::name);
+  if (rows == LSTM_ROWS_DUO) {
+    ASTK_CHECK(duo_available(xs), "%s: the two-waves-per-SIMD form needs the bf16x3 arithmetic", K::name);
     k = h == 64 ? K::template duo<1>() : h == 128 ? K::template duo<2>() : K::template duo<4>();
   } else {
     k = h == 64 ? narrow_kernel<K, 1>(xs, rows) : h == 128 ? narrow_kernel<K, 2>(xs, rows) : h == 256 ? narrow_kernel<K, 4>(xs, rows)
         : h == 512 ? wide_kernel<K, 8>(xs) : wide_kernel<K, 16>(xs);
   }
-  hipLaunchKernelGGL(k, grid, dim3(rows == 33 ? 512 : 256), 0, s, a);
+  hipLaunchKernelGGL(k, grid, dim3(rows == LSTM_ROWS_DUO ? 512 : 256), 0, s, a);
   ASTK_LAUNCH_CHECK();
   return 0;
 }
@@ -1344,9 +1338,9 @@ int lstm_persist_fwd_launch(const PersistCellHost* cells, int ncells, int nl, in
                             hipStream_t s) {
   PFwdArgs a;
   memset(&a, 0, sizeof(a));
-  ASTK_CHECK(rows == 16 || ((rows == 32 || rows == 33) && h <= 256), "lstm_persist_fwd: form %d at h = %d", rows, h);
+  ASTK_CHECK(rows == LSTM_ROWS_16 || ((rows == LSTM_ROWS_MT2 || rows == LSTM_ROWS_DUO) && h <= 256), "lstm_persist_fwd: form %d at h = %d", rows, h);
   const int nbt = lstm_persist_wg_rows(B, rows);      // (virtual) workgroup rows the counters are laid out for
-  const int nby = rows == 33 ? nbt / 2 : nbt;         // workgroup rows of the grid
+  const int nby = rows == LSTM_ROWS_DUO ? nbt / 2 : nbt;         // workgroup rows of the grid
   for (int i = 0; i < ncells; ++i) {
     const PersistCellHost& c = cells[i];
     PCellF& d = a.c[i];
@@ -1378,9 +1372,9 @@ int lstm_persist_bwd_launch(const PersistCellHost* cells, int ncells, int nl, in
                             unsigned amax_gen, int rows, hipStream_t s) {
   PBwdArgs a;
   memset(&a, 0, sizeof(a));
-  ASTK_CHECK(rows == 16 || ((rows == 32 || rows == 33) && h <= 256), "lstm_persist_bwd: form %d at h = %d", rows, h);
+  ASTK_CHECK(rows == LSTM_ROWS_16 || ((rows == LSTM_ROWS_MT2 || rows == LSTM_ROWS_DUO) && h <= 256), "lstm_persist_bwd: form %d at h = %d", rows, h);
   const int nbt = lstm_persist_wg_rows(B, rows);      // (virtual) workgroup rows: the counters are per (virtual) workgroup row
-  const int nby = rows == 33 ? nbt / 2 : nbt;         // workgroup rows of the grid
+  const int nby = rows == LSTM_ROWS_DUO ? nbt / 2 : nbt;         // workgroup rows of the grid
   for (int i = 0; i < ncells; ++i) {
     const PersistCellHost& c = cells[i];
     PCellB& d = a.c[i];
@@ -1420,7 +1414,7 @@ int lstm_persist_bwd_launch(const PersistCellHost* cells, int ncells, int nl, in
 
 // bytes of the reduce-scatter partial buffers of one cell (lstm.hip sizes the workspace with these)
 // (sized for an EVEN number of 16-row tiles: a 32-row workgroup addresses tiles 2 by and 2 by + 1 whether the second one has rows or not)
-size_t lstm_persist_pr_floats(int B, int h) { return (size_t)PR_RING * lstm_persist_wg_rows(B, 33) * (h / 16) * (h / 16) * 256; }
-size_t lstm_persist_pd_floats(int T, int B, int h) { return (size_t)T * lstm_persist_wg_rows(B, 33) * (h / 16) * (h / 16) * 256; }
+size_t lstm_persist_pr_floats(int B, int h) { return (size_t)PR_RING * lstm_persist_wg_rows(B, LSTM_ROWS_DUO) * (h / 16) * (h / 16) * 256; }
+size_t lstm_persist_pd_floats(int T, int B, int h) { return (size_t)T * lstm_persist_wg_rows(B, LSTM_ROWS_DUO) * (h / 16) * (h / 16) * 256; }
 
 }  // namespace astk
