@@ -121,6 +121,15 @@ class BeamState(_Sized, C.Structure):
                 ("n_frozen", C.c_void_p), ("hist", C.c_void_p), ("hist_alpha", C.c_void_p)]
 
 
+BEAM_CTC_MAX_T = 2048                  # astk.h ASTK_BEAM_CTC_MAX_T
+
+
+class BeamCtc(_Sized, C.Structure):
+    _fields_ = [("struct_size", C.c_size_t), ("weight", C.c_double), ("blank", C.c_int), ("first_label", C.c_int), ("logits", C.c_void_p),
+                ("ldv", C.c_long), ("state", C.c_void_p), ("att_score", C.c_void_p), ("psi", C.c_void_p), ("n_labels", C.c_void_p),
+                ("ws", C.c_void_p), ("ws_bytes", C.c_size_t)]
+
+
 CTC_MAX_LABELS = 255                   # astk.h ASTK_CTC_MAX_LABELS
 
 
@@ -242,6 +251,12 @@ SIGNATURES = {
     "astk_beam_step": (C.c_int, [C.POINTER(BeamDesc), C.POINTER(DecoderDesc), C.POINTER(DecoderParams), _VP, C.POINTER(BeamState), _I, _VP,
                                  _SZ, _VP]),
     "astk_beam_select": (C.c_int, [C.POINTER(BeamDesc), _I, _I, _I, _VP, _VP, _L, _VP, _VP, _VP, C.POINTER(BeamState), _I, _VP]),
+    "astk_beam_ctc_workspace_bytes": (_SZ, [C.POINTER(BeamDesc), C.POINTER(BeamCtc)]),
+    "astk_beam_ctc_init": (C.c_int, [C.POINTER(BeamDesc), C.POINTER(BeamState), C.POINTER(BeamCtc), _VP]),
+    "astk_beam_step_ctc": (C.c_int, [C.POINTER(BeamDesc), C.POINTER(DecoderDesc), C.POINTER(DecoderParams), _VP, C.POINTER(BeamState),
+                                     C.POINTER(BeamCtc), _I, _VP, _SZ, _VP]),
+    "astk_beam_select_ctc": (C.c_int, [C.POINTER(BeamDesc), _I, _I, _I, _VP, _VP, _L, _VP, _VP, _VP, C.POINTER(BeamState), C.POINTER(BeamCtc),
+                                       _I, _VP]),
     "astk_beam_decode_workspace_bytes": (_SZ, [C.POINTER(DecoderDesc), _I, _I, _I, _I]),
     "astk_beam_decode": (C.c_int, [C.POINTER(DecoderDesc), C.POINTER(DecoderParams), _VP, _VP, _VP, _VP, _I, _I, _I, _I, _I, _VP, _VP, _VP, _VP,
                                    _VP, _VP, _VP, _VP, _VP, _VP, _SZ, _VP]),
@@ -294,6 +309,7 @@ TEST_HOOK_SIGNATURES = {
     "astk_debug_rowgemm": (C.c_int, [C.POINTER(DebugRowGemmArgs), c_int_p, _VP]),
     "astk_debug_lstm_cell_fwd": (C.c_int, [C.POINTER(DebugCellFwdArgs), _I, c_int_p, _VP]),
     "astk_debug_lstm_cell_bwd": (C.c_int, [C.POINTER(DebugCellBwdArgs), _I, c_int_p, _VP]),
+    "astk_debug_ctc_prefix": (C.c_int, [C.POINTER(BeamDesc), C.POINTER(BeamState), C.POINTER(BeamCtc), _VP, _I, _VP, _VP, _VP]),
 }
 
 _lib = None

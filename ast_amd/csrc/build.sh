@@ -3,13 +3,13 @@
 #   ast_amd/libastk.so       the product library
 #   ast_amd/libastk_test.so  the same sources with -DASTK_TEST_HOOKS: adds the test instrumentation entry points (astk_conv_debug_*,
 #                            astk_debug_set_amax_generation, astk_debug_gemm_group, astk_debug_gemm_plan, and the row-panel launchers of rowgemm.hip:
-#                            astk_debug_rowgemm, astk_debug_lstm_cell_fwd / _bwd) that the product library does not export; loaded by
+#                            astk_debug_rowgemm, astk_debug_lstm_cell_fwd / _bwd, and the prefix scorer astk_debug_ctc_prefix) that the product library does not export; loaded by
 #                            tests only
 set -e
 cd "$(dirname "$0")"
 FLAGS="--offload-arch=gfx950 -O3 -std=c++17 -fPIC -Wno-unused-result $ASTK_EXTRA_FLAGS"
-SRCS="util gemm rowgemm attn conv norm lstm lstm_persist decoder decoder_persist decoder_wide beam ctc"
-HOOKED="gemm rowgemm conv lstm_persist decoder_persist"        # the translation units with #ifdef ASTK_TEST_HOOKS sections
+SRCS="util gemm rowgemm attn conv norm lstm lstm_persist decoder decoder_persist decoder_wide beam ctc ctc_prefix"
+HOOKED="gemm rowgemm conv lstm_persist decoder_persist ctc_prefix"        # the translation units with #ifdef ASTK_TEST_HOOKS sections
 mkdir -p ../_obj ../_obj/test
 pids=()
 # an object is stale when its source, ANY header here or the public header is newer: the headers hold the structs two translation units share

@@ -677,4 +677,22 @@ __device__ __forceinline__ float sample_gumbel(uint64_t row_key, int s, int n) {
   return -logf(-logf(sample_u01(word)));
 }
 
+// ---- CTC prefix scores of the joint beam search (ctc_prefix.hip; the step around them is beam.hip's)
+struct CtcPrefixWs {        // the carve of astk_beam_ctc.ws
+  double* lse;              // (U, T) per-frame float64 log-sum-exp over V
+  float* xt;                // (U, V, Tp) the logits with a candidate's column contiguous; Tp = T rounded up to 4
+  long Tp;
+  int32_t* cand_tok;        // (R, K) the proposals of the step
+  double* cand_lp;          // (R, K) their attention log-probabilities
+  double* cand_psi;         // (R, K)
+  double* cand_state;       // (R, K, T, 2)
+};
+size_t ctc_prefix_ws_carve(void* base, int U, int N, int K, int T, int V, CtcPrefixWs& w);
+int ctc_prefix_check(const astk_beam_desc* b, const astk_beam_ctc* c);
+int ctc_prefix_init_launch(const astk_beam_desc* b, const astk_beam_state* st, const astk_beam_ctc* c, hipStream_t s);
+// psi (R, K) and new_state (R, K, T, 2) of cand_tok (R, K) for every live row.  form 0: the shipped kernel; 1: the plain serial kernel
+// (test-hook build only); 2: the shipped kernel reading the emissions strided from the head's (U, T, ldv) logits instead of the copy
+int ctc_prefix_score_launch(const astk_beam_desc* b, const astk_beam_state* st, const astk_beam_ctc* c, const int32_t* cand_tok,
+                            double* psi, double* new_state, int form, hipStream_t s);
+
 }  // namespace astk

@@ -43,7 +43,43 @@ def decode_beam_step(model, decode_entry, beam_width):
                  "attn_history": decode_entry["attn_history"] + [alphas.squeeze().cpu().numpy()]} for pi in top[::-1]]
 
 
-def decode_beam(model, X, stop_limit, N, K):
+def checked_beam_ctc_weight(model, ctc_weight, only_batch=None):
+    """ctc_weight of a beam search as a float in [0, 1] (checked_ctc_weight's rules, and at most 1: the two terms' weights are
+    1 - w and w); a positive one needs the model's CTC head.  only_batch names the entry point that cannot rank jointly."""
+    w = checked_ctc_weight(ctc_weight, bool(getattr(model, "ctc_head", False)))
+    if w > 1.0:
+        raise ValueError(f"ctc_weight must be <= 1 in beam search (the terms weigh 1 - w and w), got {ctc_weight!r}")
+    if w > 0.0 and only_batch:
+        raise ValueError(f"{only_batch}: ctc_weight > 0 (joint CTC-attention ranking) runs in decode_beam_batch only")
+    return w
+
+
+# beam.py's joint decoding options live here, with the search they configure: the command line itself stays the reference's.
+def add_joint_decoding_arguments(parser):
+    parser.add_argument("--ctc-weight", dest="ctc_weight", type=float, default=0.0,
+                        help="joint CTC-attention decoding: weight of the CTC prefix score in the ranking, 0..1 (needs -b U and rnn_config.ctc)")
+
+
+def joint_decoding_kwargs(args, batched, device):
+    """The keyword arguments of decode_beam_batch for the parsed options (none: the plain search); SystemExit with a message where the
+    search that would run cannot rank jointly (no -b U, or --device)."""
+    from . import _lib
+    w = args["ctc_weight"]
+    if w == 0:
+        return {}
+    if not batched or device:
+        raise SystemExit("--ctc-weight: joint CTC-attention ranking runs in decode_beam_batch only: give -b U (N, K at most {0:d} / {1:d}) "
+                         "and drop --device".format(_lib.BEAM_MAX_N, _lib.BEAM_MAX_K))
+    return {"ctc_weight": w}
+
+
+def joint_entry_scores(entry):
+    """(att_score, ctc_score) of an n-best entry of a joint search, () of a plain one: what beam.py appends to its pickle's tuples."""
+    return (entry["att_score"], entry["ctc_score"]) if "ctc_score" in entry else ()
+
+
+def decode_beam(model, X, stop_limit, N, K, ctc_weight=0.0):
+    checked_beam_ctc_weight(model, ctc_weight, "decode_beam")
     with using_config("train", False):
         model.encode(X)
         n_best = [init_hyp(model)]
@@ -60,14 +96,19 @@ def decode_beam(model, X, stop_limit, N, K):
     return n_best
 
 
-def decode_beam_batch(model, Xs, stop_limit, N, K):
+def decode_beam_batch(model, Xs, stop_limit, N, K, ctc_weight=0.0):
     """decode_beam for many utterances at once: Xs is a list of (1, T_u, D) inputs; returns one N-best list per utterance, each the
     list decode_beam(model, Xs[u], stop_limit, N, K) returns (same hypotheses, order and types).  Every slot of every utterance is one
     row of a single decoder step (include/astk.h astk_beam_step: decoder step, float64 top-K / top-N selection and state gather on the
-    device); the host reads one counter per step, a step late, and backtracks the device's history once at the end."""
+    device); the host reads one counter per step, a step late, and backtracks the device's history once at the end.
+    ctc_weight = w > 0 (extension; needs rnn_config.ctc): joint CTC-attention decoding -- the K proposals of
+    every live hypothesis are ranked by (1 - w) * log p_att + w * log p_ctc(prefix) (astk_beam_step_ctc; the head runs once per search
+    on the padded encoder states); "score" is that joint score and every dict gains "att_score" and "ctc_score" (the CTC prefix
+    score, for a finished hypothesis log p_ctc of exactly its tokens).  0 is the search above: nothing else is allocated or launched."""
     import ctypes as C
     import numpy as np
     from . import _lib
+    ctc_weight = checked_beam_ctc_weight(model, ctc_weight)
     if not (1 <= N <= _lib.BEAM_MAX_N and 1 <= K <= _lib.BEAM_MAX_K):
         raise ValueError(f"decode_beam_batch: N = {N} and K = {K} must lie in 1..{_lib.BEAM_MAX_N} / 1..{_lib.BEAM_MAX_K} (use decode_beam)")
     lib = model._require_gpu()
@@ -112,13 +153,39 @@ def decode_beam_batch(model, Xs, stop_limit, N, K):
         ws = model._workspace("beam", nbytes)
         dp, stream = model._cur["dp"], torch.cuda.current_stream(dev)
         sp = C.c_void_p(stream.cuda_stream)
+        bc = None
+        if ctc_weight > 0:
+            # ---- the head once on the padded (U, Tmax, H) encoder states, then the per-frame lse, the (U, V, T) copy and the empty prefix
+            from .seq2seq import PAD_ID, UNK_ID
+            if Tmax > _lib.BEAM_CTC_MAX_T:
+                raise ValueError(f"decode_beam_batch: ctc_weight > 0 with T'' = {Tmax} above ASTK_BEAM_CTC_MAX_T = {_lib.BEAM_CTC_MAX_T}")
+            Vp = (V + 3) // 4 * 4
+            ctc_logits = torch.zeros(U * Tmax, Vp, **f32)
+            _lib.check(lib.astk_ctc_head_fwd(U * Tmax, V, H, C.c_void_p(enc.data_ptr()), model.arena.p("ctc_out/W"), model.arena.p("ctc_out/b"),
+                                             C.c_void_p(ctc_logits.data_ptr()), Vp, _lib.PREC_BY_NAME[model.gemm_precision], sp))
+            f64 = dict(dtype=torch.float64, device=dev)
+            ctc_state = torch.empty(R, Tmax, 2, **f64)
+            att_score, psi, n_labels = torch.zeros(R, **f64), torch.zeros(R, **f64), torch.zeros(R, **i32)
+            bc = _lib.BeamCtc(ctc_weight, PAD_ID, UNK_ID, ctc_logits.data_ptr(), Vp, ctc_state.data_ptr(), att_score.data_ptr(),
+                              psi.data_ptr(), n_labels.data_ptr(), None, 0)
+            cbytes = int(lib.astk_beam_ctc_workspace_bytes(C.byref(bd), C.byref(bc)))
+            if cbytes == 0:
+                _lib.check(-1)
+            cws = model._workspace("beam_ctc", cbytes)
+            bc.ws, bc.ws_bytes = cws.data_ptr(), cws.numel()
+            _lib.check(lib.astk_beam_ctc_init(C.byref(bd), C.byref(bs), C.byref(bc), sp))
+            model.last_beam_ctc = (ctc_logits.view(U, Tmax, Vp)[:, :, :V], lens)     # the head's logits and T''_u, for callers that re-score
         # ---- the loop: one astk_beam_step per step; the frozen-utterance count of step s is read after step s+1 is enqueued (steps on
         # frozen utterances only carry them again, so a step too many changes nothing)
         seen = torch.zeros(2, dtype=torch.int32, pin_memory=True)
         events, steps = [None, None], 0
         for step in range(stop_limit):
-            _lib.check(lib.astk_beam_step(C.byref(bd), C.byref(dd), C.byref(dp), C.c_void_p(enc.data_ptr()), C.byref(bs), step,
-                                          C.c_void_p(ws.data_ptr()), ws.numel(), sp))
+            if bc is None:
+                _lib.check(lib.astk_beam_step(C.byref(bd), C.byref(dd), C.byref(dp), C.c_void_p(enc.data_ptr()), C.byref(bs), step,
+                                              C.c_void_p(ws.data_ptr()), ws.numel(), sp))
+            else:
+                _lib.check(lib.astk_beam_step_ctc(C.byref(bd), C.byref(dd), C.byref(dp), C.c_void_p(enc.data_ptr()), C.byref(bs), C.byref(bc),
+                                                  step, C.c_void_p(ws.data_ptr()), ws.numel(), sp))
             steps = step + 1
             slot = step % 2
             seen[slot:slot + 1].copy_(n_frozen, non_blocking=True)
@@ -149,6 +216,11 @@ def decode_beam_batch(model, Xs, stop_limit, N, K):
                          "dec_state": {"c": [c[l, r:r + 1].clone() for l in range(nl)], "h": [h[l, r:r + 1].clone() for l in range(nl)]},
                          "attn_v": ht[r:r + 1].clone(), "attn_history": [alphas[k, :lens[u]].copy() for k in arow]}
                         for r, toks, arow in lst])
+        if bc is not None:
+            att, ps = att_score.cpu().numpy(), psi.cpu().numpy()
+            for lst, entries in zip(found, out):
+                for (r, _, _), e in zip(lst, entries):
+                    e["att_score"], e["ctc_score"] = float(att[r]), float(ps[r])
         return out
 
 
@@ -194,7 +266,7 @@ def plan_beam_tiles(n_utts, N, max_rows=32):
     return launches
 
 
-def decode_beam_device(model, Xs, stop_limit, N, K):
+def decode_beam_device(model, Xs, stop_limit, N, K, ctc_weight=0.0):
     """decode_beam_batch with the whole search of up to 32 rows in ONE persistent launch (include/astk.h astk_beam_decode): the same
     return value -- keys, types and order.  Utterances are packed into launches by plan_beam_tiles; every launch's results come back
     in one copy into one of two pinned buffers, read after the next launch has been enqueued.  Shapes the library does not run on
@@ -204,6 +276,7 @@ def decode_beam_device(model, Xs, stop_limit, N, K):
     import numpy as np
     from . import _lib
     from .seq2seq import _Pending, _vp
+    checked_beam_ctc_weight(model, ctc_weight, "decode_beam_device")
     if not (1 <= N <= _lib.BEAM_MAX_N and 1 <= K <= _lib.BEAM_MAX_K):
         raise ValueError(f"decode_beam_device: N = {N} and K = {K} must lie in 1..{_lib.BEAM_MAX_N} / 1..{_lib.BEAM_MAX_K} (use decode_beam)")
     lib = model._require_gpu()
@@ -653,14 +726,14 @@ class NN:
     def decode_beam_step(self, decode_entry, beam_width):
         return decode_beam_step(self.model, decode_entry, beam_width)
 
-    def decode_beam(self, X, stop_limit, N, K):
-        return decode_beam(self.model, X, stop_limit, N, K)
+    def decode_beam(self, X, stop_limit, N, K, ctc_weight=0.0):
+        return decode_beam(self.model, X, stop_limit, N, K, ctc_weight)
 
-    def decode_beam_batch(self, Xs, stop_limit, N, K):
-        return decode_beam_batch(self.model, Xs, stop_limit, N, K)
+    def decode_beam_batch(self, Xs, stop_limit, N, K, ctc_weight=0.0):
+        return decode_beam_batch(self.model, Xs, stop_limit, N, K, ctc_weight)
 
-    def decode_beam_device(self, Xs, stop_limit, N, K):
-        return decode_beam_device(self.model, Xs, stop_limit, N, K)
+    def decode_beam_device(self, Xs, stop_limit, N, K, ctc_weight=0.0):
+        return decode_beam_device(self.model, Xs, stop_limit, N, K, ctc_weight)
 
     def predict(self, set_key):
         preds = []

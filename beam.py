@@ -1,10 +1,13 @@
 """beam.py drop-in (beam.py:46-146 of the reference):
-    python beam.py -m <cfg_dir> -n <N hyps kept> -k <K candidates per step> -s <set key> -w <length weight> [--resume] [-b U] [--device] [--batch-encode]
+    python beam.py -m <cfg_dir> -n <N hyps kept> -k <K candidates per step> -s <set key> -w <length weight> [--resume] [-b U] [--device] [--batch-encode] [joint decoding options]
 Beam search over one set with the newest checkpoint of the experiment, n-best lists pickled to
 <cfg_dir>/<set>_beam_N-<N>_K-<K>.p, the length-normalised best hypothesis of each utterance scored with corpus BLEU
 (ast_amd.eval) and written to <cfg_dir>/<set>_beam_N-<N>_K-<K>_W-<W>.en.  -b U decodes U utterances per batched search on the
 GPU (ast_amd.nn.decode_beam_batch): the same utterances and hypotheses, the same files.  --device runs the whole search of a group
-of utterances (-b U of them, default 32) in persistent launches on the GPU (ast_amd.nn.decode_beam_device): the same files again."""
+of utterances (-b U of them, default 32) in persistent launches on the GPU (ast_amd.nn.decode_beam_device): the same files again.
+The joint decoding options are the library's (ast_amd.nn.add_joint_decoding_arguments; `python beam.py -h` lists them, DESIGN.md
+section 30): with -b U they rank every candidate by the attention decoder and the encoder's second head together; the pickled score
+is then that joint score and every entry carries the two separate scores behind its three fields."""
 import argparse
 import itertools
 import math
@@ -16,7 +19,7 @@ from tqdm import tqdm
 
 from ast_amd._lib import BEAM_MAX_K, BEAM_MAX_N
 from ast_amd.eval import Eval
-from ast_amd.nn import NN
+from ast_amd.nn import NN, add_joint_decoding_arguments, joint_decoding_kwargs, joint_entry_scores
 
 
 def rerank_hypothesis(beam_hyps, weight):
@@ -41,6 +44,7 @@ if __name__ == "__main__":
     parser.add_argument("--device", action="store_true", help="the whole search in persistent launches on the GPU (same hypotheses)")
     parser.add_argument("--batch-encode", dest="batch_encode", action="store_true",
                         help="encode the utterances of a call in one padded batch with per-row lengths instead of one by one (same encodings; effective with -b U / --device)")
+    add_joint_decoding_arguments(parser)
     args = vars(parser.parse_args())
     cfg_path, N, K, W, set_key = args["cfg_path"], int(args["N"]), int(args["K"]), float(args["W"]), args["S"]
     U = args["batch"]
@@ -49,6 +53,7 @@ if __name__ == "__main__":
     if U >= 1 and not (N <= BEAM_MAX_N and K <= BEAM_MAX_K):
         print("-b {0:d}: N and K above {1:d} / {2:d} are decoded one utterance at a time".format(U, BEAM_MAX_N, BEAM_MAX_K))
         U = 0
+    joint = joint_decoding_kwargs(args, batched=U >= 1, device=args["device"])          # (exits with a message where the search cannot rank jointly)
     nn = NN(cfg_path)
     nn.model.batch_encode = bool(args["batch_encode"])
     metrics = Eval(os.path.join(nn.cfg.train["data"]["refs_path"], set_key), nn.cfg.train["data"]["n_evals"])
@@ -74,9 +79,9 @@ if __name__ == "__main__":
                         group.append(utt)
                     if group and (utt is None or len(group) == U):
                         search = nn.decode_beam_device if args["device"] else nn.decode_beam_batch
-                        lists = search([g["X"] for g in group], stop_limit=stop_limit, N=N, K=K)
+                        lists = search([g["X"] for g in group], stop_limit=stop_limit, N=N, K=K, **joint)
                         for g, n_best in zip(group, lists):
-                            beam[g["utts"][0]] = [(e["hyp"], e["score"], e["attn_history"]) for e in n_best]
+                            beam[g["utts"][0]] = [(e["hyp"], e["score"], e["attn_history"]) + joint_entry_scores(e) for e in n_best]
                         pbar.update(len(group))
                         group = []
             else:

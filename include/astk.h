@@ -614,6 +614,54 @@ int astk_beam_step(const astk_beam_desc* b, const astk_decoder_desc* d, const as
  * states c_new / h_new (n_layers, R, H) and ht_new (R, A) every row computed. */
 int astk_beam_select(const astk_beam_desc* b, int n_layers, int H, int A, const float* logits, const float* alpha, long ld_alpha,
                      const float* c_new, const float* h_new, const float* ht_new, const astk_beam_state* st, int step, void* stream);
+/* ---------------------------------------------------------------- joint CTC-attention beam search
+ * astk_beam_step with every candidate ranked by (1 - w) * log p_att + w * log p_ctc(prefix): the CTC prefix score psi of Hori /
+ * Watanabe over the logits of the section-28 head, float64 in the log domain.  Not in the reference: a caller asks for it.
+ *   x[t][c]      float64 log_softmax of utterance u's float32 logits[u][t][0:V] (log-sum-exp in float64), t < T''_u; frames behind
+ *                T''_u are never read
+ *   a slot       holds a prefix g of n_labels tokens behind GO whose last one is astk_beam_state.tokens, att_score = its attention
+ *                log-probability, psi = psi(g), and its CTC state (T, 2): r_n[t], r_b[t] = the log-probability of all alignments of g
+ *                over frames 0..t that end in a non-blank / a blank.  Empty prefix: r_n = -inf, r_b[t] = sum_{s<=t} x[s][blank], psi = 0
+ *   g.c, c >= first_label, m = max(n, 1):   phi[t] = r_b[t] if c is g's last token, else logaddexp(r_n[t], r_b[t]);
+ *                r_n'[m-1] = x[0][c] if n = 0, else -inf;  r_b'[m-1] = -inf;  everything in front -inf;  for t >= m
+ *                r_n'[t] = logaddexp(r_n'[t-1], phi[t-1]) + x[t][c],  r_b'[t] = logaddexp(r_n'[t-1], r_b'[t-1]) + x[t][blank];
+ *                psi(g.c) = logsumexp(r_n'[m-1], {phi[t-1] + x[t][c] : m <= t < T''_u});  m > T''_u: psi = -inf, the state all -inf
+ *   c = eos      psi = logaddexp(r_n[T''_u - 1], r_b[T''_u - 1]) (the utterance is exactly g); state and n_labels stay the parent's
+ *   other c      (ids below first_label: the blank, GO) psi = -inf, the state all -inf
+ * A step: every live row proposes its K best tokens by float64 attention log_softmax exactly as astk_beam_step does; a proposal's
+ * ranking score is (1 - w) * (att_score_j + logp) + w * psi(g.c) from the two absolute terms, -inf where psi is -inf (NaN ranks as
+ * -inf); merge with the carried slots, stable top-N, history, frozen flags and the decoder-state gather are astk_beam_step's.  The
+ * gather also moves att_score, psi, n_labels and the CTC state (a new expansion takes its candidate's, a carried slot and an eos
+ * expansion keep the parent's own); astk_beam_state.score holds the ranking score.  Limits: T <= ASTK_BEAM_CTC_MAX_T, eos and the
+ * blank below first_label.  Every -inf case yields -inf, never NaN. */
+#define ASTK_BEAM_CTC_MAX_T 2048
+typedef struct {
+  size_t struct_size;    /* sizeof(astk_beam_ctc) */
+  double weight;         /* w in (0, 1] */
+  int blank;             /* the CTC blank (the model's PAD) */
+  int first_label;       /* ids >= first_label are labels (the model's UNK) */
+  const float* logits;   /* DEVICE (U, T, ldv): the head's logits of the padded encoder states (astk_ctc_head_fwd) */
+  long ldv;              /* >= V */
+  double* state;         /* DEVICE (R, T, 2) caller-owned: the slots' r_n, r_b */
+  double* att_score;     /* DEVICE (R) */
+  double* psi;           /* DEVICE (R) */
+  int32_t* n_labels;     /* DEVICE (R) */
+  void* ws;              /* DEVICE, astk_beam_ctc_workspace_bytes, 256-byte aligned; holds what astk_beam_ctc_init computed: keep it */
+  size_t ws_bytes;       /*         untouched between the init and the last step of a search */
+} astk_beam_ctc;
+/* 0 = bad arguments (astk_last_error).  Per-frame lse (U, T) float64, the logits as (U, V, T) so that a candidate's column is
+ * contiguous, the proposals (R, K) and their new CTC states (R, K, T, 2). */
+size_t astk_beam_ctc_workspace_bytes(const astk_beam_desc* b, const astk_beam_ctc* ctc);
+/* Once per search, three launches: lse and the (U, V, T) copy into ctc->ws, then the empty prefix's state in slot 0 of every utterance
+ * and att_score = psi = 0, n_labels = 0 in every slot. */
+int astk_beam_ctc_init(const astk_beam_desc* b, const astk_beam_state* st, const astk_beam_ctc* ctc, void* stream);
+/* astk_beam_step with the joint ranking: decoder step, proposals, prefix scores, selection and gather (ws: astk_beam_workspace_bytes). */
+int astk_beam_step_ctc(const astk_beam_desc* b, const astk_decoder_desc* d, const astk_decoder_params* p, const float* enc,
+                       const astk_beam_state* st, const astk_beam_ctc* ctc, int step, void* ws, size_t ws_bytes, void* stream);
+/* astk_beam_select's counterpart: proposals, prefix scores, selection and gather on a step's results supplied by the caller. */
+int astk_beam_select_ctc(const astk_beam_desc* b, int n_layers, int H, int A, const float* logits, const float* alpha, long ld_alpha,
+                         const float* c_new, const float* h_new, const float* ht_new, const astk_beam_state* st,
+                         const astk_beam_ctc* ctc, int step, void* stream);
 /* ---------------------------------------------------------------- beam search on the device  (the whole search in one launch)
  * The search of astk_beam_step for up to 32 rows in ONE persistent launch (the persistent decoder loop in its beam mode, after a fill
  * launch and the encA product, followed by one small launch that gathers the final states and, with alpha, one that normalises it).
@@ -956,6 +1004,12 @@ typedef struct {
 int astk_debug_rowgemm(const astk_debug_rowgemm_args* args, int* route, void* stream);
 int astk_debug_lstm_cell_fwd(const astk_debug_cell_fwd_args* cells, int ncells, int* route, void* stream);
 int astk_debug_lstm_cell_bwd(const astk_debug_cell_bwd_args* cells, int ncells, int* route, void* stream);
+/* The CTC prefix scorer alone (ctc_prefix.hip) behind an init: for every LIVE row r of st and k < K, psi[r][k] and new_state[r][k] (T, 2)
+ * of the candidate cand_tok[r][k] (DEVICE (R, K) int32) from the slots' states in ctc; rows that are not live are left untouched.
+ * form 0 = the shipped kernel (a wavefront per candidate), 1 = the plain one (a thread per candidate, serial over the frames), 2 = the
+ * shipped kernel with the emissions read strided from ctc->logits instead of from the init's (U, V, T) copy. */
+int astk_debug_ctc_prefix(const astk_beam_desc* b, const astk_beam_state* st, const astk_beam_ctc* ctc, const int32_t* cand_tok, int form,
+                          double* psi, double* new_state, void* stream);
 #endif
 
 /* Optional per-kernel HIP-event timing on the launch stream (bench.py's roofline legs; off by default).
