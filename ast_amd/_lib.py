@@ -285,6 +285,8 @@ SIGNATURES = {
     "astk_ctc_workspace_bytes": (_SZ, [C.POINTER(CtcDesc)]),
     "astk_ctc_loss": (C.c_int, [C.POINTER(CtcDesc), _VP, _VP, _VP, _F, _VP, _VP, _VP, _VP, _VP, _SZ, _VP]),
     "astk_ctc_greedy": (C.c_int, [C.POINTER(CtcDesc), _VP, _VP, _VP, _VP]),
+    "astk_ctc_align_workspace_bytes": (_SZ, [C.POINTER(CtcDesc)]),
+    "astk_ctc_align": (C.c_int, [C.POINTER(CtcDesc), _VP, _VP, _VP, _VP, _VP, _VP, _VP, _VP, _VP, _VP, _VP, _SZ, _VP]),
     "astk_ctc_head_fwd": (C.c_int, [_I, _I, _I, _VP, _VP, _VP, _VP, _L, _I, _VP]),
     "astk_ctc_head_bwd": (C.c_int, [_I, _I, _I, _VP, _L, _VP, _VP, _VP, _VP, _VP, _I, _I, _VP]),
     "astk_persist_status_snapshot": (C.c_int, [_VP, _VP]),

@@ -16,15 +16,13 @@
 //   k_ctc_finish  one thread: loss_acc += scale * nll of the feasible rows, in row order; the count of infeasible rows.
 // A dead state (alpha or beta = -inf) is the normal case at the sequence ends: the three-way log-add returns -inf for three -inf terms
 // instead of forming -inf - -inf.
-#include "common.h"
+#include "ctc_rows.h"
 #include <math.h>
 
 namespace astk {
 
 namespace {
 
-constexpr int CTC_ROW_THREADS = 512;
-constexpr int CTC_PF = 16;                                   // steps the emission gathers run ahead of the recursion (a memory latency is several steps long)
 constexpr int CTC_META = 4;                                  // ints per row: U, feasible, len, unused
 
 // the workspace, carved from the descriptor alone
@@ -54,8 +52,6 @@ static CtcWs ctc_carve(const astk_ctc_desc* d, void* base) {
   return w;
 }
 
-__device__ __forceinline__ int row_len(const int32_t* len, int b, int T) { return len ? min(max(len[b], 0), T) : T; }
-
 // log(exp(a) + exp(b) + exp(c)); -inf when all three are
 __device__ __forceinline__ float logadd3(float a, float b, float c) {
   const float m = fmaxf(a, fmaxf(b, c));
@@ -69,7 +65,7 @@ __global__ __launch_bounds__(256) void k_ctc_lse(int B, int T, int V, long ldv, 
   const int lane = threadIdx.x & 63;
   if (f >= (long)B * T) return;
   const int b = (int)(f / T), t = (int)(f - (long)b * T);
-  if (t >= row_len(len, b, T)) return;
+  if (t >= ctc_row_len(len, b, T)) return;
   const float* x = logits + f * ldv;
   float m = -INFINITY;
   for (int v = lane; v < V; v += 64) m = fmaxf(m, x[v]);
@@ -96,22 +92,12 @@ __global__ __launch_bounds__(CTC_ROW_THREADS) void k_ctc_rows(CtcRowArgs a, CtcW
   __shared__ int wcnt[CTC_ROW_THREADS / 64];
   __shared__ int s_rep;
   const int b = blockIdx.x, tid = threadIdx.x, nt = blockDim.x;
-  const int lane = tid & 63, wv = tid >> 6;
-  const int Tb = row_len(a.len, b, a.T);
+  const int lane = tid & 63;
+  const int Tb = ctc_row_len(a.len, b, a.T);
   const int Smax = w.Smax;
   // ---- the row's labels: entries of y[b] with id >= first_label, in order, to the odd states
-  int id = -1;
-  if (tid < a.L) id = a.y[(long)b * a.ldy + tid];
-  const bool keep = id >= a.first_label;
-  const unsigned long long km = __ballot(keep);
-  if (lane == 0) wcnt[wv] = __popcll(km);
   if (tid == 0) s_rep = 0;
-  ext[tid] = a.blank;
-  __syncthreads();
-  int before = 0, U = 0;
-  for (int i = 0; i < nt / 64; ++i) { before += i < wv ? wcnt[i] : 0; U += wcnt[i]; }
-  if (keep) ext[2 * (before + __popcll(km & ((1ull << lane) - 1ull))) + 1] = min(id, a.V - 1);
-  __syncthreads();
+  const int U = ctc_compact_labels(a.y + (long)b * a.ldy, a.L, a.first_label, a.V, a.blank, ext, wcnt);
   const int S = 2 * U + 1;
   const bool act = tid < S;
   const int cls = act ? ext[tid] : a.blank;
@@ -284,7 +270,7 @@ __global__ __launch_bounds__(256) void k_ctc_greedy(int B, int T, int V, long ld
   const int lane = threadIdx.x & 63;
   if (f >= (long)B * T) return;
   const int b = (int)(f / T), t = (int)(f - (long)b * T);
-  if (t >= row_len(len, b, T)) {
+  if (t >= ctc_row_len(len, b, T)) {
     if (lane == 0) best[f] = blank;
     return;
   }
@@ -304,6 +290,8 @@ __global__ __launch_bounds__(256) void k_ctc_greedy(int B, int T, int V, long ld
   if (lane == 0) best[f] = mi == 0x7fffffff ? blank : mi;
 }
 
+}  // namespace
+
 int ctc_check_desc(const astk_ctc_desc* d, const char* who) {
   ASTK_CHECK_DESC(d, astk_ctc_desc);
   ASTK_CHECK(d->B > 0 && d->T > 0, "%s: B and T must be positive, got B = %d, T = %d", who, d->B, d->T);
@@ -318,7 +306,12 @@ int ctc_check_desc(const astk_ctc_desc* d, const char* who) {
   return 0;
 }
 
-}  // namespace
+int ctc_lse_launch(const astk_ctc_desc* d, const float* logits, const int32_t* input_len, float* lse, hipStream_t s) {
+  const unsigned frames = (unsigned)((size_t)d->B * d->T);
+  hipLaunchKernelGGL(k_ctc_lse, dim3((frames + 3) / 4), dim3(256), 0, s, d->B, d->T, d->V, d->ldv, logits, input_len, lse);
+  ASTK_LAUNCH_CHECK();
+  return 0;
+}
 
 }  // namespace astk
 
@@ -339,8 +332,7 @@ int astk_ctc_loss(const astk_ctc_desc* d, const float* logits, const int32_t* y,
   ASTK_CHECK(ws_bytes >= w.bytes, "ctc_loss: workspace of %zu bytes, astk_ctc_workspace_bytes asks for %zu", ws_bytes, w.bytes);
   hipStream_t s = (hipStream_t)stream;
   const unsigned frames = (unsigned)((size_t)d->B * d->T);
-  hipLaunchKernelGGL(k_ctc_lse, dim3((frames + 3) / 4), dim3(256), 0, s, d->B, d->T, d->V, d->ldv, logits, input_len, w.lse);
-  ASTK_LAUNCH_CHECK();
+  ASTK_TRY(ctc_lse_launch(d, logits, input_len, w.lse, s));
   CtcRowArgs a;
   a.T = d->T; a.V = d->V; a.L = d->L; a.first_label = d->first_label; a.blank = d->blank;
   a.ldv = d->ldv; a.ldy = d->ldy;

@@ -265,6 +265,13 @@ class DataLoader:
                     out["x_len"] = x_len                      # (stays on the host: forward_loss maps it through the CNN's time formula)
                 yield out
 
+    def frame_counts(self, set_key, utts):
+        """Host int32 array of the utterances' true frame counts as get_batch loads them (cut at the longest bucket): what a training
+        batch carries as batch["x_len"], for callers that read evaluation batches."""
+        bk = self.buckets[set_key]
+        max_sp = (bk["num_b"] + 1) * bk["width_b"]
+        return np.asarray([min(int(self.info[set_key][u]["sp"]), max_sp) for u in utts], dtype=np.int32)
+
     def get_hyps(self, preds):
         dec_key = self.data_cfg["dec_key"]
         join = " " if dec_key.endswith("_w") else ""

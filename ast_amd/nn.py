@@ -800,3 +800,61 @@ class NN:
         n_tok = sum(n for _, _, n in scores)
         ppl = math.exp(-sum(lp for _, lp, _ in scores) / n_tok) if n_tok else float("nan")
         return scores, (sum(losses) / len(losses) if losses else 0.0), ppl
+
+    def ctc_align_set(self, set_key):
+        """Forced alignment of a set's references through the CTC head (SpeechEncoderDecoder.ctc_align), batch by
+        batch: {utt: the row's dict}.  The rows' true frame counts are batch["x_len"] where the loader's batches carry it, the loader's
+        own record of the utterances' lengths otherwise (evaluation batches have the keys they always had)."""
+        out = {}
+        for batch in self.data_loader.get_batch(self.cfg.train["batch_size"], set_key, train=False, labels=True):
+            x_len = batch.get("x_len")
+            if x_len is None:
+                x_len = self.data_loader.frame_counts(set_key, batch["utts"])
+            for u, row in zip(batch["utts"], self.model.ctc_align(batch["X"], batch["y"], x_lens=x_len)):
+                out[u] = row
+        return out
+
+
+# score.py's CTC alignment option lives here, with the alignment it writes: the command line itself stays the forced decoder's.
+ALIGNMENT_KEYS = ("segments", "segments_input", "labels", "confidence", "score", "total_logp")
+
+
+def add_alignment_arguments(parser):
+    parser.add_argument("--ctc-alignments", dest="ctc_alignments", metavar="OUT.npz",
+                        help="write the CTC head's forced alignments (Viterbi segments per token, confidences, best-path and full-sum "
+                             "scores) of the references, or with --nbest of every hypothesis, to this .npz (needs rnn_config.ctc)")
+
+
+def ctc_alignment_arrays(name, row):
+    """The .npz entries of one aligned row: name/segments (U, 2) encoder frames, name/segments_input (U, 2) input frames, name/labels
+    (U,), name/confidence (U,), name/score, name/total_logp."""
+    import numpy as np
+    return {"{0:s}/{1:s}".format(name, k): np.asarray(row[k]) for k in ALIGNMENT_KEYS}
+
+
+def write_alignment_file(nn, set_key, args, beam=None):
+    """score.py --ctc-alignments: nothing without the flag; the references of the set (NN.ctc_align_set), or with a beam.py pickle its
+    hypotheses, one utterance per call with X repeated over them and the hypotheses PAD-padded (key utt#rank)."""
+    import numpy as np
+    path = args.get("ctc_alignments")
+    if not path:
+        return None
+    arrays = {}
+    if beam is None:
+        for u, row in nn.ctc_align_set(set_key).items():
+            arrays.update(ctc_alignment_arrays(u, row))
+    else:
+        for utt in nn.data_loader.get_batch(1, set_key, train=False, labels=False):
+            u = utt["utts"][0]
+            if u not in beam:
+                continue
+            hyps = [[int(t) for t in h[0]] for h in beam[u]]
+            y = np.zeros((len(hyps), max(max(len(h) for h in hyps), 1)), np.int32)
+            for k, h in enumerate(hyps):
+                y[k, :len(h)] = h
+            rows = nn.model.ctc_align(utt["X"].expand(len(hyps), -1, -1), y)
+            for k, row in enumerate(rows):
+                arrays.update(ctc_alignment_arrays("{0:s}#{1:d}".format(u, k), row))
+    np.savez_compressed(path, **arrays)
+    print("CTC alignments written to: {0:s} ({1:d} rows)".format(path, len(arrays) // len(ALIGNMENT_KEYS)))
+    return path

@@ -429,6 +429,19 @@ def cnn_out_lens(cnn_layers, n):
     return out
 
 
+def input_span(cnn_layers, start, end, x_len):
+    """The input frames [lo, hi) behind the encoder frames [start, end): output step j of a layer with kernel kt, stride st and pad pt
+    reads its input steps j * st - pt .. j * st - pt + kt - 1, so through the layers from the last to the first
+        lo <- lo * st - pt   (from lo = start),      hi <- hi * st - pt + kt - 1   (from hi = end - 1),
+    and the span is [lo, hi + 1) clipped to [0, x_len]: the receptive start of the first frame and the receptive end of the last.  Both
+    ends are monotone in the frame, so ordered segments stay ordered; neighbours overlap by the receptive fields' overlap."""
+    lo, hi = int(start), int(end) - 1
+    for l in reversed(cnn_layers):
+        kt, st, pt = int(l["ksize"][0]), int(l["stride"][0]), int(l["pad"][0])
+        lo, hi = lo * st - pt, hi * st - pt + kt - 1
+    return min(max(lo, 0), int(x_len)), min(max(hi + 1, 0), int(x_len))
+
+
 def plan_encode_batches(lens, max_rows=ROWS_MAX):
     """Utterances -> encoder calls of at most max_rows rows: the indices ordered by length, longest first (ties in index order), cut
     into consecutive batches, so that a batch pads its rows to a length close to their own.  Host only."""
@@ -1192,6 +1205,76 @@ class SpeechEncoderDecoder:
             prev = np.concatenate(([-1], row[:-1]))
             out.append([int(c) for c in row[(row != prev) & (row != PAD_ID)]])
         return out
+
+    def ctc_align(self, X, y, x_lens=None):
+        """Forced alignment of the targets y (B, L) through the CTC head (eval mode): encode the batch, the head's
+        logits, the best monotonic path of every row's labels (ids >= UNK_ID of y[b], in order) over its valid frames
+        (astk_ctc_align), then astk_ctc_loss on the same logits for the full-sum score; ONE device-to-host copy brings everything back.
+        Returns one dict per row:
+          labels (U,), frame_state / frame_class (T'',) as astk.h defines them (-1 / the blank behind the row's n_frames),
+          segments (U, 2): the encoder frames [start, end) of every label,
+          segments_input (U, 2): the same in input frames (input_span), clipped to [0, x_len],
+          label_logp (U,), confidence (U,) = exp(label_logp / frames in the label), score = the best path's log-probability,
+          total_logp = log p_ctc(labels), the sum over all paths (score <= total_logp; the difference says how peaked the alignment is).
+        A row without a path (fewer frames than labels + adjacent repeats): score = total_logp = -inf, segments all -1."""
+        if not self.ctc_head:
+            raise ValueError("ctc_align needs the CTC head: set rnn_config.ctc = true in model_cfg.json")
+        lib = self._require_gpu()
+        X = self._as_input(X)
+        if x_lens is not None:
+            x_lens = checked_x_lens(x_lens, X.shape[0], X.shape[1])
+        if isinstance(y, np.ndarray):
+            y = torch.from_numpy(y)
+        y = y.to(self.device, torch.int32).contiguous()
+        if y.dim() != 2 or y.shape[0] != X.shape[0]:
+            raise ValueError(f"ctc_align: y must be (B = {X.shape[0]}, L), got {tuple(y.shape)}")
+        L = int(y.shape[1])
+        if L < 1:
+            raise ValueError("ctc_align: y holds no column")
+        if L > _lib.CTC_MAX_LABELS:
+            raise ValueError(f"ctc_align: targets of padded length {L} exceed ASTK_CTC_MAX_LABELS = {_lib.CTC_MAX_LABELS}")
+        with using_config("train", False):
+            self._cur = None
+            self.encode(X)
+        st, s = self._cur, self._stream()
+        lens = self._t2_lens(st, x_lens)
+        logits, Vp = self._ctc_logits(st, s)
+        B, T2 = st["B"], st["T2"]
+        cdesc = _lib.CtcDesc(B, T2, self.V, Vp, L, L, UNK_ID, PAD_ID)
+        need_a, need_l = int(lib.astk_ctc_align_workspace_bytes(C.byref(cdesc))), int(lib.astk_ctc_workspace_bytes(C.byref(cdesc)))
+        if not need_a or not need_l:
+            raise _lib.AstkError(lib.astk_last_error().decode())
+        ws = self._workspace("ctc", max(need_a, need_l))
+        # everything that goes back to the host, in one buffer of 4-byte words: frame_state, frame_class (B, T''); label_start,
+        # label_end, label_logp (B, L); row_score, row_nll (B)
+        cuts = np.cumsum([0, B * T2, B * T2, B * L, B * L, B * L, B, B])
+        out = self._pool("ctc_align_out", (int(cuts[-1]),), torch.int32)
+        p = [C.c_void_p(out.data_ptr() + 4 * int(c)) for c in cuts[:-1]]
+        check(lib.astk_ctc_align(C.byref(cdesc), _vp(logits), _vp(y), _vp(lens), p[0], p[1], p[2], p[3], p[4], p[5], None, _vp(ws),
+                                 ws.numel(), s))
+        # the full-sum score behind the alignment: astk_ctc_loss as it is, which leaves its gradient in place of the logits
+        check(lib.astk_ctc_loss(C.byref(cdesc), _vp(logits), _vp(y), _vp(lens), 1.0, p[6], None, _vp(logits), None, _vp(ws), ws.numel(), s))
+        host = out.cpu().numpy()
+        part = [host[a:b] for a, b in zip(cuts[:-1], cuts[1:])]
+        fs, fc = part[0].reshape(B, T2), part[1].reshape(B, T2)
+        l0, l1, lp = part[2].reshape(B, L), part[3].reshape(B, L), part[4].view(np.float32).reshape(B, L)
+        score, nll = part[5].view(np.float32), part[6].view(np.float32)
+        cc = self.cfg["cnn_config"]["cnn_layers"]
+        y_np = y.cpu().numpy()
+        rows = []
+        for b in range(B):
+            labels = np.minimum(y_np[b][y_np[b] >= UNK_ID], self.V - 1).astype(np.int32)
+            U = len(labels)
+            x_len = int(X.shape[1] if x_lens is None else x_lens[b])
+            seg = np.stack([l0[b, :U], l1[b, :U]], axis=1).astype(np.int32)
+            ok = bool(np.isfinite(score[b]))
+            seg_in = np.asarray([input_span(cc, a, e, x_len) for a, e in seg], np.int32).reshape(U, 2) if ok else np.full((U, 2), -1, np.int32)
+            with np.errstate(divide="ignore", invalid="ignore"):
+                conf = np.exp(lp[b, :U].astype(np.float64) / np.maximum(seg[:, 1] - seg[:, 0], 1)) if ok else np.zeros(U)
+            rows.append(dict(labels=labels, frame_state=fs[b].copy(), frame_class=fc[b].copy(), n_frames=int((fs[b] >= 0).sum()),
+                             segments=seg, segments_input=seg_in, label_logp=lp[b, :U].copy(), confidence=conf.astype(np.float32),
+                             score=float(score[b]), total_logp=float(-nll[b])))
+        return rows
 
     def _backward(self):
         lib = _lib.load()

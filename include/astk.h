@@ -886,6 +886,32 @@ int astk_ctc_head_fwd(int rows, int V, int H, const float* enc, const float* W, 
                       void* stream);
 int astk_ctc_head_bwd(int rows, int V, int H, const float* dlogits, long ldv, const float* W, const float* enc, float* d_enc, float* dW,
                       float* db, int precision, int deterministic, void* stream);
+/* ---------------------------------------------------------------- CTC forced alignment
+ * The best monotonic path (Viterbi) of a row's labels through its frames, over the logits of the section-28 head.  Rows, labels, the
+ * extended sequence z (S' = 2U + 1 states, blanks at the even positions), input_len (clamped to [0, T], NULL = T; n below) and L are
+ * astk_ctc_loss's, through the same descriptor.  Float32:
+ *   e[t][s]        = logits[t][z_s] - lse[t], lse the per-frame log-sum-exp with the maximum subtracted
+ *   delta[0][0]    = e[0][0], delta[0][1] = e[0][1], the rest -inf
+ *   delta[t][s]    = e[t][s] + max(delta[t-1][s], delta[t-1][s-1], [skip] delta[t-1][s-2]);  [skip]: z_s is a label and z_s != z_{s-2}
+ *   tie rule       a predecessor replaces the current choice only if it is STRICTLY greater, tried in the order stay (s), s - 1, s - 2;
+ *                  the final state is S' - 1 (the trailing blank) unless delta[n-1][S'-2] is strictly greater;
+ *                  max(-inf, -inf) + e = -inf, never NaN
+ *   frame_state    int32 (B, T): the state s of frame t on the best path for t < n, -1 behind n
+ *   frame_class    int32 (B, T) or NULL: z_s of that state (the blank id on blank states), the blank behind n
+ *   label_start /  int32 (B, L) or NULL: the frames [start, end) the path spends in label u's state 2u + 1; -1 for u >= U
+ *   label_end
+ *   label_logp     float32 (B, L) or NULL: the sum of e[t][2u+1] over those frames, in frame order; 0 for u >= U
+ *   row_score      float32 (B): delta[n-1][final state], the best path's log-probability (0 for n = 0 and U = 0: the empty path)
+ *   a row without a path (n < U + the number of adjacent equal labels): row_score = -inf, frame_state all -1, frame_class all blank,
+ *                  spans -1, label_logp 0; such rows are counted in *n_infeasible (int32, or NULL)
+ * logits is only read.  No atomics behind any output: bit-identical from run to run.  Two launches (three with n_infeasible), no
+ * allocation, no synchronisation; ws of astk_ctc_align_workspace_bytes (16-byte aligned: the lse and 2 bits of back-pointer per frame and
+ * state, T * ceil((2L + 1) / 64) * 16 bytes per row).  Refused before any launch: what astk_ctc_loss refuses from the descriptor, a
+ * NULL logits / y / frame_state / row_score / ws, and a workspace below the query (which returns 0 for a refused descriptor). */
+size_t astk_ctc_align_workspace_bytes(const astk_ctc_desc* d);
+int astk_ctc_align(const astk_ctc_desc* d, const float* logits, const int32_t* y, const int32_t* input_len, int32_t* frame_state,
+                   int32_t* frame_class, int32_t* label_start, int32_t* label_end, float* label_logp, float* row_score,
+                   int32_t* n_infeasible, void* ws, size_t ws_bytes, void* stream);
 /* One wavefront that keeps `stream` busy for `usec` microseconds (<= 100 000) and then increments *flag (may be NULL).  For probing
  * whether two streams really execute concurrently: HIP multiplexes streams onto a few hardware queues (GPU_MAX_HW_QUEUES, 4 by
  * default), and two streams that share one are serialised whatever their events say (ast_amd/seq2seq.py:_cu_streams). */

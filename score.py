@@ -1,11 +1,14 @@
 """Forced decoding from the command line:
-    python score.py -m <cfg_dir> -s <set key> [--nbest <beam pickle> [-b U]] [--alignments <out.npz>]
+    python score.py -m <cfg_dir> -s <set key> [--nbest <beam pickle> [-b U]] [--alignments <out.npz>] [the option of ast_amd.nn.add_alignment_arguments]
 Scores the set's references with the newest checkpoint of the experiment (NN.score_set): log-probability and token count per utterance
 in <cfg_dir>/<set>_scores.txt, the teacher-forced dev loss and the perplexity on the terminal.  --nbest scores every hypothesis of a
 beam.py pickle instead -- each utterance on its own, its X repeated over its hypotheses' rows and the hypotheses PAD-padded, the
 encoding the search itself saw -- writes the model score beside the beam score to <pickle>.scores.txt and prints the largest
 difference; -b U packs the hypotheses of up to U utterances into one call (ast_amd.nn.score_hypotheses_packed: every row attends over
-its own utterance's length, so the scores are those of -b 1).  --alignments also saves the attention rows, one (steps, T'') array per utterance (or per hypothesis: key utt#rank)."""
+its own utterance's length, so the scores are those of -b 1).  --alignments also saves the attention rows, one (steps, T'') array per utterance (or per hypothesis: key utt#rank).
+The CTC head's forced alignments (ast_amd.nn.write_alignment_file: Viterbi segments per token in encoder and input frames, confidences, the
+best-path and the full-sum score; keys utt/segments, utt/segments_input, utt/labels, utt/confidence, utt/score, utt/total_logp, with
+--nbest utt#rank/...) go to a file of their own; without that flag nothing else happens."""
 import argparse
 import itertools
 import os
@@ -14,7 +17,7 @@ import pickle
 import numpy as np
 from tqdm import tqdm
 
-from ast_amd.nn import NN, score_hypotheses, score_hypotheses_packed
+from ast_amd.nn import NN, add_alignment_arguments, score_hypotheses, score_hypotheses_packed, write_alignment_file
 from ast_amd.seq2seq import using_config
 
 
@@ -83,6 +86,7 @@ if __name__ == "__main__":
     parser.add_argument("-b", "--batch", type=int, default=1, help="with --nbest: pack the hypotheses of U utterances into one call (default 1)")
     parser.add_argument("--batch-encode", dest="batch_encode", action="store_true",
                         help="encode the utterances of a call in one padded batch with per-row lengths instead of one by one (same encodings; effective with -b U)")
+    add_alignment_arguments(parser)
     args = vars(parser.parse_args())
     cfg_path, set_key = args["cfg_path"], args["S"]
     nn = NN(cfg_path)
@@ -111,3 +115,4 @@ if __name__ == "__main__":
     if args["alignments"]:
         np.savez_compressed(args["alignments"], **align)
         print("Alignments written to: {0:s}".format(args["alignments"]))
+    write_alignment_file(nn, set_key, args, beam if args["nbest"] else None)
