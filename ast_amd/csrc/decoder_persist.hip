@@ -1569,6 +1569,38 @@ __global__ __launch_bounds__(256) void k_alpha_normalise(const float* __restrict
 // Weight gradients, d_enc, dq and d_embed are batched products over all steps after the loop (decoder.hip).
 enum BPhase { PB1 = 0, PB2, PB5 /* + layer: 0..2 */, PB5_1, PB5_2, PB6, PB_N };
 
+// The forms of the d_x0 role (PDecBwdArgs::b6_split; the older two are kept behind the knobs dec.b6_split / dec.b6_fused for A/B runs):
+//   B6_WHOLE  one layer only: B6 items of 16 columns of all of d_x0, handing the carry to the B1 items
+//   B6_SPLIT  B6 covers only the ht columns, every item split into two K halves (the embedding columns are one batched GEMM after
+//             the launch)
+//   B6_FUSED  no B6 role and no d_pre hand-off: the B1 items (two K halves each) add dz_{s+1} Wu[:, ht cols] to their half of
+//             dlogits Wo and leave the two partial pre-activations in DXH; B2 forms d_pre = (p0 + p1) (1 - ht^2) while it loads its
+//             operand (two hand-offs less on the chain; the embedding columns as under B6_SPLIT)
+enum B6Form { B6_WHOLE = 0, B6_SPLIT = 1, B6_FUSED = 2 };
+
+// The backward role layout, stated once: workgroups per role and whether they fit the G of the grid.
+//   NL == 1: [0, n5) cell backward, then n6 of d_x0, then d_pre and d_cvh on the same max(n1, n2) workgroups; B6_FUSED: n1 half-items of
+//            the pre-activation, then n2 of d_cvh on workgroups of their own.
+//   NL > 1:  [l n5, (l + 1) n5) cell backward of layer l; d_pre and d_cvh on the last max(n1, n2) workgroups; the split d_x0 items on the
+//            last n6, never on a workgroup that also holds the 64 float4 of a below-top cell backward.  B6_FUSED: the half-items on the
+//            last n1 -- top-layer cell owners among them, never a lower layer's -- and d_cvh on the last n2, none of which owns a cell.
+struct PDecBwdRoles {
+  int n5, n6, n1, n2;       // cell backward (per layer), d_x0, d_pre (B6_FUSED: its half-items), d_cvh
+  bool fits;
+};
+inline PDecBwdRoles pdec_bwd_roles(int nbt, int H, int A, int XI, int n_layers, int form) {
+  PDecBwdRoles r;
+  r.n5 = nbt * (H / 16);
+  r.n6 = form == B6_FUSED ? 0 : (form == B6_SPLIT ? 2 * nbt * (A / 16) : nbt * (XI / 16));
+  r.n1 = (form == B6_FUSED ? 2 : 1) * nbt * (A / 16);
+  r.n2 = nbt * (2 * H / 32);
+  const int n12 = r.n1 > r.n2 ? r.n1 : r.n2, below = (n_layers - 1) * r.n5;
+  if (form == B6_FUSED) r.fits = n_layers == 1 ? r.n5 + r.n1 + r.n2 <= G : (below + r.n1 <= G && below + r.n5 + r.n2 <= G);
+  else if (n_layers == 1) r.fits = r.n5 + r.n6 + n12 <= G;
+  else r.fits = form == B6_SPLIT && below + r.n5 + n12 <= G && r.n6 <= G - below;
+  return r;
+}
+
 struct PDecBwdArgs {
   int B, S, L, T, Tp, H, E, A, V, Vp, XI, nbt, nsplit, chunk;
   int NL;
@@ -1580,13 +1612,8 @@ struct PDecBwdArgs {
   float *ALPHA;                            // raw scores in, normalised alpha out
   float *Gt[PDEC_MAX_LAYERS];              // gates -> dz
   float *DPRE, *DCVH, *DS, *DX0, *DHATT;   // DHATT [S][B][nsplit][H]
-  float* DXH;                              // b6_split: [2][S][B][A] K-halves of d_x0[:, E:] (the carry of the next step's B1)
-  int b6_split;                            // 1: B6 covers only the ht columns, every item split into two K halves (the embedding
-                                           //    columns are one batched GEMM after the launch)
-                                           // 2: no B6 role and no d_pre hand-off: the B1 items (two K halves each) add dz_{s+1} Wu[:, ht cols]
-                                           //    to their half of dlogits Wo and leave the two partial pre-activations in DXH; B2 forms
-                                           //    d_pre = (p0 + p1) (1 - ht^2) while it loads its operand (two hand-offs less on the chain; the
-                                           //    embedding columns as under 1)
+  float* DXH;                              // B6_SPLIT, B6_FUSED: [2][S][B][A] K-halves of d_x0[:, E:] (the carry of the next step's B1)
+  int b6_split;                            // a B6Form (an int here: the argument's offset is part of the machine code)
   float *d_c0;                             // [NL][B][H]
   unsigned* ctr;
   AbortCtl ab;
@@ -1614,6 +1641,19 @@ __device__ __forceinline__ void wmac_chunked(f32x4& acc, const float4* w, __amdg
   }
 }
 
+// Vector pieces of the backward kernel, all by value: a float4 taken by reference is not a function the optimiser leaves no trace of
+// (DESIGN.md section 29).  as_u32q: the operand of a 16-byte buffer store (as in lstm_persist.hip); dot4, fma4: the four-term dot product
+// and the four-lane multiply-add of the H = 512 attention phase (B3); dpre4: d_pre = (p0 + p1) (1 - ht^2) of the fused form's B2
+template <class V> __device__ __forceinline__ u32q as_u32q(const V v) { return __builtin_bit_cast(u32q, v); }
+__device__ __forceinline__ float dot4(const float4 a, const float4 b) { return a.x * b.x + a.y * b.y + a.z * b.z + a.w * b.w; }
+__device__ __forceinline__ float4 fma4(float4 acc, const float g, const float4 e) {
+  acc.x += g * e.x; acc.y += g * e.y; acc.z += g * e.z; acc.w += g * e.w;
+  return acc;
+}
+__device__ __forceinline__ float4 dpre4(const float4 p0, const float4 p1, const float4 y) {
+  return make_float4((p0.x + p1.x) * (1.f - y.x * y.x), (p0.y + p1.y) * (1.f - y.y * y.y), (p0.z + p1.z) * (1.f - y.z * y.z), (p0.w + p1.w) * (1.f - y.w * y.w));
+}
+
 template <int NC, int NL, bool XS>   // as in decoder_persist_fwd
 __global__ __launch_bounds__(256, 1) void decoder_persist_bwd(PDecBwdArgs a) {
   extern __shared__ __attribute__((aligned(16))) float lds[];
@@ -1626,11 +1666,11 @@ __global__ __launch_bounds__(256, 1) void decoder_persist_bwd(PDecBwdArgs a) {
   unsigned* ctr = a.ctr;
 #define CTR(ph, bt) (ctr + ((ph) * nbt + (bt)) * NSH * CTRS)
 #define ROWCTR(row) (ctr + ((long)NPHASE_SLOTS * NSH * nbt + 2 + (row)) * CTRS)
-  // ---------------- roles.  NL == 1: [0,n5) cell bwd, [n5, n5+n6) dx0, [n5+n6, n5+n6+n1) d_pre + d_cvh ; attention: all.
-  // NL > 1: [l n5, (l+1) n5) cell bwd of layer l ; d_pre + d_cvh on the last max(n1, n2) workgroups ; dx0 (split) on the last n6
+  // ---------------- roles: the layout of pdec_bwd_roles, which states the counts below and what the launcher checked before it chose the
+  // form (these lines must match it: n1 here is the count of whole d_pre items, n1f that function's n1); attention: all workgroups
   constexpr int TOP = NL - 1;
-  const bool fused6 = a.b6_split == 2;
-  const int n5 = nbt * (H / 16), n6 = fused6 ? 0 : (a.b6_split ? 2 * nbt * (A / 16) : nbt * (XI / 16)), n1 = nbt * (A / 16), n2 = nbt * (2 * H / 32);
+  const bool fused6 = a.b6_split == B6_FUSED;
+  const int n5 = nbt * (H / 16), n6 = fused6 ? 0 : (a.b6_split != B6_WHOLE ? 2 * nbt * (A / 16) : nbt * (XI / 16)), n1 = nbt * (A / 16), n2 = nbt * (2 * H / 32);
   const int n12 = n1 > n2 ? n1 : n2;
   const bool has5 = wg < NL * n5;
   const int b5_l = has5 ? wg / n5 : 0, b5_i = has5 ? wg % n5 : 0;
@@ -1638,10 +1678,10 @@ __global__ __launch_bounds__(256, 1) void decoder_persist_bwd(PDecBwdArgs a) {
   const int r6 = NL > 1 ? wg - (G - n6) : wg - n5;
   const bool has6 = r6 >= 0 && r6 < n6;
   // B6 item: 16 columns of d_x0 for one batch tile; split mode: ht columns only, item (r6 >> 1), K half (r6 & 1)
-  const int b6_half = a.b6_split ? (r6 & 1) : 0;
-  const int b6_item = a.b6_split ? (r6 >> 1) : r6;
-  const int b6_per_bt = a.b6_split ? A / 16 : XI / 16;
-  const int b6_bt = has6 ? b6_item / b6_per_bt : 0, b6_n0 = has6 ? (a.b6_split ? E : 0) + (b6_item % b6_per_bt) * 16 : 0;
+  const int b6_half = a.b6_split != B6_WHOLE ? (r6 & 1) : 0;
+  const int b6_item = a.b6_split != B6_WHOLE ? (r6 >> 1) : r6;
+  const int b6_per_bt = a.b6_split != B6_WHOLE ? A / 16 : XI / 16;
+  const int b6_bt = has6 ? b6_item / b6_per_bt : 0, b6_n0 = has6 ? (a.b6_split != B6_WHOLE ? E : 0) + (b6_item % b6_per_bt) * 16 : 0;
   const int b6_k0 = b6_half * (K4 / 2);
   // fused form: 2 n1 half-items of the pre-activation, on other workgroups than the d_cvh items
   const int n1f = fused6 ? 2 * n1 : n1;
@@ -1652,7 +1692,7 @@ __global__ __launch_bounds__(256, 1) void decoder_persist_bwd(PDecBwdArgs a) {
   constexpr int KV_HALF = 64 * (NB_B1 / 2);          // fused form: dlogits Wo split at this k (9 k-blocks per wave and half)
   const int b1_kv0 = b1_half * KV_HALF, b1_kvn = b1_half ? Vp - KV_HALF : min(Vp, KV_HALF);
   // (NL > 1: the pre-activation half-items on the last 2 n1 workgroups -- top-layer cell owners among them, never a lower layer's --
-  //  and the d_cvh items on the last n2, none of which owns a cell: decoder_persist_bwd_launch checked both)
+  //  and the d_cvh items on the last n2, none of which owns a cell: pdec_bwd_roles(.., B6_FUSED).fits says both)
   const int r2 = fused6 ? (NL > 1 ? wg - (G - n2) : wg - n5 - n1f) : r1;
   const bool has2 = r2 >= 0 && r2 < n2;
   const int b2_bt = has2 ? r2 / (2 * H / 32) : 0, b2_n0 = has2 ? (r2 % (2 * H / 32)) * 32 : 0;
@@ -1677,7 +1717,7 @@ __global__ __launch_bounds__(256, 1) void decoder_persist_bwd(PDecBwdArgs a) {
     }
   }
   if (has6 && (NL > 1 || !has5)) {
-    if (a.b6_split) wload<NB_B6 / 2>(wreg + OFF_B6, a.WuT[0] + b6_k0, K4, b6_n0 + r16, K4 / 2, lane, wave);
+    if (a.b6_split != B6_WHOLE) wload<NB_B6 / 2>(wreg + OFF_B6, a.WuT[0] + b6_k0, K4, b6_n0 + r16, K4 / 2, lane, wave);
     else wload<NB_B6>(wreg + OFF_B6, a.WuT[0], K4, b6_n0 + r16, K4, lane, wave);
   }
   if (fused6) {
@@ -1750,10 +1790,10 @@ __global__ __launch_bounds__(256, 1) void decoder_persist_bwd(PDecBwdArgs a) {
         float carry = 0.f;
         TB(0)
         if (n > 0) {
-          if (!wg_wait_sh(CTR(PB6, bt), a.b6_split ? 2 * (A / 16) : XI / 16, n, a.ab, &s_flag)) return;
+          if (!wg_wait_sh(CTR(PB6, bt), a.b6_split != B6_WHOLE ? 2 * (A / 16) : XI / 16, n, a.ab, &s_flag)) return;
           TB(1)
           if (row < B) {
-            if (a.b6_split) {
+            if (a.b6_split != B6_WHOLE) {
               const float c0 = ld_sc1(a.DXH + ((long)(s + 1) * B + row) * A + col);
               const float c1 = ld_sc1(a.DXH + ((long)(S + s + 1) * B + row) * A + col);
               carry = c0 + c1;
@@ -1787,8 +1827,7 @@ __global__ __launch_bounds__(256, 1) void decoder_persist_bwd(PDecBwdArgs a) {
         const int nb2 = 2 * H / 32, my = b2_n0 / 32;
 #pragma unroll
         for (int i = 0; i < NB_B2; ++i) {
-          av[i].x = (av[i].x + p1[i].x) * (1.f - yv[i].x * yv[i].x); av[i].y = (av[i].y + p1[i].y) * (1.f - yv[i].y * yv[i].y);
-          av[i].z = (av[i].z + p1[i].z) * (1.f - yv[i].z * yv[i].z); av[i].w = (av[i].w + p1[i].w) * (1.f - yv[i].w * yv[i].w);
+          av[i] = dpre4(av[i], p1[i], yv[i]);
           const int k = 16 * (wave + 4 * i) + 4 * (lane >> 4);
           if ((wave * NB_B2 + i) % nb2 == my && k < A && m0 + r16 < B) *reinterpret_cast<float4*>(a.DPRE + rowo * A + k) = av[i];
         }
@@ -1866,7 +1905,7 @@ __global__ __launch_bounds__(256, 1) void decoder_persist_bwd(PDecBwdArgs a) {
         if (tid < HH / 4) {
           const float4 d4 = ldb128_sc1(r_dcvh, ((long)s * B + b) * 2 * HH + 4 * tid);
           *reinterpret_cast<float4*>(dS + 4 * tid) = d4;
-          cdp = cv4.x * d4.x + cv4.y * d4.y + cv4.z * d4.z + cv4.w * d4.w;
+          cdp = dot4(cv4, d4);
         }
         cdp = wave_sum(cdp);
         if (lane == 0) wred[wave] = cdp;
@@ -1889,8 +1928,8 @@ __global__ __launch_bounds__(256, 1) void decoder_persist_bwd(PDecBwdArgs a) {
           float d1 = 0.f, d2 = 0.f;
 #pragma unroll
           for (int c = 0; c < NC; ++c) {
-            d1 += x1[c].x * dv[c].x + x1[c].y * dv[c].y + x1[c].z * dv[c].z + x1[c].w * dv[c].w;
-            d2 += x2[c].x * dv[c].x + x2[c].y * dv[c].y + x2[c].z * dv[c].z + x2[c].w * dv[c].w;
+            d1 += dot4(x1[c], dv[c]);
+            d2 += dot4(x2[c], dv[c]);
           }
 #pragma unroll
           for (int o = 8; o > 0; o >>= 1) { d1 += __shfl_xor(d1, o); d2 += __shfl_xor(d2, o); }
@@ -1918,8 +1957,8 @@ __global__ __launch_bounds__(256, 1) void decoder_persist_bwd(PDecBwdArgs a) {
             d1 = 0.f; d2 = 0.f;
 #pragma unroll
             for (int c = 0; c < NC; ++c) {
-              d1 += x1[c].x * dv[c].x + x1[c].y * dv[c].y + x1[c].z * dv[c].z + x1[c].w * dv[c].w;
-              d2 += x2[c].x * dv[c].x + x2[c].y * dv[c].y + x2[c].z * dv[c].z + x2[c].w * dv[c].w;
+              d1 += dot4(x1[c], dv[c]);
+              d2 += dot4(x2[c], dv[c]);
             }
 #pragma unroll
             for (int o = 8; o > 0; o >>= 1) { d1 += __shfl_xor(d1, o); d2 += __shfl_xor(d2, o); }
@@ -1952,9 +1991,7 @@ __global__ __launch_bounds__(256, 1) void decoder_persist_bwd(PDecBwdArgs a) {
           }
           float4 acc4 = make_float4(0.f, 0.f, 0.f, 0.f);
 #pragma unroll
-          for (int i = 0; i < RPT; ++i) {
-            acc4.x += gv[i] * ev[i].x; acc4.y += gv[i] * ev[i].y; acc4.z += gv[i] * ev[i].z; acc4.w += gv[i] * ev[i].w;
-          }
+          for (int i = 0; i < RPT; ++i) acc4 = fma4(acc4, gv[i], ev[i]);
           if (nx > 0) {
 #pragma unroll
             for (int i = 0; i < RPT; ++i) {
@@ -1963,9 +2000,7 @@ __global__ __launch_bounds__(256, 1) void decoder_persist_bwd(PDecBwdArgs a) {
               gv[i] = t < nx ? dsS[nres + t] : 0.f;
             }
 #pragma unroll
-            for (int i = 0; i < RPT; ++i) {
-              acc4.x += gv[i] * ev[i].x; acc4.y += gv[i] * ev[i].y; acc4.z += gv[i] * ev[i].z; acc4.w += gv[i] * ev[i].w;
-            }
+            for (int i = 0; i < RPT; ++i) acc4 = fma4(acc4, gv[i], ev[i]);
           }
           if (RH > 1) {
             if (rh > 0) fold[(rh - 1) * (16 * NC) + cq] = acc4;
@@ -1977,9 +2012,7 @@ __global__ __launch_bounds__(256, 1) void decoder_persist_bwd(PDecBwdArgs a) {
               const float4 o = fold[(k - 1) * (16 * NC) + cq];
               acc4.x += o.x; acc4.y += o.y; acc4.z += o.z; acc4.w += o.w;
             }
-            u32q u;
-            u.x = __float_as_uint(acc4.x); u.y = __float_as_uint(acc4.y); u.z = __float_as_uint(acc4.z); u.w = __float_as_uint(acc4.w);
-            __builtin_amdgcn_raw_buffer_store_b128(u, r_dha, (int)(((((long)s * B + b) * a.nsplit + att_sp) * HH + 4 * cq) * 4), 0, 16);
+            __builtin_amdgcn_raw_buffer_store_b128(as_u32q(acc4), r_dha, (int)(((((long)s * B + b) * a.nsplit + att_sp) * HH + 4 * cq) * 4), 0, 16);
           }
         }
       } else {
@@ -2104,10 +2137,8 @@ __global__ __launch_bounds__(256, 1) void decoder_persist_bwd(PDecBwdArgs a) {
         const float dh = v + dy * mk;
         const float tc = tanh_fast(ccur);
         const float dcv = dh * g.w * (1.f - tc * tc) + dc_state;
-        u32q o;
-        o.x = __float_as_uint(dcv * g.y * (1.f - g.x * g.x)); o.y = __float_as_uint(dcv * g.x * g.y * (1.f - g.y));
-        o.z = __float_as_uint(dcv * cp * g.z * (1.f - g.z)); o.w = __float_as_uint(dh * tc * g.w * (1.f - g.w));
-        __builtin_amdgcn_raw_buffer_store_b128(o, r_g, (int)((((long)s * B + row) * K4 + 4 * u) * 4), 0, 16);
+        const float4 dz = make_float4(dcv * g.y * (1.f - g.x * g.x), dcv * g.x * g.y * (1.f - g.y), dcv * cp * g.z * (1.f - g.z), dh * tc * g.w * (1.f - g.w));
+        __builtin_amdgcn_raw_buffer_store_b128(as_u32q(dz), r_g, (int)((((long)s * B + row) * K4 + 4 * u) * 4), 0, 16);
         dc_state = dcv * g.z;
       }
       publish_sh(CTR(PB5 + l, bt), b5_u0 / 16);
@@ -2120,15 +2151,15 @@ __global__ __launch_bounds__(256, 1) void decoder_persist_bwd(PDecBwdArgs a) {
       if (!wg_wait_sh(CTR(PB5, bt), H / 16, n + 1, a.ab, &s_flag)) return;
       TB(9)
       f32x4 acc = {0.f, 0.f, 0.f, 0.f};
-      if (a.b6_split) wmac_chunked<NB_B6 / 2, 16>(acc, wreg + OFF_B6, r_g0, ((long)s * B + min(m0 + r16, B - 1)) * K4 + b6_k0, K4 / 2, lane, wave);
+      if (a.b6_split != B6_WHOLE) wmac_chunked<NB_B6 / 2, 16>(acc, wreg + OFF_B6, r_g0, ((long)s * B + min(m0 + r16, B - 1)) * K4 + b6_k0, K4 / 2, lane, wave);
       else wmac_chunked<NB_B6, 16>(acc, wreg + OFF_B6, r_g0, ((long)s * B + min(m0 + r16, B - 1)) * K4, K4, lane, wave);
       const float v = reduce16(acc, red);
       const int row = m0 + e_row;
       if (row < B) {
-        if (a.b6_split) st_sc1(a.DXH + ((long)(b6_half * S + s) * B + row) * A + (b6_n0 - E) + e_col, v);
+        if (a.b6_split != B6_WHOLE) st_sc1(a.DXH + ((long)(b6_half * S + s) * B + row) * A + (b6_n0 - E) + e_col, v);
         else st_sc1(a.DX0 + ((long)s * B + row) * XI + b6_n0 + e_col, v);
       }
-      publish_sh(CTR(PB6, bt), a.b6_split ? 2 * (b6_item % b6_per_bt) + b6_half : b6_item % b6_per_bt);
+      publish_sh(CTR(PB6, bt), a.b6_split != B6_WHOLE ? 2 * (b6_item % b6_per_bt) + b6_half : b6_item % b6_per_bt);
       TB(10)
     }
   }
@@ -2279,16 +2310,10 @@ static bool pdec_applicable(const astk_decoder_desc* d, int max_L, int* nsplit_o
   {   // backward roles and register budgets
     const int XI = d->E + d->A, Vp = (d->V + 3) / 4 * 4;
     if (Vp > 64 * NB_B1 || d->A > 64 * NB_B2 || 4 * d->H > 64 * NB_B5 || (XI % 16) || ((2 * d->H) % 32)) return false;
-    if (nbt * (d->H / 16) + nbt * (XI / 16) + nbt * (d->A / 16) > G || nbt * (2 * d->H / 32) > nbt * (d->A / 16) + (G - nbt * (d->H / 16) - nbt * (XI / 16) - nbt * (d->A / 16))) return false;
+    // (the one-layer layout with whole d_x0 items is asked of every layer count, as it has been since the multi-layer layout came)
+    if (!pdec_bwd_roles(nbt, d->H, d->A, XI, 1, B6_WHOLE).fits) return false;
     if (pdec_bwd_lds_floats(chunk, d->H) * sizeof(float) > 148 * 1024) return false;
-    if (d->n_layers > 1) {
-      // per-layer cell-backward owners, d_pre/d_cvh owners at the end of the grid, the split d_x0 items on the last n6 workgroups
-      // (never on a workgroup that also holds the 64 float4 of a below-top cell backward)
-      const int n5 = nbt * (d->H / 16), n6 = 2 * nbt * (d->A / 16), n1 = nbt * (d->A / 16), n2 = nbt * (2 * d->H / 32);
-      const int n12 = n1 > n2 ? n1 : n2;
-      if ((4 * d->H) % 128) return false;
-      if (d->n_layers * n5 + n12 > G || n6 > G - (d->n_layers - 1) * n5) return false;
-    }
+    if (d->n_layers > 1 && (((4 * d->H) % 128) || !pdec_bwd_roles(nbt, d->H, d->A, XI, d->n_layers, B6_SPLIT).fits)) return false;
   }                       // pass-1 bookkeeping uses one thread per row
   if (pdec_lds_floats(chunk, d->H, nsplit) * sizeof(float) > 136 * 1024) return false;
   *nsplit_out = nsplit;
@@ -2299,12 +2324,10 @@ bool decoder_persist_applicable(const astk_decoder_desc* d, int* nsplit_out, int
 
 // d_x0 phase of the backward kernel as 2 K-halves per item over the ht columns only: fits when the roles still fit 256 workgroups
 bool decoder_persist_b6_split(const astk_decoder_desc* d) {
-  const int nbt = (d->B + 15) / 16;
-  const int n5 = nbt * (d->H / 16), n6 = 2 * nbt * (d->A / 16), n1 = nbt * (d->A / 16), n2 = nbt * (2 * d->H / 32);
   if ((4 * d->H) % 128) return false;
   if (d->n_layers > 1) return true;           // the multi-layer role layout always uses the split form (decoder_persist_applicable checked it)
   if (!tune_on(TUNE_DEC_B6_SPLIT)) return false;
-  return n5 + n6 + (n1 > n2 ? n1 : n2) <= G;
+  return pdec_bwd_roles((d->B + 15) / 16, d->H, d->A, d->E + d->A, 1, B6_SPLIT).fits;
 }
 
 // The one launcher of the persistent decoder kernels.  pick(nc, nl, xs) names the instantiation <NC, NL, XS> of one kernel template (its
@@ -2332,14 +2355,20 @@ static void pdec_launch(Pick pick, int n_layers, int lds_cap, int H, int chunk, 
   else pdec_launch_nl<3>(pick, lds_cap, H, chunk, shm, s, a);
 }
 
+// The fourteen shape fields that PDecArgs and PDecBwdArgs share, for a loop of S steps
+template <class Args>
+static void pdec_fill_shapes(Args& a, const astk_decoder_desc* d, int S, int nsplit, int chunk) {
+  a.B = d->B; a.S = S; a.L = S + 1; a.T = d->T; a.Tp = (d->T + 3) / 4 * 4; a.H = d->H; a.E = d->E; a.A = d->A; a.V = d->V;
+  a.Vp = (d->V + 3) / 4 * 4; a.XI = d->E + d->A; a.nbt = (d->B + 15) / 16; a.nsplit = nsplit; a.chunk = chunk;
+}
+
 int decoder_persist_bwd_launch(const astk_decoder_desc* d, const float* enc, const float* rnn_masks, const DecPersistBwdBuffers& bf,
                                hipStream_t s) {
   int nsplit = 1, chunk = 1;
   ASTK_CHECK(decoder_persist_applicable(d, &nsplit, &chunk), "decoder_persist_bwd: not applicable");
   PDecBwdArgs a;
   memset(&a, 0, sizeof(a));
-  a.B = d->B; a.S = d->L - 1; a.L = d->L; a.T = d->T; a.Tp = (d->T + 3) / 4 * 4; a.H = d->H; a.E = d->E; a.A = d->A; a.V = d->V;
-  a.Vp = (d->V + 3) / 4 * 4; a.XI = d->E + d->A; a.nbt = (d->B + 15) / 16; a.nsplit = nsplit; a.chunk = chunk;
+  pdec_fill_shapes(a, d, d->L - 1, nsplit, chunk);
   a.NL = d->n_layers;
   a.WoT = bf.WoT; a.WcT = bf.WcT; a.enc = enc; a.encA = bf.ENCA; a.ALPHA = bf.ALPHA; a.CVH = bf.CVH; a.ML = bf.ML;
   for (int l = 0; l < d->n_layers; ++l) {
@@ -2349,13 +2378,10 @@ int decoder_persist_bwd_launch(const astk_decoder_desc* d, const float* enc, con
   a.HT = bf.HT; a.LOGITS = bf.LOGITS; a.DPRE = bf.DPRE; a.DCVH = bf.DCVH; a.DS = bf.DS;
   a.DX0 = bf.DX0; a.DHATT = bf.DHATT; a.d_c0 = bf.d_c0;
   a.DXH = bf.DXH;
-  a.b6_split = bf.DXH != nullptr && decoder_persist_b6_split(d) ? 1 : 0;
-  if (a.b6_split) {          // astk_set_tuning("dec.b6_fused", 0): the d_x0 role of rounds 2-3 (kept for A/B runs)
-    const int n5 = a.nbt * (a.H / 16), n1 = a.nbt * (a.A / 16), n2 = a.nbt * (2 * a.H / 32);
-    const bool fits = d->n_layers == 1 ? n5 + 2 * n1 + n2 <= G : ((d->n_layers - 1) * n5 + 2 * n1 <= G && d->n_layers * n5 + n2 <= G);
-    if (tune_on(TUNE_DEC_B6_FUSED) && fits) a.b6_split = 2;
-  }
-  ASTK_CHECK(d->n_layers == 1 || a.b6_split, "decoder_persist_bwd: the multi-layer role layout needs the split d_x0 buffers");
+  a.b6_split = bf.DXH != nullptr && decoder_persist_b6_split(d) ? B6_SPLIT : B6_WHOLE;
+  // (astk_set_tuning("dec.b6_fused", 0): the d_x0 role of rounds 2-3, kept for A/B runs)
+  if (a.b6_split == B6_SPLIT && tune_on(TUNE_DEC_B6_FUSED) && pdec_bwd_roles(a.nbt, a.H, a.A, a.XI, d->n_layers, B6_FUSED).fits) a.b6_split = B6_FUSED;
+  ASTK_CHECK(d->n_layers == 1 || a.b6_split != B6_WHOLE, "decoder_persist_bwd: the multi-layer role layout needs the split d_x0 buffers");
   a.ctr = bf.ctr;
   a.ab = abort_ctl(bf.ctr + (size_t)NPHASE_SLOTS * NSH * a.nbt * CTRS, PERSIST_DEC_BWD);
   a.tick_out = prof_tick_buffer(1);
@@ -2387,8 +2413,7 @@ int decoder_persist_fwd_launch(const astk_decoder_desc* d, const astk_decoder_pa
   ASTK_CHECK(decoder_persist_applicable(d, &nsplit, &chunk), "decoder_persist: not applicable");
   PDecArgs a;
   memset(&a, 0, sizeof(a));
-  a.B = d->B; a.S = d->L - 1; a.L = d->L; a.T = d->T; a.Tp = (d->T + 3) / 4 * 4; a.H = d->H; a.E = d->E; a.A = d->A; a.V = d->V;
-  a.Vp = (d->V + 3) / 4 * 4; a.XI = d->E + d->A; a.nbt = (d->B + 15) / 16; a.nsplit = nsplit; a.chunk = chunk;
+  pdec_fill_shapes(a, d, d->L - 1, nsplit, chunk);
   a.ntile_v = (d->V + 15) / 16;
   a.inv_count = 1.f / (float)(d->loss_rows > 0 ? d->loss_rows : d->B);
   a.embed = prm->embed;
@@ -2491,8 +2516,7 @@ static PDecArgs inference_args(const astk_decoder_desc* d, const astk_decoder_pa
                                const GreedyPlan& g) {
   PDecArgs a;
   memset(&a, 0, sizeof(a));
-  a.B = d->B; a.S = S; a.L = S + 1; a.T = d->T; a.Tp = (d->T + 3) / 4 * 4; a.H = d->H; a.E = d->E; a.A = d->A; a.V = d->V;
-  a.Vp = (d->V + 3) / 4 * 4; a.XI = d->E + d->A; a.nbt = (d->B + 15) / 16; a.nsplit = g.nsplit; a.chunk = g.chunk;
+  pdec_fill_shapes(a, d, S, g.nsplit, g.chunk);
   a.ntile_v = (d->V + 15) / 16;
   a.inv_count = 1.f / (float)d->B;
   a.embed = prm->embed;

@@ -726,6 +726,9 @@ def _dec_setup(lib, B, L, T, H, E, A, V, nl, masks, seed=0, enc_gain=1.0, out_ga
                                                     # 28 stay in LDS and the rest is streamed every step
                                                     (32, 5, 300, 512, 128, 512, 1098, 1, False), (32, 4, 420, 512, 128, 512, 1098, 3, True),
                                                     (32, 4, 233, 512, 128, 512, 300, 1, True),
+                                                    # ... and with 2 layers: slices of 30 rows, the smallest T'' and vocabulary that reach the
+                                                    # streamed H = 512 scan of the two-layer kernels (forward and backward <8, 2, true>)
+                                                    (32, 4, 233, 512, 128, 512, 300, 2, True),
                                                     # more than 32 rows at the shipped width: two persistent launches over halves of the rows (row split:
                                                     # 64 = 32 + 32, 48 = 32 + 16, 37 = 32 + 5; masks and initial states staged per half, loss over all rows)
                                                     (64, 6, 200, 512, 128, 512, 1098, 1, True), (48, 5, 200, 512, 128, 512, 1098, 3, True),
