@@ -138,6 +138,14 @@ class CtcDesc(_Sized, C.Structure):
                 ("ldy", C.c_long), ("first_label", C.c_int), ("blank", C.c_int)]
 
 
+CTC_BEAM_MAX_N, CTC_BEAM_MAX_C, CTC_BEAM_MAX_T = 16, 16, 2048      # astk.h astk_ctc_beam: the bounds of N, C and T
+
+
+class CtcBeamDesc(_Sized, C.Structure):
+    _fields_ = [("struct_size", C.c_size_t), ("B", C.c_int), ("T", C.c_int), ("V", C.c_int), ("ldv", C.c_long), ("N", C.c_int),
+                ("C", C.c_int), ("max_labels", C.c_int), ("first_label", C.c_int), ("blank", C.c_int)]
+
+
 # the row-panel launchers' mirror structs (include/astk.h, the ASTK_TEST_HOOKS section; libastk_test.so only)
 class SpecAugmentDesc(_Sized, C.Structure):
     _fields_ = [("struct_size", C.c_uint32), ("n_freq", C.c_int), ("freq_width", C.c_int), ("n_time", C.c_int), ("time_width", C.c_int),
@@ -287,6 +295,8 @@ SIGNATURES = {
     "astk_ctc_greedy": (C.c_int, [C.POINTER(CtcDesc), _VP, _VP, _VP, _VP]),
     "astk_ctc_align_workspace_bytes": (_SZ, [C.POINTER(CtcDesc)]),
     "astk_ctc_align": (C.c_int, [C.POINTER(CtcDesc), _VP, _VP, _VP, _VP, _VP, _VP, _VP, _VP, _VP, _VP, _VP, _SZ, _VP]),
+    "astk_ctc_beam_workspace_bytes": (_SZ, [C.POINTER(CtcBeamDesc)]),
+    "astk_ctc_beam": (C.c_int, [C.POINTER(CtcBeamDesc), _VP, _VP, _VP, _VP, _VP, _VP, _SZ, _VP]),
     "astk_ctc_head_fwd": (C.c_int, [_I, _I, _I, _VP, _VP, _VP, _VP, _L, _I, _VP]),
     "astk_ctc_head_bwd": (C.c_int, [_I, _I, _I, _VP, _L, _VP, _VP, _VP, _VP, _VP, _I, _I, _VP]),
     "astk_persist_status_snapshot": (C.c_int, [_VP, _VP]),

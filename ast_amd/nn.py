@@ -814,6 +814,39 @@ class NN:
                 out[u] = row
         return out
 
+    def ctc_beam_set(self, set_key, N, C):
+        """CTC prefix beam search of a set through the head alone (SpeechEncoderDecoder.ctc_beam), batch by
+        batch with the rows' true frame counts as ctc_align_set takes them: {utt: [(hyp, score, [])]}, the n-best format of beam.py's
+        pickle without attention histories (hyp = [GO] + labels + [EOS], score = the pruned CTC sum)."""
+        out = {}
+        for batch in self.data_loader.get_batch(self.cfg.train["batch_size"], set_key, train=False, labels=True):
+            x_len = batch.get("x_len")
+            if x_len is None:
+                x_len = self.data_loader.frame_counts(set_key, batch["utts"])
+            for u, row in zip(batch["utts"], self.model.ctc_beam(batch["X"], x_lens=x_len, N=N, C=C)):
+                out[u] = [(h["hyp"], h["score"], []) for h in row]
+        return out
+
+
+def rescore_ctc_nbest(model, Xs, nbest, weight, max_utts=None):
+    """The second pass over CTC n-best lists (SpeechEncoderDecoder.ctc_beam): Xs a list of (1, T_u, D) inputs, nbest[u] the list of
+    utterance u's entries ({"hyp", "score", ..}).  The attention decoder scores every hypothesis (score_hypotheses_packed: calls of up
+    to 32 rows, at most max_utts utterances each); returns per utterance the entries ranked by (1 - weight) * att + weight * ctc
+    (equal scores keep the first pass's order), each a copy with "score" = that sum and "att_score", "ctc_score" beside it, the keys
+    joint_entry_scores reads."""
+    w = float(weight)
+    if not 0.0 <= w <= 1.0:
+        raise ValueError(f"rescore_ctc_nbest: weight must lie in [0, 1] (the terms weigh 1 - w and w), got {weight!r}")
+    if len(Xs) != len(nbest):
+        raise ValueError(f"rescore_ctc_nbest: {len(Xs)} inputs for {len(nbest)} n-best lists")
+    with using_config("train", False):
+        res = score_hypotheses_packed(model, Xs, [[list(e["hyp"]) for e in lst] for lst in nbest], max_utts=max_utts)
+    out = []
+    for lst, (att, _) in zip(nbest, res):
+        new = [dict(e, score=(1.0 - w) * a + w * float(e["score"]), att_score=a, ctc_score=float(e["score"])) for e, a in zip(lst, att)]
+        out.append(sorted(new, key=lambda e: -e["score"]))
+    return out
+
 
 # score.py's CTC alignment option lives here, with the alignment it writes: the command line itself stays the forced decoder's.
 ALIGNMENT_KEYS = ("segments", "segments_input", "labels", "confidence", "score", "total_logp")

@@ -381,6 +381,19 @@ def checked_ctc_weight(weight, has_head, what="ctc_weight"):
     return weight
 
 
+def checked_ctc_beam_width(N, C, V=None):
+    """(N, C) of a CTC prefix beam search as ints within astk_ctc_beam's bounds: 1 <= N <= 16, 1 <= C <= min(16, V - UNK_ID)."""
+    for name, v in (("N", N), ("C", C)):
+        if isinstance(v, bool) or not isinstance(v, (int, np.integer)):
+            raise ValueError(f"ctc_beam: {name} must be an integer, got {v!r}")
+    if not 1 <= N <= _lib.CTC_BEAM_MAX_N:
+        raise ValueError(f"ctc_beam: the beam width N must lie in 1..{_lib.CTC_BEAM_MAX_N}, got {N}")
+    top = _lib.CTC_BEAM_MAX_C if V is None else min(_lib.CTC_BEAM_MAX_C, int(V) - UNK_ID)
+    if not 1 <= C <= top:
+        raise ValueError(f"ctc_beam: C labels per frame must lie in 1..{top}, got {C}")
+    return int(N), int(C)
+
+
 def checked_x_lens(x_lens, B, T):
     """Frames per row in front of the CNN as a (B,) int64 host array; ValueError for another count, a non-integer dtype or a length
     outside 1..T.  A host array by contract: the lengths are mapped through the CNN's time formula on the host."""
@@ -1205,6 +1218,56 @@ class SpeechEncoderDecoder:
             prev = np.concatenate(([-1], row[:-1]))
             out.append([int(c) for c in row[(row != prev) & (row != PAD_ID)]])
         return out
+
+    def ctc_beam(self, X, x_lens=None, N=5, C=5, max_labels=None):
+        """CTC prefix beam search of the head alone (eval mode): encode the batch, the head's logits, the N most
+        probable label strings of every row over its valid frames with C labels proposed per frame (astk_ctc_beam); ONE device-to-host
+        copy.  Returns per row a list in rank order of {"hyp": [GO] + labels + [EOS], "score", "labels"}; score = the pruned float64
+        sum over the string's alignments, a lower bound of log p_ctc(labels).  max_labels (default min(T'', 255)) caps the strings."""
+        if not self.ctc_head:
+            raise ValueError("ctc_beam needs the CTC head: set rnn_config.ctc = true in model_cfg.json")
+        import ctypes                                        # (the parameter C shadows the module's alias)
+        N, C = checked_ctc_beam_width(N, C, self.V)
+        if max_labels is not None and not 1 <= int(max_labels) <= _lib.CTC_MAX_LABELS:
+            raise ValueError(f"ctc_beam: max_labels must lie in 1..{_lib.CTC_MAX_LABELS}, got {max_labels!r}")
+        lib = self._require_gpu()
+        X = self._as_input(X)
+        if x_lens is not None:
+            x_lens = checked_x_lens(x_lens, X.shape[0], X.shape[1])
+        with using_config("train", False):
+            self._cur = None
+            self.encode(X)
+        st, s = self._cur, self._stream()
+        lens = self._t2_lens(st, x_lens)
+        logits, Vp = self._ctc_logits(st, s)
+        B, T2 = st["B"], st["T2"]
+        if T2 > _lib.CTC_BEAM_MAX_T:
+            raise ValueError(f"ctc_beam: {T2} encoder frames exceed the {_lib.CTC_BEAM_MAX_T} a row is limited to")
+        Lm = min(T2, _lib.CTC_MAX_LABELS) if max_labels is None else int(max_labels)
+        bdesc = _lib.CtcBeamDesc(B, T2, self.V, Vp, N, C, Lm, UNK_ID, PAD_ID)
+        nbytes = int(lib.astk_ctc_beam_workspace_bytes(ctypes.byref(bdesc)))
+        if not nbytes:
+            raise _lib.AstkError(lib.astk_last_error().decode())
+        ws = self._workspace("ctc", nbytes)
+        # everything that goes back to the host, in one buffer of 4-byte words: score (B, N) float64 first (8-byte aligned), then
+        # n_labels (B, N) and tokens (B, N, Lm)
+        cuts = np.cumsum([0, 2 * B * N, B * N, B * N * Lm])
+        out = self._pool("ctc_beam_out", (int(cuts[-1]),), torch.int32)
+        p = [ctypes.c_void_p(out.data_ptr() + 4 * int(c)) for c in cuts[:-1]]
+        check(lib.astk_ctc_beam(ctypes.byref(bdesc), _vp(logits), _vp(lens), p[2], p[1], p[0], _vp(ws), ws.numel(), s))
+        host = out.cpu().numpy()
+        score = host[:cuts[1]].view(np.float64).reshape(B, N)
+        n_lab, tok = host[cuts[1]:cuts[2]].reshape(B, N), host[cuts[2]:].reshape(B, N, Lm)
+        rows = []
+        for b in range(B):
+            row = []
+            for r in range(N):
+                if n_lab[b, r] < 0:
+                    continue
+                labels = [int(c) for c in tok[b, r, :n_lab[b, r]]]
+                row.append({"hyp": [GO_ID] + labels + [EOS_ID], "score": float(score[b, r]), "labels": labels})
+            rows.append(row)
+        return rows
 
     def ctc_align(self, X, y, x_lens=None):
         """Forced alignment of the targets y (B, L) through the CTC head (eval mode): encode the batch, the head's

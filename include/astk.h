@@ -30,7 +30,7 @@
 extern "C" {
 #endif
 
-#define ASTK_VERSION 109
+#define ASTK_VERSION 110
 #define ASTK_MAX_CNN_LAYERS 4
 #define ASTK_MAX_RNN_LAYERS 8
 #define ASTK_MAX_ATTN 4
@@ -912,6 +912,45 @@ size_t astk_ctc_align_workspace_bytes(const astk_ctc_desc* d);
 int astk_ctc_align(const astk_ctc_desc* d, const float* logits, const int32_t* y, const int32_t* input_len, int32_t* frame_state,
                    int32_t* frame_class, int32_t* label_start, int32_t* label_end, float* label_logp, float* row_score,
                    int32_t* n_infeasible, void* ws, size_t ws_bytes, void* stream);
+/* ---------------------------------------------------------------- CTC prefix beam search
+ * N-best label strings from the head's logits alone (Hannun et al. 2014): the N most probable label prefixes are kept frame by frame,
+ * all alignments of one prefix merged.  logits (B, T, ldv) float32, input_len clamped to [0, T] (NULL = T; n below); labels are the ids
+ * >= first_label.  Float64 in the log domain; x[t][c] = logits[t][c] - lse[t], lse the float64 log-sum-exp over all V classes with the
+ * maximum subtracted; logaddexp(-inf, -inf) = -inf, never NaN.
+ *   proposals   per frame the C labels with the largest x[t][c]: higher first, equal ones lower id first; the same for every prefix
+ *   state       at most N distinct prefixes with p_b, p_nb = the log-probability of their alignments over the frames 0..t that end in
+ *               a blank / a non-blank; before frame 0 the empty prefix with p_b = 0, p_nb = -inf
+ *   frame step  tot = logaddexp(p_b, p_nb); a prefix l with last label e gives
+ *                 stay l:      p_b' = tot + x[t][blank], p_nb' = p_nb + x[t][e] (-inf for the empty prefix)
+ *                 extend l.c:  for every proposal c, if l has fewer than max_labels labels: p_b' = -inf,
+ *                              p_nb' = (c == e ? p_b : tot) + x[t][c]
+ *               an extension that spells another member l' of the beam (exact equality of the label strings) is no candidate of its
+ *               own: its p_nb' is added (logaddexp) to the stay candidate of l'
+ *   selection   the N candidates with the largest logaddexp(p_b', p_nb'), none at -inf; equal scores: stay candidates before
+ *               extensions, then the lower source slot, then the earlier proposal; the slots are in rank order after every frame
+ *   tokens      int32 (B, N, max_labels): the labels of slot r, the blank id behind them and in unused slots
+ *   n_labels    int32 (B, N): their count, -1 for an unused slot
+ *   score       float64 (B, N): logaddexp(p_b, p_nb) after the row's n frames, -inf for an unused slot: a lower bound of
+ *               log p_ctc(labels), equal to it where nothing was pruned.  n = 0: the empty string with score 0 in slot 0.
+ * logits is only read.  No atomics: bit-identical from run to run.  Two launches, no allocation, no synchronisation; ws of
+ * astk_ctc_beam_workspace_bytes (16-byte aligned: per frame the lse, the blank's and the proposals' log-probabilities and ids, per row a
+ * trie of the prefixes as a hash table of 2^k >= 2 (T N + 1) 8-byte entries).  Refused before any launch: a wrong struct_size; B, T < 1;
+ * T > ASTK_BEAM_CTC_MAX_T; V <= first_label; ldv < V; blank outside [0, V) or >= first_label; N or C outside 1..16; C > V - first_label;
+ * max_labels outside 1..ASTK_CTC_MAX_LABELS; a NULL logits / tokens / n_labels / score / ws; a workspace below the query (which returns
+ * 0 for a refused descriptor). */
+typedef struct {
+  size_t struct_size;   /* = sizeof(astk_ctc_beam_desc) */
+  int B, T, V;
+  long ldv;             /* row stride of logits, >= V */
+  int N;                /* beam width */
+  int C;                /* labels proposed per frame */
+  int max_labels;       /* no prefix grows beyond it; the stride of tokens */
+  int first_label;
+  int blank;
+} astk_ctc_beam_desc;
+size_t astk_ctc_beam_workspace_bytes(const astk_ctc_beam_desc* d);
+int astk_ctc_beam(const astk_ctc_beam_desc* d, const float* logits, const int32_t* input_len, int32_t* tokens, int32_t* n_labels,
+                  double* score, void* ws, size_t ws_bytes, void* stream);
 /* One wavefront that keeps `stream` busy for `usec` microseconds (<= 100 000) and then increments *flag (may be NULL).  For probing
  * whether two streams really execute concurrently: HIP multiplexes streams onto a few hardware queues (GPU_MAX_HW_QUEUES, 4 by
  * default), and two streams that share one are serialised whatever their events say (ast_amd/seq2seq.py:_cu_streams). */
