@@ -146,6 +146,13 @@ class CtcBeamDesc(_Sized, C.Structure):
                 ("C", C.c_int), ("max_labels", C.c_int), ("first_label", C.c_int), ("blank", C.c_int)]
 
 
+PAIR_MAX_LEN = 512      # astk.h ASTK_PAIR_MAX_LEN: the longest string of astk_pair_stats
+
+
+class PairStatsDesc(_Sized, C.Structure):
+    _fields_ = [("struct_size", C.c_size_t), ("S", C.c_int), ("Lmax", C.c_int), ("P", C.c_int)]
+
+
 # the row-panel launchers' mirror structs (include/astk.h, the ASTK_TEST_HOOKS section; libastk_test.so only)
 class SpecAugmentDesc(_Sized, C.Structure):
     _fields_ = [("struct_size", C.c_uint32), ("n_freq", C.c_int), ("freq_width", C.c_int), ("n_time", C.c_int), ("time_width", C.c_int),
@@ -297,6 +304,7 @@ SIGNATURES = {
     "astk_ctc_align": (C.c_int, [C.POINTER(CtcDesc), _VP, _VP, _VP, _VP, _VP, _VP, _VP, _VP, _VP, _VP, _VP, _SZ, _VP]),
     "astk_ctc_beam_workspace_bytes": (_SZ, [C.POINTER(CtcBeamDesc)]),
     "astk_ctc_beam": (C.c_int, [C.POINTER(CtcBeamDesc), _VP, _VP, _VP, _VP, _VP, _VP, _SZ, _VP]),
+    "astk_pair_stats": (C.c_int, [C.POINTER(PairStatsDesc), _VP, _VP, _VP, _VP, _VP, _VP]),
     "astk_ctc_head_fwd": (C.c_int, [_I, _I, _I, _VP, _VP, _VP, _VP, _L, _I, _VP]),
     "astk_ctc_head_bwd": (C.c_int, [_I, _I, _I, _VP, _L, _VP, _VP, _VP, _VP, _VP, _I, _I, _VP]),
     "astk_persist_status_snapshot": (C.c_int, [_VP, _VP]),

@@ -533,6 +533,101 @@ def mbr_select(hyps):
     return best[1]
 
 
+def posterior_weights(scores, scale=1.0):
+    """softmax(scale * score) in float64, the maximum subtracted: the weights mbr_select_lists takes when the members of a list are
+    to count by their (scaled) posterior instead of equally."""
+    z = [float(scale) * float(s) for s in scores]
+    top = max(z)
+    e = [math.exp(v - top) for v in z]
+    total = sum(e)
+    return [v / total for v in e]
+
+
+def _mbr_choice(hyps, value, utility, weights):
+    """The index mbr_select_lists returns for one list: value(i, j) is the sentence BLEU ("bleu") or the edit distance ("edit") of
+    member i against member j as its reference.  Sums run over j in ascending order; ties go to the higher score, then the lower index."""
+    n, best = len(hyps), None
+    for i in range(n):
+        others = [j for j in range(n) if j != i]
+        if weights is None:
+            total = sum(value(i, j) for j in others)
+            merit = (total / len(others) if others else 0.0) if utility == "bleu" else -total
+        else:
+            mass = sum(float(weights[j]) for j in others)
+            total = sum(float(weights[j]) * value(i, j) for j in others)
+            merit = (total / mass if mass > 0.0 else 0.0) * (1.0 if utility == "bleu" else -1.0)
+        key = (merit, float(hyps[i]["score"]), -i)
+        if best is None or key > best[0]:
+            best = (key, i)
+    return best[1]
+
+
+def mbr_select_lists(lists, utility="bleu", weights=None, device=None):
+    """Minimum-Bayes-risk choice in many n-best lists at once: lists[u] holds the entries {"hyp", "score"} of
+    utterance u; returns one chosen index per list.  The lists of a call share one pool and one astk_pair_stats launch over the pairs
+    i < j inside each list (distance and matches are symmetric; the host fills both directions).
+      utility="bleu"  the member with the highest mean sentence BLEU (ast_amd.eval.bleu_from_counts) against every other member as
+                      its reference -- with weights=None exactly mbr_select(lst) for every list
+      utility="edit"  the member with the least summed edit distance to the others (an integer)
+    Ties go to the higher score, then the lower index; a one-element list chooses 0.  weights: one sequence per list (e.g.
+    posterior_weights of its scores); the mean becomes the weighted mean over the other members, in float64 on the host.  A list with a
+    hypothesis longer than PAIR_MAX_LEN tokens is handled on the host, that list only."""
+    from .eval import PAIR_MAX_LEN, bleu_from_counts, clipped_matches, edit_stats, pair_stats
+    if utility not in ("bleu", "edit"):
+        raise ValueError(f"mbr_select_lists: utility must be \"bleu\" or \"edit\", got {utility!r}")
+    if weights is not None and len(weights) != len(lists):
+        raise ValueError(f"mbr_select_lists: {len(weights)} weight sequences for {len(lists)} lists")
+    toks = []
+    for u, lst in enumerate(lists):
+        if not lst:
+            raise ValueError("mbr_select_lists: no hypotheses in list {0:d}".format(u))
+        if weights is not None and len(weights[u]) != len(lst):
+            raise ValueError(f"mbr_select_lists: {len(weights[u])} weights for the {len(lst)} hypotheses of list {u}")
+        toks.append([[int(t) for t in h["hyp"]] for h in lst])
+    on_dev = [len(ts) > 1 and max(len(t) for t in ts) <= PAIR_MAX_LEN for ts in toks]
+    pool, pairs = [], []
+    for ts, f in zip(toks, on_dev):
+        if f:
+            base = len(pool)
+            pool.extend(ts)
+            pairs.extend((base + i, base + j) for i in range(len(ts)) for j in range(i + 1, len(ts)))
+    rows = iter(pair_stats(pool, pairs, device).tolist())
+    col = slice(4, 8) if utility == "bleu" else 0
+    out = []
+    for u, (lst, ts, f) in enumerate(zip(lists, toks, on_dev)):
+        w = None if weights is None else weights[u]
+        if f:
+            table = {}
+            for i in range(len(ts)):
+                for j in range(i + 1, len(ts)):
+                    table[i, j] = table[j, i] = next(rows)[col]
+        elif utility == "bleu" and w is None:
+            out.append(mbr_select(lst))
+            continue
+        else:
+            table = {(i, j): clipped_matches(ts[i], ts[j]) if utility == "bleu" else edit_stats(ts[i], ts[j])[0]
+                     for i in range(len(ts)) for j in range(len(ts)) if i != j}
+        if utility == "bleu":
+            out.append(_mbr_choice(lst, lambda i, j: bleu_from_counts(table[i, j], len(ts[i]), len(ts[j])), utility, w))
+        else:
+            out.append(_mbr_choice(lst, lambda i, j: table[i, j], utility, w))
+    return out
+
+
+def mbr_select_set(nbest, utility="bleu", posterior_scale=None, utts_per_call=1, device=None):
+    """mbr_select_lists over an n-best pickle ({utt: [(hyp, score, ..), ..]}, as beam.py, ctc_decode.py and sample.py write it), the
+    lists of utts_per_call utterances per launch: {utt: the chosen hyp}.  posterior_scale: weigh the members of a list by
+    posterior_weights(scores, scale) instead of equally."""
+    utts, chosen = list(nbest), {}
+    for lo in range(0, len(utts), max(1, int(utts_per_call))):
+        group = utts[lo:lo + max(1, int(utts_per_call))]
+        lists = [[{"hyp": e[0], "score": e[1]} for e in nbest[u]] for u in group]
+        weights = None if posterior_scale is None else [posterior_weights([e["score"] for e in lst], posterior_scale) for lst in lists]
+        for u, k in zip(group, mbr_select_lists(lists, utility, weights, device)):
+            chosen[u] = list(nbest[u][k][0])
+    return chosen
+
+
 def _init_hyp_from(model, enc_states):
     return {"hyp": [SYMBOLS.GO_ID], "score": 0, "dec_state": enc_states,
             "attn_v": torch.zeros(1, model.cfg["rnn_config"]["attn_units"], dtype=torch.float32, device=model.device), "attn_history": []}

@@ -1,16 +1,18 @@
 """CTC prefix beam search from the command line:
-    python ctc_decode.py -m <cfg_dir> -s <set key> -n <N> -c <C> [-w <out pickle>] [--rescore <W> [-b U] [--batch-encode]]
+    python ctc_decode.py -m <cfg_dir> -s <set key> -n <N> -c <C> [-w <out pickle>] [--rescore <W> [-b U] [--batch-encode]] [--wer]
 Decodes every utterance of the set with the CTC head of the newest checkpoint alone (NN.ctc_beam_set: the N most probable label
 strings, C labels proposed per frame) and pickles the n-best lists to <cfg_dir>/<set>_ctc_N-<N>_C-<C>.p (or -w)
 in the format of beam.py's n-best pickle, so `score.py --nbest` reads it unchanged.  --rescore W adds the second pass: the attention
 decoder scores every hypothesis (ast_amd.nn.rescore_ctc_nbest; -b U packs the hypotheses of up to U utterances into one call) and the
 lists are ranked by (1 - W) * attention + W * CTC; the tuples then end with the two terms, as beam.py's do after a joint search.
-Needs rnn_config.ctc in model_cfg.json."""
+--wer prints the word error rate of every list's first hypothesis against the set's references (ast_amd.eval.error_rate, DESIGN.md
+section 34).  Needs rnn_config.ctc in model_cfg.json."""
 import argparse
 import itertools
 import os
 import pickle
 
+from ast_amd.eval import Eval
 from ast_amd.nn import NN, joint_entry_scores, rescore_ctc_nbest
 
 
@@ -26,7 +28,14 @@ def build_parser():
     parser.add_argument("-b", "--batch", type=int, default=1, help="with --rescore: pack the hypotheses of U utterances into one call (default 1)")
     parser.add_argument("--batch-encode", dest="batch_encode", action="store_true",
                         help="encode the utterances of a call in one padded batch with per-row lengths instead of one by one (same encodings; effective with -b U)")
+    parser.add_argument("--wer", action="store_true", help="print the word error rate of the 1-best against the set's references")
     return parser
+
+
+def wer_of_best(nn, set_key, nbest):
+    """Eval.calc_wer of every list's first hypothesis against the references under data.refs_path."""
+    metrics = Eval(os.path.join(nn.cfg.train["data"]["refs_path"], set_key), nn.cfg.train["data"]["n_evals"])
+    return metrics.calc_wer(nn.data_loader.get_hyps((u, list(lst[0][0])) for u, lst in nbest.items()))
 
 
 def default_name(set_key, N, C, weight=None):
@@ -73,3 +82,6 @@ if __name__ == "__main__":
     with open(out_fname, "wb") as f:
         pickle.dump(nbest, f)
     print("Hypotheses written to: {0:s} (utterances: {1:d}, path: {2})".format(out_fname, len(nbest), "ctc_beam" if W is None else "ctc_beam + rescore"))
+    if args["wer"]:
+        wer = wer_of_best(nn, set_key, nbest)
+        print("WER = {0:.2f} (S {1:d}, D {2:d}, I {3:d}, N {4:d})".format(wer["rate"] * 100, wer["S"], wer["D"], wer["I"], wer["N"]))

@@ -30,7 +30,7 @@
 extern "C" {
 #endif
 
-#define ASTK_VERSION 110
+#define ASTK_VERSION 111
 #define ASTK_MAX_CNN_LAYERS 4
 #define ASTK_MAX_RNN_LAYERS 8
 #define ASTK_MAX_ATTN 4
@@ -951,6 +951,38 @@ typedef struct {
 size_t astk_ctc_beam_workspace_bytes(const astk_ctc_beam_desc* d);
 int astk_ctc_beam(const astk_ctc_beam_desc* d, const float* logits, const int32_t* input_len, int32_t* tokens, int32_t* n_labels,
                   double* score, void* ws, size_t ws_bytes, void* stream);
+/* ---------------------------------------------------------------- pair statistics of token strings
+ * What minimum-Bayes-risk selection and error rates need of an n-best list, as integers: for every pair (a, b) = (hypothesis,
+ * reference) of a pool of token strings the Levenshtein statistics and the clipped n-gram matches of BLEU.
+ *   tokens  int32 (S, Lmax): the pool; any int32 value is an id; what lies behind a string's length is never read
+ *   lens    int32 (S): each in 0..Lmax
+ *   pairs   int32 (P, 2): rows (a, b) of indices into the pool; a == b and repeated rows are allowed
+ *   stats   int32 (P, 8) = [dist, sub, del, ins, m1, m2, m3, m4]
+ *   n_bad   int32, may be NULL: the number of bad rows
+ * Edit statistics: D[0][0] = (0, 0, 0, 0) substitutions, deletions, insertions; D[i][0] = i insertions, D[0][j] = j deletions; for
+ * i, j >= 1 the candidates are, in this order,
+ *     diagonal   D[i-1][j-1], + 1 sub when a[i-1] != b[j-1]
+ *     deletion   D[i][j-1] + 1 del (the reference token b[j-1] stays unmatched)
+ *     insertion  D[i-1][j] + 1 ins
+ * and the cell takes the one of least cost sub + del + ins, the earlier one among equals, with that candidate's three counts.  The
+ * output is D[La][Lb]: dist = sub + del + ins is the Levenshtein distance, del - ins = Lb - La, and the forward rule makes the three
+ * counts well defined without a back-pointer matrix.
+ * Clipped matches: m_n = sum over the distinct n-grams g of min(count_a(g), count_b(g)), n = 1..4; 0 when either string has fewer
+ * than n tokens; symmetric in (a, b) -- the numerator of BLEU's n-gram precision with one reference.
+ * A row is bad when an index lies outside [0, S) or a named length outside [0, Lmax]: it gets eight -1, reads nothing out of bounds
+ * and is counted in *n_bad.
+ * tokens, lens and pairs are only read.  Integers throughout and no atomics: bit-identical from run to run, equal to a host model.
+ * One launch (two with n_bad), no allocation, no synchronisation, no workspace.  Refused before any launch: a wrong struct_size;
+ * S < 1; P < 1; Lmax outside 1..ASTK_PAIR_MAX_LEN; a NULL tokens / lens / pairs / stats. */
+#define ASTK_PAIR_MAX_LEN 512
+typedef struct {
+  size_t struct_size;   /* = sizeof(astk_pair_stats_desc) */
+  int S;                /* strings in the pool */
+  int Lmax;             /* row stride of tokens, the longest string admitted */
+  int P;                /* pairs */
+} astk_pair_stats_desc;
+int astk_pair_stats(const astk_pair_stats_desc* d, const int32_t* tokens, const int32_t* lens, const int32_t* pairs, int32_t* stats,
+                    int32_t* n_bad, void* stream);
 /* One wavefront that keeps `stream` busy for `usec` microseconds (<= 100 000) and then increments *flag (may be NULL).  For probing
  * whether two streams really execute concurrently: HIP multiplexes streams onto a few hardware queues (GPU_MAX_HW_QUEUES, 4 by
  * default), and two streams that share one are serialised whatever their events say (ast_amd/seq2seq.py:_cu_streams). */
