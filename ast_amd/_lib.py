@@ -153,6 +153,25 @@ class PairStatsDesc(_Sized, C.Structure):
     _fields_ = [("struct_size", C.c_size_t), ("S", C.c_int), ("Lmax", C.c_int), ("P", C.c_int)]
 
 
+# astk.h ASTK_FEAT_*: kinds, windows, sample types and bounds of astk_speech_features
+FEAT_MFCC, FEAT_FBANK = 0, 1
+FEAT_WINDOWS = {"povey": 0, "hamming": 1, "hanning": 2, "rectangular": 3}
+FEAT_SAMPLE_F32, FEAT_SAMPLE_I16 = 0, 1
+FEAT_MAX_FRAME_LEN, FEAT_MAX_MEL_BINS = 2048, 128
+
+
+class SpeechFeaturesDesc(_Sized, C.Structure):
+    _fields_ = [("struct_size", C.c_size_t), ("B", C.c_int), ("Nmax", C.c_int), ("Fmax", C.c_int), ("sample_type", C.c_int),
+                ("kind", C.c_int), ("window", C.c_int), ("frame_len", C.c_int), ("frame_shift", C.c_int), ("num_mel_bins", C.c_int),
+                ("num_ceps", C.c_int), ("remove_dc_offset", C.c_int), ("use_energy", C.c_int), ("sample_frequency", C.c_double),
+                ("low_freq", C.c_double), ("high_freq", C.c_double), ("preemphasis", C.c_double), ("cepstral_lifter", C.c_double),
+                ("dither", C.c_double), ("seed", C.c_uint64), ("offsets", C.c_void_p)]
+
+
+class CmvnDesc(_Sized, C.Structure):
+    _fields_ = [("struct_size", C.c_size_t), ("B", C.c_int), ("Fmax", C.c_int), ("D", C.c_int), ("G", C.c_int), ("norm_vars", C.c_int)]
+
+
 # the row-panel launchers' mirror structs (include/astk.h, the ASTK_TEST_HOOKS section; libastk_test.so only)
 class SpecAugmentDesc(_Sized, C.Structure):
     _fields_ = [("struct_size", C.c_uint32), ("n_freq", C.c_int), ("freq_width", C.c_int), ("n_time", C.c_int), ("time_width", C.c_int),
@@ -305,6 +324,11 @@ SIGNATURES = {
     "astk_ctc_beam_workspace_bytes": (_SZ, [C.POINTER(CtcBeamDesc)]),
     "astk_ctc_beam": (C.c_int, [C.POINTER(CtcBeamDesc), _VP, _VP, _VP, _VP, _VP, _VP, _SZ, _VP]),
     "astk_pair_stats": (C.c_int, [C.POINTER(PairStatsDesc), _VP, _VP, _VP, _VP, _VP, _VP]),
+    "astk_speech_features_workspace_bytes": (_SZ, [C.POINTER(SpeechFeaturesDesc)]),
+    "astk_speech_features_prepare": (C.c_int, [C.POINTER(SpeechFeaturesDesc), _VP, _SZ, _VP]),
+    "astk_speech_features": (C.c_int, [C.POINTER(SpeechFeaturesDesc), _VP, _VP, _VP, _VP, _VP, _VP, _SZ, _VP]),
+    "astk_cmvn_accumulate": (C.c_int, [C.POINTER(CmvnDesc), _VP, _VP, _VP, _VP, _VP, _VP]),
+    "astk_cmvn_apply": (C.c_int, [C.POINTER(CmvnDesc), _VP, _VP, _VP, _VP, _VP, _VP]),
     "astk_ctc_head_fwd": (C.c_int, [_I, _I, _I, _VP, _VP, _VP, _VP, _L, _I, _VP]),
     "astk_ctc_head_bwd": (C.c_int, [_I, _I, _I, _VP, _L, _VP, _VP, _VP, _VP, _VP, _I, _I, _VP]),
     "astk_persist_status_snapshot": (C.c_int, [_VP, _VP]),

@@ -30,7 +30,7 @@
 extern "C" {
 #endif
 
-#define ASTK_VERSION 111
+#define ASTK_VERSION 112
 #define ASTK_MAX_CNN_LAYERS 4
 #define ASTK_MAX_RNN_LAYERS 8
 #define ASTK_MAX_ATTN 4
@@ -983,6 +983,109 @@ typedef struct {
 } astk_pair_stats_desc;
 int astk_pair_stats(const astk_pair_stats_desc* d, const int32_t* tokens, const int32_t* lens, const int32_t* pairs, int32_t* stats,
                     int32_t* n_bad, void* stream);
+/* ---------------------------------------------------------------- speech features from waveforms, and CMVN
+ * MFCC / log mel filterbank features in the sense of Kaldi's compute-mfcc-feats / compute-fbank-feats (snip-edges=true only), written
+ * from Kaldi's documented algorithm and option names; parity with Kaldi's binaries is NOT pinned (no Kaldi output exists to pin it
+ * to): the contract is the float64 restatement tests/speech_features_model.py.
+ *   wave       (B, Nmax) float32 or int16 (sample_type); sample values are used as they are (Kaldi's 16-bit scale, no division)
+ *   n_samples  int32 (B); nothing behind a row's length is read
+ *   feats      float32 (B, Fmax, D); D = num_mel_bins (fbank) or num_ceps (mfcc); frames t >= F_b are written as zeros
+ *   n_frames   int32 (B): F_b, or -1 for a bad row
+ *   n_bad      int32, may be NULL: the number of bad rows
+ * Frames: F_b = 0 if n_b < frame_len, else 1 + (n_b - frame_len) / frame_shift (integer division); frame t covers the samples
+ * t * frame_shift .. + frame_len.  N = the next power of two at or above frame_len.  Per frame, in this order:
+ *   1. dither (dither != 0): x[n] += dither * z(seed, offset_b + n); z(seed, g) is element g of the unit-normal stream of
+ *      astk_fill_normal at offset 0 (pair g >> 1: b = mix64(seed ^ mix64(g >> 1)), u1 / u2 = ((low / high half >> 8) + 1) 2^-24,
+ *      sqrt(-2 ln u1) cos(2 pi u2) for even g, .. sin .. for odd g), evaluated in float64.  A function of the SAMPLE index: a sample
+ *      carries the same dither in every frame that contains it (Kaldi draws per extracted frame).  offset_b = offsets[b], 0 if NULL.
+ *   2. remove_dc_offset: subtract the frame's mean
+ *   3. use_energy: raw log energy log(max(sum x^2, eps)) of the frame at this point; eps = 2^-23
+ *   4. pre-emphasis: x[i] -= c x[i-1] for i = frame_len-1 .. 1, then x[0] -= c x[0]
+ *   5. window: povey (0.5 - 0.5 cos(2 pi i / (frame_len - 1)))^0.85, hamming 0.54 - 0.46 cos(..), hanning 0.5 - 0.5 cos(..), rectangular
+ *   6. zero-pad to N, real FFT, power spectrum |X_k|^2
+ *   7. mel filterbank: mel(f) = 1127 ln(1 + f / 700); num_mel_bins triangles equally spaced in mel between low_freq and the resolved
+ *      high_freq (high_freq <= 0: Nyquist + high_freq); with delta = (mel_high - mel_low) / (num_mel_bins + 1), filter j has left =
+ *      mel_low + j delta, center = mel_low + (j + 1) delta, right = mel_low + (j + 2) delta.  FFT bin i in 0 .. N/2 - 1 lies at f = i sr / N and contributes to
+ *      filter j when left < mel(f) < right, with weight (mel - left) / (center - left) when mel <= center, else (right - mel) /
+ *      (right - center).  E_j = sum_i w_ji |X_i|^2 (ascending i); L_j = log(E_j) when E_j > eps, else log(eps).
+ *   8. fbank: the row is L.  mfcc: c_k = sum_j (lift_k dct[k][j]) L_j (ascending j, each product rounded, then added), dct[0][j] =
+ *      sqrt(1/M), dct[k][j] = sqrt(2/M) cos(pi/M (j + 0.5) k), lift_k = 1 + 0.5 Q sin(pi k / Q), Q = cepstral_lifter (0: no lifter);
+ *      with use_energy c_0 is the raw log energy of step 3.
+ * Float64 from step 1 to the last sum, rounded once to float32.  No atomics: two runs give identical bytes.
+ * A bad row -- n_samples outside [0, Nmax], or F_b > Fmax -- gets n_frames = -1 and all-zero feature rows, reads nothing out of bounds
+ * and is counted in *n_bad.
+ *   astk_speech_features_workspace_bytes  bytes of the table workspace (0 for a refused descriptor)
+ *   astk_speech_features_prepare          one small launch that fills the tables (window, twiddles, the filters' bin ranges and
+ *                                         weights, lift * dct) on the device in float64 and a digest of the descriptor's table fields
+ *                                         (sample_frequency, frame_len, window, num_mel_bins, num_ceps, low_freq, high_freq,
+ *                                         cepstral_lifter, kind) in the workspace head.  B, Nmax, Fmax, sample_type, frame_shift and
+ *                                         the per-frame options may differ between prepare and the calls that use the workspace.
+ *   astk_speech_features                  one launch (two with n_bad)
+ * All three only enqueue: no allocation, no copy, no synchronisation.  The library remembers the digest of every workspace address it
+ * prepared (host side) and the kernel compares the digest in the workspace head again: a workspace that was overwritten since makes
+ * every row a bad row.
+ * Refused before any launch: a wrong struct_size; B, Nmax or Fmax < 1; frame_len outside 2..2048; frame_shift < 1; num_mel_bins
+ * outside 3..128; num_ceps outside 1..num_mel_bins (mfcc); low_freq < 0, or a resolved high_freq at or below low_freq or above Nyquist;
+ * an unknown kind / window / sample type; use_energy with fbank; NULL buffers; a workspace that is too small, was never prepared, or
+ * was prepared for another descriptor. */
+#define ASTK_FEAT_MFCC 0
+#define ASTK_FEAT_FBANK 1
+#define ASTK_FEAT_WINDOW_POVEY 0
+#define ASTK_FEAT_WINDOW_HAMMING 1
+#define ASTK_FEAT_WINDOW_HANNING 2
+#define ASTK_FEAT_WINDOW_RECTANGULAR 3
+#define ASTK_FEAT_SAMPLE_F32 0
+#define ASTK_FEAT_SAMPLE_I16 1
+#define ASTK_FEAT_MAX_FRAME_LEN 2048
+#define ASTK_FEAT_MAX_MEL_BINS 128
+typedef struct {
+  size_t struct_size;      /* = sizeof(astk_speech_features_desc) */
+  int B;                   /* rows of the batch */
+  int Nmax;                /* row stride of wave, the longest waveform admitted */
+  int Fmax;                /* frames per row of feats */
+  int sample_type;         /* ASTK_FEAT_SAMPLE_* */
+  int kind;                /* ASTK_FEAT_MFCC / ASTK_FEAT_FBANK */
+  int window;              /* ASTK_FEAT_WINDOW_* */
+  int frame_len;           /* samples */
+  int frame_shift;         /* samples */
+  int num_mel_bins;
+  int num_ceps;            /* mfcc only */
+  int remove_dc_offset;
+  int use_energy;          /* mfcc only */
+  double sample_frequency;
+  double low_freq;
+  double high_freq;
+  double preemphasis;
+  double cepstral_lifter;
+  double dither;
+  uint64_t seed;
+  const int64_t* offsets;  /* device (B) dither stream offsets, or NULL for zeros */
+} astk_speech_features_desc;
+size_t astk_speech_features_workspace_bytes(const astk_speech_features_desc* d);
+int astk_speech_features_prepare(const astk_speech_features_desc* d, void* ws, size_t ws_bytes, void* stream);
+int astk_speech_features(const astk_speech_features_desc* d, const void* wave, const int32_t* n_samples, float* feats, int32_t* n_frames,
+                         int32_t* n_bad, void* ws, size_t ws_bytes, void* stream);
+/* Cepstral mean and variance normalisation of float32 feature batches (B, Fmax, D) -- from astk_speech_features or from files.
+ *   astk_cmvn_accumulate  adds the frames t < min(n_frames[b], Fmax) of the rows with n_frames[b] >= 0 to the float64 statistics
+ *                         stats (G, 2, D + 1) of group[b], Kaldi's layout: [g][0][:D] sums, [g][0][D] the frame count, [g][1][:D] sums
+ *                         of squares, [g][1][D] stays 0.  It ADDS to what is there (zero the buffer first; a speaker's statistics
+ *                         may span calls).  A group id outside [0, G) skips the row and counts it in *n_bad (may be NULL).  No atomics,
+ *                         a fixed summation order: two runs give identical bytes.
+ *   astk_cmvn_apply       y = (x - mean_g) * s_g on the same frames, in place (feats_out == feats_in) or out of place; mean = sum /
+ *                         count; s = 1 without norm_vars, else 1 / sqrt(max(sumsq / count - mean^2, 1e-20)); float64 arithmetic on
+ *                         the float32 input, rounded once.  Rows of a group with count 0 or an id outside [0, G), rows with n_frames
+ *                         < 0 and the frames at or behind n_frames[b] come out as they went in.
+ * One launch each (two with n_bad).  Refused before any launch: a wrong struct_size; B, Fmax, D or G < 1; NULL buffers. */
+typedef struct {
+  size_t struct_size;      /* = sizeof(astk_cmvn_desc) */
+  int B, Fmax, D;
+  int G;                   /* groups (speakers) */
+  int norm_vars;
+} astk_cmvn_desc;
+int astk_cmvn_accumulate(const astk_cmvn_desc* d, const float* feats, const int32_t* n_frames, const int32_t* group, double* stats,
+                         int32_t* n_bad, void* stream);
+int astk_cmvn_apply(const astk_cmvn_desc* d, const float* feats_in, float* feats_out, const int32_t* n_frames, const int32_t* group,
+                    const double* stats, void* stream);
 /* One wavefront that keeps `stream` busy for `usec` microseconds (<= 100 000) and then increments *flag (may be NULL).  For probing
  * whether two streams really execute concurrently: HIP multiplexes streams onto a few hardware queues (GPU_MAX_HW_QUEUES, 4 by
  * default), and two streams that share one are serialised whatever their events say (ast_amd/seq2seq.py:_cu_streams). */
