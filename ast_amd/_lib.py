@@ -172,6 +172,15 @@ class CmvnDesc(_Sized, C.Structure):
     _fields_ = [("struct_size", C.c_size_t), ("B", C.c_int), ("Fmax", C.c_int), ("D", C.c_int), ("G", C.c_int), ("norm_vars", C.c_int)]
 
 
+# astk.h ASTK_RESAMPLE_*: the bounds of astk_resample (reduced q, half taps K) and its tile of output samples
+RESAMPLE_MAX_PHASES, RESAMPLE_MAX_HALF_TAPS, RESAMPLE_TILE = 1024, 256, 256
+
+
+class ResampleDesc(_Sized, C.Structure):
+    _fields_ = [("struct_size", C.c_size_t), ("B", C.c_int), ("Nmax", C.c_int), ("Mmax", C.c_int), ("sample_type", C.c_int),
+                ("p", C.c_int), ("q", C.c_int), ("num_zeros", C.c_int), ("rolloff", C.c_double)]
+
+
 # the row-panel launchers' mirror structs (include/astk.h, the ASTK_TEST_HOOKS section; libastk_test.so only)
 class SpecAugmentDesc(_Sized, C.Structure):
     _fields_ = [("struct_size", C.c_uint32), ("n_freq", C.c_int), ("freq_width", C.c_int), ("n_time", C.c_int), ("time_width", C.c_int),
@@ -329,6 +338,9 @@ SIGNATURES = {
     "astk_speech_features": (C.c_int, [C.POINTER(SpeechFeaturesDesc), _VP, _VP, _VP, _VP, _VP, _VP, _SZ, _VP]),
     "astk_cmvn_accumulate": (C.c_int, [C.POINTER(CmvnDesc), _VP, _VP, _VP, _VP, _VP, _VP]),
     "astk_cmvn_apply": (C.c_int, [C.POINTER(CmvnDesc), _VP, _VP, _VP, _VP, _VP, _VP]),
+    "astk_resample_workspace_bytes": (_SZ, [C.POINTER(ResampleDesc)]),
+    "astk_resample_prepare": (C.c_int, [C.POINTER(ResampleDesc), _VP, _SZ, _VP]),
+    "astk_resample": (C.c_int, [C.POINTER(ResampleDesc), _VP, _VP, _VP, _VP, _VP, _VP, _SZ, _VP]),
     "astk_ctc_head_fwd": (C.c_int, [_I, _I, _I, _VP, _VP, _VP, _VP, _L, _I, _VP]),
     "astk_ctc_head_bwd": (C.c_int, [_I, _I, _I, _VP, _L, _VP, _VP, _VP, _VP, _VP, _I, _I, _VP]),
     "astk_persist_status_snapshot": (C.c_int, [_VP, _VP]),

@@ -1,9 +1,11 @@
 """Speech features from waveforms on the device (include/astk.h astk_speech_features, astk_cmvn_*): MFCC / log mel
 filterbank rows in the sense of Kaldi's compute-mfcc-feats / compute-fbank-feats, and cepstral mean and variance normalisation.  The
-definition is tests/speech_features_model.py; parity with Kaldi's binaries is not pinned.  There is no host fall-back: the compute path is
-the HIP library."""
+definition is tests/speech_features_model.py; parity with Kaldi's binaries is not pinned.  In front of them, resampling by a rational
+ratio and with it speed perturbation (astk_resample; the definition is tests/resample_model.py, parity with sox /
+Kaldi unpinned).  There is no host fall-back: the compute path is the HIP library."""
 import ctypes as C
 import dataclasses
+import fractions
 import wave as _wave
 
 import numpy as np
@@ -147,10 +149,102 @@ def _workspace(cfg, device, desc):
     return ws
 
 
+def _sample_type(wave, what):
+    import torch
+    if wave.dim() != 2 or not wave.is_contiguous() or wave.dtype not in (torch.int16, torch.float32) or not wave.is_cuda:
+        raise ValueError(f"{what}: wave must be a contiguous (B, Nmax) int16 or float32 tensor on the device")
+    if wave.shape[0] < 1 or wave.shape[1] < 1:
+        raise ValueError(f"{what}: wave of shape {tuple(wave.shape)}, there must be at least one row and one sample")
+    return _lib.FEAT_SAMPLE_I16 if wave.dtype == torch.int16 else _lib.FEAT_SAMPLE_F32
+
+
+def _lengths(n_samples, wave, what):
+    import torch
+    if not isinstance(n_samples, torch.Tensor) or n_samples.dtype != torch.int32 or n_samples.device != wave.device or \
+            tuple(n_samples.shape) != (wave.shape[0],) or not n_samples.is_contiguous():
+        raise ValueError(f"{what}: n_samples must be a contiguous int32 tensor of {wave.shape[0]} lengths on the wave's device")
+    return n_samples
+
+
+def compute_device(wave, n_samples, cfg, seed=0, offsets=None):
+    """The device-tensor half of compute: features of the rows of wave (B, Nmax) int16 or float32 with the int32 lengths n_samples (B),
+    both on the device -- (X (B, Fmax, D) float32, n_frames (B) int32) with Fmax = max(1, cfg.frames(Nmax)).  No host trip: the output
+    of resample goes straight in (a row it refused, n_out = -1, comes out with n_frames = -1).  offsets: the dither stream offset of
+    each row, a list of ints or an int64 device tensor (default 0)."""
+    import torch
+    stype = _sample_type(wave, "features.compute_device")
+    n_samples = _lengths(n_samples, wave, "features.compute_device")
+    device = wave.device
+    B, Nmax = wave.shape
+    Fmax = max(1, cfg.frames(Nmax))
+    off = None
+    if offsets is not None:
+        if len(offsets) != B:
+            raise ValueError(f"features.compute: {len(offsets)} offsets for {B} waveforms")
+        if isinstance(offsets, torch.Tensor):
+            off = offsets.to(device=device, dtype=torch.int64).contiguous()
+        else:
+            off = torch.tensor([int(o) for o in offsets], dtype=torch.int64, device=device)
+    desc = cfg.descriptor(B, Nmax, Fmax, stype, seed, off.data_ptr() if off is not None else None)
+    ws = _workspace(cfg, device, desc)
+    X = torch.empty(B, Fmax, cfg.dim, dtype=torch.float32, device=device)
+    n_frames = torch.empty(B, dtype=torch.int32, device=device)
+    _lib.check(_lib.load().astk_speech_features(C.byref(desc), C.c_void_p(wave.data_ptr()), C.c_void_p(n_samples.data_ptr()),
+                                                C.c_void_p(X.data_ptr()), C.c_void_p(n_frames.data_ptr()), None,
+                                                C.c_void_p(ws.data_ptr()), ws.numel(), _stream(device)))
+    return X, n_frames
+
+
+def speed_ratio(factor):
+    """(p, q) of a speed factor, p / q = Fraction(str(factor)): 0.9 is (9, 10) -- a longer, slower copy --, 1.1 is (11, 10)."""
+    f = fractions.Fraction(str(factor))
+    if f <= 0:
+        raise ValueError(f"speed factor {factor!r} must be positive")
+    return f.numerator, f.denominator
+
+
+_RESAMPLE_WORKSPACES = {}        # (reduced p, reduced q, num_zeros, rolloff, device) -> the prepared table workspace
+
+
+def resample(wave, n_samples, p, q, num_zeros=6, rolloff=0.99):
+    """Band-limited resampling of the rows of wave (B, Nmax) int16 or float32, lengths n_samples (B) int32, both on the device, by
+    out_rate / in_rate = q / p (astk_resample; the definition is tests/resample_model.py, parity with sox / Kaldi unpinned): (Y (B,
+    Mmax) float32, n_out (B) int32) with Mmax = ceil(Nmax q / p) and Y zero behind each row's n_out = ceil(n q / p).  Read at the
+    input's own rate, Y is the input at speed p / q (speed_ratio).  The prepared table is cached per (p, q, num_zeros, rolloff, device)."""
+    import math
+    import torch
+    stype = _sample_type(wave, "features.resample")
+    n_samples = _lengths(n_samples, wave, "features.resample")
+    p, q = int(p), int(q)
+    if p < 1 or q < 1:
+        raise ValueError(f"features.resample: p = {p}, q = {q}: both must be at least 1")
+    g = math.gcd(p, q)
+    p, q = p // g, q // g
+    device = wave.device
+    B, Nmax = wave.shape
+    Mmax = max(1, -((-Nmax * q) // p))
+    desc = _lib.ResampleDesc(B=B, Nmax=Nmax, Mmax=Mmax, sample_type=stype, p=p, q=q, num_zeros=int(num_zeros), rolloff=float(rolloff))
+    lib = _lib.load()
+    key = (p, q, int(num_zeros), float(rolloff), str(device))
+    ws = _RESAMPLE_WORKSPACES.get(key)
+    if ws is None:
+        nbytes = int(lib.astk_resample_workspace_bytes(C.byref(desc)))
+        if nbytes == 0:
+            _lib.check(-1)
+        ws = torch.empty(nbytes, dtype=torch.uint8, device=device)
+        _lib.check(lib.astk_resample_prepare(C.byref(desc), C.c_void_p(ws.data_ptr()), nbytes, _stream(device)))
+        _RESAMPLE_WORKSPACES[key] = ws
+    Y = torch.empty(B, Mmax, dtype=torch.float32, device=device)
+    n_out = torch.empty(B, dtype=torch.int32, device=device)
+    _lib.check(lib.astk_resample(C.byref(desc), C.c_void_p(wave.data_ptr()), C.c_void_p(n_samples.data_ptr()), C.c_void_p(Y.data_ptr()),
+                                 C.c_void_p(n_out.data_ptr()), None, C.c_void_p(ws.data_ptr()), ws.numel(), _stream(device)))
+    return Y, n_out
+
+
 def compute(waves, cfg, device, seed=0, offsets=None):
     """Features of a list of 1-D int16 (or float32) waveforms in one launch: (X (B, Fmax, D) float32, n_frames (B) int32), both on
     `device`, X zero behind each row's frames -- the (X, x_len) pair encode_rows and the CTC paths take.  offsets: the dither stream
-    offset of each row (default 0)."""
+    offset of each row (default 0).  Packs the host list and calls compute_device."""
     import torch
     device = torch.device(device)
     if len(waves) == 0:
@@ -165,26 +259,15 @@ def compute(waves, cfg, device, seed=0, offsets=None):
     else:
         raise ValueError("features.compute: waveforms must be int16 or float32 arrays")
     B = len(arrs)
-    Nmax = max(1, max(len(a) for a in arrs))
-    Fmax = max(1, max(cfg.frames(len(a)) for a in arrs))
+    Nmax = max(1, max(len(a) for a in arrs))                 # frames() is monotone: Fmax = frames(Nmax) is the longest row's count
     host = np.zeros((B, Nmax), dtype)
     for b, a in enumerate(arrs):
         host[b, :len(a)] = a
+    if offsets is not None and len(offsets) != B:
+        raise ValueError(f"features.compute: {len(offsets)} offsets for {B} waveforms")
     wave = torch.from_numpy(host).to(device)
     n_samples = torch.tensor([len(a) for a in arrs], dtype=torch.int32, device=device)
-    off = None
-    if offsets is not None:
-        if len(offsets) != B:
-            raise ValueError(f"features.compute: {len(offsets)} offsets for {B} waveforms")
-        off = torch.tensor([int(o) for o in offsets], dtype=torch.int64, device=device)
-    desc = cfg.descriptor(B, Nmax, Fmax, stype, seed, off.data_ptr() if off is not None else None)
-    ws = _workspace(cfg, device, desc)
-    X = torch.empty(B, Fmax, cfg.dim, dtype=torch.float32, device=device)
-    n_frames = torch.empty(B, dtype=torch.int32, device=device)
-    _lib.check(_lib.load().astk_speech_features(C.byref(desc), C.c_void_p(wave.data_ptr()), C.c_void_p(n_samples.data_ptr()),
-                                                C.c_void_p(X.data_ptr()), C.c_void_p(n_frames.data_ptr()), None,
-                                                C.c_void_p(ws.data_ptr()), ws.numel(), _stream(device)))
-    return X, n_frames
+    return compute_device(wave, n_samples, cfg, seed, offsets)
 
 
 def _cmvn_desc(X, G, norm_vars):

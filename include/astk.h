@@ -30,7 +30,7 @@
 extern "C" {
 #endif
 
-#define ASTK_VERSION 112
+#define ASTK_VERSION 113
 #define ASTK_MAX_CNN_LAYERS 4
 #define ASTK_MAX_RNN_LAYERS 8
 #define ASTK_MAX_ATTN 4
@@ -1086,6 +1086,51 @@ int astk_cmvn_accumulate(const astk_cmvn_desc* d, const float* feats, const int3
                          int32_t* n_bad, void* stream);
 int astk_cmvn_apply(const astk_cmvn_desc* d, const float* feats_in, float* feats_out, const int32_t* n_frames, const int32_t* group,
                     const double* stats, void* stream);
+/* ---------------------------------------------------------------- resampling and speed perturbation of waveforms
+ * Band-limited resampling by a rational ratio, out_rate / in_rate = q / p, with a Hann-windowed sinc: the operator in front of
+ * astk_speech_features for files of another rate, and -- read at the ORIGINAL rate -- a speed change by the factor p / q (0.9 is p = 9,
+ * q = 10: a longer, lower, slower copy).  Parity with sox / Kaldi is NOT pinned (Kaldi perturbs speed with sox, which does not exist
+ * here): the contract is the float64 model tests/resample_model.py.
+ *   wave       (B, Nmax) float32 or int16 (sample_type, ASTK_FEAT_SAMPLE_*); nothing behind a row's length is read
+ *   n_samples  int32 (B)
+ *   out        float32 (B, Mmax), zero at m >= n_out[b]
+ *   n_out      int32 (B): ceil(n_samples[b] q / p), or -1 for a bad row
+ *   n_bad      int32, may be NULL: the number of bad rows
+ * p and q are reduced by their gcd inside.  With Z = num_zeros, c = rolloff * min(1, q / p) and K = ceil(Z / c):
+ *   g(t) = c sinc(c t) cos^2(pi c t / (2 Z)) for |c t| < Z, else 0;  sinc(u) = sin(pi u) / (pi u), 1 at u = 0
+ *   y[m] = sum over k = -K+1 .. K of x[n0 + k] g(phi / q - k),  n0 = (m p) div q,  phi = (m p) mod q  (64-bit integers)
+ * x is 0 outside [0, n_samples[b]).  The sum runs in ascending k in float64 and is rounded once to float32.  No atomics: two runs give
+ * identical bytes.  A bad row -- n_samples outside [0, Nmax], or an output count above Mmax -- gets n_out = -1 and an all-zero row,
+ * reads nothing out of bounds and is counted in *n_bad.  Inputs are never written.
+ *   astk_resample_workspace_bytes  bytes of the table workspace (0 for a refused descriptor)
+ *   astk_resample_prepare          one small launch that fills the polyphase table (reduced q phases x 2K taps, float64, stored
+ *                                  [tap][phase]) on the device and a digest of the descriptor's table fields (reduced p and q,
+ *                                  num_zeros, rolloff) in the workspace head.  B, Nmax, Mmax and sample_type may differ between
+ *                                  prepare and the calls that use the workspace.
+ *   astk_resample                  one launch (two with n_bad)
+ * All three only enqueue.  The library remembers the digest of every workspace address it prepared (host side) and the kernel compares
+ * the digest in the workspace head again: a workspace that was overwritten since makes every row a bad row.
+ * Refused before any launch: a wrong struct_size; B, Nmax or Mmax < 1; p or q < 1; a reduced q above ASTK_RESAMPLE_MAX_PHASES; K above
+ * ASTK_RESAMPLE_MAX_HALF_TAPS; num_zeros < 1; rolloff outside (0, 1]; an unknown sample type; NULL buffers; a workspace that is too
+ * small, was never prepared, or was prepared for other table fields. */
+#define ASTK_RESAMPLE_MAX_PHASES 1024
+#define ASTK_RESAMPLE_MAX_HALF_TAPS 256
+#define ASTK_RESAMPLE_TILE 256     /* output samples per workgroup: tile t of a row covers m = 256 t .. 256 t + 255 */
+typedef struct {
+  size_t struct_size;      /* = sizeof(astk_resample_desc) */
+  int B;                   /* rows of the batch */
+  int Nmax;                /* row stride of wave, the longest waveform admitted */
+  int Mmax;                /* row stride of out, the longest output admitted */
+  int sample_type;         /* ASTK_FEAT_SAMPLE_* */
+  int p;                   /* out_rate / in_rate = q / p */
+  int q;
+  int num_zeros;           /* Z: zero crossings of the sinc on each side (6) */
+  double rolloff;          /* cut-off as a fraction of the narrower Nyquist (0.99) */
+} astk_resample_desc;
+size_t astk_resample_workspace_bytes(const astk_resample_desc* d);
+int astk_resample_prepare(const astk_resample_desc* d, void* ws, size_t ws_bytes, void* stream);
+int astk_resample(const astk_resample_desc* d, const void* wave, const int32_t* n_samples, float* out, int32_t* n_out, int32_t* n_bad,
+                  const void* ws, size_t ws_bytes, void* stream);
 /* One wavefront that keeps `stream` busy for `usec` microseconds (<= 100 000) and then increments *flag (may be NULL).  For probing
  * whether two streams really execute concurrently: HIP multiplexes streams onto a few hardware queues (GPU_MAX_HW_QUEUES, 4 by
  * default), and two streams that share one are serialised whatever their events say (ast_amd/seq2seq.py:_cu_streams). */
