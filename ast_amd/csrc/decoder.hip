@@ -424,9 +424,11 @@ struct WgradBatch {
   int n = 0;
   bool low = false;      // every product of this batch may run with fp16 operands under astk_set_low_precision_gemms(1) (K18 / K24)
   explicit WgradBatch(bool lowp_eligible = false) : low(lowp_eligible) {}
-  int add(float* dW, long ldw, int M, int N, const float* A, long lda, const float* Bm, long ldb, int rows, hipStream_t s) {
+  // (amax_a: the maximum of A, where the caller measured it -- common.h gemm_amax_many)
+  int add(float* dW, long ldw, int M, int N, const float* A, long lda, const float* Bm, long ldb, int rows, hipStream_t s,
+          const unsigned long long* amax_a = nullptr) {
     if (n == GEMM_GROUP_MAX) ASTK_TRY(flush(s));
-    list[n] = gemm_args(M, N, rows, mat(A, lda), mat(Bm, ldb), dW, ldw, nullptr, GEMM_ATOMIC, 1);
+    list[n] = with_amax_a(gemm_args(M, N, rows, mat(A, lda), mat(Bm, ldb), dW, ldw, nullptr, GEMM_ATOMIC, 1), amax_a);
     if (low) list[n] = lowp(list[n]);
     ++n;
     return 0;
@@ -889,7 +891,17 @@ int bwd_params(const DecBwdCall& b, const DecPlan& P, const DecRoute& r) {
   GemmWgCap cap(b.phase == ASTK_DEC_BWD_PARAMS ? b.d->side_wgs : 0);   // on its own stream this phase shares the CUs with the encoder's recurrence kernel
   // ---- what the persistent kernels left to this phase.  The embedding columns of d_x0 (only the embedding scatter reads them; K18's input
   // gradient): one batched product over all steps, for the wide loop and for the persistent loop's split d_x0 phase
-  const GemmArgs gx = lowp(gemm_args(S * B, E, 4 * H, mat(P.G[0], 4 * H), mat(prm->lstm[0].Wu, XI), P.DX0, XI));
+  // fp16-operand mode: the gradient operands of the eligible products -- dlogits (K24) and every cell's dz (K18; layer 0's also feeds gx)
+  // -- go in behind their measured scale: one maximum pass over all of them here (null handles outside that mode: nothing is launched).
+  // dlogits are 1 / B at most and about 1 / (B V) elsewhere, dz smaller still: cast as they are they sit on fp16's subnormals.
+  const unsigned long long* a_dz[ASTK_MAX_RNN_LAYERS + 1];      // [nl]: dlogits
+  {
+    AmaxMatrix am[ASTK_MAX_RNN_LAYERS + 1];
+    for (int l = 0; l < nl; ++l) am[l] = AmaxMatrix{low_precision_gemms() ? P.G[l] : nullptr, (long)S * B, 4L * H, 4 * H};
+    am[nl] = AmaxMatrix{low_precision_gemms() ? P.LOGITS : nullptr, (long)S * B, (long)Vp, V};
+    gemm_amax_many(am, nl + 1, a_dz, s);
+  }
+  const GemmArgs gx = with_amax_a(lowp(gemm_args(S * B, E, 4 * H, mat(P.G[0], 4 * H), mat(prm->lstm[0].Wu, XI), P.DX0, XI)), a_dz[0]);
   if (r.path == DEC_WIDE) ASTK_TRY(gemm_launch(GEMM_NN, gx, s));
   if (r.path == DEC_PERSIST) {
     // dq[s][b][:] = sum_t ds[s][b][t] enc[b][t][:]  (batched over b) -- only the weight gradients of attn_Wa need it
@@ -910,7 +922,7 @@ int bwd_params(const DecBwdCall& b, const DecPlan& P, const DecRoute& r) {
   // attention and context products stay f32-accurate.  (Without that mode both groups run exactly as one did.)
   WgradBatch wb, wbl(true);
   ColsumBatch cb;   // the bias gradients: one launch
-  ASTK_TRY(wbl.add(g->dWo, A, V, A, P.LOGITS, Vp, P.HT + (size_t)B * A, A, SB, s));
+  ASTK_TRY(wbl.add(g->dWo, A, V, A, P.LOGITS, Vp, P.HT + (size_t)B * A, A, SB, s, a_dz[nl]));
   ASTK_TRY(cb.add(g->dbo, P.LOGITS, Vp, SB, V, s));
   ASTK_TRY(wb.add(g->dWc, CW, A, CW, P.DPRE, A, P.CVH, CW, SB, s));
   ASTK_TRY(cb.add(g->dbc, P.DPRE, A, SB, A, s));
@@ -928,8 +940,8 @@ int bwd_params(const DecBwdCall& b, const DecPlan& P, const DecRoute& r) {
     if (l == 0) { xin = P.X0; ldx = XI; }
     else if (b.rnn_masks || P.ln) { xin = P.HD[l - 1]; ldx = H; }       // (with LayerNorm the layer's input is always the normalised copy)
     else { xin = P.HR[l - 1] + bh; ldx = H; }
-    ASTK_TRY(wbl.add(g->lstm[l].dWu, in, 4 * H, in, P.G[l], 4 * H, xin, ldx, SB, s));
-    ASTK_TRY(wbl.add(g->lstm[l].dWl, H, 4 * H, H, P.G[l], 4 * H, P.HR[l], H, SB, s));
+    ASTK_TRY(wbl.add(g->lstm[l].dWu, in, 4 * H, in, P.G[l], 4 * H, xin, ldx, SB, s, a_dz[l]));
+    ASTK_TRY(wbl.add(g->lstm[l].dWl, H, 4 * H, H, P.G[l], 4 * H, P.HR[l], H, SB, s, a_dz[l]));
     ASTK_TRY(cb.add(g->lstm[l].db, P.G[l], 4 * H, SB, 4 * H, s));
   }
   ASTK_TRY(cb.flush(s));

@@ -333,8 +333,11 @@ struct Stager {
     for (int p = 0; p < NP; ++p) {
       const int off = RK ? (a >> 1) * sp_hs(TL) + (NP * b + p) * 16 + (a & 1) * 8 : (b + RP * p) * sp_rs(TL) + a * 8;
       if constexpr (PREC == PREC_F16) {
-        // (behind the operand's power-of-two scale when its caller measured it -- the backward products' dY / dz would otherwise flush
-        //  to zero below 6e-8 and overflow above 65504; scale 1 for operands nobody measured: weights, forward activations)
+        // (behind the operand's power-of-two scale when its caller measured it -- a gradient operand would otherwise go subnormal below
+        //  6.1e-5, flush to zero below 3e-8 and overflow above 65504.  Measured, under every scheme (gemm_amax_many / gemm_amax_reserve
+        //  serve this mode too): the CNN's activations, re-packed weights and dY by the kernels that write them; the encoder's frames,
+        //  layer-0 weights and every cell's dz; the decoder's dlogits and cells' dz.  Scale 1 for operands nobody measures: the
+        //  decoder's weights and saved activations h~, x, h -- all inside fp16's range)
         const f16x2 lo2 = {(_Float16)(r[p].x * scl), (_Float16)(r[p].y * scl)}, hi2 = {(_Float16)(r[p].z * scl), (_Float16)(r[p].w * scl)};
         *reinterpret_cast<uint2*>(S + off) = make_uint2(__builtin_bit_cast(unsigned, lo2), __builtin_bit_cast(unsigned, hi2));
       } else if constexpr (PREC == PREC_F16X2) {
@@ -1782,10 +1785,14 @@ int gemm_launch_group(int layout, const GemmArgs* list, int n, hipStream_t s) {
 
 int gemm_launch(int layout, const GemmArgs& g, hipStream_t s) { return gemm_launch_group(layout, &g, 1, s); }
 
+// Who reads a caller's maxima: the fp16x2 scheme (every product), and the fp16-operand mode under ANY scheme -- its eligible launches
+// scale the operands that come with a handle and cast the others as they are (Stager::store_split), and a gradient operand cast as it
+// is (dz, dlogits: 1e-5 ... 1e-9 once the loss is divided by the batch) lands on fp16's subnormals or on zero.
+static bool amax_wanted() { return default_prec() == PREC_F16X2 || low_precision_gemms() != 0; }
 void gemm_amax_many(const AmaxMatrix* m, int n, const unsigned long long** out, hipStream_t s) {
   for (int i = 0; i < n; ++i) out[i] = nullptr;
   unsigned long long* ring = amax_ring();
-  if (default_prec() != PREC_F16X2 || !ring) return;
+  if (!amax_wanted() || !ring) return;
   ProfScope prof(PROF_GEMM, s, 0.0);       // part of the GEMMs' cost: timed with them (no flops of its own)
   AmaxJobs J;
   memset(&J, 0, sizeof(J));
@@ -1807,7 +1814,7 @@ void gemm_amax_many(const AmaxMatrix* m, int n, const unsigned long long** out, 
 
 void gemm_amax_reserve(int n, unsigned long long** slots, unsigned* gen, hipStream_t s) {
   unsigned long long* ring = amax_ring();
-  const bool on = default_prec() == PREC_F16X2 && ring != nullptr;
+  const bool on = amax_wanted() && ring != nullptr;
   *gen = on ? next_amax_gen(s) : 0;
   for (int i = 0; i < n; ++i) slots[i] = on ? amax_take_handle(ring) : nullptr;
 }
@@ -1815,7 +1822,7 @@ void gemm_amax_reserve(int n, unsigned long long** slots, unsigned* gen, hipStre
 // constant maxima (bounded matrices): 8 slots of 16 words; word 0 of a slot holds the bound, the others stay 0
 __device__ unsigned long long g_amax_bounds[8 * AMAX_SLOT_WORDS];
 const unsigned long long* gemm_amax_bound(float bound, hipStream_t s) {
-  if (default_prec() != PREC_F16X2 && low_precision_gemms() == 0) return nullptr;
+  if (!amax_wanted()) return nullptr;
   static std::mutex mu;
   static float cached[16][8];          // per device: the bound each slot holds (0 = free)
   int dev = 0;
@@ -1877,6 +1884,43 @@ extern "C" int astk_debug_gemm_group(int layout, int n, const int* M, const int*
   }
   if (forward) { GemmForwardScope fs; return gemm_launch_group(layout, g, n, (hipStream_t)stream); }
   return gemm_launch_group(layout, g, n, (hipStream_t)stream);
+}
+// libastk_test.so only: astk_debug_gemm_group with everything an op can set per product -- mode, batch with strides, leading dimensions, the
+// fp16-operand mark -- and the operands' maxima measured in front of the launch the way an op measures them (gemm_amax_many; measure[i]
+// bit 0: A, bit 1: B), under PrecScope(precision, gemm_operands): the fp16-operand kernel alone, against a model of its arithmetic.
+extern "C" int astk_debug_gemm_group_lowp(int layout, int n, const int* M, const int* N, const int* K, const int* batch, const int* mode, const int* lowp,
+                                          const int* measure, const float* const* A, const long* lda, const long* sA, const float* const* B,
+                                          const long* ldb, const long* sB, float* const* C, const long* ldc, const long* sC, int precision,
+                                          int gemm_operands, void* stream) {
+  using namespace astk;
+  ASTK_CHECK(n >= 1 && n <= GEMM_GROUP_MAX && layout >= GEMM_NT && layout <= GEMM_TN, "debug_gemm_group_lowp: bad arguments");
+  hipStream_t s = (hipStream_t)stream;
+  PrecScope prec_scope(precision, gemm_operands);
+  GemmArgs g[GEMM_GROUP_MAX];
+  AmaxMatrix am[2 * GEMM_GROUP_MAX];
+  for (int i = 0; i < n; ++i) {
+    // stored rows x inner extent of either operand
+    const long rowsA = layout == GEMM_TN ? K[i] : M[i], innerA = layout == GEMM_TN ? M[i] : K[i];
+    const long rowsB = layout == GEMM_NT ? N[i] : K[i], innerB = layout == GEMM_NT ? K[i] : N[i];
+    ASTK_CHECK(M[i] > 0 && N[i] > 0 && K[i] > 0 && batch[i] >= 1 && mode[i] >= GEMM_STORE && mode[i] <= GEMM_ATOMIC && A[i] && B[i] && C[i] &&
+                   lda[i] >= innerA && ldb[i] >= innerB && ldc[i] >= N[i],
+               "debug_gemm_group_lowp: product %d: bad shape, mode or leading dimension", i);
+    ASTK_CHECK(batch[i] == 1 || (sA[i] >= rowsA * lda[i] && sB[i] >= rowsB * ldb[i] && sC[i] >= (long)M[i] * ldc[i]),
+               "debug_gemm_group_lowp: product %d: batch slices overlap", i);
+    g[i] = gemm_args(M[i], N[i], K[i], mat(A[i], lda[i]), mat(B[i], ldb[i]), C[i], ldc[i], nullptr, mode[i]);
+    g[i].batch = batch[i];
+    g[i].sA = sA[i]; g[i].sB = sB[i]; g[i].sC = sC[i];
+    g[i].lowp = lowp[i] != 0;
+    // (a batched operand is measured as one matrix: its slices must follow each other without a gap)
+    ASTK_CHECK(batch[i] == 1 || ((!(measure[i] & 1) || sA[i] == rowsA * lda[i]) && (!(measure[i] & 2) || sB[i] == rowsB * ldb[i])),
+               "debug_gemm_group_lowp: product %d: a measured batched operand must be dense", i);
+    am[2 * i] = AmaxMatrix{(measure[i] & 1) ? A[i] : nullptr, rowsA * batch[i], lda[i], (int)innerA};
+    am[2 * i + 1] = AmaxMatrix{(measure[i] & 2) ? B[i] : nullptr, rowsB * batch[i], ldb[i], (int)innerB};
+  }
+  const unsigned long long* h[2 * GEMM_GROUP_MAX];
+  gemm_amax_many(am, 2 * n, h, s);
+  for (int i = 0; i < n; ++i) g[i] = with_amax_b(with_amax_a(g[i], h[2 * i]), h[2 * i + 1]);
+  return gemm_launch_group(layout, g, n, s);
 }
 // libastk_test.so only: what ONE grouped launch of n dense row-major products would do, as text (one gemm.log line per product, "" for a
 // group with nothing to launch) in out[0, out_bytes).  Opens the scopes an op would open, reads the state of the call and runs gemm_plan

@@ -67,9 +67,12 @@ int astk_gemm_f32_ex(int layout, int M, int N, int K,
 
 /* BASELINE configs[4] ("fp16 MFMA GEMMs"): mode 1 lets the batched products of the CNN layers >= 1 (K6), of the encoder's layer-0
  * input projection (K9) -- forward and backward -- and of the decoder LSTMs' and the output layer's backward (K18, K24: their weight
- * gradients over all steps, the embedding columns of the input gradient) run with operands rounded to fp16 behind the operand's
- * power-of-two scale where its caller measured it (one v_mfma_f32_32x32x16_f16 per tile, f32 accumulation) instead of the f32-accurate
- * split (below).  The per-step products of K18 / K24 live inside the latency-bound decoder loop kernels and stay on f32 MFMAs.  Reduced precision: the 1e-4 fp32 parity gate does not apply in
+ * gradients over all steps, the embedding columns of the input gradient) run with operands rounded to fp16 (one
+ * v_mfma_f32_32x32x16_f16 per tile, f32 accumulation) instead of the f32-accurate split (below).  Whatever the `precision`, every
+ * gradient operand (the CNN's dY, the encoder cells' dz, the decoder's dlogits and dz) and the CNN's and encoder's activations, frames
+ * and weights are rounded behind a power-of-two scale taken from the operand's measured absolute maximum (the maximum lands in
+ * [2^14, 2^15): fp16's subnormal floor sits 2^-39 below it); the decoder's weights and saved activations, all inside fp16's range, are
+ * cast as they are.  A result is the product of the rounded operands up to f32 summation (tests/lowp_model.py).  The per-step products of K18 / K24 live inside the latency-bound decoder loop kernels and stay on f32 MFMAs.  Reduced precision: the 1e-4 fp32 parity gate does not apply in
  * this mode (SURVEY.md 8d asks for the loss drift instead: tests/test_gpu_model.py).  Process-wide DEFAULT for descriptors whose
  * gemm_operands field is ASTK_OPERANDS_DEFAULT; 0 (default) = off. */
 int astk_set_low_precision_gemms(int mode);
@@ -110,6 +113,14 @@ int astk_debug_set_amax_generation(unsigned gen);
  * issues it -- under the forward ops' two-contributor rule when `forward` is set -- for shapes no op of the step produces. */
 int astk_debug_gemm_group(int layout, int n, const int* M, const int* N, const int* K, const float* const* A, const float* const* B,
                           float* const* C, int forward, int precision, void* stream);
+/* Test hook (libastk_test.so only): astk_debug_gemm_group plus what an op sets per product -- `mode` (0 store / 1 accumulate / 2 atomic),
+ * `batch` with the strides sA / sB / sC, the leading dimensions, the fp16-operand mark `lowp` -- and `measure` (bit 0: A, bit 1: B): the
+ * operand's absolute maximum is taken in front of the launch and handed to it, as an op does for the operands it measures.  The launch
+ * runs under the descriptor fields `precision` / `gemm_operands`.  Not a forward launch. */
+int astk_debug_gemm_group_lowp(int layout, int n, const int* M, const int* N, const int* K, const int* batch, const int* mode, const int* lowp,
+                               const int* measure, const float* const* A, const long* lda, const long* sA, const float* const* B,
+                               const long* ldb, const long* sB, float* const* C, const long* ldc, const long* sC, int precision,
+                               int gemm_operands, void* stream);
 /* Test hook (libastk_test.so only): what ONE grouped launch of n dense row-major products (leading dimensions as in astk_debug_gemm_group;
  * per product M, N, K, batch, mode 0 store / 1 accumulate / 2 atomic, the fp16-operand mark `lowp`, and `given` = the caller supplies both
  * operands' maxima) WOULD do under `forward`, the descriptor fields `precision` / `gemm_operands` / `deterministic`, a workgroup cap

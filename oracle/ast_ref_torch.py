@@ -13,13 +13,18 @@ import torch
 import torch.nn.functional as TF
 
 
-def cnn_torch(cfg, P, X, noise=None, bn_eps=2e-5):
-    """seq2seq.py:158-180 -> (T'',B,C*F') with feature index c*F'+f."""
+def cnn_torch(cfg, P, X, noise=None, bn_eps=2e-5, conv=None):
+    """seq2seq.py:158-180 -> (T'',B,C*F') with feature index c*F'+f.
+    conv(i, h, W, stride, padding): replaces layer i's convolution -- the library marks the window products of the layers >= 1 lowp(...)
+    (tests/lowp_model.py); default: conv2d."""
     if noise is not None:
         X = X * noise
     h = X.unsqueeze(1)                                        # (B,1,T,D)
     for i, l in enumerate(cfg["cnn_config"]["cnn_layers"]):
-        h = TF.conv2d(h, P[f"CNN_{i}/W"], stride=tuple(l["stride"]), padding=tuple(l["pad"]))
+        if conv is None:
+            h = TF.conv2d(h, P[f"CNN_{i}/W"], stride=tuple(l["stride"]), padding=tuple(l["pad"]))
+        else:
+            h = conv(i, h, P[f"CNN_{i}/W"], tuple(l["stride"]), tuple(l["pad"]))
         if "cnn_pool" in cfg["cnn_config"]:                     # old path, enc_dec.py:444-456: max_pooling_nd, stride = window, cover_all
             kt, kf = cfg["cnn_config"]["cnn_pool"][i]
             k = (h.shape[2] if kt == -1 else max(kt, 1), h.shape[3] if kf == -1 else max(kf, 1))
@@ -31,12 +36,12 @@ def cnn_torch(cfg, P, X, noise=None, bn_eps=2e-5):
     return h.permute(2, 0, 1, 3).reshape(T2, B, C * F2)
 
 
-def _lstm_run(x_seq, Wu, b, Wl, masks=None):
+def _lstm_run(x_seq, Wu, b, Wl, masks=None, proj=None):
     """x_seq (n,B,in) in consumption order.  Chainer interleaved gates (A1): column 4j+k, k=a,i,f,o.
-    Returns dropped outputs per step and the final un-dropped (c,h)."""
+    Returns dropped outputs per step and the final un-dropped (c,h).  proj(x, W): the batched upward product x W^T (default: exact)."""
     n, B, _ = x_seq.shape
     hdim = Wl.shape[1]
-    zx = x_seq @ Wu.t() + b                                   # batched upward
+    zx = (x_seq @ Wu.t() if proj is None else proj(x_seq, Wu)) + b   # batched upward
     h = None
     c = torch.zeros(B, hdim, dtype=x_seq.dtype)
     outs = []
@@ -50,9 +55,11 @@ def _lstm_run(x_seq, Wu, b, Wl, masks=None):
     return torch.stack(outs, 0), c, h
 
 
-def encoder_torch(cfg, P, feats, masks=None):
+def encoder_torch(cfg, P, feats, masks=None, proj0=None):
     """seq2seq.py:205-242.  feats (T'',B,in).  masks: None or array (2, n_layers, T'', B, h) indexed by loop step.
-    Returns enc_states (B,T'',H) and the per-layer finals cT,hT as (2,n_layers,B,h)."""
+    Returns enc_states (B,T'',H) and the per-layer finals cT,hT as (2,n_layers,B,h).
+    proj0(x, W): replaces the layer-0 input projection x W^T of both directions -- the encoder's products the library marks lowp(...)
+    (tests/lowp_model.py); default: the exact product."""
     rc = cfg["rnn_config"]
     T2 = feats.shape[0]
     nl = rc["enc_layers"]
@@ -62,8 +69,8 @@ def encoder_torch(cfg, P, feats, masks=None):
     for k in range(nl):
         mf = masks[0][k] if masks is not None else None
         mr = masks[1][k] if masks is not None else None
-        xs_f, cf, hf = _lstm_run(xs_f, P[f"L{k}_enc/upward/W"], P[f"L{k}_enc/upward/b"], P[f"L{k}_enc/lateral/W"], mf)
-        xs_r, cr, hr = _lstm_run(xs_r, P[f"L{k}_rev_enc/upward/W"], P[f"L{k}_rev_enc/upward/b"], P[f"L{k}_rev_enc/lateral/W"], mr)
+        xs_f, cf, hf = _lstm_run(xs_f, P[f"L{k}_enc/upward/W"], P[f"L{k}_enc/upward/b"], P[f"L{k}_enc/lateral/W"], mf, proj0 if k == 0 else None)
+        xs_r, cr, hr = _lstm_run(xs_r, P[f"L{k}_rev_enc/upward/W"], P[f"L{k}_rev_enc/upward/b"], P[f"L{k}_rev_enc/lateral/W"], mr, proj0 if k == 0 else None)
         cT[0].append(cf); cT[1].append(cr); hT[0].append(hf); hT[1].append(hr)
     enc = torch.cat([xs_f, torch.flip(xs_r, [0])], 2).transpose(0, 1)   # (B,T'',H)
     cT = torch.stack([torch.stack(cT[0]), torch.stack(cT[1])])
@@ -71,9 +78,15 @@ def encoder_torch(cfg, P, feats, masks=None):
     return enc, cT, hT
 
 
-def decoder_torch(cfg, P, enc, c0, h0, y, use_truth, V, emb_mask=None, rnn_masks=None):
+def decoder_torch(cfg, P, enc, c0, h0, y, use_truth, V, emb_mask=None, rnn_masks=None, tap=None):
     """seq2seq.py:361-473.  c0,h0 (n_layers,B,H); emb_mask (S,B,E); rnn_masks (n_layers,S,B,H).
-    Returns loss, preds (S,B)."""
+    Returns loss, preds (S,B).
+    tap(name, t, *operands) -> t: an identity on t that lets a caller see, per step, the operands and the incoming gradient of the
+    products the library batches over all steps and marks lowp(...) (tests/lowp_model.py DecoderTaps): "embed" (the embedding rows, with
+    the tokens and the mask), "L{k}" (a cell's pre-activations, with its input and previous output), "out" (the logits, with h~).
+    Default: nothing is tapped."""
+    if tap is None:
+        tap = lambda name, t, *operands: t
     rc = cfg["rnn_config"]
     dt = enc.dtype
     B = enc.shape[0]
@@ -91,12 +104,13 @@ def decoder_torch(cfg, P, enc, c0, h0, y, use_truth, V, emb_mask=None, rnn_masks
         if use_truth[s]:
             dec_in = yT[s]
         e = P["embed_dec/W"][dec_in]
+        e = tap("embed", e, dec_in, emb_mask[s] if emb_mask is not None else torch.ones_like(e))
         if emb_mask is not None:
             e = e * emb_mask[s]
         x = torch.cat([e, ht], 1)
         for k in range(nd):
             Wu, b, Wl = P[f"L{k}_dec/upward/W"], P[f"L{k}_dec/upward/b"], P[f"L{k}_dec/lateral/W"]
-            z = (x @ Wu.t() + b + hs[k] @ Wl.t()).view(B, -1, 4)
+            z = tap(f"L{k}", x @ Wu.t() + b + hs[k] @ Wl.t(), x, hs[k]).view(B, -1, 4)
             a, i, f, o = torch.tanh(z[..., 0]), torch.sigmoid(z[..., 1]), torch.sigmoid(z[..., 2]), torch.sigmoid(z[..., 3])
             cs[k] = a * i + f * cs[k]
             hs[k] = o * torch.tanh(cs[k])
@@ -105,7 +119,7 @@ def decoder_torch(cfg, P, enc, c0, h0, y, use_truth, V, emb_mask=None, rnn_masks
         alpha = torch.softmax(torch.einsum("bth,bh->bt", enc, q), dim=1)
         cv = torch.einsum("bth,bt->bh", enc, alpha)
         ht = torch.tanh(torch.cat([cv, x], 1) @ P["context/W"].t() + P["context/b"])
-        logits = ht @ P["out/W"].t() + P["out/b"]
+        logits = tap("out", ht @ P["out/W"].t() + P["out/b"], ht)
         dec_in = logits.argmax(1)
         preds.append(dec_in)
         loss = loss + TF.cross_entropy(logits, yT[s + 1], weight=w, reduction="sum") / B   # Q6: /B, PAD rows weigh 0

@@ -49,9 +49,10 @@ def dec_draws(B, L, T, H, E, A, V, nl, masks, seed=0, enc_gain=1.0, out_gain=1.0
 
 
 # ------------------------------------------------------------------ encoder stacks
-def lstm_draws(T, B, in_dim, h, nl, masks, bias_gain=1.0, x_gain=1.0):
-    """Parameters, input, masks and the three upstream gradients (enc_states (B, T, 2h); cT, hT (2, nl, B, h)) in the operator test's draw order."""
-    rng = np.random.default_rng(T + B)
+def lstm_draws(T, B, in_dim, h, nl, masks, bias_gain=1.0, x_gain=1.0, seed=None):
+    """Parameters, input, masks and the three upstream gradients (enc_states (B, T, 2h); cT, hT (2, nl, B, h)) in the operator test's draw order.
+    seed: default T + B, the operator test's."""
+    rng = np.random.default_rng(T + B if seed is None else seed)
     P, names = {}, []
     for pat in ("L{}_enc", "L{}_rev_enc"):
         n_in = in_dim
