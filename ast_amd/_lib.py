@@ -153,6 +153,15 @@ class PairStatsDesc(_Sized, C.Structure):
     _fields_ = [("struct_size", C.c_size_t), ("S", C.c_int), ("Lmax", C.c_int), ("P", C.c_int)]
 
 
+RISK_MAX_LIST = 64      # astk.h ASTK_RISK_MAX_LIST: the longest candidate list of astk_risk_weights
+RISK_COSTS = {"bleu": 0, "edit": 1}      # astk.h ASTK_RISK_COST_*
+
+
+class RiskDesc(_Sized, C.Structure):
+    _fields_ = [("struct_size", C.c_size_t), ("U", C.c_int), ("R", C.c_int), ("cost", C.c_int), ("alpha", C.c_float),
+                ("risk_scale", C.c_float), ("ref_weight", C.c_float)]
+
+
 # astk.h ASTK_FEAT_*: kinds, windows, sample types and bounds of astk_speech_features
 FEAT_MFCC, FEAT_FBANK = 0, 1
 FEAT_WINDOWS = {"povey": 0, "hamming": 1, "hanning": 2, "rectangular": 3}
@@ -253,6 +262,8 @@ SIGNATURES = {
                                    _VP, _SZ, _VP]),
     "astk_decoder_fwd_ex": (C.c_int, [C.POINTER(DecoderDesc), C.POINTER(DecoderParams), _VP, _VP, _VP, _VP, _VP, _VP, _VP, _VP, _VP, _VP, _VP,
                                       _VP, _SZ, _VP]),
+    "astk_decoder_fwd_w": (C.c_int, [C.POINTER(DecoderDesc), C.POINTER(DecoderParams), _VP, _VP, _VP, _VP, _VP, _VP, _VP, _VP, _VP, _VP, _VP,
+                                     _VP, _VP, _SZ, _VP]),
     "astk_decoder_bwd_phase_ex": (C.c_int, [C.POINTER(DecoderDesc), C.POINTER(DecoderParams), C.POINTER(DecoderGrads), _VP, _VP, _VP, _VP,
                                             _VP, _VP, _VP, _VP, _VP, _VP, _VP, _SZ, _I, _VP]),
     "astk_layernorm_fwd": (C.c_int, [_I, _I, _VP, _L, _VP, _VP, _F, _VP, _L, _VP]),
@@ -307,6 +318,7 @@ SIGNATURES = {
     "astk_spin": (C.c_int, [C.c_uint, _VP, _VP]),
     "astk_softmax_ce_fwd": (C.c_int, [_I, _I, _L, _VP, _VP, _L, _VP, _F, _VP, _VP, _VP]),
     "astk_softmax_ce_fwd_ex": (C.c_int, [_I, _I, _L, _VP, _VP, _L, _VP, _F, _F, _VP, _VP, _VP]),
+    "astk_softmax_ce_fwd_w": (C.c_int, [_I, _I, _L, _VP, _VP, _L, _VP, _VP, _F, _F, _VP, _VP, _VP]),
     "astk_grad_sqnorm": (C.c_int, [_VP, _VP, _F, _SZ, _VP, _VP]),
     "astk_decay_clip_amsgrad_step": (C.c_int, [_VP, _VP, _VP, _VP, _VP, _SZ, _F, _F, _VP, _F, C.c_double, C.c_double, _F, _I, _VP]),
     "astk_decay_clip_sgd_step": (C.c_int, [_VP, _VP, _SZ, _F, _F, _VP, _F, _VP]),
@@ -333,6 +345,7 @@ SIGNATURES = {
     "astk_ctc_beam_workspace_bytes": (_SZ, [C.POINTER(CtcBeamDesc)]),
     "astk_ctc_beam": (C.c_int, [C.POINTER(CtcBeamDesc), _VP, _VP, _VP, _VP, _VP, _VP, _SZ, _VP]),
     "astk_pair_stats": (C.c_int, [C.POINTER(PairStatsDesc), _VP, _VP, _VP, _VP, _VP, _VP]),
+    "astk_risk_weights": (C.c_int, [C.POINTER(RiskDesc), _VP, _VP, _VP, _VP, _VP, _VP, _VP, _VP, _VP, _VP, _VP]),
     "astk_speech_features_workspace_bytes": (_SZ, [C.POINTER(SpeechFeaturesDesc)]),
     "astk_speech_features_prepare": (C.c_int, [C.POINTER(SpeechFeaturesDesc), _VP, _SZ, _VP]),
     "astk_speech_features": (C.c_int, [C.POINTER(SpeechFeaturesDesc), _VP, _VP, _VP, _VP, _VP, _VP, _SZ, _VP]),

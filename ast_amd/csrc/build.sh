@@ -8,7 +8,7 @@
 set -e
 cd "$(dirname "$0")"
 FLAGS="--offload-arch=gfx950 -O3 -std=c++17 -fPIC -Wno-unused-result $ASTK_EXTRA_FLAGS"
-SRCS="util gemm rowgemm attn conv norm lstm lstm_persist decoder decoder_persist decoder_wide beam ctc ctc_prefix ctc_align ctc_beam pairs features resample"
+SRCS="util gemm rowgemm attn conv norm lstm lstm_persist decoder decoder_persist decoder_wide beam ctc ctc_prefix ctc_align ctc_beam pairs features resample risk"
 HOOKED="gemm rowgemm conv lstm_persist decoder_persist ctc_prefix"        # the translation units with #ifdef ASTK_TEST_HOOKS sections
 mkdir -p ../_obj ../_obj/test
 pids=()

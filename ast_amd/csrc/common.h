@@ -570,7 +570,7 @@ constexpr float LN_EPS = 1e-6f;        // L.LayerNormalization's default eps
 
 // ---- decoder helpers (decoder.hip)
 int softmax_ce_launch(int B, int V, long ld, float* logits, const int32_t* targets, long t_stride, const float* cw,
-                      float inv_count, float eps, float* loss_rows, int32_t* argmax, hipStream_t s);
+                      float inv_count, float eps, float* loss_rows, int32_t* argmax, hipStream_t s, const float* row_weight = nullptr);
 
 
 // ---- column-reduction skeleton shared by the bias-gradient and BatchNorm statistics kernels.

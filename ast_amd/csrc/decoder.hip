@@ -298,10 +298,12 @@ __global__ void k_embed_bwd_det(float* __restrict__ d_embed, const int32_t* __re
 // eps > 0: label smoothing (astk_decoder_desc.label_smoothing).  The uniform term LSE - mean(x) is formed as
 // log(se) - mean(x - mx) from the deviations the sum of exponentials reads anyway (all <= 0: no cancellation, whatever the offset of the
 // row); eps == 0 runs the arithmetic this kernel always had.
+// rw: per-row weights (astk_decoder_fwd_w / astk_softmax_ce_fwd_w), one per batch row of a step, or null: a factor
+// on the class weight, so on the loss row and on the gradient row alike; null runs the arithmetic without it.
 __global__ __launch_bounds__(256) void k_softmax_ce(int V, long ld, float* logits, const int32_t* __restrict__ targets,
                                                     long t_stride, int rows_per_step, const float* __restrict__ cw, float inv_count, float eps,
                                                     float* __restrict__ loss_rows, int32_t* __restrict__ argmax, int argmax_only,
-                                                    const int32_t* __restrict__ fed_flags, int n_steps) {
+                                                    const int32_t* __restrict__ fed_flags, int n_steps, const float* __restrict__ rw) {
   __shared__ float sv[4], sd[4];
   __shared__ int si[4];
   const int b = blockIdx.x;
@@ -346,7 +348,8 @@ __global__ __launch_bounds__(256) void k_softmax_ce(int V, long ld, float* logit
   int t = targets[(long)brow * t_stride + step];
   const bool ignore = t < 0;                      // ignore_label = -1 never occurs on this path (PAD is 0)
   t = t < 0 ? 0 : (t >= V ? V - 1 : t);
-  const float w = ignore ? 0.f : (cw ? cw[t] : 1.f);
+  float w = ignore ? 0.f : (cw ? cw[t] : 1.f);
+  if (rw) w *= rw[brow];
   // The target's logit has to be READ before any thread overwrites the row with the gradient below.  It used to be an ordinary load in
   // front of the barrier whose only use sat behind it; with `logits` declared __restrict__ the compiler was free to sink the load to
   // that use, i.e. behind the barrier, where thread (t % 256) may already have stored the gradient: one loss row in a few thousand
@@ -559,12 +562,13 @@ int step_fwd(const DecPlan& P, const astk_decoder_params* prm, const float* enc,
   return rowgemm_launch(a, s);
 }
 
-// ---- forward.  astk_decoder_fwd_ex validates, routes and calls one of fwd_split, fwd_persist, fwd_wide, fwd_steps.
+// ---- forward.  astk_decoder_fwd_w validates, routes and calls one of fwd_split, fwd_persist, fwd_wide, fwd_steps.
 struct DecFwdCall {
   const astk_decoder_desc* d; const astk_decoder_params* prm;
   const float *enc, *c0, *h0; const int32_t *y, *use_truth;
   const float *emb_mask, *rnn_masks, *out_mask;
   const int32_t *targets, *tgt;      // the caller's class ids or null; tgt = targets ? targets : y (scored at step s: column s + 1)
+  const float* row_weight;           // (B) per-row loss weights or null (astk_decoder_fwd_w)
   float* loss; int32_t* pred;
   hipStream_t s;
 };
@@ -580,9 +584,9 @@ int fwd_split(const DecFwdCall& f, const SplitPlan& sp) {
     ASTK_TRY(copy2d_f32(sp.h0[i], (long)b * H, f.h0 + (size_t)off * H, (long)B * H, nl, b * H, b * H, f.s));
     if (f.emb_mask) ASTK_TRY(copy2d_f32(sp.emb[i], (long)b * E, f.emb_mask + (size_t)off * E, (long)B * E, S, b * E, b * E, f.s));
     if (f.rnn_masks) ASTK_TRY(copy2d_f32(sp.rnn[i], (long)b * H, f.rnn_masks + (size_t)off * H, (long)B * H, nl * S, b * H, b * H, f.s));
-    ASTK_TRY(astk_decoder_fwd_ex(&sp.sub[i], f.prm, f.enc + (size_t)off * d->T * H, sp.c0[i], sp.h0[i], f.y + (size_t)off * d->L, f.use_truth,
+    ASTK_TRY(astk_decoder_fwd_w(&sp.sub[i], f.prm, f.enc + (size_t)off * d->T * H, sp.c0[i], sp.h0[i], f.y + (size_t)off * d->L, f.use_truth,
                                  f.emb_mask ? sp.emb[i] : nullptr, f.rnn_masks ? sp.rnn[i] : nullptr, nullptr,
-                                 f.targets ? f.targets + (size_t)off * d->L : nullptr, sp.loss2 + i, f.pred ? sp.pred[i] : nullptr, sp.ws[i], sp.wsb[i], f.s));
+                                 f.targets ? f.targets + (size_t)off * d->L : nullptr, f.row_weight ? f.row_weight + off : nullptr, sp.loss2 + i, f.pred ? sp.pred[i] : nullptr, sp.ws[i], sp.wsb[i], f.s));
     if (f.pred) ASTK_TRY(copy2d_f32((float*)f.pred + off, B, (const float*)sp.pred[i], b, S, b, b, f.s));      // (S, b) -> columns of (S, B); a bit copy
   }
   return 0;
@@ -591,7 +595,7 @@ int fwd_split(const DecFwdCall& f, const SplitPlan& sp) {
 // the persistent loop: ONE launch (and its fill), including the loss sum, the predictions and the status snapshot
 int fwd_persist(const DecFwdCall& f, const DecPlan& P) {
   return decoder_persist_fwd_launch(f.d, f.prm, f.enc, f.y, f.tgt, f.use_truth, f.emb_mask, f.rnn_masks, persist_fwd_buffers(P, f.c0, f.h0), f.loss,
-                                    f.pred, f.s);
+                                    f.pred, f.s, f.row_weight);
 }
 
 // what the wide and the per-launch loop need in front: initial states and zero attention vector (seq2seq.py:318-333, :420) in one fill
@@ -619,7 +623,7 @@ int fwd_score_all(const DecFwdCall& f, const DecPlan& P) {
   ASTK_TRY(gemm_launch(GEMM_NT, gemm_args(S * B, V, A, mat(P.HT + (size_t)B * A, A), mat(f.prm->Wo, A), P.LOGITS, P.Vp, f.prm->bo), f.s));
   if (f.out_mask) ASTK_TRY(mul_rows_launch(P.LOGITS, P.Vp, f.out_mask, V, S * B, V, f.s));
   hipLaunchKernelGGL(k_softmax_ce, dim3(S * B), dim3(256), 0, f.s, V, (long)P.Vp, P.LOGITS, f.tgt + 1, (long)P.L, B, f.prm->class_weight, inv_count,
-                     f.d->label_smoothing, P.LOSSROWS, P.PRED, 0, f.use_truth, S);
+                     f.d->label_smoothing, P.LOSSROWS, P.PRED, 0, f.use_truth, S, f.row_weight);
   ASTK_LAUNCH_CHECK();
   if (f.out_mask) ASTK_TRY(mul_rows_launch(P.LOGITS, P.Vp, f.out_mask, V, S * B, V, f.s));
   return 0;
@@ -677,11 +681,11 @@ int fwd_steps(const DecFwdCall& f, const DecPlan& P) {
       if (om) ASTK_TRY(mul_rows_launch(lg, P.Vp, om, V, B, V, s));
       if (uth) {
         hipLaunchKernelGGL(k_softmax_ce, dim3(B), dim3(256), 0, s, V, (long)P.Vp, lg, f.tgt + st + 1, (long)P.L, B, (const float*)nullptr, 1.f,
-                           0.f, (float*)nullptr, P.PRED + (size_t)st * B, 1, (const int32_t*)nullptr, 0);
+                           0.f, (float*)nullptr, P.PRED + (size_t)st * B, 1, (const int32_t*)nullptr, 0, (const float*)nullptr);
         ASTK_LAUNCH_CHECK();
       } else {
         ASTK_TRY(softmax_ce_launch(B, V, P.Vp, lg, f.tgt + st + 1, P.L, prm->class_weight, inv_count, f.d->label_smoothing, P.LOSSROWS + (size_t)st * B,
-                                  P.PRED + (size_t)st * B, s));
+                                  P.PRED + (size_t)st * B, s, f.row_weight));
         if (om) ASTK_TRY(mul_rows_launch(lg, P.Vp, om, V, B, V, s));
       }
     }
@@ -965,11 +969,11 @@ int bwd_params(const DecBwdCall& b, const DecPlan& P, const DecRoute& r) {
 }  // namespace
 
 int softmax_ce_launch(int B, int V, long ld, float* logits, const int32_t* targets, long t_stride, const float* cw, float inv_count,
-                      float eps, float* loss_rows, int32_t* argmax, hipStream_t s) {
+                      float eps, float* loss_rows, int32_t* argmax, hipStream_t s, const float* row_weight) {
   ASTK_CHECK(B > 0 && V > 0 && ld >= V && logits && targets, "softmax_ce: bad arguments");
   ASTK_CHECK(label_smoothing_ok(eps), "softmax_ce: label_smoothing %g (finite, 0 <= eps < 1)", (double)eps);
   hipLaunchKernelGGL(k_softmax_ce, dim3(B), dim3(256), 0, s, V, ld, logits, targets, t_stride, B, cw, inv_count, eps, loss_rows, argmax, 0,
-                     (const int32_t*)nullptr, 0);
+                     (const int32_t*)nullptr, 0, row_weight);
   ASTK_LAUNCH_CHECK();
   return 0;
 }
@@ -1013,8 +1017,14 @@ int astk_softmax_ce_fwd(int B, int V, long ld, float* logits_inout, const int32_
 
 int astk_softmax_ce_fwd_ex(int B, int V, long ld, float* logits_inout, const int32_t* targets, long t_stride, const float* class_weight,
                            float inv_count, float label_smoothing, float* loss_rows, int32_t* argmax, void* stream) {
+  return astk_softmax_ce_fwd_w(B, V, ld, logits_inout, targets, t_stride, class_weight, nullptr, inv_count, label_smoothing, loss_rows, argmax,
+                               stream);
+}
+
+int astk_softmax_ce_fwd_w(int B, int V, long ld, float* logits_inout, const int32_t* targets, long t_stride, const float* class_weight,
+                          const float* row_weight, float inv_count, float label_smoothing, float* loss_rows, int32_t* argmax, void* stream) {
   return softmax_ce_launch(B, V, ld, logits_inout, targets, t_stride, class_weight, inv_count, label_smoothing, loss_rows, argmax,
-                           (hipStream_t)stream);
+                           (hipStream_t)stream, row_weight);
 }
 
 int astk_decoder_fwd(const astk_decoder_desc* d, const astk_decoder_params* prm, const float* enc, const float* c0, const float* h0,
@@ -1026,6 +1036,12 @@ int astk_decoder_fwd(const astk_decoder_desc* d, const astk_decoder_params* prm,
 int astk_decoder_fwd_ex(const astk_decoder_desc* d, const astk_decoder_params* prm, const float* enc, const float* c0, const float* h0,
                         const int32_t* y, const int32_t* use_truth, const float* emb_mask, const float* rnn_masks, const float* out_mask,
                         const int32_t* targets, float* loss, int32_t* pred, void* ws, size_t ws_bytes, void* stream) {
+  return astk_decoder_fwd_w(d, prm, enc, c0, h0, y, use_truth, emb_mask, rnn_masks, out_mask, targets, nullptr, loss, pred, ws, ws_bytes, stream);
+}
+
+int astk_decoder_fwd_w(const astk_decoder_desc* d, const astk_decoder_params* prm, const float* enc, const float* c0, const float* h0,
+                       const int32_t* y, const int32_t* use_truth, const float* emb_mask, const float* rnn_masks, const float* out_mask,
+                       const int32_t* targets, const float* row_weight, float* loss, int32_t* pred, void* ws, size_t ws_bytes, void* stream) {
   hipStream_t s = (hipStream_t)stream;
   ASTK_CHECK_DESC(d, astk_decoder_desc);
   PrecScope prec_scope(d->precision, d->gemm_operands);
@@ -1039,7 +1055,7 @@ int astk_decoder_fwd_ex(const astk_decoder_desc* d, const astk_decoder_params* p
   const size_t need = r.split ? sp.bytes : P.bytes;
   ASTK_CHECK(ws && ws_bytes >= need, "decoder_fwd: workspace too small (%zu < %zu)", ws_bytes, need);
   ASTK_CHECK(prm && enc && c0 && h0 && y && use_truth && loss, "decoder_fwd: null pointer");
-  const DecFwdCall f = {d, prm, enc, c0, h0, y, use_truth, emb_mask, rnn_masks, out_mask, targets, targets ? targets : y, loss, pred, s};
+  const DecFwdCall f = {d, prm, enc, c0, h0, y, use_truth, emb_mask, rnn_masks, out_mask, targets, targets ? targets : y, row_weight, loss, pred, s};
   const float* loss_parts;      // what the tail sums
   int n_parts;
   if (r.split) {

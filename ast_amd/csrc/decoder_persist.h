@@ -22,7 +22,7 @@ bool decoder_persist_applicable(const astk_decoder_desc* d, int* nsplit_out, int
 bool pdec_special(int H, int chunk);
 int decoder_persist_fwd_launch(const astk_decoder_desc* d, const astk_decoder_params* prm, const float* enc, const int32_t* y,
                                const int32_t* ytgt, const int32_t* use_truth, const float* emb_mask, const float* rnn_masks, const DecPersistBuffers& bf,
-                               float* loss, int32_t* pred_out, hipStream_t s);
+                               float* loss, int32_t* pred_out, hipStream_t s, const float* row_weight = nullptr);
 
 struct DecPersistBwdBuffers {
   void* zero_ptr; size_t zero_bytes;      // astk_decoder_desc.zero_ptr: zeroed by the launcher's fill launch

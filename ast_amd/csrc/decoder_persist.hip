@@ -2189,6 +2189,9 @@ __global__ __launch_bounds__(256, 1) void decoder_persist_bwd(PDecBwdArgs a) {
 // row, fences and arrives ONCE on `done_ctr` (a word the forward launcher's fill zeroes); the block whose arrival completes S*B sums all
 // rows the way block 0 does.  No block waits for another, nothing spins, and there are no float atomics: the sum is the same whichever
 // block comes last.  eps == 0 is the code this kernel always ran.
+// rw (astk_decoder_fwd_w's row_weight, (B) or null): the loop kernels know no row weights (P6 writes the unweighted
+// row), so the block of row (s, b) scales its gradient sweep and its loss row by rw[b].  That rewrites rows as eps > 0 does, and takes the
+// same path: "rows are rewritten" is eps > 0 || rw.  rw == null is the code without it.
 template <bool ATOMIC_LOADS>
 __device__ __forceinline__ void post_sum_rows(const float* rows, int n, float* loss, double* red) {
   double acc = 0.0;
@@ -2207,7 +2210,7 @@ __global__ __launch_bounds__(256) void k_decoder_post(const float* __restrict__ 
                                                       const float* __restrict__ cw, float* lossrows, float* __restrict__ loss,
                                                       int32_t* __restrict__ pred_out, int S, int B, int L, int E, int XI, int V, int Vp, float inv_count,
                                                       float eps, unsigned* done_ctr, const unsigned* __restrict__ status,
-                                                      float* __restrict__ status_dst) {
+                                                      float* __restrict__ status_dst, const float* __restrict__ rw) {
   __shared__ double red[4];
   const int r = blockIdx.x, s = r / B, b = r % B;
   if (r == 0 && threadIdx.x == 0 && status_dst) *status_dst = (float)(*status);      // (astk_decoder_desc.status_dst: the snapshot without its launch)
@@ -2230,17 +2233,18 @@ __global__ __launch_bounds__(256) void k_decoder_post(const float* __restrict__ 
     const float scale = (cw ? cw[t] : 1.f) * inv_count;
     const float ls = lse[r];
     float* x = logits + (long)r * Vp;
-    if (eps > 0.f) {
+    if (eps > 0.f || rw) {      // the rows are rewritten
       __shared__ float sdev[4];
       __shared__ int s_last;
-      const float uni = eps / (float)V, hot = (1.f - eps) * scale;
+      const float rb = rw ? rw[b] : 1.f, gs = scale * rb;
+      const float uni = eps / (float)V, hot = (1.f - eps) * gs;
       float dev = 0.f;
       for (int v = threadIdx.x; v < Vp; v += 256) {
         float g = 0.f;
         if (v < V) {
           const float dv = x[v] - ls;
           dev += dv;
-          g = (expf(dv) - uni) * scale;
+          g = (expf(dv) - uni) * gs;
           if (v == t) g -= hot;
         }
         x[v] = g;
@@ -2250,7 +2254,9 @@ __global__ __launch_bounds__(256) void k_decoder_post(const float* __restrict__ 
       __syncthreads();
       if (threadIdx.x == 0) {
         dev = (sdev[0] + sdev[1]) + (sdev[2] + sdev[3]);
-        const float row = (1.f - eps) * lossrows[r] + eps * scale * (-(dev / (float)V));
+        float row = lossrows[r];
+        if (eps > 0.f) row = (1.f - eps) * row + eps * scale * (-(dev / (float)V));
+        if (rw) row *= rb;
         __hip_atomic_store(lossrows + r, row, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
         // release: the row is visible to the device before the arrival; acquire: the last block sees every other block's row
         s_last = __hip_atomic_fetch_add(done_ctr, 1u, __ATOMIC_ACQ_REL, __HIP_MEMORY_SCOPE_AGENT) + 1u == (unsigned)(S * B);
@@ -2405,7 +2411,7 @@ int decoder_persist_bwd_launch(const astk_decoder_desc* d, const float* enc, con
 
 int decoder_persist_fwd_launch(const astk_decoder_desc* d, const astk_decoder_params* prm, const float* enc, const int32_t* y,
                                const int32_t* ytgt, const int32_t* use_truth, const float* emb_mask, const float* rnn_masks, const DecPersistBuffers& bf,
-                               float* loss, int32_t* pred_out, hipStream_t s) {
+                               float* loss, int32_t* pred_out, hipStream_t s, const float* row_weight) {
   int nsplit = 1, chunk = 1;
   // encA = enc . Wa (one batched GEMM): the score of decoder step s is encA[b,t,:].h_s + enc[b,t,:].ba, so the per-step
   // q = Wa h phase drops out of the sequential chain; Q itself is rebuilt after the loop for the backward.
@@ -2460,7 +2466,7 @@ int decoder_persist_fwd_launch(const astk_decoder_desc* d, const astk_decoder_pa
   unsigned* post_ctr = bf.ctr + ((size_t)NPHASE_SLOTS * NSH * a.nbt + 2 + a.B) * CTRS;
   hipLaunchKernelGGL(k_decoder_post, dim3(a.S * a.B), dim3(256), 0, s, prm->embed, y, ytgt ? ytgt : y, use_truth, bf.PRED, emb_mask, bf.TOK, bf.X0, bf.LOGITS, bf.LSE,
                      prm->class_weight, bf.LOSSROWS, loss, pred_out, a.S, a.B, a.L, a.E, a.XI, a.V, a.Vp, a.inv_count, d->label_smoothing, post_ctr,
-                     persist_status_word(), d->status_dst);
+                     persist_status_word(), d->status_dst, row_weight);
   ASTK_LAUNCH_CHECK();
   return 0;
 }

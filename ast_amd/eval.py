@@ -107,15 +107,19 @@ def pair_stats_host(strings, pairs):
     return [list(edit_stats(strings[a], strings[b])) + list(clipped_matches(strings[a], strings[b])) for a, b in pairs]
 
 
-def pair_stats(strings, pairs, device=None):
+def pair_stats(strings, pairs, device=None, return_device=False):
     """One astk_pair_stats launch over a pool of int token strings (each at most PAIR_MAX_LEN long) and the pairs (a, b) of indices
-    into it: a (P, 8) int32 array [dist, sub, del, ins, m1, .., m4].  Needs the GPU: no host fallback behind this name."""
+    into it: a (P, 8) int32 array [dist, sub, del, ins, m1, .., m4].  Needs the GPU: no host fallback behind this name.
+    return_device: the device tensors (stats (P, 8), lens (S,), pairs (P, 2)) instead, with nothing read back and so no check of the
+    bad-row count -- what astk_risk_weights reads; P must be at least 1."""
     import ctypes
     import numpy as np
     import torch
     from . import _lib
     S, P = len(strings), len(pairs)
     if P == 0:
+        if return_device:
+            raise ValueError("pair_stats: return_device needs at least one pair")
         return np.zeros((0, 8), np.int32)
     lens = np.asarray([len(s) for s in strings], np.int32)
     if lens.max() > PAIR_MAX_LEN:
@@ -135,6 +139,8 @@ def pair_stats(strings, pairs, device=None):
         desc = _lib.PairStatsDesc(S, Lmax, P)
         _lib.check(lib.astk_pair_stats(ctypes.byref(desc), _lib.ptr(t), _lib.ptr(l), _lib.ptr(p), _lib.ptr(out),
                                        ctypes.c_void_p(out.data_ptr() + 4 * P * 8), ctypes.c_void_p(torch.cuda.current_stream(dev).cuda_stream)))
+        if return_device:
+            return out[:-1].view(P, 8), l, p
         host = out.cpu().numpy()
     if host[-1] != 0:
         raise _lib.AstkError(f"pair_stats: {int(host[-1])} of {P} pairs name a string outside the pool")

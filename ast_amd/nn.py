@@ -11,7 +11,7 @@ import torch
 from tqdm import tqdm
 
 from . import dist as adist
-from . import optimizers, serializers
+from . import mrt, optimizers, serializers
 from .config import Config
 from .dataloader import SYMBOLS, FisherDataLoader, GlobalPhoneDataLoader, SyntheticDataLoader
 from .seq2seq import (SpeechEncoderDecoder, checked_ctc_weight, checked_label_smoothing, ctc_count_of, raise_if_aborted,
@@ -663,6 +663,15 @@ class NN:
         self.ctc_weight = checked_ctc_weight(self.cfg.train.get("extras", {}).get("ctc_weight", 0.0),
                                              bool(self.cfg.model["rnn_config"].get("ctc", False)), "extras.ctc_weight")
         self.ctc_epoch = None                          # (mean CTC term per utterance, rows without a path) of the last train_epoch
+        # extension key: extras.mrt = {"samples", "alpha", "cost", "mle_weight", "max_len", "temperature", "top_k", "top_p", "seed",
+        # "start_epoch"}: minimum-risk training (ast_amd.mrt); absent or null = off, nothing of the branch runs.
+        # A train_epoch call runs MRT steps once `start_epoch` epochs have been trained (the checkpoint's and this object's together).
+        ex_ = self.cfg.train.get("extras", {})
+        self.mrt = mrt.checked_mrt(ex_.get("mrt"), "extras.mrt")
+        mrt.checked_mrt_setup(self.mrt, self.ctc_weight, ex_.get("random_out", 0), adist.world_size(), "extras.mrt")
+        self.mrt_epoch = None                          # mean expected cost per utterance of the last train_epoch that ran MRT steps
+        self.mrt_stream = 0                            # the running sample counter: the first stream no step has drawn from (set below)
+        self.epochs_trained = 0                        # train_epoch calls of this object
         self.model_dir = self.cfg.model["model_dir"]
         self.gpuid = self.cfg.train["gpuid"]
         if adist.is_distributed():
@@ -675,6 +684,7 @@ class NN:
         if adist.is_distributed():
             self.data_loader.rank, self.data_loader.world = adist.rank(), adist.world_size()
         self.get_model()
+        self.mrt_stream = self.max_epoch << 40         # a resumed run draws behind every stream of the epochs already trained
         # extension key: extras.spec_augment = {"freq_masks", "freq_width", "time_masks", "time_width", "time_ratio", "fill", "seed"} masks
         # the TRAINING batches inside the loader (ast_amd.spec_augment); absent, null or {} = off.  Evaluation
         # batches are never masked.  A resumed run starts its presentation counter behind every counter of the epochs already trained.
@@ -774,6 +784,8 @@ class NN:
         pending = None
         ctc_sum = [0.0, 0]                     # extras.ctc_weight > 0: sum of the steps' CTC terms / batch size, rows without a path
         kw = {}
+        use_mrt = self.mrt is not None and self.max_epoch + self.epochs_trained >= self.mrt["start_epoch"]
+        risk_sum = [0.0, 0]                    # MRT steps: sum of the steps' mean expected costs, steps
 
         def settle(p):
             nonlocal total_loss, n_batches, avg_loss
@@ -782,6 +794,10 @@ class NN:
             if len(vals) > 2:                                          # ... rows without a CTC path (int32), the attention term alone
                 ctc_sum[0] += (vals[0] - vals[3]) / p[1]
                 ctc_sum[1] += ctc_count_of(vals[2])
+            if len(p) > 3:                                             # an MRT step: the utterances' expected costs, read with the loss
+                risks = p[3].tolist()
+                risk_sum[0] += sum(risks) / len(risks)
+                risk_sum[1] += 1
             loss_val = vals[0] / p[1]                                  # quirk Q5: divided by the batch size
             n_batches += 1
             total_loss += loss_val
@@ -794,6 +810,14 @@ class NN:
         torch.cuda.synchronize(self.model.device)
         with tqdm(total=n_utts, ncols=80, disable=adist.rank() != 0) as pbar, torch.cuda.stream(self._compute_stream):
             for batch in self.data_loader.get_batch(self.cfg.train["batch_size"], set_key, train=True, labels=True):
+                if use_mrt:
+                    st = mrt.mrt_step(self.model, batch["X"], batch["y"], self.mrt, self.mrt_stream, self.optimizer)
+                    self.mrt_stream = st.next_stream
+                    cur = (st.loss.pair.clone(), len(st.batch["y"]), len(batch["X"]), st.risk.clone())
+                    if pending is not None:
+                        settle(pending)
+                    pending = cur
+                    continue
                 if self.ctc_weight > 0:
                     kw = {"ctc_weight": self.ctc_weight, "x_lens": batch.get("x_len")}
                 with using_config("train", True):
@@ -812,6 +836,8 @@ class NN:
                 settle(pending)
         torch.cuda.synchronize(self.model.device)      # later default-stream work (predict, checkpoint) sees the epoch's updates
         self.ctc_epoch = (ctc_sum[0] / max(n_batches, 1), ctc_sum[1]) if self.ctc_weight > 0 else None
+        self.mrt_epoch = risk_sum[0] / max(risk_sum[1], 1) if use_mrt else None
+        self.epochs_trained += 1
         return avg_loss
 
     # ---- nn.py:235-322

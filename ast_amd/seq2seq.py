@@ -1066,7 +1066,8 @@ class SpeechEncoderDecoder:
         dst.copy_(buf[:len(flags)], non_blocking=True)
         ev.record(torch.cuda.current_stream(self.device))
 
-    def forward_loss(self, X, y, teach_ratio, random_out=0, add_noise=0, y_global=None, label_smoothing=0.0, ctc_weight=0.0, x_lens=None):
+    def forward_loss(self, X, y, teach_ratio, random_out=0, add_noise=0, row_weight=None, y_global=None, label_smoothing=0.0, ctc_weight=0.0,
+                     x_lens=None):
         """seq2seq.py:399-473.  ctc_weight (extension): weight of the auxiliary CTC loss of the `ctc_out` head on the
         encoder states, loss = loss_attention + ctc_weight * mean_b nll_b; needs rnn_config.ctc; 0 = the reference's loss, and nothing
         of the branch is launched.  The labels of a row are its targets from UNK_ID on (PAD, GO and EOS dropped), the blank is PAD_ID.
@@ -1074,9 +1075,15 @@ class SpeechEncoderDecoder:
         ctc_weight > 0 only.  The attention term, `pred` and every decoder gradient do not depend on either.  label_smoothing (extension): eps of the training loss, uniform over all classes and
         weighted by the target's class weight; 0 = the reference's loss.  Predictions and fed-back tokens do not depend on it.  y_global (data parallelism with random_out > 0 only): the targets of the WHOLE unsharded batch as a host
         array, global row b * world + r = row b of rank r -- the loader has them before it shards (`batch["y_global"]`); without it the
-        ranks' targets are all-gathered, a host-blocking collective in front of every step."""
+        ranks' targets are all-gathered, a host-blocking collective in front of every step.  row_weight (extension):
+        None, or one finite float per batch row -- a (B,) float32 device tensor, or a host array that is uploaded -- that multiplies the
+        row's loss and gradient at every step (astk_decoder_fwd_w); any sign, 0 switches a row off exactly.  Predictions and fed-back
+        tokens do not depend on it.  Not with ctc_weight > 0: the CTC term has no row weights.  (It stands in front of the extension keywords, whose
+        order their own tests pin; pass it by name.)"""
         label_smoothing = checked_label_smoothing(label_smoothing)
         ctc_weight = checked_ctc_weight(ctc_weight, self.ctc_head)
+        if row_weight is not None and ctc_weight > 0:
+            raise ValueError("forward_loss: row_weight with ctc_weight > 0 (the CTC term has no row weights)")
         lib = self._require_gpu()
         X = self._as_input(X)
         if ctc_weight > 0:
@@ -1093,6 +1100,12 @@ class SpeechEncoderDecoder:
         if ctc_weight > 0 and L > _lib.CTC_MAX_LABELS:
             raise ValueError(f"ctc_weight > 0: targets of padded length {L} exceed ASTK_CTC_MAX_LABELS = {_lib.CTC_MAX_LABELS}")
         S = L - 1
+        if row_weight is not None:
+            if not isinstance(row_weight, torch.Tensor):
+                row_weight = torch.from_numpy(np.ascontiguousarray(row_weight, dtype=np.float32))
+            row_weight = row_weight.to(self.device, torch.float32).contiguous()
+            if tuple(row_weight.shape) != (B,):
+                raise ValueError(f"forward_loss: row_weight of shape {tuple(row_weight.shape)}, one weight per batch row ({B},) is needed")
         # quirk Q4: one Python-`random` coin per step for 0 < i < L-2, truth otherwise (seq2seq.py:431-436).  With random_out > 0
         # (seq2seq.py:456-465) the SAME stream also decides, behind each step's coin, which targets >= 4 are replaced (draw ABOVE
         # random_out) by a class id from xp.random.randint(4, dec_vocab_size + 1).  That range is inclusive of dec_vocab_size, one past the
@@ -1131,14 +1144,15 @@ class SpeechEncoderDecoder:
         st["dd"].label_smoothing = label_smoothing          # read by the forward call only (include/astk.h)
         st["y"] = y
         st["targets"] = targets
+        st["row_weight"] = row_weight
         dr = self.cfg["dropout"]
         st["emb_mask"] = self._masks("emb_mask", (S, B, self.E), dr["embed"])
         st["rnn_masks"] = self._masks("rnn_masks", (len(self.rnn_dec), S, B, self.H), dr["rnn"])
         st["out_mask"] = self._masks("out_mask", (S, B, self.V), dr.get("out", 0))       # dropout on the logits (seq2seq.py:394)
         wd = self._workspace("dec", st["ws_dec"])
-        check(lib.astk_decoder_fwd_ex(C.byref(st["dd"]), C.byref(st["dp"]), _vp(st["enc_states"]), _vp(st["c0"]), _vp(st["h0"]),
-                                      _vp(y), _vp(st["flags"]), _vp(st["emb_mask"]), _vp(st["rnn_masks"]), _vp(st["out_mask"]), _vp(targets),
-                                      _vp(st["loss"]), _vp(st["pred"]), _vp(wd), wd.numel(), self._stream()))
+        check(lib.astk_decoder_fwd_w(C.byref(st["dd"]), C.byref(st["dp"]), _vp(st["enc_states"]), _vp(st["c0"]), _vp(st["h0"]),
+                                     _vp(y), _vp(st["flags"]), _vp(st["emb_mask"]), _vp(st["rnn_masks"]), _vp(st["out_mask"]), _vp(targets),
+                                     _vp(row_weight), _vp(st["loss"]), _vp(st["pred"]), _vp(wd), wd.numel(), self._stream()))
         # (loss[1] = the persistent kernels' status word: written by the op itself, astk_decoder_desc.status_dst)
         st["ctc"] = self._ctc_forward(st, y, ctc_weight, x_lens) if ctc_weight > 0 else None
         st["pending_backward"] = True

@@ -420,6 +420,19 @@ int astk_decoder_fwd_ex(const astk_decoder_desc* d, const astk_decoder_params* p
                         const float* c0, const float* h0, const int32_t* y, const int32_t* use_truth,
                         const float* emb_mask, const float* rnn_masks, const float* out_mask, const int32_t* targets,
                         float* loss, int32_t* pred, void* ws, size_t ws_bytes, void* stream);
+/* ... with one weight per batch row: row_weight NULL or (B) float32.  With r_b = row_weight[b] (NULL: 1) every
+ * step's row of batch row b is
+ *     row_{s,b}  = r_b w[t] c [ (1 - eps)(LSE - x_t) + eps (LSE - mean_v x_v) ]
+ *     dx_{s,b,v} = r_b w[t] c [ softmax(x)_v - (1 - eps)[v == t] - eps / V ]
+ * (w = class_weight, c = 1 / loss_rows, eps = label_smoothing).  r_b is any FINITE float, negative and zero included; the weights are
+ * not checked on the device.  A row with r_b == 0 adds exactly 0 to the loss and has an exactly-zero gradient row.  pred, the argmax,
+ * the fed-back tokens and the status word do not depend on the weights; the backward calls need nothing (the gradient of the logits is
+ * formed in this call).  Every path takes it (per-launch, persistent, wide, the row split, which hands each half its part of the
+ * vector).  astk_decoder_fwd_ex is this call with row_weight = NULL: the same bits as before the argument existed. */
+int astk_decoder_fwd_w(const astk_decoder_desc* d, const astk_decoder_params* p, const float* enc,
+                       const float* c0, const float* h0, const int32_t* y, const int32_t* use_truth,
+                       const float* emb_mask, const float* rnn_masks, const float* out_mask, const int32_t* targets,
+                       const float* row_weight, float* loss, int32_t* pred, void* ws, size_t ws_bytes, void* stream);
 /* The same backward in two phases, for callers that overlap them: ASTK_DEC_BWD_CHAIN runs the reversed loop and writes
  * everything the encoder's backward needs (d_enc, d_c0, d_h0); ASTK_DEC_BWD_PARAMS accumulates the parameter gradients from
  * what the chain phase left in `ws` -- it only has to be ordered after the chain phase (an event), so it can run on a second
@@ -736,6 +749,12 @@ int astk_softmax_ce_fwd(int B, int V, long ld, float* logits_inout, const int32_
 int astk_softmax_ce_fwd_ex(int B, int V, long ld, float* logits_inout, const int32_t* targets, long t_stride,
                            const float* class_weight, float inv_count, float label_smoothing, float* loss_rows, int32_t* argmax,
                            void* stream);
+/* ... with one weight per row: row_weight NULL or (B) float32, finite (not checked on the device), any sign; a factor on
+ * class_weight[t_b], so on loss_rows[b] and on the row of dlogits alike; a zero weight gives an exactly-zero row of both.  argmax does
+ * not depend on it.  astk_softmax_ce_fwd_ex is this call with row_weight = NULL. */
+int astk_softmax_ce_fwd_w(int B, int V, long ld, float* logits_inout, const int32_t* targets, long t_stride,
+                          const float* class_weight, const float* row_weight, float inv_count, float label_smoothing, float* loss_rows,
+                          int32_t* argmax, void* stream);
 
 /* ---------------------------------------------------------------- optimizer  (nn.py:81-119, Chainer-sem A7/A8)
  * One flat parameter / gradient buffer.  ONE norm launch at a time per process: astk_grad_sqnorm(_scaled) folds its per-block partial
@@ -994,6 +1013,42 @@ typedef struct {
 } astk_pair_stats_desc;
 int astk_pair_stats(const astk_pair_stats_desc* d, const int32_t* tokens, const int32_t* lens, const int32_t* pairs, int32_t* stats,
                     int32_t* n_bad, void* stream);
+/* ---------------------------------------------------------------- risk weights for minimum-risk training
+ * Turns the integers of astk_pair_stats and the candidates' sequence log-probabilities into the per-row weights of astk_decoder_fwd_w
+ * under which the weighted cross-entropy's gradient is the gradient of the expected cost of each list (utterance):
+ *     Q_i = exp(alpha (s_i - s_max)) / sum_j ..   Rbar = sum_i Q_i c_i   weight_i = risk_scale alpha Q_i (Rbar - c_i) + [flag bit 1] ref_weight
+ * over the live rows of the list, in float64, each output rounded once to float32.
+ *   first     int32 (U+1): row offsets of the lists, ascending, first[U] == R
+ *   score     (R) sequence log-probabilities s_i
+ *   stats     int32 (R, 8) of astk_pair_stats: row i is pair i of that call
+ *   lens, pairs  the arrays that call read: hyp_len = lens[pairs[i][0]], ref_len = lens[pairs[i][1]]
+ *   flags     int32 (R): bit 0 live (in the candidate set), bit 1 reference row
+ *   weight    (R);  risk (U) the expected cost Rbar, may be NULL;  cost_out (R) c_i, may be NULL;  n_bad int32, may be NULL: bad lists
+ * Cost: ASTK_RISK_COST_BLEU c = 1 - BLEU from (m1..m4, hyp_len, ref_len) -- method-2 smoothing ((m+1)/(t+1) for n >= 2), denominators
+ * max(1, hyp_len - n + 1), the brevity penalty exp(1 - ref_len / hyp_len) (0 for an empty hypothesis), 0 when a match count is 0;
+ * ASTK_RISK_COST_EDIT c = dist / max(1, ref_len).  A row is dead when bit 0 of its flag is clear or its stats row is the all -1 bad row:
+ * Q = 0, cost_out = 0, only the reference term in its weight.  A list without live rows has risk 0.  A list is bad when it has more
+ * than ASTK_RISK_MAX_LIST rows or its offsets do not ascend within [0, R] -- 0 <= first[u-1] <= first[u] <= first[u+1] <= R, so the
+ * list behind a descent is bad too (it would share rows with an earlier one): its weights (its rows inside [0, R) and behind
+ * first[u-1]), their cost_out and its risk are 0, nothing is read out of bounds, and it is counted in *n_bad.  score and flags must be finite / as described: they are not checked.
+ * One wavefront per list, a lane per row, the three reductions as fixed-order shuffle trees: bit-identical from run to run.  One launch
+ * (two with n_bad), no allocation, no synchronisation, no workspace, no atomics.  Refused before any launch: a wrong struct_size; U or
+ * R < 1; cost outside {0, 1}; alpha negative or not finite; risk_scale or ref_weight not finite; a NULL first / score / stats / lens /
+ * pairs / flags / weight. */
+#define ASTK_RISK_MAX_LIST 64
+enum { ASTK_RISK_COST_BLEU = 0, ASTK_RISK_COST_EDIT = 1 };
+typedef struct {
+  size_t struct_size;   /* = sizeof(astk_risk_desc) */
+  int U;                /* lists (utterances) */
+  int R;                /* rows = candidates over all lists */
+  int cost;             /* ASTK_RISK_COST_* */
+  float alpha;          /* sharpness of Q, finite, >= 0 */
+  float risk_scale;     /* factor on the risk term, finite */
+  float ref_weight;     /* added to the weight of a row whose flag has bit 1 set, finite */
+} astk_risk_desc;
+int astk_risk_weights(const astk_risk_desc* d, const int32_t* first, const float* score, const int32_t* stats, const int32_t* lens,
+                      const int32_t* pairs, const int32_t* flags, float* weight, float* risk, float* cost_out, int32_t* n_bad,
+                      void* stream);
 /* ---------------------------------------------------------------- speech features from waveforms, and CMVN
  * MFCC / log mel filterbank features in the sense of Kaldi's compute-mfcc-feats / compute-fbank-feats (snip-edges=true only), written
  * from Kaldi's documented algorithm and option names; parity with Kaldi's binaries is NOT pinned (no Kaldi output exists to pin it

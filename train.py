@@ -50,6 +50,8 @@ if __name__ == "__main__":
                 f.write("{0:d}, {1:.4f}\n".format(epoch, epoch_loss))
             if nn.ctc_epoch is not None:        # extras.ctc_weight > 0: the part of the epoch's loss that is the weighted CTC term
                 print("CTC term = {0:.4f}, rows without a CTC path = {1:d}".format(*nn.ctc_epoch))
+            if nn.mrt_epoch is not None:        # extras.mrt: the mean expected cost of the epoch's sampled candidate sets
+                print("MRT expected cost = {0:.4f}".format(nn.mrt_epoch))
         if metrics is not None and adist.rank() == 0:
             if args["dev_loss"]:
                 preds, dev_loss, _ = nn.predict_scored(dev_key)
