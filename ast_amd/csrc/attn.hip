@@ -312,26 +312,36 @@ using namespace astk;
 
 extern "C" {
 
-size_t astk_attn_workspace_bytes(int B, int T, int H) { return attn_ws_bytes(B, T, H); }
+// (0 for dimensions no launch accepts: the plan divides by B and by the chunk)
+size_t astk_attn_workspace_bytes(int B, int T, int H) { return B > 0 && T > 0 && H > 0 ? attn_ws_bytes(B, T, H) : 0; }
+
+// The entry points below refuse what the launchers refuse BEFORE they size the workspace and zero its counters: a refused call divides
+// by nothing and leaves the workspace as it found it.
+#define ASTK_ATTN_DIMS(B, T, H) \
+  ASTK_CHECK((B) > 0 && (T) > 0 && (H) > 0 && ((H) % 4) == 0 && (H) <= 2048, "attn: need B, T > 0, H %% 4 == 0 and H <= 2048 (B=%d T=%d H=%d)", B, T, H)
 
 // alpha is (B, Tp) with Tp = round_up(T, 4) (the layout the decoder keeps it in); cv (B, H).
 int astk_attn_step_fwd(int B, int T, int H, const float* enc, const float* q, float* alpha, float* cv, void* ws,
                        size_t ws_bytes, void* stream) {
-  ASTK_CHECK(ws_bytes >= attn_ws_bytes(B, T, H), "attn_step_fwd: workspace too small");
+  ASTK_ATTN_DIMS(B, T, H);
+  ASTK_CHECK(ws && ws_bytes >= attn_ws_bytes(B, T, H), "attn_step_fwd: workspace too small");
   ASTK_TRY(attn_ws_init(ws, B, T, H, (hipStream_t)stream));
   return attn_fwd_launch(B, T, H, enc, q, H, alpha, cv, H, nullptr, 0, ws, (hipStream_t)stream);
 }
 
 int astk_attn_step_fwd_rows(int R, int T, int H, const float* enc, const int32_t* row_utt, const int32_t* row_len, const float* q,
                             float* alpha, float* cv, void* ws, size_t ws_bytes, void* stream) {
-  ASTK_CHECK(ws_bytes >= attn_ws_bytes(R, T, H), "attn_step_fwd_rows: workspace too small");
+  ASTK_ATTN_DIMS(R, T, H);
+  ASTK_CHECK(row_utt && row_len, "attn_step_fwd_rows: null row map");
+  ASTK_CHECK(ws && ws_bytes >= attn_ws_bytes(R, T, H), "attn_step_fwd_rows: workspace too small");
   ASTK_TRY(attn_ws_init(ws, R, T, H, (hipStream_t)stream));
   return attn_fwd_rows_launch(R, T, H, enc, row_utt, row_len, q, H, alpha, cv, H, ws, (hipStream_t)stream);
 }
 
 int astk_attn_step_bwd(int B, int T, int H, const float* enc, const float* alpha, const float* cv, const float* d_cv,
                        float* ds, float* dq, void* ws, size_t ws_bytes, void* stream) {
-  ASTK_CHECK(ws_bytes >= attn_ws_bytes(B, T, H), "attn_step_bwd: workspace too small");
+  ASTK_ATTN_DIMS(B, T, H);
+  ASTK_CHECK(ws && ws_bytes >= attn_ws_bytes(B, T, H), "attn_step_bwd: workspace too small");
   ASTK_TRY(attn_ws_init(ws, B, T, H, (hipStream_t)stream));
   return attn_bwd_launch(B, T, H, enc, alpha, cv, H, d_cv, H, ds, dq, ws, (hipStream_t)stream);
 }

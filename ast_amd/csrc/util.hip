@@ -908,6 +908,9 @@ int astk_bridge_states(float* dec_c, float* dec_h, float* enc_c, float* enc_h, i
 }
 int astk_colsum_add_f32(float* dst, const float* src, long lds, int rows, int cols, void* stream) {
   ASTK_CHECK(dst && src && rows > 0 && cols > 0 && lds >= cols, "colsum_add: bad arguments");
+  // the kernel reads 16-byte quads at src + r * lds + c: a shifted quad sums the wrong columns, and the last row's runs past the matrix
+  ASTK_CHECK((lds % 4) == 0, "colsum_add: the leading dimension must be a multiple of 4 floats (lds=%ld)", lds);
+  ASTK_CHECK(aligned16(src), "colsum_add: src must be 16-byte aligned");
   return colsum_add_f32(dst, src, lds, rows, cols, (hipStream_t)stream);
 }
 

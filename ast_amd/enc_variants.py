@@ -260,6 +260,7 @@ class LinearProjEncoder(_Layerwise):
                 self._bwd((l, d), c["desc"], c["p"], c["g"], c["x"], c["mk"], dU[d], d_cT[d, l].contiguous().view(1, 1, B, h),
                           d_hT[d, l].contiguous().view(1, 1, B, h), dx)
                 if d == 1:                                        # every step of the reverse stack read the same frame: sum over the steps
+                    # (colsum_add wants a leading dimension that is a multiple of 4: `width` is one, astk_lstm_stack_* refuse any other in_dim)
                     check(lib.astk_colsum_add_f32(_vp(dprev[T2 - 1]), _vp(dx), B * width, T2, B * width, s))
             if l == nl - 1 and l > 0:
                 # the input of the top layer is also the attention memory: both gradients meet here

@@ -319,7 +319,9 @@ int astk_lstm_stack_bwd_on(const astk_lstm_stack_desc* d, const astk_lstm_params
 /* ---------------------------------------------------------------- attention step  (seq2seq.py:336-357)
  * q = Wa h + ba is computed by the caller (GEMM); this is the scan over enc_states:
  * s[b,t] = enc[b,t,:].q[b,:]; alpha = softmax_t(s) (no mask, quirk Q2); cv[b,:] = sum_t alpha[b,t] enc[b,t,:].
- * One streaming read of enc_states (online softmax), split over nsplit time chunks per batch row. */
+ * One streaming read of enc_states (online softmax), split over nsplit time chunks per batch row.
+ * Needs B, T > 0, H % 4 == 0, H <= 2048; anything else, a short workspace or (rows variant) a null row map is refused before the
+ * workspace is touched, and astk_attn_workspace_bytes answers 0 for dimensions that are not positive. */
 size_t astk_attn_workspace_bytes(int B, int T, int H);
 int astk_attn_step_fwd(int B, int T, int H, const float* enc, const float* q, float* alpha, float* cv,
                        void* ws, size_t ws_bytes, void* stream);
@@ -816,7 +818,8 @@ int astk_fill_random(const astk_rand_seg* segs, int n_segs, void* stream);
 int astk_fill_random_ex(const astk_rand_seg* segs, int n_segs, const int32_t* words, int n_words, int32_t* words_dst, void* stream);
 int astk_scale_f32(float* x, size_t n, float s, void* stream);
 /* dst += src (n floats); dst[c] += sum_r src[r*lds + c] (bias gradients; the sum over time of the linear_proj encoder's reverse-stack
- * input gradient, whose input is one frame fed at every step). */
+ * input gradient, whose input is one frame fed at every step).  The column sum loads 16-byte quads: src must be 16-byte aligned and
+ * lds a multiple of 4 (the columns behind cols inside the last quad are read, never summed); any other layout is refused. */
 int astk_add_f32(float* dst, const float* src, size_t n, void* stream);
 int astk_colsum_add_f32(float* dst, const float* src, long lds, int rows, int cols, void* stream);
 /* init_decoder_state (seq2seq.py:318-333) and its backward as ONE launch each: decoder layer k < n starts from [fwd_k ; rev_k] of the
