@@ -2,13 +2,15 @@
 // domain, no floating-point atomics: row_nll, loss_acc and dlogits are the same bits from run to run.
 //
 // Four launches on the caller's stream:
-//   k_ctc_lse     one wavefront per frame (b, t): lse[b][t] = log sum_v exp(logits[b][t][v]), maximum subtracted.  Coalesced over V.
+//   k_ctc_lse     one wavefront per frame (b, t): lse[b][t] = log sum_v exp(logits[b][t][v]), maximum subtracted (ctc_rows.h
+//                 ctc_wave_lse).  Coalesced over V.
 //   k_ctc_rows    one workgroup per batch row, one thread per state s of the extended sequence (S' = 2U + 1 <= 511, blanks at the even
-//                 positions).  The workgroup compacts the row's labels from y into LDS (ballot prefix sums, no launch of its own), runs
-//                 the alpha recursion over t with alpha rolled in two LDS buffers (one barrier per step) and stored to the workspace,
-//                 T * S' floats per row, next to the emissions e[t][s] = logits[t][class(s)] - lse[t] it gathered (once: the beta pass
-//                 reads them back).  The gathers do not depend on the recursion and are issued sixteen steps ahead.  Then beta is rolled
-//                 in LDS from t = len - 1 down, and the occupancy gamma[t][s] = exp(alpha + beta - e - log p) overwrites alpha[t][s].
+//                 positions).  The workgroup compacts the row's labels from y into LDS (ctc_rows.h ctc_row_setup: ballot prefix sums, no
+//                 launch of its own), runs the alpha recursion over t with alpha rolled in two LDS buffers (one barrier per step) and
+//                 stored to the workspace, T * S' floats per row, next to the emissions e[t][s] = logits[t][class(s)] - lse[t] it
+//                 gathered (once: the beta pass reads them back).  The gathers do not depend on the recursion and are issued sixteen
+//                 steps ahead (ctc_rows.h ctc_run_ahead, the loop of both passes).  Then beta is rolled in LDS from t = len - 1 down,
+//                 and the occupancy gamma[t][s] = exp(alpha + beta - e - log p) overwrites alpha[t][s].
 //   k_ctc_grad    one workgroup per frame, the V-wide coalesced pass: dlogits = scale * softmax, then scale * occupancy of every class
 //                 that has states is subtracted by ONE writer per class in a fixed order: the blank's states by a fixed-shape tree (two
 //                 per thread, xor tree per wave, the four waves in order), a label's states by the class's first state, which walks the
@@ -40,15 +42,14 @@ static CtcWs ctc_carve(const astk_ctc_desc* d, void* base) {
   CtcWs w;
   w.Smax = 2 * d->L + 1;
   const size_t bt = (size_t)d->B * d->T;
-  size_t off = 0;
-  auto take = [&](size_t n) { const size_t o = off; off += (n * 4 + 15) & ~(size_t)15; return (char*)base + o; };      // n 4-byte words
-  w.lse = (float*)take(bt);
-  w.alpha = (float*)take(bt * w.Smax);
-  w.em = (float*)take(bt * w.Smax);
-  w.own = (int*)take((size_t)d->B * w.Smax);
-  w.nxt = (int*)take((size_t)d->B * w.Smax);
-  w.meta = (int*)take((size_t)d->B * CTC_META);
-  w.bytes = off;
+  CtcBump c(base);
+  w.lse = c.take<float>(bt);
+  w.alpha = c.take<float>(bt * w.Smax);
+  w.em = c.take<float>(bt * w.Smax);
+  w.own = c.take<int>((size_t)d->B * w.Smax);
+  w.nxt = c.take<int>((size_t)d->B * w.Smax);
+  w.meta = c.take<int>((size_t)d->B * CTC_META);
+  w.bytes = c.off;
   return w;
 }
 
@@ -66,23 +67,11 @@ __global__ __launch_bounds__(256) void k_ctc_lse(int B, int T, int V, long ldv, 
   if (f >= (long)B * T) return;
   const int b = (int)(f / T), t = (int)(f - (long)b * T);
   if (t >= ctc_row_len(len, b, T)) return;
-  const float* x = logits + f * ldv;
-  float m = -INFINITY;
-  for (int v = lane; v < V; v += 64) m = fmaxf(m, x[v]);
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) m = fmaxf(m, __shfl_xor(m, o));
-  float s = 0.f;
-  for (int v = lane; v < V; v += 64) s += expf(x[v] - m);
-  s = wave_sum(s);
-  if (lane == 0) lse[f] = m + logf(s);
+  const float l = ctc_wave_lse<float>(logits + f * ldv, V, lane);
+  if (lane == 0) lse[f] = l;
 }
 
-struct CtcRowArgs {
-  int T, V, L, first_label, blank;
-  long ldv, ldy;
-  const float* logits;
-  const int32_t* y;
-  const int32_t* len;
+struct CtcRowArgs : CtcRowIn {
   float* row_nll;
 };
 
@@ -91,21 +80,13 @@ __global__ __launch_bounds__(CTC_ROW_THREADS) void k_ctc_rows(CtcRowArgs a, CtcW
   __shared__ float ab[2][CTC_ROW_THREADS + 4];          // the rolled recursion, two guard cells on either side
   __shared__ int wcnt[CTC_ROW_THREADS / 64];
   __shared__ int s_rep;
-  const int b = blockIdx.x, tid = threadIdx.x, nt = blockDim.x;
-  const int lane = tid & 63;
+  const int b = blockIdx.x, tid = threadIdx.x;
   const int Tb = ctc_row_len(a.len, b, a.T);
   const int Smax = w.Smax;
-  // ---- the row's labels: entries of y[b] with id >= first_label, in order, to the odd states
-  if (tid == 0) s_rep = 0;
-  const int U = ctc_compact_labels(a.y + (long)b * a.ldy, a.L, a.first_label, a.V, a.blank, ext, wcnt);
-  const int S = 2 * U + 1;
-  const bool act = tid < S;
-  const int cls = act ? ext[tid] : a.blank;
-  const bool odd = act && (tid & 1);
-  const bool skip_f = odd && tid >= 3 && ext[tid - 2] != cls;       // the transition s - 2 -> s
+  const CtcRow r = ctc_row_setup(a, b, Tb, ext, wcnt, &s_rep, &ab[0][0]);
+  const int U = r.U, S = r.S, cls = r.cls;
+  const bool act = r.act, odd = r.odd, skip_f = r.skip, feasible = r.feasible;
   const bool skip_b = odd && tid + 2 < S && ext[tid + 2] != cls;    // the transition s -> s + 2
-  const unsigned long long rm = __ballot(odd && tid >= 3 && ext[tid - 2] == cls);
-  if (lane == 0 && rm) atomicAdd(&s_rep, __popcll(rm));             // (an integer count: order-free)
   if (tid < Smax) {
     // the class chains k_ctc_grad walks: a label's first state owns the class
     int own = -1, nx = -1;
@@ -117,10 +98,6 @@ __global__ __launch_bounds__(CTC_ROW_THREADS) void k_ctc_rows(CtcRowArgs a, CtcW
     w.own[(size_t)b * Smax + tid] = own;
     w.nxt[(size_t)b * Smax + tid] = nx;
   }
-  for (int i = tid; i < 2 * (CTC_ROW_THREADS + 4); i += nt) (&ab[0][0])[i] = -INFINITY;
-  __syncthreads();
-  const int rep = s_rep;
-  const bool feasible = Tb >= U + rep;
   if (tid == 0) {
     w.meta[b * CTC_META + 0] = U;
     w.meta[b * CTC_META + 1] = feasible ? 1 : 0;
@@ -136,41 +113,24 @@ __global__ __launch_bounds__(CTC_ROW_THREADS) void k_ctc_rows(CtcRowArgs a, CtcW
   float* em = w.em + (size_t)b * a.T * Smax + tid;
   int cur = 0;
   // ---- alpha, t = 0 .. len - 1
-  {
-    float xq[CTC_PF], lq[CTC_PF];
-#pragma unroll
-    for (int k = 0; k < CTC_PF; ++k) {
-      xq[k] = (act && k < Tb) ? lg[(size_t)k * a.ldv] : 0.f;
-      lq[k] = k < Tb ? ls[k] : 0.f;
-    }
-    for (int t0 = 0; t0 < Tb; t0 += CTC_PF) {
-      float xc[CTC_PF], lc[CTC_PF];
-#pragma unroll
-      for (int k = 0; k < CTC_PF; ++k) { xc[k] = xq[k]; lc[k] = lq[k]; }
-#pragma unroll
-      for (int k = 0; k < CTC_PF; ++k) {
-        const int t = t0 + CTC_PF + k;
-        xq[k] = (act && t < Tb) ? lg[(size_t)t * a.ldv] : 0.f;
-        lq[k] = t < Tb ? ls[t] : 0.f;
-      }
-#pragma unroll
-      for (int k = 0; k < CTC_PF; ++k) {
-        const int t = t0 + k;
-        if (t < Tb) {                                   // (uniform)
-          if (act) {
-            const float* p = &ab[cur][2 + tid];
-            const float e = xc[k] - lc[k];
-            const float v = logadd3(p[0], p[-1], skip_f ? p[-2] : -INFINITY) + e;
-            ab[cur ^ 1][2 + tid] = v;
-            al[(size_t)t * Smax] = v;
-            em[(size_t)t * Smax] = e;
-          }
-          __syncthreads();
-          cur ^= 1;
+  ctc_run_ahead(
+      Tb,
+      [&](int t, float& x, float& l) {
+        l = t < Tb ? ls[t] : 0.f;                         // (the uniform guard first: it stays a scalar branch)
+        x = (act && t < Tb) ? lg[(size_t)t * a.ldv] : 0.f;
+      },
+      [&](int t, float x, float l) {
+        if (act) {
+          const float* p = &ab[cur][2 + tid];
+          const float e = x - l;
+          const float v = logadd3(p[0], p[-1], skip_f ? p[-2] : -INFINITY) + e;
+          ab[cur ^ 1][2 + tid] = v;
+          al[(size_t)t * Smax] = v;
+          em[(size_t)t * Smax] = e;
         }
-      }
-    }
-  }
+        __syncthreads();
+        cur ^= 1;
+      });
   const float ll = logadd3(ab[cur][2 + S - 1], S >= 2 ? ab[cur][2 + S - 2] : -INFINITY, -INFINITY);
   if (tid == 0) a.row_nll[b] = -ll;
   __syncthreads();
@@ -180,42 +140,24 @@ __global__ __launch_bounds__(CTC_ROW_THREADS) void k_ctc_rows(CtcRowArgs a, CtcW
   if (tid == 0) ab[0][2 + S - 1] = 0.f;                 // the virtual step behind t = len - 1
   __syncthreads();
   cur = 0;
-  {
-    float aq[CTC_PF], eq[CTC_PF];
-#pragma unroll
-    for (int k = 0; k < CTC_PF; ++k) {
-      const int t = Tb - 1 - k;
-      aq[k] = (act && t >= 0) ? al[(size_t)t * Smax] : 0.f;
-      eq[k] = (act && t >= 0) ? em[(size_t)t * Smax] : 0.f;
-    }
-    for (int t0 = Tb - 1; t0 >= 0; t0 -= CTC_PF) {
-      float ac[CTC_PF], ec[CTC_PF];
-#pragma unroll
-      for (int k = 0; k < CTC_PF; ++k) { ac[k] = aq[k]; ec[k] = eq[k]; }
-#pragma unroll
-      for (int k = 0; k < CTC_PF; ++k) {
-        const int t = t0 - CTC_PF - k;
-        aq[k] = (act && t >= 0) ? al[(size_t)t * Smax] : 0.f;
-        eq[k] = (act && t >= 0) ? em[(size_t)t * Smax] : 0.f;
-      }
-#pragma unroll
-      for (int k = 0; k < CTC_PF; ++k) {
-        const int t = t0 - k;
-        if (t >= 0) {                                   // (uniform)
-          if (act) {
-            const float* p = &ab[cur][2 + tid];
-            const float e = ec[k];
-            const float v = logadd3(p[0], p[1], skip_b ? p[2] : -INFINITY) + e;
-            ab[cur ^ 1][2 + tid] = v;
-            const float alpha = ac[k];
-            al[(size_t)t * Smax] = (alpha == -INFINITY || v == -INFINITY) ? 0.f : expf(alpha + v - e - ll);
-          }
-          __syncthreads();
-          cur ^= 1;
+  ctc_run_ahead(
+      Tb,
+      [&](int i, float& alpha, float& e) {
+        const int t = Tb - 1 - i;
+        alpha = (act && t >= 0) ? al[(size_t)t * Smax] : 0.f;
+        e = (act && t >= 0) ? em[(size_t)t * Smax] : 0.f;
+      },
+      [&](int i, float alpha, float e) {
+        const int t = Tb - 1 - i;
+        if (act) {
+          const float* p = &ab[cur][2 + tid];
+          const float v = logadd3(p[0], p[1], skip_b ? p[2] : -INFINITY) + e;
+          ab[cur ^ 1][2 + tid] = v;
+          al[(size_t)t * Smax] = (alpha == -INFINITY || v == -INFINITY) ? 0.f : expf(alpha + v - e - ll);
         }
-      }
-    }
-  }
+        __syncthreads();
+        cur ^= 1;
+      });
 }
 
 __global__ __launch_bounds__(256) void k_ctc_grad(int T, int V, long ldv, int blank, float scale, const float* logits, float* dlogits, CtcWs w) {
@@ -325,18 +267,16 @@ size_t astk_ctc_workspace_bytes(const astk_ctc_desc* d) {
 int astk_ctc_loss(const astk_ctc_desc* d, const float* logits, const int32_t* y, const int32_t* input_len, float scale, float* row_nll,
                   float* loss_acc, float* dlogits, int32_t* n_infeasible, void* ws, size_t ws_bytes, void* stream) {
   ASTK_TRY(ctc_check_desc(d, "ctc_loss"));
-  ASTK_CHECK(logits && y && row_nll && dlogits && ws, "ctc_loss: logits, y, row_nll, dlogits and ws must not be null");
-  ASTK_CHECK(aligned16(ws), "ctc_loss: the workspace must be 16-byte aligned");
-  ASTK_CHECK(scale == scale && fabsf(scale) <= 3.4e38f, "ctc_loss: scale must be finite, got %g", (double)scale);
   const CtcWs w = ctc_carve(d, ws);
-  ASTK_CHECK(ws_bytes >= w.bytes, "ctc_loss: workspace of %zu bytes, astk_ctc_workspace_bytes asks for %zu", ws_bytes, w.bytes);
+  ASTK_TRY(ctc_check_ptrs("ctc_loss", logits && y && row_nll && dlogits, "logits, y, row_nll, dlogits", ws));
+  ASTK_CHECK(scale == scale && fabsf(scale) <= 3.4e38f, "ctc_loss: scale must be finite, got %g", (double)scale);
+  ASTK_TRY(ctc_check_ws_bytes("ctc_loss", "ctc", ws_bytes, w.bytes));
   hipStream_t s = (hipStream_t)stream;
   const unsigned frames = (unsigned)((size_t)d->B * d->T);
   ASTK_TRY(ctc_lse_launch(d, logits, input_len, w.lse, s));
   CtcRowArgs a;
-  a.T = d->T; a.V = d->V; a.L = d->L; a.first_label = d->first_label; a.blank = d->blank;
-  a.ldv = d->ldv; a.ldy = d->ldy;
-  a.logits = logits; a.y = y; a.len = input_len; a.row_nll = row_nll;
+  ctc_row_in(a, d, logits, y, input_len);
+  a.row_nll = row_nll;
   const int nt = (w.Smax + 63) / 64 * 64;               // one thread per state of the longest row the descriptor admits (<= 512)
   hipLaunchKernelGGL(k_ctc_rows, dim3(d->B), dim3(nt), 0, s, a, w);
   ASTK_LAUNCH_CHECK();

@@ -4,8 +4,10 @@
 //
 // Two launches on the caller's stream (three with n_infeasible):
 //   k_ctc_lse     ctc.hip's, through ctc_lse_launch: one wavefront per frame.
-//   k_ctc_align   one workgroup per batch row, one thread per state s (ctc_rows.h compacts the labels as k_ctc_rows does).
-//     forward     delta rolled in two LDS buffers, one barrier per step, the emission gathers sixteen steps ahead; per state a
+//   k_ctc_align   one workgroup per batch row, one thread per state s (ctc_rows.h ctc_row_setup: the labels, the state flags and the
+//                 feasibility as k_ctc_rows has them).
+//     forward     delta rolled in two LDS buffers, one barrier per step, the emission gathers sixteen steps ahead (ctc_rows.h
+//                 ctc_run_ahead, k_ctc_rows' loop); per state a
 //                 compare chain (stay, s - 1, s - 2: a later one wins only when strictly greater) and one add, no transcendental.  The
 //                 choice, 0 / 1 / 2 states back, goes out as two wavefront ballots (bit 0, bit 1) per wave and step: lane 0 of each
 //                 wave stores them as ONE 16-byte vector store, T * blockDim / 64 * 16 bytes per row.
@@ -36,21 +38,15 @@ static CtcAlignWs align_carve(const astk_ctc_desc* d, void* base) {
   CtcAlignWs w;
   w.W = (2 * d->L + 1 + 63) / 64;
   const size_t bt = (size_t)d->B * d->T;
-  size_t off = 0;
-  auto take = [&](size_t nbytes) { const size_t o = off; off += (nbytes + 15) & ~(size_t)15; return (char*)base + o; };
-  w.lse = (float*)take(bt * 4);
-  w.bp = (ulonglong2*)take(bt * w.W * sizeof(ulonglong2));
-  w.feasible = (int*)take((size_t)d->B * 4);
-  w.bytes = off;
+  CtcBump c(base);
+  w.lse = c.take<float>(bt);
+  w.bp = c.take<ulonglong2>(bt * w.W);
+  w.feasible = c.take<int>((size_t)d->B);
+  w.bytes = c.off;
   return w;
 }
 
-struct CtcAlignArgs {
-  int T, V, L, first_label, blank;
-  long ldv, ldy;
-  const float* logits;
-  const int32_t* y;
-  const int32_t* len;
+struct CtcAlignArgs : CtcRowIn {
   int32_t* frame_state;        // (B, T)
   int32_t* frame_class;        // (B, T) or null
   int32_t* label_start;        // (B, L) or null
@@ -69,19 +65,11 @@ __global__ __launch_bounds__(CTC_ROW_THREADS) void k_ctc_align(CtcAlignArgs a, C
   const int b = blockIdx.x, tid = threadIdx.x, nt = blockDim.x;
   const int lane = tid & 63, wv = tid >> 6, W = nt >> 6;
   const int Tb = ctc_row_len(a.len, b, a.T);
-  if (tid == 0) s_rep = 0;
-  const int U = ctc_compact_labels(a.y + (long)b * a.ldy, a.L, a.first_label, a.V, a.blank, ext, wcnt);
-  const int S = 2 * U + 1;
-  const bool act = tid < S;
-  const int cls = act ? ext[tid] : a.blank;
-  const bool odd = act && (tid & 1);
-  const bool skip = odd && tid >= 3 && ext[tid - 2] != cls;            // the transition s - 2 -> s
-  const unsigned long long rm = __ballot(odd && tid >= 3 && ext[tid - 2] == cls);
-  if (lane == 0 && rm) atomicAdd(&s_rep, __popcll(rm));               // (an integer count: order-free)
-  for (int i = tid; i < 2 * (CTC_ROW_THREADS + 4); i += nt) (&dl[0][0])[i] = -INFINITY;
-  for (int i = tid; i < 2 * (ASTK_CTC_MAX_LABELS + 1); i += nt) (&span[0][0])[i] = 0;      // (a path through NaN logits may miss a label: an empty span)
-  __syncthreads();
-  const bool feasible = Tb >= U + s_rep;
+  const CtcRow r = ctc_row_setup(a, b, Tb, ext, wcnt, &s_rep, &dl[0][0]);
+  const int U = r.U, S = r.S;
+  const bool act = r.act, skip = r.skip, feasible = r.feasible;
+  // (a path through NaN logits may miss a label: an empty span; the spans are written behind the barriers of the recursion)
+  for (int i = tid; i < 2 * (ASTK_CTC_MAX_LABELS + 1); i += nt) (&span[0][0])[i] = 0;
   const int nv = feasible ? Tb : 0;                     // frames that carry a path
   int32_t* fs = a.frame_state + (size_t)b * a.T;
   int32_t* fc = a.frame_class ? a.frame_class + (size_t)b * a.T : nullptr;
@@ -102,49 +90,32 @@ __global__ __launch_bounds__(CTC_ROW_THREADS) void k_ctc_align(CtcAlignArgs a, C
   if (!feasible) return;
   if (tid == 0) dl[0][2] = 0.f;                         // the virtual step in front of t = 0: the path stands in front of state 0
   __syncthreads();
-  const float* lg = a.logits + (size_t)b * a.T * a.ldv + cls;
+  const float* lg = a.logits + (size_t)b * a.T * a.ldv + r.cls;
   const float* ls = w.lse + (size_t)b * a.T;
   ulonglong2* bp = w.bp + (size_t)b * a.T * W;
   int cur = 0;
   // ---- delta and the back-pointers, t = 0 .. len - 1
-  {
-    float xq[CTC_PF], lq[CTC_PF];
-#pragma unroll
-    for (int k = 0; k < CTC_PF; ++k) {
-      xq[k] = (act && k < Tb) ? lg[(size_t)k * a.ldv] : 0.f;
-      lq[k] = k < Tb ? ls[k] : 0.f;
-    }
-    for (int t0 = 0; t0 < Tb; t0 += CTC_PF) {
-      float xc[CTC_PF], lc[CTC_PF];
-#pragma unroll
-      for (int k = 0; k < CTC_PF; ++k) { xc[k] = xq[k]; lc[k] = lq[k]; }
-#pragma unroll
-      for (int k = 0; k < CTC_PF; ++k) {
-        const int t = t0 + CTC_PF + k;
-        xq[k] = (act && t < Tb) ? lg[(size_t)t * a.ldv] : 0.f;
-        lq[k] = t < Tb ? ls[t] : 0.f;
-      }
-#pragma unroll
-      for (int k = 0; k < CTC_PF; ++k) {
-        const int t = t0 + k;
-        if (t < Tb) {                                   // (uniform)
-          int back = 0;
-          if (act) {
-            const float* p = &dl[cur][2 + tid];
-            float best = p[0];
-            const float p1 = p[-1], p2 = skip ? p[-2] : -INFINITY;
-            if (p1 > best) { best = p1; back = 1; }
-            if (p2 > best) { best = p2; back = 2; }
-            dl[cur ^ 1][2 + tid] = best + (xc[k] - lc[k]);
-          }
-          const unsigned long long b0 = __ballot(back & 1), b1 = __ballot(back >> 1);
-          if (lane == 0) bp[(size_t)t * W + wv] = make_ulonglong2(b0, b1);
-          __syncthreads();
-          cur ^= 1;
+  ctc_run_ahead(
+      Tb,
+      [&](int t, float& x, float& l) {
+        l = t < Tb ? ls[t] : 0.f;                         // (the uniform guard first: it stays a scalar branch)
+        x = (act && t < Tb) ? lg[(size_t)t * a.ldv] : 0.f;
+      },
+      [&](int t, float x, float l) {
+        int back = 0;
+        if (act) {
+          const float* p = &dl[cur][2 + tid];
+          float best = p[0];
+          const float p1 = p[-1], p2 = skip ? p[-2] : -INFINITY;
+          if (p1 > best) { best = p1; back = 1; }
+          if (p2 > best) { best = p2; back = 2; }
+          dl[cur ^ 1][2 + tid] = best + (x - l);
         }
-      }
-    }
-  }
+        const unsigned long long b0 = __ballot(back & 1), b1 = __ballot(back >> 1);
+        if (lane == 0) bp[(size_t)t * W + wv] = make_ulonglong2(b0, b1);
+        __syncthreads();
+        cur ^= 1;
+      });
   // ---- the final state: the trailing blank, unless the last label is strictly better
   int sF = S - 1;
   if (S >= 2 && dl[cur][2 + S - 2] > dl[cur][2 + S - 1]) sF = S - 2;
@@ -233,16 +204,13 @@ int astk_ctc_align(const astk_ctc_desc* d, const float* logits, const int32_t* y
                    int32_t* frame_class, int32_t* label_start, int32_t* label_end, float* label_logp, float* row_score,
                    int32_t* n_infeasible, void* ws, size_t ws_bytes, void* stream) {
   ASTK_TRY(ctc_check_desc(d, "ctc_align"));
-  ASTK_CHECK(logits && y && frame_state && row_score && ws, "ctc_align: logits, y, frame_state, row_score and ws must not be null");
-  ASTK_CHECK(aligned16(ws), "ctc_align: the workspace must be 16-byte aligned");
   const CtcAlignWs w = align_carve(d, ws);
-  ASTK_CHECK(ws_bytes >= w.bytes, "ctc_align: workspace of %zu bytes, astk_ctc_align_workspace_bytes asks for %zu", ws_bytes, w.bytes);
+  ASTK_TRY(ctc_check_ptrs("ctc_align", logits && y && frame_state && row_score, "logits, y, frame_state, row_score", ws));
+  ASTK_TRY(ctc_check_ws_bytes("ctc_align", "ctc_align", ws_bytes, w.bytes));
   hipStream_t s = (hipStream_t)stream;
   ASTK_TRY(ctc_lse_launch(d, logits, input_len, w.lse, s));
   CtcAlignArgs a;
-  a.T = d->T; a.V = d->V; a.L = d->L; a.first_label = d->first_label; a.blank = d->blank;
-  a.ldv = d->ldv; a.ldy = d->ldy;
-  a.logits = logits; a.y = y; a.len = input_len;
+  ctc_row_in(a, d, logits, y, input_len);
   a.frame_state = frame_state; a.frame_class = frame_class; a.label_start = label_start; a.label_end = label_end;
   a.label_logp = label_logp; a.row_score = row_score;
   hipLaunchKernelGGL(k_ctc_align, dim3(d->B), dim3(w.W * 64), 0, s, a, w);     // one thread per state of the longest row the descriptor admits (<= 512)

@@ -3,7 +3,7 @@
 // (tests/ctc_beam_model.py).  logits is only read.
 //
 // Two launches on the caller's stream:
-//   k_ctc_beam_frames  one wavefront per valid frame (b, t): the float64 log-sum-exp over V (maximum subtracted), the blank's
+//   k_ctc_beam_frames  one wavefront per valid frame (b, t): the float64 log-sum-exp over V (ctc_rows.h ctc_wave_lse), the blank's
 //                      log-probability and the C best labels >= first_label in the candidate order (higher first, equal ones lower id
 //                      first).  Independent of the recursion, coalesced over V.
 //   k_ctc_beam_scan    one workgroup per row, one thread per candidate: thread j < N is the stay candidate of slot j, thread
@@ -53,26 +53,18 @@ static int table_bits(long nodes) {
 static CtcBeamWs beam_carve(const astk_ctc_beam_desc* d, void* base) {
   CtcBeamWs w;
   const size_t bt = (size_t)d->B * d->T;
-  size_t off = 0;
-  auto take = [&](size_t nbytes) { const size_t o = off; off += (nbytes + 15) & ~(size_t)15; return (char*)base + o; };
+  CtcBump c(base);
   w.tab_bits = table_bits((long)d->T * d->N + 1);
-  w.fr = (double2*)take(bt * sizeof(double2));
-  w.px = (double*)take(bt * d->C * 8);
-  w.pid = (int*)take(bt * d->C * 4);
-  w.tab = (unsigned long long*)take(((size_t)d->B << w.tab_bits) * 8);
-  w.bytes = off;
+  w.fr = c.take<double2>(bt);
+  w.px = c.take<double>(bt * d->C);
+  w.pid = c.take<int>(bt * d->C);
+  w.tab = c.take<unsigned long long>((size_t)d->B << w.tab_bits);
+  w.bytes = c.off;
   return w;
 }
 
 // the proposal order of one frame: higher log-probability first, equal ones lower id first
 __device__ __forceinline__ bool cb_before(double a, int ia, double b, int ib) { return a > b || (a == b && ia < ib); }
-
-// log(exp(a) + exp(b)), symmetric in its arguments; -inf for two -inf terms
-__device__ __forceinline__ double cb_logadd(double a, double b) {
-  const double m = fmax(a, b);
-  if (m == -INFINITY) return -INFINITY;
-  return m + log1p(exp(fmin(a, b) - m));
-}
 
 __global__ __launch_bounds__(256) void k_ctc_beam_frames(int B, int T, int V, long ldv, int C, int first_label, int blank,
                                                          const float* __restrict__ logits, const int32_t* __restrict__ len, CtcBeamWs w) {
@@ -82,15 +74,7 @@ __global__ __launch_bounds__(256) void k_ctc_beam_frames(int B, int T, int V, lo
   const int b = (int)(f / T), t = (int)(f - (long)b * T);
   if (t >= ctc_row_len(len, b, T)) return;
   const float* x = logits + f * ldv;
-  double mx = -INFINITY;
-  for (int v = lane; v < V; v += 64) mx = fmax(mx, (double)x[v]);
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) mx = fmax(mx, __shfl_xor(mx, o));
-  double sum = 0.0;
-  for (int v = lane; v < V; v += 64) sum += exp((double)x[v] - mx);
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) sum += __shfl_xor(sum, o);
-  const double lse = log(sum) + mx;
+  const double lse = ctc_wave_lse<double>(x, V, lane);
   if (lane == 0) w.fr[f] = make_double2((double)x[blank] - lse, lse);
   double pv = INFINITY;
   int pi = -1;
@@ -215,8 +199,8 @@ __global__ __launch_bounds__(CB_THREADS) void k_ctc_beam_scan(CtcBeamArgs a, Ctc
       // ---- B: the scores
       if (is_stay) {
         const double m = s_mrg[tid];
-        if (m > -INFINITY) my_pnb = cb_logadd(my_pnb, m);
-        my_score = cb_logadd(my_pb, my_pnb);
+        if (m > -INFINITY) my_pnb = lae(my_pnb, m);
+        my_score = lae(my_pb, my_pnb);
       }
       if (tid < ncand) c_score[tid] = my_score;
       const bool live = my_score > -INFINITY;
@@ -342,10 +326,9 @@ size_t astk_ctc_beam_workspace_bytes(const astk_ctc_beam_desc* d) {
 int astk_ctc_beam(const astk_ctc_beam_desc* d, const float* logits, const int32_t* input_len, int32_t* tokens, int32_t* n_labels,
                   double* score, void* ws, size_t ws_bytes, void* stream) {
   ASTK_TRY(beam_check_desc(d, "ctc_beam"));
-  ASTK_CHECK(logits && tokens && n_labels && score && ws, "ctc_beam: logits, tokens, n_labels, score and ws must not be null");
-  ASTK_CHECK(aligned16(ws), "ctc_beam: the workspace must be 16-byte aligned");
   const CtcBeamWs w = beam_carve(d, ws);
-  ASTK_CHECK(ws_bytes >= w.bytes, "ctc_beam: workspace of %zu bytes, astk_ctc_beam_workspace_bytes asks for %zu", ws_bytes, w.bytes);
+  ASTK_TRY(ctc_check_ptrs("ctc_beam", logits && tokens && n_labels && score, "logits, tokens, n_labels, score", ws));
+  ASTK_TRY(ctc_check_ws_bytes("ctc_beam", "ctc_beam", ws_bytes, w.bytes));
   hipStream_t s = (hipStream_t)stream;
   const unsigned frames = (unsigned)((size_t)d->B * d->T);
   hipLaunchKernelGGL(k_ctc_beam_frames, dim3((frames + 3) / 4), dim3(256), 0, s, d->B, d->T, d->V, d->ldv, d->C, d->first_label, d->blank,

@@ -1,7 +1,8 @@
 // CTC prefix scores for the joint CTC-attention beam search (include/astk.h "joint CTC-attention beam search").
 //
 // Once per search (ctc_prefix_init_launch):
-//   k_ctcp_lse        one wavefront per frame (u, t < T''_u): the float64 log-sum-exp of the head's float32 logits
+//   k_ctcp_lse        one wavefront per frame (u, t < T''_u): the float64 log-sum-exp of the head's float32 logits (ctc_rows.h
+//                     ctc_wave_lse)
 //   k_ctcp_transpose  the logits as (U, V, Tp): a candidate's column x[.][c] becomes contiguous over t (64 x 64 tiles through LDS)
 //   k_ctcp_empty      one thread per utterance: the empty prefix's state in slot 0, att_score = psi = 0 and n_labels = 0 in every slot
 // Once per step (ctc_prefix_score_launch), for every live row and each of its K proposals:
@@ -16,8 +17,8 @@
 //                     (the measurement the copy was chosen by: DESIGN.md section 30).
 //   k_ctcp_serial     the plain form, one thread per candidate, serial over the frames (test-hook build only: the operator test's
 //                     second implementation, and the launch the shipped one is measured against)
-// Everything is float64 in the log domain; logaddexp of two dead terms is -inf, never NaN.
-#include "common.h"
+// Everything is float64 in the log domain; logaddexp (ctc_rows.h lae) of two dead terms is -inf, never NaN.
+#include "ctc_rows.h"
 
 namespace astk {
 
@@ -25,28 +26,14 @@ namespace {
 
 constexpr int ST_LIVE = 1;
 
-__device__ __forceinline__ double lae(double a, double b) {
-  const double m = fmax(a, b);
-  if (m == -INFINITY) return -INFINITY;
-  return m + log1p(exp(fmin(a, b) - m));
-}
-
 __global__ __launch_bounds__(256) void k_ctcp_lse(int U, int T, int V, long ldv, const float* __restrict__ logits,
                                                   const int32_t* __restrict__ row_len, int N, double* __restrict__ lse) {
   const long f = (long)blockIdx.x * 4 + (threadIdx.x >> 6);
   if (f >= (long)U * T) return;
   const int u = (int)(f / T), t = (int)(f % T), lane = threadIdx.x & 63;
   if (t >= row_len[(long)u * N]) return;
-  const float* x = logits + f * ldv;
-  double mx = -INFINITY;
-  for (int v = lane; v < V; v += 64) mx = fmax(mx, (double)x[v]);
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) mx = fmax(mx, __shfl_xor(mx, o));
-  double sum = 0.0;
-  for (int v = lane; v < V; v += 64) sum += exp((double)x[v] - mx);
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) sum += __shfl_xor(sum, o);
-  if (lane == 0) lse[f] = log(sum) + mx;
+  const double l = ctc_wave_lse<double>(logits + f * ldv, V, lane);
+  if (lane == 0) lse[f] = l;
 }
 
 // grid (ceil(T / 64), ceil(V / 64), U), 256 threads: tile[t][v] in, [v][t] out; frames behind T''_u are written as 0 and not read

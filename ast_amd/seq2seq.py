@@ -1208,11 +1208,15 @@ class SpeechEncoderDecoder:
                                             _vp(st["enc_states"]), _vp(st["d_enc"]), a.g("ctc_out/W"), a.g("ctc_out/b"),
                                             _lib.PREC_BY_NAME[self.gemm_precision], 1 if self.deterministic else 0, s))
 
-    def ctc_predict(self, X, x_lens=None):
-        """Greedy decode of the CTC head (eval mode): encode the batch, the head's logits, the per-frame argmax over each row's valid
-        frames (astk_ctc_greedy), then on the host repeats collapsed and blanks dropped.  Returns a list of token lists."""
+    def _ctc_eval_logits(self, who, X, x_lens, refuse=None):
+        """What the CTC head's eval-mode methods open with: the head check (`who` names the method in its message; refuse(), if
+        given, then raises for the method's own arguments, before the library or the device is touched), the inputs on the device,
+        the eval-mode encode, the rows' frames behind the CNN and the head's logits.  Returns the library, X and x_lens as checked,
+        the shape state, the stream, the device lengths (or None), the logits and their leading dimension Vp."""
         if not self.ctc_head:
-            raise ValueError("ctc_predict needs the CTC head: set rnn_config.ctc = true in model_cfg.json")
+            raise ValueError(f"{who} needs the CTC head: set rnn_config.ctc = true in model_cfg.json")
+        if refuse is not None:
+            refuse()
         lib = self._require_gpu()
         X = self._as_input(X)
         if x_lens is not None:
@@ -1223,6 +1227,24 @@ class SpeechEncoderDecoder:
         st, s = self._cur, self._stream()
         lens = self._t2_lens(st, x_lens)
         logits, Vp = self._ctc_logits(st, s)
+        return lib, X, x_lens, st, s, lens, logits, Vp
+
+    def _int32_parts(self, name, sizes):
+        """One pooled int32 buffer of sum(sizes) 4-byte words for everything a call sends back to the host (a float64 part goes first:
+        8-byte aligned).  Returns the pointer of every part and read(): ONE device-to-host copy, the parts as numpy int32 views."""
+        cuts = np.cumsum([0] + list(sizes))
+        out = self._pool(name, (int(cuts[-1]),), torch.int32)
+        ptrs = [C.c_void_p(out.data_ptr() + 4 * int(c)) for c in cuts[:-1]]
+
+        def read():
+            host = out.cpu().numpy()
+            return [host[a:b] for a, b in zip(cuts[:-1], cuts[1:])]
+        return ptrs, read
+
+    def ctc_predict(self, X, x_lens=None):
+        """Greedy decode of the CTC head (eval mode): encode the batch, the head's logits, the per-frame argmax over each row's valid
+        frames (astk_ctc_greedy), then on the host repeats collapsed and blanks dropped.  Returns a list of token lists."""
+        lib, X, x_lens, st, s, lens, logits, Vp = self._ctc_eval_logits("ctc_predict", X, x_lens)
         B, T2 = st["B"], st["T2"]
         cdesc = _lib.CtcDesc(B, T2, self.V, Vp, 1, 1, UNK_ID, PAD_ID)
         best = self._pool("ctc_best", (B, T2), torch.int32)
@@ -1238,22 +1260,14 @@ class SpeechEncoderDecoder:
         probable label strings of every row over its valid frames with C labels proposed per frame (astk_ctc_beam); ONE device-to-host
         copy.  Returns per row a list in rank order of {"hyp": [GO] + labels + [EOS], "score", "labels"}; score = the pruned float64
         sum over the string's alignments, a lower bound of log p_ctc(labels).  max_labels (default min(T'', 255)) caps the strings."""
-        if not self.ctc_head:
-            raise ValueError("ctc_beam needs the CTC head: set rnn_config.ctc = true in model_cfg.json")
         import ctypes                                        # (the parameter C shadows the module's alias)
-        N, C = checked_ctc_beam_width(N, C, self.V)
-        if max_labels is not None and not 1 <= int(max_labels) <= _lib.CTC_MAX_LABELS:
-            raise ValueError(f"ctc_beam: max_labels must lie in 1..{_lib.CTC_MAX_LABELS}, got {max_labels!r}")
-        lib = self._require_gpu()
-        X = self._as_input(X)
-        if x_lens is not None:
-            x_lens = checked_x_lens(x_lens, X.shape[0], X.shape[1])
-        with using_config("train", False):
-            self._cur = None
-            self.encode(X)
-        st, s = self._cur, self._stream()
-        lens = self._t2_lens(st, x_lens)
-        logits, Vp = self._ctc_logits(st, s)
+
+        def refuse():
+            nonlocal N, C
+            N, C = checked_ctc_beam_width(N, C, self.V)
+            if max_labels is not None and not 1 <= int(max_labels) <= _lib.CTC_MAX_LABELS:
+                raise ValueError(f"ctc_beam: max_labels must lie in 1..{_lib.CTC_MAX_LABELS}, got {max_labels!r}")
+        lib, X, x_lens, st, s, lens, logits, Vp = self._ctc_eval_logits("ctc_beam", X, x_lens, refuse)
         B, T2 = st["B"], st["T2"]
         if T2 > _lib.CTC_BEAM_MAX_T:
             raise ValueError(f"ctc_beam: {T2} encoder frames exceed the {_lib.CTC_BEAM_MAX_T} a row is limited to")
@@ -1265,13 +1279,10 @@ class SpeechEncoderDecoder:
         ws = self._workspace("ctc", nbytes)
         # everything that goes back to the host, in one buffer of 4-byte words: score (B, N) float64 first (8-byte aligned), then
         # n_labels (B, N) and tokens (B, N, Lm)
-        cuts = np.cumsum([0, 2 * B * N, B * N, B * N * Lm])
-        out = self._pool("ctc_beam_out", (int(cuts[-1]),), torch.int32)
-        p = [ctypes.c_void_p(out.data_ptr() + 4 * int(c)) for c in cuts[:-1]]
+        p, read = self._int32_parts("ctc_beam_out", [2 * B * N, B * N, B * N * Lm])
         check(lib.astk_ctc_beam(ctypes.byref(bdesc), _vp(logits), _vp(lens), p[2], p[1], p[0], _vp(ws), ws.numel(), s))
-        host = out.cpu().numpy()
-        score = host[:cuts[1]].view(np.float64).reshape(B, N)
-        n_lab, tok = host[cuts[1]:cuts[2]].reshape(B, N), host[cuts[2]:].reshape(B, N, Lm)
+        part = read()
+        score, n_lab, tok = part[0].view(np.float64).reshape(B, N), part[1].reshape(B, N), part[2].reshape(B, N, Lm)
         rows = []
         for b in range(B):
             row = []
@@ -1294,28 +1305,19 @@ class SpeechEncoderDecoder:
           label_logp (U,), confidence (U,) = exp(label_logp / frames in the label), score = the best path's log-probability,
           total_logp = log p_ctc(labels), the sum over all paths (score <= total_logp; the difference says how peaked the alignment is).
         A row without a path (fewer frames than labels + adjacent repeats): score = total_logp = -inf, segments all -1."""
-        if not self.ctc_head:
-            raise ValueError("ctc_align needs the CTC head: set rnn_config.ctc = true in model_cfg.json")
-        lib = self._require_gpu()
-        X = self._as_input(X)
-        if x_lens is not None:
-            x_lens = checked_x_lens(x_lens, X.shape[0], X.shape[1])
-        if isinstance(y, np.ndarray):
-            y = torch.from_numpy(y)
+        def refuse():                                        # (the shapes alone, on the host: y moves to the device behind the checks)
+            nonlocal y
+            if isinstance(y, np.ndarray):
+                y = torch.from_numpy(y)
+            if y.dim() != 2 or y.shape[0] != X.shape[0]:
+                raise ValueError(f"ctc_align: y must be (B = {X.shape[0]}, L), got {tuple(y.shape)}")
+            if y.shape[1] < 1:
+                raise ValueError("ctc_align: y holds no column")
+            if y.shape[1] > _lib.CTC_MAX_LABELS:
+                raise ValueError(f"ctc_align: targets of padded length {int(y.shape[1])} exceed ASTK_CTC_MAX_LABELS = {_lib.CTC_MAX_LABELS}")
+        lib, X, x_lens, st, s, lens, logits, Vp = self._ctc_eval_logits("ctc_align", X, x_lens, refuse)
         y = y.to(self.device, torch.int32).contiguous()
-        if y.dim() != 2 or y.shape[0] != X.shape[0]:
-            raise ValueError(f"ctc_align: y must be (B = {X.shape[0]}, L), got {tuple(y.shape)}")
         L = int(y.shape[1])
-        if L < 1:
-            raise ValueError("ctc_align: y holds no column")
-        if L > _lib.CTC_MAX_LABELS:
-            raise ValueError(f"ctc_align: targets of padded length {L} exceed ASTK_CTC_MAX_LABELS = {_lib.CTC_MAX_LABELS}")
-        with using_config("train", False):
-            self._cur = None
-            self.encode(X)
-        st, s = self._cur, self._stream()
-        lens = self._t2_lens(st, x_lens)
-        logits, Vp = self._ctc_logits(st, s)
         B, T2 = st["B"], st["T2"]
         cdesc = _lib.CtcDesc(B, T2, self.V, Vp, L, L, UNK_ID, PAD_ID)
         need_a, need_l = int(lib.astk_ctc_align_workspace_bytes(C.byref(cdesc))), int(lib.astk_ctc_workspace_bytes(C.byref(cdesc)))
@@ -1324,15 +1326,12 @@ class SpeechEncoderDecoder:
         ws = self._workspace("ctc", max(need_a, need_l))
         # everything that goes back to the host, in one buffer of 4-byte words: frame_state, frame_class (B, T''); label_start,
         # label_end, label_logp (B, L); row_score, row_nll (B)
-        cuts = np.cumsum([0, B * T2, B * T2, B * L, B * L, B * L, B, B])
-        out = self._pool("ctc_align_out", (int(cuts[-1]),), torch.int32)
-        p = [C.c_void_p(out.data_ptr() + 4 * int(c)) for c in cuts[:-1]]
+        p, read = self._int32_parts("ctc_align_out", [B * T2, B * T2, B * L, B * L, B * L, B, B])
         check(lib.astk_ctc_align(C.byref(cdesc), _vp(logits), _vp(y), _vp(lens), p[0], p[1], p[2], p[3], p[4], p[5], None, _vp(ws),
                                  ws.numel(), s))
         # the full-sum score behind the alignment: astk_ctc_loss as it is, which leaves its gradient in place of the logits
         check(lib.astk_ctc_loss(C.byref(cdesc), _vp(logits), _vp(y), _vp(lens), 1.0, p[6], None, _vp(logits), None, _vp(ws), ws.numel(), s))
-        host = out.cpu().numpy()
-        part = [host[a:b] for a, b in zip(cuts[:-1], cuts[1:])]
+        part = read()
         fs, fc = part[0].reshape(B, T2), part[1].reshape(B, T2)
         l0, l1, lp = part[2].reshape(B, L), part[3].reshape(B, L), part[4].view(np.float32).reshape(B, L)
         score, nll = part[5].view(np.float32), part[6].view(np.float32)

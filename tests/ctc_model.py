@@ -136,7 +136,8 @@ def _distinct(first, n):
 # name -> dict(kind, family, B, T, V, L, rows = per row a label count or an explicit label list, lens, ldv pad).  The smallest shapes at
 # which the kernels can go wrong: V below / no multiple of / above a wavefront and of 4; one row, a few, more rows than a wave set; T = 1,
 # 2; U = 0, 1; S' = 63, 65, 129, 511 around the wavefront boundaries; T = U + repeats (exactly one path); all labels equal; ragged
-# lengths down to 1; an infeasible row between feasible ones (U = 255 in 64 frames).  `family` names the tolerance the case is held to.
+# lengths down to 1; an infeasible row between feasible ones (U = 255 in 64 frames); row lengths one short of, at and one past
+# the step loop's block of 16 (ctc_rows.h CTC_PF).  `family` names the tolerance the case is held to.
 OP_CASES = {
     "t1-v5": dict(kind="normal", family="short", B=3, T=1, V=5, L=4, rows=[0, [4], 0], lens=None),
     "t2-v5": dict(kind="normal", family="short", B=3, T=2, V=5, L=4, rows=[0, [3], [3, 4]], lens=[2, 1, 2]),
@@ -154,6 +155,7 @@ OP_CASES = {
     "u255-infeasible-between": dict(kind="normal", family="long", B=3, T=64, V=57, L=255, rows=[5, 255, 64], lens=[64, 64, 64]),
     "u255-s511": dict(kind="normal", family="s511", B=1, T=300, V=57, L=255, rows=[255], lens=None),
     "ldv-pad": dict(kind="normal", family="long", B=3, T=64, V=57, L=40, rows=[32, 31, 1], lens=[64, 40, 1], ldv=64),
+    "t17-blocks": dict(kind="normal", family="long", B=3, T=17, V=57, L=6, rows=[2, [5, 5, 9], 4], lens=[16, 17, 15]),
 }
 
 
