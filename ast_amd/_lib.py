@@ -362,6 +362,7 @@ SIGNATURES = {
     "astk_device_cu_count": (C.c_int, []),
     "astk_lstm_stack_path": (C.c_int, [C.POINTER(LstmStackDesc)]),
     "astk_lstm_stack_free_cus": (C.c_int, [C.POINTER(LstmStackDesc)]),
+    "astk_lstm_stack_form": (C.c_int, [C.POINTER(LstmStackDesc), C.POINTER(C.c_int), C.POINTER(C.c_int)]),
     "astk_lstm_stack_side_plan": (C.c_int, [C.POINTER(LstmStackDesc), C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_int)]),
     "astk_decoder_path": (C.c_int, [C.POINTER(DecoderDesc)]),
     "astk_prof_begin": (C.c_int, []),

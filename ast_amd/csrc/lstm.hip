@@ -36,15 +36,17 @@ enum LstmPath { LSTM_PER_STEP = 0, LSTM_PERSIST = 1, LSTM_HOISTED = 2 };      //
 struct LstmRoute {
   LstmPath path;
   int rows;        // form of the recurrence workgroups (lstm_persist.h: LSTM_ROWS_16, _MT2 or _DUO); 16 on the hoisted path
+  int xs;          // arithmetic of the recurrence kernels of that form (lstm_persist.h: LSTM_XS_*), what astk_lstm_stack_form reports
   int lpl;         // layers per launch: groups start at multiples of it (<= n_layers; 1 on the hoisted path)
   int wgs_first;   // workgroups of the first launch: what the side-stream plans leave to the recurrence
   int wg_rows;     // (virtual) workgroup rows of a cell: rows of the counters, arrivals per unit slice, rows of the db sums
 };
 LstmRoute lstm_route(const astk_lstm_stack_desc* d) {
-  LstmRoute R = {LSTM_PER_STEP, LSTM_ROWS_16, 0, 0, lstm_persist_wg_rows(d->B, LSTM_ROWS_16)};
+  LstmRoute R = {LSTM_PER_STEP, LSTM_ROWS_16, lstm_persist_xs(d->h, LSTM_ROWS_16), 0, 0, lstm_persist_wg_rows(d->B, LSTM_ROWS_16)};
   if (!lstm_persist_applicable(d->T, d->B, d->h, d->n_layers, d->n_dirs)) return R;
   R.path = lstm_persist_hoisted(d->h) ? LSTM_HOISTED : LSTM_PERSIST;
   R.rows = lstm_persist_rows(d->B, d->h, d->n_layers, d->n_dirs, d->side_stream != nullptr);
+  R.xs = lstm_persist_xs(d->h, R.rows);
   R.lpl = lstm_persist_layers_per_launch(d->B, d->h, d->n_layers, d->n_dirs, R.rows);
   R.wgs_first = lstm_persist_grid_wgs(d->B, d->h, R.lpl, d->n_dirs, R.rows);
   R.wg_rows = lstm_persist_wg_rows(d->B, R.rows);
@@ -851,6 +853,17 @@ int astk_lstm_stack_free_cus(const astk_lstm_stack_desc* d) {
   PrecScope prec_scope(d->precision, d->gemm_operands);
   const LstmRoute R = lstm_route(d);
   return R.path == LSTM_PER_STEP ? 0 : std::max(0, device_cu_count() - R.wgs_first);
+}
+
+int astk_lstm_stack_form(const astk_lstm_stack_desc* d, int* rows, int* xs) {
+  ASTK_CHECK_DESC(d, astk_lstm_stack_desc);
+  ASTK_CHECK(d->T > 0 && d->B > 0 && d->in_dim > 0 && d->h > 0 && d->n_layers >= 1 && d->n_layers <= ASTK_MAX_RNN_LAYERS && (d->n_dirs == 1 || d->n_dirs == 2),
+             "lstm_stack_form: bad dims");
+  PrecScope prec_scope(d->precision, d->gemm_operands);
+  const LstmRoute R = lstm_route(d);
+  if (rows) *rows = R.rows;
+  if (xs) *xs = R.xs;
+  return 0;
 }
 
 size_t astk_lstm_stack_workspace_bytes(const astk_lstm_stack_desc* d) {

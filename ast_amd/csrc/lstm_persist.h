@@ -30,6 +30,9 @@ constexpr int LSTM_ROWS_16 = 16, LSTM_ROWS_MT2 = 32, LSTM_ROWS_DUO = 33;
 // splits; bf16x3 = three-term bf16 splits, resident weights in registers (h <= 256); bf16x3 with the weights' lo plane in LDS (h >= 512)
 constexpr int LSTM_XS_F32 = 0, LSTM_XS_FP16X2 = 2, LSTM_XS_BF16X3 = 3, LSTM_XS_BF16X3_LDS = 4;
 int lstm_persist_rows(int B, int h, int nl, int nd, bool side);
+// The arithmetic (LSTM_XS_*) of the kernels a launch of form `rows` at width h runs under the mode and the knobs in force: what the
+// launchers instantiate (the DUO form is bf16x3 with the lo plane in LDS at every width)
+int lstm_persist_xs(int h, int rows);
 // (Virtual) workgroup rows of a cell under form `rows`: 16-row batch tiles at 16; at 33 two virtual workgroups per 32 rows, so an EVEN number
 // of 16-row tiles (what lstm.hip sizes the workspace for, whatever the form); at 32 one workgroup per 32 rows.  The grid has as many rows at 16
 // and 32, half as many at 33.  Rows of the arrival counters (the abort word sits behind them), arrivals per unit slice on a progress counter,

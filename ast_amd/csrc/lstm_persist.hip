@@ -1250,6 +1250,8 @@ static int recurrence_xs(int h) {
 }
 // the DUO form runs where the arithmetic is bf16x3 with the weights in registers (h <= 256) and the lo plane may live in LDS
 static bool duo_available(int xs) { return xs == LSTM_XS_BF16X3 && tune_on(TUNE_LSTM_X4); }
+// what launch_recurrence instantiates: the DUO kernels are the XS = 4 code whatever the width
+int lstm_persist_xs(int h, int rows) { return rows == LSTM_ROWS_DUO ? LSTM_XS_BF16X3_LDS : recurrence_xs(h); }
 int lstm_persist_wg_rows(int B, int rows) {
   return rows == LSTM_ROWS_16 ? (B + 15) / 16 : rows == LSTM_ROWS_DUO ? 2 * ((B + 31) / 32) : (B + 31) / 32;
 }

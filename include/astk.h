@@ -1235,6 +1235,14 @@ int astk_lstm_stack_path(const astk_lstm_stack_desc* d);
 /* CUs the persistent recurrence launches of this shape leave FREE on the current device (0: not the persistent path, or none): what a
  * caller may pass as `side_wgs` for work it runs on a second stream beside the recurrences (astk_decoder_desc.side_wgs). */
 int astk_lstm_stack_free_cus(const astk_lstm_stack_desc* d);
+/* Which recurrence kernels astk_lstm_stack_fwd / _bwd would launch for this descriptor on the current device -- `precision` and `side_stream`
+ * as the calls would see them, under the tuning table in force.  Read-only.  *rows: the workgroup form, 16 = one 16-row batch tile per
+ * workgroup, 32 = two tiles against one set of weight fragments ("lstm.rows32" 1), 33 = two virtual 16-row workgroups in one of 512 threads
+ * ("lstm.rows32" 2, bf16x3 only).  *xs: the arithmetic of the recurrences' products, 0 = f32 MFMAs, 2 = fp16x2, 3 = bf16x3 with all three
+ * planes of the weights in registers, 4 = bf16x3 with the weights' lowest plane in LDS (h >= 512, and the form 33).  On the per-step path
+ * (astk_lstm_stack_path 0) no recurrence kernel runs and the values say what one would be.  Either pointer may be NULL.  Returns 0, or -1 for
+ * a bad descriptor (astk_last_error). */
+int astk_lstm_stack_form(const astk_lstm_stack_desc* d, int* rows, int* xs);
 /* What astk_lstm_stack_fwd / _bwd (with an input gradient) would run beside the recurrences for this descriptor -- `side_stream`, `side_wgs`,
  * `precision` and `deterministic` as the calls would see them -- on the current device, under the tuning table in force: the loop steps of the
  * layer-0 input projection multiplied in line (T: all of them), the chunks of it on the side stream, and the chunks of the input gradient on
