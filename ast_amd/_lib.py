@@ -376,6 +376,9 @@ TEST_HOOK_SIGNATURES = {
     "astk_conv_debug_kill_units": (C.c_int, [_VP, _I]),
     "astk_debug_gemm_group": (C.c_int, [_I, _I, c_int_p, c_int_p, c_int_p, C.POINTER(C.c_void_p), C.POINTER(C.c_void_p), C.POINTER(C.c_void_p), _I, _I, _VP]),
     "astk_debug_gemm_group_lowp": (C.c_int, [_I, _I] + [c_int_p] * 7 + [C.POINTER(C.c_void_p), C.POINTER(C.c_long), C.POINTER(C.c_long)] * 3 + [_I, _I, _VP]),
+    "astk_debug_gemm_views": (C.c_int, [_I, _I] + [c_int_p] * 7 + [C.POINTER(C.c_void_p), C.POINTER(C.c_long), C.POINTER(C.c_long)] * 3
+                              + [c_int_p, C.POINTER(C.c_long), C.POINTER(C.c_long), C.POINTER(C.c_void_p), C.POINTER(C.c_long)] * 2
+                              + [c_int_p, C.POINTER(C.c_long), C.POINTER(C.c_long), C.POINTER(C.c_void_p), _I, _I, _I, C.c_char_p, _SZ, _VP]),
     "astk_debug_gemm_plan": (C.c_int, [_I, _I] + [c_int_p] * 7 + [_I] * 6 + [C.c_char_p, _SZ]),
     "astk_debug_rowgemm": (C.c_int, [C.POINTER(DebugRowGemmArgs), c_int_p, _VP]),
     "astk_debug_lstm_cell_fwd": (C.c_int, [C.POINTER(DebugCellFwdArgs), _I, c_int_p, _VP]),

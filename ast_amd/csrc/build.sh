@@ -2,7 +2,7 @@
 # Builds (gfx950 only, in-tree):
 #   ast_amd/libastk.so       the product library
 #   ast_amd/libastk_test.so  the same sources with -DASTK_TEST_HOOKS: adds the test instrumentation entry points (astk_conv_debug_*,
-#                            astk_debug_set_amax_generation, astk_debug_gemm_group, astk_debug_gemm_group_lowp, astk_debug_gemm_plan, and the row-panel launchers of rowgemm.hip:
+#                            astk_debug_set_amax_generation, astk_debug_gemm_group, astk_debug_gemm_group_lowp, astk_debug_gemm_views, astk_debug_gemm_plan, and the row-panel launchers of rowgemm.hip:
 #                            astk_debug_rowgemm, astk_debug_lstm_cell_fwd / _bwd, and the prefix scorer astk_debug_ctc_prefix) that the product library does not export; loaded by
 #                            tests only
 set -e

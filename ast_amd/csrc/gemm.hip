@@ -1922,6 +1922,101 @@ extern "C" int astk_debug_gemm_group_lowp(int layout, int n, const int* M, const
   for (int i = 0; i < n; ++i) g[i] = with_amax_b(with_amax_a(g[i], h[2 * i]), h[2 * i + 1]);
   return gemm_launch_group(layout, g, n, s);
 }
+// libastk_test.so only: astk_debug_gemm_group_lowp with the addressing an op can give each operand -- two-level rows (tn, sg, st), indexed
+// rows (rowidx into an array of idx_rows rows; 0: a permutation of the operand's own rows) and two-level C rows -- and a bias, through the
+// real gemm_launch_group under the process default of "gemm.deterministic".  The plan of the launch goes to plan_out as text (the
+// "gemm.log" lines) when plan_out is given; launch = 0 stops there: no operand is touched and no HIP call is made.  A measured operand
+// (measure bit) must have plain rows: the launch's own maximum pass serves the others.
+extern "C" int astk_debug_gemm_views(int layout, int n, const int* M, const int* N, const int* K, const int* batch, const int* mode, const int* lowp,
+                                     const int* measure, const float* const* A, const long* lda, const long* sA, const float* const* B,
+                                     const long* ldb, const long* sB, float* const* C, const long* ldc, const long* sC,
+                                     const int* a_tn, const long* a_sg, const long* a_st, const int* const* a_rowidx, const long* a_idx_rows,
+                                     const int* b_tn, const long* b_sg, const long* b_st, const int* const* b_rowidx, const long* b_idx_rows,
+                                     const int* c_tn, const long* c_sg, const long* c_st, const float* const* bias, int precision,
+                                     int gemm_operands, int launch, char* plan_out, size_t plan_bytes, void* stream) {
+  using namespace astk;
+  ASTK_CHECK(n >= 1 && n <= GEMM_GROUP_MAX && layout >= GEMM_NT && layout <= GEMM_TN, "debug_gemm_views: bad arguments");
+  ASTK_CHECK(M && N && K && batch && mode && lowp && measure && A && lda && sA && B && ldb && sB && C && ldc && sC && a_tn && a_sg && a_st && a_rowidx &&
+                 a_idx_rows && b_tn && b_sg && b_st && b_rowidx && b_idx_rows && c_tn && c_sg && c_st,
+             "debug_gemm_views: null argument array (only bias, plan_out and stream may be null)");
+  hipStream_t s = (hipStream_t)stream;
+  PrecScope prec_scope(precision, gemm_operands);
+  DetScope det_scope(0);
+  GemmArgs g[GEMM_GROUP_MAX];
+  AmaxMatrix am[2 * GEMM_GROUP_MAX];
+  static const unsigned long long* const maximum = (const unsigned long long*)(uintptr_t)0x4000;      // (plan only: never read)
+  auto view = [](const float* p, long ld, int tn, long sg, long st, const int* idx, long idx_rows) {
+    MatView v = tn > 0 ? mat2(p, tn, sg, st) : mat_idx(p, ld, idx);
+    v.idx_rows = idx_rows;
+    return v;
+  };
+  for (int i = 0; i < n; ++i) {
+    const long rowsA = layout == GEMM_TN ? K[i] : M[i], innerA = layout == GEMM_TN ? M[i] : K[i];
+    const long rowsB = layout == GEMM_NT ? N[i] : K[i], innerB = layout == GEMM_NT ? K[i] : N[i];
+    const bool plainA = a_tn[i] <= 0 && !a_rowidx[i], plainB = b_tn[i] <= 0 && !b_rowidx[i];
+    ASTK_CHECK(M[i] > 0 && N[i] > 0 && K[i] > 0 && batch[i] >= 1 && mode[i] >= GEMM_STORE && mode[i] <= GEMM_ATOMIC && A[i] && B[i] && C[i] &&
+                   (a_tn[i] > 0 || lda[i] >= innerA) && (b_tn[i] > 0 || ldb[i] >= innerB) && (c_tn[i] > 0 || ldc[i] >= N[i]),
+               "debug_gemm_views: product %d: bad shape, mode or leading dimension", i);
+    ASTK_CHECK(!(a_tn[i] > 0 && a_rowidx[i]) && !(b_tn[i] > 0 && b_rowidx[i]), "debug_gemm_views: product %d: two-level OR indexed rows", i);
+    // (plain rows only: the slices of a view may interleave on purpose)
+    ASTK_CHECK(batch[i] == 1 || ((!plainA || sA[i] >= rowsA * lda[i]) && (!plainB || sB[i] >= rowsB * ldb[i]) && (c_tn[i] > 0 || sC[i] >= (long)M[i] * ldc[i])),
+               "debug_gemm_views: product %d: batch slices overlap", i);
+    ASTK_CHECK((plainA || !(measure[i] & 1)) && (plainB || !(measure[i] & 2)), "debug_gemm_views: product %d: a measured operand must have plain rows", i);
+    ASTK_CHECK(batch[i] == 1 || ((!(measure[i] & 1) || sA[i] == rowsA * lda[i]) && (!(measure[i] & 2) || sB[i] == rowsB * ldb[i])),
+               "debug_gemm_views: product %d: a measured batched operand must be dense", i);
+    g[i] = gemm_args(M[i], N[i], K[i], view(A[i], lda[i], a_tn[i], a_sg[i], a_st[i], a_rowidx[i], a_idx_rows[i]),
+                     view(B[i], ldb[i], b_tn[i], b_sg[i], b_st[i], b_rowidx[i], b_idx_rows[i]), C[i], ldc[i], bias ? bias[i] : nullptr, mode[i]);
+    g[i].batch = batch[i];
+    g[i].sA = sA[i]; g[i].sB = sB[i]; g[i].sC = sC[i];
+    g[i].c_tn = c_tn[i]; g[i].c_sg = c_sg[i]; g[i].c_st = c_st[i];
+    g[i].lowp = lowp[i] != 0;
+    am[2 * i] = AmaxMatrix{(measure[i] & 1) ? A[i] : nullptr, rowsA * batch[i], lda[i], (int)innerA};
+    am[2 * i + 1] = AmaxMatrix{(measure[i] & 2) ? B[i] : nullptr, rowsB * batch[i], ldb[i], (int)innerB};
+  }
+  if (launch) {
+    const unsigned long long* h[2 * GEMM_GROUP_MAX];
+    gemm_amax_many(am, 2 * n, h, s);
+    for (int i = 0; i < n; ++i) g[i] = with_amax_b(with_amax_a(g[i], h[2 * i]), h[2 * i + 1]);
+  } else {
+    for (int i = 0; i < n; ++i) g[i] = with_amax_b(with_amax_a(g[i], (measure[i] & 1) ? maximum : nullptr), (measure[i] & 2) ? maximum : nullptr);
+  }
+  if (plan_out) {
+    ASTK_CHECK(plan_bytes > 0, "debug_gemm_views: no room for the plan");
+    plan_out[0] = 0;
+    GemmPlan P;
+    ASTK_TRY(gemm_plan(layout, g, n, gemm_env(), P));
+    size_t used = 0;
+    for (int i = 0; i < P.grp.n; ++i) {
+      const int w = gemm_plan_line(plan_out + used, plan_bytes - used, P, layout, i);
+      ASTK_CHECK(w > 0 && (size_t)w < plan_bytes - used, "debug_gemm_views: the text needs more than %zu bytes", plan_bytes);
+      used += (size_t)w;
+    }
+    // per product the contributors of every tile, counted with the kernel's own wg_first_iter ("contrib <product> <n of tile 0> ..."):
+    // launches in plain tile-major stream-K order only (no data-parallel waves, no chunk-major product)
+    for (int i = 0; i < P.grp.n && P.grp.dp_waves == 0; ++i) {
+      const GemmArgs& a = P.grp.g[i];
+      const long tiles = (P.grp.iter_start[i + 1] - P.grp.iter_start[i]) / a.kt;
+      if (a.cs > 0 || tiles > 64) continue;
+      int cnt[64] = {0};
+      for (long w = 0; w < P.G; ++w) {
+        const long lo = std::max(wg_first_iter(P.grp, (unsigned)w, (unsigned)P.G), P.grp.iter_start[i]);
+        const long hi = std::min(wg_first_iter(P.grp, (unsigned)(w + 1), (unsigned)P.G), P.grp.iter_start[i + 1]);
+        if (lo >= hi) continue;
+        for (long t = (lo - P.grp.iter_start[i]) / a.kt; t <= (hi - 1 - P.grp.iter_start[i]) / a.kt; ++t) ++cnt[t];
+      }
+      int w = snprintf(plan_out + used, plan_bytes - used, "contrib %d", i);
+      for (long t = 0; t < tiles && w > 0 && (size_t)w < plan_bytes - used; ++t) {
+        used += (size_t)w;
+        w = snprintf(plan_out + used, plan_bytes - used, " %d", cnt[t]);
+      }
+      ASTK_CHECK(w > 0 && (size_t)w + 1 < plan_bytes - used, "debug_gemm_views: the text needs more than %zu bytes", plan_bytes);
+      used += (size_t)w;
+      plan_out[used++] = '\n';
+      plan_out[used] = 0;
+    }
+  }
+  return launch ? gemm_launch_group(layout, g, n, s) : 0;
+}
 // libastk_test.so only: what ONE grouped launch of n dense row-major products would do, as text (one gemm.log line per product, "" for a
 // group with nothing to launch) in out[0, out_bytes).  Opens the scopes an op would open, reads the state of the call and runs gemm_plan
 // only: no operand is touched (their addresses are made up) and no HIP call is made, so it runs on a machine without a GPU.

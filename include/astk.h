@@ -121,6 +121,21 @@ int astk_debug_gemm_group_lowp(int layout, int n, const int* M, const int* N, co
                                const int* measure, const float* const* A, const long* lda, const long* sA, const float* const* B,
                                const long* ldb, const long* sB, float* const* C, const long* ldc, const long* sC, int precision,
                                int gemm_operands, void* stream);
+/* Test hook (libastk_test.so only): astk_debug_gemm_group_lowp plus the addressing an op can give each operand and the result -- per
+ * product and operand two-level rows (`tn` > 0: row r at (r / tn) * sg + (r % tn) * st floats; the leading dimension is ignored), indexed
+ * rows (`rowidx`, device int32: row r at rowidx[r] * ld; `idx_rows` = rows of the array the indices point into, 0 = a permutation of the
+ * operand's own rows), two-level C rows (c_tn, c_sg, c_st) -- and a bias per product (`bias` or its entries may be NULL).  Runs the real
+ * grouped launch under `precision` / `gemm_operands`, the process default of "gemm.deterministic" and the tuning knobs in force.  A
+ * measured operand (`measure`) must have plain rows.  With `plan_out` the launch's plan is written there as text first (the lines of
+ * astk_debug_gemm_plan, `twolvl` as the views decide it, then per product "contrib <product> <n> ...": the workgroups that contribute to each
+ * tile, for launches in plain stream-K order with at most 64 tiles); `launch` = 0 stops behind the plan: no operand is touched, no device is needed. */
+int astk_debug_gemm_views(int layout, int n, const int* M, const int* N, const int* K, const int* batch, const int* mode, const int* lowp,
+                          const int* measure, const float* const* A, const long* lda, const long* sA, const float* const* B,
+                          const long* ldb, const long* sB, float* const* C, const long* ldc, const long* sC,
+                          const int* a_tn, const long* a_sg, const long* a_st, const int* const* a_rowidx, const long* a_idx_rows,
+                          const int* b_tn, const long* b_sg, const long* b_st, const int* const* b_rowidx, const long* b_idx_rows,
+                          const int* c_tn, const long* c_sg, const long* c_st, const float* const* bias, int precision,
+                          int gemm_operands, int launch, char* plan_out, size_t plan_bytes, void* stream);
 /* Test hook (libastk_test.so only): what ONE grouped launch of n dense row-major products (leading dimensions as in astk_debug_gemm_group;
  * per product M, N, K, batch, mode 0 store / 1 accumulate / 2 atomic, the fp16-operand mark `lowp`, and `given` = the caller supplies both
  * operands' maxima) WOULD do under `forward`, the descriptor fields `precision` / `gemm_operands` / `deterministic`, a workgroup cap
