@@ -1,4 +1,5 @@
-// Persistent forward loop of the wide (H = A = 1024) decoder: decoder_wide.hip, driven by decoder.hip's forward loop.
+// The persistent loops of the wide (H = A = 1024) decoder, forward and backward: decoder_wide.hip, driven by decoder.hip's wide route.
+// The layouts of the scratch and counter buffers sized here are stated at decoder_wide.hip's WidePlan.
 #pragma once
 #include "common.h"
 
@@ -7,7 +8,7 @@ namespace astk {
 struct DecWideBuffers {     // slices of decoder.hip's DecPlan (layer 0)
   int32_t *TOK, *PRED;
   float *X0, *G, *C, *HR, *Q, *ALPHA, *CVH, *HT;
-  float* PART;              // [B][nsplit][H + 4] + [B][ceil(V / 16)][2]   (decoder_wide_part_floats)
+  float* PART;              // decoder_wide_part_floats
   unsigned* ctr;            // decoder_wide_ctr_words
 };
 bool decoder_wide_applicable(const astk_decoder_desc* d, int* nsplit_out, int* chunk_out);

@@ -1,5 +1,6 @@
-// Persistent forward loop for the WIDE decoder of BASELINE configs[4] (H = A = 1024, E = 128, one layer, one attention head, input
-// feeding; seq2seq.py:361-397): all decoder steps in ONE launch.
+// Persistent loops for the WIDE decoder of BASELINE configs[4] (H = A = 1024, E = 128, one layer, one attention head, input feeding;
+// seq2seq.py:361-397): all decoder steps in ONE launch, forward (role map below) and backward (role map in front of decoder_wide_bwd).
+// What host and kernels must agree on -- split of the time axis, LDS, scratch carve, counter lines -- is stated once, at WidePlan.
 //
 // decoder_persist.hip keeps every decoder weight in registers; at this width they are 77 MB (cell 35.6, context 8.4, logits 32.8), 300 of
 // the 512 registers of every lane on the chip.  This kernel drops the logits from the chain (decoder.hip scores all steps with one product
@@ -29,6 +30,10 @@ constexpr int Q0 = 64, CTX0 = 128, CMB0 = 192;   // first workgroup of the Q / C
 constexpr int NQ = WH / 16, NCTX = WA / 16;
 enum { C_CELL = 0, C_Q, C_CMB, C_CTX, C_LOG, C_ARG, C_N };
 constexpr int PARTW = WH + 4;
+constexpr int MAXB = 32;              // most batch rows of a launch: the two 16-row tiles every product works on
+// dynamic LDS of both kernels, in floats: enc slice [chunk][WH] | sacc [4][WH] | red | zt | sml (the backward loop leaves sml unused)
+constexpr int LDS_RED = 2048, LDS_ZT = 512, LDS_SML = 16;
+constexpr int LDS_MAX = 158 * 1024;                    // bytes a workgroup may ask for
 
 struct WideArgs {
   int B, S, L, T, Tp, V, s0, s1, nsplit, chunk;
@@ -36,19 +41,55 @@ struct WideArgs {
   const float* enc;
   const int32_t *y, *use_truth;
   int32_t* PRED;
-  float* LMAX;         // [B][ntile][2]: per (batch row, 16-column logits tile) maximum and its class id (fed-back steps only)
+  float* LMAX;         // per (batch row, 16-column logits tile) maximum and its class id (fed-back steps only)
   int ntile;
   const float *emb_mask, *rnn_mask;
   int32_t* TOK;
-  float *X0, *G, *C, *HR, *Q, *ALPHA, *CVH, *HT, *PART;
-  unsigned* ctr;       // [C_N][NSH] lines, then [B] lines (per batch row: ATT -> CMB)
+  float *X0, *G, *C, *HR, *Q, *ALPHA, *CVH, *HT, *PART;      // PART, LMAX: the forward scratch of WidePlan
+  unsigned* ctr;       // the forward counter lines of WidePlan
   AbortCtl ab;
 };
+// the token of (step s, batch row): the given one when the step is teacher-forced, else the argmax the loop left in PRED; clamped to the table
+__device__ __forceinline__ int step_tok(const WideArgs& a, int s, int row) {
+  const int t = (a.use_truth[s] || s == 0) ? a.y[(long)row * a.L + s] : ldi_sc1(a.PRED + (long)(s - 1) * a.B + row);
+  return t < 0 ? 0 : (t >= a.V ? a.V - 1 : t);
+}
 
 // Handed-off activations are read by every workgroup of an XCD (the 32 rows x 1024 columns of h, ht, [cv; h]: 128-256 KB per workgroup and
 // step) with sc1 loads, as in decoder_persist.hip.  (Rejected: ordinary loads behind an agent-scope acquire after every wait, so that the 32
 // workgroups of an XCD share one fetch of a line -- the ten L2 invalidations per step cost more than the shared fetches save: configs[4]
 // shape, 18.7 ms per train step against 17.9 with sc1 loads.)
+// the [NSH] counter lines of a phase (C_* forward, D_* backward); C_N / D_N: the first line behind the phases
+__device__ __forceinline__ unsigned* phase_ctr(unsigned* ctr, int phase) { return ctr + (size_t)phase * NSH * CTRS; }
+// one k-step of 4: both 16-row batch tiles (a0, a1) against the same weight fragment
+__device__ __forceinline__ void mfma2(f32x4 (&acc)[2], const float a0, const float a1, const float w) {
+  acc[0] = __builtin_amdgcn_mfma_f32_16x16x4f32(a0, w, acc[0], 0, 0, 0);
+  acc[1] = __builtin_amdgcn_mfma_f32_16x16x4f32(a1, w, acc[1], 0, 0, 0);
+}
+// by value, as in decoder_persist.hip
+__device__ __forceinline__ float dot4(const float4 a, const float4 b) { return a.x * b.x + a.y * b.y + a.z * b.z + a.w * b.w; }
+__device__ __forceinline__ float4 fma4(float4 acc, const float g, const float4 e) {
+  acc.x += g * e.x; acc.y += g * e.y; acc.z += g * e.z; acc.w += g * e.w;
+  return acc;
+}
+// the argmax merge: the larger value wins, the lowest class id on ties
+__device__ __forceinline__ bool beats(float om, int oi, float m, int mi) { return om > m || (om == m && oi < mi); }
+// this workgroup's slice of enc_states -> LDS (stays for the whole launch)
+__device__ __forceinline__ void stage_enc_slice(float* s_enc, const float* enc, int b, int T, int t0, int nrow, int tid) {
+  for (int i = tid; i < nrow * (WH / 4); i += 256) {
+    const int j = i / (WH / 4), c = (i % (WH / 4)) * 4;
+    *reinterpret_cast<float4*>(&s_enc[j * WH + c]) = *reinterpret_cast<const float4*>(enc + ((long)b * T + t0 + j) * WH + c);
+  }
+}
+// the rows of both batch tiles this thread holds after reduce2: f(tile, batch row)
+template <class F>
+__device__ __forceinline__ void tile_rows(int B, F f) {
+#pragma unroll
+  for (int mt = 0; mt < 2; ++mt) {
+    const int rw = 16 * mt + ((int)threadIdx.x >> 4);
+    if (rw < B) f(mt, rw);
+  }
+}
 // NB k-blocks of 16 floats per wave (block wave + 4 i): both 16-row batch tiles against the same resident weight fragments.
 // `ra` addresses the activation matrix, off0 / off1 are the float offsets of this lane's row in tile 0 / 1 (incl. 4 q).
 template <int NB>
@@ -60,20 +101,16 @@ __device__ __forceinline__ void mac2(f32x4 (&acc)[2], const float4* w, __amdgpu_
     a1[i] = ldb128_sc1(ra, off1 + 16 * (wave + 4 * i));
   }
   __builtin_amdgcn_sched_barrier(0);
-  f32x4 b0 = {0.f, 0.f, 0.f, 0.f}, b1 = {0.f, 0.f, 0.f, 0.f};
+  f32x4 b[2] = {{0.f, 0.f, 0.f, 0.f}, {0.f, 0.f, 0.f, 0.f}};      // a second accumulator chain per tile
 #pragma unroll
   for (int i = 0; i < NB; ++i) {
-    acc[0] = __builtin_amdgcn_mfma_f32_16x16x4f32(a0[i].x, w[i].x, acc[0], 0, 0, 0);
-    acc[1] = __builtin_amdgcn_mfma_f32_16x16x4f32(a1[i].x, w[i].x, acc[1], 0, 0, 0);
-    b0 = __builtin_amdgcn_mfma_f32_16x16x4f32(a0[i].y, w[i].y, b0, 0, 0, 0);
-    b1 = __builtin_amdgcn_mfma_f32_16x16x4f32(a1[i].y, w[i].y, b1, 0, 0, 0);
-    acc[0] = __builtin_amdgcn_mfma_f32_16x16x4f32(a0[i].z, w[i].z, acc[0], 0, 0, 0);
-    acc[1] = __builtin_amdgcn_mfma_f32_16x16x4f32(a1[i].z, w[i].z, acc[1], 0, 0, 0);
-    b0 = __builtin_amdgcn_mfma_f32_16x16x4f32(a0[i].w, w[i].w, b0, 0, 0, 0);
-    b1 = __builtin_amdgcn_mfma_f32_16x16x4f32(a1[i].w, w[i].w, b1, 0, 0, 0);
+    mfma2(acc, a0[i].x, a1[i].x, w[i].x);
+    mfma2(b, a0[i].y, a1[i].y, w[i].y);
+    mfma2(acc, a0[i].z, a1[i].z, w[i].z);
+    mfma2(b, a0[i].w, a1[i].w, w[i].w);
   }
-  acc[0] += b0;
-  acc[1] += b1;
+  acc[0] += b[0];
+  acc[1] += b[1];
 }
 // resident weight fragments: k-blocks wave + 4 i of W row `row` (K-contiguous), starting at column c0
 template <int NB>
@@ -97,24 +134,18 @@ __device__ __forceinline__ void reduce2(const f32x4 (&acc)[2], float (&v)[2], fl
 
 __global__ __launch_bounds__(256, 1) void decoder_wide_fwd(WideArgs a) {
   extern __shared__ __attribute__((aligned(16))) float lds[];
-  // LDS: enc slice [chunk][WH] | sacc [4][WH] | red [2048] | zt [512] | sml [16] | scr [chunk padded]
   float* s_enc = lds;
   float* s_acc = s_enc + (size_t)a.chunk * WH;
   float* s_red = s_acc + 4 * WH;
-  float* s_zt = s_red + 2048;
-  float* s_ml = s_zt + 512;
+  float* s_zt = s_red + LDS_RED;
+  float* s_ml = s_zt + LDS_ZT;
   __shared__ int s_flag;
   const int w = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const int r = lane & 15, q4 = (lane >> 4) * 4;
   const int B = a.B;
   const int row0 = min(r, B - 1), row1 = min(16 + r, B - 1);
-  unsigned* c_cell = a.ctr + (size_t)C_CELL * NSH * CTRS;
-  unsigned* c_q = a.ctr + (size_t)C_Q * NSH * CTRS;
-  unsigned* c_cmb = a.ctr + (size_t)C_CMB * NSH * CTRS;
-  unsigned* c_ctx = a.ctr + (size_t)C_CTX * NSH * CTRS;
-  unsigned* c_log = a.ctr + (size_t)C_LOG * NSH * CTRS;
-  unsigned* c_arg = a.ctr + (size_t)C_ARG * NSH * CTRS;
-  unsigned* c_row = a.ctr + (size_t)C_N * NSH * CTRS;
+  unsigned *c_cell = phase_ctr(a.ctr, C_CELL), *c_q = phase_ctr(a.ctr, C_Q), *c_cmb = phase_ctr(a.ctr, C_CMB), *c_ctx = phase_ctr(a.ctr, C_CTX),
+           *c_log = phase_ctr(a.ctr, C_LOG), *c_arg = phase_ctr(a.ctr, C_ARG), *c_row = phase_ctr(a.ctr, C_N);
   const bool is_q = w >= Q0 && w < Q0 + NQ, is_ctx = w >= CTX0 && w < CTX0 + NCTX, is_cmb = w >= CMB0 && w < CMB0 + B;
   const bool is_att = w < B * a.nsplit;
   const int ab_ = w % B, asp = w / B;                         // attention item (batch row, chunk)
@@ -128,11 +159,7 @@ __global__ __launch_bounds__(256, 1) void decoder_wide_fwd(WideArgs a) {
   float4 wX[32];                                              // Q: Wa row (16 k-blocks); CTX: Wc row (32 k-blocks)
   if (is_q) wload<16>(wX, a.Wa, WH, 16 * (w - Q0) + r, 0, lane, wave);
   if (is_ctx) wload<32>(wX, a.Wc, 2 * WH, 16 * (w - CTX0) + r, 0, lane, wave);
-  // ---- this workgroup's slice of enc_states -> LDS (stays for the whole launch)
-  for (int i = tid; i < nrow * (WH / 4); i += 256) {
-    const int j = i / (WH / 4), c = (i % (WH / 4)) * 4;
-    *reinterpret_cast<float4*>(&s_enc[j * WH + c]) = *reinterpret_cast<const float4*>(a.enc + ((long)ab_ * a.T + t0 + j) * WH + c);
-  }
+  stage_enc_slice(s_enc, a.enc, ab_, a.T, t0, nrow, tid);
   // cell state of this thread's (batch row, unit): threads 0..127, row = tid >> 2, unit = 4w + (tid & 3)
   const int crow = tid >> 2, cu = 4 * w + (tid & 3);
   float c_state = 0.f;
@@ -154,12 +181,8 @@ __global__ __launch_bounds__(256, 1) void decoder_wide_fwd(WideArgs a) {
     {   // embedding part (off the chain unless the token is fed back): rows gathered from the table, times the embedding dropout mask
       int tok[2];
 #pragma unroll
-      for (int mt = 0; mt < 2; ++mt) {
-        const int rw = mt ? row1 : row0;
-        int t = (a.use_truth[s] || s == 0) ? a.y[(long)rw * a.L + s] : ldi_sc1(a.PRED + (long)(s - 1) * B + rw);
-        tok[mt] = t < 0 ? 0 : (t >= a.V ? a.V - 1 : t);
-      }
-      f32x4 b0 = {0.f, 0.f, 0.f, 0.f}, b1 = {0.f, 0.f, 0.f, 0.f};
+      for (int mt = 0; mt < 2; ++mt) tok[mt] = step_tok(a, s, mt ? row1 : row0);
+      f32x4 b[2] = {{0.f, 0.f, 0.f, 0.f}, {0.f, 0.f, 0.f, 0.f}};
 #pragma unroll
       for (int i = 0; i < 2; ++i) {
         const int k = 16 * (wave + 4 * i) + q4;
@@ -171,21 +194,16 @@ __global__ __launch_bounds__(256, 1) void decoder_wide_fwd(WideArgs a) {
           e0.x *= m0.x; e0.y *= m0.y; e0.z *= m0.z; e0.w *= m0.w;
           e1.x *= m1.x; e1.y *= m1.y; e1.z *= m1.z; e1.w *= m1.w;
         }
-        acc[0] = __builtin_amdgcn_mfma_f32_16x16x4f32(e0.x, wE[i].x, acc[0], 0, 0, 0);
-        acc[1] = __builtin_amdgcn_mfma_f32_16x16x4f32(e1.x, wE[i].x, acc[1], 0, 0, 0);
-        b0 = __builtin_amdgcn_mfma_f32_16x16x4f32(e0.y, wE[i].y, b0, 0, 0, 0);
-        b1 = __builtin_amdgcn_mfma_f32_16x16x4f32(e1.y, wE[i].y, b1, 0, 0, 0);
-        acc[0] = __builtin_amdgcn_mfma_f32_16x16x4f32(e0.z, wE[i].z, acc[0], 0, 0, 0);
-        acc[1] = __builtin_amdgcn_mfma_f32_16x16x4f32(e1.z, wE[i].z, acc[1], 0, 0, 0);
-        b0 = __builtin_amdgcn_mfma_f32_16x16x4f32(e0.w, wE[i].w, b0, 0, 0, 0);
-        b1 = __builtin_amdgcn_mfma_f32_16x16x4f32(e1.w, wE[i].w, b1, 0, 0, 0);
+        mfma2(acc, e0.x, e1.x, wE[i].x);
+        mfma2(b, e0.y, e1.y, wE[i].y);
+        mfma2(acc, e0.z, e1.z, wE[i].z);
+        mfma2(b, e0.w, e1.w, wE[i].w);
       }
-      acc[0] += b0;
-      acc[1] += b1;
+      acc[0] += b[0];
+      acc[1] += b[1];
       // the saved embedding rows (the weight gradients' operand) and tokens: workgroup b writes row b
       if (w < B) {
-        int t = (a.use_truth[s] || s == 0) ? a.y[(long)w * a.L + s] : ldi_sc1(a.PRED + (long)(s - 1) * B + w);
-        t = t < 0 ? 0 : (t >= a.V ? a.V - 1 : t);
+        const int t = step_tok(a, s, w);
         if (tid == 0) a.TOK[(long)s * B + w] = t;
         if (tid < WE) {
           float v = a.embed[(long)t * WE + tid];
@@ -228,11 +246,7 @@ __global__ __launch_bounds__(256, 1) void decoder_wide_fwd(WideArgs a) {
       reduce2(aq, v, s_red);
       const int col = 16 * (w - Q0) + (tid & 15);
       const float bb = a.ba[col];
-#pragma unroll
-      for (int mt = 0; mt < 2; ++mt) {
-        const int rw = 16 * mt + (tid >> 4);
-        if (rw < B) st_sc1(a.Q + ((long)s * B + rw) * WH + col, v[mt] + bb);
-      }
+      tile_rows(B, [&](int mt, int rw) { st_sc1(a.Q + ((long)s * B + rw) * WH + col, v[mt] + bb); });
       publish(c_q + ((w - Q0) & (NSH - 1)) * CTRS);
     }
     // ================= ATT: scores and partial context of (batch row, chunk)
@@ -251,7 +265,7 @@ __global__ __launch_bounds__(256, 1) void decoder_wide_fwd(WideArgs a) {
 #pragma unroll
         for (int c = 0; c < 4; ++c) {
           e[c] = *reinterpret_cast<const float4*>(&s_enc[j * WH + 256 * c + 4 * lane]);
-          d += e[c].x * qv[c].x + e[c].y * qv[c].y + e[c].z * qv[c].z + e[c].w * qv[c].w;
+          d += dot4(e[c], qv[c]);
         }
         const float sc_ = wave_sum(d);
         if (lane == 0) st_sc1(a.ALPHA + ((long)s * B + ab_) * a.Tp + t0 + j, sc_);
@@ -375,7 +389,7 @@ __global__ __launch_bounds__(256, 1) void decoder_wide_fwd(WideArgs a) {
           for (int o = 8; o > 0; o >>= 1) {           // the 16 lanes of a row: maximum, lowest class id on ties
             const float om = __shfl_xor(m, o);
             const int oi = __shfl_xor(mi, o);
-            if (om > m || (om == m && oi < mi)) { m = om; mi = oi; }
+            if (beats(om, oi, m, mi)) { m = om; mi = oi; }
           }
           const int rw = 16 * mt + (tid >> 4);
           if ((tid & 15) == 0 && rw < B) {
@@ -394,13 +408,13 @@ __global__ __launch_bounds__(256, 1) void decoder_wide_fwd(WideArgs a) {
           const float* lm = a.LMAX + ((long)w * a.ntile + t) * 2;
           const float om = ld_sc1(lm);
           const int oi = __float_as_int(ld_sc1(lm + 1));
-          if (om > m || (om == m && oi < mi)) { m = om; mi = oi; }
+          if (beats(om, oi, m, mi)) { m = om; mi = oi; }
         }
 #pragma unroll
         for (int o = 32; o > 0; o >>= 1) {
           const float om = __shfl_xor(m, o);
           const int oi = __shfl_xor(mi, o);
-          if (om > m || (om == m && oi < mi)) { m = om; mi = oi; }
+          if (beats(om, oi, m, mi)) { m = om; mi = oi; }
         }
         if (lane == 0) { s_ml[wave] = m; s_ml[8 + wave] = __int_as_float(mi); }
         __syncthreads();
@@ -408,7 +422,7 @@ __global__ __launch_bounds__(256, 1) void decoder_wide_fwd(WideArgs a) {
           for (int k = 1; k < 4; ++k) {
             const float om = s_ml[k];
             const int oi = __float_as_int(s_ml[8 + k]);
-            if (om > m || (om == m && oi < mi)) { m = om; mi = oi; }
+            if (beats(om, oi, m, mi)) { m = om; mi = oi; }
           }
           sti_sc1(a.PRED + (long)s * B + w, mi);
         }
@@ -432,6 +446,7 @@ __global__ __launch_bounds__(256, 1) void decoder_wide_fwd(WideArgs a) {
 // Chain: P1 -> ATTB -> DQC -> P3 -> CELLB -> DZ -> P5R -> next P1.  The embedding columns of d_x0 are one batched product behind the loop.
 constexpr int BP1 = 0, BP3 = 128, BDQC = 128, BP5R = 192;
 constexpr int NP1 = 2 * WH / 16, NP3 = WH / 16, NTILE = WH / 16;
+constexpr int QPART = MAXB * 16;      // one K-quarter's partial sums of a 16-unit tile: [MAXB rows][16 columns]
 enum { D_P1 = 0, D_DQC, D_P3, D_CELL, D_DPRE, D_N };
 
 struct WideBwdArgs {
@@ -440,30 +455,25 @@ struct WideBwdArgs {
   const float* enc;
   const float *ALPHA, *CVH, *HT, *C, *rnn_mask;
   float *G, *DPRE, *DCVH, *DS, *DQ, *DHTOP, *DC0;
-  float *PARTB;        // [B][nsplit][H]
-  float *PREC, *PCAR;  // [64 tiles][4][32][16] partial sums of the recurrent / carry products
-  unsigned* ctr;       // [D_N][NSH] lines | [B] per-row lines | [64] rec-tile lines | [64] carry-tile lines | abort
+  float *PARTB, *PREC, *PCAR;      // the backward scratch of WidePlan
+  unsigned* ctr;                   // the backward counter lines of WidePlan
   AbortCtl ab;
 };
 
 __global__ __launch_bounds__(256, 1) void decoder_wide_bwd(WideBwdArgs a) {
   extern __shared__ __attribute__((aligned(16))) float lds[];
   float* s_enc = lds;
-  float* s_acc = s_enc + (size_t)a.chunk * WH;      // [4][WH]
-  float* s_red = s_acc + 4 * WH;                    // [2048]
-  float* s_zt = s_red + 2048;                       // [512]
+  float* s_acc = s_enc + (size_t)a.chunk * WH;
+  float* s_red = s_acc + 4 * WH;
+  float* s_zt = s_red + LDS_RED;
   __shared__ int s_flag;
   const int w = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const int r = lane & 15, q4 = (lane >> 4) * 4;
   const int B = a.B, S = a.S;
   const int row0 = min(r, B - 1), row1 = min(16 + r, B - 1);
-  unsigned* c_p1 = a.ctr + (size_t)D_P1 * NSH * CTRS;
-  unsigned* c_dqc = a.ctr + (size_t)D_DQC * NSH * CTRS;
-  unsigned* c_p3 = a.ctr + (size_t)D_P3 * NSH * CTRS;
-  unsigned* c_cell = a.ctr + (size_t)D_CELL * NSH * CTRS;
-  unsigned* c_dpre = a.ctr + (size_t)D_DPRE * NSH * CTRS;
-  unsigned* c_row = a.ctr + (size_t)D_N * NSH * CTRS;
-  unsigned* c_rec = c_row + (size_t)32 * CTRS;
+  unsigned *c_p1 = phase_ctr(a.ctr, D_P1), *c_dqc = phase_ctr(a.ctr, D_DQC), *c_p3 = phase_ctr(a.ctr, D_P3), *c_cell = phase_ctr(a.ctr, D_CELL),
+           *c_dpre = phase_ctr(a.ctr, D_DPRE), *c_row = phase_ctr(a.ctr, D_N);
+  unsigned* c_rec = c_row + (size_t)MAXB * CTRS;
   unsigned* c_car = c_rec + (size_t)NTILE * CTRS;
   const bool is_p1 = w < NP1, is_p3 = w >= BP3 && w < BP3 + NP3, is_dqc = w >= BDQC && w < BDQC + B, is_p5r = w >= BP5R;
   const bool is_att = w < B * a.nsplit;
@@ -477,10 +487,7 @@ __global__ __launch_bounds__(256, 1) void decoder_wide_bwd(WideBwdArgs a) {
   wload<16>(wCar, a.WuT, 4 * WH, WE + 16 * tj + r, 1024 * kq, lane, wave);       // dz Wu[:, E + ...]: carry column 16 tj + r
   if (is_p1) wload<16>(wX, a.WcT, WA, 16 * w + r, 0, lane, wave);
   if (is_p3) wload<16>(wX, a.WaT, WH, 16 * (w - BP3) + r, 0, lane, wave);
-  for (int i = tid; i < nrow * (WH / 4); i += 256) {
-    const int j = i / (WH / 4), c = (i % (WH / 4)) * 4;
-    *reinterpret_cast<float4*>(&s_enc[j * WH + c]) = *reinterpret_cast<const float4*>(a.enc + ((long)ab_ * a.T + t0 + j) * WH + c);
-  }
+  stage_enc_slice(s_enc, a.enc, ab_, a.T, t0, nrow, tid);
   const int crow = tid >> 2, cu = 16 * tj + 4 * kq + (tid & 3), ccol = 4 * kq + (tid & 3);
   float dc_next = 0.f;
   const __amdgpu_buffer_rsrc_t r_dpre = make_rsrc(a.DPRE), r_dcvh = make_rsrc(a.DCVH), r_dq = make_rsrc(a.DQ), r_g = make_rsrc(a.G),
@@ -496,11 +503,7 @@ __global__ __launch_bounds__(256, 1) void decoder_wide_bwd(WideBwdArgs a) {
       mac2<16>(acc, wX, r_dpre, ((long)st * B + row0) * WA + q4, ((long)st * B + row1) * WA + q4, wave);
       float v[2];
       reduce2(acc, v, s_red);
-#pragma unroll
-      for (int mt = 0; mt < 2; ++mt) {
-        const int rw = 16 * mt + (tid >> 4);
-        if (rw < B) st_sc1(a.DCVH + ((long)st * B + rw) * 2 * WH + 16 * w + (tid & 15), v[mt]);
-      }
+      tile_rows(B, [&](int mt, int rw) { st_sc1(a.DCVH + ((long)st * B + rw) * 2 * WH + 16 * w + (tid & 15), v[mt]); });
       publish(c_p1 + (w & (NSH - 1)) * CTRS);
     }
     // ================= ATTB
@@ -512,7 +515,7 @@ __global__ __launch_bounds__(256, 1) void decoder_wide_bwd(WideBwdArgs a) {
       for (int c = 0; c < 4; ++c) {
         dcv[c] = ldb128_sc1(r_dcvh, ((long)st * B + ab_) * 2 * WH + 256 * c + 4 * lane);
         cvv[c] = *reinterpret_cast<const float4*>(a.CVH + ((long)st * B + ab_) * 2 * WH + 256 * c + 4 * lane);
-        c0 += dcv[c].x * cvv[c].x + dcv[c].y * cvv[c].y + dcv[c].z * cvv[c].z + dcv[c].w * cvv[c].w;
+        c0 += dot4(dcv[c], cvv[c]);
         ac[c] = make_float4(0.f, 0.f, 0.f, 0.f);
       }
       c0 = wave_sum(c0);
@@ -522,15 +525,13 @@ __global__ __launch_bounds__(256, 1) void decoder_wide_bwd(WideBwdArgs a) {
 #pragma unroll
         for (int c = 0; c < 4; ++c) {
           e[c] = *reinterpret_cast<const float4*>(&s_enc[j * WH + 256 * c + 4 * lane]);
-          d += e[c].x * dcv[c].x + e[c].y * dcv[c].y + e[c].z * dcv[c].z + e[c].w * dcv[c].w;
+          d += dot4(e[c], dcv[c]);
         }
         const float al = a.ALPHA[((long)st * B + ab_) * a.Tp + t0 + j];
         const float ds = al * (wave_sum(d) - c0);
         if (lane == 0) a.DS[((long)st * B + ab_) * a.Tp + t0 + j] = ds;
 #pragma unroll
-        for (int c = 0; c < 4; ++c) {
-          ac[c].x += ds * e[c].x; ac[c].y += ds * e[c].y; ac[c].z += ds * e[c].z; ac[c].w += ds * e[c].w;
-        }
+        for (int c = 0; c < 4; ++c) ac[c] = fma4(ac[c], ds, e[c]);
       }
 #pragma unroll
       for (int c = 0; c < 4; ++c) *reinterpret_cast<float4*>(&s_acc[wave * WH + 256 * c + 4 * lane]) = ac[c];
@@ -564,11 +565,7 @@ __global__ __launch_bounds__(256, 1) void decoder_wide_bwd(WideBwdArgs a) {
       float v[2];
       reduce2(acc, v, s_red);
       const int col = 16 * (w - BP3) + (tid & 15);
-#pragma unroll
-      for (int mt = 0; mt < 2; ++mt) {
-        const int rw = 16 * mt + (tid >> 4);
-        if (rw < B) st_sc1(a.DHTOP + (long)rw * WH + col, v[mt] + ld_sc1(a.DCVH + ((long)st * B + rw) * 2 * WH + WH + col));
-      }
+      tile_rows(B, [&](int mt, int rw) { st_sc1(a.DHTOP + (long)rw * WH + col, v[mt] + ld_sc1(a.DCVH + ((long)st * B + rw) * 2 * WH + WH + col)); });
       publish(c_p3 + ((w - BP3) & (NSH - 1)) * CTRS);
     }
     // ================= CELLB: pointwise LSTM backward of this workgroup's 4 units
@@ -581,8 +578,8 @@ __global__ __launch_bounds__(256, 1) void decoder_wide_bwd(WideBwdArgs a) {
         if (a.rnn_mask) dy *= a.rnn_mask[(long)st * B * WH + bu];
         float dh = dy;
         if (n > 1) {
-          const float* pr = a.PREC + ((long)tj * 4 * 32 + crow) * 16 + ccol;
-          dh += ld_sc1(pr) + ld_sc1(pr + 512) + ld_sc1(pr + 1024) + ld_sc1(pr + 1536);
+          const float* pr = a.PREC + ((long)tj * 4 * MAXB + crow) * 16 + ccol;
+          dh += ld_sc1(pr) + ld_sc1(pr + QPART) + ld_sc1(pr + 2 * QPART) + ld_sc1(pr + 3 * QPART);
         }
         float* gp = a.G + ((long)st * B + crow) * 4 * WH + 4 * cu;
         const float4 g = ldb128_sc1(r_g, ((long)st * B + crow) * 4 * WH + 4 * cu);      // the saved gates a, i, f, o (dz goes in their place)
@@ -614,30 +611,22 @@ __global__ __launch_bounds__(256, 1) void decoder_wide_bwd(WideBwdArgs a) {
       f32x4 rec[2] = {{0.f, 0.f, 0.f, 0.f}, {0.f, 0.f, 0.f, 0.f}}, car[2] = {{0.f, 0.f, 0.f, 0.f}, {0.f, 0.f, 0.f, 0.f}};
 #pragma unroll
       for (int i = 0; i < 16; ++i) {
-        rec[0] = __builtin_amdgcn_mfma_f32_16x16x4f32(a0[i].x, wRec[i].x, rec[0], 0, 0, 0);
-        rec[1] = __builtin_amdgcn_mfma_f32_16x16x4f32(a1[i].x, wRec[i].x, rec[1], 0, 0, 0);
-        car[0] = __builtin_amdgcn_mfma_f32_16x16x4f32(a0[i].x, wCar[i].x, car[0], 0, 0, 0);
-        car[1] = __builtin_amdgcn_mfma_f32_16x16x4f32(a1[i].x, wCar[i].x, car[1], 0, 0, 0);
-        rec[0] = __builtin_amdgcn_mfma_f32_16x16x4f32(a0[i].y, wRec[i].y, rec[0], 0, 0, 0);
-        rec[1] = __builtin_amdgcn_mfma_f32_16x16x4f32(a1[i].y, wRec[i].y, rec[1], 0, 0, 0);
-        car[0] = __builtin_amdgcn_mfma_f32_16x16x4f32(a0[i].y, wCar[i].y, car[0], 0, 0, 0);
-        car[1] = __builtin_amdgcn_mfma_f32_16x16x4f32(a1[i].y, wCar[i].y, car[1], 0, 0, 0);
-        rec[0] = __builtin_amdgcn_mfma_f32_16x16x4f32(a0[i].z, wRec[i].z, rec[0], 0, 0, 0);
-        rec[1] = __builtin_amdgcn_mfma_f32_16x16x4f32(a1[i].z, wRec[i].z, rec[1], 0, 0, 0);
-        car[0] = __builtin_amdgcn_mfma_f32_16x16x4f32(a0[i].z, wCar[i].z, car[0], 0, 0, 0);
-        car[1] = __builtin_amdgcn_mfma_f32_16x16x4f32(a1[i].z, wCar[i].z, car[1], 0, 0, 0);
-        rec[0] = __builtin_amdgcn_mfma_f32_16x16x4f32(a0[i].w, wRec[i].w, rec[0], 0, 0, 0);
-        rec[1] = __builtin_amdgcn_mfma_f32_16x16x4f32(a1[i].w, wRec[i].w, rec[1], 0, 0, 0);
-        car[0] = __builtin_amdgcn_mfma_f32_16x16x4f32(a0[i].w, wCar[i].w, car[0], 0, 0, 0);
-        car[1] = __builtin_amdgcn_mfma_f32_16x16x4f32(a1[i].w, wCar[i].w, car[1], 0, 0, 0);
+        mfma2(rec, a0[i].x, a1[i].x, wRec[i].x);
+        mfma2(car, a0[i].x, a1[i].x, wCar[i].x);
+        mfma2(rec, a0[i].y, a1[i].y, wRec[i].y);
+        mfma2(car, a0[i].y, a1[i].y, wCar[i].y);
+        mfma2(rec, a0[i].z, a1[i].z, wRec[i].z);
+        mfma2(car, a0[i].z, a1[i].z, wCar[i].z);
+        mfma2(rec, a0[i].w, a1[i].w, wRec[i].w);
+        mfma2(car, a0[i].w, a1[i].w, wCar[i].w);
       }
       float v[2];
-      float* pc = a.PCAR + (long)w * 512;            // [tile][quarter] = [w]: [32 rows][16 cols]
+      float* pc = a.PCAR + (long)w * QPART;          // [tile][quarter] = [w]
       reduce2(car, v, s_red);
       st_sc1(pc + tid, v[0]);
       st_sc1(pc + 256 + tid, v[1]);
       publish(c_car + (size_t)tj * CTRS);          // the carry first: it is on the chain
-      float* pr = a.PREC + (long)w * 512;
+      float* pr = a.PREC + (long)w * QPART;
       reduce2(rec, v, s_red);
       st_sc1(pr + tid, v[0]);
       st_sc1(pr + 256 + tid, v[1]);
@@ -647,13 +636,13 @@ __global__ __launch_bounds__(256, 1) void decoder_wide_bwd(WideBwdArgs a) {
     if (is_p5r) {
       const int j = w - BP5R;
       if (!wg_wait(c_car + (size_t)j * CTRS, (unsigned)(4 * n), a.ab, &s_flag)) return;
-      const float* pc = a.PCAR + (long)j * 4 * 512;
+      const float* pc = a.PCAR + (long)j * 4 * QPART;
 #pragma unroll
       for (int mt = 0; mt < 2; ++mt) {
         const int rw = 16 * mt + (tid >> 4), col = 16 * j + (tid & 15);
         if (rw < B) {
           const int e = mt * 256 + tid;
-          const float carry = ld_sc1(pc + e) + ld_sc1(pc + 512 + e) + ld_sc1(pc + 1024 + e) + ld_sc1(pc + 1536 + e);
+          const float carry = ld_sc1(pc + e) + ld_sc1(pc + QPART + e) + ld_sc1(pc + 2 * QPART + e) + ld_sc1(pc + 3 * QPART + e);
           float* dp = a.DPRE + ((long)(st - 1) * B + rw) * WA + col;
           const float y = a.HT[((long)st * B + rw) * WA + col];
           st_sc1(dp, (*dp + carry) * (1.f - y * y));
@@ -664,99 +653,102 @@ __global__ __launch_bounds__(256, 1) void decoder_wide_bwd(WideBwdArgs a) {
   }
 }
 
-size_t wide_lds_bytes(int chunk) { return ((size_t)chunk * WH + 4 * WH + 2048 + 512 + 16) * sizeof(float); }
-
-}  // namespace
+// ---------------------------------------------------------------------------------------------------------------- launch plan
+// What the host and the two kernels agree on for one descriptor; the fields mean nothing unless `ok`.  LDS: the layout at LDS_RED.
+//   time axis          nsplit slices of chunk frames per batch row, B nsplit <= WG_ workgroups; Tp = T'' padded to 4, the row length of ALPHA / DS
+//   forward scratch    (DecWideBuffers::PART, floats)  PART [B][nsplit][PARTW]: (max, sum, -, -, context partial [WH]) | LMAX [B][ntile][2]
+//   forward counters   (lines of CTRS words)           [C_N][NSH] phases | [B] rows (ATT -> CMB) | abort
+//   backward scratch   (DecWideBwdBuffers::scratch)    PARTB [B][nsplit][WH] | PREC [NTILE][4][QPART]: recurrent partials | PCAR: carry partials, the same
+//   backward counters                                  [D_N][NSH] phases | [MAXB] rows (ATTB -> DQC) | [NTILE] rec | [NTILE] car | abort
+struct WidePlan {
+  bool ok;
+  int nsplit, chunk, Tp, ntile;
+  size_t lds_bytes;
+  size_t lmax_off, part_floats, fwd_abort_line, fwd_ctr_lines;                  // offsets and sizes in floats; counter lines
+  size_t prec_off, pcar_off, bwd_floats, bwd_abort_line, bwd_ctr_lines;
+};
+static_assert(WG_ == 4 * NTILE, "PREC / PCAR: one quarter partial per workgroup");
 
 // Applicable: configs[4]'s decoder shape, one layer, one attention head, input feeding, no LayerNorm; the device's CUs hold the grid; the
 // time slices fit LDS.  (decoder.hip additionally needs the host copy of the teacher-forcing flags to cut the loop into segments.)
-bool decoder_wide_applicable(const astk_decoder_desc* d, int* nsplit_out, int* chunk_out) {
-  if (!tune_on(TUNE_DEC_WIDE)) return false;
-  if (d->H != WH || d->A != WA || d->E != WE || d->n_layers != 1 || d->n_attn > 1 || d->no_feed_attn || d->ln) return false;
-  if (d->B < 1 || d->B > 32 || d->T < 1 || d->V < 2 || device_cu_count() < WG_) return false;
-  int nsplit = WG_ / d->B;
-  if (nsplit > d->T) nsplit = d->T;
-  if (nsplit > 64) nsplit = 64;
-  const int chunk = (d->T + nsplit - 1) / nsplit;
-  nsplit = (d->T + chunk - 1) / chunk;
-  if (wide_lds_bytes(chunk) > 158 * 1024) return false;      // slices of up to 32 rows (T'' <= 256 at batch 32)
-  if (nsplit_out) *nsplit_out = nsplit;
-  if (chunk_out) *chunk_out = chunk;
-  return true;
+WidePlan wide_plan(const astk_decoder_desc* d) {
+  WidePlan p = {};
+  if (!tune_on(TUNE_DEC_WIDE)) return p;
+  if (d->H != WH || d->A != WA || d->E != WE || d->n_layers != 1 || d->n_attn > 1 || d->no_feed_attn || d->ln) return p;
+  if (d->B < 1 || d->B > MAXB || d->T < 1 || d->V < 2 || device_cu_count() < WG_) return p;
+  p.nsplit = std::min(std::min(WG_ / d->B, d->T), 64);
+  p.chunk = (d->T + p.nsplit - 1) / p.nsplit;
+  p.nsplit = (d->T + p.chunk - 1) / p.chunk;
+  p.lds_bytes = ((size_t)p.chunk * WH + 4 * WH + LDS_RED + LDS_ZT + LDS_SML) * sizeof(float);
+  if (p.lds_bytes > (size_t)LDS_MAX) return p;               // slices of up to 32 rows (T'' <= 256 at batch 32)
+  p.Tp = (d->T + 3) / 4 * 4; p.ntile = (d->V + 15) / 16;
+  p.lmax_off = (size_t)d->B * p.nsplit * PARTW;
+  p.part_floats = p.lmax_off + (size_t)d->B * p.ntile * 2;
+  p.fwd_abort_line = (size_t)C_N * NSH + d->B; p.fwd_ctr_lines = p.fwd_abort_line + 1;
+  p.prec_off = (size_t)d->B * p.nsplit * WH;
+  p.pcar_off = p.prec_off + (size_t)NTILE * 4 * QPART;
+  p.bwd_floats = p.pcar_off + (size_t)NTILE * 4 * QPART;
+  p.bwd_abort_line = (size_t)D_N * NSH + MAXB + 2 * NTILE; p.bwd_ctr_lines = p.bwd_abort_line + 1;
+  p.ok = true;
+  return p;
 }
 
-size_t decoder_wide_part_floats(const astk_decoder_desc* d) {
-  int ns = 1, ch = 1;
-  return decoder_wide_applicable(d, &ns, &ch) ? (size_t)d->B * ns * PARTW + (size_t)d->B * ((d->V + 15) / 16) * 2 : 4;
+// zeroes the counter lines, then launches K (one `attr_once` per kernel: each sets its LDS attribute at its first launch)
+template <auto K, class Args>
+int wide_launch(const Args& a, size_t ctr_lines, size_t shm, hipStream_t s) {
+  ASTK_HIP(hipMemsetAsync(a.ctr, 0, ctr_lines * CTRS * sizeof(unsigned), s));
+  static const hipError_t attr_once = hipFuncSetAttribute((const void*)K, hipFuncAttributeMaxDynamicSharedMemorySize, LDS_MAX);
+  (void)attr_once;
+  hipLaunchKernelGGL(K, dim3(WG_), dim3(256), shm, s, a);
+  ASTK_LAUNCH_CHECK();
+  return 0;
 }
-size_t decoder_wide_ctr_words(const astk_decoder_desc* d) {
-  return decoder_wide_applicable(d, nullptr, nullptr) ? ((size_t)C_N * NSH + d->B + 1) * CTRS : 4;
+
+}  // namespace
+
+bool decoder_wide_applicable(const astk_decoder_desc* d, int* nsplit_out, int* chunk_out) {
+  const WidePlan p = wide_plan(d);
+  if (p.ok && nsplit_out) *nsplit_out = p.nsplit;
+  if (p.ok && chunk_out) *chunk_out = p.chunk;
+  return p.ok;
 }
+// (a placeholder of 4 elements where the loops do not apply)
+size_t decoder_wide_part_floats(const astk_decoder_desc* d) { const WidePlan p = wide_plan(d); return p.ok ? p.part_floats : 4; }
+size_t decoder_wide_ctr_words(const astk_decoder_desc* d) { const WidePlan p = wide_plan(d); return p.ok ? p.fwd_ctr_lines * CTRS : 4; }
+size_t decoder_wide_bwd_floats(const astk_decoder_desc* d) { const WidePlan p = wide_plan(d); return p.ok ? p.bwd_floats : 4; }
+size_t decoder_wide_bwd_ctr_words(const astk_decoder_desc* d) { const WidePlan p = wide_plan(d); return p.ok ? p.bwd_ctr_lines * CTRS : 4; }
 
 int decoder_wide_fwd_launch(const astk_decoder_desc* d, const astk_decoder_params* prm, const float* enc, const int32_t* y,
                             const int32_t* use_truth, const float* emb_mask, const float* rnn_mask, const DecWideBuffers& bf, int s0, int s1,
                             hipStream_t s) {
-  int nsplit = 1, chunk = 1;
-  ASTK_CHECK(decoder_wide_applicable(d, &nsplit, &chunk), "decoder_wide: not applicable");
+  const WidePlan p = wide_plan(d);
+  ASTK_CHECK(p.ok, "decoder_wide: not applicable");
   ASTK_CHECK(s0 >= 0 && s1 >= s0 && s1 < d->L - 1, "decoder_wide: bad segment [%d, %d]", s0, s1);
   WideArgs a;
   memset(&a, 0, sizeof(a));
-  a.B = d->B; a.S = d->L - 1; a.L = d->L; a.T = d->T; a.Tp = (d->T + 3) / 4 * 4; a.V = d->V; a.s0 = s0; a.s1 = s1;
-  a.nsplit = nsplit; a.chunk = chunk;
+  a.B = d->B; a.S = d->L - 1; a.L = d->L; a.T = d->T; a.Tp = p.Tp; a.V = d->V; a.s0 = s0; a.s1 = s1;
+  a.nsplit = p.nsplit; a.chunk = p.chunk; a.ntile = p.ntile;
   a.embed = prm->embed; a.Wu = prm->lstm[0].Wu; a.bias = prm->lstm[0].b; a.Wl = prm->lstm[0].Wl;
   a.Wa = prm->Wa; a.ba = prm->ba; a.Wc = prm->Wc; a.bc = prm->bc; a.Wo = prm->Wo; a.bo = prm->bo;
-  a.ntile = (d->V + 15) / 16;
-  a.LMAX = bf.PART + (size_t)d->B * nsplit * PARTW;
   a.enc = enc; a.y = y; a.use_truth = use_truth; a.PRED = bf.PRED; a.emb_mask = emb_mask; a.rnn_mask = rnn_mask;
   a.TOK = bf.TOK; a.X0 = bf.X0; a.G = bf.G; a.C = bf.C; a.HR = bf.HR; a.Q = bf.Q; a.ALPHA = bf.ALPHA; a.CVH = bf.CVH; a.HT = bf.HT;
-  a.PART = bf.PART; a.ctr = bf.ctr;
-  const size_t nctr = ((size_t)C_N * NSH + d->B + 1) * CTRS;
-  a.ab = abort_ctl(bf.ctr + ((size_t)C_N * NSH + d->B) * CTRS, PERSIST_DEC_FWD);
-  ASTK_HIP(hipMemsetAsync(bf.ctr, 0, nctr * sizeof(unsigned), s));
-  const size_t shm = wide_lds_bytes(chunk);
-  static bool attr_done = false;
-  if (!attr_done) {
-    (void)hipFuncSetAttribute((const void*)decoder_wide_fwd, hipFuncAttributeMaxDynamicSharedMemorySize, 158 * 1024);
-    attr_done = true;
-  }
-  hipLaunchKernelGGL(decoder_wide_fwd, dim3(WG_), dim3(256), shm, s, a);
-  ASTK_LAUNCH_CHECK();
-  return 0;
-}
-
-size_t decoder_wide_bwd_floats(const astk_decoder_desc* d) {       // PARTB + PREC + PCAR
-  int ns = 1, ch = 1;
-  return decoder_wide_applicable(d, &ns, &ch) ? (size_t)d->B * ns * WH + 2 * (size_t)WG_ * 512 : 4;
-}
-size_t decoder_wide_bwd_ctr_words(const astk_decoder_desc* d) {
-  return decoder_wide_applicable(d, nullptr, nullptr) ? ((size_t)D_N * NSH + 32 + 2 * NTILE + 1) * CTRS : 4;
+  a.PART = bf.PART; a.LMAX = bf.PART + p.lmax_off; a.ctr = bf.ctr;
+  a.ab = abort_ctl(bf.ctr + p.fwd_abort_line * CTRS, PERSIST_DEC_FWD);
+  return wide_launch<decoder_wide_fwd>(a, p.fwd_ctr_lines, p.lds_bytes, s);
 }
 
 int decoder_wide_bwd_launch(const astk_decoder_desc* d, const float* enc, const float* rnn_mask, const DecWideBwdBuffers& bf, hipStream_t s) {
-  int nsplit = 1, chunk = 1;
-  ASTK_CHECK(decoder_wide_applicable(d, &nsplit, &chunk), "decoder_wide_bwd: not applicable");
+  const WidePlan p = wide_plan(d);
+  ASTK_CHECK(p.ok, "decoder_wide_bwd: not applicable");
   WideBwdArgs a;
   memset(&a, 0, sizeof(a));
-  a.B = d->B; a.S = d->L - 1; a.T = d->T; a.Tp = (d->T + 3) / 4 * 4; a.nsplit = nsplit; a.chunk = chunk;
+  a.B = d->B; a.S = d->L - 1; a.T = d->T; a.Tp = p.Tp; a.nsplit = p.nsplit; a.chunk = p.chunk;
   a.WcT = bf.WcT; a.WaT = bf.WaT; a.WlT = bf.WlT; a.WuT = bf.WuT; a.enc = enc;
   a.ALPHA = bf.ALPHA; a.CVH = bf.CVH; a.HT = bf.HT; a.C = bf.C; a.rnn_mask = rnn_mask;
   a.G = bf.G; a.DPRE = bf.DPRE; a.DCVH = bf.DCVH; a.DS = bf.DS; a.DQ = bf.DQ; a.DHTOP = bf.DHTOP; a.DC0 = bf.DC0;
-  a.PARTB = bf.scratch;
-  a.PREC = bf.scratch + (size_t)d->B * nsplit * WH;
-  a.PCAR = a.PREC + (size_t)WG_ * 512;
-  a.ctr = bf.ctr;
-  const size_t nctr = ((size_t)D_N * NSH + 32 + 2 * NTILE + 1) * CTRS;
-  a.ab = abort_ctl(bf.ctr + nctr - CTRS, PERSIST_DEC_BWD);
-  ASTK_HIP(hipMemsetAsync(bf.ctr, 0, nctr * sizeof(unsigned), s));
-  const size_t shm = wide_lds_bytes(chunk);
-  static bool attr_done = false;
-  if (!attr_done) {
-    (void)hipFuncSetAttribute((const void*)decoder_wide_bwd, hipFuncAttributeMaxDynamicSharedMemorySize, 158 * 1024);
-    attr_done = true;
-  }
-  hipLaunchKernelGGL(decoder_wide_bwd, dim3(WG_), dim3(256), shm, s, a);
-  ASTK_LAUNCH_CHECK();
-  return 0;
+  a.PARTB = bf.scratch; a.PREC = bf.scratch + p.prec_off; a.PCAR = bf.scratch + p.pcar_off; a.ctr = bf.ctr;
+  a.ab = abort_ctl(bf.ctr + p.bwd_abort_line * CTRS, PERSIST_DEC_BWD);
+  return wide_launch<decoder_wide_bwd>(a, p.bwd_ctr_lines, p.lds_bytes, s);
 }
 
 }  // namespace astk
